@@ -136,6 +136,7 @@ struct PbState {
 	int down_rounds = 1, ids_per_round = 0; // k_pb_down: pieces of a workgroup's block range per panel (one LDS image each)
 	void* down_image = nullptr; // rounds > 1: the images, prepared once (k_pb_down_image)
 	size_t down_lds = 0;
+	size_t down_lds_pf = 0; // k_pb_down's PF form: the image plus the task sums
 	int32_t* order = nullptr; // blocks of every workgroup's range by decreasing list length
 	int* pace = nullptr;
 	double* z = nullptr; // alpha C y of the product in flight (n_blk * pitch doubles)

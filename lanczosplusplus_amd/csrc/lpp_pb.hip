@@ -449,6 +449,7 @@ lpp_status pb_build(lpp_engine* e, int64_t n_up, int64_t n_blk, const int64_t* t
 		B.ids_per_round = per_round(r);
 	}
 	B.down_lds = pb_down_lds_bytes(B.ids_per_round, B.rowcap);
+	B.down_lds_pf = B.down_lds + pb_down_task_sum_bytes(B.ids_per_round); // the counter-scheduled form where that fits the same bound (pb_down_pf_fits)
 	if (n_blk >= ((int64_t)1 << 24)) return fail(LPP_ERR_INVALID, "pb_build: more than 2^24 - 1 blocks");
 	B.parts = parts;
 	B.wide = wide;
@@ -744,10 +745,14 @@ static int launch_up_big(lpp_engine* e, const double* y, double* u, const uint8_
 // with pace == null: the barrier per step keeps a workgroup together, the counter keeps its waves on neighbouring tasks): faster where a panel of all blocks
 // fits an XCD's L2 with room to spare -- complex couplings at 11440 blocks 2.27 -> 2.08 ms, the 3x6 lattice's (6,6) sector (18564 blocks) 2.72 -> 2.56 ms -- and
 // slower where it does not (38760 blocks, 4.96 MB: 28.4 -> 35.8 ms; with pacing on top of the counter 28.5): up to 3 MB per panel.  LPP_PB_DOWN_TASKS=0 / 1
+// The counter-scheduled form keeps its task sums in LDS behind the image (k_pb_down, PF): it runs only where both fit 150 KB; the fixed-share form,
+// whose sums follow a fixed order by construction, takes the rest
+static bool pb_down_pf_fits(const PbState& B) { return B.down_lds_pf <= (size_t)150 * 1024; }
+
 static bool pb_down_tasks(const PbState& B, int64_t n_blk)
 {
+	if (!pb_down_pf_fits(B)) return false;
 	if (const char* s = getenv("LPP_PB_DOWN_TASKS")) return atoi(s) != 0;
-	(void)B;
 	return (size_t)n_blk * 128 <= (size_t)3 << 20;
 }
 
@@ -758,8 +763,9 @@ static void pb_launch_down_plain(const PbState& B, PbDownArgs& d, hipStream_t st
 	if (d.pace) (void)hipMemsetAsync(d.pace, 0, sizeof(int) * 8 * (size_t)d.npanels, st);
 #define LPP_PB_DOWN_PLAIN(WIDE_, CPLX_, PF_)                                                                           \
 	do {                                                                                                              \
-		(void)hipFuncSetAttribute((const void*)k_pb_down<1024, false, WIDE_, CPLX_, PF_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)B.down_lds); \
-		k_pb_down<1024, false, WIDE_, CPLX_, PF_><<<B.down_grid, 1024, B.down_lds, st>>>(d);                            \
+		const size_t lds_ = PF_ ? B.down_lds_pf : B.down_lds;                                                            \
+		(void)hipFuncSetAttribute((const void*)k_pb_down<1024, false, WIDE_, CPLX_, PF_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_); \
+		k_pb_down<1024, false, WIDE_, CPLX_, PF_><<<B.down_grid, 1024, lds_, st>>>(d);                                  \
 	} while (0)
 	if (B.cplx && B.wide) {
 		if (tasks) LPP_PB_DOWN_PLAIN(true, true, true);
@@ -1064,7 +1070,8 @@ int pb_launch_chain(lpp_engine* e, void* w, void* y, double* partial, const EpiS
 	d.cdict = (const double2*)B.cdict;
 	// the last wave touches the u lines ahead of the tasks and the tasks are handed out by a counter (k_pb_down<..., PF>): config 2 3.03 -> 2.88 ms
 	// per step; LPP_PB_DOWN_PF=0: every wave its fixed share of the tasks, no touching
-	static const bool pf = !(getenv("LPP_PB_DOWN_PF") && atoi(getenv("LPP_PB_DOWN_PF")) == 0);
+	static const bool pf_env = !(getenv("LPP_PB_DOWN_PF") && atoi(getenv("LPP_PB_DOWN_PF")) == 0);
+	const bool pf = pf_env && pb_down_pf_fits(B);
 	d.pf_lead = 2;
 	// ... and with the tasks handed out by a counter and a barrier per panel the workgroups of a group stay together by themselves: the bounded pacing
 	// (one atomic, one poll and one more barrier per panel, a memset per launch) only costs here -- config 2 1.51 -> 1.41 ms, the 4x4 lattice's (7,7) sector
@@ -1074,8 +1081,9 @@ int pb_launch_chain(lpp_engine* e, void* w, void* y, double* partial, const EpiS
 	if (d.pace) (void)hipMemsetAsync(d.pace, 0, sizeof(int) * 8 * (size_t)d.npanels, st);
 #define LPP_PB_DOWN_RMW(CPLX_, PF_)                                                                                    \
 	do {                                                                                                              \
-		(void)hipFuncSetAttribute((const void*)k_pb_down<1024, true, false, CPLX_, PF_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)B.down_lds); \
-		k_pb_down<1024, true, false, CPLX_, PF_><<<B.down_grid, 1024, B.down_lds, st>>>(d);                             \
+		const size_t lds_ = PF_ ? B.down_lds_pf : B.down_lds;                                                            \
+		(void)hipFuncSetAttribute((const void*)k_pb_down<1024, true, false, CPLX_, PF_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_); \
+		k_pb_down<1024, true, false, CPLX_, PF_><<<B.down_grid, 1024, lds_, st>>>(d);                                   \
 	} while (0)
 	if (B.cplx && pf) LPP_PB_DOWN_RMW(true, true);
 	else if (B.cplx) LPP_PB_DOWN_RMW(true, false);

@@ -404,6 +404,30 @@ template <bool DOT, int GT, bool CHAIN = false, int PRE0 = kPbPre> __global__ __
 // (0.8 of its 0.875 ms at config 2: scripts/experiments/r03_down_parts_ab.sh).
 __host__ __device__ inline int pb_down_stride(int rowcap) { return ((rowcap >> 2) & 1) ? rowcap : rowcap + 4; }
 __host__ __device__ inline size_t pb_down_lds_bytes(int ids_per_wg, int rowcap) { return (((size_t)ids_per_wg * 8 + 15) & ~(size_t)15) + (size_t)ids_per_wg * (size_t)pb_down_stride(rowcap) * 4 + 16; }
+// sum over the wave in a fixed order without LDS traffic (wave_sum's shuffles are LDS instructions, and the coupling kernel's
+// instruction skeleton waits on the LDS pipeline): DPP shifts inside each row of 16 lanes, then the four row sums in lane order
+template <int CTRL> __device__ __forceinline__ double dpp_shr(double v)
+{
+	const long long b = __double_as_longlong(v);
+	const int lo = __builtin_amdgcn_update_dpp(0, (int)b, CTRL, 0xf, 0xf, true);
+	const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xf, 0xf, true);
+	return __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
+}
+__device__ __forceinline__ double wave_sum_rows(double v)
+{
+	v += dpp_shr<0x111>(v); // row_shr:1
+	v += dpp_shr<0x112>(v); // row_shr:2
+	v += dpp_shr<0x114>(v); // row_shr:4
+	v += dpp_shr<0x118>(v); // row_shr:8
+	auto lane_val = [&](int l) __attribute__((always_inline)) {
+		const long long b = __double_as_longlong(v);
+		const int lo = __builtin_amdgcn_readlane((int)b, l), hi = __builtin_amdgcn_readlane((int)(b >> 32), l);
+		return __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
+	};
+	return ((lane_val(15) + lane_val(31)) + lane_val(47)) + lane_val(63);
+}
+// the PF form's task sums behind the image in k_pb_down's dynamic LDS: two buffers of (Re<y|z>, |z - s y|^2) per task of 8 blocks
+__host__ __device__ inline size_t pb_down_task_sum_bytes(int ids_per_wg) { return (size_t)((ids_per_wg + 7) / 8) * 4 * sizeof(double); }
 
 // The image of `nown` blocks order[b0 ...]: row[il] = block * rowmul, len[il] = its list length, place[il * stride + k] = source block | code << 24.
 // Places beyond a list carry code 0 (+0.0) and the address the task's first block (the longest list) reads at this place, so the filling
@@ -497,6 +521,26 @@ template <int THREADS, bool RMW = false, bool WIDE = false, bool CPLX = false, b
 	const int64_t b0w = (int64_t)slot * a.ids_per_wg; // this workgroup's range of `order`
 	const int nown_w = (int)max((int64_t)0, min((int64_t)a.ids_per_wg, a.n_blk - b0w));
 	const int rounds = a.rounds;
+	// PF: tasks go to whichever wave asks first, so a wave's running sums would depend on the schedule.  Each task's sums go to its own
+	// LDS slot instead, and wave 0 adds a step's slots in task order once the barrier behind the step has passed; the other waves go on
+	// with the next step in the other buffer (every step ends in a barrier, so buffer q & 1 is free again for step q + 2).
+	const int tcap = (a.ids_per_round + BPT - 1) / BPT;
+	double* const tsum_s = (double*)(lds_raw + pb_down_lds_bytes(a.ids_per_round, a.rowcap)); // [2][2][tcap]
+	auto fold = [&](int q, int ng) __attribute__((always_inline)) {
+		if (wave != 0) return;
+		const double* const t = tsum_s + (size_t)(q & 1) * 2 * tcap;
+		double sd = 0.0, sn = 0.0;
+		for (int i = lane; i < ng; i += 64) {
+			sd += t[i];
+			if (RMW) sn += t[tcap + i];
+		}
+		sd = wave_sum(sd);
+		if (RMW) sn = wave_sum(sn);
+		if (lane == 0) {
+			dot += sd;
+			nrm += sn;
+		}
+	};
 	int64_t b0 = b0w;
 	int nown = rounds == 1 ? nown_w : 0;
 	auto build_image = [&](int r) __attribute__((always_inline)) {
@@ -559,6 +603,7 @@ template <int THREADS, bool RMW = false, bool WIDE = false, bool CPLX = false, b
 		for (int r = 0; r < rounds; r++) {
 		if (rounds > 1) { // (wave-uniform) this piece of the workgroup's range: its image replaces the previous piece's
 			__syncthreads();
+			if (PF && r > 0) fold(pk * rounds + r - 1, (nown + BPT - 1) / BPT);
 			build_image(r);
 			__syncthreads();
 		}
@@ -628,16 +673,29 @@ template <int THREADS, bool RMW = false, bool WIDE = false, bool CPLX = false, b
 				}
 			}
 			const double2 yown = *(const double2*)(ysrc + at(row_s[il])); // the panel is in L2
+			double td = 0.0, tn = 0.0;
 			if (valid) {
 				acc.x = fma(alpha, acc.x, fma(beta, xo.x, uo.x));
 				acc.y = fma(alpha, acc.y, fma(beta, xo.y, uo.y));
 				__builtin_nontemporal_store(acc.x, &zp->x);
 				__builtin_nontemporal_store(acc.y, &zp->y);
-				dot += yown.x * acc.x + yown.y * acc.y;
+				td = yown.x * acc.x + yown.y * acc.y;
 				if (RMW) {
 					const double dx = acc.x - sh * yown.x, dy = acc.y - sh * yown.y;
-					nrm += dx * dx + dy * dy;
+					tn = dx * dx + dy * dy;
 				}
+			}
+			if (PF) {
+				double* const t = tsum_s + (size_t)(q & 1) * 2 * tcap;
+				td = wave_sum_rows(td);
+				if (RMW) tn = wave_sum_rows(tn);
+				if (lane == 0) {
+					t[g] = td;
+					if (RMW) t[tcap + g] = tn;
+				}
+			} else {
+				dot += td;
+				nrm += tn;
 			}
 		}
 		}
@@ -650,6 +708,7 @@ template <int THREADS, bool RMW = false, bool WIDE = false, bool CPLX = false, b
 		if (a.pace || PF) {
 			__syncthreads();
 			if (a.pace && threadIdx.x == 0) __hip_atomic_fetch_add(a.pace + (int64_t)grp * a.npanels + p, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+			if (PF) fold(pk * rounds + rounds - 1, (nown + BPT - 1) / BPT);
 		}
 	}
 	if (a.partial) {

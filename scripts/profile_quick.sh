@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 O=$R/gpurun_out/profile_$TAG
 mkdir -p $O
 cd /tmp
-CMDP="python3 $R/bench.py --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline --no-generic-csr --no-e0-check --no-reortho-leg $BENCH_ARGS"
+CMDP="python3 $R/bench.py --steps ${STEPS:-10} --warmup 2 $BENCH_ARGS"
 $CMDP > $O/bench.json 2> $O/bench.err
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- $CMDP > $O/trace.log 2>&1
 timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/write -- $CMDP > $O/write.log 2>&1

@@ -7,9 +7,10 @@ export TMPDIR=/tmp
 O=$R/gpurun_out/profile_$TAG
 mkdir -p $O
 cd /tmp
-CMD="python3 $R/bench.py --steps 40 --warmup 5 $BENCH_ARGS"
-$CMD > $O/bench.json 2> $O/bench.err
-CMDP="python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-generic-csr --no-e0-check --no-reortho-leg $BENCH_ARGS"
+CMD="python3 $R/bench.py --full --steps 40 --warmup 5 $BENCH_ARGS"
+$CMD > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+[ -n "$LINE_ONLY" ] && exit 0  # the bench line alone (scripts/profile_set.sh <tag> lines)
+CMDP="python3 $R/bench.py --steps 10 --warmup 2 $BENCH_ARGS"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- $CMDP > $O/trace.log 2>&1
 timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch -- $CMDP > $O/fetch.log 2>&1
 timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/write -- $CMDP > $O/write.log 2>&1

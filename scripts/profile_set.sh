@@ -25,14 +25,13 @@ for c in ${CONFIGS:-c2_stored c2otf c2otf_kron c3 c4 c1 c5_76}; do
   if [ $MODE = counters ]; then
     SQ_PASS=$([ $c = c2_stored ] && echo 1) BENCH_ARGS="$(cfg $c)" bash scripts/profile_round.sh ${T}_$c > gpurun_out/ps_$c.out 2>&1 || { tail -5 gpurun_out/ps_$c.out; exit 1; }
   else
-    mkdir -p gpurun_out/profile_${T}_$c
-    (cd /tmp && timeout -k 10 500 python3 $R/bench.py --steps 40 --warmup 5 $(cfg $c) > $R/gpurun_out/profile_${T}_$c/bench.json 2> $R/gpurun_out/profile_${T}_$c/bench.err) || { tail -5 gpurun_out/profile_${T}_$c/bench.err; exit 1; }
+    LINE_ONLY=1 BENCH_ARGS="$(cfg $c)" timeout -k 10 500 bash scripts/profile_round.sh ${T}_$c || exit 1
   fi
   echo "$c done: $(python3 -c "import json;d=json.loads(open('gpurun_out/profile_${T}_$c/bench.json').read().strip().splitlines()[-1]);print(round(d['value'],1),'it/s; traffic',d['roofline'].get('traffic'),d['roofline'].get('traffic_note',''))")"
 done
 if [ $MODE = counters ] && [ -z "$NO_REORTHO" ]; then
   export TMPDIR=/tmp; O=$R/gpurun_out/profile_${T}_reortho; mkdir -p $O; cd /tmp
-  CMDR="python3 $R/bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-generic-csr --no-e0-check"
+  CMDR="python3 $R/bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-generic-csr --no-e0-check"
   timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- $CMDR > $O/bench.json 2> $O/trace.log
   python3 - <<PY
 import csv,glob

@@ -1,8 +1,9 @@
 """Complex hoppings beyond one LDS window at full size (4x4 lattice, Peierls phases, 8 up 7 down: 1.47e8 complex states): the pieces form of the
 product-basis layout against the general layout -- resident bytes, time per step, exact free-fermion energy.  Run on the GPU box."""
 import os, sys, time, numpy as np
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
-sys.path.insert(0, os.path.join(os.environ.get("GRAFT_REPO_ROOT", "/root/repo"), "tests"))
+TESTS = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(TESTS))
+sys.path.insert(0, TESTS)
 from lanczosplusplus_amd import LanczosEngine
 from test_gpu_fullsize import square, _exact
 L = 16

@@ -1,5 +1,6 @@
 import sys, time, os
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+TESTS = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(TESTS)); sys.path.insert(0, TESTS)
 import numpy as np
 from helpers import square
 from lanczosplusplus_amd import LanczosEngine

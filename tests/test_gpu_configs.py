@@ -166,3 +166,56 @@ def test_bench_line_of_the_other_model_families(workload):
     assert line["roofline"]["achieved"] > 0 and 0 < line["roofline"]["frac"] <= 1.0
     if workload == "hubbard_4x4_6up6down_complex_U4":
         assert line["config"]["layout"]["kernel"] == "product" and line["config"]["layout"]["chained_step"]
+
+
+def test_bench_plain_line_full_line_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` line times the steps and nothing else; `--full` adds the checks against the CPU-oracle fixture (C4 here,
+    the cheapest workload that has one).  `--dump-outputs` writes the coefficients of the timed run: as many as warm-up plus timed
+    steps, bitwise the same in both runs (same seeded start vector), the line's E0 their lowest Ritz value, the first ones the fixture's."""
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    name, steps, warmup = "tj_4x5_9up9down_complex", 6, 2
+    lines, dumps = {}, {}
+    for kind, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--no-generic-csr", "--no-reortho-leg"])):
+        d = tmp_path / kind
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", name, "--steps", str(steps), "--warmup", str(warmup),
+                              "--dump-outputs", str(d)] + extra, capture_output=True, text=True, timeout=400)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines[kind] = json.loads(out.stdout.strip().splitlines()[-1])
+        dumps[kind] = {k: np.load(d / (k + ".npy")) for k in ("lanczos_alpha", "lanczos_beta", "ritz_lowest")}
+    plain, full = lines["plain"], lines["full"]
+    for line in (plain, full):
+        assert line["steps"] == steps and line["warmup"] == warmup and line["value"] > 0 and line["unit"] == "iterations/s"
+        assert abs(line["ms_per_step"] - 1e3 / line["value"]) <= 1e-9 * line["ms_per_step"]
+    assert not any(k in plain for k in ("e0_check", "generic_csr", "reortho", "cpu_baseline"))
+    assert plain["config"]["coefficients_vs_cpu_oracle"] is None
+    assert full["config"]["coefficients_vs_cpu_oracle"]["max_rel_diff"] < 1e-6 and full["e0_check"]["rel_diff"] < E_TOL
+    g = json.load(open(os.path.join(GOLD, "c4_tj_4x5_complex.json")))
+    for kind in ("plain", "full"):
+        a, b, e0 = dumps[kind]["lanczos_alpha"], dumps[kind]["lanczos_beta"], dumps[kind]["ritz_lowest"]
+        assert a.dtype == b.dtype == e0.dtype == np.float64 and a.shape == b.shape == (steps + warmup,) and e0.shape == (1,)
+        assert e0[0] == lines[kind]["e0_after_steps"]
+        assert rel(a, g["a"][:steps + warmup]) < 1e-8 and rel(b, g["b"][:steps + warmup]) < 1e-8
+    for k in ("lanczos_alpha", "lanczos_beta", "ritz_lowest"):  # same arguments, same inputs: the same numbers, bit for bit
+        assert np.array_equal(_bits(dumps["plain"][k]), _bits(dumps["full"][k])), k
+
+
+def test_config2_chained_step_is_bitwise_reproducible():
+    """BASELINE config 2 on the default path (product-basis layout, chained step, coupling tasks handed out by a counter): two runs of
+    200 steps from the same start vector give the same coefficients bit for bit.  The schedule of the tasks must not reach the sums."""
+    L = 16
+    hop = square(4, 4, -1.0, pbc=True)
+    runs = []
+    for _ in range(2):
+        with LanczosEngine(max_steps=210, eps=0.0, save_vectors=0) as e:
+            e.assemble_hubbard(L, 8, 8, hop, np.full(L, 4.0))
+            lay = e.layout()
+            assert lay["kernel"] == 4 and lay["chained_step"] == 1, lay
+            e.begin(None)
+            e.step(200)
+            runs.append(e.coeffs())
+    (a0, b0), (a1, b1) = runs
+    assert len(a0) == 200
+    assert np.array_equal(_bits(a0), _bits(a1)) and np.array_equal(_bits(b0), _bits(b1))

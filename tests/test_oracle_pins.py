@@ -65,13 +65,20 @@ def test_golden_heisenberg_sector_enumeration_and_diagonal():
 
 
 def test_golden_reference_binary_if_present():
-    """In the build container the reference program itself is re-run (oracle/_ref); elsewhere skipped."""
+    """The reference program's line for the periodic L = 12 chain.  Where oracle/_ref is built the program is re-run and its line must
+    equal the recorded one in tests/golden/heis_inf_temp.json; elsewhere only the recorded line is checked (the name keeps the first
+    case), and the oracle part repeats test_golden_heisenberg_sector_enumeration_and_diagonal for this one case."""
+    gold = json.load(open(os.path.join(HERE, "golden", "heis_inf_temp.json")))
+    rec = next(c for c in gold["cases"] if (c["L"], c["twiceS"], c["periodic"]) == (12, 1, 1))
+    recorded = ["%d" % rec["sum"], "%d" % rec["count"]]
     exe = os.path.join(HERE, "..", "oracle", "_ref", "heis_inf_temp")
-    if not os.path.exists(exe):
-        pytest.skip("oracle/_ref not built here")
-    import subprocess
-    out = subprocess.check_output([exe, "12", "1", "1"], text=True).splitlines()[-1].split()
-    assert out[1:] == ["-252", "924"]
+    if os.path.exists(exe):
+        import subprocess
+        out = subprocess.check_output([exe, "12", "1", "1"], text=True).splitlines()[-1].split()
+        assert out[1:] == recorded
+    assert recorded == ["-252", "924"]
+    A = oracle.heis_csr(12, 1, 6, np.zeros((12, 12)), chain(12, 1.0, True))
+    assert A.nrows == 924 and A.values.sum() == -252.0
 
 
 def test_heisenberg_literal_index_equals_fast_index():
