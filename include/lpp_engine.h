@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LPP_ABI_VERSION 5 /* 5: LPP_SPMV_HOLE_MAJOR (lpp_layout.kernel of the t-J model), lpp_engine_set_model_tj / _heisenberg; 4: lpp_layout.segments, lpp_pb_seg_plan_stats; 2: lpp_layout.stream_bytes, lpp_pb_pack_template(bank_ways), set_solver / stream / _ext / _spin entry points; 3: lpp_layout.pieces / coupling_parts / diagonal_plain / chained_step / split_panel, lpp_stats.reortho_* */
+#define LPP_ABI_VERSION 6 /* 6: observables -- LPP_OP_*, lpp_obs_*, lpp_engine_apply_operator, _keep_states, _state_device, *_device start vectors, _two_point, _spectral_decomposition, lpp_continued_fraction; 5: LPP_SPMV_HOLE_MAJOR (lpp_layout.kernel of the t-J model), lpp_engine_set_model_tj / _heisenberg; 4: lpp_layout.segments, lpp_pb_seg_plan_stats; 2: lpp_layout.stream_bytes, lpp_pb_pack_template(bank_ways), set_solver / stream / _ext / _spin entry points; 3: lpp_layout.pieces / coupling_parts / diagonal_plain / chained_step / split_panel, lpp_stats.reortho_* */
 
 typedef int32_t lpp_status;
 enum {
@@ -360,6 +360,81 @@ lpp_status lpp_pb_seg_plan_stats(int64_t rows, const int64_t* rowptr, const int3
  * spin patterns, low positions of a segment, work items, bonds, moves, bonds among the low positions, most bonds / moves of one configuration. */
 lpp_status lpp_tj_plan_stats(int32_t nsites, int32_t nup, int32_t ndown, const double* hop_re, const double* hop_im, const double* jpm, int64_t nrows,
                              const int64_t* rowptr, const int32_t* colind, const void* values, int32_t is_complex, int64_t* out);
+
+/* ---- observables of the Hubbard product basis (ABI 6; one GPU; csrc/lpp_obs.hip) ----
+ * What the reference's users run after the ground state in the same `lanczos` call: -c <op> (Engine::twoPoint, Engine.h:266-338) and
+ * -g <op> (Engine::spectralFunction :134-206).  Models: HubbardOneBand, HubbardOneBandExtended, SuperHubbardExtended, KaneMeleHubbard
+ * (all on BasisHubbardLanczos).  A partitioned (multi-rank) engine or a hole-major t-J engine handed to any of these entry points returns
+ * LPP_ERR_STATE with a message. */
+
+/* operators, numbered as LabeledOperator::Label (LabeledOperator.h:10-17) */
+enum { LPP_OP_C = 1, LPP_OP_SZ = 2, LPP_OP_CDAGGER = 3, LPP_OP_N = 4, LPP_OP_SPLUS = 5, LPP_OP_SMINUS = 6 };
+enum { LPP_SPIN_UP = 0, LPP_SPIN_DOWN = 1 }; /* ProgramGlobals.h:105 */
+
+/* HubbardOneOrbital::hasNewParts (HubbardOneOrbital.h:87-109, :212-253), host only: *has = 1 and the new (nup, ndown), or *has = 0 where the
+ * reference returns false (a count below 0 or above nsites, the (0,0) sector for c / cdagger, sz).  LPP_OP_N: the reference throws -> LPP_ERR_INVALID. */
+lpp_status lpp_obs_new_parts(int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t* has, int32_t* nup_new, int32_t* ndown_new);
+
+/* The plan of one operator application (host only; exposed for the CPU test-suite): the sector the operator leads to (n and sz stay, LabeledOperator.h:83-90)
+ * and the two per-species tables the kernel reads, table[destination species rank] = +-(source species rank + 1) or 0 = none, ranks as
+ * BasisOneSpin::perfectIndex (BasisOneSpin.h:73-81).  The entry's sign is the species' share of doSignGf (BasisHubbardLanczos.h:106-137; for SPIN_DOWN
+ * the parity of the down bits below the site -- at site 0 the parity of the up electrons, folded into the down table) and doSignSpSm (:151-160).
+ * For LPP_OP_SZ the tables are the two occupancy tables of n and the value is (up occupied) - (down occupied) (getBraIndexSz :210-223: +1 / -1 / none, not +-1/2).
+ * table_up[n_up_dst], table_down[n_down_dst]; NULL tables: sizes only.  *has = 0: hasNewParts refused, nothing else is written. */
+lpp_status lpp_obs_plan(int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t* has, int32_t* nup_new, int32_t* ndown_new,
+                        int64_t* n_up_dst, int64_t* n_down_dst, int32_t* table_up, int32_t* table_down);
+
+/* Engine::accModifiedState_ (Engine.h:416-458) on device vectors of the engine's GPU and dtype, both in the basis order rank(up) + rank(down) * N_up
+ * (BasisHubbardLanczos.h:59-63):  z[bra] += factor * sign * value * src[ket]  (accumulate = 0: z = ..., destinations the reference does not touch
+ * are written as 0).  d_src: C(nsites,nup)*C(nsites,ndown) elements, d_dst: the new sector's, 16-byte aligned.  One launch on the engine's stream,
+ * no host sync; destination driven, no atomics (csrc/lpp_obs_kernels.h).  The engine needs no matrix.  *has = 0: no such sector, nothing was done. */
+lpp_status lpp_engine_apply_operator(lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, double factor_re,
+                                     double factor_im, const void* d_src, void* d_dst, int32_t accumulate, int32_t* has);
+/* the same on host vectors (copied in and out; dst is read only when accumulate != 0) */
+lpp_status lpp_engine_apply_operator_host(lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, double factor_re,
+                                          double factor_im, const void* src, void* dst, int32_t accumulate, int32_t* has);
+/* Time `iters` accumulating applications on zeroed resident vectors with HIP events; model_bytes = sizeof(value) * (2 N_dst + source entries read). */
+lpp_status lpp_engine_bench_operator(lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t warmup, int32_t iters,
+                                     double* ms_per_launch, double* model_bytes);
+
+/* Keep the lowest k Ritz vectors of the NEXT lpp_engine_lanczos / _lanczos_device on the device (Engine::vectors_, Engine.h:601-657), in the basis
+ * order -- unpitched, un-permuted whatever the layout stores -- on both Ritz paths (saved Krylov basis, two-pass replay).  The host buffer of
+ * lpp_engine_lanczos may then be NULL.  k = 0 (default): nothing is kept.  The states live until the engine is destroyed or the next lpp_engine_lanczos / _lanczos_device
+ * starts: from then on pointers returned by lpp_engine_state_device are invalid (the buffer may be reallocated), and a solve that fails leaves no state. */
+lpp_status lpp_engine_keep_states(lpp_engine* e, int32_t k);
+/* device pointer (16-byte aligned) and length in elements of resident state k */
+lpp_status lpp_engine_state_device(lpp_engine* e, int32_t k, void** d_ptr, int64_t* len);
+lpp_status lpp_engine_state_to_host(lpp_engine* e, int32_t k, void* host);
+
+/* lpp_engine_lanczos / _lanczos_begin / _decomposition with a DEVICE start vector: d_init holds rows() elements in the basis order on the engine's
+ * GPU (not NULL) and is copied into the internal form on the device; everything else as the host-vector entry points. */
+lpp_status lpp_engine_lanczos_device(lpp_engine* e, const void* d_init, int32_t nstates, double* eigs, void* ritz_vectors, lpp_stats* stats);
+lpp_status lpp_engine_lanczos_begin_device(lpp_engine* e, const void* d_init);
+lpp_status lpp_engine_decomposition_device(lpp_engine* e, const void* d_init, int32_t* nsteps, double* a, double* b, lpp_stats* stats);
+
+/* Engine::twoPoint (Engine.h:266-338) for resident states bra_state / ket_state of sector (nup, ndown):
+ *   result[i * nsites + j] = (A_j^{spin2} bra) . (A_i^{spin1} ket),  the left factor conjugated for c128,
+ * the modified vectors built as Engine::accModifiedState does (:535-599: n directly, sz as n_up/2 - n_down/2, the others as given).  An operator
+ * that leads to no sector leaves the matrix at the reference's -100 fill (:303-305).  c / cdagger / splus / sminus with spin1 != spin2 ->
+ * LPP_ERR_INVALID (the reference throws, :276-282).  result: nsites*nsites values of the engine dtype; trace (one value, may be NULL): the sum
+ * of the diagonal the reference prints as MatrixDiagonal (:337).  The bra vectors are built in panels sized to the free memory and contracted
+ * with the panel-dot kernel of the blocked Gram-Schmidt. */
+lpp_status lpp_engine_two_point(lpp_engine* e, int32_t op, int32_t spin1, int32_t spin2, int32_t nsites, int32_t nup, int32_t ndown, int32_t bra_state,
+                                int32_t ket_state, void* result, void* trace);
+
+/* One type of Engine::spectralFunction (Engine.h:160-205): the modified state  A_i gs + isign A_j gs  (getModifiedState :494-533 -- for i == j the
+ * state is accumulated twice, as the reference does for this model) is built on the device from resident state `state` of e, *weight = <modif|modif>
+ * (calcSpectral :479), and `sector` -- an engine on the same GPU holding the Hamiltonian of the operator's sector (lpp_obs_new_parts) -- runs
+ * LanczosSolver::decomposition from it (:478) with its own solver parameters (ParametersForSolver(io,"Spectral")).  a, b, nsteps, stats as
+ * lpp_engine_decomposition.  The caller picks the operator of the type (odd: the operator, even: its transpose-conjugate, :163) and isign
+ * (-1 for types above 1, :521), keeps the sector engines alive across calls and applies s / s2 of :481-489. */
+lpp_status lpp_engine_spectral_decomposition(lpp_engine* e, int32_t state, lpp_engine* sector, int32_t op, int32_t isite, int32_t jsite, int32_t spin, double isign,
+                                             int32_t nsites, int32_t nup, int32_t ndown, double* weight, int32_t* nsteps, double* a, double* b, lpp_stats* stats);
+
+/* Host helper: a record (a[n], b[n], Eg, w = weight*s2, sigma = -s: the argument list of cf.set, Engine.h:489) evaluated at complex z,
+ *   G(z) = w / (z + sigma (a_0 - Eg) - b_0^2 / (z + sigma (a_1 - Eg) - b_1^2 / ...)),   b_k = the coefficient lpp_engine_decomposition returns at index k.
+ * This is this project's stated convention: PsimagLite's ContinuedFraction was not available to compare with.  out[2] = (re, im). */
+lpp_status lpp_continued_fraction(int32_t n, const double* a, const double* b, double eg, double weight, double sigma, double z_re, double z_im, double* out);
 
 #ifdef __cplusplus
 }

@@ -10,10 +10,12 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # LPP_ENGINE_LIB: another build of the same library (scripts/experiments build their variants into a scratch directory, never over this one)
 LIB_PATH = os.environ.get("LPP_ENGINE_LIB") or os.path.join(_HERE, "csrc", "liblpp_engine.so")
 
-LPP_ABI_VERSION = 5
+LPP_ABI_VERSION = 6
 LPP_OK, LPP_ERR_INVALID, LPP_ERR_HIP, LPP_ERR_NOMEM, LPP_ERR_NOCONV, LPP_ERR_STATE, LPP_ERR_COMM = range(7)
 LPP_F64, LPP_C128 = 0, 1
 LPP_SPMV_AUTO, LPP_SPMV_ROWGROUP, LPP_SPMV_SLICED, LPP_SPMV_WINDOW = 0, 1, 2, 3
+LPP_OP_C, LPP_OP_SZ, LPP_OP_CDAGGER, LPP_OP_N, LPP_OP_SPLUS, LPP_OP_SMINUS = 1, 2, 3, 4, 5, 6
+LPP_SPIN_UP, LPP_SPIN_DOWN = 0, 1
 
 STATUS_NAMES = {0: "LPP_OK", 1: "LPP_ERR_INVALID", 2: "LPP_ERR_HIP", 3: "LPP_ERR_NOMEM", 4: "LPP_ERR_NOCONV",
                 5: "LPP_ERR_STATE", 6: "LPP_ERR_COMM"}
@@ -113,6 +115,21 @@ SYMBOLS = {
                                          C.POINTER(C.c_int64), _P, _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32]),
     "lpp_pb_seg_plan_stats": (C.c_int32, [C.c_int64, _P, _P, _P, C.c_int32, _P, _P]),
     "lpp_tj_plan_stats": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_int32, _P]),
+    "lpp_obs_new_parts": (C.c_int32, [C.c_int32] * 5 + [C.POINTER(C.c_int32)] * 3),
+    "lpp_obs_plan": (C.c_int32, [C.c_int32] * 6 + [C.POINTER(C.c_int32)] * 3 + [C.POINTER(C.c_int64)] * 2 + [_P, _P]),
+    "lpp_engine_apply_operator": (C.c_int32, [_P] + [C.c_int32] * 6 + [C.c_double, C.c_double, _P, _P, C.c_int32, C.POINTER(C.c_int32)]),
+    "lpp_engine_apply_operator_host": (C.c_int32, [_P] + [C.c_int32] * 6 + [C.c_double, C.c_double, _P, _P, C.c_int32, C.POINTER(C.c_int32)]),
+    "lpp_engine_bench_operator": (C.c_int32, [_P] + [C.c_int32] * 8 + [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "lpp_engine_keep_states": (C.c_int32, [_P, C.c_int32]),
+    "lpp_engine_state_device": (C.c_int32, [_P, C.c_int32, C.POINTER(_P), C.POINTER(C.c_int64)]),
+    "lpp_engine_state_to_host": (C.c_int32, [_P, C.c_int32, _P]),
+    "lpp_engine_lanczos_device": (C.c_int32, [_P, _P, C.c_int32, _P, _P, C.POINTER(Stats)]),
+    "lpp_engine_lanczos_begin_device": (C.c_int32, [_P, _P]),
+    "lpp_engine_decomposition_device": (C.c_int32, [_P, _P, C.POINTER(C.c_int32), _P, _P, C.POINTER(Stats)]),
+    "lpp_engine_two_point": (C.c_int32, [_P] + [C.c_int32] * 8 + [_P, _P]),
+    "lpp_engine_spectral_decomposition": (C.c_int32, [_P, C.c_int32, _P] + [C.c_int32] * 4 + [C.c_double] + [C.c_int32] * 3
+                                          + [C.POINTER(C.c_double), C.POINTER(C.c_int32), _P, _P, C.POINTER(Stats)]),
+    "lpp_continued_fraction": (C.c_int32, [C.c_int32, _P, _P] + [C.c_double] * 5 + [_P]),
 }
 
 _lib = None

@@ -1074,6 +1074,7 @@ lpp_status lpp_engine_destroy(lpp_engine* e)
 	free_csr(e->A_rem);
 	drop_product(e);
 	free_pb(e);
+	free_obs(e);
 	for (double* p : { e->x, e->y, e->V, e->partial, e->scal_own, e->zwork })
 		if (p) (void)hipFree(p);
 	if (e->h_scal) (void)hipHostFree(e->h_scal);

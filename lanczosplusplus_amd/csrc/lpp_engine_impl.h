@@ -306,6 +306,14 @@ struct lpp_engine {
 		coef_dev = base + coef_off;
 		tmp_dev = base + tmp_off;
 	}
+	// observables (lpp_obs.hip): the lowest keep_k Ritz vectors of the next lpp_engine_lanczos stay on the device in the basis order
+	// (unpitched, un-permuted), state k at resident + k * resident_stride doubles; obs: the per-species tables already uploaded
+	int keep_k = 0;
+	double* resident = nullptr;
+	int resident_n = 0, resident_cap = 0; // states valid now (0 until a solve has written them); states the buffer has room for
+	int64_t resident_stride = 0, resident_len = 0; // doubles between states (even), elements per state
+	void* obs = nullptr;
+
 	lpp_status adopt_comm(const lpp_comm* c);
 	void collect_spmv_times();
 };
@@ -379,4 +387,8 @@ lpp_status model_layout_from_hint(lpp_engine* e, const DevCsr& A, bool* done);
 lpp_status vec_from_host(lpp_engine* e, double* dev, const void* host);
 lpp_status vec_to_host(lpp_engine* e, void* host, const double* dev);
 void vec_fill_random(lpp_engine* e, double* dev, uint64_t seed);
+// the device-side halves of the two: `basis` is a device vector of n_local elements in the basis order
+lpp_status vec_from_device(lpp_engine* e, double* dev, const void* basis);
+lpp_status vec_to_device(lpp_engine* e, void* basis, const double* dev);
+void free_obs(lpp_engine* e); // resident states and operator tables (lpp_obs.hip)
 } // namespace lpp

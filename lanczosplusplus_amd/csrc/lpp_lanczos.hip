@@ -439,9 +439,15 @@ lpp_status ensure_krylov(lpp_engine* e, int ncols, bool required, bool* got)
 	return LPP_OK;
 }
 
-lpp_status begin_run(lpp_engine* e, const void* init, bool want_save)
+// dev_init: `init` is a device vector in the basis order on the engine's GPU (the *_device entry points)
+lpp_status begin_run(lpp_engine* e, const void* init, bool want_save, bool dev_init = false)
 {
 	if (!e->has_matrix()) return fail(LPP_ERR_STATE, "no matrix: call lpp_engine_set_csr / lpp_engine_assemble_* first");
+	if (dev_init) {
+		if (!init) return fail(LPP_ERR_INVALID, "device start vector: null pointer");
+		if (multi(e)) return fail(LPP_ERR_STATE, "device start vector: not on a partitioned (multi-rank) engine");
+		if (e->tj.active) return fail(LPP_ERR_STATE, "device start vector: not on a hole-major t-J engine");
+	}
 	HIP_TRY(hipSetDevice(e->cfg.device));
 	if (e->n_global <= 0) return fail(LPP_ERR_INVALID, "empty matrix");
 	const int maxs = effective_max_steps(e);
@@ -459,7 +465,7 @@ lpp_status begin_run(lpp_engine* e, const void* init, bool want_save)
 	// start vector -> x (scratch)
 	HIP_TRY(hipMemsetAsync(e->x, 0, sizeof(double) * (size_t)e->nd_pad, st));
 	if (init) {
-		lpp_status rc0 = vec_from_host(e, e->x, init);
+		lpp_status rc0 = dev_init ? vec_from_device(e, e->x, init) : vec_from_host(e, e->x, init);
 		if (rc0 != LPP_OK) return rc0;
 	} else {
 		vec_fill_random(e, e->x, e->cfg.seed);
@@ -592,6 +598,12 @@ lpp_status lpp_engine_lanczos_begin(lpp_engine* e, const void* init)
 	return begin_run(e, init, false);
 }
 
+lpp_status lpp_engine_lanczos_begin_device(lpp_engine* e, const void* d_init)
+{
+	if (!e) return fail(LPP_ERR_INVALID, "lpp_engine_lanczos_begin_device: null engine");
+	return begin_run(e, d_init, false, true);
+}
+
 lpp_status lpp_engine_lanczos_step(lpp_engine* e, int32_t nsteps)
 {
 	if (!e || nsteps < 0) return fail(LPP_ERR_INVALID, "lpp_engine_lanczos_step: bad argument");
@@ -622,12 +634,32 @@ lpp_status lpp_engine_lanczos_coeffs(lpp_engine* e, int32_t* steps, double* a, d
 	return LPP_OK;
 }
 
-lpp_status lpp_engine_lanczos(lpp_engine* e, const void* init, int32_t nstates, double* eigs, void* ritz_vectors, lpp_stats* stats)
+static lpp_status lanczos_impl(lpp_engine* e, const void* init, bool dev_init, int32_t nstates, double* eigs, void* ritz_vectors, lpp_stats* stats)
 {
 	if (!e || nstates < 1 || !eigs) return fail(LPP_ERR_INVALID, "lpp_engine_lanczos: bad argument");
 	const auto t0 = std::chrono::steady_clock::now();
-	lpp_status st = begin_run(e, init, ritz_vectors != nullptr);
+	// lpp_engine_keep_states: the lowest nkeep Ritz vectors are formed even without a host buffer and stay on the device
+	const int nkeep = std::min<int>(e->keep_k, nstates);
+	if (nkeep > 0 && (multi(e) || e->tj.active)) return fail(LPP_ERR_STATE, "lpp_engine_keep_states: not on a partitioned or hole-major t-J engine");
+	const bool want_vectors = ritz_vectors != nullptr || nkeep > 0;
+	lpp_status st = begin_run(e, init, want_vectors, dev_init);
 	if (st != LPP_OK) return st;
+	// States kept by an earlier solve are gone from here on (their buffer is reused or reallocated, so pointers handed out by
+	// lpp_engine_state_device are invalid); resident_n names the new ones only once they have been written, so a solve that fails leaves none.
+	e->resident_n = 0;
+	if (nkeep > 0) {
+		const int64_t stride = ((int64_t)(e->esz / sizeof(double)) * e->n_local + 1) & ~(int64_t)1;
+		if (e->resident_cap < nkeep || e->resident_stride != stride) {
+			if (e->resident) (void)hipFree(e->resident);
+			e->resident = nullptr;
+			e->resident_cap = 0;
+			HIP_TRY_MEM(hipMalloc(&e->resident, sizeof(double) * (size_t)stride * (size_t)nkeep + 16));
+			e->resident_cap = nkeep;
+			HIP_TRY(hipMemsetAsync(e->resident, 0, sizeof(double) * (size_t)stride * (size_t)nkeep, e->stream)); // the padding element of an odd length stays 0
+		}
+		e->resident_stride = stride;
+		e->resident_len = e->n_local;
+	}
 	SolveResult res;
 	st = run_recurrence(e, res);
 	e->active = false;
@@ -635,7 +667,7 @@ lpp_status lpp_engine_lanczos(lpp_engine* e, const void* init, int32_t nstates, 
 	const int steps = res.steps;
 	if (steps < nstates) return fail(LPP_ERR_NOCONV, "Lanczos: fewer steps than requested states");
 	std::vector<double> w(nstates), S;
-	if (ritz_vectors) {
+	if (want_vectors) {
 		S.resize((size_t)steps * nstates);
 		st = lpp_tridiag_lowest(steps, res.a.data(), res.b.data(), nstates, w.data(), S.data());
 	} else {
@@ -644,7 +676,7 @@ lpp_status lpp_engine_lanczos(lpp_engine* e, const void* init, int32_t nstates, 
 	if (st != LPP_OK) return st;
 	for (int k = 0; k < nstates; k++) eigs[k] = w[k];
 	const int steps_enq = e->stats.steps_enqueued;
-	if (ritz_vectors) {
+	if (want_vectors) {
 		const int nb = blas_blocks(e->n2);
 		if (e->saving) {
 			// z_k = sum_j S(j,k) v_j from the on-device Krylov basis (x is free after the run)
@@ -665,7 +697,8 @@ lpp_status lpp_engine_lanczos(lpp_engine* e, const void* init, int32_t nstates, 
 						k_multi_axpy<false><<<nb, kBlock, 0, e->stream>>>((double2*)e->x, v0, e->ldv / 2, np, e->coef_dev + 2 * p0, 1.0, e->n2);
 				}
 				HIP_TRY(hipGetLastError());
-				st = vec_to_host(e, (char*)ritz_vectors + (size_t)k * e->esz * (size_t)e->n_local, e->x);
+				if (k < nkeep && (st = vec_to_device(e, e->resident + (int64_t)k * e->resident_stride, e->x)) != LPP_OK) return st;
+				if (ritz_vectors) st = vec_to_host(e, (char*)ritz_vectors + (size_t)k * e->esz * (size_t)e->n_local, e->x);
 				if (st != LPP_OK) return st;
 				HIP_TRY(hipStreamSynchronize(e->stream));
 			}
@@ -675,7 +708,7 @@ lpp_status lpp_engine_lanczos(lpp_engine* e, const void* init, int32_t nstates, 
 			e->zwork = nullptr;
 			HIP_TRY_MEM(hipMalloc(&e->zwork, sizeof(double) * (size_t)e->nd_pad * (size_t)nstates));
 			lpp_stats keep = e->stats;
-			st = begin_run(e, init, false);
+			st = begin_run(e, init, false, dev_init);
 			if (st != LPP_OK) return st;
 			HIP_TRY(hipMemsetAsync(e->zwork, 0, sizeof(double) * (size_t)e->nd_pad * (size_t)nstates, e->stream));
 			std::vector<double> coefk(nstates);
@@ -695,13 +728,15 @@ lpp_status lpp_engine_lanczos(lpp_engine* e, const void* init, int32_t nstates, 
 			keep.spmv_launches += e->stats.spmv_launches;
 			e->stats = keep;
 			for (int k = 0; k < nstates; k++) {
-				st = vec_to_host(e, (char*)ritz_vectors + (size_t)k * e->esz * (size_t)e->n_local, e->zwork + (int64_t)k * e->nd_pad);
+				if (k < nkeep && (st = vec_to_device(e, e->resident + (int64_t)k * e->resident_stride, e->zwork + (int64_t)k * e->nd_pad)) != LPP_OK) return st;
+				if (ritz_vectors) st = vec_to_host(e, (char*)ritz_vectors + (size_t)k * e->esz * (size_t)e->n_local, e->zwork + (int64_t)k * e->nd_pad);
 				if (st != LPP_OK) return st;
 			}
 			HIP_TRY(hipStreamSynchronize(e->stream));
 			(void)hipFree(e->zwork);
 			e->zwork = nullptr;
 		}
+		e->resident_n = nkeep; // written and synchronised
 	}
 	e->collect_spmv_times();
 	e->stats.steps = steps;
@@ -712,11 +747,22 @@ lpp_status lpp_engine_lanczos(lpp_engine* e, const void* init, int32_t nstates, 
 	return LPP_OK;
 }
 
-lpp_status lpp_engine_decomposition(lpp_engine* e, const void* init, int32_t* nsteps, double* a, double* b, lpp_stats* stats)
+lpp_status lpp_engine_lanczos(lpp_engine* e, const void* init, int32_t nstates, double* eigs, void* ritz_vectors, lpp_stats* stats)
+{
+	return lanczos_impl(e, init, false, nstates, eigs, ritz_vectors, stats);
+}
+
+lpp_status lpp_engine_lanczos_device(lpp_engine* e, const void* d_init, int32_t nstates, double* eigs, void* ritz_vectors, lpp_stats* stats)
+{
+	if (!d_init) return fail(LPP_ERR_INVALID, "lpp_engine_lanczos_device: null start vector");
+	return lanczos_impl(e, d_init, true, nstates, eigs, ritz_vectors, stats);
+}
+
+static lpp_status decomposition_impl(lpp_engine* e, const void* init, bool dev_init, int32_t* nsteps, double* a, double* b, lpp_stats* stats)
 {
 	if (!e || !nsteps || !a || !b) return fail(LPP_ERR_INVALID, "lpp_engine_decomposition: bad argument");
 	const auto t0 = std::chrono::steady_clock::now();
-	lpp_status st = begin_run(e, init, false);
+	lpp_status st = begin_run(e, init, false, dev_init);
 	if (st != LPP_OK) return st;
 	SolveResult res;
 	st = run_recurrence(e, res);
@@ -735,6 +781,17 @@ lpp_status lpp_engine_decomposition(lpp_engine* e, const void* init, int32_t* ns
 	e->stats.seconds_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 	if (stats) lpp_engine_get_stats(e, stats);
 	return LPP_OK;
+}
+
+lpp_status lpp_engine_decomposition(lpp_engine* e, const void* init, int32_t* nsteps, double* a, double* b, lpp_stats* stats)
+{
+	return decomposition_impl(e, init, false, nsteps, a, b, stats);
+}
+
+lpp_status lpp_engine_decomposition_device(lpp_engine* e, const void* d_init, int32_t* nsteps, double* a, double* b, lpp_stats* stats)
+{
+	if (!d_init) return fail(LPP_ERR_INVALID, "lpp_engine_decomposition_device: null start vector");
+	return decomposition_impl(e, d_init, true, nsteps, a, b, stats);
 }
 
 } // extern "C"

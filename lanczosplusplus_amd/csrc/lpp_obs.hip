@@ -1,0 +1,654 @@
+// lpp_obs.hip -- ground-state observables of the Hubbard product basis on one GPU: one-site operators applied to device vectors
+// (Engine::accModifiedState_, reference src/Engine/Engine.h:416-458), the two-point matrix (Engine::twoPoint :266-338) and the modified
+// state + decomposition of one spectral-function type (Engine::spectralFunction :134-206, getModifiedState :494-533, calcSpectral :460-490).
+//
+// Host part (no GPU): sector arithmetic (HubbardOneOrbital::hasNewParts, HubbardOneOrbital.h:87-109,212-253), the per-species tables the
+// kernel of lpp_obs_kernels.h reads, and the continued-fraction evaluator.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <complex>
+#include <cstring>
+#include <map>
+#include <tuple>
+#include <vector>
+
+#include "lpp_engine_impl.h"
+#include "lpp_obs_kernels.h"
+
+using namespace lpp;
+
+namespace {
+
+inline bool needs_new_basis(int op) { return op == LPP_OP_C || op == LPP_OP_CDAGGER || op == LPP_OP_SPLUS || op == LPP_OP_SMINUS; } // LabeledOperator.h:83-90
+inline bool valid_op(int op) { return op == LPP_OP_C || op == LPP_OP_SZ || op == LPP_OP_CDAGGER || op == LPP_OP_N || op == LPP_OP_SPLUS || op == LPP_OP_SMINUS; }
+
+int64_t binom(int n, int k)
+{
+	if (k < 0 || k > n) return 0;
+	long double r = 1;
+	for (int i = 1; i <= k; i++) r = r * (n - k + i) / i;
+	return (int64_t)(r + 0.5L);
+}
+
+// HubbardOneOrbital::hasNewParts for c / cdagger / splus / sminus
+bool new_parts(int op, int spin, int L, int nup, int ndn, int* n1, int* n2)
+{
+	int p1 = nup, p2 = ndn;
+	if (op == LPP_OP_C || op == LPP_OP_CDAGGER) { // hasNewPartsCorCdagger :212-230
+		const int c = (op == LPP_OP_C) ? -1 : 1;
+		if (spin == LPP_SPIN_UP) p1 += c;
+		else p2 += c;
+		if (p1 < 0 || p2 < 0) return false;
+		if (p1 > L || p2 > L) return false;
+		if (p1 == 0 && p2 == 0) return false;
+	} else { // hasNewPartsSplusOrSminus :232-253
+		const int c = (op == LPP_OP_SPLUS) ? 1 : -1;
+		p1 += c;
+		p2 -= c;
+		if (p1 < 0 || p2 < 0) return false;
+		if (p1 > L || p2 > L) return false;
+	}
+	*n1 = p1;
+	*n2 = p2;
+	return true;
+}
+
+// BasisOneSpin::perfectIndex (BasisOneSpin.h:73-81): the rank of a word among the ascending words of its popcount
+struct Ranker {
+	int L;
+	std::vector<int64_t> comb; // comb[b * (L + 2) + c]
+	explicit Ranker(int L_) : L(L_), comb((size_t)(L_ + 1) * (L_ + 2))
+	{
+		for (int b = 0; b <= L; b++)
+			for (int c = 0; c <= L + 1; c++) comb[(size_t)b * (L + 2) + c] = binom(b, c);
+	}
+	int64_t rank(uint64_t w) const
+	{
+		int64_t n = 0;
+		int c = 1;
+		for (int b = 0; w; b++, w >>= 1)
+			if (w & 1) n += comb[(size_t)b * (L + 2) + c++];
+		return n;
+	}
+};
+
+enum { SP_C, SP_CDAGGER, SP_N };
+
+// one species: destination rank -> +-(source rank + 1) or 0.  kind: what the operator does to the KET word (BasisOneSpin::getBra :121-149);
+// with_sign: the parity of the ket's bits below `site` (doSignGf :112-136 for ind > 0 and both species; ProgramGlobals::doSign :109-114)
+void species_table(const Ranker& R, int L, int n_dst, int kind, int site, bool with_sign, int global_sign, std::vector<int32_t>& tab)
+{
+	const int64_t cnt = binom(L, n_dst);
+	tab.assign((size_t)cnt, 0);
+	if (cnt == 0) return;
+	const uint64_t bit = 1ull << site;
+	uint64_t w = (n_dst == 0) ? 0 : ((1ull << n_dst) - 1);
+	for (int64_t i = 0; i < cnt; i++) {
+		uint64_t ket = 0;
+		bool ok = false;
+		if (kind == SP_C) { // the bra lacks the bit the ket had
+			ok = !(w & bit);
+			ket = w | bit;
+		} else if (kind == SP_CDAGGER) {
+			ok = (w & bit) != 0;
+			ket = w ^ bit;
+		} else {
+			ok = (w & bit) != 0;
+			ket = w;
+		}
+		if (ok) {
+			int s = global_sign;
+			if (with_sign && (__builtin_popcountll(ket & (bit - 1)) & 1)) s = -s;
+			tab[(size_t)i] = (int32_t)(s * (R.rank(ket) + 1));
+		}
+		if (n_dst > 0 && i + 1 < cnt) { // next word of the same popcount (BasisOneSpin.h:53-61)
+			const uint64_t c = w & (~w + 1), r = w + c;
+			w = (((r ^ w) >> 2) / c) | r;
+		}
+	}
+}
+
+struct ObsPlan {
+	int nup2 = 0, ndn2 = 0;
+	int64_t n_up_src = 0, n_dn_src = 0, n_up_dst = 0, n_dn_dst = 0;
+	bool sz = false;
+	std::vector<int32_t> tu, td; // empty: the species is untouched
+};
+
+// has == false: the operator leads to no sector (hasNewParts refused)
+lpp_status obs_plan(int op, int site, int spin, int L, int nup, int ndn, bool* has, ObsPlan& P)
+{
+	*has = false;
+	if (!valid_op(op)) return fail(LPP_ERR_INVALID, "observables: unknown operator (LPP_OP_*)");
+	if (spin != LPP_SPIN_UP && spin != LPP_SPIN_DOWN) return fail(LPP_ERR_INVALID, "observables: spin must be LPP_SPIN_UP or LPP_SPIN_DOWN");
+	if (L < 1 || L > 30 || site < 0 || site >= L || nup < 0 || ndn < 0 || nup > L || ndn > L) return fail(LPP_ERR_INVALID, "observables: bad sites / site / sector");
+	P = ObsPlan();
+	P.nup2 = nup;
+	P.ndn2 = ndn;
+	if (needs_new_basis(op) && !new_parts(op, spin, L, nup, ndn, &P.nup2, &P.ndn2)) return LPP_OK;
+	P.n_up_src = binom(L, nup);
+	P.n_dn_src = binom(L, ndn);
+	P.n_up_dst = binom(L, P.nup2);
+	P.n_dn_dst = binom(L, P.ndn2);
+	if (P.n_up_src >= (int64_t)INT32_MAX - 4096 || P.n_dn_src >= (int64_t)INT32_MAX - 4096 || P.n_up_dst >= (int64_t)INT32_MAX - 4096 || P.n_dn_dst >= (int64_t)INT32_MAX - 4096)
+		return fail(LPP_ERR_INVALID, "observables: a species with 2^31 states or more");
+	const Ranker R(L);
+	const int kind = (op == LPP_OP_C) ? SP_C : SP_CDAGGER;
+	switch (op) {
+	case LPP_OP_C:
+	case LPP_OP_CDAGGER:
+		if (spin == LPP_SPIN_UP) {
+			species_table(R, L, P.nup2, kind, site, true, 1, P.tu);
+		} else {
+			// doSignGf, SPIN_DOWN: for ind > 0 the up parity computed first is overwritten by the parity of the down bits below ind;
+			// for ind == 0 the up parity is the whole sign (BasisHubbardLanczos.h:125-136) -- a constant of the source sector
+			const int up_parity = (site == 0 && (nup & 1)) ? -1 : 1;
+			species_table(R, L, P.ndn2, kind, site, site > 0, up_parity, P.td);
+		}
+		break;
+	case LPP_OP_N:
+		if (spin == LPP_SPIN_UP) species_table(R, L, nup, SP_N, site, false, 1, P.tu);
+		else species_table(R, L, ndn, SP_N, site, false, 1, P.td);
+		break;
+	case LPP_OP_SZ: // getBraIndexSz :210-223: +1 up only, -1 down only
+		species_table(R, L, nup, SP_N, site, false, 1, P.tu);
+		species_table(R, L, ndn, SP_N, site, false, 1, P.td);
+		P.sz = true;
+		break;
+	case LPP_OP_SPLUS: // getBraIndexSplusSminus :225-246: cdagger on the up word, c on the down word; sign doSignSpSm :151-160
+		species_table(R, L, P.nup2, SP_CDAGGER, site, true, 1, P.tu);
+		species_table(R, L, P.ndn2, SP_C, site, true, 1, P.td);
+		break;
+	case LPP_OP_SMINUS:
+		species_table(R, L, P.nup2, SP_C, site, true, 1, P.tu);
+		species_table(R, L, P.ndn2, SP_CDAGGER, site, true, 1, P.td);
+		break;
+	}
+	*has = true;
+	return LPP_OK;
+}
+
+// ---- device side ---------------------------------------------------------------------------------------------------------------------
+
+struct DevPlan {
+	ObsPlan host; // tables dropped after the upload
+	bool has = false;
+	int32_t *tu = nullptr, *td = nullptr;
+};
+
+typedef std::tuple<int, int, int, int, int, int> PlanKey;
+struct ObsCache {
+	std::map<PlanKey, DevPlan> plans;
+};
+
+inline bool multi(const lpp_engine* e) { return e->has_comm && e->comm.nranks > 1; }
+
+lpp_status refuse(const lpp_engine* e, const char* who)
+{
+	if (multi(e)) return fail(LPP_ERR_STATE, std::string(who) + ": not on a partitioned (multi-rank) engine");
+	if (e->tj.active) return fail(LPP_ERR_STATE, std::string(who) + ": not on a hole-major t-J engine");
+	return LPP_OK;
+}
+
+void free_plan(DevPlan& D)
+{
+	if (D.tu) (void)hipFree(D.tu);
+	if (D.td) (void)hipFree(D.td);
+	D.tu = D.td = nullptr;
+}
+
+// The tables of one (operator, site, spin, sites, sector), uploaded once and kept with the engine.  The key is what the caller passes -- the engine
+// needs no model for lpp_engine_apply_operator -- so the cache is bounded: a density of states or a two-point matrix uses at most 2 * sites entries
+// per operator; past kMaxPlans entries everything is dropped and rebuilt on demand.  The returned pointer is valid until the next get_plan.
+constexpr size_t kMaxPlans = 256;
+
+lpp_status get_plan(lpp_engine* e, int op, int site, int spin, int L, int nup, int ndn, const DevPlan** out)
+{
+	if (!e->obs) e->obs = new ObsCache();
+	ObsCache* C = (ObsCache*)e->obs;
+	const PlanKey key(op, site, spin, L, nup, ndn);
+	auto it = C->plans.find(key);
+	if (it == C->plans.end()) {
+		DevPlan D;
+		bool has = false;
+		lpp_status st = obs_plan(op, site, spin, L, nup, ndn, &has, D.host);
+		if (st != LPP_OK) return st;
+		D.has = has;
+		if (has) {
+			for (int s = 0; s < 2; s++) {
+				std::vector<int32_t>& t = s ? D.host.td : D.host.tu;
+				if (t.empty()) continue;
+				int32_t* d = nullptr;
+				hipError_t err = hipMalloc(&d, sizeof(int32_t) * t.size());
+				(s ? D.td : D.tu) = d;
+				if (err == hipSuccess) err = hipMemcpy(d, t.data(), sizeof(int32_t) * t.size(), hipMemcpyHostToDevice);
+				if (err != hipSuccess) {
+					free_plan(D); // the other species' table too
+					if (err == hipErrorOutOfMemory) {
+						(void)hipGetLastError();
+						return fail(LPP_ERR_NOMEM, "observables: no device memory for the operator tables");
+					}
+					HIP_TRY(err);
+				}
+				std::vector<int32_t>().swap(t);
+			}
+		}
+		if (C->plans.size() >= kMaxPlans) {
+			HIP_TRY(hipStreamSynchronize(e->stream)); // launches that still read the old tables
+			for (auto& kv : C->plans) free_plan(kv.second);
+			C->plans.clear();
+		}
+		it = C->plans.emplace(key, D).first;
+	}
+	*out = &it->second;
+	return LPP_OK;
+}
+
+int obs_grid(const lpp_engine* e, int64_t units)
+{
+	const int64_t tiles = (units + kObsTile - 1) / kObsTile;
+	return (int)std::max<int64_t>(1, std::min<int64_t>(tiles, (int64_t)e->num_cus * 32));
+}
+
+// z (+)= factor * A src on device vectors in the basis order; *has == false: no such sector, nothing was launched
+lpp_status apply_dev(lpp_engine* e, int op, int site, int spin, int L, int nup, int ndn, double fr, double fi, const void* d_src, void* d_dst, bool acc, bool* has,
+                     int64_t* n_dst)
+{
+	const DevPlan* D = nullptr;
+	lpp_status st = get_plan(e, op, site, spin, L, nup, ndn, &D);
+	if (st != LPP_OK) return st;
+	*has = D->has;
+	if (!D->has) return LPP_OK;
+	const ObsPlan& P = D->host;
+	if (n_dst) *n_dst = P.n_up_dst * P.n_dn_dst;
+	if (!d_src || !d_dst) return fail(LPP_ERR_INVALID, "observables: null vector");
+	// the destination is written in 16-byte units; a c128 source element is read as one double2, an f64 source element as one double
+	if (((uintptr_t)d_dst & 15) != 0) return fail(LPP_ERR_INVALID, "observables: the destination must be 16-byte aligned");
+	if (((uintptr_t)d_src & (e->is_complex ? 15 : 7)) != 0) return fail(LPP_ERR_INVALID, "observables: the source must be aligned to its element size (8 bytes f64, 16 bytes c128)");
+	if (!e->is_complex && fi != 0.0) return fail(LPP_ERR_INVALID, "observables: complex factor on a real engine");
+	const int64_t nd = P.n_up_dst * P.n_dn_dst;
+	if (nd == 0) return LPP_OK;
+	ObsArgs A { D->tu, D->td, P.n_up_dst, P.n_dn_dst, P.n_up_src, P.sz ? 1 : 0, fr, fi };
+	const int64_t units = e->is_complex ? nd : (nd + 1) / 2;
+	const int g = obs_grid(e, units);
+	if (e->is_complex) {
+		if (acc) k_obs_apply<true, true><<<g, kObsBlock, 0, e->stream>>>((double*)d_dst, (const double*)d_src, A);
+		else k_obs_apply<true, false><<<g, kObsBlock, 0, e->stream>>>((double*)d_dst, (const double*)d_src, A);
+	} else {
+		if (acc) k_obs_apply<false, true><<<g, kObsBlock, 0, e->stream>>>((double*)d_dst, (const double*)d_src, A);
+		else k_obs_apply<false, false><<<g, kObsBlock, 0, e->stream>>>((double*)d_dst, (const double*)d_src, A);
+	}
+	HIP_TRY(hipGetLastError());
+	return LPP_OK;
+}
+
+// the operator Engine::accModifiedState applies (Engine.h:535-599): n directly, sz as n_up/2 - n_down/2, the others as given
+lpp_status acc_modified_dev(lpp_engine* e, int op, int site, int spin, int L, int nup, int ndn, double isign, const void* d_src, void* d_dst, bool acc, bool* has)
+{
+	if (op == LPP_OP_SZ) {
+		lpp_status st = apply_dev(e, LPP_OP_N, site, LPP_SPIN_UP, L, nup, ndn, isign * 0.5, 0.0, d_src, d_dst, acc, has, nullptr);
+		if (st != LPP_OK) return st;
+		return apply_dev(e, LPP_OP_N, site, LPP_SPIN_DOWN, L, nup, ndn, -isign * 0.5, 0.0, d_src, d_dst, true, has, nullptr);
+	}
+	return apply_dev(e, op, site, spin, L, nup, ndn, isign, 0.0, d_src, d_dst, acc, has, nullptr);
+}
+
+struct DevBuf {
+	void* p = nullptr;
+	~DevBuf()
+	{
+		if (p) (void)hipFree(p);
+	}
+};
+
+int blas_blocks(int64_t n2)
+{
+	const int64_t b = (n2 + kBlock - 1) / kBlock;
+	return (int)std::max<int64_t>(1, std::min<int64_t>(b, 2048));
+}
+
+lpp_status state_ptr(lpp_engine* e, int k, const char* who, double** p)
+{
+	if (k < 0 || k >= e->resident_n || !e->resident) return fail(LPP_ERR_STATE, std::string(who) + ": no such resident state (lpp_engine_keep_states before lpp_engine_lanczos)");
+	*p = e->resident + (int64_t)k * e->resident_stride;
+	return LPP_OK;
+}
+
+} // namespace
+
+namespace lpp {
+void free_obs(lpp_engine* e)
+{
+	if (e->obs) {
+		ObsCache* C = (ObsCache*)e->obs;
+		for (auto& kv : C->plans) free_plan(kv.second);
+		delete C;
+		e->obs = nullptr;
+	}
+	if (e->resident) (void)hipFree(e->resident);
+	e->resident = nullptr;
+	e->resident_n = e->resident_cap = 0;
+}
+} // namespace lpp
+
+extern "C" {
+
+lpp_status lpp_obs_new_parts(int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t* has, int32_t* nup_new, int32_t* ndown_new)
+{
+	if (!has) return fail(LPP_ERR_INVALID, "lpp_obs_new_parts: null argument");
+	*has = 0;
+	if (spin != LPP_SPIN_UP && spin != LPP_SPIN_DOWN) return fail(LPP_ERR_INVALID, "lpp_obs_new_parts: bad spin");
+	if (nsites < 1 || nup < 0 || ndown < 0 || nup > nsites || ndown > nsites) return fail(LPP_ERR_INVALID, "lpp_obs_new_parts: bad sector");
+	if (op == LPP_OP_SZ) return LPP_OK; // HubbardOneOrbital.h:101-102
+	if (!needs_new_basis(op)) return fail(LPP_ERR_INVALID, "hasNewParts: unsupported operator"); // the reference throws (:104-108)
+	int n1 = 0, n2 = 0;
+	if (!new_parts(op, spin, nsites, nup, ndown, &n1, &n2)) return LPP_OK;
+	*has = 1;
+	if (nup_new) *nup_new = n1;
+	if (ndown_new) *ndown_new = n2;
+	return LPP_OK;
+}
+
+lpp_status lpp_obs_plan(int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t* has, int32_t* nup_new, int32_t* ndown_new,
+                        int64_t* n_up_dst, int64_t* n_down_dst, int32_t* table_up, int32_t* table_down)
+{
+	if (!has) return fail(LPP_ERR_INVALID, "lpp_obs_plan: null argument");
+	ObsPlan P;
+	bool h = false;
+	lpp_status st = obs_plan(op, site, spin, nsites, nup, ndown, &h, P);
+	if (st != LPP_OK) return st;
+	*has = h ? 1 : 0;
+	if (!h) return LPP_OK;
+	if (nup_new) *nup_new = P.nup2;
+	if (ndown_new) *ndown_new = P.ndn2;
+	if (n_up_dst) *n_up_dst = P.n_up_dst;
+	if (n_down_dst) *n_down_dst = P.n_dn_dst;
+	for (int s = 0; s < 2; s++) {
+		int32_t* out = s ? table_down : table_up;
+		if (!out) continue;
+		const std::vector<int32_t>& t = s ? P.td : P.tu;
+		const int64_t n = s ? P.n_dn_dst : P.n_up_dst;
+		for (int64_t i = 0; i < n; i++) out[i] = t.empty() ? (int32_t)(i + 1) : t[(size_t)i];
+	}
+	return LPP_OK;
+}
+
+lpp_status lpp_continued_fraction(int32_t n, const double* a, const double* b, double eg, double weight, double sigma, double z_re, double z_im, double* out)
+{
+	if (n < 1 || !a || !b || !out) return fail(LPP_ERR_INVALID, "lpp_continued_fraction: bad argument");
+	const std::complex<double> z(z_re, z_im);
+	std::complex<double> t = z + sigma * (a[n - 1] - eg);
+	for (int k = n - 2; k >= 0; k--) t = z + sigma * (a[k] - eg) - b[k] * b[k] / t; // b[k] couples levels k and k+1
+	const std::complex<double> g = weight / t;
+	out[0] = g.real();
+	out[1] = g.imag();
+	return LPP_OK;
+}
+
+lpp_status lpp_engine_apply_operator(lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, double factor_re,
+                                     double factor_im, const void* d_src, void* d_dst, int32_t accumulate, int32_t* has)
+{
+	if (!e || !has) return fail(LPP_ERR_INVALID, "lpp_engine_apply_operator: null argument");
+	lpp_status st = refuse(e, "lpp_engine_apply_operator");
+	if (st != LPP_OK) return st;
+	HIP_TRY(hipSetDevice(e->cfg.device));
+	bool h = false;
+	st = apply_dev(e, op, site, spin, nsites, nup, ndown, factor_re, factor_im, d_src, d_dst, accumulate != 0, &h, nullptr);
+	*has = h ? 1 : 0;
+	return st;
+}
+
+lpp_status lpp_engine_apply_operator_host(lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, double factor_re,
+                                          double factor_im, const void* src, void* dst, int32_t accumulate, int32_t* has)
+{
+	if (!e || !has || !src || !dst) return fail(LPP_ERR_INVALID, "lpp_engine_apply_operator_host: null argument");
+	lpp_status st = refuse(e, "lpp_engine_apply_operator_host");
+	if (st != LPP_OK) return st;
+	HIP_TRY(hipSetDevice(e->cfg.device));
+	const DevPlan* D = nullptr;
+	st = get_plan(e, op, site, spin, nsites, nup, ndown, &D);
+	if (st != LPP_OK) return st;
+	*has = D->has ? 1 : 0;
+	if (!D->has) return LPP_OK;
+	const size_t ns = e->esz * (size_t)(D->host.n_up_src * D->host.n_dn_src), nd = e->esz * (size_t)(D->host.n_up_dst * D->host.n_dn_dst);
+	DevBuf ds, dd;
+	HIP_TRY_MEM(hipMalloc(&ds.p, std::max<size_t>(ns, 16)));
+	HIP_TRY_MEM(hipMalloc(&dd.p, std::max<size_t>(nd, 16) + 16));
+	HIP_TRY(hipMemcpyAsync(ds.p, src, ns, hipMemcpyHostToDevice, e->stream));
+	if (accumulate) HIP_TRY(hipMemcpyAsync(dd.p, dst, nd, hipMemcpyHostToDevice, e->stream));
+	bool h = false;
+	st = apply_dev(e, op, site, spin, nsites, nup, ndown, factor_re, factor_im, ds.p, dd.p, accumulate != 0, &h, nullptr);
+	if (st != LPP_OK) return st;
+	HIP_TRY(hipMemcpyAsync(dst, dd.p, nd, hipMemcpyDeviceToHost, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	return LPP_OK;
+}
+
+lpp_status lpp_engine_bench_operator(lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t warmup, int32_t iters,
+                                     double* ms_per_launch, double* model_bytes)
+{
+	if (!e || !ms_per_launch || iters < 1 || warmup < 0) return fail(LPP_ERR_INVALID, "lpp_engine_bench_operator: bad argument");
+	lpp_status st = refuse(e, "lpp_engine_bench_operator");
+	if (st != LPP_OK) return st;
+	HIP_TRY(hipSetDevice(e->cfg.device));
+	const DevPlan* D = nullptr;
+	st = get_plan(e, op, site, spin, nsites, nup, ndown, &D);
+	if (st != LPP_OK) return st;
+	if (!D->has) return fail(LPP_ERR_INVALID, "lpp_engine_bench_operator: the operator leads to no sector");
+	const int64_t ns = D->host.n_up_src * D->host.n_dn_src, nd = D->host.n_up_dst * D->host.n_dn_dst;
+	DevBuf ds, dd;
+	HIP_TRY_MEM(hipMalloc(&ds.p, std::max<size_t>(e->esz * (size_t)ns, 16)));
+	HIP_TRY_MEM(hipMalloc(&dd.p, std::max<size_t>(e->esz * (size_t)nd, 16) + 16));
+	HIP_TRY(hipMemsetAsync(ds.p, 0, e->esz * (size_t)ns, e->stream));
+	HIP_TRY(hipMemsetAsync(dd.p, 0, e->esz * (size_t)nd, e->stream));
+	hipEvent_t t0 = nullptr, t1 = nullptr;
+	HIP_TRY(hipEventCreate(&t0));
+	HIP_TRY(hipEventCreate(&t1));
+	bool h = false;
+	for (int i = 0; i < warmup + iters && st == LPP_OK; i++) {
+		if (i == warmup) (void)hipEventRecord(t0, e->stream);
+		st = apply_dev(e, op, site, spin, nsites, nup, ndown, 1.0, 0.0, ds.p, dd.p, true, &h, nullptr);
+	}
+	(void)hipEventRecord(t1, e->stream);
+	hipError_t err = hipEventSynchronize(t1);
+	float ms = 0;
+	if (err == hipSuccess) err = hipEventElapsedTime(&ms, t0, t1);
+	(void)hipEventDestroy(t0);
+	(void)hipEventDestroy(t1);
+	if (st != LPP_OK) return st;
+	HIP_TRY(err);
+	*ms_per_launch = ms / iters;
+	// the issue's byte model of z += A src: destination read + write, source entries read once
+	int64_t touched = 0;
+	{
+		ObsPlan P;
+		bool hh = false;
+		st = obs_plan(op, site, spin, nsites, nup, ndown, &hh, P);
+		if (st != LPP_OK) return st;
+		int64_t cu = P.n_up_dst, cd = P.n_dn_dst;
+		if (!P.tu.empty()) cu = (int64_t)std::count_if(P.tu.begin(), P.tu.end(), [](int32_t v) { return v != 0; });
+		if (!P.td.empty()) cd = (int64_t)std::count_if(P.td.begin(), P.td.end(), [](int32_t v) { return v != 0; });
+		touched = cu * cd;
+	}
+	if (model_bytes) *model_bytes = (double)e->esz * (2.0 * (double)nd + (double)touched);
+	return LPP_OK;
+}
+
+lpp_status lpp_engine_keep_states(lpp_engine* e, int32_t k)
+{
+	if (!e || k < 0) return fail(LPP_ERR_INVALID, "lpp_engine_keep_states: bad argument");
+	if (e->active) return fail(LPP_ERR_STATE, "lpp_engine_keep_states: a Lanczos run is active");
+	if (k > 0) {
+		lpp_status st = refuse(e, "lpp_engine_keep_states");
+		if (st != LPP_OK) return st;
+	}
+	e->keep_k = k;
+	return LPP_OK;
+}
+
+lpp_status lpp_engine_state_device(lpp_engine* e, int32_t k, void** d_ptr, int64_t* len)
+{
+	if (!e || !d_ptr) return fail(LPP_ERR_INVALID, "lpp_engine_state_device: null argument");
+	double* p = nullptr;
+	lpp_status st = state_ptr(e, k, "lpp_engine_state_device", &p);
+	if (st != LPP_OK) return st;
+	*d_ptr = p;
+	if (len) *len = e->resident_len;
+	return LPP_OK;
+}
+
+lpp_status lpp_engine_state_to_host(lpp_engine* e, int32_t k, void* host)
+{
+	if (!e || !host) return fail(LPP_ERR_INVALID, "lpp_engine_state_to_host: null argument");
+	double* p = nullptr;
+	lpp_status st = state_ptr(e, k, "lpp_engine_state_to_host", &p);
+	if (st != LPP_OK) return st;
+	HIP_TRY(hipSetDevice(e->cfg.device));
+	HIP_TRY(hipMemcpyAsync(host, p, e->esz * (size_t)e->resident_len, hipMemcpyDeviceToHost, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	return LPP_OK;
+}
+
+lpp_status lpp_engine_two_point(lpp_engine* e, int32_t op, int32_t spin1, int32_t spin2, int32_t nsites, int32_t nup, int32_t ndown, int32_t bra_state,
+                                int32_t ket_state, void* result, void* trace)
+{
+	if (!e || !result) return fail(LPP_ERR_INVALID, "lpp_engine_two_point: null argument");
+	lpp_status st = refuse(e, "lpp_engine_two_point");
+	if (st != LPP_OK) return st;
+	if (!valid_op(op)) return fail(LPP_ERR_INVALID, "lpp_engine_two_point: unknown operator");
+	if ((spin1 != 0 && spin1 != 1) || (spin2 != 0 && spin2 != 1)) return fail(LPP_ERR_INVALID, "lpp_engine_two_point: bad spin");
+	const int L = nsites;
+	if (L < 1 || L > 30 || nup < 0 || ndown < 0 || nup > L || ndown > L) return fail(LPP_ERR_INVALID, "lpp_engine_two_point: bad sites / sector");
+	double *bra = nullptr, *ket = nullptr;
+	if ((st = state_ptr(e, bra_state, "lpp_engine_two_point", &bra)) != LPP_OK) return st;
+	if ((st = state_ptr(e, ket_state, "lpp_engine_two_point", &ket)) != LPP_OK) return st;
+	if (e->resident_len != binom(L, nup) * binom(L, ndown)) return fail(LPP_ERR_INVALID, "lpp_engine_two_point: (sites, nup, ndown) is not the sector of the resident states");
+	HIP_TRY(hipSetDevice(e->cfg.device));
+	const int w = e->is_complex ? 2 : 1;
+	double* res = (double*)result;
+	for (int64_t i = 0; i < (int64_t)L * L; i++) { // Engine.h:303-305
+		res[w * i] = -100.0;
+		if (w == 2) res[w * i + 1] = 0.0;
+	}
+	if (trace) {
+		((double*)trace)[0] = 0.0;
+		if (w == 2) ((double*)trace)[1] = 0.0;
+	}
+	int nup2 = nup, ndn2 = ndown;
+	if (needs_new_basis(op)) {
+		if (spin1 != spin2) return fail(LPP_ERR_INVALID, "twoPoint: no support yet for off-diagonal spin when needs new basis"); // Engine.h:276-282
+		if (!new_parts(op, spin1, L, nup, ndown, &nup2, &ndn2)) return LPP_OK; // no such sector: the matrix keeps its fill
+	}
+	const int64_t ndst = binom(L, nup2) * binom(L, ndn2);
+	if (ndst == 0) return LPP_OK;
+	const int64_t stride = ((ndst * w + 1) & ~(int64_t)1) + 0; // doubles per modified vector, 16-byte aligned columns
+	const int64_t ld2 = stride / 2, n2 = stride / 2;
+	const bool same = (bra == ket) && (spin1 == spin2);
+	// panels of bra vectors sized to the free memory; the ket vectors are one scratch vector each unless they ARE the bra vectors
+	size_t free_b = 0, total_b = 0;
+	HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+	const size_t vec_bytes = sizeof(double) * (size_t)stride;
+	int64_t fit = (int64_t)((double)free_b * 0.8 / (double)vec_bytes) - 1;
+	if (fit < 1) return fail(LPP_ERR_NOMEM, "lpp_engine_two_point: no room for two modified vectors");
+	const int panel = (int)std::min<int64_t>(L, fit);
+	DevBuf B, K, part, out;
+	HIP_TRY_MEM(hipMalloc(&B.p, vec_bytes * (size_t)panel));
+	HIP_TRY_MEM(hipMalloc(&K.p, vec_bytes));
+	const int nb = blas_blocks(n2);
+	HIP_TRY_MEM(hipMalloc(&part.p, sizeof(double) * (size_t)nb * 2 * kPanel));
+	HIP_TRY_MEM(hipMalloc(&out.p, sizeof(double) * 2 * (size_t)L * (size_t)L));
+	HIP_TRY(hipMemsetAsync(out.p, 0, sizeof(double) * 2 * (size_t)L * (size_t)L, e->stream));
+	HIP_TRY(hipMemsetAsync(B.p, 0, vec_bytes * (size_t)panel, e->stream)); // the padding element of an odd length stays 0
+	HIP_TRY(hipMemsetAsync(K.p, 0, vec_bytes, e->stream));
+	bool has = false;
+	for (int j0 = 0; j0 < L; j0 += panel) {
+		const int nj = std::min(panel, L - j0);
+		for (int j = 0; j < nj; j++) {
+			st = acc_modified_dev(e, op, j0 + j, spin2, L, nup, ndown, 1.0, bra, (double*)B.p + (int64_t)j * stride, false, &has);
+			if (st != LPP_OK) return st;
+		}
+		for (int i = 0; i < L; i++) {
+			const double* xi = nullptr;
+			if (same && i >= j0 && i < j0 + nj) {
+				xi = (const double*)B.p + (int64_t)(i - j0) * stride;
+			} else {
+				st = acc_modified_dev(e, op, i, spin1, L, nup, ndown, 1.0, ket, K.p, false, &has);
+				if (st != LPP_OK) return st;
+				xi = (const double*)K.p;
+			}
+			for (int p0 = 0; p0 < nj; p0 += kPanel) {
+				const int np = std::min(kPanel, nj - p0);
+				const double2* v0 = (const double2*)((double*)B.p + (int64_t)p0 * stride);
+				// coef_p = sum conj(v_p) x: the bra side (the left factor of modifVector2 * modifVector1) is conjugated
+				if (e->is_complex) k_multi_dot<true><<<nb, kBlock, 0, e->stream>>>((const double2*)xi, v0, ld2, np, n2, (double*)part.p);
+				else k_multi_dot<false><<<nb, kBlock, 0, e->stream>>>((const double2*)xi, v0, ld2, np, n2, (double*)part.p);
+				k_reduce_final<<<1, kBlock, 0, e->stream>>>((const double*)part.p, nb, 2 * kPanel, 2 * np, (double*)out.p + 2 * ((int64_t)i * L + j0 + p0));
+			}
+		}
+	}
+	HIP_TRY(hipGetLastError());
+	std::vector<double> h(2 * (size_t)L * (size_t)L);
+	HIP_TRY(hipMemcpyAsync(h.data(), out.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	double tr = 0, ti = 0;
+	for (int i = 0; i < L; i++)
+		for (int j = 0; j < L; j++) {
+			const size_t q = (size_t)i * L + j;
+			res[w * q] = h[2 * q];
+			if (w == 2) res[w * q + 1] = h[2 * q + 1];
+			if (i == j) {
+				tr += h[2 * q];
+				ti += h[2 * q + 1];
+			}
+		}
+	if (trace) {
+		((double*)trace)[0] = tr;
+		if (w == 2) ((double*)trace)[1] = ti;
+	}
+	return LPP_OK;
+}
+
+lpp_status lpp_engine_spectral_decomposition(lpp_engine* e, int32_t state, lpp_engine* sector, int32_t op, int32_t isite, int32_t jsite, int32_t spin, double isign,
+                                             int32_t nsites, int32_t nup, int32_t ndown, double* weight, int32_t* nsteps, double* a, double* b, lpp_stats* stats)
+{
+	if (!e || !sector || !weight || !nsteps || !a || !b) return fail(LPP_ERR_INVALID, "lpp_engine_spectral_decomposition: null argument");
+	lpp_status st = refuse(e, "lpp_engine_spectral_decomposition");
+	if (st != LPP_OK) return st;
+	if ((st = refuse(sector, "lpp_engine_spectral_decomposition (sector engine)")) != LPP_OK) return st;
+	if (e->cfg.device != sector->cfg.device || e->is_complex != sector->is_complex) return fail(LPP_ERR_INVALID, "lpp_engine_spectral_decomposition: the sector engine must share device and dtype");
+	if (!sector->has_matrix()) return fail(LPP_ERR_STATE, "lpp_engine_spectral_decomposition: the sector engine has no matrix");
+	double* gs = nullptr;
+	if ((st = state_ptr(e, state, "lpp_engine_spectral_decomposition", &gs)) != LPP_OK) return st;
+	const int L = nsites;
+	if (L < 1 || L > 30 || nup < 0 || ndown < 0 || nup > L || ndown > L || e->resident_len != binom(L, nup) * binom(L, ndown))
+		return fail(LPP_ERR_INVALID, "lpp_engine_spectral_decomposition: (sites, nup, ndown) is not the sector of the resident state");
+	int nup2 = nup, ndn2 = ndown;
+	if (needs_new_basis(op) && !new_parts(op, spin, L, nup, ndown, &nup2, &ndn2)) return fail(LPP_ERR_INVALID, "lpp_engine_spectral_decomposition: the operator leads to no sector (lpp_obs_new_parts)");
+	const int64_t ndst = binom(L, nup2) * binom(L, ndn2);
+	if (ndst != sector->n_global) return fail(LPP_ERR_INVALID, "lpp_engine_spectral_decomposition: the sector engine does not hold the operator's sector");
+	HIP_TRY(hipSetDevice(e->cfg.device));
+	const int w = e->is_complex ? 2 : 1;
+	const int64_t stride = (ndst * w + 1) & ~(int64_t)1;
+	DevBuf M, part;
+	HIP_TRY_MEM(hipMalloc(&M.p, sizeof(double) * (size_t)stride + 16));
+	const int nb = blas_blocks(stride / 2);
+	HIP_TRY_MEM(hipMalloc(&part.p, sizeof(double) * (size_t)(nb + 1)));
+	HIP_TRY(hipMemsetAsync(M.p, 0, sizeof(double) * (size_t)stride, e->stream));
+	bool has = false;
+	// getModifiedState (Engine.h:494-533): A_i gs, then isign A_j gs on top -- for i == j the state is accumulated twice
+	st = apply_dev(e, op, isite, spin, L, nup, ndown, 1.0, 0.0, gs, M.p, true, &has, nullptr);
+	if (st != LPP_OK) return st;
+	st = apply_dev(e, op, jsite, spin, L, nup, ndown, isign, 0.0, gs, M.p, true, &has, nullptr);
+	if (st != LPP_OK) return st;
+	k_dot<<<nb, kBlock, 0, e->stream>>>((const double2*)M.p, (const double2*)M.p, stride / 2, (double*)part.p);
+	k_reduce_final<<<1, kBlock, 0, e->stream>>>((const double*)part.p, nb, 1, 1, (double*)part.p + nb);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(weight, (double*)part.p + nb, sizeof(double), hipMemcpyDeviceToHost, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream)); // the sector engine runs on a stream of its own
+	return lpp_engine_decomposition_device(sector, M.p, nsteps, a, b, stats);
+}
+
+} // extern "C"

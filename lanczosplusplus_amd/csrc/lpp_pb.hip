@@ -1543,6 +1543,46 @@ lpp_status vec_to_host(lpp_engine* e, void* host, const double* dev)
 	return LPP_OK;
 }
 
+// device vector in the basis order -> the internal (pitched / permuted) form: vec_from_host without the host
+lpp_status vec_from_device(lpp_engine* e, double* dev, const void* basis)
+{
+	if (e->tj.active) return fail(LPP_ERR_STATE, "device vectors: not on a hole-major t-J engine");
+	if (e->pitch > 0) {
+		const PbState& B = e->pb;
+		double* const land = B.perm ? B.u : dev;
+		HIP_TRY(hipMemsetAsync(land, 0, sizeof(double) * (size_t)e->nd_pad, e->stream));
+		HIP_TRY(hipMemcpy2DAsync(land, e->esz * (size_t)e->pitch, basis, e->esz * (size_t)e->pitch_rows, e->esz * (size_t)e->pitch_rows, (size_t)e->pitch_blocks,
+		                         hipMemcpyDeviceToDevice, e->stream));
+		if (B.perm) {
+			k_pb_permute<true><<<2048, 256, 0, e->stream>>>(dev, land, B.perm, e->pitch_blocks, e->pitch_rows, e->pitch);
+			HIP_TRY(hipGetLastError());
+		}
+		return LPP_OK;
+	}
+	HIP_TRY(hipMemcpyAsync(dev, basis, e->esz * (size_t)e->n_local, hipMemcpyDeviceToDevice, e->stream));
+	return LPP_OK;
+}
+
+// ... and back: vec_to_host with a device destination
+lpp_status vec_to_device(lpp_engine* e, void* basis, const double* dev)
+{
+	if (e->tj.active) return fail(LPP_ERR_STATE, "device vectors: not on a hole-major t-J engine");
+	if (e->pitch > 0) {
+		const PbState& B = e->pb;
+		const double* from = dev;
+		if (B.perm) {
+			k_pb_permute<false><<<2048, 256, 0, e->stream>>>(B.u, dev, B.perm, e->pitch_blocks, e->pitch_rows, e->pitch);
+			HIP_TRY(hipGetLastError());
+			from = B.u;
+		}
+		HIP_TRY(hipMemcpy2DAsync(basis, e->esz * (size_t)e->pitch_rows, from, e->esz * (size_t)e->pitch, e->esz * (size_t)e->pitch_rows, (size_t)e->pitch_blocks,
+		                         hipMemcpyDeviceToDevice, e->stream));
+		return LPP_OK;
+	}
+	HIP_TRY(hipMemcpyAsync(basis, dev, e->esz * (size_t)e->n_local, hipMemcpyDeviceToDevice, e->stream));
+	return LPP_OK;
+}
+
 void vec_fill_random(lpp_engine* e, double* dev, uint64_t seed)
 {
 	if (e->tj.active) {

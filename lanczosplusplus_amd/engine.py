@@ -22,6 +22,20 @@ def _mat(a, L):
     return np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(L, L))
 
 
+# LabeledOperator::toId (reference src/Engine/LabeledOperator.h:36-59)
+OPERATORS = {"c": _capi.LPP_OP_C, "sz": _capi.LPP_OP_SZ, "cdagger": _capi.LPP_OP_CDAGGER, "n": _capi.LPP_OP_N,
+             "splus": _capi.LPP_OP_SPLUS, "sminus": _capi.LPP_OP_SMINUS}
+_TRANSPOSE_CONJUGATE = {"c": "cdagger", "cdagger": "c", "splus": "sminus", "sminus": "splus", "n": "n", "sz": "sz"}  # :107-119
+_FERMIONIC = ("c", "cdagger")  # :100-105
+
+
+def _op_id(op):
+    try:
+        return OPERATORS[op]
+    except KeyError:
+        raise ValueError("unsupported operator %r (one of %s)" % (op, ", ".join(sorted(OPERATORS))))
+
+
 class LanczosEngine:
     """One engine = one GPU (one process per GPU in the multi-GPU path)."""
 
@@ -49,6 +63,12 @@ class LanczosEngine:
         cfg.compress_values = int(compress_values)
         self.max_steps = max_steps
         self._comm_keepalive = None
+        self._ctor = dict(dtype="c128" if self.is_complex else "f64", device=device, check_lag=check_lag, spmv_kernel=spmv_kernel,
+                          time_kernels=time_kernels, seed=seed, compress_values=compress_values)
+        self._model = None  # what assemble_hubbard / setup_hubbard_onthefly were given (spectral_function builds the N+-1 sectors from it)
+        self._energies = None
+        self._sectors = {}  # (nup, ndown) -> LanczosEngine holding that sector's Hamiltonian
+        self.sector_assemblies = 0
         check(self._lib.lpp_engine_create(C.byref(self._h), C.byref(cfg)))
 
     def stream_ptr(self):
@@ -61,6 +81,9 @@ class LanczosEngine:
         return not (getattr(self, "_h", None) is not None and self._h)
 
     def close(self):
+        for eng in getattr(self, "_sectors", {}).values():
+            eng.close()
+        self._sectors = {}
         if getattr(self, "_h", None) is not None and self._h:
             self._lib.lpp_engine_destroy(self._h)
             self._h = C.c_void_p()
@@ -132,6 +155,7 @@ class LanczosEngine:
         V = np.zeros(L) if V is None else np.ascontiguousarray(np.asarray(V, np.float64)[:L])
         nj = None if ninj is None else _mat(ninj, L)
         self._comm_keepalive = comm
+        self._set_model("assemble_hubbard", L, nup, ndown, hop, U, V, ninj, jcoup, comm)
         cs = C.byref(comm.struct) if comm is not None else None
         jc = None if jcoup is None else _mat(jcoup, L)
         check(self._lib.lpp_engine_assemble_hubbard_super(self._h, cs, L, nup, ndown, _vp(hr), _vp(hi), _vp(U), _vp(V), _vp(nj), _vp(jc)))
@@ -147,6 +171,7 @@ class LanczosEngine:
         V = np.zeros(L) if V is None else np.ascontiguousarray(np.asarray(V, np.float64)[:L])
         nj = None if ninj is None else _mat(ninj, L)
         self._comm_keepalive = comm
+        self._set_model("setup_hubbard_onthefly", L, nup, ndown, hop, U, V, ninj, jcoup, comm)
         cs = C.byref(comm.struct) if comm is not None else None
         jc = None if jcoup is None else _mat(jcoup, L)
         check(self._lib.lpp_engine_setup_hubbard_onthefly_super(self._h, cs, L, nup, ndown, _vp(hr), _vp(hi), _vp(U), _vp(V), _vp(nj), _vp(jc)))
@@ -205,28 +230,39 @@ class LanczosEngine:
             raise ValueError("initial vector length does not match rows()")
         return init, _vp(init)
 
-    def computeAllStatesBelow(self, nstates=1, init=None, want_vectors=True):
-        """Lowest `nstates` Ritz values (and vectors): LanczosSolver::computeAllStatesBelow."""
-        keep, ip = self._init_ptr(init)
+    def computeAllStatesBelow(self, nstates=1, init=None, want_vectors=True, init_device=None):
+        """Lowest `nstates` Ritz values (and vectors): LanczosSolver::computeAllStatesBelow.
+        init_device: raw device address of a start vector in the basis order on the engine's GPU (lpp_engine_lanczos_device)."""
         eigs = np.zeros(nstates, np.float64)
         zs = np.zeros((nstates, self.rows()), self.np_dtype) if want_vectors else None
         st = Stats()
-        check(self._lib.lpp_engine_lanczos(self._h, ip, nstates, _vp(eigs), _vp(zs), C.byref(st)))
+        if init_device is not None:
+            check(self._lib.lpp_engine_lanczos_device(self._h, C.c_void_p(int(init_device)), nstates, _vp(eigs), _vp(zs), C.byref(st)))
+        else:
+            keep, ip = self._init_ptr(init)
+            check(self._lib.lpp_engine_lanczos(self._h, ip, nstates, _vp(eigs), _vp(zs), C.byref(st)))
+        self._energies = eigs.copy()
         return eigs, zs, st.as_dict()
 
     lanczos = computeAllStatesBelow
 
-    def decomposition(self, init=None):
-        keep, ip = self._init_ptr(init)
+    def decomposition(self, init=None, init_device=None):
         a = np.zeros(self.max_steps + 2)
         b = np.zeros(self.max_steps + 2)
         n = C.c_int32()
         st = Stats()
-        check(self._lib.lpp_engine_decomposition(self._h, ip, C.byref(n), _vp(a), _vp(b), C.byref(st)))
+        if init_device is not None:
+            check(self._lib.lpp_engine_decomposition_device(self._h, C.c_void_p(int(init_device)), C.byref(n), _vp(a), _vp(b), C.byref(st)))
+        else:
+            keep, ip = self._init_ptr(init)
+            check(self._lib.lpp_engine_decomposition(self._h, ip, C.byref(n), _vp(a), _vp(b), C.byref(st)))
         return a[:n.value].copy(), b[:n.value].copy(), st.as_dict()
 
     # ---- incremental interface ------------------------------------------------------------------
-    def begin(self, init=None):
+    def begin(self, init=None, init_device=None):
+        if init_device is not None:
+            check(self._lib.lpp_engine_lanczos_begin_device(self._h, C.c_void_p(int(init_device))))
+            return
         keep, ip = self._init_ptr(init)
         check(self._lib.lpp_engine_lanczos_begin(self._h, ip))
 
@@ -260,7 +296,184 @@ class LanczosEngine:
         return ms.value
 
 
+    # ---- observables of the Hubbard product basis (one GPU) -----------------------------------------
+    def _set_model(self, how, L, nup, ndown, hop, U, V, ninj, jcoup, comm):
+        self._model = None if comm is not None else dict(how=how, L=L, nup=nup, ndown=ndown, hop=np.array(hop, copy=True), U=np.array(U, copy=True),
+                                                         V=None if V is None else np.array(V, copy=True), ninj=None if ninj is None else np.array(ninj, copy=True),
+                                                         jcoup=None if jcoup is None else np.array(jcoup, copy=True))
+        for eng in self._sectors.values():
+            eng.close()
+        self._sectors = {}
+
+    def keep_states(self, k=1):
+        """Keep the lowest k Ritz vectors of the next lanczos() on the device, in the basis order (lpp_engine_keep_states)."""
+        check(self._lib.lpp_engine_keep_states(self._h, int(k)))
+
+    def state_device(self, k=0):
+        """(raw device address, length in elements) of resident state k"""
+        p, n = C.c_void_p(), C.c_int64()
+        check(self._lib.lpp_engine_state_device(self._h, int(k), C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def state(self, k=0):
+        """resident state k copied to the host"""
+        _, n = self.state_device(k)
+        out = np.zeros(n, self.np_dtype)
+        check(self._lib.lpp_engine_state_to_host(self._h, int(k), _vp(out)))
+        return out
+
+    def apply_operator(self, op, site, spin, L, nup, ndown, src, factor=1.0, out=None):
+        """Engine::accModifiedState_ (Engine.h:416-458) on the GPU: returns (z, (nup', ndown')) with z[bra] += factor*sign*value*src[ket],
+        z starting from `out` (new sector's length) or from zero; (None, None) where the operator leads to no sector.  src: host vector of the
+        (nup, ndown) sector in the basis order."""
+        oid = _op_id(op)
+        src = np.ascontiguousarray(src, self.np_dtype)
+        has, n1, n2 = C.c_int32(), C.c_int32(), C.c_int32()
+        nu, nd = C.c_int64(), C.c_int64()
+        check(self._lib.lpp_obs_plan(oid, site, spin, L, nup, ndown, C.byref(has), C.byref(n1), C.byref(n2), C.byref(nu), C.byref(nd), None, None))
+        if not has.value:
+            return None, None
+        if len(src) != sector_size(L, nup, ndown):
+            raise ValueError("src does not have the length of sector (%d, %d)" % (nup, ndown))
+        n = nu.value * nd.value
+        if out is None:
+            z = np.zeros(n, self.np_dtype)
+        else:
+            z = np.ascontiguousarray(out, self.np_dtype)
+            if len(z) != n:
+                raise ValueError("out does not have the length of sector (%d, %d)" % (n1.value, n2.value))
+        f = complex(factor)
+        check(self._lib.lpp_engine_apply_operator_host(self._h, oid, site, spin, L, nup, ndown, f.real, f.imag, _vp(src), _vp(z), int(out is not None), C.byref(has)))
+        return z, (n1.value, n2.value)
+
+    def bench_operator(self, op, site, spin, L, nup, ndown, warmup=2, iters=10):
+        """(ms per launch, bytes of the byte model) of the operator kernel on resident vectors"""
+        ms, by = C.c_double(), C.c_double()
+        check(self._lib.lpp_engine_bench_operator(self._h, _op_id(op), site, spin, L, nup, ndown, warmup, iters, C.byref(ms), C.byref(by)))
+        return ms.value, by.value
+
+    def _need_model(self, who):
+        if self._model is None:
+            raise _capi.LppError(_capi.LPP_ERR_STATE, "%s needs a single-GPU Hubbard engine set up by assemble_hubbard / setup_hubbard_onthefly" % who)
+        return self._model
+
+    def two_point(self, op, spins=(0, 0), bra=0, ket=0):
+        """Engine::twoPoint (Engine.h:266-338): (L x L matrix, trace) with result[i, j] = (A_j^{spins[1]} bra) . (A_i^{spins[0]} ket) for resident
+        states bra / ket (keep_states before lanczos); -100 everywhere where the operator leads to no sector."""
+        m = self._need_model("two_point")
+        L = m["L"]
+        res = np.zeros((L, L), self.np_dtype)
+        tr = np.zeros(1, self.np_dtype)
+        check(self._lib.lpp_engine_two_point(self._h, _op_id(op), int(spins[0]), int(spins[1]), L, m["nup"], m["ndown"], int(bra), int(ket), _vp(res), _vp(tr)))
+        return res, tr[0]
+
+    def _sector_engine(self, nup, ndown, solver):
+        eng = self._sectors.get((nup, ndown))
+        if eng is None:
+            m = self._model
+            eng = LanczosEngine(**self._ctor)
+            getattr(eng, m["how"])(m["L"], nup, ndown, m["hop"], m["U"], m["V"], ninj=m["ninj"], jcoup=m["jcoup"])
+            self._sectors[(nup, ndown)] = eng
+            self.sector_assemblies += 1
+        eng.set_solver(**solver)
+        return eng
+
+    def spectral_function(self, op, isite, jsite, spin=0, state=0, energy=None, max_steps=200, min_steps=4, eps=1e-12, reortho=False):
+        """Engine::spectralFunction (Engine.h:134-206) for one (operator, site pair, spin): a list of records, one per type 0..3 (odd types: the
+        operator, even types: its transpose-conjugate; a diagonal pair skips types 2 and 3; a type whose sector does not exist is skipped).
+        A record is the argument list of cf.set (:489): a, b, Eg, weight (= <modif|modif> * s2), sigma (= -s), plus type, label, steps,
+        ms_per_step and `assemblies` = sector Hamiltonians assembled by this engine so far (the N+-1 engines are kept, keyed by (nup, ndown)).
+        max_steps .. reortho: ParametersForSolver(io, "Spectral").  energy: Eg, default the lowest eigenvalue of the last lanczos()."""
+        m = self._need_model("spectral_function")
+        L, nup, ndown = m["L"], m["nup"], m["ndown"]
+        _op_id(op)
+        if op in ("n", "sz"):  # before any sector engine is assembled
+            raise _capi.LppError(_capi.LPP_ERR_INVALID, "spectral_function: operators that stay in the sector (n, sz) are not supported")
+        if energy is None:
+            if self._energies is None:
+                raise _capi.LppError(_capi.LPP_ERR_STATE, "spectral_function: run lanczos() first (after keep_states) or pass energy")
+            energy = float(self._energies[0])
+        op2 = _TRANSPOSE_CONJUGATE[op]
+        diagonal = isite == jsite
+        solver = dict(max_steps=max_steps, min_steps=min_steps, eps=eps, reortho=reortho, save_vectors=0)
+        records = []
+        for typ in range(4):  # LabeledOperator::numberOfTypes
+            if diagonal and typ > 1:
+                continue
+            o = op if (typ & 1) else op2
+            oid = OPERATORS[o]
+            has, c1, c2 = C.c_int32(), C.c_int32(), C.c_int32()
+            check(self._lib.lpp_obs_new_parts(oid, spin, L, nup, ndown, C.byref(has), C.byref(c1), C.byref(c2)))
+            if not has.value:
+                continue
+            n1, n2 = c1.value, c2.value
+            eng = self._sector_engine(n1, n2, solver)
+            a = np.zeros(max_steps + 2)
+            b = np.zeros(max_steps + 2)
+            n, w, st = C.c_int32(), C.c_double(), Stats()
+            isign = -1.0 if typ > 1 else 1.0
+            check(self._lib.lpp_engine_spectral_decomposition(self._h, int(state), eng._h, oid, isite, jsite, spin, isign, L, nup, ndown,
+                                                              C.byref(w), C.byref(n), _vp(a), _vp(b), C.byref(st)))
+            s = -1 if (typ & 1) else 1  # calcSpectral, Engine.h:481-489
+            s2 = -1.0 if typ > 1 else 1.0
+            if o not in _FERMIONIC:
+                s2 *= s
+            s2 *= 1.0 if diagonal else 0.5
+            records.append(dict(type=typ, label="%d,%d,0,0" % (spin, typ), a=a[:n.value].copy(), b=b[:n.value].copy(), Eg=energy, weight=w.value * s2,
+                                sigma=float(-s), modif_norm2=w.value, steps=n.value, sector=(n1, n2),
+                                ms_per_step=1e3 * st.seconds_total / max(st.steps_enqueued, 1), assemblies=self.sector_assemblies))
+        return records
+
+
 # ---- host-only helpers (no GPU) -------------------------------------------------------------------
+OP_NAMES = tuple(OPERATORS)
+
+
+def sector_size(L, nup, ndown):
+    from math import comb
+    return comb(L, nup) * comb(L, ndown)
+
+
+def new_parts(op, spin, L, nup, ndown):
+    """HubbardOneOrbital::hasNewParts: the new (nup, ndown), or None where the reference returns false (LPP_ERR_INVALID for n: it throws)."""
+    has, n1, n2 = C.c_int32(), C.c_int32(), C.c_int32()
+    check(_capi.lib().lpp_obs_new_parts(_op_id(op), spin, L, nup, ndown, C.byref(has), C.byref(n1), C.byref(n2)))
+    return (n1.value, n2.value) if has.value else None
+
+
+def operator_plan(op, site, spin, L, nup, ndown):
+    """The plan of one operator application (lpp_obs_plan): None where the operator leads to no sector, else a dict with the new sector and the two
+    per-species tables, table[destination species rank] = +-(source species rank + 1) or 0 (for sz: the two occupancy tables)."""
+    lib = _capi.lib()
+    oid = _op_id(op)
+    has, n1, n2 = C.c_int32(), C.c_int32(), C.c_int32()
+    nu, nd = C.c_int64(), C.c_int64()
+    check(lib.lpp_obs_plan(oid, site, spin, L, nup, ndown, C.byref(has), C.byref(n1), C.byref(n2), C.byref(nu), C.byref(nd), None, None))
+    if not has.value:
+        return None
+    tu, td = np.zeros(nu.value, np.int32), np.zeros(nd.value, np.int32)
+    check(lib.lpp_obs_plan(oid, site, spin, L, nup, ndown, C.byref(has), C.byref(n1), C.byref(n2), C.byref(nu), C.byref(nd), _vp(tu), _vp(td)))
+    return dict(nup=n1.value, ndown=n2.value, table_up=tu, table_down=td)
+
+
+def continued_fraction(record, z):
+    """G(z) = w / (z + sigma (a_0 - Eg) - b_0^2 / (z + sigma (a_1 - Eg) - ...)) for a record of spectral_function (or any mapping with a, b, Eg,
+    weight, sigma); b_k is the decomposition's coefficient at index k, the one that couples Lanczos vectors k and k+1.  The project's own
+    convention: PsimagLite's ContinuedFraction was not at hand to compare with.  z: scalar or array of complex frequencies."""
+    a = np.ascontiguousarray(record["a"], np.float64)
+    b = np.ascontiguousarray(record["b"], np.float64)
+    if len(b) < len(a):
+        b = np.concatenate([b, np.zeros(len(a) - len(b))])
+    zs = np.atleast_1d(np.asarray(z, np.complex128))
+    out = np.zeros(zs.shape, np.complex128)
+    o = np.zeros(2)
+    lib = _capi.lib()
+    for k, zz in enumerate(zs.ravel()):
+        check(lib.lpp_continued_fraction(len(a), _vp(a), _vp(b), float(record["Eg"]), float(record["weight"]), float(record["sigma"]), zz.real, zz.imag, _vp(o)))
+        out.ravel()[k] = complex(o[0], o[1])
+    return out if np.ndim(z) else out[0]
+
+
 def partition_rows(nrows, nranks, block=1):
     starts = np.zeros(nranks + 1, np.int64)
     check(_capi.lib().lpp_partition_rows(nrows, nranks, block, _vp(starts)))

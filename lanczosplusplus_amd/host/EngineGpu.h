@@ -4,13 +4,19 @@
 //   InternalProductStored  src/Engine/InternalProductStored.h:93-132 (rows(), matrixVectorProduct: x += H y)
 //   ParametersForSolver    [PsimagLite] as used at src/Engine/Engine.h:609 and src/SpinOrbital.cpp:213-216
 //   LanczosSolver          [PsimagLite] computeAllStatesBelow / decomposition / computeOneState
-//   Engine                 src/Engine/Engine.h:84-98,601-657 (only the ground-state part)
+//   Engine                 src/Engine/Engine.h:84-98,601-657 (ground state), :134-206 spectralFunction, :266-338 twoPoint
+//   LabeledOperator        src/Engine/LabeledOperator.h:10-119
+//   ContinuedFraction(Collection)  [PsimagLite] as used at Engine.h:188,204,489 and LanczosDriver1.h:147-179 (this project's own text layout)
 // The device boundary sits between Engine and the solver: the CSR is uploaded once by
 // InternalProductStored, the whole Lanczos loop runs on the GPU.  Errors surface as std::runtime_error.
 #ifndef LPP_HOST_ENGINE_GPU_H
 #define LPP_HOST_ENGINE_GPU_H
 
+#include <fstream>
+#include <iomanip>
 #include <iostream>
+#include <map>
+#include <memory>
 
 #include "../../include/lpp_engine.h"
 #include "Models.h"
@@ -339,6 +345,102 @@ private:
 	SizeType steps_ = 0;
 };
 
+// LabeledOperator (LabeledOperator.h:10-119): the operator names of -g / -c, numbered as LPP_OP_*
+class LabeledOperator {
+public:
+	explicit LabeledOperator(const LppHost::String& s) : id_(toId(s)) { }
+	explicit LabeledOperator(int id) : id_(id) { }
+	int id() const { return id_; }
+	LppHost::String toString() const
+	{
+		static const char* names[] = { "", "c", "sz", "cdagger", "n", "splus", "sminus" };
+		return names[id_];
+	}
+	bool needsNewBasis() const { return id_ != LPP_OP_N && id_ != LPP_OP_SZ; } // :83-90
+	bool isFermionic() const { return id_ == LPP_OP_C || id_ == LPP_OP_CDAGGER; } // :100-105
+	SizeType numberOfTypes() const { return 4; }
+	LabeledOperator transposeConjugate() const // :107-119
+	{
+		switch (id_) {
+		case LPP_OP_C: return LabeledOperator(LPP_OP_CDAGGER);
+		case LPP_OP_CDAGGER: return LabeledOperator(LPP_OP_C);
+		case LPP_OP_SPLUS: return LabeledOperator(LPP_OP_SMINUS);
+		case LPP_OP_SMINUS: return LabeledOperator(LPP_OP_SPLUS);
+		default: return *this;
+		}
+	}
+
+private:
+	static int toId(const LppHost::String& s) // :36-59
+	{
+		if (s == "c") return LPP_OP_C;
+		if (s == "sz") return LPP_OP_SZ;
+		if (s == "cdagger") return LPP_OP_CDAGGER;
+		if (s == "n") return LPP_OP_N;
+		if (s == "splus") return LPP_OP_SPLUS;
+		if (s == "sminus") return LPP_OP_SMINUS;
+		throw std::runtime_error("LabeledOperator: unsupported operator " + s + " (c, cdagger, n, sz, splus, sminus)\n");
+	}
+	int id_;
+};
+
+// One record of a spectral function: the argument list of cf.set (Engine.h:489) and, through lpp_continued_fraction, its value at complex z.
+// The text layout written here is this project's own; PsimagLite's writer was not available to compare with.
+class ContinuedFraction {
+public:
+	typedef TridiagonalMatrix TridiagonalMatrixType;
+	void set(const TridiagonalMatrix& ab, double Eg, double weight, int isign)
+	{
+		ab_ = ab;
+		Eg_ = Eg;
+		weight_ = weight;
+		isign_ = isign;
+	}
+	std::complex<double> operator()(const std::complex<double>& z) const
+	{
+		double out[2] = { 0, 0 };
+		lppCheck(lpp_continued_fraction((int32_t)ab_.size(), ab_.a_.data(), ab_.b_.data(), Eg_, weight_, (double)isign_, z.real(), z.imag(), out));
+		return std::complex<double>(out[0], out[1]);
+	}
+	void write(std::ostream& os) const
+	{
+		os << std::setprecision(17);
+		os << "#Avector " << ab_.size();
+		for (SizeType k = 0; k < ab_.size(); k++) os << " " << ab_.a(k);
+		os << "\n#Bvector " << ab_.size();
+		for (SizeType k = 0; k < ab_.size(); k++) os << " " << ab_.b(k);
+		os << "\n#CFEnergy=" << Eg_ << "\n#CFWeight=" << weight_ << "\n#CFIsign=" << isign_ << "\n";
+	}
+	const TridiagonalMatrix& ab() const { return ab_; }
+	double energy() const { return Eg_; }
+	double weight() const { return weight_; }
+	int isign() const { return isign_; }
+
+private:
+	TridiagonalMatrix ab_;
+	double Eg_ = 0, weight_ = 0;
+	int isign_ = 1;
+};
+
+template <typename ContinuedFractionType_> class ContinuedFractionCollection {
+public:
+	typedef ContinuedFractionType_ ContinuedFractionType;
+	void push(const ContinuedFractionType& cf) { data_.push_back(cf); }
+	SizeType size() const { return data_.size(); }
+	const ContinuedFractionType& operator[](SizeType k) const { return data_[k]; }
+	void write(std::ostream& os) const
+	{
+		os << "#ContinuedFractionCollection=" << data_.size() << "\n";
+		for (SizeType k = 0; k < data_.size(); k++) {
+			os << "#ContinuedFraction=" << k << "\n";
+			data_[k].write(os);
+		}
+	}
+
+private:
+	std::vector<ContinuedFractionType> data_;
+};
+
 // deterministic stand-in for PsimagLite::fillRandom (Engine.h:621): splitmix64 -> uniform(-0.5, 0.5), seed 1234
 template <typename VectorType> void fillRandom(VectorType& v, uint64_t seed = 1234)
 {
@@ -379,8 +481,139 @@ public:
 	SizeType lanczosSteps() const { return steps_; }
 	SizeType sector() const { return sector_; } // the symmetry sector the returned states live in
 	bool usedFullDiag() const { return usedFullDiag_; }
+	typedef std::pair<SizeType, SizeType> PairType;
+	typedef std::vector<LppHost::String> VectorStringType;
+	typedef LabeledOperator LabeledOperatorType;
+	// N +- 1 sector Hamiltonians assembled so far by spectralFunction: they are kept, keyed by (nup, ndown) (the reference re-assembles per call, :186-187)
+	SizeType sectorAssemblies() const { return sectorAssemblies_; }
+
+	// Engine::twoPoint for a list of spin pairs (Engine.h:251-261)
+	void twoPoint(LppHost::Matrix<ComplexOrRealType>& result, const LabeledOperatorType& lOperator, const std::vector<PairType>& spins, const PairType& orbs,
+	              const PairType& braAndKet) const
+	{
+		for (SizeType i = 0; i < spins.size(); i++) {
+			std::cout << "spins=" << spins[i].first << " " << spins[i].second << "\n";
+			twoPoint(result, lOperator, spins[i], orbs, braAndKet);
+		}
+	}
+
+	// Engine::twoPoint (Engine.h:266-338) on the resident states of the GPU engine: result(i, j) = (A_j^{spins.second} bra) . (A_i^{spins.first} ket),
+	// -100 where the operator leads to no sector, the trace printed as MatrixDiagonal (:337)
+	void twoPoint(LppHost::Matrix<ComplexOrRealType>& result, const LabeledOperatorType& lOperator, const PairType& spins, const PairType& orbs,
+	              const PairType& braAndKet) const
+	{
+		lpp_engine* e = observableEngine("twoPoint");
+		if (orbs.first != 0 || orbs.second != 0) throw std::runtime_error("twoPoint: one orbital only\n");
+		checkBraOrKet("bra", braAndKet.first);
+		checkBraOrKet("ket", braAndKet.second);
+		const SizeType total = model_.geometry().numberOfSites();
+		if (result.n_row() != total || result.n_col() != total) result.resize(total, total);
+		const typename ModelType::BasisBaseType::PairIntType parts = model_.basis().parts();
+		std::vector<ComplexOrRealType> flat(total * total);
+		ComplexOrRealType sum = 0;
+		std::cout << "orbs=" << orbs.first << " " << orbs.second << "\n";
+		lppCheck(lpp_engine_two_point(e, lOperator.id(), (int32_t)spins.first, (int32_t)spins.second, (int32_t)total, (int32_t)parts.first, (int32_t)parts.second,
+		                              (int32_t)braAndKet.first, (int32_t)braAndKet.second, flat.data(), &sum));
+		for (SizeType i = 0; i < total; i++)
+			for (SizeType j = 0; j < total; j++) result(i, j) = flat[i * total + j];
+		std::cout << "MatrixDiagonal = " << sum << "\n";
+	}
+
+	// Engine::spectralFunction for a list of spin pairs, as the driver calls it (LanczosDriver1.h:165-171)
+	template <typename ContinuedFractionCollectionType>
+	void spectralFunction(ContinuedFractionCollectionType& cfCollection, VectorStringType& vstr, const LabeledOperatorType& lOperator1, int isite, int jsite,
+	                      const std::vector<PairType>& spins, const PairType& orbs) const
+	{
+		for (SizeType i = 0; i < spins.size(); i++) spectralFunction(cfCollection, vstr, lOperator1, isite, jsite, spins[i], orbs);
+	}
+
+	// Engine::spectralFunction (Engine.h:134-206): per type the modified state is built on the device from the resident ground state, the engine of
+	// the operator's sector (device-assembled once from the model's parameters) decomposes it with the Spectral solver parameters (calcSpectral :460-490)
+	template <typename ContinuedFractionCollectionType>
+	void spectralFunction(ContinuedFractionCollectionType& cfCollection, VectorStringType& vstr, const LabeledOperatorType& lOperator1, int isite, int jsite,
+	                      const PairType& spins, const PairType& orbs) const
+	{
+		typedef typename ContinuedFractionCollectionType::ContinuedFractionType ContinuedFractionType;
+		if (spins.first != spins.second) throw std::runtime_error("spectralFunction: no support yet for off-diagonal spin\n");
+		if (orbs.first != 0 || orbs.second != 0) throw std::runtime_error("spectralFunction: one orbital only\n");
+		lpp_engine* e = observableEngine("spectralFunction");
+		const LabeledOperatorType lOperator2 = lOperator1.transposeConjugate();
+		// refused before any sector engine is assembled
+		if (!lOperator1.needsNewBasis()) throw std::runtime_error("spectralFunction: operators that stay in the sector (n, sz) are not supported\n");
+		const int n = (int)model_.geometry().numberOfSites();
+		if (isite < 0 || jsite < 0 || isite >= n || jsite >= n) throw std::runtime_error("spectralFunction: site out of range\n");
+		const bool isDiagonal = (isite == jsite);
+		const typename ModelType::BasisBaseType::PairIntType oldParts = model_.basis().parts();
+		ParametersForSolverType params(io_, "Spectral");
+		for (SizeType type = 0; type < lOperator1.numberOfTypes(); ++type) {
+			if (isDiagonal && type > 1) continue;
+			const LabeledOperatorType& lOperator = (type & 1) ? lOperator1 : lOperator2;
+			int32_t has = 0, nup2 = 0, ndown2 = 0;
+			lppCheck(lpp_obs_new_parts(lOperator.id(), (int32_t)spins.first, n, (int32_t)oldParts.first, (int32_t)oldParts.second, &has, &nup2, &ndown2));
+			if (!has) continue;
+			lpp_engine* sector = sectorEngine(nup2, ndown2, params);
+			TridiagonalMatrixType ab;
+			ab.resize(params.steps + 2);
+			double weight = 0;
+			int32_t nsteps = 0;
+			lppCheck(lpp_engine_spectral_decomposition(e, 0, sector, lOperator.id(), isite, jsite, (int32_t)spins.first, type > 1 ? -1.0 : 1.0, n, (int32_t)oldParts.first,
+			                                           (int32_t)oldParts.second, &weight, &nsteps, &ab.a(0), &ab.b(0), nullptr));
+			ab.a_.resize(nsteps);
+			ab.b_.resize(nsteps);
+			if (std::sqrt(weight) < 1e-10) std::cerr << "spectralFunction: modifVector==0, type=" << type << "\n";
+			const int s = (type & 1) ? -1 : 1; // calcSpectral, Engine.h:481-489
+			RealType s2 = (type > 1) ? -1 : 1;
+			if (!lOperator.isFermionic()) s2 *= s;
+			s2 *= isDiagonal ? 1 : 0.5;
+			ContinuedFractionType cf;
+			cf.set(ab, energies_[0], weight * s2, -s);
+			vstr.push_back(std::to_string(spins.first) + "," + std::to_string(type) + "," + std::to_string(orbs.first) + "," + std::to_string(orbs.second));
+			cfCollection.push(cf);
+		}
+	}
 
 private:
+	void checkBraOrKet(const char* what, SizeType ind) const
+	{
+		if (ind >= vectors_.size()) throw std::runtime_error(std::string("Engine: ") + what + " index exceeds the states computed (Excited=)\n");
+	}
+
+	// the GPU engine that holds the resident states: the Hubbard family on one GPU, a one-sector symmetry, states from the device solver
+	lpp_engine* observableEngine(const char* who) const
+	{
+		if (!hubbard() || !hamiltonian_ || !statesResident_)
+			throw std::runtime_error(std::string(who) + ": needs a Model of the HubbardOneOrbital family solved by the GPU Lanczos (no symmetry sectors, no dense fallback)\n");
+		return hamiltonian_->engine();
+	}
+
+	const HubbardOneOrbital<ComplexOrRealType>* hubbard() const { return dynamic_cast<const HubbardOneOrbital<ComplexOrRealType>*>(&model_); }
+
+	lpp_engine* sectorEngine(int nup, int ndown, const ParametersForSolverType& params) const
+	{
+		std::unique_ptr<EngineHandle>& slot = sectorEngines_[PairType(nup, ndown)];
+		if (!slot) {
+			const HubbardOneOrbital<ComplexOrRealType>* hub = hubbard();
+			const SizeType n = model_.geometry().numberOfSites();
+			std::vector<double> hr(n * n), hi(n * n);
+			for (SizeType k = 0; k < n * n; k++) {
+				hr[k] = LppHost::real(hub->hoppings()[k]);
+				hi[k] = LppHost::imag(hub->hoppings()[k]);
+			}
+			lpp_config cfg;
+			lpp_config_default(&cfg);
+			cfg.device = device_;
+			cfg.dtype = LppDtype<ComplexOrRealType>::value;
+			std::unique_ptr<EngineHandle> fresh(new EngineHandle(cfg));
+			lppCheck(lpp_engine_assemble_hubbard_super(fresh->get(), nullptr, (int32_t)n, nup, ndown, hr.data(), sizeof(ComplexOrRealType) == 16 ? hi.data() : nullptr,
+			                                           hub->hubbardU.data(), hub->potentialEffective.data(), hub->coulombCoupling(), hub->jCoupling()));
+			slot.swap(fresh);
+			sectorAssemblies_++;
+		}
+		const bool reortho = params.options.find("reortho") != LppHost::String::npos;
+		lppCheck(lpp_engine_set_solver(slot->get(), (int32_t)params.steps, (int32_t)params.minSteps, params.tolerance, reortho ? 1 : 0, 0));
+		return slot->get();
+	}
+
 	// What one symmetry sector yields: its lowest levels and their vectors (sector-local), from the device solver or -- when that
 	// throws -- from the dense fallback of the reference (Engine.h:627-639).
 	struct SectorStates {
@@ -423,9 +656,14 @@ private:
 		lpp_config_default(&cfg);
 		cfg.device = device_;
 		cfg.dtype = LppDtype<ComplexOrRealType>::value;
-		SpecialSymmetryType rs(model_.basis(), model_.geometry(), "");
-		InternalProductType hamiltonian(model_, rs, cfg);
+		// the symmetry and the matrix object outlive this call: the GPU engine keeps the states resident for twoPoint / spectralFunction
+		rs_.reset(new SpecialSymmetryType(model_.basis(), model_.geometry(), ""));
+		hamiltonian_.reset(new InternalProductType(model_, *rs_, cfg));
+		SpecialSymmetryType& rs = *rs_;
+		InternalProductType& hamiltonian = *hamiltonian_;
 		LanczosSolverType lanczosSolver(hamiltonian, params); // pushes params into the engine
+		const bool keep = hubbard() && rs.sectors() == 1;
+		if (keep) lppCheck(lpp_engine_keep_states(hamiltonian.engine(), (int32_t)nstates));
 		energies_.assign(nstates, 0);
 		vectors_.assign(nstates, VectorType());
 		bool have = false;
@@ -445,6 +683,7 @@ private:
 			rowsBefore += dim;
 		}
 		rs.transform(vectors_, bestOffset); // Engine.h:654
+		statesResident_ = keep && have && !usedFullDiag_;
 		for (SizeType k = 0; k < nstates; k++) { // printEnergiesAndNorms, Engine.h:666-674
 			RealType nrm = 0;
 			for (const ComplexOrRealType& z : vectors_[k]) nrm += LppHost::real(z * LppHost::conj(z));
@@ -457,7 +696,11 @@ private:
 	VectorRealType energies_;
 	VectorVectorType vectors_;
 	SizeType steps_ = 0, sector_ = 0;
-	bool usedFullDiag_ = false;
+	bool usedFullDiag_ = false, statesResident_ = false;
+	std::unique_ptr<SpecialSymmetryType> rs_;
+	std::unique_ptr<InternalProductType> hamiltonian_;
+	mutable std::map<PairType, std::unique_ptr<EngineHandle>> sectorEngines_;
+	mutable SizeType sectorAssemblies_ = 0;
 };
 
 } // namespace LanczosPlusPlus

@@ -1,9 +1,10 @@
 // lanczos.cpp -- driver with the reference's command line for this path (src/lanczos.cpp:99-226,
 // src/Engine/LanczosDriver1.h:47-66): reads an InputNg-style file (the reference's TestSuite inputs work
 // unmodified for the in-scope models), builds the model, runs the GPU engine, prints "Energy=".
-//   lanczos -f input.inp [-p precision] [-d device]
-// SolverOptions=useComplex selects complex<double> (lanczos.cpp:194-226).  Observables (-g, -c, -m, ...)
-// are out of scope.
+//   lanczos -f input.inp [-p precision] [-d device] [-g operator] [-c operator] [-s "s1,s2;..."]
+// SolverOptions=useComplex selects complex<double> (lanczos.cpp:194-226).  -c prints the two-point matrix of the ground state, -g writes the
+// continued fractions of the spectral function for the site pairs the input names (TSPSites, TSPCenter=, DoAllPairs=,
+// ComputeDensityOfStates=) into <input basename><counter>.comb (LanczosDriver1.h:81-199; Hubbard family, one GPU).  -m, -r, -M are out of scope.
 #include <getopt.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -12,26 +13,144 @@
 #include <cstdlib>
 #include <cstring>
 #include <ctime>
+#include <fstream>
 #include <iostream>
+#include <sstream>
 
 #include "../../include/lpp_comm_rccl.h"
 #include "EngineGpu.h"
 
 using namespace LanczosPlusPlus;
 
-// mainLoop3 (LanczosDriver1.h:47-66): build the engine, print the ground-state energy
+// LanczosOptions (src/Engine/LanczosOptions.h): what -g, -c and -s collect
+struct LanczosOptions {
+	typedef std::pair<SizeType, SizeType> PairSizeType;
+	LanczosOptions() : spins(1, PairSizeType(0, 0)) { }
+	std::vector<LabeledOperator> gf, cicj;
+	std::vector<SizeType> sites;
+	std::vector<PairSizeType> spins;
+};
+
+// -s "s1,s2;s1,s2;..." (lanczos.cpp:17-34, :147-152)
+static void fillSpins(std::vector<LanczosOptions::PairSizeType>& spins, const LppHost::String& arg)
+{
+	spins.clear();
+	std::istringstream all(arg);
+	LppHost::String item;
+	while (std::getline(all, item, ';')) {
+		const SizeType comma = item.find(',');
+		if (comma == LppHost::String::npos) throw std::runtime_error("-s needs pairs \"s1,s2\" separated by ;\n");
+		const int s1 = atoi(item.substr(0, comma).c_str()), s2 = atoi(item.substr(comma + 1).c_str());
+		if (s1 < 0 || s1 > 1 || s2 < 0 || s2 > 1) throw std::runtime_error("-s: a spin is 0 (up) or 1 (down)\n");
+		spins.push_back(LanczosOptions::PairSizeType(s1, s2));
+	}
+	if (spins.empty()) throw std::runtime_error("-s: no spin pair given\n");
+}
+
+static LppHost::String basenameOf(const LppHost::String& path)
+{
+	const SizeType slash = path.find_last_of('/');
+	return slash == LppHost::String::npos ? path : path.substr(slash + 1);
+}
+
+// PsimagLite::Matrix's operator<< as the reference's driver uses it (LanczosDriver1.h:196): "rows cols", then one row per line
+template <typename T> static void printMatrix(std::ostream& os, const LppHost::Matrix<T>& m)
+{
+	os << m.n_row() << " " << m.n_col() << "\n";
+	for (SizeType i = 0; i < m.n_row(); i++) {
+		for (SizeType j = 0; j < m.n_col(); j++) os << m(i, j) << " ";
+		os << "\n";
+	}
+}
+
+// mainLoop3 (LanczosDriver1.h:47-199): build the engine, print the ground-state energy, then the observables asked for
 template <typename ModelType, typename SymmetryType, template <typename, typename> class InternalProductTemplate>
-int mainLoop3(const ModelType& model, LppHost::InputReadable& io, int device, int precision)
+int mainLoop3(const ModelType& model, LppHost::InputReadable& io, int device, int precision, LanczosOptions& lanczosOptions)
 {
 	typedef Engine<ModelType, InternalProductTemplate, SymmetryType> EngineType;
+	typedef typename ModelType::ComplexOrRealType ComplexOrRealType;
+	typedef LanczosOptions::PairSizeType PairSizeType;
 	std::cout.precision(precision);
 	EngineType engine(model, io, device);
 	std::cout << "Energy=" << engine.energies(0) << "\n";
 	std::cerr << "#LanczosSteps=" << engine.lanczosSteps() << " rows=" << model.size() << "\n";
+	const LppHost::String filename = basenameOf(io.filename());
+	const SizeType n = model.geometry().numberOfSites();
+
+	// the site pairs of -g (LanczosDriver1.h:81-136)
+	bool needsDos = false;
+	if (io.has("ComputeDensityOfStates=")) {
+		int tmp = 0;
+		io.readline(tmp, "ComputeDensityOfStates=");
+		needsDos = (tmp > 0);
+	}
+	std::vector<PairSizeType> pairOfSites;
+	if (needsDos) {
+		lanczosOptions.gf.push_back(LabeledOperator("c"));
+		for (SizeType i = 0; i < n; ++i) pairOfSites.push_back(PairSizeType(i, i));
+	}
+	if (io.has("TSPSites")) {
+		io.read(lanczosOptions.sites, "TSPSites");
+		if (lanczosOptions.sites.size() == 0) throw std::runtime_error("TSPSites must have at least one site\n");
+		if (lanczosOptions.sites.size() == 1) lanczosOptions.sites.push_back(lanczosOptions.sites[0]);
+		pairOfSites.push_back(PairSizeType(lanczosOptions.sites[0], lanczosOptions.sites[1]));
+	}
+	bool hasCenter = false;
+	SizeType centerSite = 0;
+	if (io.has("TSPCenter=")) {
+		io.readline(centerSite, "TSPCenter=");
+		std::cout << "TSPCenter=" << centerSite << "\n";
+		for (SizeType i = 0; i < n; ++i) pairOfSites.push_back(PairSizeType(centerSite, i));
+		hasCenter = true;
+	}
+	bool doAllPairs = false;
+	if (io.has("DoAllPairs=")) {
+		int tmp = 0;
+		io.readline(tmp, "DoAllPairs=");
+		doAllPairs = (tmp > 0);
+	}
+	if (doAllPairs && hasCenter) throw std::runtime_error("You cannot have both TSPCenter and DoAllPairs\n");
+	if (doAllPairs)
+		for (SizeType i = 0; i < n; ++i)
+			for (SizeType j = 0; j < n; ++j) pairOfSites.push_back(PairSizeType(i, j));
+
+	// -g (LanczosDriver1.h:138-183): one .comb file per site pair, in the working directory
+	for (SizeType gfi = 0; gfi < lanczosOptions.gf.size(); ++gfi) {
+		SizeType counter = 0;
+		for (SizeType sIndex = 0; sIndex < pairOfSites.size(); ++sIndex) {
+			const SizeType site0 = pairOfSites[sIndex].first, site1 = pairOfSites[sIndex].second;
+			std::cout << "#gf(i=" << site0 << ", j=" << site1 << ")\n";
+			typename EngineType::VectorStringType vstr;
+			ContinuedFractionCollection<ContinuedFraction> cfCollection;
+			engine.spectralFunction(cfCollection, vstr, lanczosOptions.gf[gfi], (int)site0, (int)site1, lanczosOptions.spins, PairSizeType(0, 0));
+			const LppHost::String outName = filename + std::to_string(counter) + ".comb";
+			std::ofstream ioOut(outName.c_str());
+			if (!ioOut) throw std::runtime_error("lanczos: cannot write " + outName + "\n");
+			ioOut << "Site0=" << site0 << "\n";
+			ioOut << "Site1=" << site1 << "\n";
+			if (hasCenter) ioOut << "TSPCenter=" << centerSite << "\n";
+			ioOut << "#INDEXTOCF ";
+			for (SizeType i = 0; i < vstr.size(); ++i) ioOut << vstr[i] << " ";
+			ioOut << "\n";
+			cfCollection.write(ioOut);
+			ioOut.close();
+			if (!ioOut) throw std::runtime_error("lanczos: cannot write " + outName + "\n");
+			std::cerr << "lanczos: Written to " << outName << "\n";
+			++counter;
+		}
+	}
+	if (lanczosOptions.gf.size() > 0) std::cerr << "#SectorAssemblies=" << engine.sectorAssemblies() << "\n";
+
+	// -c (LanczosDriver1.h:185-199)
+	for (SizeType cicji = 0; cicji < lanczosOptions.cicj.size(); cicji++) {
+		LppHost::Matrix<ComplexOrRealType> cicjMatrix(n, n);
+		engine.twoPoint(cicjMatrix, lanczosOptions.cicj[cicji], lanczosOptions.spins, PairSizeType(0, 0), PairSizeType(0, 0));
+		printMatrix(std::cout, cicjMatrix);
+	}
 	return 0;
 }
 
-template <typename ComplexOrRealType> int mainLoop0(LppHost::InputReadable& io, int device, int precision, bool onthefly)
+template <typename ComplexOrRealType> int mainLoop0(LppHost::InputReadable& io, int device, int precision, bool onthefly, LanczosOptions& lanczosOptions)
 {
 	typedef LppHost::Geometry<ComplexOrRealType> GeometryType;
 	typedef ModelBase<ComplexOrRealType> ModelType;
@@ -41,8 +160,8 @@ template <typename ComplexOrRealType> int mainLoop0(LppHost::InputReadable& io, 
 	const ModelType& model = modelSelector();
 	model.print(std::cout);
 	// stored / on-the-fly switch on the SolverOptions substring (LanczosDriver1.h:217-239)
-	if (onthefly) return mainLoop3<ModelType, SymmetryType, InternalProductOnTheFly>(model, io, device, precision);
-	return mainLoop3<ModelType, SymmetryType, InternalProductStored>(model, io, device, precision);
+	if (onthefly) return mainLoop3<ModelType, SymmetryType, InternalProductOnTheFly>(model, io, device, precision, lanczosOptions);
+	return mainLoop3<ModelType, SymmetryType, InternalProductStored>(model, io, device, precision, lanczosOptions);
 }
 
 static int envInt(const char* name, int dflt)
@@ -249,27 +368,38 @@ int main(int argc, char** argv)
 	LppHost::String file;
 	int device = 0, precision = 8, opt = 0;
 	bool partitioned = false;
-	while ((opt = getopt(argc, argv, "f:p:d:P")) != -1) {
+	const char* usage = " -f filename [-p precision] [-d device] [-P] [-g operator] [-c operator] [-s \"s1,s2;...\"]\n";
+	LanczosOptions lanczosOptions;
+	LppHost::String spinsArg;
+	std::vector<LppHost::String> gfArgs, cicjArgs;
+	while ((opt = getopt(argc, argv, "f:p:d:Pg:c:s:")) != -1) {
 		switch (opt) {
 		case 'f': file = optarg; break;
+		case 'g': gfArgs.push_back(optarg); break;
+		case 'c': cicjArgs.push_back(optarg); break;
+		case 's': spinsArg = optarg; break;
 		case 'p': precision = atoi(optarg); break;
 		case 'd': device = atoi(optarg); break;
 		case 'P': partitioned = true; break;
-		default: std::cerr << "USAGE: " << argv[0] << " -f filename [-p precision] [-d device] [-P]\n"; return 1;
+		default: std::cerr << "USAGE: " << argv[0] << usage; return 1;
 		}
 	}
 	if (file.empty()) {
-		std::cerr << "USAGE: " << argv[0] << " -f filename [-p precision] [-d device] [-P]\n";
+		std::cerr << "USAGE: " << argv[0] << usage;
 		return 1;
 	}
 	try {
+		for (const LppHost::String& g : gfArgs) lanczosOptions.gf.push_back(LabeledOperator(g));
+		for (const LppHost::String& c : cicjArgs) lanczosOptions.cicj.push_back(LabeledOperator(c));
+		if (!spinsArg.empty()) fillSpins(lanczosOptions.spins, spinsArg);
+		if (partitioned && (!gfArgs.empty() || !cicjArgs.empty())) throw std::runtime_error("-g / -c run on one GPU: not with -P\n");
 		LppHost::InputReadable io(file);
 		LppHost::String options("none");
 		if (io.has("SolverOptions=")) io.readline(options, "SolverOptions=");
 		const bool onthefly = options.find("InternalProductOnTheFly") != LppHost::String::npos;
 		const bool isComplex = options.find("useComplex") != LppHost::String::npos;
 		if (partitioned) return isComplex ? mainPartitioned<std::complex<double>>(io, precision, onthefly) : mainPartitioned<double>(io, precision, onthefly);
-		return isComplex ? mainLoop0<std::complex<double>>(io, device, precision, onthefly) : mainLoop0<double>(io, device, precision, onthefly);
+		return isComplex ? mainLoop0<std::complex<double>>(io, device, precision, onthefly, lanczosOptions) : mainLoop0<double>(io, device, precision, onthefly, lanczosOptions);
 	} catch (std::exception& e) {
 		std::cerr << "lanczos: " << e.what();
 		return 2;
