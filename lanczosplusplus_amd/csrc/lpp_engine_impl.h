@@ -139,6 +139,12 @@ struct PbState {
 	size_t down_lds_pf = 0; // k_pb_down's PF form: the image plus the task sums
 	int32_t* order = nullptr; // blocks of every workgroup's range by decreasing list length
 	int* pace = nullptr;
+	// launch forms, resolved at the end of pb_build from the LPP_PB_* launch switches and from what was built; the launches read only these
+	bool chain_ok = false; // the chained scale-free step serves this layout (LPP_PB_CHAIN; pb_chain_ok adds: no plain-stream diagonal)
+	bool down_tasks = false; // plain coupling kernel: tasks handed out by the LDS counter, no pacing (LPP_PB_DOWN_TASKS)
+	bool down_pf = false; // chained coupling kernel: the counter form with the u lines touched ahead (LPP_PB_DOWN_PF)
+	bool chain_drop_pace = false; // ... and without the pacing (LPP_PB_CHAIN_PACE=1 keeps it)
+	bool lazy_tx = false; // transposition exchange: the update rides in the next step's pack kernel (LPP_PB_LAZY_TX)
 	double* z = nullptr; // alpha C y of the product in flight (n_blk * pitch doubles)
 	double* u = nullptr; // alpha (T y + D y) of the product in flight
 	double* xy = nullptr; // device scalar: Re<x|y> left by the last combine pass = the next step's <y | x_old>
@@ -288,6 +294,7 @@ struct lpp_engine {
 	double* ycur = nullptr; // current Lanczos vector (V column or e->y)
 	double* xcur = nullptr; // accumulator vector of the recurrence (e->x, or e->y/e->x alternating when scale-free)
 	bool scalefree = false; // unnormalised Lanczos vectors, scalings folded into the SpMV epilogue (no swap pass)
+	bool fused_allreduce = true; // transposition exchange, scale-free: a_j and b_j^2 share one all-reduce (LPP_FUSED_ALLREDUCE, read per run)
 	std::vector<hipEvent_t> step_events;
 	std::vector<std::pair<hipEvent_t, hipEvent_t>> spmv_events;
 	std::vector<int> spmv_event_cols; // per bracket: 0 = a product, > 0 = a blocked Gram-Schmidt call against that many columns
@@ -358,7 +365,8 @@ lpp_status pb_chain(lpp_engine* e, const AsmParams& P, int L, int n, const std::
 lpp_status assemble_heisenberg_raw(lpp_engine* e, int L, int m, const double* jpm, const double* jzz, const double* field, int nfield, DevCsr& A);
 int pb_launch(lpp_engine* e, const void* y, void* x, double* partial, const EpiScale& sc = EpiScale { nullptr, nullptr, 0 }, bool defer_combine = false);
 // the streaming pass of the scale-free Lanczos step on a product-basis matrix: x = beta x + u + z - (a/b2_prev) y, |x|^2 partials
-bool pb_chain_ok(const lpp_engine* e);
+bool pb_chain_ok(const lpp_engine* e); // PbState::chain_ok and no plain-stream diagonal
+// (pb_launch_chain: a negative count means the state is not one the chained kernels serve; nothing was launched)
 void pb_tx_up(lpp_engine* e, const void* y, const EpiScale& sc, int64_t b0, int64_t cnt);
 void pb_tx_down(lpp_engine* e, const void* gath, void* send2, const EpiScale& sc);
 int pb_tx_unpack_combine(lpp_engine* e, void* x, const void* y, const void* recv2, const EpiScale& sc, int64_t chunk, double* partial, const double* shift);

@@ -92,11 +92,17 @@ namespace {
 
 inline bool multi(const lpp_engine* e) { return e->has_comm && e->comm.nranks > 1; }
 
+// what a communicator callback returned (0: fine) -> status and error text
+lpp_status comm_result(int rc, const char* name) { return rc == 0 ? LPP_OK : fail(LPP_ERR_COMM, std::string(name) + " callback failed"); }
+#define COMM_TRY(call, name)                                                                                          \
+	do {                                                                                                               \
+		const lpp_status _st = comm_result((call), name);                                                              \
+		if (_st != LPP_OK) return _st;                                                                                 \
+	} while (0)
+
 lpp_status comm_allreduce(lpp_engine* e, int offset, int count)
 {
-	if (!multi(e)) return LPP_OK;
-	if (e->comm.allreduce_sum(e->comm.ctx, offset, count) != 0) return fail(LPP_ERR_COMM, "allreduce_sum callback failed");
-	return LPP_OK;
+	return multi(e) ? comm_result(e->comm.allreduce_sum(e->comm.ctx, offset, count), "allreduce_sum") : LPP_OK;
 }
 
 struct SpmvTimer {
@@ -182,8 +188,7 @@ lpp_status one_step(lpp_engine* e, const double* ritz, int nst)
 	// product-basis layout, no vectors kept: two launches per step, the axpy of step j rides in the product of step j+1
 	const bool pb_chain = e->pb.active && e->scalefree && !ritz && pb_chain_ok(e);
 	// the same deferral on the transposition exchange: the update rides in the next step's pack kernel (k_pack_transpose_axpy)
-	const bool pb_lazy_tx = e->pb.active && e->pb.tx && multi(e) && e->tx && e->scalefree && !ritz &&
-	                        !(getenv("LPP_PB_LAZY_TX") && atoi(getenv("LPP_PB_LAZY_TX")) == 0);
+	const bool pb_lazy_tx = e->pb.active && e->pb.lazy_tx && multi(e) && e->tx && e->scalefree && !ritz;
 	if (e->pb.pending && !pb_chain && !pb_lazy_tx) { // someone needs r_j itself: run the pass the chain left out
 		pb_materialise(e, ycur, xcur, e->pb.pend_a, e->pb.pend_b2, e->partial);
 		e->pb.pending = false;
@@ -215,74 +220,75 @@ lpp_status one_step(lpp_engine* e, const double* ritz, int nst)
 		else
 			k_pack_transpose<double><<<nbp, kBlock, 0, st>>>((const double*)ycur, (double*)e->comm.send_buf, nid, n_up, e->tx_peru, chunk, e->pitch);
 		if (e->pb.active) {
-		// product-basis layout: both parts are the single-GPU kernels (lpp_pb.hip, "several GPUs"); each all-to-all has half of
-		// the in-block part to hide behind
-		const int64_t half = split_blocks(nid, e->num_cus);
-		if (e->comm.exchange_begin(e->comm.ctx, 0) != 0) return fail(LPP_ERR_COMM, "exchange_begin(0) callback failed");
-		{
-			SpmvTimer t(e);
-			pb_tx_up(e, ycur, sc, 0, half);
-			t.stop();
-		}
-		if (e->comm.exchange_end(e->comm.ctx, 0) != 0) return fail(LPP_ERR_COMM, "exchange_end(0) callback failed");
-		{
-			SpmvTimer t(e);
-			pb_tx_down(e, e->comm.gath_buf, e->comm.send2_buf, sc);
-			t.stop();
-		}
-		if (e->comm.exchange_begin(e->comm.ctx, 1) != 0) return fail(LPP_ERR_COMM, "exchange_begin(1) callback failed");
-		{
-			SpmvTimer t(e);
-			pb_tx_up(e, ycur, sc, half, nid - half);
-			t.stop();
-		}
-		if (e->comm.exchange_end(e->comm.ctx, 1) != 0) return fail(LPP_ERR_COMM, "exchange_end(1) callback failed");
-		np = pb_tx_unpack_combine(e, xcur, ycur, e->comm.recv2_buf, sc, chunk, e->partial, e->scalefree ? e->tmp_dev + 1 : nullptr);
-		tx_pair = true;
-	} else {
-		if (e->comm.exchange_begin(e->comm.ctx, 0) != 0) return fail(LPP_ERR_COMM, "exchange_begin(0) callback failed");
-		// The local part (diagonal / U + up-hops on the own slice) needs no exchange.  The matrix-free engine runs the first
-		// half of its blocks beside all-to-all #1 and the second half beside all-to-all #2, so both transfers have a kernel to
-		// hide behind; the stored local matrix is one launch, beside #1.
-		const int64_t half = e->kron.active ? split_blocks(nid, e->num_cus) : nid;
-		{
-			SpmvTimer t(e); // overlaps all-to-all #1
-			if (e->kron.active)
-				kron_launch(e, ycur, ycur, xcur, nullptr, sc, 1, 0, half);
+			// product-basis layout: both parts are the single-GPU kernels (lpp_pb.hip, "several GPUs"); each all-to-all has half of
+			// the in-block part to hide behind
+			const int64_t half = split_blocks(nid, e->num_cus);
+			COMM_TRY(e->comm.exchange_begin(e->comm.ctx, 0), "exchange_begin(0)");
+			{
+				SpmvTimer t(e);
+				pb_tx_up(e, ycur, sc, 0, half);
+				t.stop();
+			}
+			COMM_TRY(e->comm.exchange_end(e->comm.ctx, 0), "exchange_end(0)");
+			{
+				SpmvTimer t(e);
+				pb_tx_down(e, e->comm.gath_buf, e->comm.send2_buf, sc);
+				t.stop();
+			}
+			COMM_TRY(e->comm.exchange_begin(e->comm.ctx, 1), "exchange_begin(1)");
+			{
+				SpmvTimer t(e);
+				pb_tx_up(e, ycur, sc, half, nid - half);
+				t.stop();
+			}
+			COMM_TRY(e->comm.exchange_end(e->comm.ctx, 1), "exchange_end(1)");
+			np = pb_tx_unpack_combine(e, xcur, ycur, e->comm.recv2_buf, sc, chunk, e->partial, e->scalefree ? e->tmp_dev + 1 : nullptr);
+			tx_pair = true;
+		} else {
+			COMM_TRY(e->comm.exchange_begin(e->comm.ctx, 0), "exchange_begin(0)");
+			// The local part (diagonal / U + up-hops on the own slice) needs no exchange.  The matrix-free engine runs the first
+			// half of its blocks beside all-to-all #1 and the second half beside all-to-all #2, so both transfers have a kernel to
+			// hide behind; the stored local matrix is one launch, beside #1.
+			const int64_t half = e->kron.active ? split_blocks(nid, e->num_cus) : nid;
+			{
+				SpmvTimer t(e); // overlaps all-to-all #1
+				if (e->kron.active)
+					kron_launch(e, ycur, ycur, xcur, nullptr, sc, 1, 0, half);
+				else
+					spmv_launch(e, e->A_loc, ycur, xcur, nullptr, nullptr, sc);
+				t.stop();
+			}
+			COMM_TRY(e->comm.exchange_end(e->comm.ctx, 0), "exchange_end(0)");
+			HIP_TRY(hipMemsetAsync(e->comm.send2_buf, 0, e->esz * (size_t)chunk * (size_t)e->comm.nranks, st));
+			{
+				EpiScale sc2 = sc;
+				sc2.beta_one = 1; // wT = alpha * (down-hop part) yT into the zeroed buffer
+				SpmvTimer t(e);
+				if (e->kron.active)
+					kron_launch(e, nullptr, e->comm.gath_buf, e->comm.send2_buf, nullptr, sc2, 2);
+				else
+					spmv_launch(e, e->A_rem, e->comm.gath_buf, e->comm.send2_buf, nullptr, nullptr, sc2);
+				t.stop();
+			}
+			COMM_TRY(e->comm.exchange_begin(e->comm.ctx, 1), "exchange_begin(1)");
+			if (half < nid) {
+				SpmvTimer t(e); // overlaps all-to-all #2
+				kron_launch(e, ycur, ycur, xcur, nullptr, sc, 1, half, nid - half);
+				t.stop();
+			}
+			COMM_TRY(e->comm.exchange_end(e->comm.ctx, 1), "exchange_end(1)");
+			if (e->is_complex)
+				k_unpack_add_dot<cplx, true><<<nbp, kBlock, 0, st>>>((cplx*)xcur, (const cplx*)e->comm.recv2_buf, (const cplx*)ycur, nid, n_up, e->tx_peru, chunk, e->partial, e->scalefree ? e->tmp_dev + 1 : nullptr);
 			else
-				spmv_launch(e, e->A_loc, ycur, xcur, nullptr, nullptr, sc);
-			t.stop();
+				k_unpack_add_dot<double, true><<<nbp, kBlock, 0, st>>>((double*)xcur, (const double*)e->comm.recv2_buf, (const double*)ycur, nid, n_up, e->tx_peru, chunk, e->partial, e->scalefree ? e->tmp_dev + 1 : nullptr);
+			np = nbp;
+			tx_pair = true; // the partials come in (Re<y|x>, |x|^2) pairs
 		}
-		if (e->comm.exchange_end(e->comm.ctx, 0) != 0) return fail(LPP_ERR_COMM, "exchange_end(0) callback failed");
-		HIP_TRY(hipMemsetAsync(e->comm.send2_buf, 0, e->esz * (size_t)chunk * (size_t)e->comm.nranks, st));
-		{
-			EpiScale sc2 = sc;
-			sc2.beta_one = 1; // wT = alpha * (down-hop part) yT into the zeroed buffer
-			SpmvTimer t(e);
-			if (e->kron.active)
-				kron_launch(e, nullptr, e->comm.gath_buf, e->comm.send2_buf, nullptr, sc2, 2);
-			else
-				spmv_launch(e, e->A_rem, e->comm.gath_buf, e->comm.send2_buf, nullptr, nullptr, sc2);
-			t.stop();
-		}
-		if (e->comm.exchange_begin(e->comm.ctx, 1) != 0) return fail(LPP_ERR_COMM, "exchange_begin(1) callback failed");
-		if (half < nid) {
-			SpmvTimer t(e); // overlaps all-to-all #2
-			kron_launch(e, ycur, ycur, xcur, nullptr, sc, 1, half, nid - half);
-			t.stop();
-		}
-		if (e->comm.exchange_end(e->comm.ctx, 1) != 0) return fail(LPP_ERR_COMM, "exchange_end(1) callback failed");
-		if (e->is_complex)
-			k_unpack_add_dot<cplx, true><<<nbp, kBlock, 0, st>>>((cplx*)xcur, (const cplx*)e->comm.recv2_buf, (const cplx*)ycur, nid, n_up, e->tx_peru, chunk, e->partial, e->scalefree ? e->tmp_dev + 1 : nullptr);
-		else
-			k_unpack_add_dot<double, true><<<nbp, kBlock, 0, st>>>((double*)xcur, (const double*)e->comm.recv2_buf, (const double*)ycur, nid, n_up, e->tx_peru, chunk, e->partial, e->scalefree ? e->tmp_dev + 1 : nullptr);
-		np = nbp;
-		tx_pair = true; // the partials come in (Re<y|x>, |x|^2) pairs
-	}
 	} else if (pb_chain) {
 		SpmvTimer t(e);
 		np = pb_launch_chain(e, ycur, xcur, e->partial, sc, e->pb.pending ? e->pb.pend_a : nullptr, e->pb.pend_b2, e->tmp_dev + 1);
 		t.stop();
+		if (np < 0) return fail(LPP_ERR_STATE, "chained step: the coupling kernel needs one LDS image per workgroup (coupling rounds > 1)");
 		tx_pair = true; // pairs (Re<r_j|w_j>, |w_j|^2)
 	} else if (e->pb.active) {
 		// scale-free: x is formed by pb_combine_axpy below, together with the recurrence update; the bracket then closes behind that
@@ -293,21 +299,21 @@ lpp_status one_step(lpp_engine* e, const double* ritz, int nst)
 	} else if (e->kron.active) {
 		// matrix-free product with the all-gather: the down part needs the whole vector, so the gather completes first
 		if (multi(e)) {
-			if (e->comm.allgather_begin(e->comm.ctx) != 0) return fail(LPP_ERR_COMM, "allgather_begin callback failed");
-			if (e->comm.allgather_end(e->comm.ctx) != 0) return fail(LPP_ERR_COMM, "allgather_end callback failed");
+			COMM_TRY(e->comm.allgather_begin(e->comm.ctx), "allgather_begin");
+			COMM_TRY(e->comm.allgather_end(e->comm.ctx), "allgather_end");
 		}
 		SpmvTimer t(e);
 		np = kron_launch(e, ycur, multi(e) ? e->comm.gath_buf : ycur, xcur, e->partial, sc);
 		t.stop();
 	} else if (multi(e)) {
 		// the slice of the current vector was written to comm.send_buf by the previous step's last kernel
-		if (e->comm.allgather_begin(e->comm.ctx) != 0) return fail(LPP_ERR_COMM, "allgather_begin callback failed");
+		COMM_TRY(e->comm.allgather_begin(e->comm.ctx), "allgather_begin");
 		{
 			SpmvTimer t(e);
 			spmv_launch(e, e->A_loc, ycur, xcur, nullptr, nullptr, sc); // local columns: overlaps the all-gather
 			t.stop();
 		}
-		if (e->comm.allgather_end(e->comm.ctx) != 0) return fail(LPP_ERR_COMM, "allgather_end callback failed");
+		COMM_TRY(e->comm.allgather_end(e->comm.ctx), "allgather_end");
 		{
 			EpiScale sc2 = sc;
 			sc2.beta_one = 1; // x already holds beta*x_old + alpha*(A_loc y)
@@ -322,7 +328,7 @@ lpp_status one_step(lpp_engine* e, const double* ritz, int nst)
 	}
 	const bool pb_sf = e->pb.active && !e->pb.tx && e->scalefree && !pb_chain; // single GPU, three-kernel form
 	// transposition exchange + scale-free recurrence: a_j and b_j^2 share ONE all-reduce (k_b2_from_w)
-	const bool fused_ab = pb_chain || (tx_pair && e->scalefree && !(getenv("LPP_FUSED_ALLREDUCE") && atoi(getenv("LPP_FUSED_ALLREDUCE")) == 0));
+	const bool fused_ab = pb_chain || (tx_pair && e->scalefree && e->fused_allreduce);
 	lpp_status rc = LPP_OK;
 	if (pb_sf) // the product kernels never read x: raw_j = Re<y | u + z> + beta Re<y | x_old>
 		k_pb_reduce_a<<<1, kBlock, 0, st>>>(e->partial, np, e->pb.xy, sc, a_ptr);
@@ -459,6 +465,7 @@ lpp_status begin_run(lpp_engine* e, const void* init, bool want_save, bool dev_i
 	}
 	e->saving = got;
 	e->scalefree = !e->saving && !e->cfg.reortho && getenv("LPP_NO_SCALE_FREE") == nullptr;
+	e->fused_allreduce = !(getenv("LPP_FUSED_ALLREDUCE") && atoi(getenv("LPP_FUSED_ALLREDUCE")) == 0);
 	e->step = 0;
 	hipStream_t st = e->stream;
 	const int nb = blas_blocks(e->n2);
@@ -634,6 +641,17 @@ lpp_status lpp_engine_lanczos_coeffs(lpp_engine* e, int32_t* steps, double* a, d
 	return LPP_OK;
 }
 
+// the end of a solve: kernel times, step count, wall time since t0 (stats.steps_enqueued is the recurrence's own: a second pass for the
+// Ritz vectors puts the first pass's statistics back before it gets here)
+static void finish_stats(lpp_engine* e, const SolveResult& res, std::chrono::steady_clock::time_point t0, lpp_stats* stats)
+{
+	e->collect_spmv_times();
+	e->stats.steps = res.steps;
+	e->stats.converged = res.converged ? 1 : 0;
+	e->stats.seconds_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+	if (stats) lpp_engine_get_stats(e, stats);
+}
+
 static lpp_status lanczos_impl(lpp_engine* e, const void* init, bool dev_init, int32_t nstates, double* eigs, void* ritz_vectors, lpp_stats* stats)
 {
 	if (!e || nstates < 1 || !eigs) return fail(LPP_ERR_INVALID, "lpp_engine_lanczos: bad argument");
@@ -675,7 +693,6 @@ static lpp_status lanczos_impl(lpp_engine* e, const void* init, bool dev_init, i
 	}
 	if (st != LPP_OK) return st;
 	for (int k = 0; k < nstates; k++) eigs[k] = w[k];
-	const int steps_enq = e->stats.steps_enqueued;
 	if (want_vectors) {
 		const int nb = blas_blocks(e->n2);
 		if (e->saving) {
@@ -738,12 +755,7 @@ static lpp_status lanczos_impl(lpp_engine* e, const void* init, bool dev_init, i
 		}
 		e->resident_n = nkeep; // written and synchronised
 	}
-	e->collect_spmv_times();
-	e->stats.steps = steps;
-	e->stats.steps_enqueued = steps_enq;
-	e->stats.converged = res.converged ? 1 : 0;
-	e->stats.seconds_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-	if (stats) lpp_engine_get_stats(e, stats);
+	finish_stats(e, res, t0, stats);
 	return LPP_OK;
 }
 
@@ -773,13 +785,7 @@ static lpp_status decomposition_impl(lpp_engine* e, const void* init, bool dev_i
 		a[j] = res.a[j];
 		b[j] = res.b[j];
 	}
-	const int steps_enq = e->stats.steps_enqueued;
-	e->collect_spmv_times();
-	e->stats.steps = res.steps;
-	e->stats.steps_enqueued = steps_enq;
-	e->stats.converged = res.converged ? 1 : 0;
-	e->stats.seconds_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-	if (stats) lpp_engine_get_stats(e, stats);
+	finish_stats(e, res, t0, stats);
 	return LPP_OK;
 }
 

@@ -84,6 +84,65 @@ void pb_realify(int64_t n, const int64_t* rp, const int32_t* ci, const double* v
 		}
 }
 
+// ---- kernel arguments: everything that comes from the state, in one place per struct; whatever is not named here is zero -----------
+// k_pb_down (all forms) and k_pb_down_image on rows of `pitch` positions; the caller sets y, z, u_in, shift, partial, sc, u_has_beta, pf_lead
+static PbDownArgs down_args(const PbState& B, int64_t pitch)
+{
+	PbDownArgs d = {};
+	d.pitch = pitch;
+	d.n_blk = B.n_blk;
+	d.npanels = (int)(pitch / 16);
+	d.ids_per_wg = B.ids_per_wg;
+	d.rounds = B.down_rounds;
+	d.ids_per_round = B.ids_per_round;
+	d.image = (const uint4*)B.down_image;
+	d.rowcap = B.rowcap;
+	d.c_ptr = B.c_ptr;
+	d.c_col = B.c_col;
+	d.c_code = B.c_code;
+	d.dict = B.dict;
+	d.cdict = (const double2*)B.cdict;
+	d.pace = B.pace;
+	d.order = B.order;
+	return d;
+}
+
+// k_pb_up (all forms); the caller sets dcode, n_blk, y, u, partial, sc and, in the chained form, wbuf, ybuf, g_a, g_b2
+static PbUpArgs up_args(const PbState& B)
+{
+	PbUpArgs u = {};
+	u.tw = B.tw;
+	u.tw_off = B.tw_off;
+	u.tw_len = B.tw_len;
+	u.G = B.G;
+	for (int g = 0; g < kPbMaxGroups; g++) u.gval[g] = B.gval[g];
+	u.dict = B.dict;
+	u.n_up = B.n_up;
+	u.pitch = B.pitch;
+	u.spb = B.spb;
+	return u;
+}
+
+// k_pb_combine; the caller sets a_ptr, b2_prev and the partials it wants
+static PbCombineArgs combine_args(const PbState& B, void* x, const void* y, const EpiScale& sc)
+{
+	PbCombineArgs c = {};
+	c.n2 = (B.n_blk * B.pitch) >> 1;
+	c.x = (double2*)x;
+	c.y = (const double2*)y;
+	c.u = (const double2*)B.u;
+	c.z = B.c_nnz > 0 ? (const double2*)B.z : nullptr;
+	c.sc = sc;
+	c.d = (const double2*)B.dval;
+	return c;
+}
+
+// The counter-scheduled form of k_pb_down (PF) keeps its task sums in LDS behind the image: it runs only where both fit 150 KB; the
+// fixed-share form, whose sums follow a fixed order by construction, takes the rest
+static bool pb_down_pf_fits(const PbState& B) { return B.down_lds_pf <= (size_t)150 * 1024; }
+// a panel (16 positions = 128 bytes of every block) fits an XCD's 4 MB L2 with room to spare
+static bool pb_panel_fits_l2(int64_t n_blk) { return (size_t)n_blk * 128 <= (size_t)3 << 20; }
+
 lpp_status pb_build(lpp_engine* e, int64_t n_up, int64_t n_blk, const int64_t* t_rp, const int32_t* t_ci, const double* t_va,
                     const int64_t* c_rp, const int32_t* c_ci, const double* c_va, const double* dict256, int ndict,
                     int64_t blk0, int64_t nblk_loc, int64_t pitch_dn, int64_t nblk_padded, const PbCplxInput* cx, SegPlan* pre, int64_t pre_nnz)
@@ -529,17 +588,7 @@ lpp_status pb_build(lpp_engine* e, int64_t n_up, int64_t n_blk, const int64_t* t
 		// ((7,6) sector of the 4x5 lattice forced into two rounds: coupling kernel 33.2 ms in one round, 43.0 ms rebuilding)
 		const size_t bytes = pb_down_lds_bytes(B.ids_per_round, B.rowcap) * (size_t)slots * (size_t)B.down_rounds;
 		HIP_TRY_MEM(hipMalloc(&B.down_image, bytes));
-		PbDownArgs d = {};
-		d.n_blk = n_blk;
-		d.ids_per_wg = B.ids_per_wg;
-		d.rounds = B.down_rounds;
-		d.ids_per_round = B.ids_per_round;
-		d.rowcap = B.rowcap;
-		d.c_ptr = B.c_ptr;
-		d.c_col = B.c_col;
-		d.c_code = B.c_code;
-		d.order = B.order;
-		k_pb_down_image<<<slots * B.down_rounds, 256, 0, st>>>(d, (uint4*)B.down_image);
+		k_pb_down_image<<<slots * B.down_rounds, 256, 0, st>>>(down_args(B, pitch), (uint4*)B.down_image); // (reads the lists, the order and the round geometry only)
 	}
 	if (!(getenv("LPP_PB_PACE") && atoi(getenv("LPP_PB_PACE")) == 0))
 		HIP_TRY_MEM(hipMalloc(&B.pace, sizeof(int) * 8 * (parts ? (size_t)B.pace_stride : (size_t)(std::max(pitch, pitch_dn) / 16))));
@@ -560,10 +609,33 @@ lpp_status pb_build(lpp_engine* e, int64_t n_up, int64_t n_blk, const int64_t* t
 	e->pitch = cx ? pitch / 2 : pitch; // in vector elements
 	e->pitch_rows = cx ? cx->n_c : n_up;
 	e->pitch_blocks = nblk_loc;
+	{
+		// the launch forms ("launches" below), decided here once: a launch reads these fields, never the environment
+		auto sw = [](const char* k, int dflt) {
+			const char* s = getenv(k);
+			return s ? atoi(s) : dflt;
+		};
+		const bool pf_fits = pb_down_pf_fits(B), l2 = pb_panel_fits_l2(n_blk);
+		// (more than two value groups -- complex hoppings realified, t-t' models -- take the any-number-of-groups path of k_pb_up)
+		B.chain_ok = sw("LPP_PB_CHAIN", 1) != 0 && !tx && !B.big && !parts && !wide && B.down_rounds == 1 && B.c_nnz > 0 && B.G >= 1 && B.G <= kPbMaxGroups;
+		B.down_tasks = pf_fits && sw("LPP_PB_DOWN_TASKS", l2 ? 1 : 0) != 0;
+		B.down_pf = pf_fits && sw("LPP_PB_DOWN_PF", 1) != 0;
+		B.chain_drop_pace = B.down_pf && l2 && sw("LPP_PB_CHAIN_PACE", 0) == 0;
+		B.lazy_tx = tx && sw("LPP_PB_LAZY_TX", 1) != 0;
+		if (getenv("LPP_VERBOSE"))
+			fprintf(stderr, "lpp: product-basis launch forms: chain %d, down tasks %d, chained counter form %d, pacing dropped %d, lazy exchange %d\n", B.chain_ok ? 1 : 0,
+			        B.down_tasks ? 1 : 0, B.down_pf ? 1 : 0, B.chain_drop_pace ? 1 : 0, B.lazy_tx ? 1 : 0);
+	}
 	B.active = true;
 	return LPP_OK;
 }
 
+// ---- launches ----------------------------------------------------------------------------------------------------------
+// Nothing from here to the handed-over-CSR section reads the environment.  Which form of a kernel a launch takes was decided at the
+// end of pb_build and is kept in PbState (chain_ok, down_tasks, down_pf, chain_drop_pace, lazy_tx): LPP_PB_CHAIN, LPP_PB_DOWN_TASKS,
+// LPP_PB_DOWN_PF, LPP_PB_CHAIN_PACE and LPP_PB_LAZY_TX take effect when the layout is BUILT, not at the first or at every launch.
+// Kernel arguments come from down_args / up_args / combine_args (above pb_build); a launch site sets only what is its own.
+//
 // x = beta x + alpha H y (EpiScale semantics of the other product kernels) as two independent kernels that only read y,
 //   k_pb_down  z = alpha C y            (+ partials of Re<y|z>)
 //   k_pb_up    u = alpha (T y + D y)    (+ partials of Re<y|u>, stored in front of the first kernel's)
@@ -744,21 +816,11 @@ static int launch_up_big(lpp_engine* e, const double* y, double* u, const uint8_
 // The plain coupling kernel with the tasks of a step handed out by the LDS counter and NO pacing between the workgroups of a group (k_pb_down<.., PF>
 // with pace == null: the barrier per step keeps a workgroup together, the counter keeps its waves on neighbouring tasks): faster where a panel of all blocks
 // fits an XCD's L2 with room to spare -- complex couplings at 11440 blocks 2.27 -> 2.08 ms, the 3x6 lattice's (6,6) sector (18564 blocks) 2.72 -> 2.56 ms -- and
-// slower where it does not (38760 blocks, 4.96 MB: 28.4 -> 35.8 ms; with pacing on top of the counter 28.5): up to 3 MB per panel.  LPP_PB_DOWN_TASKS=0 / 1
-// The counter-scheduled form keeps its task sums in LDS behind the image (k_pb_down, PF): it runs only where both fit 150 KB; the fixed-share form,
-// whose sums follow a fixed order by construction, takes the rest
-static bool pb_down_pf_fits(const PbState& B) { return B.down_lds_pf <= (size_t)150 * 1024; }
-
-static bool pb_down_tasks(const PbState& B, int64_t n_blk)
-{
-	if (!pb_down_pf_fits(B)) return false;
-	if (const char* s = getenv("LPP_PB_DOWN_TASKS")) return atoi(s) != 0;
-	return (size_t)n_blk * 128 <= (size_t)3 << 20;
-}
-
+// slower where it does not (38760 blocks, 4.96 MB: 28.4 -> 35.8 ms; with pacing on top of the counter 28.5): up to 3 MB per panel (pb_panel_fits_l2), and
+// only where the task sums fit LDS (pb_down_pf_fits).  LPP_PB_DOWN_TASKS=0 / 1 overrides the panel test.  PbState::down_tasks
 static void pb_launch_down_plain(const PbState& B, PbDownArgs& d, hipStream_t st)
 {
-	const bool tasks = pb_down_tasks(B, d.n_blk);
+	const bool tasks = B.down_tasks;
 	if (tasks) d.pace = nullptr;
 	if (d.pace) (void)hipMemsetAsync(d.pace, 0, sizeof(int) * 8 * (size_t)d.npanels, st);
 #define LPP_PB_DOWN_PLAIN(WIDE_, CPLX_, PF_)                                                                           \
@@ -841,69 +903,30 @@ int pb_launch(lpp_engine* e, const void* y, void* x, double* partial, const EpiS
 		const int n = launch_down_parts(e, (const double*)y, B.z, B.pitch, partial ? partial + nb : nullptr, sc, sd);
 		if (partial) np += n;
 	} else if (both) {
-		PbDownArgs d = {};
-		d.pitch = B.pitch;
-		d.n_blk = B.n_blk;
-		d.npanels = (int)(B.pitch / 16);
-		d.ids_per_wg = B.ids_per_wg;
-	d.rounds = B.down_rounds;
-	d.ids_per_round = B.ids_per_round;
-	d.image = (const uint4*)B.down_image;
-		d.rowcap = B.rowcap;
-		d.c_ptr = B.c_ptr;
-		d.c_col = B.c_col;
-		d.c_code = B.c_code;
-		d.dict = B.dict;
+		PbDownArgs d = down_args(B, B.pitch);
 		d.y = (const double*)y;
 		d.z = B.z;
-		d.u_in = nullptr;
-		d.shift = nullptr;
 		d.partial = partial ? partial + nb : nullptr;
 		d.sc = sc;
-		d.pace = B.pace;
-		d.order = B.order;
-		d.u_has_beta = 0;
-		d.cdict = (const double2*)B.cdict;
 		pb_launch_down_plain(B, d, sd);
 		if (partial) np += B.down_grid;
 	}
 	if (B.big) {
 		launch_up_big(e, (const double*)y, B.u, B.dcode, B.n_blk, partial, sc, st); // nb partials, in front of the couplings'
 	} else {
-	PbUpArgs u = {};
-	u.tw = B.tw;
-	u.tw_off = B.tw_off;
-	u.tw_len = B.tw_len;
-	u.G = B.G;
-	for (int g = 0; g < kPbMaxGroups; g++) u.gval[g] = B.gval[g];
-	u.dict = B.dict;
-	u.dcode = B.dcode;
-	u.n_up = B.n_up;
-	u.pitch = B.pitch;
-	u.n_blk = B.n_blk;
-	u.spb = B.spb;
-	u.y = (const double*)y;
-	u.u = B.u;
-	u.partial = partial;
-	u.sc = sc;
-	u.wbuf = u.ybuf = nullptr;
-	u.g_a = u.g_b2 = nullptr;
-	const size_t lds = pb_up_lds_bytes(B.pitch, B.spb, B.G);
-	if (partial) launch_up<true>(B, u, nb, lds, st);
-	else launch_up<false>(B, u, nb, lds, st);
+		PbUpArgs u = up_args(B);
+		u.dcode = B.dcode;
+		u.n_blk = B.n_blk;
+		u.y = (const double*)y;
+		u.u = B.u;
+		u.partial = partial;
+		u.sc = sc;
+		const size_t lds = pb_up_lds_bytes(B.pitch, B.spb, B.G);
+		if (partial) launch_up<true>(B, u, nb, lds, st);
+		else launch_up<false>(B, u, nb, lds, st);
 	}
 	if (!defer_combine) {
-		PbCombineArgs c;
-		c.n2 = (B.n_blk * B.pitch) >> 1;
-		c.x = (double2*)x;
-		c.y = (const double2*)y;
-		c.u = (const double2*)B.u;
-		c.z = B.c_nnz > 0 ? (const double2*)B.z : nullptr;
-		c.sc = sc;
-		c.a_ptr = nullptr;
-		c.b2_prev = nullptr;
-		c.d = (const double2*)B.dval;
-		c.partial_dq = nullptr;
+		PbCombineArgs c = combine_args(B, x, y, sc);
 		const int nbc = combine_blocks(c.n2);
 		c.partial_nrm = want_dot ? want_dot + nbc : nullptr; // |x|^2 partials: not used by these callers
 		c.partial_xy = want_dot;
@@ -918,22 +941,6 @@ int pb_launch(lpp_engine* e, const void* y, void* x, double* partial, const EpiS
 // transposed slice -> all-to-all #2 || pb_tx_up(second half) -> pb_tx_unpack_combine.  Both parts of the product are the
 // single-GPU kernels: the in-block kernel on the rank's own blocks, the panel-major coupling kernel on the transposed slice
 // (all N_down blocks, rows = this rank's up-index range: the same C (x) 1 structure with narrower rows).
-static void fill_up_args(const PbState& B, PbUpArgs& u)
-{
-	u.tw = B.tw;
-	u.tw_off = B.tw_off;
-	u.tw_len = B.tw_len;
-	u.G = B.G;
-	for (int g = 0; g < kPbMaxGroups; g++) u.gval[g] = B.gval[g];
-	u.dict = B.dict;
-	u.n_up = B.n_up;
-	u.pitch = B.pitch;
-	u.spb = B.spb;
-	u.partial = nullptr;
-	u.wbuf = u.ybuf = nullptr;
-	u.g_a = u.g_b2 = nullptr;
-}
-
 void pb_tx_up(lpp_engine* e, const void* y, const EpiScale& sc, int64_t b0, int64_t cnt)
 {
 	PbState& B = e->pb;
@@ -942,8 +949,7 @@ void pb_tx_up(lpp_engine* e, const void* y, const EpiScale& sc, int64_t b0, int6
 		launch_up_big(e, (const double*)y + b0 * B.pitch, B.u + b0 * B.pitch, B.dcode + b0 * B.pitch, cnt, nullptr, sc, e->stream);
 		return;
 	}
-	PbUpArgs u = {};
-	fill_up_args(B, u);
+	PbUpArgs u = up_args(B);
 	u.dcode = B.dcode + b0 * B.pitch;
 	u.n_blk = cnt;
 	u.y = (const double*)y + b0 * B.pitch;
@@ -960,28 +966,10 @@ void pb_tx_down(lpp_engine* e, const void* gath, void* send2, const EpiScale& sc
 		launch_down_parts(e, (const double*)gath, (double*)send2, B.pitch_dn, nullptr, sc, e->stream);
 		return;
 	}
-	PbDownArgs d = {};
-	d.pitch = B.pitch_dn;
-	d.n_blk = B.n_blk;
-	d.npanels = (int)(B.pitch_dn / 16);
-	d.ids_per_wg = B.ids_per_wg;
-	d.rounds = B.down_rounds;
-	d.ids_per_round = B.ids_per_round;
-	d.image = (const uint4*)B.down_image;
-	d.rowcap = B.rowcap;
-	d.c_ptr = B.c_ptr;
-	d.c_col = B.c_col;
-	d.c_code = B.c_code;
-	d.dict = B.dict;
+	PbDownArgs d = down_args(B, B.pitch_dn); // (cdict: null here as before -- pb_build refuses complex hoppings on the exchange)
 	d.y = (const double*)gath;
 	d.z = (double*)send2;
-	d.u_in = nullptr;
-	d.shift = nullptr;
-	d.partial = nullptr;
 	d.sc = sc;
-	d.pace = B.pace;
-	d.order = B.order;
-	d.u_has_beta = 0;
 	pb_launch_down_plain(B, d, e->stream);
 }
 
@@ -996,12 +984,8 @@ int pb_tx_unpack_combine(lpp_engine* e, void* x, const void* y, const void* recv
 }
 
 // ---- the chained scale-free step (k_pb_up<KC>, k_pb_down<RMW>) -------------------------------------------------
-bool pb_chain_ok(const lpp_engine* e)
-{
-	const PbState& B = e->pb;
-	if (getenv("LPP_PB_CHAIN") && atoi(getenv("LPP_PB_CHAIN")) == 0) return false;
-	return B.active && !B.tx && !B.big && !B.parts && !B.wide && !B.dval && B.down_rounds == 1 && B.c_nnz > 0 && B.G >= 1 && B.G <= kPbMaxGroups; // more than two value groups (complex hoppings realified, t-t' models): the any-number-of-groups path of k_pb_up
-}
+// (a plain-stream diagonal is attached by pb_build's caller, after the build: the streaming pass of the three-kernel form adds it)
+bool pb_chain_ok(const lpp_engine* e) { return e->pb.chain_ok && !e->pb.dval; }
 
 template <int GT, int PRE0 = kPbPre> static void launch_up_chain(const PbUpArgs& u, int nb, size_t lds, hipStream_t st)
 {
@@ -1010,27 +994,19 @@ template <int GT, int PRE0 = kPbPre> static void launch_up_chain(const PbUpArgs&
 }
 
 // One scale-free Lanczos step in two launches.  In: w (= w_{j-1}, or r_j itself when g_a is null) and y (= r_{j-1}).
-// Out: w holds r_j, y holds w_j = alpha H r_j + beta r_{j-1} (the in-block part passes through pb.u); partial holds pairs (Re<r_j|w_j>, |w_j|^2), their number is returned.
+// Out: w holds r_j, y holds w_j = alpha H r_j + beta r_{j-1} (the in-block part passes through pb.u); partial holds pairs (Re<r_j|w_j>, |w_j|^2), their number is returned
+// (negative: the state is not one the chained kernels serve, nothing was launched).
 int pb_launch_chain(lpp_engine* e, void* w, void* y, double* partial, const EpiScale& sc, const double* g_a, const double* g_b2, const double* shift)
 {
 	PbState& B = e->pb;
 	hipStream_t st = e->stream;
+	// k_pb_down<RMW> adds u_in and touches the u lines ahead once per panel: one LDS image per workgroup, whatever let the caller in here
+	if (B.down_rounds != 1) return -1;
 	const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(B.n_blk, (int64_t)e->num_cus));
-	PbUpArgs u = {};
-	u.tw = B.tw;
-	u.tw_off = B.tw_off;
-	u.tw_len = B.tw_len;
-	u.G = B.G;
-	for (int g = 0; g < kPbMaxGroups; g++) u.gval[g] = B.gval[g];
-	u.dict = B.dict;
+	PbUpArgs u = up_args(B);
 	u.dcode = B.dcode;
-	u.n_up = B.n_up;
-	u.pitch = B.pitch;
 	u.n_blk = B.n_blk;
-	u.spb = B.spb;
-	u.y = nullptr;
 	u.u = B.u;
-	u.partial = nullptr;
 	u.sc = sc;
 	u.wbuf = (double*)w;
 	u.ybuf = (double*)y;
@@ -1045,39 +1021,23 @@ int pb_launch_chain(lpp_engine* e, void* w, void* y, double* partial, const EpiS
 		else if (B.pre0 == kPreHi) launch_up_chain<2, kPreHi>(u, nb, lds, st);
 		else launch_up_chain<2>(u, nb, lds, st);
 	}
-	PbDownArgs d = {};
-	d.pitch = B.pitch;
-	d.n_blk = B.n_blk;
-	d.npanels = (int)(B.pitch / 16);
-	d.ids_per_wg = B.ids_per_wg;
-	d.rounds = B.down_rounds;
-	d.ids_per_round = B.ids_per_round;
-	d.image = (const uint4*)B.down_image;
-	d.rowcap = B.rowcap;
-	d.c_ptr = B.c_ptr;
-	d.c_col = B.c_col;
-	d.c_code = B.c_code;
-	d.dict = B.dict;
+	PbDownArgs d = down_args(B, B.pitch);
 	d.y = (const double*)w;
 	d.z = (double*)y;
 	d.u_in = B.u;
 	d.shift = shift;
 	d.partial = partial;
 	d.sc = sc;
-	d.pace = B.pace;
-	d.order = B.order;
 	d.u_has_beta = 1; // the in-block kernel has put beta r_{j-1} into u
-	d.cdict = (const double2*)B.cdict;
 	// the last wave touches the u lines ahead of the tasks and the tasks are handed out by a counter (k_pb_down<..., PF>): config 2 3.03 -> 2.88 ms
-	// per step; LPP_PB_DOWN_PF=0: every wave its fixed share of the tasks, no touching
-	static const bool pf_env = !(getenv("LPP_PB_DOWN_PF") && atoi(getenv("LPP_PB_DOWN_PF")) == 0);
-	const bool pf = pf_env && pb_down_pf_fits(B);
+	// per step; LPP_PB_DOWN_PF=0: every wave its fixed share of the tasks, no touching (PbState::down_pf)
+	const bool pf = B.down_pf;
 	d.pf_lead = 2;
 	// ... and with the tasks handed out by a counter and a barrier per panel the workgroups of a group stay together by themselves: the bounded pacing
 	// (one atomic, one poll and one more barrier per panel, a memset per launch) only costs here -- config 2 1.51 -> 1.41 ms, the 4x4 lattice's (7,7) sector
-	// 1.19 -> 1.08, complex hoppings at (6,6) 1.25 -> 1.09 ms; the plain kernel needs it (3x6 lattice, (6,6): 2.7 ms with, 6.1 without).  LPP_PB_CHAIN_PACE=1: keep it
-	static const bool chain_pace = getenv("LPP_PB_CHAIN_PACE") && atoi(getenv("LPP_PB_CHAIN_PACE")) != 0;
-	if (pf && !chain_pace && (size_t)B.n_blk * 128 <= (size_t)3 << 20) d.pace = nullptr; // (a panel beyond an XCD's L2 keeps it: see pb_down_tasks)
+	// 1.19 -> 1.08, complex hoppings at (6,6) 1.25 -> 1.09 ms; the plain kernel needs it (3x6 lattice, (6,6): 2.7 ms with, 6.1 without).  LPP_PB_CHAIN_PACE=1: keep it;
+	// a panel beyond an XCD's L2 keeps it too (PbState::chain_drop_pace)
+	if (B.chain_drop_pace) d.pace = nullptr;
 	if (d.pace) (void)hipMemsetAsync(d.pace, 0, sizeof(int) * 8 * (size_t)d.npanels, st);
 #define LPP_PB_DOWN_RMW(CPLX_, PF_)                                                                                    \
 	do {                                                                                                              \
@@ -1106,19 +1066,12 @@ void pb_materialise(lpp_engine* e, void* y, const void* x, const double* g_a, co
 int pb_combine_axpy(lpp_engine* e, void* x, const void* y, const EpiScale& sc, const double* a_ptr, const double* b2_prev, double* partial)
 {
 	const PbState& B = e->pb;
-	PbCombineArgs c;
-	c.n2 = (B.n_blk * B.pitch) >> 1;
-	c.x = (double2*)x;
-	c.y = (const double2*)y;
-	c.u = (const double2*)B.u;
-	c.z = B.c_nnz > 0 ? (const double2*)B.z : nullptr;
-	c.sc = sc;
+	PbCombineArgs c = combine_args(B, x, y, sc);
 	c.a_ptr = a_ptr;
 	c.b2_prev = b2_prev;
 	const int nb = combine_blocks(c.n2);
 	c.partial_nrm = partial;
 	c.partial_xy = partial + nb;
-	c.d = (const double2*)B.dval;
 	c.partial_dq = B.dval ? partial + 2 * nb : nullptr;
 	k_pb_combine<<<nb, kBlock, 0, e->stream>>>(c);
 	k_reduce_final<<<1, kBlock, 0, e->stream>>>(partial + nb, nb, 1, 1, B.xy); // next step's <y | x_old>
@@ -1504,29 +1457,27 @@ lpp_status pb_get_csr(lpp_engine* e, int64_t* rowptr, int32_t* colind, void* val
 }
 
 // ---- vector copies that know the pitched layout ------------------------------------------------
-lpp_status vec_from_host(lpp_engine* e, double* dev, const void* host)
+// basis order (`src` / `dst`: host or device memory, as `kind` says) <-> the internal pitched / permuted form (`dev`)
+static lpp_status vec_in(lpp_engine* e, double* dev, const void* src, hipMemcpyKind kind)
 {
-	if (e->tj.active) return tj_vec_from_host(e, dev, host);
 	if (e->pitch > 0) {
 		const PbState& B = e->pb;
 		// stored order of the positions (PbState::perm): the copy lands in pb.u in the basis order and is gathered from there
 		double* const land = B.perm ? B.u : dev;
 		HIP_TRY(hipMemsetAsync(land, 0, sizeof(double) * (size_t)e->nd_pad, e->stream));
-		HIP_TRY(hipMemcpy2DAsync(land, e->esz * (size_t)e->pitch, host, e->esz * (size_t)e->pitch_rows, e->esz * (size_t)e->pitch_rows, (size_t)e->pitch_blocks,
-		                         hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpy2DAsync(land, e->esz * (size_t)e->pitch, src, e->esz * (size_t)e->pitch_rows, e->esz * (size_t)e->pitch_rows, (size_t)e->pitch_blocks, kind, e->stream));
 		if (B.perm) {
 			k_pb_permute<true><<<2048, 256, 0, e->stream>>>(dev, land, B.perm, e->pitch_blocks, e->pitch_rows, e->pitch);
 			HIP_TRY(hipGetLastError());
 		}
 		return LPP_OK;
 	}
-	HIP_TRY(hipMemcpyAsync(dev, host, e->esz * (size_t)e->n_local, hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipMemcpyAsync(dev, src, e->esz * (size_t)e->n_local, kind, e->stream));
 	return LPP_OK;
 }
 
-lpp_status vec_to_host(lpp_engine* e, void* host, const double* dev)
+static lpp_status vec_out(lpp_engine* e, void* dst, const double* dev, hipMemcpyKind kind)
 {
-	if (e->tj.active) return tj_vec_to_host(e, host, dev);
 	if (e->pitch > 0) {
 		const PbState& B = e->pb;
 		const double* from = dev;
@@ -1535,52 +1486,23 @@ lpp_status vec_to_host(lpp_engine* e, void* host, const double* dev)
 			HIP_TRY(hipGetLastError());
 			from = B.u;
 		}
-		HIP_TRY(hipMemcpy2DAsync(host, e->esz * (size_t)e->pitch_rows, from, e->esz * (size_t)e->pitch, e->esz * (size_t)e->pitch_rows, (size_t)e->pitch_blocks,
-		                         hipMemcpyDeviceToHost, e->stream));
+		HIP_TRY(hipMemcpy2DAsync(dst, e->esz * (size_t)e->pitch_rows, from, e->esz * (size_t)e->pitch, e->esz * (size_t)e->pitch_rows, (size_t)e->pitch_blocks, kind, e->stream));
 		return LPP_OK;
 	}
-	HIP_TRY(hipMemcpyAsync(host, dev, e->esz * (size_t)e->n_local, hipMemcpyDeviceToHost, e->stream));
+	HIP_TRY(hipMemcpyAsync(dst, dev, e->esz * (size_t)e->n_local, kind, e->stream));
 	return LPP_OK;
 }
 
-// device vector in the basis order -> the internal (pitched / permuted) form: vec_from_host without the host
+// the hole-major t-J layout has host copies of its own and no device-side ones
+lpp_status vec_from_host(lpp_engine* e, double* dev, const void* host) { return e->tj.active ? tj_vec_from_host(e, dev, host) : vec_in(e, dev, host, hipMemcpyHostToDevice); }
+lpp_status vec_to_host(lpp_engine* e, void* host, const double* dev) { return e->tj.active ? tj_vec_to_host(e, host, dev) : vec_out(e, host, dev, hipMemcpyDeviceToHost); }
 lpp_status vec_from_device(lpp_engine* e, double* dev, const void* basis)
 {
-	if (e->tj.active) return fail(LPP_ERR_STATE, "device vectors: not on a hole-major t-J engine");
-	if (e->pitch > 0) {
-		const PbState& B = e->pb;
-		double* const land = B.perm ? B.u : dev;
-		HIP_TRY(hipMemsetAsync(land, 0, sizeof(double) * (size_t)e->nd_pad, e->stream));
-		HIP_TRY(hipMemcpy2DAsync(land, e->esz * (size_t)e->pitch, basis, e->esz * (size_t)e->pitch_rows, e->esz * (size_t)e->pitch_rows, (size_t)e->pitch_blocks,
-		                         hipMemcpyDeviceToDevice, e->stream));
-		if (B.perm) {
-			k_pb_permute<true><<<2048, 256, 0, e->stream>>>(dev, land, B.perm, e->pitch_blocks, e->pitch_rows, e->pitch);
-			HIP_TRY(hipGetLastError());
-		}
-		return LPP_OK;
-	}
-	HIP_TRY(hipMemcpyAsync(dev, basis, e->esz * (size_t)e->n_local, hipMemcpyDeviceToDevice, e->stream));
-	return LPP_OK;
+	return e->tj.active ? fail(LPP_ERR_STATE, "device vectors: not on a hole-major t-J engine") : vec_in(e, dev, basis, hipMemcpyDeviceToDevice);
 }
-
-// ... and back: vec_to_host with a device destination
 lpp_status vec_to_device(lpp_engine* e, void* basis, const double* dev)
 {
-	if (e->tj.active) return fail(LPP_ERR_STATE, "device vectors: not on a hole-major t-J engine");
-	if (e->pitch > 0) {
-		const PbState& B = e->pb;
-		const double* from = dev;
-		if (B.perm) {
-			k_pb_permute<false><<<2048, 256, 0, e->stream>>>(B.u, dev, B.perm, e->pitch_blocks, e->pitch_rows, e->pitch);
-			HIP_TRY(hipGetLastError());
-			from = B.u;
-		}
-		HIP_TRY(hipMemcpy2DAsync(basis, e->esz * (size_t)e->pitch_rows, from, e->esz * (size_t)e->pitch, e->esz * (size_t)e->pitch_rows, (size_t)e->pitch_blocks,
-		                         hipMemcpyDeviceToDevice, e->stream));
-		return LPP_OK;
-	}
-	HIP_TRY(hipMemcpyAsync(basis, dev, e->esz * (size_t)e->n_local, hipMemcpyDeviceToDevice, e->stream));
-	return LPP_OK;
+	return e->tj.active ? fail(LPP_ERR_STATE, "device vectors: not on a hole-major t-J engine") : vec_out(e, basis, dev, hipMemcpyDeviceToDevice);
 }
 
 void vec_fill_random(lpp_engine* e, double* dev, uint64_t seed)

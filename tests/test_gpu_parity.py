@@ -853,16 +853,14 @@ def test_product_basis_layout(case, form, monkeypatch):
         assert rel(xw, xg) < SPMV_TOL
 
 
-def test_chained_step_with_fixed_task_shares():
-    """LPP_PB_DOWN_PF=0: the coupling kernel of the chained step without the task counter and without the wave that touches the u lines
-    ahead (round 3's form, kept as a switch) gives the same energy, stopping step and coefficients.  The switch is read once per process,
-    so the run is a child process."""
+def _pb_child(case, env, product_to=None):
+    """One solve and one decomposition of a PB_CASES matrix in a child process (scale-free recurrence, LPP_PRODUCT_LAYOUT=1 plus `env`):
+    (layout's chained_step, energy, steps, a, b) as a dict and the child's stderr.  product_to: also x += H y on the oracle's vectors of
+    _pb_oracle, saved there."""
     import json
     import os
     import subprocess
     import sys
-    case = "ladder_2x6"
-    A, x0, y, xo, init, eo, so, steps_o, ao, bo, e3o, s3o = _pb_oracle(case)
     code = (
         "import sys, json, numpy as np\n"
         "sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
@@ -873,15 +871,61 @@ def test_chained_step_with_fixed_task_shares():
         "with LanczosEngine(save_vectors=0) as e:\n"
         "    e.assemble_hubbard(L, nup, ndown, hop, U, V)\n"
         "    lay = e.layout()\n"
+        "    n = e.stats()['nrows']\n"
+        "    if len(sys.argv) > 1:\n"
+        "        np.save(sys.argv[1], e.matrixVectorProduct(oracle.fill_random(n, 7), oracle.fill_random(n, 8)))\n"
         "    eg, _, st = e.lanczos(1, want_vectors=False)\n"
-        "    ag, bg, _ = e.decomposition(oracle.fill_random(e.stats()['nrows'], 4321))\n"
+        "    ag, bg, _ = e.decomposition(oracle.fill_random(n, 4321))\n"
         "print('RESULT ' + json.dumps({'chained': lay['chained_step'], 'e0': float(eg[0]), 'steps': st['steps'], 'a': list(map(float, ag)), 'b': list(map(float, bg))}))\n"
     ) % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), os.path.dirname(os.path.abspath(__file__)), case)
-    env = dict(os.environ, LPP_PRODUCT_LAYOUT="1", LPP_PB_DOWN_PF="0")
-    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
+    env = dict(os.environ, LPP_PRODUCT_LAYOUT="1", **env)
+    out = subprocess.run([sys.executable, "-c", code] + ([str(product_to)] if product_to else []), env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
-    r = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
+    return json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:]), out.stderr
+
+
+def test_chained_step_with_fixed_task_shares():
+    """LPP_PB_DOWN_PF=0: the coupling kernel of the chained step without the task counter and without the wave that touches the u lines
+    ahead (round 3's form, kept as a switch) gives the same energy, stopping step and coefficients.  The switch is read when the layout is
+    built (pb_build); the run is a child process with the switch in its environment from the start."""
+    case = "ladder_2x6"
+    A, x0, y, xo, init, eo, so, steps_o, ao, bo, e3o, s3o = _pb_oracle(case)
+    r, _ = _pb_child(case, dict(LPP_PB_DOWN_PF="0"))
     assert r["chained"] == 1
+    assert abs(r["e0"] - eo[0]) <= E_TOL * abs(eo[0]) and r["steps"] == so
+    assert len(r["a"]) == steps_o and rel(np.array(r["a"]), ao) < 1e-8 and rel(np.array(r["b"]), bo) < 1e-8
+
+
+# ladder_2x6: 924 blocks of 924 positions on one GPU.  A panel of all blocks is 924 * 128 bytes = 116 KB (far below the 3 MB up to which the
+# coupling kernels drop the pacing), a coupling workgroup owns 29 blocks (image and task sums far below 150 KB of LDS: the counter forms
+# fit), and there is no exchange.  So every form is on by itself except "lazy exchange", and a switch turns off exactly its own form --
+# LPP_PB_DOWN_PF=0 also "pacing dropped", which only the counter form of the chained kernel can do.
+#                                          chain, down tasks, chained counter form, pacing dropped, lazy exchange
+LAUNCH_FORMS = {
+    "none": ({}, (1, 1, 1, 1, 0)),
+    "chain0": (dict(LPP_PB_CHAIN="0"), (0, 1, 1, 1, 0)),
+    "down_tasks0": (dict(LPP_PB_DOWN_TASKS="0"), (1, 0, 1, 1, 0)),
+    "down_pf0": (dict(LPP_PB_DOWN_PF="0"), (1, 1, 0, 0, 0)),
+    "chain_pace1": (dict(LPP_PB_CHAIN_PACE="1"), (1, 1, 1, 0, 0)),
+}
+
+
+@pytest.mark.parametrize("switch", list(LAUNCH_FORMS))
+def test_launch_switches_select_their_forms(switch, tmp_path):
+    """The product-basis launch forms are resolved once, when the layout is built (PbState::chain_ok, down_tasks, down_pf, chain_drop_pace,
+    lazy_tx), and printed under LPP_VERBOSE.  Every launch switch still selects its form -- the printed line shows exactly the flags the
+    environment implies, the layout reports the chained step accordingly -- and every form gives the oracle's energy, stopping step and
+    coefficients (chained or three-kernel step) and the oracle's product (plain coupling kernel, which LPP_PB_DOWN_TASKS steers)."""
+    import re
+    case = "ladder_2x6"
+    A, x0, y, xo, init, eo, so, steps_o, ao, bo, e3o, s3o = _pb_oracle(case)
+    env, forms = LAUNCH_FORMS[switch]
+    r, err = _pb_child(case, dict(env, LPP_VERBOSE="1"), tmp_path / "x.npy")
+    lines = re.findall(r"lpp: product-basis launch forms: chain (\d+), down tasks (\d+), chained counter form (\d+), pacing dropped (\d+), lazy exchange (\d+)", err)
+    print(switch, lines, r["chained"], r["e0"], r["steps"])
+    assert lines and all(tuple(map(int, ln)) == forms for ln in lines), (lines, err[-2000:])
+    assert r["chained"] == forms[0]
+    assert rel(np.load(tmp_path / "x.npy"), xo) < SPMV_TOL
     assert abs(r["e0"] - eo[0]) <= E_TOL * abs(eo[0]) and r["steps"] == so
     assert len(r["a"]) == steps_o and rel(np.array(r["a"]), ao) < 1e-8 and rel(np.array(r["b"]), bo) < 1e-8
 
