@@ -67,14 +67,6 @@ std::vector<uint64_t> comb_table()
 	return c;
 }
 
-struct DevBuf {
-	void* p = nullptr;
-	~DevBuf()
-	{
-		if (p) (void)hipFree(p);
-	}
-};
-
 template <int MODEL, typename T>
 lpp_status run_assembly(lpp_engine* e, AsmParams P, DevCsr& A, int force_mode = 0, int64_t force_block = 0, bool raw = false)
 {
@@ -238,21 +230,13 @@ lpp_status assemble_hubbard_pb(lpp_engine* e, AsmParams P, int nup, int ndown, i
 	// LPP_PRODUCT_LAYOUT = 0: never, 1: whenever it applies; unset: from 32 MB per vector on.  Below that everything sits in
 	// L2 / Infinity Cache anyway and the step is launch-bound: measured on Hubbard chains (scripts/experiments/pb_threshold.sh),
 	// 8.5e5 rows 17.2k (product) vs 18.8k (general) iterations/s, 1.2e7 rows 4164 vs 3833, 1.3e8 rows 385 vs 246
-	bool forced = false;
-	if (const char* s = getenv("LPP_PRODUCT_LAYOUT")) {
-		if (atoi(s) == 0) return LPP_OK;
-		forced = true;
-	}
+	const LayoutGate gate = layout_gate(e, "LPP_PRODUCT_LAYOUT");
+	if (gate == LayoutGate::Never) return LPP_OK;
+	const bool forced = gate == LayoutGate::Forced;
 	if (!forced && (size_t)n_up * (size_t)n_dn * sizeof(double) < ((size_t)32 << 20)) return LPP_OK;
 	// complex hoppings run the any-number-of-groups in-block kernel (4 groups): measured 1659 against 1687 iterations/s (general layout) at
 	// 1.2e7 states (0.19 GB per vector), 327 against 170 at 6.4e7 states (1.0 GB per vector; 0.14 against 8.6 GB resident)
 	if (!forced && cplx && (size_t)n_up * (size_t)n_dn * 2 * sizeof(double) < ((size_t)512 << 20)) return LPP_OK;
-	if (e->cfg.spmv_kernel != LPP_SPMV_AUTO || getenv("LPP_SPMV_KERNEL")) return LPP_OK;
-	int want = e->cfg.compress_values;
-	if (const char* s = getenv("LPP_COMPRESS_VALUES")) want = atoi(s);
-	if (want == 0) return LPP_OK;
-	for (const char* k : { "LPP_SHARED_OFFSETS", "LPP_LOCAL16", "LPP_DIAG_CODES", "LPP_BLOCK_TEMPLATE", "LPP_WINDOW_ROWS" })
-		if (getenv(k)) return LPP_OK; // switches of the general layout: measure that one
 	const int64_t pitch = pb_pitch_for(cplx ? 2 * n_up : n_up); // in doubles
 	// rows beyond one LDS window and vectors beyond 4 GiB take the pieces / parts kernels (lpp_pbig_kernels.h); what the layout
 	// cannot hold at all (more than 65535 blocks, coupling lists beyond LDS) comes back from pb_build as "does not apply"
@@ -305,65 +289,44 @@ lpp_status assemble_hubbard_pb(lpp_engine* e, AsmParams P, int nup, int ndown, i
 	if ((rc = fetch_csr(Tm, trp, tci, tva, cplx ? 2 : 1)) != LPP_OK) return rc;
 	if ((rc = fetch_csr(Cm, crp, cci, cva, cplx ? 2 : 1)) != LPP_OK) return rc;
 	// distinct diagonal values over all rows
-	DevBuf table, overflow;
-	HIP_TRY_MEM(hipMalloc(&table.p, sizeof(unsigned long long) * kDictTable));
-	HIP_TRY_MEM(hipMalloc(&overflow.p, sizeof(int)));
-	HIP_TRY(hipMemsetAsync(table.p, 0xff, sizeof(unsigned long long) * kDictTable, st));
-	HIP_TRY(hipMemsetAsync(overflow.p, 0, sizeof(int), st));
+	DictTable table;
+	if ((rc = table.init(st)) != LPP_OK) return rc;
 	AsmParams Pf = P;
 	Pf.row0 = 0;
 	Pf.nloc = P.nrows_global;
 	Pf.part = 0;
 	const int nb = (int)std::max<int64_t>(1, std::min<int64_t>((Pf.nloc + kBlock - 1) / kBlock, 1 << 16));
-	k_pb_diag_collect<ASM_HUBBARD><<<nb, kBlock, 0, st>>>(Pf, (unsigned long long*)table.p, (int*)overflow.p);
-	std::vector<unsigned long long> host(kDictTable);
-	int ov = 0;
-	HIP_TRY(hipMemcpyAsync(host.data(), table.p, sizeof(unsigned long long) * kDictTable, hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipMemcpyAsync(&ov, overflow.p, sizeof(int), hipMemcpyDeviceToHost, st));
+	k_pb_diag_collect<ASM_HUBBARD><<<nb, kBlock, 0, st>>>(Pf, table.dev(), table.dev_overflow());
+	if ((rc = table.fetch(st)) != LPP_OK) return rc;
 	HIP_TRY(hipStreamSynchronize(st));
-	// More than 256 distinct diagonal values (site-dependent hubbardU / potentialV, HubbardHelper.h:138-189: disorder) do not
-	// end the layout: the diagonal then travels as ONE plain f64 stream (8 instead of 1 byte per row), added by the streaming
-	// pass behind the two product kernels (PbCombineArgs::d); T and C stay what they are.  LPP_PB_PLAIN_DIAG=1 forces it (tests).
-	std::vector<unsigned long long> keys;
-	keys.push_back(0ull); // code 0 = +0.0 (padding places of k_pb_down)
-	auto add_key = [&](unsigned long long k) {
-		if (std::find(keys.begin(), keys.end(), k) == keys.end()) keys.push_back(k);
-	};
-	size_t ndiag = 0;
-	for (unsigned long long k : host)
-		if (k != kDictEmpty) ndiag++;
-	bool plain_diag = ov != 0 || ndiag > 250 || (getenv("LPP_PB_PLAIN_DIAG") && atoi(getenv("LPP_PB_PLAIN_DIAG")) != 0);
-	if (plain_diag && getenv("LPP_PB_PLAIN_DIAG") && atoi(getenv("LPP_PB_PLAIN_DIAG")) == 0) return LPP_OK; // switched off: general layout
-	if (!plain_diag)
-		for (unsigned long long k : host)
-			if (k != kDictEmpty) add_key(k);
-	if (!cplx) // (complex couplings have a dictionary of their own: pb_build)
-		for (int64_t b = 0; b < n_dn; b++)
-			for (int64_t p = crp[(size_t)b]; p < crp[(size_t)b + 1] && keys.size() <= 256; p++)
-				if (cci[(size_t)p] != b) {
-					unsigned long long k;
-					std::memcpy(&k, &cva[(size_t)p], 8);
-					add_key(k);
-				}
-	if (keys.size() > 256) return LPP_OK;
-	std::sort(keys.begin(), keys.end());
-	std::vector<double> dict(256);
-	for (size_t i = 0; i < 256; i++) std::memcpy(&dict[i], &keys[std::min(i, keys.size() - 1)], 8);
-	if (cplx) {
-		std::vector<int64_t> rrp;
-		std::vector<int32_t> rci;
-		std::vector<double> rva;
-		pb_realify(n_up, trp.data(), tci.data(), tva.data(), rrp, rci, rva);
-		PbCplxInput cx;
-		cx.n_c = n_up;
-		cx.t_rp = trp.data();
-		cx.t_ci = tci.data();
-		cx.t_va = tva.data();
-		cx.c_va = cva.data();
-		rc = pb_build(e, 2 * n_up, n_dn, rrp.data(), rci.data(), rva.data(), crp.data(), cci.data(), nullptr, dict.data(), (int)keys.size(), 0, -1, 0, 0, &cx);
-	} else
-	rc = pb_build(e, n_up, n_dn, trp.data(), tci.data(), tva.data(), crp.data(), cci.data(), cva.data(), dict.data(), (int)keys.size(), blk0, nblk_loc, pitch_dn,
-	              nblk_padded);
+	// the distinct off-diagonal coupling values, by bit pattern; more than 256 end the layout, so the collection stops there
+	// (complex couplings have a dictionary of their own: pb_build)
+	std::vector<double> cvals;
+	auto seen = [&](const double& v) { return std::any_of(cvals.begin(), cvals.end(), [&](const double& w) { return std::memcmp(&w, &v, 8) == 0; }); };
+	for (int64_t b = 0; !cplx && b < n_dn; b++)
+		for (int64_t p = crp[(size_t)b]; p < crp[(size_t)b + 1] && cvals.size() <= 256; p++)
+			if (cci[(size_t)p] != b && !seen(cva[(size_t)p])) cvals.push_back(cva[(size_t)p]);
+	const PbDict D = pb_diag_dict(table, true, cvals.data(), cvals.size());
+	if (!D.applies) return LPP_OK;
+	const bool plain_diag = D.plain_diag;
+	PbBuildInput in;
+	in.n_up = n_up;
+	in.n_blk = n_dn;
+	in.t_rp = trp.data();
+	in.t_ci = tci.data();
+	in.t_va = tva.data();
+	in.c_rp = crp.data();
+	in.c_ci = cci.data();
+	in.c_va = cva.data();
+	in.dict256 = D.dict.data();
+	in.ndict = D.ndict;
+	if (!cplx) { // (complex hoppings: the single-GPU form, the block range keeps its defaults)
+		in.blk0 = blk0;
+		in.nblk_loc = nblk_loc;
+		in.pitch_dn = pitch_dn;
+		in.nblk_padded = nblk_padded;
+	}
+	rc = pb_build_host(e, in, cplx);
 	if (rc == LPP_ERR_INVALID) { // not representable (e.g. more than 8 distinct in-block values): general path
 		if (getenv("LPP_VERBOSE")) fprintf(stderr, "lpp: the product-basis layout does not apply: %s\n", lpp_last_error());
 		free_pb(e);

@@ -950,32 +950,13 @@ lpp_status alloc_work(lpp_engine* e)
 
 } // namespace lpp
 
-// device scratch released on scope exit
-struct DevScratch {
-	void* p = nullptr;
-	DevScratch() = default;
-	DevScratch(const DevScratch&) = delete;
-	DevScratch& operator=(const DevScratch&) = delete;
-	~DevScratch()
-	{
-		if (p) (void)hipFree(p);
-	}
-	hipError_t alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 8)); }
-	void take(DevScratch& o)
-	{
-		if (p) (void)hipFree(p);
-		p = o.p;
-		o.p = nullptr;
-	}
-};
-
 // Plain CSR order (columns, values) of a matrix whose only resident form is the sliced layout: undo the slot-major
 // order (template-aware), decode the value codes, then merge the per-slice shared entries and the diagonal codes back.
-template <typename T> static lpp_status rebuild_csr_t(lpp_engine* e, const DevCsr& A, DevScratch& col_out, DevScratch& val_out)
+template <typename T> static lpp_status rebuild_csr_t(lpp_engine* e, const DevCsr& A, DevBuf& col_out, DevBuf& val_out)
 {
 	const int64_t* rp = A.rrowptr ? A.rrowptr : A.rowptr; // the sliced arrays hold the rest CSR when entries were split off
 	const int64_t nz = A.rrowptr ? A.rnnz : A.nnz;
-	DevScratch tcol, tval;
+	DevBuf tcol, tval;
 	if (tcol.alloc(sizeof(int32_t) * (size_t)nz) != hipSuccess || tval.alloc(sizeof(T) * (size_t)nz) != hipSuccess)
 		return fail(LPP_ERR_NOMEM, "lpp_engine_get_csr: scratch allocation failed");
 	const int nb2 = (int)std::max<int64_t>(1, std::min<int64_t>((A.geom.nslices + 3) / 4, 8192));
@@ -986,7 +967,7 @@ template <typename T> static lpp_status rebuild_csr_t(lpp_engine* e, const DevCs
 		k_slice_fill<T, true><<<nb2, kBlock, 0, e->stream>>>(A.geom, rp, A.scol, (const T*)A.sval, (int32_t*)tcol.p, plain_vals, 0, A.outs_first ? 1 : 0, A.pad);
 	if (A.coded) k_slice_decode<T><<<nb2, kBlock, 0, e->stream>>>(A.geom, rp, A.codes, A.code_ptr, A.dict, (T*)tval.p, A.tmpl == 2 ? 1 : 0);
 	if (A.rrowptr) {
-		DevScratch fcol, fval;
+		DevBuf fcol, fval;
 		if (fcol.alloc(sizeof(int32_t) * (size_t)A.nnz) != hipSuccess || fval.alloc(sizeof(T) * (size_t)A.nnz) != hipSuccess)
 			return fail(LPP_ERR_NOMEM, "lpp_engine_get_csr: scratch allocation failed");
 		k_dia_merge<T><<<(int)((A.nrows + 255) / 256), 256, 0, e->stream>>>(A.geom, A.rowptr, rp, (const int32_t*)tcol.p, (const T*)tval.p, A.dia_stride,
@@ -1369,7 +1350,7 @@ lpp_status lpp_engine_get_csr(lpp_engine* e, int32_t which, int64_t* nrows, int6
 	HIP_TRY(hipSetDevice(e->cfg.device));
 	HIP_TRY(hipStreamSynchronize(e->stream));
 	// plain (col, val) arrays of one stored CSR on the device: the resident ones, or rebuilt from the sliced layout
-	auto plain_of = [&](const DevCsr& X, DevScratch& scol, DevScratch& sval, const int32_t*& dcol, const void*& dval) -> lpp_status {
+	auto plain_of = [&](const DevCsr& X, DevBuf& scol, DevBuf& sval, const int32_t*& dcol, const void*& dval) -> lpp_status {
 		dcol = X.col;
 		dval = X.val;
 		if (X.nnz == 0 || (dcol && dval)) return LPP_OK;
@@ -1388,7 +1369,7 @@ lpp_status lpp_engine_get_csr(lpp_engine* e, int32_t which, int64_t* nrows, int6
 		P.nb = A.split_nb;
 		P.nparts = A.split_parts;
 		P.pblk = A.split_pblk;
-		DevScratch ic, iv, oc[kSplitMaxParts], ov[kSplitMaxParts], mrp, mc, mv;
+		DevBuf ic, iv, oc[kSplitMaxParts], ov[kSplitMaxParts], mrp, mc, mv;
 		const int32_t* dic = nullptr;
 		const void* div = nullptr;
 		lpp_status st = plain_of(A, ic, iv, dic, div);
@@ -1424,7 +1405,7 @@ lpp_status lpp_engine_get_csr(lpp_engine* e, int32_t which, int64_t* nrows, int6
 	}
 	if (rowptr) HIP_TRY(hipMemcpy(rowptr, A.rowptr, sizeof(int64_t) * (size_t)(A.nrows + 1), hipMemcpyDeviceToHost));
 	if ((colind || values) && A.nnz) {
-		DevScratch scol, sval;
+		DevBuf scol, sval;
 		const int32_t* dcol = nullptr;
 		const void* dval = nullptr;
 		lpp_status st = plain_of(A, scol, sval, dcol, dval);

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <initializer_list>
 #include <string>
 #include <utility>
 #include <vector>
@@ -28,6 +30,25 @@
 	} while (0)
 
 namespace lpp {
+
+// device memory released on scope exit (set-up and read-back scratch)
+struct DevBuf {
+	void* p = nullptr;
+	DevBuf() = default;
+	DevBuf(const DevBuf&) = delete;
+	DevBuf& operator=(const DevBuf&) = delete;
+	~DevBuf()
+	{
+		if (p) (void)hipFree(p);
+	}
+	hipError_t alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 8)); }
+	void take(DevBuf& o)
+	{
+		if (p) (void)hipFree(p);
+		p = o.p;
+		o.p = nullptr;
+	}
+};
 
 // device-resident CSR (+ optional sliced layout used by k_spmv_sliced)
 struct DevCsr {
@@ -349,12 +370,67 @@ struct PbCplxInput {
 };
 // complex in-block matrix (n rows, (re, im) pairs, diagonal skipped) -> the realified one of 2n rows (PbState::cplx)
 void pb_realify(int64_t n, const int64_t* rp, const int32_t* ci, const double* va, std::vector<int64_t>& rrp, std::vector<int32_t>& rci, std::vector<double>& rva);
-// T and C as host CSRs over one species each (diagonal entries are ignored), sorted 256-entry dictionary holding every coupling
-// value; the caller fills pb.dcode (n_blk*pitch codes) afterwards
-lpp_status pb_build(lpp_engine* e, int64_t n_up, int64_t n_blk, const int64_t* t_rp, const int32_t* t_ci, const double* t_va,
-                    const int64_t* c_rp, const int32_t* c_ci, const double* c_va, const double* dict256, int ndict,
-                    int64_t blk0 = 0, int64_t nblk_loc = -1, int64_t pitch_dn = 0, int64_t nblk_padded = 0, const struct PbCplxInput* cx = nullptr,
-                    struct SegPlan* pre = nullptr, int64_t pre_nnz = 0);
+// What pb_build is given: T and C as host CSRs over one species each (diagonal entries are ignored), sorted 256-entry dictionary holding
+// every coupling value; the caller fills pb.dcode (n_blk*pitch codes) afterwards.  Whatever a caller does not set keeps its default.
+struct PbBuildInput {
+	int64_t n_up = 0, n_blk = 0; // positions per block, blocks
+	const int64_t *t_rp = nullptr, *c_rp = nullptr; // the in-block CSR T (null with `pre`) and the coupling CSR C
+	const int32_t *t_ci = nullptr, *c_ci = nullptr;
+	const double *t_va = nullptr, *c_va = nullptr;
+	const double* dict256 = nullptr;
+	int ndict = 0;
+	// several GPUs (transposition exchange): the rank's block range, the row length of its transposed slice, the blocks of that slice
+	int64_t blk0 = 0, nblk_loc = -1, pitch_dn = 0, nblk_padded = 0;
+	const PbCplxInput* cx = nullptr; // complex hoppings
+	struct SegPlan* pre = nullptr; // a ready-made plan of the segmented form (pb_chain; moved from) standing for pre_nnz entries
+	int64_t pre_nnz = 0;
+};
+lpp_status pb_build(lpp_engine* e, const PbBuildInput& in);
+// ... from T and C as the caller holds them: n_up positions, (re, im) values when cplx -- T then goes in realified, the complex matrices as `cx`
+lpp_status pb_build_host(lpp_engine* e, PbBuildInput in, bool cplx);
+
+// ---- shared by the builders of the special layouts (assemble_hubbard_pb, pb_from_csr, pb_chain, tj_build; defined in lpp_pb.hip) ----
+// Until a layout's check has passed the engine must not describe it: `drop` runs on scope exit unless *done
+struct DropUnlessDone {
+	lpp_engine* e;
+	bool* done;
+	void (*drop)(lpp_engine*);
+	~DropUnlessDone()
+	{
+		if (!*done) drop(e);
+	}
+};
+// The admission gate.  `force_switch` (LPP_PRODUCT_LAYOUT, LPP_TJ_LAYOUT): 0 = never, any other value = forced, unset = by size (the
+// thresholds are the caller's).  An explicit kernel choice, uncompressed values and the switches of the general layout mean "measure that
+// one": never.  Read at every call.  The four callers' rules had drifted apart; the differences are inherited as found:
+//   extra: further switches of the general layout (pb_chain and tj_applies list LPP_KEEP_PLAIN_CSR, the other two nothing)
+//   any_compress_value: LPP_COMPRESS_VALUES refuses whatever its value (tj_applies); otherwise only when it resolves to 0
+enum class LayoutGate { Never, Forced, BySize };
+LayoutGate layout_gate(const lpp_engine* e, const char* force_switch, std::initializer_list<const char*> extra = {}, bool any_compress_value = false);
+// The diagonal's dictionary, device part: the table of distinct 64-bit patterns and its overflow flag, allocated and cleared by init();
+// after the caller's collect kernel fetch() enqueues the copies into `host` / `ov` (the caller synchronises)
+struct DictTable {
+	DevBuf table, overflow;
+	std::vector<unsigned long long> host;
+	int ov = 0;
+	unsigned long long* dev() const { return (unsigned long long*)table.p; }
+	int* dev_overflow() const { return (int*)overflow.p; }
+	lpp_status init(hipStream_t st); // once per table
+	lpp_status fetch(hipStream_t st);
+};
+// ... host part: the sorted dictionary pb_build is given, from the table and n_extra further values (the real coupling values).
+// honour_switch: LPP_PB_PLAIN_DIAG is read (assemble_hubbard_pb and pb_from_csr do, pb_chain does not: inherited as found).
+// applies == false: plain diagonal switched off, or more than 256 keys -- the general layout
+struct PbDict {
+	bool applies = false, plain_diag = false; // plain_diag: the diagonal travels as a plain f64 stream, the dictionary holds +0.0 and the extras
+	int ndict = 0;
+	std::vector<double> dict; // 256: the keys ascending by bit pattern, +0.0 first, the last one repeated
+};
+PbDict pb_diag_dict(const DictTable& t, bool honour_switch, const double* extra = nullptr, size_t n_extra = 0);
+// The check of a model's layout against the assembler's row walk: largest |a - b| (dmax) and largest |b| (xmax) over n doubles; *same:
+// within 1e-12 of the largest element
+lpp_status row_walk_compare(lpp_engine* e, int64_t n, const double* a, const double* b, bool* same, double* dmax, double* xmax);
+void sum_i64(hipStream_t st, const int64_t* v, int64_t n, unsigned long long* out); // *out += the sum of v (a device word)
 // A matrix whose off-diagonal part is the hopping matrix of ONE species on a chain -- the S = 1/2 Heisenberg chain in the S_z basis
 // (Heisenberg.h:278-307: S+S- moves an up spin, nothing sits between neighbours) -- as ONE block of the product-basis form: the in-block
 // kernel k_pb_up_seg and the streaming pass, no couplings.  Planned from the model alone (P: the assembler's parameters of the same model,

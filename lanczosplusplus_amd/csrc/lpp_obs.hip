@@ -296,14 +296,6 @@ lpp_status acc_modified_dev(lpp_engine* e, int op, int site, int spin, int L, in
 	return apply_dev(e, op, site, spin, L, nup, ndn, isign, 0.0, d_src, d_dst, acc, has, nullptr);
 }
 
-struct DevBuf {
-	void* p = nullptr;
-	~DevBuf()
-	{
-		if (p) (void)hipFree(p);
-	}
-};
-
 int blas_blocks(int64_t n2)
 {
 	const int64_t b = (n2 + kBlock - 1) / kBlock;

@@ -84,6 +84,135 @@ void pb_realify(int64_t n, const int64_t* rp, const int32_t* ci, const double* v
 		}
 }
 
+// ---- shared by the builders of the special layouts (lpp_engine_impl.h) -----------------------------------------------------------------
+LayoutGate layout_gate(const lpp_engine* e, const char* force_switch, std::initializer_list<const char*> extra, bool any_compress_value)
+{
+	bool forced = false;
+	if (const char* s = getenv(force_switch)) {
+		if (atoi(s) == 0) return LayoutGate::Never;
+		forced = true;
+	}
+	if (e->cfg.spmv_kernel != LPP_SPMV_AUTO || getenv("LPP_SPMV_KERNEL")) return LayoutGate::Never;
+	int want = e->cfg.compress_values;
+	if (const char* s = getenv("LPP_COMPRESS_VALUES")) want = any_compress_value ? 0 : atoi(s);
+	if (want == 0) return LayoutGate::Never;
+	for (const char* k : { "LPP_SHARED_OFFSETS", "LPP_LOCAL16", "LPP_DIAG_CODES", "LPP_BLOCK_TEMPLATE", "LPP_WINDOW_ROWS" })
+		if (getenv(k)) return LayoutGate::Never; // switches of the general layout: measure that one
+	for (const char* k : extra)
+		if (getenv(k)) return LayoutGate::Never;
+	return forced ? LayoutGate::Forced : LayoutGate::BySize;
+}
+
+lpp_status DictTable::init(hipStream_t st)
+{
+	HIP_TRY_MEM(hipMalloc(&table.p, sizeof(unsigned long long) * kDictTable));
+	HIP_TRY_MEM(hipMalloc(&overflow.p, sizeof(int)));
+	HIP_TRY(hipMemsetAsync(table.p, 0xff, sizeof(unsigned long long) * kDictTable, st));
+	HIP_TRY(hipMemsetAsync(overflow.p, 0, sizeof(int), st));
+	return LPP_OK;
+}
+
+lpp_status DictTable::fetch(hipStream_t st)
+{
+	host.resize(kDictTable);
+	HIP_TRY(hipMemcpyAsync(host.data(), table.p, sizeof(unsigned long long) * kDictTable, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipMemcpyAsync(&ov, overflow.p, sizeof(int), hipMemcpyDeviceToHost, st));
+	return LPP_OK;
+}
+
+// More than 256 distinct diagonal values (site-dependent hubbardU / potentialV, HubbardHelper.h:138-189: disorder) do not end the layout:
+// the diagonal then travels as ONE plain f64 stream (8 instead of 1 byte per row), added by the streaming pass behind the two product
+// kernels (PbCombineArgs::d); T and C stay what they are.  LPP_PB_PLAIN_DIAG=1 forces it (tests).
+PbDict pb_diag_dict(const DictTable& t, bool honour_switch, const double* extra, size_t n_extra)
+{
+	PbDict d;
+	std::vector<unsigned long long> keys;
+	keys.push_back(0ull); // code 0 = +0.0 (padding places of k_pb_down)
+	auto add_key = [&](unsigned long long k) {
+		if (std::find(keys.begin(), keys.end(), k) == keys.end()) keys.push_back(k);
+	};
+	size_t ndiag = 0;
+	for (unsigned long long k : t.host)
+		if (k != kDictEmpty) ndiag++;
+	const char* sw = honour_switch ? getenv("LPP_PB_PLAIN_DIAG") : nullptr;
+	d.plain_diag = t.ov != 0 || ndiag > 250 || (sw && atoi(sw) != 0);
+	if (d.plain_diag && sw && atoi(sw) == 0) return d; // switched off: general layout
+	if (!d.plain_diag)
+		for (unsigned long long k : t.host)
+			if (k != kDictEmpty) add_key(k);
+	for (size_t p = 0; p < n_extra && keys.size() <= 256; p++) {
+		unsigned long long k;
+		std::memcpy(&k, &extra[p], 8);
+		add_key(k);
+	}
+	if (keys.size() > 256) return d;
+	std::sort(keys.begin(), keys.end());
+	d.dict.resize(256);
+	for (size_t i = 0; i < 256; i++) std::memcpy(&d.dict[i], &keys[std::min(i, keys.size() - 1)], 8);
+	d.ndict = (int)keys.size();
+	d.applies = true;
+	return d;
+}
+
+lpp_status pb_build_host(lpp_engine* e, PbBuildInput in, bool cplx)
+{
+	if (!cplx) return pb_build(e, in);
+	std::vector<int64_t> rrp;
+	std::vector<int32_t> rci;
+	std::vector<double> rva;
+	pb_realify(in.n_up, in.t_rp, in.t_ci, in.t_va, rrp, rci, rva);
+	const PbCplxInput cx { in.n_up, in.t_rp, in.t_ci, in.t_va, in.c_va };
+	in.cx = &cx;
+	in.n_up *= 2;
+	in.t_rp = rrp.data();
+	in.t_ci = rci.data();
+	in.t_va = rva.data();
+	in.c_va = nullptr;
+	return pb_build(e, in);
+}
+
+namespace {
+// largest |a - b| and largest |b| as the bit patterns of non-negative doubles (ordered like unsigned integers)
+__global__ void k_max_diff(int64_t n, const double* __restrict__ a, const double* __restrict__ b, unsigned long long* __restrict__ out)
+{
+	double d = 0.0, m = 0.0;
+	for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+		d = fmax(d, fabs(a[i] - b[i]));
+		m = fmax(m, fabs(b[i]));
+		if (a[i] != a[i]) d = 1e300;
+	}
+	atomicMax(out, (unsigned long long)__double_as_longlong(d));
+	atomicMax(out + 1, (unsigned long long)__double_as_longlong(m));
+}
+__global__ void k_sum_i64(const int64_t* __restrict__ v, int64_t n, unsigned long long* __restrict__ out)
+{
+	unsigned long long s = 0;
+	for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) s += (unsigned long long)v[k];
+	for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+	if ((threadIdx.x & 63) == 0) atomicAdd(out, s);
+}
+} // namespace
+
+void sum_i64(hipStream_t st, const int64_t* v, int64_t n, unsigned long long* out) { k_sum_i64<<<1024, 256, 0, st>>>(v, n, out); }
+
+lpp_status row_walk_compare(lpp_engine* e, int64_t n, const double* a, const double* b, bool* same, double* dmax, double* xmax)
+{
+	*same = false;
+	hipStream_t st = e->stream;
+	DevBuf d_cmp;
+	HIP_TRY_MEM(hipMalloc(&d_cmp.p, sizeof(unsigned long long) * 2));
+	HIP_TRY(hipMemsetAsync(d_cmp.p, 0, sizeof(unsigned long long) * 2, st));
+	k_max_diff<<<1024, 256, 0, st>>>(n, a, b, (unsigned long long*)d_cmp.p);
+	unsigned long long cmp[2] = { 0, 0 };
+	HIP_TRY(hipMemcpyAsync(cmp, d_cmp.p, sizeof(cmp), hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipStreamSynchronize(st));
+	std::memcpy(dmax, &cmp[0], 8);
+	std::memcpy(xmax, &cmp[1], 8);
+	*same = *dmax <= 1e-12 * std::max(*xmax, 1e-300);
+	return LPP_OK;
+}
+
 // ---- kernel arguments: everything that comes from the state, in one place per struct; whatever is not named here is zero -----------
 // k_pb_down (all forms) and k_pb_down_image on rows of `pitch` positions; the caller sets y, z, u_in, shift, partial, sc, u_has_beta, pf_lead
 static PbDownArgs down_args(const PbState& B, int64_t pitch)
@@ -143,10 +272,16 @@ static bool pb_down_pf_fits(const PbState& B) { return B.down_lds_pf <= (size_t)
 // a panel (16 positions = 128 bytes of every block) fits an XCD's 4 MB L2 with room to spare
 static bool pb_panel_fits_l2(int64_t n_blk) { return (size_t)n_blk * 128 <= (size_t)3 << 20; }
 
-lpp_status pb_build(lpp_engine* e, int64_t n_up, int64_t n_blk, const int64_t* t_rp, const int32_t* t_ci, const double* t_va,
-                    const int64_t* c_rp, const int32_t* c_ci, const double* c_va, const double* dict256, int ndict,
-                    int64_t blk0, int64_t nblk_loc, int64_t pitch_dn, int64_t nblk_padded, const PbCplxInput* cx, SegPlan* pre, int64_t pre_nnz)
+lpp_status pb_build(lpp_engine* e, const PbBuildInput& in)
 {
+	const int64_t n_up = in.n_up, n_blk = in.n_blk, blk0 = in.blk0, pre_nnz = in.pre_nnz;
+	const int64_t *const t_rp = in.t_rp, *const c_rp = in.c_rp;
+	const int32_t *const t_ci = in.t_ci, *const c_ci = in.c_ci;
+	const double *const t_va = in.t_va, *const c_va = in.c_va, *const dict256 = in.dict256;
+	const int ndict = in.ndict;
+	int64_t nblk_loc = in.nblk_loc, pitch_dn = in.pitch_dn, nblk_padded = in.nblk_padded;
+	const PbCplxInput* const cx = in.cx;
+	SegPlan* const pre = in.pre;
 	free_pb(e);
 	PbState& B = e->pb;
 	hipStream_t st = e->stream;
@@ -1095,27 +1230,12 @@ lpp_status pb_from_csr(lpp_engine* e, const DevCsr& A, int64_t n_up, bool* done)
 	const size_t vd = cplx ? 2 : 1; // doubles per matrix value
 	const int64_t n_blk = A.nrows / n_up;
 	if (n_blk < 2 || n_blk > 65535) return LPP_OK;
-	bool forced = false;
-	if (const char* s = getenv("LPP_PRODUCT_LAYOUT")) {
-		if (atoi(s) == 0) return LPP_OK;
-		forced = true;
-	}
-	if (!forced && (size_t)A.nrows * vd * sizeof(double) < (cplx ? (size_t)512 << 20 : (size_t)32 << 20)) return LPP_OK; // as for device assembly (assemble_hubbard_pb)
-	if (e->cfg.spmv_kernel != LPP_SPMV_AUTO || getenv("LPP_SPMV_KERNEL")) return LPP_OK;
-	int want = e->cfg.compress_values;
-	if (const char* s = getenv("LPP_COMPRESS_VALUES")) want = atoi(s);
-	if (want == 0) return LPP_OK;
-	for (const char* k : { "LPP_SHARED_OFFSETS", "LPP_LOCAL16", "LPP_DIAG_CODES", "LPP_BLOCK_TEMPLATE", "LPP_WINDOW_ROWS" })
-		if (getenv(k)) return LPP_OK; // switches of the general layout: measure that one
+	const LayoutGate gate = layout_gate(e, "LPP_PRODUCT_LAYOUT");
+	if (gate == LayoutGate::Never) return LPP_OK;
+	if (gate == LayoutGate::BySize && (size_t)A.nrows * vd * sizeof(double) < (cplx ? (size_t)512 << 20 : (size_t)32 << 20)) return LPP_OK; // as for device assembly (assemble_hubbard_pb)
 	hipStream_t st = e->stream;
 	const int64_t pitch = pb_pitch_for(cplx ? 2 * n_up : n_up); // in doubles
-	struct Buf {
-		void* p = nullptr;
-		~Buf()
-		{
-			if (p) (void)hipFree(p);
-		}
-	} d_bad, d_clen, d_cptr, d_ccol, d_cval, d_dval, d_table, d_ov;
+	DevBuf d_bad, d_clen, d_cptr, d_ccol, d_cval, d_dval;
 	HIP_TRY_MEM(hipMalloc(&d_bad.p, sizeof(int) * 2));
 	HIP_TRY(hipMemsetAsync(d_bad.p, 0, sizeof(int) * 2, st));
 	// T: block 0's rows, columns inside the block
@@ -1164,15 +1284,12 @@ lpp_status pb_from_csr(lpp_engine* e, const DevCsr& A, int64_t n_up, bool* done)
 	else
 		k_pb_csr_diagonal<<<nbr, 256, 0, st>>>(n_up, n_blk, pitch, A.rowptr, A.col, (const double*)A.val, (double*)d_dval.p, (int*)d_bad.p);
 	// its distinct values
-	HIP_TRY_MEM(hipMalloc(&d_table.p, sizeof(unsigned long long) * kDictTable));
-	HIP_TRY_MEM(hipMalloc(&d_ov.p, sizeof(int)));
-	HIP_TRY(hipMemsetAsync(d_table.p, 0xff, sizeof(unsigned long long) * kDictTable, st));
-	HIP_TRY(hipMemsetAsync(d_ov.p, 0, sizeof(int), st));
-	k_dict_collect<<<2048, kBlock, 0, st>>>((const double*)d_dval.p, (int64_t)loc, (unsigned long long*)d_table.p, (int*)d_ov.p);
-	std::vector<unsigned long long> host(kDictTable);
-	int ov = 0, bad[2] = { 0, 0 };
-	HIP_TRY(hipMemcpyAsync(host.data(), d_table.p, sizeof(unsigned long long) * kDictTable, hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipMemcpyAsync(&ov, d_ov.p, sizeof(int), hipMemcpyDeviceToHost, st));
+	DictTable table;
+	lpp_status rc;
+	if ((rc = table.init(st)) != LPP_OK) return rc;
+	k_dict_collect<<<2048, kBlock, 0, st>>>((const double*)d_dval.p, (int64_t)loc, table.dev(), table.dev_overflow());
+	int bad[2] = { 0, 0 };
+	if ((rc = table.fetch(st)) != LPP_OK) return rc;
 	HIP_TRY(hipMemcpyAsync(bad, d_bad.p, sizeof(int) * 2, hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipStreamSynchronize(st));
@@ -1188,44 +1305,21 @@ lpp_status pb_from_csr(lpp_engine* e, const DevCsr& A, int64_t n_up, bool* done)
 			}
 		trp[(size_t)r + 1] = (int64_t)tci.size();
 	}
-	std::vector<unsigned long long> keys;
-	keys.push_back(0ull);
-	auto add_key = [&](unsigned long long k) {
-		if (std::find(keys.begin(), keys.end(), k) == keys.end()) keys.push_back(k);
-	};
-	size_t ndiag = 0;
-	for (unsigned long long k : host)
-		if (k != kDictEmpty) ndiag++;
-	bool plain_diag = ov != 0 || ndiag > 250 || (getenv("LPP_PB_PLAIN_DIAG") && atoi(getenv("LPP_PB_PLAIN_DIAG")) != 0);
-	if (plain_diag && getenv("LPP_PB_PLAIN_DIAG") && atoi(getenv("LPP_PB_PLAIN_DIAG")) == 0) return LPP_OK;
-	if (!plain_diag)
-		for (unsigned long long k : host)
-			if (k != kDictEmpty) add_key(k);
-	for (int64_t p = 0; !cplx && p < cz && keys.size() <= 256; p++) { // (complex couplings: a dictionary of their own, pb_build)
-		unsigned long long k;
-		std::memcpy(&k, &cva[(size_t)p], 8);
-		add_key(k);
-	}
-	if (keys.size() > 256) return LPP_OK;
-	std::sort(keys.begin(), keys.end());
-	std::vector<double> dict(256);
-	for (size_t i = 0; i < 256; i++) std::memcpy(&dict[i], &keys[std::min(i, keys.size() - 1)], 8);
+	const PbDict D = pb_diag_dict(table, true, cplx ? nullptr : cva.data(), cplx ? 0 : (size_t)cz); // (complex couplings: a dictionary of their own, pb_build)
+	if (!D.applies) return LPP_OK;
 	// two work vectors + the two parts of a product + the diagonal must fit once the CSR is gone (it is still resident here)
-	lpp_status rc;
-	if (cplx) {
-		std::vector<int64_t> rrp;
-		std::vector<int32_t> rci;
-		std::vector<double> rva;
-		pb_realify(n_up, trp.data(), tci.data(), tva.data(), rrp, rci, rva);
-		PbCplxInput cx;
-		cx.n_c = n_up;
-		cx.t_rp = trp.data();
-		cx.t_ci = tci.data();
-		cx.t_va = tva.data();
-		cx.c_va = cva.data();
-		rc = pb_build(e, 2 * n_up, n_blk, rrp.data(), rci.data(), rva.data(), crp.data(), cci.data(), nullptr, dict.data(), (int)keys.size(), 0, -1, 0, 0, &cx);
-	} else
-		rc = pb_build(e, n_up, n_blk, trp.data(), tci.data(), tva.data(), crp.data(), cci.data(), cva.data(), dict.data(), (int)keys.size());
+	PbBuildInput in;
+	in.n_up = n_up;
+	in.n_blk = n_blk;
+	in.t_rp = trp.data();
+	in.t_ci = tci.data();
+	in.t_va = tva.data();
+	in.c_rp = crp.data();
+	in.c_ci = cci.data();
+	in.c_va = cva.data();
+	in.dict256 = D.dict.data();
+	in.ndict = D.ndict;
+	rc = pb_build_host(e, in, cplx);
 	if (rc == LPP_ERR_INVALID || rc == LPP_ERR_NOMEM) { // not representable, or no room beside the CSR: the general layout
 		if (getenv("LPP_VERBOSE")) fprintf(stderr, "lpp: the product-basis layout does not apply to the uploaded matrix: %s\n", lpp_last_error());
 		free_pb(e);
@@ -1234,19 +1328,12 @@ lpp_status pb_from_csr(lpp_engine* e, const DevCsr& A, int64_t n_up, bool* done)
 	if (rc != LPP_OK) return rc;
 	PbState& B = e->pb;
 	// until every row has been verified the engine must not describe a product-basis matrix: any early return below drops the layout
-	struct Undo {
-		lpp_engine* e;
-		bool* done;
-		~Undo()
-		{
-			if (!*done) free_pb(e);
-		}
-	} undo { e, done };
+	DropUnlessDone undo { e, done, free_pb };
 	if (B.perm) { // the diagonal was read off the CSR in the basis order: into the stored order (pb.u is free until the first product)
 		k_pb_permute<true><<<nbr, 256, 0, st>>>(B.u, (const double*)d_dval.p, B.perm, n_blk, n_up, pitch);
 		HIP_TRY(hipMemcpyAsync(d_dval.p, B.u, sizeof(double) * loc, hipMemcpyDeviceToDevice, st));
 	}
-	if (plain_diag) {
+	if (D.plain_diag) {
 		B.dval = (double*)d_dval.p; // the codes stay 0 (+0.0)
 		d_dval.p = nullptr;
 	} else {
@@ -1267,45 +1354,14 @@ lpp_status pb_from_csr(lpp_engine* e, const DevCsr& A, int64_t n_up, bool* done)
 }
 
 // ---- one block: the S = 1/2 Heisenberg chain ------------------------------------------------------------------------------
-namespace {
-// largest |a - b| and largest |b| as the bit patterns of non-negative doubles (ordered like unsigned integers)
-__global__ void k_max_diff(int64_t n, const double* __restrict__ a, const double* __restrict__ b, unsigned long long* __restrict__ out)
-{
-	double d = 0.0, m = 0.0;
-	for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-		d = fmax(d, fabs(a[i] - b[i]));
-		m = fmax(m, fabs(b[i]));
-		if (a[i] != a[i]) d = 1e300;
-	}
-	atomicMax(out, (unsigned long long)__double_as_longlong(d));
-	atomicMax(out + 1, (unsigned long long)__double_as_longlong(m));
-}
-__global__ void k_sum_i64(const int64_t* __restrict__ v, int64_t n, unsigned long long* __restrict__ out)
-{
-	unsigned long long s = 0;
-	for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) s += (unsigned long long)v[k];
-	for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-	if ((threadIdx.x & 63) == 0) atomicAdd(out, s);
-}
-} // namespace
-
 lpp_status pb_chain(lpp_engine* e, const AsmParams& P, int L, int n, const std::vector<double>& hv, bool* done)
 {
 	*done = false;
 	if (e->is_complex || P.nloc <= 0 || P.model != ASM_HEISENBERG) return LPP_OK;
-	bool forced = false;
-	if (const char* s = getenv("LPP_PRODUCT_LAYOUT")) {
-		if (atoi(s) == 0) return LPP_OK;
-		forced = true;
-	}
+	const LayoutGate gate = layout_gate(e, "LPP_PRODUCT_LAYOUT", { "LPP_KEEP_PLAIN_CSR" }); // (the extra switch: inherited as found)
+	if (gate == LayoutGate::Never) return LPP_OK;
 	const int64_t n_up = P.nloc, pitch = pb_pitch_for(n_up);
-	if (!forced && (size_t)n_up * sizeof(double) < ((size_t)32 << 20)) return LPP_OK; // as for the Hubbard matrices (assemble_hubbard_pb)
-	if (e->cfg.spmv_kernel != LPP_SPMV_AUTO || getenv("LPP_SPMV_KERNEL")) return LPP_OK;
-	int want = e->cfg.compress_values;
-	if (const char* s = getenv("LPP_COMPRESS_VALUES")) want = atoi(s);
-	if (want == 0) return LPP_OK;
-	for (const char* k : { "LPP_SHARED_OFFSETS", "LPP_LOCAL16", "LPP_DIAG_CODES", "LPP_BLOCK_TEMPLATE", "LPP_WINDOW_ROWS", "LPP_KEEP_PLAIN_CSR" })
-		if (getenv(k)) return LPP_OK; // switches of the general layout: measure that one
+	if (gate == LayoutGate::BySize && (size_t)n_up * sizeof(double) < ((size_t)32 << 20)) return LPP_OK; // as for the Hubbard matrices (assemble_hubbard_pb)
 	if (getenv("LPP_PB_SEG") && atoi(getenv("LPP_PB_SEG")) == 0) return LPP_OK;
 	if ((size_t)(pitch + kPbZeroSlots) * sizeof(double) <= (size_t)156 * 1024 && !getenv("LPP_PB_PIECE_ROWS")) return LPP_OK; // a row that fits one LDS window: the general layout's window kernel
 	int wcap = 8128;
@@ -1321,13 +1377,7 @@ lpp_status pb_chain(lpp_engine* e, const AsmParams& P, int L, int n, const std::
 		        ok ? "planned" : "does not apply", SP.L, SP.n, SP.s, SP.segs.size(), SP.items.size(), SP.wmax, SP.max_cross, SP.max_hh);
 	if (!ok || SP.n_up != n_up || SP.nc_pad > 2) return LPP_OK; // (one block per workgroup: the instances with <= 2 pairs of cross hops)
 	hipStream_t st = e->stream;
-	struct Buf {
-		void* p = nullptr;
-		~Buf()
-		{
-			if (p) (void)hipFree(p);
-		}
-	} d_dval, d_table, d_ov, d_len, d_sum, d_y, d_x, d_ys, d_xs, d_cmp;
+	DevBuf d_dval, d_len, d_sum, d_y, d_x, d_ys, d_xs;
 	// D: the diagonal of every row straight from the state (the assembler's diag_of: Heisenberg.h:251-275 in the reference's loop order),
 	// in the basis order; and the number of entries of the CSR this stands for (the assembler's counting pass)
 	const size_t loc = (size_t)pitch;
@@ -1339,36 +1389,28 @@ lpp_status pb_chain(lpp_engine* e, const AsmParams& P, int L, int n, const std::
 	HIP_TRY_MEM(hipMalloc(&d_sum.p, sizeof(unsigned long long)));
 	HIP_TRY(hipMemsetAsync(d_sum.p, 0, sizeof(unsigned long long), st));
 	k_asm_count<ASM_HEISENBERG><<<nbr, kBlock, 0, st>>>(P, (int64_t*)d_len.p);
-	k_sum_i64<<<1024, 256, 0, st>>>((const int64_t*)d_len.p, n_up, (unsigned long long*)d_sum.p);
-	HIP_TRY_MEM(hipMalloc(&d_table.p, sizeof(unsigned long long) * kDictTable));
-	HIP_TRY_MEM(hipMalloc(&d_ov.p, sizeof(int)));
-	HIP_TRY(hipMemsetAsync(d_table.p, 0xff, sizeof(unsigned long long) * kDictTable, st));
-	HIP_TRY(hipMemsetAsync(d_ov.p, 0, sizeof(int), st));
-	k_dict_collect<<<2048, kBlock, 0, st>>>((const double*)d_dval.p, (int64_t)loc, (unsigned long long*)d_table.p, (int*)d_ov.p);
-	std::vector<unsigned long long> host(kDictTable);
-	int ov = 0;
+	sum_i64(st, (const int64_t*)d_len.p, n_up, (unsigned long long*)d_sum.p);
+	DictTable table;
+	if ((rc = table.init(st)) != LPP_OK) return rc;
+	k_dict_collect<<<2048, kBlock, 0, st>>>((const double*)d_dval.p, (int64_t)loc, table.dev(), table.dev_overflow());
 	unsigned long long nnz = 0;
-	HIP_TRY(hipMemcpyAsync(host.data(), d_table.p, sizeof(unsigned long long) * kDictTable, hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipMemcpyAsync(&ov, d_ov.p, sizeof(int), hipMemcpyDeviceToHost, st));
+	if ((rc = table.fetch(st)) != LPP_OK) return rc;
 	HIP_TRY(hipMemcpyAsync(&nnz, d_sum.p, sizeof(nnz), hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipStreamSynchronize(st));
 	(void)hipFree(d_len.p);
 	d_len.p = nullptr;
-	std::vector<unsigned long long> keys;
-	keys.push_back(0ull);
-	size_t ndiag = 0;
-	for (unsigned long long k : host)
-		if (k != kDictEmpty) ndiag++;
-	const bool plain_diag = ov != 0 || ndiag > 250;
-	if (!plain_diag)
-		for (unsigned long long k : host)
-			if (k != kDictEmpty && std::find(keys.begin(), keys.end(), k) == keys.end()) keys.push_back(k);
-	std::sort(keys.begin(), keys.end());
-	std::vector<double> dict(256);
-	for (size_t i = 0; i < 256; i++) std::memcpy(&dict[i], &keys[std::min(i, keys.size() - 1)], 8);
+	const PbDict D = pb_diag_dict(table, false); // (LPP_PB_PLAIN_DIAG is not honoured here: inherited as found; at most 251 keys, so it always applies)
 	const int64_t c_rp[2] = { 0, 0 };
-	rc = pb_build(e, n_up, 1, nullptr, nullptr, nullptr, c_rp, nullptr, nullptr, dict.data(), (int)keys.size(), 0, -1, 0, 0, nullptr, &SP, (int64_t)nnz);
+	PbBuildInput in;
+	in.n_up = n_up;
+	in.n_blk = 1;
+	in.c_rp = c_rp;
+	in.dict256 = D.dict.data();
+	in.ndict = D.ndict;
+	in.pre = &SP;
+	in.pre_nnz = (int64_t)nnz;
+	rc = pb_build(e, in);
 	if (rc == LPP_ERR_INVALID || rc == LPP_ERR_NOMEM) {
 		if (getenv("LPP_VERBOSE")) fprintf(stderr, "lpp: the chain keeps the general layout: %s\n", lpp_last_error());
 		free_pb(e);
@@ -1376,18 +1418,11 @@ lpp_status pb_chain(lpp_engine* e, const AsmParams& P, int L, int n, const std::
 	}
 	if (rc != LPP_OK) return rc;
 	PbState& B = e->pb;
-	struct Undo { // until the check below has passed the engine must not describe a product-basis matrix
-		lpp_engine* e;
-		bool* done;
-		~Undo()
-		{
-			if (!*done) free_pb(e);
-		}
-	} undo { e, done };
+	DropUnlessDone undo { e, done, free_pb }; // until the check below has passed the engine must not describe a product-basis matrix
 	// the diagonal into the stored order of the positions (pb.u is free until the first product)
 	k_pb_permute<true><<<nbr, 256, 0, st>>>(B.u, (const double*)d_dval.p, B.perm, 1, n_up, pitch);
 	HIP_TRY(hipMemcpyAsync(d_dval.p, B.u, sizeof(double) * loc, hipMemcpyDeviceToDevice, st));
-	if (plain_diag) {
+	if (D.plain_diag) {
 		B.dval = (double*)d_dval.p; // the codes stay 0 (+0.0)
 		d_dval.p = nullptr;
 	} else
@@ -1398,11 +1433,9 @@ lpp_status pb_chain(lpp_engine* e, const AsmParams& P, int L, int n, const std::
 	HIP_TRY_MEM(hipMalloc(&d_x.p, sizeof(double) * loc));
 	HIP_TRY_MEM(hipMalloc(&d_ys.p, sizeof(double) * loc));
 	HIP_TRY_MEM(hipMalloc(&d_xs.p, sizeof(double) * loc));
-	HIP_TRY_MEM(hipMalloc(&d_cmp.p, sizeof(unsigned long long) * 2));
 	HIP_TRY(hipMemsetAsync(d_y.p, 0, sizeof(double) * loc, st));
 	HIP_TRY(hipMemsetAsync(d_x.p, 0, sizeof(double) * loc, st));
 	HIP_TRY(hipMemsetAsync(d_xs.p, 0, sizeof(double) * loc, st));
-	HIP_TRY(hipMemsetAsync(d_cmp.p, 0, sizeof(unsigned long long) * 2, st));
 	k_fill_random<<<1024, 256, 0, st>>>((double*)d_y.p, n_up, 0, 4711);
 	k_asm_apply<ASM_HEISENBERG, double, false><<<nbr, kBlock, 0, st>>>(P, (const double*)d_y.p, (double*)d_x.p, nullptr, EpiScale { nullptr, nullptr, 0 });
 	k_pb_permute<true><<<nbr, 256, 0, st>>>((double*)d_ys.p, (const double*)d_y.p, B.perm, 1, n_up, pitch);
@@ -1410,16 +1443,11 @@ lpp_status pb_chain(lpp_engine* e, const AsmParams& P, int L, int n, const std::
 	e->pitch = pitch;
 	pb_launch(e, d_ys.p, d_xs.p, nullptr); // x += H y on a zeroed x
 	k_pb_permute<false><<<nbr, 256, 0, st>>>((double*)d_y.p, (const double*)d_xs.p, B.perm, 1, n_up, pitch); // back into the basis order (d_y is free now)
-	k_max_diff<<<1024, 256, 0, st>>>(n_up, (const double*)d_y.p, (const double*)d_x.p, (unsigned long long*)d_cmp.p);
-	unsigned long long cmp[2] = { 0, 0 };
-	HIP_TRY(hipMemcpyAsync(cmp, d_cmp.p, sizeof(cmp), hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipStreamSynchronize(st));
-	double dmax, xmax;
-	std::memcpy(&dmax, &cmp[0], 8);
-	std::memcpy(&xmax, &cmp[1], 8);
+	bool same = false;
+	double dmax = 0.0, xmax = 0.0;
+	if ((rc = row_walk_compare(e, n_up, (const double*)d_y.p, (const double*)d_x.p, &same, &dmax, &xmax)) != LPP_OK) return rc;
 	if (getenv("LPP_VERBOSE")) fprintf(stderr, "lpp: chain layout against the assembler's row walk: largest difference %.3g of %.3g\n", dmax, xmax);
-	if (!(dmax <= 1e-12 * std::max(xmax, 1e-300))) return LPP_OK; // not the same matrix: the general layout (the guard drops this one)
+	if (!same) return LPP_OK; // not the same matrix: the general layout (the guard drops this one)
 	B.chain_model = true; // (the caller records the model: lpp_engine_get_csr re-runs the assembler from it)
 	*done = true;
 	return LPP_OK;
@@ -1430,13 +1458,7 @@ lpp_status pb_get_csr(lpp_engine* e, int64_t* rowptr, int32_t* colind, void* val
 	const PbState& B = e->pb;
 	const int64_t n = (B.cplx ? B.n_c : B.n_up) * B.n_blk;
 	const size_t vsz = B.cplx ? 2 * sizeof(double) : sizeof(double);
-	struct Buf {
-		void* p = nullptr;
-		~Buf()
-		{
-			if (p) (void)hipFree(p);
-		}
-	} drp, dci, dva;
+	DevBuf drp, dci, dva;
 	if (rowptr) HIP_TRY_MEM(hipMalloc(&drp.p, sizeof(int64_t) * (size_t)(n + 1)));
 	if (colind || values) {
 		HIP_TRY_MEM(hipMalloc(&dci.p, sizeof(int32_t) * (size_t)std::max<int64_t>(B.nnz, 1)));

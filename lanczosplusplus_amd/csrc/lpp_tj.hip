@@ -16,14 +16,6 @@ using namespace lpp;
 
 namespace {
 
-struct Buf {
-	void* p = nullptr;
-	~Buf()
-	{
-		if (p) (void)hipFree(p);
-	}
-};
-
 template <typename V> lpp_status to_dev(V** dst, const std::vector<V>& src, hipStream_t st)
 {
 	HIP_TRY_MEM(hipMalloc((void**)dst, sizeof(V) * std::max<size_t>(src.size(), 1)));
@@ -108,27 +100,6 @@ __global__ void k_tj_fill_random(double* __restrict__ v, const int32_t* __restri
 	}
 }
 
-__global__ void k_tj_sum_i64(const int64_t* __restrict__ v, int64_t n, unsigned long long* __restrict__ out)
-{
-	unsigned long long s = 0;
-	for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) s += (unsigned long long)v[k];
-	for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-	if ((threadIdx.x & 63) == 0) atomicAdd(out, s);
-}
-
-// largest |a - b| and largest |b| over n doubles, as the bit patterns of non-negative doubles (ordered like unsigned integers)
-__global__ void k_tj_max_diff(int64_t n, const double* __restrict__ a, const double* __restrict__ b, unsigned long long* __restrict__ out)
-{
-	double d = 0.0, m = 0.0;
-	for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-		d = fmax(d, fabs(a[i] - b[i]));
-		m = fmax(m, fabs(b[i]));
-		if (a[i] != a[i]) d = 1e300;
-	}
-	atomicMax(out, (unsigned long long)__double_as_longlong(d));
-	atomicMax(out + 1, (unsigned long long)__double_as_longlong(m));
-}
-
 int blocks_for(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 1 << 16)); }
 
 } // namespace
@@ -143,6 +114,13 @@ void free_tj(lpp_engine* e)
 		if (p) (void)hipFree(p);
 	S = TjState();
 	if (was) e->pitch = e->pitch_rows = e->pitch_blocks = 0;
+}
+
+// what tj_build leaves behind when its check does not pass: nothing, the pitch it sets for the check's product included
+static void tj_drop(lpp_engine* e)
+{
+	free_tj(e);
+	e->pitch = e->pitch_rows = e->pitch_blocks = 0;
 }
 
 int tj_launch(lpp_engine* e, const void* src, void* x, const void* ydot, double* partial, const EpiScale& sc)
@@ -195,7 +173,7 @@ int tj_launch(lpp_engine* e, const void* src, void* x, const void* ydot, double*
 lpp_status tj_vec_from_host(lpp_engine* e, double* dev, const void* host)
 {
 	const TjState& S = e->tj;
-	Buf land;
+	DevBuf land;
 	const size_t bytes = e->esz * (size_t)e->n_local;
 	HIP_TRY_MEM(hipMalloc(&land.p, bytes));
 	HIP_TRY(hipMemcpyAsync(land.p, host, bytes, hipMemcpyHostToDevice, e->stream));
@@ -213,7 +191,7 @@ lpp_status tj_vec_from_host(lpp_engine* e, double* dev, const void* host)
 lpp_status tj_vec_to_host(lpp_engine* e, void* host, const double* dev)
 {
 	const TjState& S = e->tj;
-	Buf land;
+	DevBuf land;
 	const size_t bytes = e->esz * (size_t)e->n_local;
 	HIP_TRY_MEM(hipMalloc(&land.p, bytes));
 	const int nb = blocks_for((int64_t)S.nblk * S.ns);
@@ -241,21 +219,15 @@ void tj_fill_random(lpp_engine* e, double* dev, uint64_t seed)
 // whether the hole-major form would be taken for this model at all (switches, sizes): the part of tj_build that needs no device work
 bool tj_applies(const lpp_engine* e, const TjModel& M)
 {
-	bool forced = false;
-	if (const char* s = getenv("LPP_TJ_LAYOUT")) {
-		if (atoi(s) == 0) return false;
-		forced = true;
-	}
-	if (e->cfg.spmv_kernel != LPP_SPMV_AUTO || getenv("LPP_SPMV_KERNEL")) return false;
-	for (const char* k : { "LPP_SHARED_OFFSETS", "LPP_LOCAL16", "LPP_DIAG_CODES", "LPP_BLOCK_TEMPLATE", "LPP_WINDOW_ROWS", "LPP_COMPRESS_VALUES", "LPP_KEEP_PLAIN_CSR" })
-		if (getenv(k)) return false; // switches of the general layout: measure that one
-	if (e->cfg.compress_values == 0) return false;
+	// (LPP_KEEP_PLAIN_CSR listed, LPP_COMPRESS_VALUES refusing whatever its value: both inherited as found)
+	const LayoutGate gate = layout_gate(e, "LPP_TJ_LAYOUT", { "LPP_KEEP_PLAIN_CSR" }, true);
+	if (gate == LayoutGate::Never) return false;
 	const int L = M.L, nup = M.nup, ndown = M.ndown, Lo = nup + ndown, nholes = L - Lo;
 	if (Lo < 2 || Lo > 2 * kTjMaxHalf || nup < 1 || ndown < 1 || L > 31 || nholes < 0) return false;
 	const uint64_t ns64 = binom_h(Lo, nup), nblk64 = binom_h(L, nholes);
 	if (ns64 * nblk64 >= ((uint64_t)1 << 31) || ns64 < 64 || nblk64 > (1u << 20)) return false;
 	// from 32 MB per vector on (as the product-basis layout of the Hubbard matrices); below that the general layout's launch is shorter
-	if (!forced && ns64 * nblk64 * e->esz < ((uint64_t)32 << 20)) return false;
+	if (gate == LayoutGate::BySize && ns64 * nblk64 * e->esz < ((uint64_t)32 << 20)) return false;
 	if (M.has_im && !e->is_complex) return false;
 	return true;
 }
@@ -297,14 +269,7 @@ lpp_status tj_build(lpp_engine* e, const TjModel& M, const AsmParams& P, bool* d
 	for (int b = 0; b < nblk; b++) order[(size_t)b] = b;
 	free_tj(e);
 	TjState& S = e->tj;
-	struct Undo { // until the check below has passed the engine must not describe this form
-		lpp_engine* e;
-		bool* done;
-		~Undo()
-		{
-			if (!*done) free_tj(e);
-		}
-	} undo { e, done };
+	DropUnlessDone undo { e, done, tj_drop }; // until the check below has passed the engine must not describe this form
 	S.model = M;
 	S.Lo = Lo;
 	S.lb = lb;
@@ -332,7 +297,7 @@ lpp_status tj_build(lpp_engine* e, const TjModel& M, const AsmParams& P, bool* d
 	if ((rc = to_dev(&S.order, order, st)) != LPP_OK) return rc;
 	if ((rc = to_dev((TjItem**)&S.items, items, st)) != LPP_OK) return rc;
 	uint32_t* d_holes = nullptr;
-	Buf holes_buf;
+	DevBuf holes_buf;
 	if ((rc = to_dev(&d_holes, holes, st)) != LPP_OK) return rc;
 	holes_buf.p = d_holes;
 	const int64_t n = (int64_t)nblk * ns, nstored = (int64_t)nblk * S.pitch;
@@ -343,27 +308,25 @@ lpp_status tj_build(lpp_engine* e, const TjModel& M, const AsmParams& P, bool* d
 	S.table_bytes = (int64_t)(sizeof(uint32_t) * pat.size() + sizeof(int32_t) * hi_base.size() + sizeof(uint16_t) * lo_rank.size() + sizeof(TjBlock) * blocks.size()
 	                          + sizeof(TjPair) * pairs.size() + sizeof(TjHop) * hops.size() + sizeof(int32_t) * order.size() + sizeof(TjItem) * items.size());
 	// ---- entries of the CSR this stands for (the assembler's counting pass) -------------------------------------------------------
-	Buf d_len, d_sum;
+	DevBuf d_len, d_sum;
 	HIP_TRY_MEM(hipMalloc(&d_len.p, sizeof(int64_t) * (size_t)n));
 	HIP_TRY_MEM(hipMalloc(&d_sum.p, sizeof(unsigned long long)));
 	HIP_TRY(hipMemsetAsync(d_sum.p, 0, sizeof(unsigned long long), st));
 	k_asm_count<ASM_TJ><<<blocks_for(n), kBlock, 0, st>>>(P, (int64_t*)d_len.p);
-	k_tj_sum_i64<<<1024, 256, 0, st>>>((const int64_t*)d_len.p, n, (unsigned long long*)d_sum.p);
+	sum_i64(st, (const int64_t*)d_len.p, n, (unsigned long long*)d_sum.p);
 	unsigned long long nnz = 0;
 	HIP_TRY(hipMemcpyAsync(&nnz, d_sum.p, sizeof(nnz), hipMemcpyDeviceToHost, st));
 	// ---- the check: one product through this form and through the assembler's row walk --------------------------------------------
 	const int comp = e->is_complex ? 2 : 1;
 	const size_t vb = e->esz * (size_t)n, vs = e->esz * (size_t)nstored;
-	Buf d_y, d_xr, d_ys, d_xs, d_cmp;
+	DevBuf d_y, d_xr, d_ys, d_xs;
 	HIP_TRY_MEM(hipMalloc(&d_y.p, vb));
 	HIP_TRY_MEM(hipMalloc(&d_xr.p, vb));
 	HIP_TRY_MEM(hipMalloc(&d_ys.p, vs));
 	HIP_TRY_MEM(hipMalloc(&d_xs.p, vs));
-	HIP_TRY_MEM(hipMalloc(&d_cmp.p, sizeof(unsigned long long) * 2));
 	HIP_TRY(hipMemsetAsync(d_xr.p, 0, vb, st));
 	HIP_TRY(hipMemsetAsync(d_ys.p, 0, vs, st));
 	HIP_TRY(hipMemsetAsync(d_xs.p, 0, vs, st));
-	HIP_TRY(hipMemsetAsync(d_cmp.p, 0, sizeof(unsigned long long) * 2, st));
 	k_fill_random<<<1024, 256, 0, st>>>((double*)d_y.p, n * comp, 0, 4711);
 	const int nbr = blocks_for(n);
 	const EpiScale one { nullptr, nullptr, 0 };
@@ -380,19 +343,13 @@ lpp_status tj_build(lpp_engine* e, const TjModel& M, const AsmParams& P, bool* d
 		k_tj_scatter<cplx><<<nbr, 256, 0, st>>>((cplx*)d_y.p, (const cplx*)d_xs.p, S.perm, nblk, ns, S.pitch); // back into the basis order (d_y is free now)
 	else
 		k_tj_scatter<double><<<nbr, 256, 0, st>>>((double*)d_y.p, (const double*)d_xs.p, S.perm, nblk, ns, S.pitch);
-	k_tj_max_diff<<<1024, 256, 0, st>>>(n * comp, (const double*)d_y.p, (const double*)d_xr.p, (unsigned long long*)d_cmp.p);
-	unsigned long long cmp[2] = { 0, 0 };
-	HIP_TRY(hipMemcpyAsync(cmp, d_cmp.p, sizeof(cmp), hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipStreamSynchronize(st));
-	e->pitch = 0;
-	double dmax, xmax;
-	std::memcpy(&dmax, &cmp[0], 8);
-	std::memcpy(&xmax, &cmp[1], 8);
+	bool same = false;
+	double dmax = 0.0, xmax = 0.0;
+	if ((rc = row_walk_compare(e, n * comp, (const double*)d_y.p, (const double*)d_xr.p, &same, &dmax, &xmax)) != LPP_OK) return rc;
 	if (verbose)
 		fprintf(stderr, "lpp: t-J hole-major form: %d hole configurations x %d spin patterns in %zu items (segments of the low %d positions), %zu bonds, %zu moves, %.2f MB of tables; against the row walk: largest difference %.3g of %.3g\n",
 		        nblk, ns, items.size(), kbits, pairs.size(), hops.size(), 1e-6 * (double)S.table_bytes, dmax, xmax);
-	if (!(dmax <= 1e-12 * std::max(xmax, 1e-300))) return LPP_OK; // not the same matrix: the general layout (the guard drops this one)
+	if (!same) return LPP_OK; // not the same matrix: the general layout (the guard drops this one)
 	S.nnz = (int64_t)nnz;
 	S.active = true;
 	e->pitch = S.pitch;

@@ -1502,6 +1502,77 @@ def test_heisenberg_chain_csr_handed_over_with_its_model_description(monkeypatch
         assert rel(e.matrixVectorProduct(x0.copy(), y), xo) < SPMV_TOL
 
 
+def _special(k):
+    return lambda kernel: kernel == k
+
+
+def _general(kernel):
+    return kernel != 4
+
+
+def _general_tj(kernel):
+    return kernel in (1, 2, 3)
+
+
+# environment beside the forcing switch -> what layout()["kernel"] must satisfy, per builder.  Read off the code as it stood when the four
+# admission gates were still four copies; LPP_KEEP_PLAIN_CSR and "LPP_COMPRESS_VALUES set to anything" are where the copies differ.
+GATE_ROWS = [
+    #                                hubbard_assembled, csr_uploaded, heisenberg_chain, tj
+    ({},                             (_special(4), _special(4), _special(4), _special(5))),
+    (dict(LPP_SHARED_OFFSETS="1"),   (_general, _general, _general, _general_tj)),
+    (dict(LPP_SPMV_KERNEL="2"),      (_general, _general, _general, _general_tj)),
+    (dict(LPP_COMPRESS_VALUES="1"),  (_special(4), _special(4), _special(4), _general_tj)),
+    (dict(LPP_COMPRESS_VALUES="0"),  (_general, _general, _general, _general_tj)),
+    (dict(LPP_KEEP_PLAIN_CSR="1"),   (_special(4), _special(4), _general, _general_tj)),
+]
+GATE_BUILDERS = ["hubbard_assembled", "csr_uploaded", "heisenberg_chain", "tj"]
+
+
+@pytest.mark.parametrize("builder", GATE_BUILDERS)
+def test_general_layout_switches_keep_the_special_layouts_out(builder, monkeypatch):
+    """Characterisation of the admission gate in front of the four special-layout builders (assemble_hubbard_pb, pb_from_csr, pb_chain,
+    tj_build): with its forcing switch set to 1 every builder takes its layout, a switch of the general layout keeps it out, and the
+    result is the oracle's x += H y either way.  The rows also pin the differences the gates have inherited (the chain and the t-J form
+    list LPP_KEEP_PLAIN_CSR, the t-J form refuses LPP_COMPRESS_VALUES whatever its value); they assert nothing about whether those are right."""
+    col = GATE_BUILDERS.index(builder)
+    dtype = "f64"
+    if builder in ("hubbard_assembled", "csr_uploaded"):
+        L, nup, ndown, hop, U, V = PB_CASES["ladder_2x6"]()  # L = 12, (6, 6)
+        A = oracle.hubbard_csr(L, nup, ndown, hop, U, V)
+        force = dict(LPP_PRODUCT_LAYOUT="1")
+        if builder == "hubbard_assembled":
+            build = lambda e: e.assemble_hubbard(L, nup, ndown, hop, U, V)
+        else:
+            build = lambda e: e.set_csr(A.rowptr, A.colind, A.values)
+    elif builder == "heisenberg_chain":
+        L, m = 16, 8
+        jpm, jzz = chain(L, 1.0, False), chain(L, 0.7, False)
+        A = oracle.heis_csr(L, 1, m, jpm, jzz)
+        force = dict(LPP_PRODUCT_LAYOUT="1", LPP_PB_PIECE_ROWS="256")
+        build = lambda e: e.assemble_heisenberg(L, m, jpm, jzz, None)
+    else:
+        L, nup, ndown, hop, jpm, jzz, w, pv, dtype = TJ_CASES["no_holes"]()  # the smallest: 924 states
+        A = oracle.tj_csr(L, nup, ndown, hop, jpm, jzz, w, pv)
+        force = dict(LPP_TJ_LAYOUT="1")
+        build = lambda e: e.assemble_tj(L, nup, ndown, hop, jpm, jzz, w, pv)
+    x0, y = oracle.fill_random(A.nrows, 7), oracle.fill_random(A.nrows, 8)
+    xo = oracle.spmv_acc(A, x0.copy(), y)
+    for k, v in force.items():
+        monkeypatch.setenv(k, v)
+    for env, expect in GATE_ROWS:
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        with LanczosEngine(dtype=dtype) as e:
+            build(e)
+            kernel = e.layout()["kernel"]
+            err = rel(e.matrixVectorProduct(x0.copy(), y), xo)
+        print(builder, env, "kernel", kernel, "error", err)
+        assert expect[col](kernel), (builder, env, kernel)
+        assert err < SPMV_TOL, (builder, env, err)
+        for k in env:
+            monkeypatch.delenv(k)
+
+
 @pytest.mark.parametrize("source", ["assembled", "uploaded"])
 @pytest.mark.parametrize("pitched", [0, 1])
 def test_plain_format_window_layout_outs_first_and_pitched(source, pitched, monkeypatch):
