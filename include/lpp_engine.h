@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LPP_ABI_VERSION 6 /* 6: observables -- LPP_OP_*, lpp_obs_*, lpp_engine_apply_operator, _keep_states, _state_device, *_device start vectors, _two_point, _spectral_decomposition, lpp_continued_fraction; 5: LPP_SPMV_HOLE_MAJOR (lpp_layout.kernel of the t-J model), lpp_engine_set_model_tj / _heisenberg; 4: lpp_layout.segments, lpp_pb_seg_plan_stats; 2: lpp_layout.stream_bytes, lpp_pb_pack_template(bank_ways), set_solver / stream / _ext / _spin entry points; 3: lpp_layout.pieces / coupling_parts / diagonal_plain / chained_step / split_panel, lpp_stats.reortho_* */
+#define LPP_ABI_VERSION 7 /* 7: reduced density matrix -- lpp_rdm_plan, lpp_engine_reduced_density_matrix, _host, lpp_engine_state_reduced_density_matrix, lpp_engine_bench_rdm; 6: observables -- LPP_OP_*, lpp_obs_*, lpp_engine_apply_operator, _keep_states, _state_device, *_device start vectors, _two_point, _spectral_decomposition, lpp_continued_fraction; 5: LPP_SPMV_HOLE_MAJOR (lpp_layout.kernel of the t-J model), lpp_engine_set_model_tj / _heisenberg; 4: lpp_layout.segments, lpp_pb_seg_plan_stats; 2: lpp_layout.stream_bytes, lpp_pb_pack_template(bank_ways), set_solver / stream / _ext / _spin entry points; 3: lpp_layout.pieces / coupling_parts / diagonal_plain / chained_step / split_panel, lpp_stats.reortho_* */
 
 typedef int32_t lpp_status;
 enum {
@@ -435,6 +435,49 @@ lpp_status lpp_engine_spectral_decomposition(lpp_engine* e, int32_t state, lpp_e
  *   G(z) = w / (z + sigma (a_0 - Eg) - b_0^2 / (z + sigma (a_1 - Eg) - b_1^2 / ...)),   b_k = the coefficient lpp_engine_decomposition returns at index k.
  * This is this project's stated convention: PsimagLite's ContinuedFraction was not available to compare with.  out[2] = (re, im). */
 lpp_status lpp_continued_fraction(int32_t n, const double* a, const double* b, double eg, double weight, double sigma, double z_re, double z_im, double* out);
+
+/* ---- reduced density matrix of the lattice cut at a site (ABI 7; one GPU; csrc/lpp_rdm.hip) ----
+ * The reference's `-r siteForSplit` (ReducedDensityMatrix.h, LanczosDriver1.h:201-206): part A = sites 0 .. split-1 = the low `split` bits of a species'
+ * word, rdm(alpha, alpha') = sum over the environment of conj(psi(alpha, beta)) psi(alpha', beta) -- the conjugate on the ROW index, as the
+ * reference has it (:73).  alpha = lo_up + lo_down * 2^split (unpackHubbard :104-123; one species: unpackHeisenberg :90-102).  The matrix is block
+ * diagonal in the particle numbers (k_up, k_down) of part A; the engine computes and returns the blocks, packed.  Bases: BasisHubbardLanczos
+ * and the S = 1/2 words of BasisHeisenberg, the two the reference supports (:78-88); higher spins are refused in the callers (the reference's masks
+ * are not meaningful for several bits per site). */
+enum { LPP_BASIS_HUBBARD = 0, LPP_BASIS_SPIN_HALF = 1 }; /* SPIN_HALF: nup = number of set bits, ndown is ignored */
+
+typedef struct lpp_rdm_block {
+	int32_t k_up, k_down; /* particles of each species in part A */
+	int64_t dim_up, dim_down; /* C(split, k): the block has dim_up * dim_down rows, row = a_up + a_down * dim_up (ranks of the low words) */
+	int64_t env_up, env_down; /* environment configurations per species: the sum runs over env_up * env_down terms */
+	int64_t offset; /* first element of the block in the packed result (row-major d x d) */
+} lpp_rdm_block;
+
+/* The plan (host only; exposed for the CPU test-suite).  Blocks in ascending (k_down, k_up), empty classes left out.  NULL pointers: sizes only.
+ * *nblocks, *total = packed elements (sum of d^2), *nrows = sum of d, *nstarts_up / *nstarts_down = entries of the run-start tables;
+ * blocks[*nblocks]; alpha[*nrows]: the alpha word of every row of every block, in packed row order; starts_up / starts_down: per class k ascending,
+ * then per environment word t ascending (C(nsites - split, n - k) entries per class), the rank of the first state of the run that shares t
+ * (ranks as BasisOneSpin::perfectIndex; the run has C(split, k) states ordered by their low word).  split = 0 (one 1 x 1 block, the norm) and
+ * split = nsites (one block, one term) are valid; split < 0, split > nsites or an impossible sector -> LPP_ERR_INVALID. */
+lpp_status lpp_rdm_plan(int32_t basis, int32_t nsites, int32_t nup, int32_t ndown, int32_t split, int32_t* nblocks, int64_t* total, int64_t* nrows, int64_t* nstarts_up,
+                        int64_t* nstarts_down, lpp_rdm_block* blocks, int64_t* alpha, int64_t* starts_up, int64_t* starts_down);
+
+/* The packed blocks of the reduced density matrix of a device vector: d_psi holds C(nsites,nup)*C(nsites,ndown) elements of the engine's dtype in
+ * the basis order on the engine's GPU, d_out receives *total elements; both 16-byte aligned.  Launches on the engine's stream, no host sync; the
+ * engine needs no matrix.  A gather-SYRK on the f64 MFMA (csrc/lpp_rdm_kernels.h): one triangle of 64 x 64 tiles is computed and mirrored, so
+ * the result is Hermitian bit for bit; long sums of small blocks are cut into fixed K ranges and added in a fixed order (no atomics): two calls
+ * on the same vector return the same bits.  The plan, its tables and the split-K workspace stay with the engine until another cut is asked for.
+ * A workspace that does not fit in the free device memory -> LPP_ERR_NOMEM before any launch; a partitioned or hole-major t-J engine -> LPP_ERR_STATE. */
+lpp_status lpp_engine_reduced_density_matrix(lpp_engine* e, int32_t basis, int32_t nsites, int32_t nup, int32_t ndown, int32_t split, const void* d_psi, void* d_out);
+/* the same on host buffers (copied in and out).  The packed result plus workspace must fit in the free device memory: LPP_ERR_NOMEM with the sizes
+ * in the message otherwise, before any launch.  out == NULL: every check is made and nothing is launched (psi is not read). */
+lpp_status lpp_engine_reduced_density_matrix_host(lpp_engine* e, int32_t basis, int32_t nsites, int32_t nup, int32_t ndown, int32_t split, const void* psi, void* out);
+/* the same for resident state `state` (lpp_engine_keep_states before the solve): a missing state -> LPP_ERR_STATE, a sector that is not the
+ * resident states' -> LPP_ERR_INVALID.  out_host == NULL: checks only. */
+lpp_status lpp_engine_state_reduced_density_matrix(lpp_engine* e, int32_t state, int32_t basis, int32_t nsites, int32_t nup, int32_t ndown, int32_t split, void* out_host);
+/* Time `iters` calls on a resident pseudo-random vector with HIP events.  *macs = sum over blocks of d^2 * K real multiply-adds (times 4 for c128):
+ * BOTH triangles are counted, as a full product would compute them, although the kernel computes one and mirrors it. */
+lpp_status lpp_engine_bench_rdm(lpp_engine* e, int32_t basis, int32_t nsites, int32_t nup, int32_t ndown, int32_t split, int32_t warmup, int32_t iters, double* ms_per_call,
+                                double* macs);
 
 #ifdef __cplusplus
 }

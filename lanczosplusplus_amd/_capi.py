@@ -10,12 +10,13 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # LPP_ENGINE_LIB: another build of the same library (scripts/experiments build their variants into a scratch directory, never over this one)
 LIB_PATH = os.environ.get("LPP_ENGINE_LIB") or os.path.join(_HERE, "csrc", "liblpp_engine.so")
 
-LPP_ABI_VERSION = 6
+LPP_ABI_VERSION = 7
 LPP_OK, LPP_ERR_INVALID, LPP_ERR_HIP, LPP_ERR_NOMEM, LPP_ERR_NOCONV, LPP_ERR_STATE, LPP_ERR_COMM = range(7)
 LPP_F64, LPP_C128 = 0, 1
 LPP_SPMV_AUTO, LPP_SPMV_ROWGROUP, LPP_SPMV_SLICED, LPP_SPMV_WINDOW = 0, 1, 2, 3
 LPP_OP_C, LPP_OP_SZ, LPP_OP_CDAGGER, LPP_OP_N, LPP_OP_SPLUS, LPP_OP_SMINUS = 1, 2, 3, 4, 5, 6
 LPP_SPIN_UP, LPP_SPIN_DOWN = 0, 1
+LPP_BASIS_HUBBARD, LPP_BASIS_SPIN_HALF = 0, 1
 
 STATUS_NAMES = {0: "LPP_OK", 1: "LPP_ERR_INVALID", 2: "LPP_ERR_HIP", 3: "LPP_ERR_NOMEM", 4: "LPP_ERR_NOCONV",
                 5: "LPP_ERR_STATE", 6: "LPP_ERR_COMM"}
@@ -55,6 +56,11 @@ class Layout(C.Structure):
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class RdmBlock(C.Structure):
+    _fields_ = [("k_up", C.c_int32), ("k_down", C.c_int32), ("dim_up", C.c_int64), ("dim_down", C.c_int64),
+                ("env_up", C.c_int64), ("env_down", C.c_int64), ("offset", C.c_int64)]
 
 
 CB_VOID = C.CFUNCTYPE(C.c_int32, C.c_void_p)
@@ -130,6 +136,11 @@ SYMBOLS = {
     "lpp_engine_spectral_decomposition": (C.c_int32, [_P, C.c_int32, _P] + [C.c_int32] * 4 + [C.c_double] + [C.c_int32] * 3
                                           + [C.POINTER(C.c_double), C.POINTER(C.c_int32), _P, _P, C.POINTER(Stats)]),
     "lpp_continued_fraction": (C.c_int32, [C.c_int32, _P, _P] + [C.c_double] * 5 + [_P]),
+    "lpp_rdm_plan": (C.c_int32, [C.c_int32] * 5 + [C.POINTER(C.c_int32)] + [C.POINTER(C.c_int64)] * 4 + [_P, _P, _P, _P]),
+    "lpp_engine_reduced_density_matrix": (C.c_int32, [_P] + [C.c_int32] * 5 + [_P, _P]),
+    "lpp_engine_reduced_density_matrix_host": (C.c_int32, [_P] + [C.c_int32] * 5 + [_P, _P]),
+    "lpp_engine_state_reduced_density_matrix": (C.c_int32, [_P] + [C.c_int32] * 6 + [_P]),
+    "lpp_engine_bench_rdm": (C.c_int32, [_P] + [C.c_int32] * 7 + [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 }
 
 _lib = None

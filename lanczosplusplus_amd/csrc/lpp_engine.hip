@@ -1056,6 +1056,7 @@ lpp_status lpp_engine_destroy(lpp_engine* e)
 	drop_product(e);
 	free_pb(e);
 	free_obs(e);
+	free_rdm(e);
 	for (double* p : { e->x, e->y, e->V, e->partial, e->scal_own, e->zwork })
 		if (p) (void)hipFree(p);
 	if (e->h_scal) (void)hipHostFree(e->h_scal);

@@ -341,6 +341,7 @@ struct lpp_engine {
 	int resident_n = 0, resident_cap = 0; // states valid now (0 until a solve has written them); states the buffer has room for
 	int64_t resident_stride = 0, resident_len = 0; // doubles between states (even), elements per state
 	void* obs = nullptr;
+	void* rdm = nullptr; // the plan of the last reduced density matrix, uploaded (lpp_rdm.hip)
 
 	lpp_status adopt_comm(const lpp_comm* c);
 	void collect_spmv_times();
@@ -475,4 +476,5 @@ void vec_fill_random(lpp_engine* e, double* dev, uint64_t seed);
 lpp_status vec_from_device(lpp_engine* e, double* dev, const void* basis);
 lpp_status vec_to_device(lpp_engine* e, void* basis, const double* dev);
 void free_obs(lpp_engine* e); // resident states and operator tables (lpp_obs.hip)
+void free_rdm(lpp_engine* e); // reduced-density-matrix plan and workspace (lpp_rdm.hip)
 } // namespace lpp

@@ -65,6 +65,7 @@ class LanczosEngine:
         self._comm_keepalive = None
         self._ctor = dict(dtype="c128" if self.is_complex else "f64", device=device, check_lag=check_lag, spmv_kernel=spmv_kernel,
                           time_kernels=time_kernels, seed=seed, compress_values=compress_values)
+        self._basis = None  # (basis name, L, nup, ndown) of the model set up last, or a string: why it has no reduced density matrix
         self._model = None  # what assemble_hubbard / setup_hubbard_onthefly were given (spectral_function builds the N+-1 sectors from it)
         self._energies = None
         self._sectors = {}  # (nup, ndown) -> LanczosEngine holding that sector's Hamiltonian
@@ -130,10 +131,12 @@ class LanczosEngine:
         n = len(rowptr) - 1
         if n < 0 or len(colind) != rowptr[-1] or len(values) != rowptr[-1]:
             raise ValueError("inconsistent CSR arrays")
+        self._basis = None
         check(self._lib.lpp_engine_set_csr(self._h, n, _vp(rowptr), _vp(colind), _vp(values)))
 
     def set_csr_device(self, nrows, d_rowptr, d_colind, d_values):
         """CSR already resident on the engine's GPU: raw device addresses (e.g. torch tensor .data_ptr())."""
+        self._basis = None
         check(self._lib.lpp_engine_set_csr_device(self._h, int(nrows), C.c_void_p(d_rowptr), C.c_void_p(d_colind), C.c_void_p(d_values)))
 
     def set_csr_partition(self, comm, global_rows, shard_starts, rowptr, colind, values):
@@ -142,6 +145,7 @@ class LanczosEngine:
         colind = np.ascontiguousarray(colind, np.int32)
         values = np.ascontiguousarray(values, self.np_dtype)
         self._comm_keepalive = comm
+        self._basis = None
         check(self._lib.lpp_engine_set_csr_partition(self._h, C.byref(comm.struct), global_rows, _vp(shard_starts),
                                                      _vp(rowptr), _vp(colind), _vp(values)))
 
@@ -156,6 +160,7 @@ class LanczosEngine:
         nj = None if ninj is None else _mat(ninj, L)
         self._comm_keepalive = comm
         self._set_model("assemble_hubbard", L, nup, ndown, hop, U, V, ninj, jcoup, comm)
+        self._basis = ("hubbard", L, nup, ndown) if comm is None else None
         cs = C.byref(comm.struct) if comm is not None else None
         jc = None if jcoup is None else _mat(jcoup, L)
         check(self._lib.lpp_engine_assemble_hubbard_super(self._h, cs, L, nup, ndown, _vp(hr), _vp(hi), _vp(U), _vp(V), _vp(nj), _vp(jc)))
@@ -172,6 +177,7 @@ class LanczosEngine:
         nj = None if ninj is None else _mat(ninj, L)
         self._comm_keepalive = comm
         self._set_model("setup_hubbard_onthefly", L, nup, ndown, hop, U, V, ninj, jcoup, comm)
+        self._basis = ("hubbard", L, nup, ndown) if comm is None else None
         cs = C.byref(comm.struct) if comm is not None else None
         jc = None if jcoup is None else _mat(jcoup, L)
         check(self._lib.lpp_engine_setup_hubbard_onthefly_super(self._h, cs, L, nup, ndown, _vp(hr), _vp(hi), _vp(U), _vp(V), _vp(nj), _vp(jc)))
@@ -179,6 +185,8 @@ class LanczosEngine:
     def assemble_heisenberg(self, L, szPlusConst, jpm, jzz, field=None, twiceS=1, anisotropy=None):
         """Heisenberg.h:80-114 on the device; twiceS > 1 or an anisotropy take the any-spin assembler (digit basis)."""
         f = None if field is None else np.ascontiguousarray(field, np.float64)
+        # ReducedDensityMatrix::unpackHeisenberg reads one bit per site: S = 1/2 only
+        self._basis = ("spin_half", L, szPlusConst, 0) if twiceS == 1 else "the reduced density matrix of a Heisenberg model needs twiceS = 1 (one bit per site)"
         if twiceS == 1 and anisotropy is None:
             check(self._lib.lpp_engine_assemble_heisenberg(self._h, L, szPlusConst, _vp(_mat(jpm, L)), _vp(_mat(jzz, L)),
                                                            _vp(f), 0 if f is None else len(f)))
@@ -192,6 +200,7 @@ class LanczosEngine:
         hr = _mat(hop.real, L)
         hi = _mat(hop.imag, L) if np.iscomplexobj(hop) else None
         pv = None if potentialV is None else np.ascontiguousarray(potentialV, np.float64)
+        self._basis = None
         check(self._lib.lpp_engine_assemble_tj(self._h, L, nup, ndown, _vp(hr), _vp(hi), _vp(_mat(jpm, L)),
                                                _vp(_mat(jzz, L)), _vp(_mat(w, L)), _vp(pv),
                                                0 if pv is None else len(pv)))
@@ -352,6 +361,64 @@ class LanczosEngine:
         check(self._lib.lpp_engine_bench_operator(self._h, _op_id(op), site, spin, L, nup, ndown, warmup, iters, C.byref(ms), C.byref(by)))
         return ms.value, by.value
 
+    # ---- reduced density matrix of the low `split` sites (lpp_rdm.hip) ---------------------------------------
+    def _rdm_call(self, call, plan, dense):
+        """two calls: every refusal first (out = NULL launches nothing), then the packed result"""
+        check(call(None))
+        flat = np.zeros(plan["total"], self.np_dtype)
+        check(call(_vp(flat)))
+        blocks = [(b["k_up"], b["k_down"], b["alpha"], flat[b["offset"]:b["offset"] + b["dim"] ** 2].reshape(b["dim"], b["dim"])) for b in plan["blocks"]]
+        return _rdm_dense(blocks, plan, self.np_dtype) if dense else blocks
+
+    def reduced_density_matrix(self, split, state=0, dense=False):
+        """ReducedDensityMatrix (ReducedDensityMatrix.h:65-76) of resident state `state` (keep_states before lanczos), sites 0 .. split-1 kept:
+        a list of blocks (k_up, k_down, alpha, matrix), matrix[r, c] = sum over the environment of conj(psi(alpha[r], beta)) psi(alpha[c], beta)
+        -- the conjugate on the row index, as the reference has it.  dense=True: the reference's square matrix of 4^split (spin 1/2: 2^split)
+        rows indexed by alpha.  For engines set up by assemble_hubbard / setup_hubbard_onthefly / assemble_heisenberg with twiceS=1."""
+        if self._basis is None or isinstance(self._basis, str):
+            raise _capi.LppError(_capi.LPP_ERR_STATE if self._basis is None else _capi.LPP_ERR_INVALID,
+                                 self._basis or "reduced_density_matrix needs an engine set up by assemble_hubbard / setup_hubbard_onthefly / assemble_heisenberg")
+        basis, L, nup, ndown = self._basis
+        plan = _rdm_plan_checked(L, nup, ndown, split, basis, dense)
+        bid = BASES[basis]
+        return self._rdm_call(lambda out: self._lib.lpp_engine_state_reduced_density_matrix(self._h, int(state), bid, L, nup, ndown, int(split), out), plan, dense)
+
+    def reduced_density_matrix_of(self, psi, L, nup, ndown, split, basis="hubbard", dense=False):
+        """the same for a host vector of sector (nup, ndown) in the basis order; the engine needs no matrix"""
+        plan = _rdm_plan_checked(L, nup, ndown, split, basis, dense)
+        psi = np.ascontiguousarray(psi, self.np_dtype)
+        if len(psi) != plan["states"]:
+            raise ValueError("psi has %d elements, the sector has %d" % (len(psi), plan["states"]))
+        bid = BASES[basis]
+        return self._rdm_call(lambda out: self._lib.lpp_engine_reduced_density_matrix_host(self._h, bid, L, nup, ndown, int(split), _vp(psi), out), plan, dense)
+
+    def reduced_density_matrix_device(self, d_psi, d_out, L, nup, ndown, split, basis="hubbard"):
+        """raw device addresses (16-byte aligned) on the engine's GPU: one enqueue on the engine's stream, no sync; d_out takes rdm_plan(...)["total"] elements"""
+        check(self._lib.lpp_engine_reduced_density_matrix(self._h, _basis_id(basis), L, nup, ndown, int(split), C.c_void_p(int(d_psi)), C.c_void_p(int(d_out))))
+
+    def entanglement_spectrum(self, split, state=0):
+        """(eigenvalues ascending, labels): all eigenvalues of all blocks (numpy.linalg.eigvalsh per block), labels[i] = (k_up, k_down) of eigenvalue i"""
+        vals, labels = [], []
+        for ku, kd, _, m in self.reduced_density_matrix(split, state):
+            w = np.linalg.eigvalsh(m)
+            vals.append(w)
+            labels += [(ku, kd)] * len(w)
+        vals = np.concatenate(vals)
+        order = np.argsort(vals, kind="stable")
+        return vals[order], [labels[i] for i in order]
+
+    def entanglement_entropy(self, split, state=0):
+        """-sum lambda ln lambda over the eigenvalues lambda > 0 of the reduced density matrix"""
+        w, _ = self.entanglement_spectrum(split, state)
+        w = w[w > 0]
+        return float(-np.sum(w * np.log(w)))
+
+    def bench_rdm(self, L, nup, ndown, split, basis="hubbard", warmup=1, iters=3):
+        """(ms per call, multiply-adds: sum of d^2 K over the blocks, both triangles counted, times 4 for c128) on a resident pseudo-random vector"""
+        ms, macs = C.c_double(), C.c_double()
+        check(self._lib.lpp_engine_bench_rdm(self._h, _basis_id(basis), L, nup, ndown, int(split), warmup, iters, C.byref(ms), C.byref(macs)))
+        return ms.value, macs.value
+
     def _need_model(self, who):
         if self._model is None:
             raise _capi.LppError(_capi.LPP_ERR_STATE, "%s needs a single-GPU Hubbard engine set up by assemble_hubbard / setup_hubbard_onthefly" % who)
@@ -427,6 +494,67 @@ class LanczosEngine:
 
 # ---- host-only helpers (no GPU) -------------------------------------------------------------------
 OP_NAMES = tuple(OPERATORS)
+
+
+# the bases ReducedDensityMatrix::unpack knows (ReducedDensityMatrix.h:78-88)
+BASES = {"hubbard": _capi.LPP_BASIS_HUBBARD, "spin_half": _capi.LPP_BASIS_SPIN_HALF}
+RDM_DENSE_MAX_ROWS = 4096
+
+
+def _basis_id(basis):
+    try:
+        return BASES[basis]
+    except KeyError:
+        raise ValueError("unsupported basis %r (one of %s)" % (basis, ", ".join(sorted(BASES))))
+
+
+def rdm_plan(L, nup, ndown, split, basis="hubbard"):
+    """The plan of the reduced density matrix of sites 0 .. split-1 (lpp_rdm_plan): a dict with `blocks` (ascending (k_down, k_up); each a dict of
+    k_up, k_down, dim_up, dim_down, dim, env_up, env_down, terms = env_up * env_down, offset, alpha = the alpha word of every row), `total`
+    (packed elements), `states` (the sector's size) and `starts_up` / `starts_down`: {k: run-start ranks of the environment words, ascending}.
+    basis "spin_half": nup = number of set bits, ndown is ignored."""
+    from math import comb
+    lib = _capi.lib()
+    bid = _basis_id(basis)
+    nb, tot, rows, nsu, nsd = C.c_int32(), C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+    args = (bid, int(L), int(nup), int(ndown), int(split), C.byref(nb), C.byref(tot), C.byref(rows), C.byref(nsu), C.byref(nsd))
+    check(lib.lpp_rdm_plan(*args, None, None, None, None))
+    blk = (_capi.RdmBlock * nb.value)()
+    alpha, su, sd = np.zeros(rows.value, np.int64), np.zeros(nsu.value, np.int64), np.zeros(nsd.value, np.int64)
+    check(lib.lpp_rdm_plan(*args, C.cast(blk, C.c_void_p), _vp(alpha), _vp(su), _vp(sd)))
+    if bid == _capi.LPP_BASIS_SPIN_HALF:
+        ndown = 0
+    blocks, r = [], 0
+    for b in blk:
+        d = b.dim_up * b.dim_down
+        blocks.append(dict(k_up=b.k_up, k_down=b.k_down, dim_up=b.dim_up, dim_down=b.dim_down, dim=d, env_up=b.env_up, env_down=b.env_down,
+                           terms=b.env_up * b.env_down, offset=b.offset, alpha=alpha[r:r + d].copy()))
+        r += d
+
+    def by_class(tab, n):
+        out, o = {}, 0
+        for k in range(max(0, n - (L - split)), min(split, n) + 1):
+            c = comb(L - split, n - k)
+            out[k] = tab[o:o + c].copy()
+            o += c
+        return out
+
+    return dict(blocks=blocks, total=tot.value, states=comb(L, nup) * comb(L, ndown), starts_up=by_class(su, nup), starts_down=by_class(sd, ndown),
+                dense_rows=(2 if bid == _capi.LPP_BASIS_SPIN_HALF else 4) ** split)
+
+
+def _rdm_plan_checked(L, nup, ndown, split, basis, dense):
+    _basis_id(basis)
+    if dense and 0 <= split <= L and (2 if basis == "spin_half" else 4) ** split > RDM_DENSE_MAX_ROWS:
+        raise ValueError("dense=True: the matrix would have more than %d rows; take the blocks" % RDM_DENSE_MAX_ROWS)
+    return rdm_plan(L, nup, ndown, split, basis)
+
+
+def _rdm_dense(blocks, plan, dtype):
+    out = np.zeros((plan["dense_rows"], plan["dense_rows"]), dtype)
+    for _, _, alpha, m in blocks:
+        out[np.ix_(alpha, alpha)] = m
+    return out
 
 
 def sector_size(L, nup, ndown):

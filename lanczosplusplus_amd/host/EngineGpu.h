@@ -572,6 +572,44 @@ public:
 		}
 	}
 
+	// ReducedDensityMatrix (ReducedDensityMatrix.h:40-76) of the resident ground state for the lattice cut at `split` (sites 0 .. split-1 kept), as the
+	// blocks of fixed particle numbers (k_up, k_down) in the kept sites: rho(r, c) = sum over the environment of conj(psi(alpha[r], beta)) psi(alpha[c], beta)
+	// -- the conjugate on the row index (:73).  The Hubbard family, for which the states are resident; other models throw, as the reference's unpack does (:87).
+	struct RdmBlockType {
+		int kUp = 0, kDown = 0;
+		std::vector<SizeType> alpha; // the reference's row index of every row: lo_up + lo_down * 2^split (unpackHubbard :104-123)
+		LppHost::Matrix<ComplexOrRealType> rho;
+	};
+
+	void reducedDensityMatrix(std::vector<RdmBlockType>& blocks, SizeType split) const
+	{
+		lpp_engine* e = observableEngine("reducedDensityMatrix");
+		const int32_t n = (int32_t)model_.geometry().numberOfSites();
+		const typename ModelType::BasisBaseType::PairIntType parts = model_.basis().parts();
+		const int32_t nup = (int32_t)parts.first, ndown = (int32_t)parts.second, cut = (int32_t)split;
+		int32_t nb = 0;
+		int64_t total = 0, rows = 0;
+		lppCheck(lpp_rdm_plan(LPP_BASIS_HUBBARD, n, nup, ndown, cut, &nb, &total, &rows, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+		std::vector<lpp_rdm_block> blk((size_t)nb);
+		std::vector<int64_t> alpha((size_t)rows);
+		lppCheck(lpp_rdm_plan(LPP_BASIS_HUBBARD, n, nup, ndown, cut, &nb, &total, &rows, nullptr, nullptr, blk.data(), alpha.data(), nullptr, nullptr));
+		lppCheck(lpp_engine_state_reduced_density_matrix(e, 0, LPP_BASIS_HUBBARD, n, nup, ndown, cut, nullptr)); // every refusal, the memory check among them
+		std::vector<ComplexOrRealType> flat((size_t)total);
+		lppCheck(lpp_engine_state_reduced_density_matrix(e, 0, LPP_BASIS_HUBBARD, n, nup, ndown, cut, flat.data()));
+		blocks.assign((size_t)nb, RdmBlockType());
+		size_t row0 = 0;
+		for (size_t b = 0; b < blocks.size(); b++) {
+			const SizeType d = (SizeType)(blk[b].dim_up * blk[b].dim_down);
+			blocks[b].kUp = blk[b].k_up;
+			blocks[b].kDown = blk[b].k_down;
+			blocks[b].alpha.assign(alpha.begin() + row0, alpha.begin() + row0 + d);
+			blocks[b].rho.resize(d, d);
+			for (SizeType i = 0; i < d; i++)
+				for (SizeType j = 0; j < d; j++) blocks[b].rho(i, j) = flat[(size_t)blk[b].offset + i * d + j];
+			row0 += d;
+		}
+	}
+
 private:
 	void checkBraOrKet(const char* what, SizeType ind) const
 	{

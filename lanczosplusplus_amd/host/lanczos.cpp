@@ -1,14 +1,17 @@
 // lanczos.cpp -- driver with the reference's command line for this path (src/lanczos.cpp:99-226,
 // src/Engine/LanczosDriver1.h:47-66): reads an InputNg-style file (the reference's TestSuite inputs work
 // unmodified for the in-scope models), builds the model, runs the GPU engine, prints "Energy=".
-//   lanczos -f input.inp [-p precision] [-d device] [-g operator] [-c operator] [-s "s1,s2;..."]
+//   lanczos -f input.inp [-p precision] [-d device] [-g operator] [-c operator] [-s "s1,s2;..."] [-r siteForSplit]
 // SolverOptions=useComplex selects complex<double> (lanczos.cpp:194-226).  -c prints the two-point matrix of the ground state, -g writes the
 // continued fractions of the spectral function for the site pairs the input names (TSPSites, TSPCenter=, DoAllPairs=,
-// ComputeDensityOfStates=) into <input basename><counter>.comb (LanczosDriver1.h:81-199; Hubbard family, one GPU).  -m, -r, -M are out of scope.
+// ComputeDensityOfStates=) into <input basename><counter>.comb (LanczosDriver1.h:81-199; Hubbard family, one GPU).  -r prints the reduced density
+// matrix of the lattice cut at a site, its eigenvectors, eigenvalues and the entanglement entropy (LanczosDriver1.h:201-206).  -m, -M are out of scope.
 #include <getopt.h>
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -29,6 +32,7 @@ struct LanczosOptions {
 	std::vector<LabeledOperator> gf, cicj;
 	std::vector<SizeType> sites;
 	std::vector<PairSizeType> spins;
+	int split = -1; // -r siteForSplit (LanczosOptions.h), -1: no reduced density matrix
 };
 
 // -s "s1,s2;s1,s2;..." (lanczos.cpp:17-34, :147-152)
@@ -61,6 +65,46 @@ template <typename T> static void printMatrix(std::ostream& os, const LppHost::M
 		for (SizeType j = 0; j < m.n_col(); j++) os << m(i, j) << " ";
 		os << "\n";
 	}
+}
+
+// -r (LanczosDriver1.h:201-206, ReducedDensityMatrix::printAll :53-61): the matrix is block diagonal in the particle numbers (k_up, k_down) of the kept
+// sites and is printed block by block -- "# block k_up= k_down= dim=", "# alpha" with the reference's row index of every row, then the block as
+// printMatrix prints a matrix; blocks of more than 64 rows print their two comment lines only.  The eigenvalues of all blocks follow merged
+// ascending ("count" on a line, then the values), then EntanglementEntropy= -sum lambda ln lambda over lambda > 0.
+template <typename EngineType> static void printReducedDensityMatrix(std::ostream& os, const EngineType& engine, SizeType split)
+{
+	typedef typename EngineType::ComplexOrRealType ComplexOrRealType;
+	const SizeType maxPrinted = 64;
+	std::vector<typename EngineType::RdmBlockType> blocks;
+	engine.reducedDensityMatrix(blocks, split);
+	std::vector<LppHost::Matrix<ComplexOrRealType>> vectors(blocks.size());
+	std::vector<double> all;
+	for (SizeType b = 0; b < blocks.size(); b++) {
+		std::vector<double> eigs;
+		vectors[b] = blocks[b].rho;
+		LppHost::diag(vectors[b], eigs, 'V');
+		all.insert(all.end(), eigs.begin(), eigs.end());
+	}
+	for (int what = 0; what < 2; what++) {
+		os << (what == 0 ? "Reduced Density Matrix\n" : "Eigenvectors of Reduced Density Matrix\n");
+		for (SizeType b = 0; b < blocks.size(); b++) {
+			const SizeType d = blocks[b].rho.n_row();
+			os << "# block k_up=" << blocks[b].kUp << " k_down=" << blocks[b].kDown << " dim=" << d << "\n";
+			os << "# alpha";
+			for (SizeType i = 0; i < d && d <= maxPrinted; i++) os << " " << blocks[b].alpha[i];
+			if (d > maxPrinted) os << " (not printed: more than " << maxPrinted << " rows)";
+			os << "\n";
+			if (d <= maxPrinted) printMatrix(os, what == 0 ? blocks[b].rho : vectors[b]);
+		}
+	}
+	std::sort(all.begin(), all.end());
+	os << "Eigenvalues of Reduced Density Matrix\n" << all.size() << "\n";
+	double entropy = 0;
+	for (SizeType i = 0; i < all.size(); i++) {
+		os << all[i] << " ";
+		if (all[i] > 0) entropy -= all[i] * std::log(all[i]);
+	}
+	os << "\nEntanglementEntropy=" << entropy << "\n";
 }
 
 // mainLoop3 (LanczosDriver1.h:47-199): build the engine, print the ground-state energy, then the observables asked for
@@ -147,6 +191,9 @@ int mainLoop3(const ModelType& model, LppHost::InputReadable& io, int device, in
 		engine.twoPoint(cicjMatrix, lanczosOptions.cicj[cicji], lanczosOptions.spins, PairSizeType(0, 0), PairSizeType(0, 0));
 		printMatrix(std::cout, cicjMatrix);
 	}
+
+	// -r (LanczosDriver1.h:201-206)
+	if (lanczosOptions.split >= 0) printReducedDensityMatrix(std::cout, engine, (SizeType)lanczosOptions.split);
 	return 0;
 }
 
@@ -368,16 +415,17 @@ int main(int argc, char** argv)
 	LppHost::String file;
 	int device = 0, precision = 8, opt = 0;
 	bool partitioned = false;
-	const char* usage = " -f filename [-p precision] [-d device] [-P] [-g operator] [-c operator] [-s \"s1,s2;...\"]\n";
+	const char* usage = " -f filename [-p precision] [-d device] [-P] [-g operator] [-c operator] [-s \"s1,s2;...\"] [-r siteForSplit]\n";
 	LanczosOptions lanczosOptions;
 	LppHost::String spinsArg;
 	std::vector<LppHost::String> gfArgs, cicjArgs;
-	while ((opt = getopt(argc, argv, "f:p:d:Pg:c:s:")) != -1) {
+	while ((opt = getopt(argc, argv, "f:p:d:Pg:c:s:r:")) != -1) {
 		switch (opt) {
 		case 'f': file = optarg; break;
 		case 'g': gfArgs.push_back(optarg); break;
 		case 'c': cicjArgs.push_back(optarg); break;
 		case 's': spinsArg = optarg; break;
+		case 'r': lanczosOptions.split = atoi(optarg); break;
 		case 'p': precision = atoi(optarg); break;
 		case 'd': device = atoi(optarg); break;
 		case 'P': partitioned = true; break;
@@ -392,7 +440,7 @@ int main(int argc, char** argv)
 		for (const LppHost::String& g : gfArgs) lanczosOptions.gf.push_back(LabeledOperator(g));
 		for (const LppHost::String& c : cicjArgs) lanczosOptions.cicj.push_back(LabeledOperator(c));
 		if (!spinsArg.empty()) fillSpins(lanczosOptions.spins, spinsArg);
-		if (partitioned && (!gfArgs.empty() || !cicjArgs.empty())) throw std::runtime_error("-g / -c run on one GPU: not with -P\n");
+		if (partitioned && (!gfArgs.empty() || !cicjArgs.empty() || lanczosOptions.split >= 0)) throw std::runtime_error("-g / -c / -r run on one GPU: not with -P\n");
 		LppHost::InputReadable io(file);
 		LppHost::String options("none");
 		if (io.has("SolverOptions=")) io.readline(options, "SolverOptions=");
