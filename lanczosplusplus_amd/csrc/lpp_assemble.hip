@@ -67,6 +67,29 @@ std::vector<uint64_t> comb_table()
 	return c;
 }
 
+inline int asm_blocks(int64_t nloc) { return (int)std::max<int64_t>(1, std::min<int64_t>((nloc + kBlock - 1) / kBlock, 1 << 20)); }
+
+// The count pass: the lengths of P.nloc rows (and a trailing 0) into len, their sum into *nnz; with `scan` the lengths become the row
+// pointers, in place.  Synchronises the stream.
+template <int MODEL> lpp_status count_rows(hipStream_t st, const AsmParams& P, int64_t* len, bool scan, int64_t* nnz)
+{
+	const int64_t n = P.nloc + 1;
+	const int64_t nblk = (n + kScanChunk - 1) / kScanChunk;
+	DevBuf sums, total;
+	HIP_TRY(hipMemsetAsync(len, 0, sizeof(int64_t) * (size_t)n, st));
+	HIP_TRY_MEM(hipMalloc(&sums.p, sizeof(int64_t) * (size_t)nblk));
+	HIP_TRY_MEM(hipMalloc(&total.p, sizeof(int64_t)));
+	if (P.nloc > 0) k_asm_count<MODEL><<<asm_blocks(P.nloc), kBlock, 0, st>>>(P, len);
+	// exclusive scan of nloc+1 lengths (last is 0) -> rowptr
+	k_scan_block_sums<<<(int)nblk, kBlock, 0, st>>>(len, n, (int64_t*)sums.p);
+	k_scan_sums<<<1, kBlock, 0, st>>>((int64_t*)sums.p, nblk, (int64_t*)total.p);
+	if (scan) k_scan_apply<<<(int)nblk, kBlock, 0, st>>>(len, n, (const int64_t*)sums.p, len);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(nnz, total.p, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipStreamSynchronize(st));
+	return LPP_OK;
+}
+
 template <int MODEL, typename T>
 lpp_status run_assembly(lpp_engine* e, AsmParams P, DevCsr& A, int force_mode = 0, int64_t force_block = 0, bool raw = false)
 {
@@ -80,26 +103,13 @@ lpp_status run_assembly(lpp_engine* e, AsmParams P, DevCsr& A, int force_mode = 
 	A.owned = true;
 	A.known_sorted = true; // rows come out of the delta-sorted term list in column order
 	HIP_TRY_MEM(hipMalloc(&A.rowptr, sizeof(int64_t) * (size_t)(P.nloc + 1)));
-	HIP_TRY(hipMemsetAsync(A.rowptr, 0, sizeof(int64_t) * (size_t)(P.nloc + 1), st));
-	const int nb = (int)std::max<int64_t>(1, std::min<int64_t>((P.nloc + kBlock - 1) / kBlock, 1 << 20));
-	if (P.nloc > 0) k_asm_count<MODEL><<<nb, kBlock, 0, st>>>(P, A.rowptr);
-	// exclusive scan of nloc+1 lengths (last is 0) -> rowptr
-	const int64_t n = P.nloc + 1;
-	const int64_t nblk = (n + kScanChunk - 1) / kScanChunk;
-	DevBuf sums, total;
-	HIP_TRY_MEM(hipMalloc(&sums.p, sizeof(int64_t) * (size_t)nblk));
-	HIP_TRY_MEM(hipMalloc(&total.p, sizeof(int64_t)));
-	k_scan_block_sums<<<(int)nblk, kBlock, 0, st>>>(A.rowptr, n, (int64_t*)sums.p);
-	k_scan_sums<<<1, kBlock, 0, st>>>((int64_t*)sums.p, nblk, (int64_t*)total.p);
-	k_scan_apply<<<(int)nblk, kBlock, 0, st>>>(A.rowptr, n, (const int64_t*)sums.p, A.rowptr);
-	HIP_TRY(hipGetLastError());
 	int64_t nnz = 0;
-	HIP_TRY(hipMemcpyAsync(&nnz, total.p, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipStreamSynchronize(st));
+	lpp_status rc = count_rows<MODEL>(st, P, A.rowptr, true, &nnz);
+	if (rc != LPP_OK) return rc;
 	A.nnz = nnz;
 	HIP_TRY_MEM(hipMalloc(&A.col, sizeof(int32_t) * (size_t)std::max<int64_t>(nnz, 1)));
 	HIP_TRY_MEM(hipMalloc(&A.val, sizeof(T) * (size_t)std::max<int64_t>(nnz, 1)));
-	if (P.nloc > 0) k_asm_fill<MODEL, T><<<nb, kBlock, 0, st>>>(P, A.rowptr, A.col, (T*)A.val);
+	if (P.nloc > 0) k_asm_fill<MODEL, T><<<asm_blocks(P.nloc), kBlock, 0, st>>>(P, A.rowptr, A.col, (T*)A.val);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipStreamSynchronize(st));
 	if (getenv("LPP_VERBOSE"))
@@ -143,7 +153,7 @@ uint64_t binom(const std::vector<uint64_t>& c, int n, int m)
 
 // terms of the Hubbard hopping: c^dagger_j c_i for every ordered pair with hoppings_(i,j) != 0, both species,
 // value h * doSign(ket,i) * doSign(ket^bit(i), j)   (HubbardHelper.h:205-243, ProgramGlobals.h:109-114)
-void hubbard_terms(int L, const double* hop_re, const double* hop_im, std::vector<HostProc>& hp, int species_mask = 3)
+void hubbard_terms(int L, const double* hop_re, const double* hop_im, std::vector<HostProc>& hp, int species_mask)
 {
 	for (int i = 0; i < L; i++) {
 		for (int j = 0; j < L; j++) {
@@ -183,6 +193,94 @@ void super_terms(int L, const double* jcoup, std::vector<HostProc>& hp)
 			const double amp = a + b; // one rounding at most, the same whichever of the two SparseRow::finalize meets first
 			push(hp, bit(j) | (bit(i) << L), bit(i) | (bit(j) << L), both | (both << L), rng | (rng << L), 0, 0, amp, 0.0, true);
 		}
+}
+
+int64_t species_states(int L, int n) { return (int64_t)binom(comb_table(), L, n); } // states of n particles on L sites
+
+void set_tx(lpp_engine* e, const TxGeom& g, int64_t n_up)
+{
+	e->tx = true;
+	e->tx_per = g.per;
+	e->tx_peru = g.peru;
+	e->kron_n_up_tx = n_up;
+}
+
+bool any_nonzero(const double* a, size_t n)
+{
+	bool nz = false;
+	for (size_t k = 0; a && k < n; k++) nz |= (a[k] != 0);
+	return nz;
+}
+
+// what the Hubbard entry points share of their argument check (each says "bad argument" under its own name)
+bool hubbard_args_ok(const lpp_engine* e, int L, int nup, int ndown, const double* hop_re, const double* U, const double* V)
+{
+	return e && hop_re && U && V && L >= 1 && L <= 31 && nup >= 0 && ndown >= 0 && nup <= L && ndown <= L;
+}
+
+// the term list and couplings of the Hubbard models on the device (lpp_engine_assemble_hubbard*, lpp_engine_setup_hubbard_onthefly*)
+struct HubbardDev {
+	DevBuf procs, comb, U, V, zeroU, ninj, jcoup;
+};
+// The delta-sorted term list into d and P: the hops of the species in species_mask (bit 0: up, bit 1: down) and, with jcoup, the spin-flip terms
+lpp_status hubbard_term_list(lpp_engine* e, int L, const double* hop_re, const double* hop_im, const double* jcoup, int species_mask, DevBuf& d, AsmParams& P)
+{
+	std::vector<HostProc> hp;
+	hubbard_terms(L, hop_re, hop_im, hp, species_mask);
+	if (jcoup) super_terms(L, jcoup, hp);
+	std::vector<Proc> procs;
+	int nneg = 0;
+	lpp_status st = finish_procs(hp, procs, &nneg);
+	if (st != LPP_OK) return st;
+	if ((st = upload(e->stream, d, procs.data(), sizeof(Proc) * procs.size())) != LPP_OK) return st;
+	HIP_TRY(hipStreamSynchronize(e->stream)); // procs is a local
+	P.procs = (const Proc*)d.p;
+	P.nproc = (int)procs.size();
+	P.nneg = nneg;
+	return LPP_OK;
+}
+// The whole matrix on one GPU (row0 = 0, nloc = every row, part 0); a caller with a partition sets its own rows.  ninj, jcoup: null = none
+lpp_status hubbard_asm_params(lpp_engine* e, int L, int nup, int ndown, const double* hop_re, const double* hop_im, const double* U, const double* V,
+                              const double* ninj, const double* jcoup, int species_mask, HubbardDev& D, AsmParams& P)
+{
+	const std::vector<uint64_t> comb = comb_table();
+	const std::vector<double> zeroU((size_t)L, 0.0);
+	P = AsmParams {};
+	lpp_status st = hubbard_term_list(e, L, hop_re, hop_im, jcoup, species_mask, D.procs, P);
+	if (st != LPP_OK) return st;
+	if ((st = upload(e->stream, D.comb, comb.data(), sizeof(uint64_t) * comb.size())) != LPP_OK) return st;
+	if ((st = upload(e->stream, D.U, U, sizeof(double) * L)) != LPP_OK) return st;
+	if ((st = upload(e->stream, D.V, V, sizeof(double) * L)) != LPP_OK) return st;
+	if ((st = upload(e->stream, D.zeroU, zeroU.data(), sizeof(double) * L)) != LPP_OK) return st;
+	if (ninj && (st = upload(e->stream, D.ninj, ninj, sizeof(double) * L * L)) != LPP_OK) return st;
+	if (jcoup && (st = upload(e->stream, D.jcoup, jcoup, sizeof(double) * L * L)) != LPP_OK) return st;
+	HIP_TRY(hipStreamSynchronize(e->stream)); // the host copies above are locals
+	P.model = ASM_HUBBARD;
+	P.L = L;
+	P.nup = nup;
+	P.ndown = ndown;
+	P.n_up = (int64_t)binom(comb, L, nup);
+	P.nrows_global = P.nloc = P.n_up * (int64_t)binom(comb, L, ndown);
+	P.comb = (const uint64_t*)D.comb.p;
+	P.d0 = (const double*)D.U.p;
+	P.d1 = (const double*)D.V.p;
+	P.d2 = (const double*)D.ninj.p; // Coulomb coupling of HubbardOneBandExtended
+	P.d3 = (const double*)D.jcoup.p; // spin coupling of SuperHubbardExtended
+	return LPP_OK;
+}
+// The same assembler with the other species empty: the one-species matrix of n_particles on P.L sites, n_states rows -- its hops plus its
+// potential diagonal sum_i V_i n_i (HubbardHelper.h:180-183); no U, no Coulomb term, no spin flips
+AsmParams one_species(AsmParams P, int n_particles, int64_t n_states, const double* zeroU)
+{
+	P.d0 = zeroU;
+	P.d2 = P.d3 = nullptr;
+	P.ndown = 0;
+	P.part = 0;
+	P.row0 = 0;
+	P.nup = n_particles;
+	P.n_up = n_states;
+	P.nrows_global = P.nloc = n_states;
+	return P;
 }
 
 // columns_are_local: every stored column index is rank-local (transposition exchange: own slice + transposed slice), so only
@@ -267,21 +365,9 @@ lpp_status assemble_hubbard_pb(lpp_engine* e, AsmParams P, int nup, int ndown, i
 			free_csr(b);
 		}
 	} guard { Tm, Cm };
-	AsmParams P1 = P;
-	P1.d0 = zeroU_dev;
-	P1.d2 = nullptr;
-	P1.ndown = 0;
-	P1.part = 0;
-	P1.row0 = 0;
-	P1.nup = nup;
-	P1.n_up = n_up;
-	P1.nrows_global = P1.nloc = n_up;
-	lpp_status rc = dispatch<ASM_HUBBARD>(e, P1, Tm, LPP_SPMV_ROWGROUP, 0);
+	lpp_status rc = dispatch<ASM_HUBBARD>(e, one_species(P, nup, n_up, zeroU_dev), Tm, LPP_SPMV_ROWGROUP, 0);
 	if (rc != LPP_OK) return rc;
-	P1.nup = ndown;
-	P1.n_up = n_dn;
-	P1.nrows_global = P1.nloc = n_dn;
-	rc = dispatch<ASM_HUBBARD>(e, P1, Cm, LPP_SPMV_ROWGROUP, 0);
+	rc = dispatch<ASM_HUBBARD>(e, one_species(P, ndown, n_dn, zeroU_dev), Cm, LPP_SPMV_ROWGROUP, 0);
 	if (rc != LPP_OK) return rc;
 	std::vector<int64_t> trp, crp;
 	std::vector<int32_t> tci, cci;
@@ -625,184 +711,102 @@ lpp_status lpp_engine_assemble_hubbard_super(lpp_engine* e, const lpp_comm* comm
                                              const double* hop_re, const double* hop_im, const double* U, const double* V,
                                              const double* ninj, const double* jcoup)
 {
-	if (!e || !hop_re || !U || !V || L < 1 || L > 31 || nup < 0 || ndown < 0 || nup > L || ndown > L)
-		return fail(LPP_ERR_INVALID, "lpp_engine_assemble_hubbard: bad argument (1 <= L <= 31)");
-	const std::vector<uint64_t> comb = comb_table();
-	const int64_t n_up = (int64_t)binom(comb, L, nup), n_dn = (int64_t)binom(comb, L, ndown);
+	if (!hubbard_args_ok(e, L, nup, ndown, hop_re, U, V)) return fail(LPP_ERR_INVALID, "lpp_engine_assemble_hubbard: bad argument (1 <= L <= 31)");
+	const int64_t n_up = species_states(L, nup), n_dn = species_states(L, ndown);
 	const int64_t nrows = n_up * n_dn;
-	bool cplx_in = false;
-	if (hop_im)
-		for (int k = 0; k < L * L; k++) cplx_in |= (hop_im[k] != 0);
-	// with the transposition exchange a rank stores columns of its own slice and of its transposed slice only
-	const bool local_columns = comm && comm->nranks > 1 && comm->exchange_begin && comm->exchange_end && comm->xchg_chunk > 0;
-	lpp_status st = common_setup(e, nrows, cplx_in, local_columns);
-	if (st != LPP_OK) return st;
-
-	bool has_j = false; // Model=SuperHubbardExtended: spin coupling (geometry term 2)
-	if (jcoup)
-		for (int k = 0; k < L * L; k++) has_j |= (jcoup[k] != 0);
-	if (!has_j) jcoup = nullptr;
-	std::vector<HostProc> hp;
-	hubbard_terms(L, hop_re, hop_im, hp);
-	if (jcoup) super_terms(L, jcoup, hp);
-	std::vector<Proc> procs;
-	int nneg = 0;
-	st = finish_procs(hp, procs, &nneg);
-	if (st != LPP_OK) return st;
-
-	DevBuf d_procs, d_comb, d_U, d_V, d_U0, d_jc;
-	if (jcoup && (st = upload(e->stream, d_jc, jcoup, sizeof(double) * L * L)) != LPP_OK) return st;
-	const std::vector<double> zeroU((size_t)L, 0.0);
-	if ((st = upload(e->stream, d_procs, procs.data(), sizeof(Proc) * procs.size())) != LPP_OK) return st;
-	if ((st = upload(e->stream, d_comb, comb.data(), sizeof(uint64_t) * comb.size())) != LPP_OK) return st;
-	if ((st = upload(e->stream, d_U, U, sizeof(double) * L)) != LPP_OK) return st;
-	if ((st = upload(e->stream, d_V, V, sizeof(double) * L)) != LPP_OK) return st;
-	if ((st = upload(e->stream, d_U0, zeroU.data(), sizeof(double) * L)) != LPP_OK) return st;
-	DevBuf d_ninj;
-	if (ninj && (st = upload(e->stream, d_ninj, ninj, sizeof(double) * L * L)) != LPP_OK) return st;
-
-	AsmParams P {};
-	P.model = ASM_HUBBARD;
-	P.L = L;
-	P.nup = nup;
-	P.ndown = ndown;
-	P.nproc = (int)procs.size();
-	P.nneg = nneg;
-	P.n_up = n_up;
-	P.nrows_global = nrows;
-	P.procs = (const Proc*)d_procs.p;
-	P.comb = (const uint64_t*)d_comb.p;
-	P.d0 = (const double*)d_U.p;
-	P.d1 = (const double*)d_V.p;
-	P.d2 = ninj ? (const double*)d_ninj.p : nullptr; // Coulomb coupling of HubbardOneBandExtended
-	P.d3 = jcoup ? (const double*)d_jc.p : nullptr; // spin coupling of SuperHubbardExtended
-
 	const bool multi = comm && comm->nranks > 1;
+	const TxGeom g = tx_geometry(comm, n_up, n_dn);
+	// with the transposition exchange a rank stores columns of its own slice and of its transposed slice only
+	lpp_status st = common_setup(e, nrows, any_nonzero(hop_im, (size_t)L * L), multi && g.requested);
+	if (st != LPP_OK) return st;
+	if (!any_nonzero(jcoup, (size_t)L * L)) jcoup = nullptr; // Model=SuperHubbardExtended: spin coupling (geometry term 2)
+	HubbardDev D;
+	AsmParams P {};
+	if ((st = hubbard_asm_params(e, L, nup, ndown, hop_re, hop_im, U, V, ninj, jcoup, 3, D, P)) != LPP_OK) return st;
+	const double* zeroU = (const double*)D.zeroU.p;
+
 	if (!multi) {
-		e->has_comm = false;
-		e->bind_scalars(e->scal_own);
-		free_csr(e->A_rem);
-		drop_product(e);
-		P.row0 = 0;
-		P.nloc = nrows;
-		P.part = 0;
+		begin_single_gpu(e);
 		bool as_product = false;
-		st = assemble_hubbard_pb(e, P, nup, ndown, n_up, n_dn, (const double*)d_U0.p, &as_product, 0, -1, 0, 0, true);
+		st = assemble_hubbard_pb(e, P, nup, ndown, n_up, n_dn, zeroU, &as_product, 0, -1, 0, 0, true);
 		if (st != LPP_OK) return st;
-		if (as_product) {
+		if (as_product)
 			free_csr(e->A_loc);
-		} else {
-			st = dispatch<ASM_HUBBARD>(e, P, e->A_loc);
-			if (st != LPP_OK) return st;
-		}
-		e->n_local = e->n_global = nrows;
-		e->row_start = 0;
-	} else {
-		st = e->adopt_comm(comm);
-		if (st != LPP_OK) return st;
-		// partition at multiples of N_up: whole down-configurations per rank, so the diagonal and all
-		// up-hops stay rank-local; gathered index == global index because stride == per*N_up
-		std::vector<int64_t> starts(comm->nranks + 1);
-		st = lpp_partition_rows(nrows, comm->nranks, n_up, starts.data());
-		if (st != LPP_OK) return st;
-		const int64_t per = (n_dn + comm->nranks - 1) / comm->nranks;
-		if (comm->shard_stride != per * n_up) return fail(LPP_ERR_INVALID, "assemble_hubbard: comm.shard_stride must be ceil(N_down/nranks)*N_up");
-		const bool transpose = comm->exchange_begin && comm->exchange_end && comm->xchg_chunk > 0;
-		if (transpose && jcoup) return fail(LPP_ERR_INVALID, "assemble_hubbard: spin-flip terms (SuperHubbardExtended) need the all-gather exchange");
-		// all-gather: remote columns index the gathered vector; transposition: columns index the rank's own slice (and its
-		// transposed slice, checked below), so the GLOBAL dimension may exceed 2^31 (e.g. the 3.0e9-state (7,6) sector of the 4x5 lattice)
-		if (!transpose && (int64_t)comm->nranks * comm->shard_stride > (int64_t)INT32_MAX)
-			return fail(LPP_ERR_INVALID, "assemble_hubbard: gathered vector exceeds 32-bit column range (use the transposition exchange)");
-		if (comm->shard_stride > (int64_t)INT32_MAX) return fail(LPP_ERR_INVALID, "assemble_hubbard: a rank's slice exceeds 32-bit column range");
-		P.row0 = starts[comm->rank];
-		P.nloc = starts[comm->rank + 1] - starts[comm->rank];
-		P.col_lo = starts[comm->rank];
-		P.col_hi = starts[comm->rank + 1];
-		drop_product(e);
-		if (!transpose) {
-			e->tx = false;
-			P.part = 1;
-			st = dispatch<ASM_HUBBARD>(e, P, e->A_loc);
-			if (st != LPP_OK) return st;
-			P.part = 2;
-			e->A_rem.src_elems = (int64_t)comm->nranks * comm->shard_stride;
-			st = dispatch<ASM_HUBBARD>(e, P, e->A_rem);
-			if (st != LPP_OK) return st;
-		} else {
-			// Transposition scheme: the up-hop + diagonal part acts on the rank's own slice (down-index partition);
-			// the down-hop part is assembled for the rank's UP-index range over ALL down indices, in the layout
-			// row = id*peru + (iu - iu0), and acts on the transposed slice delivered by the first all-to-all.
-			// xchg_chunk = per * peru with peru >= ceil(N_up/P) up indices per rank; a caller that rounds peru up to a multiple of 16
-			// gets the product-basis kernels on both parts when the matrix qualifies
-			const int64_t peru = per > 0 ? comm->xchg_chunk / per : 0;
-			if (!comm->send2_buf || !comm->recv2_buf || per <= 0 || comm->xchg_chunk != per * peru || peru * comm->nranks < n_up)
-				return fail(LPP_ERR_INVALID, "assemble_hubbard: transposition exchange needs send2/recv2 buffers and xchg_chunk == ceil(N_down/P) * peru, peru >= ceil(N_up/P)");
-			if ((int64_t)comm->nranks * per * peru > (int64_t)INT32_MAX) return fail(LPP_ERR_INVALID, "assemble_hubbard: transposed slice exceeds 32-bit column range");
-			if ((peru & 15) == 0 && P.nloc % n_up == 0) {
-				bool as_product = false;
-				st = assemble_hubbard_pb(e, P, nup, ndown, n_up, n_dn, (const double*)d_U0.p, &as_product, P.row0 / n_up, P.nloc / n_up, peru, (int64_t)comm->nranks * per);
-				if (st != LPP_OK) return st;
-				if (as_product) {
-					free_csr(e->A_loc);
-					free_csr(e->A_rem);
-					e->tx = true;
-					e->tx_per = per;
-					e->tx_peru = peru;
-					e->kron_n_up_tx = n_up;
-					e->n_local = P.nloc;
-					e->n_global = nrows;
-					e->row_start = P.row0;
-					e->active = false;
-					set_spmv_bytes(e);
-					return alloc_work(e);
-				}
-			}
-			std::vector<HostProc> hu, hd;
-			hubbard_terms(L, hop_re, hop_im, hu, 1);
-			hubbard_terms(L, hop_re, hop_im, hd, 2);
-			std::vector<Proc> pu, pd;
-			int nnegu = 0, nnegd = 0;
-			if ((st = finish_procs(hu, pu, &nnegu)) != LPP_OK) return st;
-			if ((st = finish_procs(hd, pd, &nnegd)) != LPP_OK) return st;
-			DevBuf d_pu, d_pd;
-			if ((st = upload(e->stream, d_pu, pu.data(), sizeof(Proc) * pu.size())) != LPP_OK) return st;
-			if ((st = upload(e->stream, d_pd, pd.data(), sizeof(Proc) * pd.size())) != LPP_OK) return st;
-			AsmParams Pu = P;
-			Pu.procs = (const Proc*)d_pu.p;
-			Pu.nproc = (int)pu.size();
-			Pu.nneg = nnegu;
-			Pu.part = 1;
-			st = dispatch<ASM_HUBBARD>(e, Pu, e->A_loc);
-			if (st != LPP_OK) return st;
-			AsmParams Pd = P;
-			Pd.procs = (const Proc*)d_pd.p;
-			Pd.nproc = (int)pd.size();
-			Pd.nneg = nnegd;
-			Pd.part = 0;
-			Pd.no_diag = 1;
-			Pd.tr = 1;
-			Pd.peru = peru;
-			Pd.iu0 = std::min<int64_t>((int64_t)comm->rank * peru, n_up);
-			Pd.nu = std::min<int64_t>(Pd.iu0 + peru, n_up) - Pd.iu0;
-			Pd.n_dn = n_dn;
-			Pd.row0 = 0;
-			Pd.nloc = (int64_t)comm->nranks * per * peru;
-			e->A_rem.src_elems = Pd.nloc;
-			st = dispatch<ASM_HUBBARD>(e, Pd, e->A_rem, LPP_SPMV_SLICED, peru);
-			if (st != LPP_OK) return st;
-			e->A_rem.hint_block = 0;
-			e->tx = true;
-			e->tx_per = per;
-			e->tx_peru = peru;
-			e->kron_n_up_tx = n_up;
-		}
-		e->n_local = P.nloc;
-		e->n_global = nrows;
-		e->row_start = P.row0;
+		else if ((st = dispatch<ASM_HUBBARD>(e, P, e->A_loc)) != LPP_OK)
+			return st;
+		return finish_setup(e, nrows, nrows, 0);
 	}
-	e->active = false;
-	set_spmv_bytes(e);
-	return alloc_work(e);
+	st = e->adopt_comm(comm);
+	if (st != LPP_OK) return st;
+	// partition at multiples of N_up: whole down-configurations per rank, so the diagonal and all
+	// up-hops stay rank-local; gathered index == global index because stride == per*N_up
+	std::vector<int64_t> starts(comm->nranks + 1);
+	st = lpp_partition_rows(nrows, comm->nranks, n_up, starts.data());
+	if (st != LPP_OK) return st;
+	if (comm->shard_stride != g.per * n_up) return fail(LPP_ERR_INVALID, "assemble_hubbard: comm.shard_stride must be ceil(N_down/nranks)*N_up");
+	const bool transpose = g.requested;
+	if (transpose && jcoup) return fail(LPP_ERR_INVALID, "assemble_hubbard: spin-flip terms (SuperHubbardExtended) need the all-gather exchange");
+	// all-gather: remote columns index the gathered vector; transposition: columns index the rank's own slice (and its
+	// transposed slice, checked below), so the GLOBAL dimension may exceed 2^31 (e.g. the 3.0e9-state (7,6) sector of the 4x5 lattice)
+	if (!transpose && (int64_t)comm->nranks * comm->shard_stride > (int64_t)INT32_MAX)
+		return fail(LPP_ERR_INVALID, "assemble_hubbard: gathered vector exceeds 32-bit column range (use the transposition exchange)");
+	if (comm->shard_stride > (int64_t)INT32_MAX) return fail(LPP_ERR_INVALID, "assemble_hubbard: a rank's slice exceeds 32-bit column range");
+	P.row0 = starts[comm->rank];
+	P.nloc = starts[comm->rank + 1] - starts[comm->rank];
+	P.col_lo = starts[comm->rank];
+	P.col_hi = starts[comm->rank + 1];
+	drop_product(e);
+	if (!transpose) {
+		P.part = 1;
+		st = dispatch<ASM_HUBBARD>(e, P, e->A_loc);
+		if (st != LPP_OK) return st;
+		P.part = 2;
+		e->A_rem.src_elems = (int64_t)comm->nranks * comm->shard_stride;
+		st = dispatch<ASM_HUBBARD>(e, P, e->A_rem);
+		if (st != LPP_OK) return st;
+		return finish_setup(e, P.nloc, nrows, P.row0);
+	}
+	// Transposition scheme: the up-hop + diagonal part acts on the rank's own slice (down-index partition);
+	// the down-hop part is assembled for the rank's UP-index range over ALL down indices, in the layout
+	// row = id*peru + (iu - iu0), and acts on the transposed slice delivered by the first all-to-all.
+	// xchg_chunk = per * peru with peru >= ceil(N_up/P) up indices per rank; a caller that rounds peru up to a multiple of 16
+	// gets the product-basis kernels on both parts when the matrix qualifies
+	if (!g.valid) return fail(LPP_ERR_INVALID, std::string("assemble_hubbard: ") + kTxGeomNeeds);
+	if (!g.fits32) return fail(LPP_ERR_INVALID, "assemble_hubbard: transposed slice exceeds 32-bit column range");
+	const int64_t nslice = (int64_t)comm->nranks * g.per; // down configurations in the transposed slice, padding included
+	bool as_product = false;
+	if (g.mult16 && P.nloc % n_up == 0) {
+		st = assemble_hubbard_pb(e, P, nup, ndown, n_up, n_dn, zeroU, &as_product, P.row0 / n_up, P.nloc / n_up, g.peru, nslice);
+		if (st != LPP_OK) return st;
+	}
+	if (as_product) {
+		free_csr(e->A_loc);
+		free_csr(e->A_rem);
+	} else {
+		DevBuf d_pu, d_pd; // the term lists of one species each
+		AsmParams Pu = P;
+		if ((st = hubbard_term_list(e, L, hop_re, hop_im, nullptr, 1, d_pu, Pu)) != LPP_OK) return st;
+		AsmParams Pd = P;
+		if ((st = hubbard_term_list(e, L, hop_re, hop_im, nullptr, 2, d_pd, Pd)) != LPP_OK) return st;
+		Pu.part = 1;
+		st = dispatch<ASM_HUBBARD>(e, Pu, e->A_loc);
+		if (st != LPP_OK) return st;
+		Pd.part = 0;
+		Pd.no_diag = 1;
+		Pd.tr = 1;
+		Pd.peru = g.peru;
+		Pd.iu0 = std::min<int64_t>((int64_t)comm->rank * g.peru, n_up);
+		Pd.nu = std::min<int64_t>(Pd.iu0 + g.peru, n_up) - Pd.iu0;
+		Pd.n_dn = n_dn;
+		Pd.row0 = 0;
+		Pd.nloc = nslice * g.peru;
+		e->A_rem.src_elems = Pd.nloc;
+		st = dispatch<ASM_HUBBARD>(e, Pd, e->A_rem, LPP_SPMV_SLICED, g.peru);
+		if (st != LPP_OK) return st;
+		e->A_rem.hint_block = 0;
+	}
+	set_tx(e, g, n_up);
+	return finish_setup(e, P.nloc, nrows, P.row0);
 }
 
 lpp_status lpp_engine_assemble_heisenberg(lpp_engine* e, int32_t L, int32_t szPlusConst, const double* jpm, const double* jzz,
@@ -817,10 +821,7 @@ lpp_status lpp_engine_assemble_heisenberg(lpp_engine* e, int32_t L, int32_t szPl
 	HeisDev D;
 	AsmParams P {};
 	if ((st = heis_asm_params(e, L, szPlusConst, jpm, jzz, field, nfield, D, P)) != LPP_OK) return st;
-	e->has_comm = false;
-	e->bind_scalars(e->scal_own);
-	free_csr(e->A_rem);
-	drop_product(e);
+	begin_single_gpu(e);
 	// A chain (couplings between neighbours, and between the two ends): one block of the product-basis form, planned from the couplings alone
 	// (heis_chain_try): no CSR is assembled (lpp_engine_get_csr re-runs the assembler), so the largest chain is bounded by its vectors
 	bool as_chain = false;
@@ -832,11 +833,7 @@ lpp_status lpp_engine_assemble_heisenberg(lpp_engine* e, int32_t L, int32_t szPl
 		st = dispatch<ASM_HEISENBERG>(e, P, e->A_loc);
 		if (st != LPP_OK) return st;
 	}
-	e->n_local = e->n_global = nrows;
-	e->row_start = 0;
-	e->active = false;
-	set_spmv_bytes(e);
-	return alloc_work(e);
+	return finish_setup(e, nrows, nrows, 0);
 }
 
 // Heisenberg with any spin the reference's digit width can hold (BasisHeisenberg.h:28-46: bits = 1 + floor(log2(twiceS + 1)), one
@@ -936,17 +933,10 @@ lpp_status lpp_engine_assemble_heisenberg_spin(lpp_engine* e, int32_t L, int32_t
 	P.row0 = 0;
 	P.nloc = nrows;
 	P.part = 0;
-	e->has_comm = false;
-	e->bind_scalars(e->scal_own);
-	free_csr(e->A_rem);
-	drop_product(e);
+	begin_single_gpu(e);
 	st = dispatch<ASM_HEISENBERG_S>(e, P, e->A_loc);
 	if (st != LPP_OK) return st;
-	e->n_local = e->n_global = nrows;
-	e->row_start = 0;
-	e->active = false;
-	set_spmv_bytes(e);
-	return alloc_work(e);
+	return finish_setup(e, nrows, nrows, 0);
 }
 
 lpp_status lpp_engine_assemble_tj(lpp_engine* e, int32_t L, int32_t nup, int32_t ndown, const double* hop_re, const double* hop_im,
@@ -955,21 +945,7 @@ lpp_status lpp_engine_assemble_tj(lpp_engine* e, int32_t L, int32_t nup, int32_t
 	if (!e || !hop_re || !jpm || !jzz || !w || L < 1 || L > 31 || nup < 0 || ndown < 0 || nup + ndown > L)
 		return fail(LPP_ERR_INVALID, "lpp_engine_assemble_tj: bad argument (1 <= L <= 31, nup+ndown <= L)");
 	if (potentialV && npot > 0 && npot < 2 * L) return fail(LPP_ERR_INVALID, "lpp_engine_assemble_tj: potentialV needs 2*L entries (up then down)");
-	TjModel M;
-	M.L = L;
-	M.nup = nup;
-	M.ndown = ndown;
-	M.npot = npot;
-	const size_t LL = (size_t)L * L;
-	M.hop_re.assign(hop_re, hop_re + LL);
-	if (hop_im) M.hop_im.assign(hop_im, hop_im + LL);
-	M.jpm.assign(jpm, jpm + LL);
-	M.jzz.assign(jzz, jzz + LL);
-	M.w.assign(w, w + LL);
-	M.has_pv = potentialV && npot > 0;
-	if (M.has_pv) M.pv.assign(potentialV, potentialV + 2 * (size_t)L);
-	if (hop_im)
-		for (size_t k = 0; k < LL; k++) M.has_im |= (hop_im[k] != 0);
+	const TjModel M = tj_model_from_args(L, nup, ndown, hop_re, hop_im, jpm, jzz, w, potentialV, npot);
 	const std::vector<uint64_t> comb = comb_table();
 	const int64_t nrows = (int64_t)binom(comb, L, ndown) * (int64_t)binom(comb, L - ndown, nup);
 	lpp_status st = common_setup(e, nrows, M.has_im);
@@ -977,10 +953,7 @@ lpp_status lpp_engine_assemble_tj(lpp_engine* e, int32_t L, int32_t nup, int32_t
 	TjDev D;
 	AsmParams P {};
 	if ((st = tj_asm_params(e, M, D, P)) != LPP_OK) return st;
-	e->has_comm = false;
-	e->bind_scalars(e->scal_own);
-	free_csr(e->A_rem);
-	drop_product(e);
+	begin_single_gpu(e);
 	// the hole-major form without a stored matrix (lpp_tj_kernels.h) where it applies; otherwise the CSR in the general layout
 	bool as_tj = false;
 	if ((st = tj_build(e, M, P, &as_tj)) != LPP_OK) return st;
@@ -990,11 +963,7 @@ lpp_status lpp_engine_assemble_tj(lpp_engine* e, int32_t L, int32_t nup, int32_t
 		st = dispatch<ASM_TJ>(e, P, e->A_loc);
 		if (st != LPP_OK) return st;
 	}
-	e->n_local = e->n_global = nrows;
-	e->row_start = 0;
-	e->active = false;
-	set_spmv_bytes(e);
-	return alloc_work(e);
+	return finish_setup(e, nrows, nrows, 0);
 }
 
 
@@ -1116,121 +1085,54 @@ lpp_status lpp_engine_setup_hubbard_onthefly_ext(lpp_engine* e, const lpp_comm* 
                                                  const double* hop_re, const double* hop_im, const double* U, const double* V,
                                                  const double* ninj)
 {
-	if (!e || !hop_re || !U || !V || L < 1 || L > 31 || nup < 0 || ndown < 0 || nup > L || ndown > L)
-		return fail(LPP_ERR_INVALID, "lpp_engine_setup_hubbard_onthefly: bad argument (1 <= L <= 31)");
-	const std::vector<uint64_t> comb = comb_table();
-	const int64_t n_up = (int64_t)binom(comb, L, nup), n_dn = (int64_t)binom(comb, L, ndown);
-	bool cplx_in = false;
-	if (hop_im)
-		for (int k = 0; k < L * L; k++) cplx_in |= (hop_im[k] != 0);
-	if (cplx_in && !e->is_complex) return fail(LPP_ERR_INVALID, "setup_hubbard_onthefly: complex hoppings need a c128 engine");
+	if (!hubbard_args_ok(e, L, nup, ndown, hop_re, U, V)) return fail(LPP_ERR_INVALID, "lpp_engine_setup_hubbard_onthefly: bad argument (1 <= L <= 31)");
+	const int64_t n_up = species_states(L, nup), n_dn = species_states(L, ndown);
+	if (any_nonzero(hop_im, (size_t)L * L) && !e->is_complex) return fail(LPP_ERR_INVALID, "setup_hubbard_onthefly: complex hoppings need a c128 engine");
 	if (n_up <= 0 || n_dn <= 0) return fail(LPP_ERR_INVALID, "setup_hubbard_onthefly: empty Hilbert space");
 	if (n_up > (int64_t)INT32_MAX || n_dn > (int64_t)INT32_MAX) return fail(LPP_ERR_INVALID, "setup_hubbard_onthefly: one-species space too large");
 	HIP_TRY(hipSetDevice(e->cfg.device));
 	const bool multi = comm && comm->nranks > 1;
+	const TxGeom g = tx_geometry(comm, n_up, n_dn);
 	lpp_status st = LPP_OK;
 	int64_t id0 = 0, nid = n_dn;
 	if (multi) {
 		st = e->adopt_comm(comm);
 		if (st != LPP_OK) return st;
-		const int64_t per = (n_dn + comm->nranks - 1) / comm->nranks;
-		if (comm->shard_stride != per * n_up) return fail(LPP_ERR_INVALID, "setup_hubbard_onthefly: comm.shard_stride must be ceil(N_down/nranks)*N_up");
-		id0 = std::min<int64_t>((int64_t)comm->rank * per, n_dn);
-		nid = std::min<int64_t>(id0 + per, n_dn) - id0;
-	} else {
-		e->has_comm = false;
-		e->bind_scalars(e->scal_own);
-	}
+		if (comm->shard_stride != g.per * n_up) return fail(LPP_ERR_INVALID, "setup_hubbard_onthefly: comm.shard_stride must be ceil(N_down/nranks)*N_up");
+		id0 = std::min<int64_t>((int64_t)comm->rank * g.per, n_dn);
+		nid = std::min<int64_t>(id0 + g.per, n_dn) - id0;
+		free_csr(e->A_rem);
+		drop_product(e);
+	} else
+		begin_single_gpu(e);
 	free_csr(e->A_loc);
-	free_csr(e->A_rem);
-	drop_product(e);
 	KronState& K = e->kron;
-
-	std::vector<HostProc> hp;
-	hubbard_terms(L, hop_re, hop_im, hp);
-	std::vector<Proc> procs;
-	int nneg = 0;
-	st = finish_procs(hp, procs, &nneg);
-	if (st != LPP_OK) return st;
-	std::vector<double> zeroU(L, 0.0);
-	DevBuf d_procs, d_comb, d_U0, d_V;
-	if ((st = upload(e->stream, d_procs, procs.data(), sizeof(Proc) * procs.size())) != LPP_OK) return st;
-	if ((st = upload(e->stream, d_comb, comb.data(), sizeof(uint64_t) * comb.size())) != LPP_OK) return st;
-	if ((st = upload(e->stream, d_U0, zeroU.data(), sizeof(double) * L)) != LPP_OK) return st;
-	if ((st = upload(e->stream, d_V, V, sizeof(double) * L)) != LPP_OK) return st;
+	HubbardDev D;
+	AsmParams Pf {};
+	if ((st = hubbard_asm_params(e, L, nup, ndown, hop_re, hop_im, U, V, ninj, nullptr, 3, D, Pf)) != LPP_OK) return st;
+	Pf.row0 = id0 * n_up;
+	Pf.nloc = nid * n_up;
+	const double* zeroU = (const double*)D.zeroU.p;
 	// Where one species' row fits the LDS window the matrix-free product IS the product-basis one: H = 1 (x) T + C (x) 1 + D with T, C
 	// (a few hundred KB) and one diagonal code per row -- an eighth of a vector -- is everything it keeps, and its two kernels move a
 	// third of what the fused block-order kernel below moves (10.9 against 31.3 GB per step at BASELINE config 2).  The kernels
 	// below serve what does not qualify: rows beyond the window (config 5's sectors), complex hoppings, small problems.
 	// LPP_ONTHEFLY_KRON=1 keeps them for everything (tests cross-check the two).
 	if (!e->is_complex && !(getenv("LPP_ONTHEFLY_KRON") && atoi(getenv("LPP_ONTHEFLY_KRON")) != 0)) {
-		DevBuf d_U, d_nj;
-		if ((st = upload(e->stream, d_U, U, sizeof(double) * L)) != LPP_OK) return st;
-		if (ninj && (st = upload(e->stream, d_nj, ninj, sizeof(double) * L * L)) != LPP_OK) return st;
-		AsmParams Pf {};
-		Pf.model = ASM_HUBBARD;
-		Pf.L = L;
-		Pf.nup = nup;
-		Pf.ndown = ndown;
-		Pf.nproc = (int)procs.size();
-		Pf.nneg = nneg;
-		Pf.n_up = n_up;
-		Pf.nrows_global = n_up * n_dn;
-		Pf.procs = (const Proc*)d_procs.p;
-		Pf.comb = (const uint64_t*)d_comb.p;
-		Pf.d0 = (const double*)d_U.p;
-		Pf.d1 = (const double*)d_V.p;
-		Pf.d2 = ninj ? (const double*)d_nj.p : nullptr;
-		Pf.row0 = id0 * n_up;
-		Pf.nloc = nid * n_up;
 		bool as_product = false;
-		if (!multi) {
-			st = assemble_hubbard_pb(e, Pf, nup, ndown, n_up, n_dn, (const double*)d_U0.p, &as_product);
-		} else if (comm->exchange_begin && comm->exchange_end && comm->xchg_chunk > 0 && comm->send2_buf && comm->recv2_buf) {
-			const int64_t per = (n_dn + comm->nranks - 1) / comm->nranks, peru = per > 0 ? comm->xchg_chunk / per : 0;
-			if (per > 0 && comm->xchg_chunk == per * peru && peru * comm->nranks >= n_up && (peru & 15) == 0) {
-				st = assemble_hubbard_pb(e, Pf, nup, ndown, n_up, n_dn, (const double*)d_U0.p, &as_product, id0, nid, peru, (int64_t)comm->nranks * per);
-				if (st == LPP_OK && as_product) {
-					e->tx = true;
-					e->tx_per = per;
-					e->tx_peru = peru;
-					e->kron_n_up_tx = n_up;
-				}
-			}
+		if (!multi)
+			st = assemble_hubbard_pb(e, Pf, nup, ndown, n_up, n_dn, zeroU, &as_product);
+		else if (g.valid && g.mult16) { // (any other geometry: the kernels below, whose own check follows)
+			st = assemble_hubbard_pb(e, Pf, nup, ndown, n_up, n_dn, zeroU, &as_product, id0, nid, g.peru, (int64_t)comm->nranks * g.per);
+			if (st == LPP_OK && as_product) set_tx(e, g, n_up);
 		}
 		if (st != LPP_OK) return st;
-		if (as_product) {
-			e->n_local = nid * n_up;
-			e->n_global = n_up * n_dn;
-			e->row_start = id0 * n_up;
-			e->active = false;
-			set_spmv_bytes(e);
-			return alloc_work(e);
-		}
+		if (as_product) return finish_setup(e, nid * n_up, n_up * n_dn, id0 * n_up);
 	}
-	// one-species matrices = the Hubbard assembler with the other species empty: hops of that species plus
-	// its potential diagonal sum_i V_i n_i (HubbardHelper.h:180-183); the U term is applied by the kernel
-	AsmParams P {};
-	P.model = ASM_HUBBARD;
-	P.L = L;
-	P.ndown = 0;
-	P.nproc = (int)procs.size();
-	P.nneg = nneg;
-	P.procs = (const Proc*)d_procs.p;
-	P.comb = (const uint64_t*)d_comb.p;
-	P.d0 = (const double*)d_U0.p;
-	P.d1 = (const double*)d_V.p;
-	P.part = 0;
-	P.row0 = 0;
-	P.nup = nup;
-	P.n_up = n_up;
-	P.nrows_global = P.nloc = n_up;
-	st = dispatch<ASM_HUBBARD>(e, P, K.up, LPP_SPMV_ROWGROUP, 0); // plain CSR first; packed or sliced below
+	// the one-species matrices; the U term is applied by the kernel
+	st = dispatch<ASM_HUBBARD>(e, one_species(Pf, nup, n_up, zeroU), K.up, LPP_SPMV_ROWGROUP, 0); // plain CSR first; packed or sliced below
 	if (st != LPP_OK) return st;
-	P.nup = ndown;
-	P.n_up = n_dn;
-	P.nrows_global = P.nloc = n_dn;
-	st = dispatch<ASM_HUBBARD>(e, P, K.dn, LPP_SPMV_ROWGROUP, 0); // plain CSR
+	st = dispatch<ASM_HUBBARD>(e, one_species(Pf, ndown, n_dn, zeroU), K.dn, LPP_SPMV_ROWGROUP, 0); // plain CSR
 	if (st != LPP_OK) return st;
 	K.up.hint_block = K.dn.hint_block = 0;
 	st = e->is_complex ? build_kron_up<cplx>(e, n_up) : build_kron_up<double>(e, n_up);
@@ -1242,8 +1144,8 @@ lpp_status lpp_engine_setup_hubbard_onthefly_ext(lpp_engine* e, const lpp_comm* 
 	std::vector<double> U32(32, 0.0);
 	for (int i = 0; i < L; i++) U32[i] = U[i];
 	HIP_TRY(hipMemcpyAsync(K.U, U32.data(), sizeof(double) * 32, hipMemcpyHostToDevice, e->stream));
-	k_basis_words<<<(int)((n_up + 255) / 256), 256, 0, e->stream>>>((const uint64_t*)d_comb.p, kCombDim, n_up, nup, L, K.up_words);
-	k_basis_words<<<(int)((n_dn + 255) / 256), 256, 0, e->stream>>>((const uint64_t*)d_comb.p, kCombDim, n_dn, ndown, L, K.dn_words);
+	k_basis_words<<<(int)((n_up + 255) / 256), 256, 0, e->stream>>>((const uint64_t*)D.comb.p, kCombDim, n_up, nup, L, K.up_words);
+	k_basis_words<<<(int)((n_dn + 255) / 256), 256, 0, e->stream>>>((const uint64_t*)D.comb.p, kCombDim, n_dn, ndown, L, K.dn_words);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipStreamSynchronize(e->stream));
 	if (ninj) {
@@ -1289,23 +1191,13 @@ lpp_status lpp_engine_setup_hubbard_onthefly_ext(lpp_engine* e, const lpp_comm* 
 	// entries of the stored CSR this product represents (one diagonal per row + all hops), for the local rows
 	const double off_up = (double)K.up.nnz - (double)n_up, off_dn_total = (double)K.dn.nnz - (double)n_dn;
 	K.equiv_nnz = (double)nid * ((double)n_up + off_up) + (double)n_up * off_dn_total * ((double)nid / (double)n_dn);
-	if (multi && comm->exchange_begin && comm->exchange_end && comm->xchg_chunk > 0) {
-		const int64_t per = (n_dn + comm->nranks - 1) / comm->nranks, peru = per > 0 ? comm->xchg_chunk / per : 0;
+	if (multi && g.requested) {
 		if (!K.packed) return fail(LPP_ERR_INVALID, "setup_hubbard_onthefly: the transposition exchange needs the packed H_up layout");
-		if (!comm->send2_buf || !comm->recv2_buf || per <= 0 || comm->xchg_chunk != per * peru || peru * comm->nranks < n_up)
-			return fail(LPP_ERR_INVALID, "setup_hubbard_onthefly: transposition exchange needs send2/recv2 buffers and xchg_chunk == ceil(N_down/P) * peru, peru >= ceil(N_up/P)");
-		e->tx = true;
-		e->tx_per = per;
-		e->tx_peru = peru;
-		e->kron_n_up_tx = n_up;
+		if (!g.valid) return fail(LPP_ERR_INVALID, std::string("setup_hubbard_onthefly: ") + kTxGeomNeeds);
+		set_tx(e, g, n_up);
 	}
 	K.active = true;
-	e->n_local = nid * n_up;
-	e->n_global = n_up * n_dn;
-	e->row_start = id0 * n_up;
-	e->active = false;
-	set_spmv_bytes(e);
-	return alloc_work(e);
+	return finish_setup(e, nid * n_up, n_up * n_dn, id0 * n_up);
 }
 
 
@@ -1313,81 +1205,34 @@ lpp_status lpp_engine_setup_hubbard_onthefly_super(lpp_engine* e, const lpp_comm
                                                    const double* hop_re, const double* hop_im, const double* U, const double* V,
                                                    const double* ninj, const double* jcoup)
 {
-	bool has_j = false;
-	if (jcoup && L >= 1 && L <= 31)
-		for (int k = 0; k < L * L; k++) has_j |= (jcoup[k] != 0);
+	const bool has_j = jcoup && L >= 1 && L <= 31 && any_nonzero(jcoup, (size_t)L * L);
 	if (!has_j) return lpp_engine_setup_hubbard_onthefly_ext(e, comm, L, nup, ndown, hop_re, hop_im, U, V, ninj);
-	if (!e || !hop_re || !U || !V || nup < 0 || ndown < 0 || nup > L || ndown > L) return fail(LPP_ERR_INVALID, "lpp_engine_setup_hubbard_onthefly_super: bad argument (1 <= L <= 31)");
+	if (!hubbard_args_ok(e, L, nup, ndown, hop_re, U, V)) return fail(LPP_ERR_INVALID, "lpp_engine_setup_hubbard_onthefly_super: bad argument (1 <= L <= 31)");
 	if (comm && comm->nranks > 1) return fail(LPP_ERR_INVALID, "setup_hubbard_onthefly_super: the term-list product runs on one GPU (partition the stored matrix instead: lpp_engine_assemble_hubbard_super)");
-	const std::vector<uint64_t> comb = comb_table();
-	const int64_t n_up = (int64_t)binom(comb, L, nup), n_dn = (int64_t)binom(comb, L, ndown);
-	bool cplx_in = false;
-	if (hop_im)
-		for (int k = 0; k < L * L; k++) cplx_in |= (hop_im[k] != 0);
-	if (cplx_in && !e->is_complex) return fail(LPP_ERR_INVALID, "setup_hubbard_onthefly_super: complex hoppings need a c128 engine");
+	const int64_t n_up = species_states(L, nup), n_dn = species_states(L, ndown);
+	if (any_nonzero(hop_im, (size_t)L * L) && !e->is_complex) return fail(LPP_ERR_INVALID, "setup_hubbard_onthefly_super: complex hoppings need a c128 engine");
 	if (n_up <= 0 || n_dn <= 0) return fail(LPP_ERR_INVALID, "setup_hubbard_onthefly_super: empty Hilbert space");
 	HIP_TRY(hipSetDevice(e->cfg.device));
-	e->has_comm = false;
-	e->bind_scalars(e->scal_own);
+	begin_single_gpu(e);
 	free_csr(e->A_loc);
-	free_csr(e->A_rem);
-	drop_product(e);
 	KronState& K = e->kron;
-	std::vector<HostProc> hp;
-	hubbard_terms(L, hop_re, hop_im, hp);
-	super_terms(L, jcoup, hp);
-	std::vector<Proc> procs;
-	int nneg = 0;
-	lpp_status st = finish_procs(hp, procs, &nneg);
+	HubbardDev D;
+	AsmParams P {};
+	lpp_status st = hubbard_asm_params(e, L, nup, ndown, hop_re, hop_im, U, V, ninj, jcoup, 3, D, P);
 	if (st != LPP_OK) return st;
-	// the device buffers live as long as the product does (K.terms_bufs, released by free_kron)
-	auto keep = [&](int slot, const void* src, size_t bytes) -> lpp_status {
-		HIP_TRY_MEM(hipMalloc(&K.terms_bufs[slot], std::max<size_t>(bytes, 8)));
-		if (bytes) HIP_TRY(hipMemcpyAsync(K.terms_bufs[slot], src, bytes, hipMemcpyHostToDevice, e->stream));
-		return LPP_OK;
-	};
-	if ((st = keep(0, procs.data(), sizeof(Proc) * procs.size())) != LPP_OK) return st;
-	if ((st = keep(1, comb.data(), sizeof(uint64_t) * comb.size())) != LPP_OK) return st;
-	if ((st = keep(2, U, sizeof(double) * L)) != LPP_OK) return st;
-	if ((st = keep(3, V, sizeof(double) * L)) != LPP_OK) return st;
-	if (ninj && (st = keep(4, ninj, sizeof(double) * L * L)) != LPP_OK) return st;
-	if ((st = keep(5, jcoup, sizeof(double) * L * L)) != LPP_OK) return st;
-	HIP_TRY(hipStreamSynchronize(e->stream)); // the host vectors above go out of scope
-	AsmParams* P = new AsmParams();
-	P->model = ASM_HUBBARD;
-	P->L = L;
-	P->nup = nup;
-	P->ndown = ndown;
-	P->nproc = (int)procs.size();
-	P->nneg = nneg;
-	P->n_up = n_up;
-	P->nrows_global = P->nloc = n_up * n_dn;
-	P->row0 = 0;
-	P->part = 0;
-	P->procs = (const Proc*)K.terms_bufs[0];
-	P->comb = (const uint64_t*)K.terms_bufs[1];
-	P->d0 = (const double*)K.terms_bufs[2];
-	P->d1 = (const double*)K.terms_bufs[3];
-	P->d2 = (const double*)K.terms_bufs[4];
-	P->d3 = (const double*)K.terms_bufs[5];
-	K.terms_params = P;
+	K.terms_params = new AsmParams(P);
+	// the device buffers live as long as the product does: handed to K.terms_bufs, released by free_kron
+	int slot = 0;
+	for (DevBuf* b : { &D.procs, &D.comb, &D.U, &D.V, &D.zeroU, &D.ninj, &D.jcoup }) {
+		K.terms_bufs[slot++] = b->p;
+		b->p = nullptr;
+	}
 	// entries of the CSR this product stands for (statistics only): one count pass
 	{
-		DevBuf len, sums, total;
-		const int64_t n = P->nloc + 1;
-		const int64_t nblk = (n + kScanChunk - 1) / kScanChunk;
-		HIP_TRY_MEM(hipMalloc(&len.p, sizeof(int64_t) * (size_t)n));
-		HIP_TRY(hipMemsetAsync(len.p, 0, sizeof(int64_t) * (size_t)n, e->stream));
-		HIP_TRY_MEM(hipMalloc(&sums.p, sizeof(int64_t) * (size_t)nblk));
-		HIP_TRY_MEM(hipMalloc(&total.p, sizeof(int64_t)));
-		const int nb = (int)std::max<int64_t>(1, std::min<int64_t>((P->nloc + kBlock - 1) / kBlock, 1 << 20));
-		k_asm_count<ASM_HUBBARD><<<nb, kBlock, 0, e->stream>>>(*P, (int64_t*)len.p);
-		k_scan_block_sums<<<(int)nblk, kBlock, 0, e->stream>>>((const int64_t*)len.p, n, (int64_t*)sums.p);
-		k_scan_sums<<<1, kBlock, 0, e->stream>>>((int64_t*)sums.p, nblk, (int64_t*)total.p);
+		DevBuf len;
 		int64_t nnz = 0;
-		HIP_TRY(hipMemcpyAsync(&nnz, total.p, sizeof(int64_t), hipMemcpyDeviceToHost, e->stream));
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipStreamSynchronize(e->stream));
+		HIP_TRY_MEM(hipMalloc(&len.p, sizeof(int64_t) * (size_t)(P.nloc + 1)));
+		if ((st = count_rows<ASM_HUBBARD>(e->stream, P, (int64_t*)len.p, false, &nnz)) != LPP_OK) return st;
 		K.equiv_nnz = (double)nnz;
 	}
 	K.terms = true;
@@ -1397,11 +1242,7 @@ lpp_status lpp_engine_setup_hubbard_onthefly_super(lpp_engine* e, const lpp_comm
 	K.id0 = 0;
 	K.nid = n_dn;
 	K.active = true;
-	e->n_local = e->n_global = n_up * n_dn;
-	e->row_start = 0;
-	e->active = false;
-	set_spmv_bytes(e);
-	return alloc_work(e);
+	return finish_setup(e, n_up * n_dn, n_up * n_dn, 0);
 }
 
 } // extern "C"

@@ -948,6 +948,27 @@ lpp_status alloc_work(lpp_engine* e)
 	return LPP_OK;
 }
 
+// The skeleton of a matrix set-up entry point: begin, build, finish.  The opening step of the single-GPU ones: no communicator,
+// the engine's own scalars, no remote part, no product state.  A_loc is the caller's to free, before or after its builder.
+void begin_single_gpu(lpp_engine* e)
+{
+	e->has_comm = false;
+	e->bind_scalars(e->scal_own);
+	free_csr(e->A_rem);
+	drop_product(e);
+}
+
+// ... and the closing step of every one: the only place that sets the rows of a new matrix and ends a Lanczos run in flight
+lpp_status finish_setup(lpp_engine* e, int64_t n_local, int64_t n_global, int64_t row_start)
+{
+	e->n_local = n_local;
+	e->n_global = n_global;
+	e->row_start = row_start;
+	e->active = false;
+	set_spmv_bytes(e);
+	return alloc_work(e);
+}
+
 } // namespace lpp
 
 // Plain CSR order (columns, values) of a matrix whose only resident form is the sliced layout: undo the slot-major
@@ -1107,23 +1128,24 @@ static lpp_status try_product_layout(lpp_engine* e, DevCsr& A, bool* as_product)
 	return LPP_OK;
 }
 
-static lpp_status upload_csr(lpp_engine* e, DevCsr& A, int64_t nrows, const int64_t* rowptr, const int32_t* colind, const void* values,
-                             int64_t hint_block = 0, bool try_product = false)
+// rowptr / colind / values: host or device memory, as `kind` says
+static lpp_status upload_csr(lpp_engine* e, DevCsr& A, int64_t nrows, int64_t nnz, const int64_t* rowptr, const int32_t* colind, const void* values,
+                             hipMemcpyKind kind, int64_t hint_block = 0, bool try_product = false)
 {
-	const int64_t keep_src = A.src_elems;
+	const int64_t keep_src = A.src_elems; // (A_rem: set by the caller before the call; A_loc never has one)
 	free_csr(A);
 	A.src_elems = keep_src;
 	A.hint_block = hint_block;
 	A.nrows = nrows;
-	A.nnz = rowptr ? rowptr[nrows] : 0;
+	A.nnz = nnz;
 	A.owned = true;
 	HIP_TRY_MEM(hipMalloc(&A.rowptr, sizeof(int64_t) * (size_t)(nrows + 1)));
 	HIP_TRY_MEM(hipMalloc(&A.col, sizeof(int32_t) * (size_t)std::max<int64_t>(A.nnz, 1)));
 	HIP_TRY_MEM(hipMalloc(&A.val, e->esz * (size_t)std::max<int64_t>(A.nnz, 1)));
-	HIP_TRY(hipMemcpyAsync(A.rowptr, rowptr, sizeof(int64_t) * (size_t)(nrows + 1), hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipMemcpyAsync(A.rowptr, rowptr, sizeof(int64_t) * (size_t)(nrows + 1), kind, e->stream));
 	if (A.nnz > 0) {
-		HIP_TRY(hipMemcpyAsync(A.col, colind, sizeof(int32_t) * (size_t)A.nnz, hipMemcpyHostToDevice, e->stream));
-		HIP_TRY(hipMemcpyAsync(A.val, values, e->esz * (size_t)A.nnz, hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(A.col, colind, sizeof(int32_t) * (size_t)A.nnz, kind, e->stream));
+		HIP_TRY(hipMemcpyAsync(A.val, values, e->esz * (size_t)A.nnz, kind, e->stream));
 	}
 	HIP_TRY(hipStreamSynchronize(e->stream));
 	if (try_product) {
@@ -1160,21 +1182,7 @@ lpp_status lpp_engine_set_model_tj(lpp_engine* e, int32_t L, int32_t nup, int32_
 	if (L == 0) return LPP_OK; // forget the description
 	if (!hop_re || !jpm || !jzz || !w || L < 1 || L > 31 || nup < 0 || ndown < 0 || nup + ndown > L || (potentialV && npot > 0 && npot < 2 * L))
 		return fail(LPP_ERR_INVALID, "lpp_engine_set_model_tj: bad argument");
-	TjModel& M = e->hint.tj;
-	M.L = L;
-	M.nup = nup;
-	M.ndown = ndown;
-	M.npot = npot;
-	const size_t LL = (size_t)L * L;
-	M.hop_re.assign(hop_re, hop_re + LL);
-	if (hop_im) M.hop_im.assign(hop_im, hop_im + LL);
-	M.jpm.assign(jpm, jpm + LL);
-	M.jzz.assign(jzz, jzz + LL);
-	M.w.assign(w, w + LL);
-	M.has_pv = potentialV && npot > 0;
-	if (M.has_pv) M.pv.assign(potentialV, potentialV + 2 * (size_t)L);
-	if (hop_im)
-		for (size_t k = 0; k < LL; k++) M.has_im |= (hop_im[k] != 0);
+	e->hint.tj = tj_model_from_args(L, nup, ndown, hop_re, hop_im, jpm, jzz, w, potentialV, npot);
 	e->hint.kind = 1;
 	return LPP_OK;
 }
@@ -1204,17 +1212,10 @@ lpp_status lpp_engine_set_csr(lpp_engine* e, int64_t nrows, const int64_t* rowpt
 	lpp_status st = check_csr_host(nrows, nrows, rowptr, colind);
 	if (st != LPP_OK) return st;
 	HIP_TRY(hipSetDevice(e->cfg.device));
-	e->has_comm = false;
-	e->bind_scalars(e->scal_own);
-	free_csr(e->A_rem);
-	drop_product(e);
-	st = upload_csr(e, e->A_loc, nrows, rowptr, colind, values, e->row_block_hint, true);
+	begin_single_gpu(e);
+	st = upload_csr(e, e->A_loc, nrows, rowptr[nrows], rowptr, colind, values, hipMemcpyHostToDevice, e->row_block_hint, true);
 	if (st != LPP_OK) return st;
-	e->n_local = e->n_global = nrows;
-	e->row_start = 0;
-	e->active = false;
-	set_spmv_bytes(e);
-	return alloc_work(e);
+	return finish_setup(e, nrows, nrows, 0);
 }
 
 lpp_status lpp_engine_set_csr_device(lpp_engine* e, int64_t nrows, const int64_t* d_rowptr, const int32_t* d_colind, const void* d_values)
@@ -1237,35 +1238,10 @@ lpp_status lpp_engine_set_csr_device(lpp_engine* e, int64_t nrows, const int64_t
 	(void)hipFree(bad);
 	if (e1 != hipSuccess || e2 != hipSuccess) return fail(LPP_ERR_HIP, "lpp_engine_set_csr_device: validation failed to run");
 	if (hbad) return fail(LPP_ERR_INVALID, "CSR: rowptr not monotone from 0 or column index out of range");
-	e->has_comm = false;
-	e->bind_scalars(e->scal_own);
-	free_csr(e->A_rem);
-	drop_product(e);
-	DevCsr& A = e->A_loc;
-	free_csr(A);
-	A.hint_block = e->row_block_hint;
-	A.nrows = nrows;
-	A.nnz = nnz;
-	A.owned = true;
-	HIP_TRY_MEM(hipMalloc(&A.rowptr, sizeof(int64_t) * (size_t)(nrows + 1)));
-	HIP_TRY_MEM(hipMalloc(&A.col, sizeof(int32_t) * (size_t)std::max<int64_t>(nnz, 1)));
-	HIP_TRY_MEM(hipMalloc(&A.val, e->esz * (size_t)std::max<int64_t>(nnz, 1)));
-	HIP_TRY(hipMemcpyAsync(A.rowptr, d_rowptr, sizeof(int64_t) * (size_t)(nrows + 1), hipMemcpyDeviceToDevice, e->stream));
-	if (nnz > 0) {
-		HIP_TRY(hipMemcpyAsync(A.col, d_colind, sizeof(int32_t) * (size_t)nnz, hipMemcpyDeviceToDevice, e->stream));
-		HIP_TRY(hipMemcpyAsync(A.val, d_values, e->esz * (size_t)nnz, hipMemcpyDeviceToDevice, e->stream));
-	}
-	HIP_TRY(hipStreamSynchronize(e->stream));
-	bool as_product = false;
-	lpp_status st = try_product_layout(e, A, &as_product);
+	begin_single_gpu(e);
+	lpp_status st = upload_csr(e, e->A_loc, nrows, nnz, d_rowptr, d_colind, d_values, hipMemcpyDeviceToDevice, e->row_block_hint, true);
 	if (st != LPP_OK) return st;
-	if (!as_product) st = finalize_csr(e, A, true);
-	if (st != LPP_OK) return st;
-	e->n_local = e->n_global = nrows;
-	e->row_start = 0;
-	e->active = false;
-	set_spmv_bytes(e);
-	return alloc_work(e);
+	return finish_setup(e, nrows, nrows, 0);
 }
 
 lpp_status lpp_engine_set_csr_partition(lpp_engine* e, const lpp_comm* comm, int64_t global_rows, const int64_t* shard_starts,
@@ -1293,17 +1269,12 @@ lpp_status lpp_engine_set_csr_partition(lpp_engine* e, const lpp_comm* comm, int
 	drop_product(e);
 	// the hint survives the partition when this rank's rows start on a block boundary (columns of A_loc are local)
 	const int64_t hint = (e->row_block_hint > 0 && shard_starts[r] % e->row_block_hint == 0) ? e->row_block_hint : 0;
-	st = upload_csr(e, e->A_loc, local, rpl.data(), cl.data(), vl.data(), hint);
+	st = upload_csr(e, e->A_loc, local, rpl[local], rpl.data(), cl.data(), vl.data(), hipMemcpyHostToDevice, hint);
 	if (st != LPP_OK) return st;
 	e->A_rem.src_elems = (int64_t)comm->nranks * comm->shard_stride;
-	st = upload_csr(e, e->A_rem, local, rpr.data(), cr.data(), vr.data());
+	st = upload_csr(e, e->A_rem, local, rpr[local], rpr.data(), cr.data(), vr.data(), hipMemcpyHostToDevice);
 	if (st != LPP_OK) return st;
-	e->n_local = local;
-	e->n_global = global_rows;
-	e->row_start = shard_starts[r];
-	e->active = false;
-	set_spmv_bytes(e);
-	return alloc_work(e);
+	return finish_setup(e, local, global_rows, shard_starts[r]);
 }
 
 lpp_status lpp_engine_get_csr(lpp_engine* e, int32_t which, int64_t* nrows, int64_t* nnz, int64_t* rowptr, int32_t* colind, void* values)

@@ -13,6 +13,7 @@
 #include "lpp_pb_kernels.h"
 #include "lpp_pbig_kernels.h"
 #include "lpp_tj.h"
+#include "lpp_txgeom.h"
 
 #define HIP_TRY(expr)                                                                                                  \
 	do {                                                                                                               \
@@ -357,6 +358,9 @@ int kron_launch(lpp_engine* e, const void* ywin, const void* ydown, void* x, dou
                 int64_t b0 = 0, int64_t cnt = -1); // blocks [b0, b0+cnt) of the slice (parts 0 and 1)
 void set_spmv_bytes(lpp_engine* e);
 lpp_status alloc_work(lpp_engine* e);
+// the opening step of a single-GPU matrix set-up and the closing step of every set-up (lpp_engine.hip)
+void begin_single_gpu(lpp_engine* e);
+lpp_status finish_setup(lpp_engine* e, int64_t n_local, int64_t n_global, int64_t row_start);
 int spmv_launch(lpp_engine* e, const DevCsr& A, const void* src, void* x, const void* ydot, double* partial, const EpiScale& sc = EpiScale { nullptr, nullptr, 0 });
 // product-basis layout (lpp_pb.hip)
 void free_pb(lpp_engine* e);

@@ -46,6 +46,26 @@ struct TjModel {
 	bool has_im = false, has_pv = false;
 	std::vector<double> hop_re, hop_im, jpm, jzz, w, pv;
 };
+// ... from the arguments of those two entry points, which each validate them first (L x L matrices; potentialV: 2 L entries when npot > 0)
+inline TjModel tj_model_from_args(int L, int nup, int ndown, const double* hop_re, const double* hop_im, const double* jpm, const double* jzz,
+                                  const double* w, const double* potentialV, int npot)
+{
+	TjModel M;
+	M.L = L;
+	M.nup = nup;
+	M.ndown = ndown;
+	M.npot = npot;
+	const size_t LL = (size_t)L * L;
+	M.hop_re.assign(hop_re, hop_re + LL);
+	if (hop_im) M.hop_im.assign(hop_im, hop_im + LL);
+	M.jpm.assign(jpm, jpm + LL);
+	M.jzz.assign(jzz, jzz + LL);
+	M.w.assign(w, w + LL);
+	M.has_pv = potentialV && npot > 0;
+	if (M.has_pv) M.pv.assign(potentialV, potentialV + 2 * (size_t)L);
+	for (double v : M.hop_im) M.has_im |= (v != 0);
+	return M;
+}
 
 // the plan: everything the kernel reads except the diagonal and the boundary's permutation (which come from the device assembler)
 struct TjPlan {

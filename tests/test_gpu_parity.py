@@ -8,6 +8,7 @@ from math import comb
 
 import numpy as np
 import pytest
+import torch  # noqa: F401  (ThreadComm's buffers: loaded before the engine library, so that both use one HIP runtime -- INTEGRATION.md)
 
 import oracle
 from helpers import chain, rel, square
@@ -114,6 +115,83 @@ def test_errors_are_loud():
             e.lanczos(1)  # no matrix
         with pytest.raises(LppError):
             e.set_csr(np.array([0, 1], np.int64), np.array([5], np.int32), np.array([1.0]))  # column out of range
+
+
+def test_model_setup_rejections_keep_their_status_and_text():
+    """What the model set-up entry points refuse, and with which words: the C entry points themselves (the ctypes library on e._h, so the
+    Python wrappers' own checks cannot answer first).  Single GPU: every refusal comes before any change of state -- the installed matrix
+    gives the same product, bit for bit, after each.  Two ranks: the checks of the partition and of the transposition-exchange geometry,
+    on rank 0 of a two-rank thread group with no second thread (every row returns before a collective); status and text only."""
+    import ctypes as C
+
+    from lanczosplusplus_amd import _capi
+    from lanczosplusplus_amd.comm import ThreadComm, ThreadGroup
+    lib = _capi.lib()
+    INVALID = _capi.LPP_ERR_INVALID
+    L, n = 8, 4
+    N = comb(L, n)  # 70 states per species
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    hop, zero = chain(L, -1.0), np.zeros((L, L))
+    him = np.zeros((L, L))
+    him[0, 1], him[1, 0] = 0.3, -0.3
+    jc = chain(L, 0.5)
+    U, V, pot = np.full(L, 4.0), np.zeros(L), np.zeros(2 * L)
+
+    def refused(status, text, at_start=False):
+        msg = lib.lpp_last_error().decode()
+        print(status, msg)
+        assert status == INVALID, (status, msg)
+        assert msg.startswith(text) if at_start else text in msg, msg
+
+    with LanczosEngine() as e:
+        h = e._h
+        e.assemble_hubbard(L, n, n, hop, U)
+        y = oracle.fill_random(N * N, 8)
+        want = e.matrixVectorProduct(np.zeros(N * N), y).tobytes()
+        rows = [
+            (lambda: lib.lpp_engine_assemble_hubbard_super(h, None, 32, n, n, vp(hop), None, vp(U), vp(V), None, None),
+             "lpp_engine_assemble_hubbard: bad argument"),
+            (lambda: lib.lpp_engine_assemble_hubbard_super(h, None, L, n, n, vp(hop), vp(him), vp(U), vp(V), None, None),
+             "complex couplings need a c128 engine"),
+            (lambda: lib.lpp_engine_setup_hubbard_onthefly_ext(h, None, L, n, n, vp(hop), vp(him), vp(U), vp(V), None),
+             "setup_hubbard_onthefly: complex hoppings need a c128 engine"),
+            (lambda: lib.lpp_engine_assemble_tj(h, L, 5, 4, vp(hop), None, vp(jc), vp(jc), vp(zero), None, 0),
+             "lpp_engine_assemble_tj: bad argument"),
+            (lambda: lib.lpp_engine_assemble_tj(h, L, 3, 3, vp(hop), None, vp(jc), vp(jc), vp(zero), vp(pot), L),
+             "potentialV needs 2*L entries"),
+            (lambda: lib.lpp_engine_assemble_heisenberg(h, L, L + 1, vp(jc), vp(jc), None, 0),
+             "lpp_engine_assemble_heisenberg: bad argument"),
+            (lambda: lib.lpp_engine_set_model_tj(h, L, 5, 4, vp(hop), None, vp(jc), vp(jc), vp(zero), None, 0),
+             "lpp_engine_set_model_tj: bad argument"),
+        ]
+        for call, text in rows:
+            refused(call(), text)
+            assert e.matrixVectorProduct(np.zeros(N * N), y).tobytes() == want, text
+
+    per = -(-N // 2)  # 35 down configurations per rank
+    chunk = lib.lpp_xchg_chunk(N, N, 2)
+    assert (per, chunk) == (35, 1680)
+    comm = ThreadComm(ThreadGroup(2, torch.device("cuda", 0)), 0, per * N, 200, False, xchg_chunk=chunk)
+
+    def with_(**changed):  # the communicator with some fields set differently
+        s = _capi.Comm()
+        for name, _ in _capi.Comm._fields_:
+            setattr(s, name, changed.get(name, getattr(comm.struct, name)))
+        return C.byref(s)
+
+    short = per * 16  # 16 up indices per rank: 32 < 70 in all
+    with comm.stream_context(), LanczosEngine(max_steps=200, stream=comm.stream_handle) as e:
+        h = e._h
+        refused(lib.lpp_engine_setup_hubbard_onthefly_super(h, with_(), L, n, n, vp(hop), None, vp(U), vp(V), None, vp(jc)), "runs on one GPU")
+        refused(lib.lpp_engine_assemble_hubbard_super(h, with_(shard_stride=per * N + 1), L, n, n, vp(hop), None, vp(U), vp(V), None, None),
+                "shard_stride must be ceil(N_down/nranks)*N_up")
+        refused(lib.lpp_engine_assemble_hubbard_super(h, with_(), L, n, n, vp(hop), None, vp(U), vp(V), None, vp(jc)), "need the all-gather exchange")
+        refused(lib.lpp_engine_assemble_hubbard_super(h, with_(xchg_chunk=short), L, n, n, vp(hop), None, vp(U), vp(V), None, None),
+                "assemble_hubbard: transposition exchange needs send2/recv2")
+        # the one-species matrix of this sector takes the packed layout, so of the two sentences this entry point has for the
+        # transposition exchange it is the geometry's that answers ("setup_hubbard_onthefly: transposition exchange needs ...")
+        refused(lib.lpp_engine_setup_hubbard_onthefly_ext(h, with_(xchg_chunk=short), L, n, n, vp(hop), None, vp(U), vp(V), None),
+                "setup_hubbard_onthefly:", at_start=True)
 
 
 @pytest.mark.parametrize("name", ["hubbard", "heisenberg", "tj_complex", "hubbard_complex"])
