@@ -436,6 +436,52 @@ lpp_status lpp_engine_spectral_decomposition(lpp_engine* e, int32_t state, lpp_e
  * This is this project's stated convention: PsimagLite's ContinuedFraction was not available to compare with.  out[2] = (re, im). */
 lpp_status lpp_continued_fraction(int32_t n, const double* a, const double* b, double eg, double weight, double sigma, double z_re, double z_im, double* out);
 
+/* ---- observables of the one-orbital t-J basis (entry points added under ABI 7, no struct changes; one GPU; csrc/lpp_obs.hip, csrc/lpp_obs_tj_kernels.h) ----
+ * The same three user-level results for Model=TjMultiOrb with Orbitals=1 (BasisTjMultiOrbLanczos: the sorted words (down << L) | up without double
+ * occupancy, index = rank(up compressed onto the sites the down electrons leave free) + rank(down) * C(L - ndown, nup)).  Operators c, cdagger, n, sz,
+ * splus, sminus (BasisTjMultiOrbLanczos.h:163-245, :296-315, :414-469).  Semantics, as the reference RUNS:
+ *   - doSignGf (:163-192) carries the parity of the up electrons for SPIN_DOWN at every site, site 0 included (no site-0 quirk as in the Hubbard basis);
+ *   - splus / sminus carry no sign (doSignSpSm is BasisBase's 1);
+ *   - a raw application of sz is n of the given spin (getBraSzOrN :456-469); two-point and spectral calls build sz as n_up/2 - n_down/2 (Engine.h:535-599);
+ *   - Engine.h:519 / :546 test the model name "Tj1Orb.h", which TjMultiOrb never has: a diagonal pair accumulates the modified state twice, as for Hubbard;
+ *   - splus / sminus with LPP_SPIN_DOWN -> LPP_ERR_INVALID from every call that applies them: hasNewPartsSplusOrMinus then names the sector
+ *     (nup -+ 1, ndown +- 1) while getBraIndex ignores the spin and makes states of (nup +- 1, ndown -+ 1) -- the reference ranks words that are not in
+ *     the basis.  lpp_obs_new_parts_tj itself restates hasNewParts and answers for both spins.
+ * Sector sizes are C(L, ndown) * C(L - ndown, nup); nup + ndown <= nsites <= 30; an operator that changes the up pattern needs at most 24 sites free of down
+ * electrons in the source sector (the pattern rank tables live in LDS) -> LPP_ERR_INVALID beyond.  Only a partitioned engine is refused (LPP_ERR_STATE):
+ * `e` and `sector` may be hole-major or general-layout t-J engines.  Every ABI-6 / ABI-7 entry point above and below keeps its behaviour, refusals included. */
+
+/* TjMultiOrb::hasNewParts (TjMultiOrb.h:140-159, :538-584), host only: as lpp_obs_new_parts, plus "nup + ndown > nsites -> no sector", the (0,0) refusal for
+ * splus / sminus too, and splus / sminus reading the spin.  LPP_OP_N and LPP_OP_SZ: the reference throws -> LPP_ERR_INVALID. */
+lpp_status lpp_obs_new_parts_tj(int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t* has, int32_t* nup_new, int32_t* ndown_new);
+
+/* The plan of one operator application, expanded (host only; exposed for the CPU test-suite): action[dst] = +-(src + 1), or 0 where the reference does not
+ * touch destination dst; *n_dst entries.  Expanded through the same tables and the same lookup function (obs_tj_source) the kernel uses.  action == NULL:
+ * sizes only.  *has = 0: hasNewParts refused, nothing else is written.  An empty species (nup = 0 or ndown = 0) is a valid sector. */
+lpp_status lpp_obs_plan_tj(int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t* has, int32_t* nup_new, int32_t* ndown_new,
+                           int64_t* n_dst, int64_t* action);
+
+/* lpp_engine_apply_operator / _host / lpp_engine_bench_operator in the t-J basis: arguments and contracts as those calls (basis-order vectors, 16-byte aligned
+ * destination, one launch on the engine's stream, no sync; the same byte model).  The engine needs no matrix. */
+lpp_status lpp_engine_apply_operator_tj(lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, double factor_re,
+                                        double factor_im, const void* d_src, void* d_dst, int32_t accumulate, int32_t* has);
+lpp_status lpp_engine_apply_operator_tj_host(lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, double factor_re,
+                                             double factor_im, const void* src, void* dst, int32_t accumulate, int32_t* has);
+lpp_status lpp_engine_bench_operator_tj(lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t warmup, int32_t iters,
+                                        double* ms_per_launch, double* model_bytes);
+
+/* lpp_engine_keep_states that also accepts a hole-major t-J engine: its resident states are then the host Ritz vectors bit for bit (both are permutations
+ * of the same device vector).  A second name only because lpp_engine_keep_states keeps the refusal its ABI-6 block documents; lpp_engine_state_device and
+ * lpp_engine_state_to_host serve any resident state.  A later lpp_engine_keep_states call puts the refusal back. */
+lpp_status lpp_engine_keep_states_tj(lpp_engine* e, int32_t k);
+
+/* lpp_engine_two_point / lpp_engine_spectral_decomposition in the t-J basis, arguments as those calls; one body serves both families.  A hole-major sector
+ * engine takes the modified state through its permutation on the device. */
+lpp_status lpp_engine_two_point_tj(lpp_engine* e, int32_t op, int32_t spin1, int32_t spin2, int32_t nsites, int32_t nup, int32_t ndown, int32_t bra_state,
+                                   int32_t ket_state, void* result, void* trace);
+lpp_status lpp_engine_spectral_decomposition_tj(lpp_engine* e, int32_t state, lpp_engine* sector, int32_t op, int32_t isite, int32_t jsite, int32_t spin, double isign,
+                                                int32_t nsites, int32_t nup, int32_t ndown, double* weight, int32_t* nsteps, double* a, double* b, lpp_stats* stats);
+
 /* ---- reduced density matrix of the lattice cut at a site (ABI 7; one GPU; csrc/lpp_rdm.hip) ----
  * The reference's `-r siteForSplit` (ReducedDensityMatrix.h, LanczosDriver1.h:201-206): part A = sites 0 .. split-1 = the low `split` bits of a species'
  * word, rdm(alpha, alpha') = sum over the environment of conj(psi(alpha, beta)) psi(alpha', beta) -- the conjugate on the ROW index, as the

@@ -135,6 +135,15 @@ SYMBOLS = {
     "lpp_engine_two_point": (C.c_int32, [_P] + [C.c_int32] * 8 + [_P, _P]),
     "lpp_engine_spectral_decomposition": (C.c_int32, [_P, C.c_int32, _P] + [C.c_int32] * 4 + [C.c_double] + [C.c_int32] * 3
                                           + [C.POINTER(C.c_double), C.POINTER(C.c_int32), _P, _P, C.POINTER(Stats)]),
+    "lpp_obs_new_parts_tj": (C.c_int32, [C.c_int32] * 5 + [C.POINTER(C.c_int32)] * 3),
+    "lpp_obs_plan_tj": (C.c_int32, [C.c_int32] * 6 + [C.POINTER(C.c_int32)] * 3 + [C.POINTER(C.c_int64), _P]),
+    "lpp_engine_apply_operator_tj": (C.c_int32, [_P] + [C.c_int32] * 6 + [C.c_double, C.c_double, _P, _P, C.c_int32, C.POINTER(C.c_int32)]),
+    "lpp_engine_apply_operator_tj_host": (C.c_int32, [_P] + [C.c_int32] * 6 + [C.c_double, C.c_double, _P, _P, C.c_int32, C.POINTER(C.c_int32)]),
+    "lpp_engine_bench_operator_tj": (C.c_int32, [_P] + [C.c_int32] * 8 + [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "lpp_engine_keep_states_tj": (C.c_int32, [_P, C.c_int32]),
+    "lpp_engine_two_point_tj": (C.c_int32, [_P] + [C.c_int32] * 8 + [_P, _P]),
+    "lpp_engine_spectral_decomposition_tj": (C.c_int32, [_P, C.c_int32, _P] + [C.c_int32] * 4 + [C.c_double] + [C.c_int32] * 3
+                                             + [C.POINTER(C.c_double), C.POINTER(C.c_int32), _P, _P, C.POINTER(Stats)]),
     "lpp_continued_fraction": (C.c_int32, [C.c_int32, _P, _P] + [C.c_double] * 5 + [_P]),
     "lpp_rdm_plan": (C.c_int32, [C.c_int32] * 5 + [C.POINTER(C.c_int32)] + [C.POINTER(C.c_int64)] * 4 + [_P, _P, _P, _P]),
     "lpp_engine_reduced_density_matrix": (C.c_int32, [_P] + [C.c_int32] * 5 + [_P, _P]),

@@ -338,6 +338,7 @@ struct lpp_engine {
 	// observables (lpp_obs.hip): the lowest keep_k Ritz vectors of the next lpp_engine_lanczos stay on the device in the basis order
 	// (unpitched, un-permuted), state k at resident + k * resident_stride doubles; obs: the per-species tables already uploaded
 	int keep_k = 0;
+	bool keep_tj = false; // keep_k came through lpp_engine_keep_states_tj: a hole-major t-J engine keeps its states too
 	double* resident = nullptr;
 	int resident_n = 0, resident_cap = 0; // states valid now (0 until a solve has written them); states the buffer has room for
 	int64_t resident_stride = 0, resident_len = 0; // doubles between states (even), elements per state
@@ -466,6 +467,9 @@ lpp_status tj_build(lpp_engine* e, const TjModel& M, const AsmParams& P, bool* d
 int tj_launch(lpp_engine* e, const void* src, void* x, const void* ydot, double* partial, const EpiScale& sc);
 lpp_status tj_vec_from_host(lpp_engine* e, double* dev, const void* host);
 lpp_status tj_vec_to_host(lpp_engine* e, void* host, const double* dev);
+// the device-side halves: `basis` is a device vector of n_local elements in the basis order (one gather / scatter through S.perm)
+lpp_status tj_vec_from_device(lpp_engine* e, double* dev, const void* basis);
+lpp_status tj_vec_to_device(lpp_engine* e, void* basis, const double* dev);
 void tj_fill_random(lpp_engine* e, double* dev, uint64_t seed);
 lpp_status assemble_tj_raw(lpp_engine* e, const TjModel& M, DevCsr& A); // the plain CSR in the reference's order (lpp_assemble.hip)
 // A CSR handed over together with a description of its model (lpp_engine_set_model_*; lpp_assemble.hip): the device assembler regenerates the
@@ -479,6 +483,9 @@ void vec_fill_random(lpp_engine* e, double* dev, uint64_t seed);
 // the device-side halves of the two: `basis` is a device vector of n_local elements in the basis order
 lpp_status vec_from_device(lpp_engine* e, double* dev, const void* basis);
 lpp_status vec_to_device(lpp_engine* e, void* basis, const double* dev);
+// lpp_engine_decomposition_device for internal callers: a hole-major t-J engine is served as well (lpp_lanczos.hip; the public entry point
+// keeps its refusal)
+lpp_status decomposition_device_any(lpp_engine* e, const void* d_init, int32_t* nsteps, double* a, double* b, lpp_stats* stats);
 void free_obs(lpp_engine* e); // resident states and operator tables (lpp_obs.hip)
 void free_rdm(lpp_engine* e); // reduced-density-matrix plan and workspace (lpp_rdm.hip)
 } // namespace lpp

@@ -445,14 +445,15 @@ lpp_status ensure_krylov(lpp_engine* e, int ncols, bool required, bool* got)
 	return LPP_OK;
 }
 
-// dev_init: `init` is a device vector in the basis order on the engine's GPU (the *_device entry points)
-lpp_status begin_run(lpp_engine* e, const void* init, bool want_save, bool dev_init = false)
+// dev_init: `init` is a device vector in the basis order on the engine's GPU (the *_device entry points); tj_ok: the caller is not one of
+// the public ABI-6 entry points, whose documented refusal of a hole-major t-J engine stays
+lpp_status begin_run(lpp_engine* e, const void* init, bool want_save, bool dev_init = false, bool tj_ok = false)
 {
 	if (!e->has_matrix()) return fail(LPP_ERR_STATE, "no matrix: call lpp_engine_set_csr / lpp_engine_assemble_* first");
 	if (dev_init) {
 		if (!init) return fail(LPP_ERR_INVALID, "device start vector: null pointer");
 		if (multi(e)) return fail(LPP_ERR_STATE, "device start vector: not on a partitioned (multi-rank) engine");
-		if (e->tj.active) return fail(LPP_ERR_STATE, "device start vector: not on a hole-major t-J engine");
+		if (e->tj.active && !tj_ok) return fail(LPP_ERR_STATE, "device start vector: not on a hole-major t-J engine");
 	}
 	HIP_TRY(hipSetDevice(e->cfg.device));
 	if (e->n_global <= 0) return fail(LPP_ERR_INVALID, "empty matrix");
@@ -658,7 +659,7 @@ static lpp_status lanczos_impl(lpp_engine* e, const void* init, bool dev_init, i
 	const auto t0 = std::chrono::steady_clock::now();
 	// lpp_engine_keep_states: the lowest nkeep Ritz vectors are formed even without a host buffer and stay on the device
 	const int nkeep = std::min<int>(e->keep_k, nstates);
-	if (nkeep > 0 && (multi(e) || e->tj.active)) return fail(LPP_ERR_STATE, "lpp_engine_keep_states: not on a partitioned or hole-major t-J engine");
+	if (nkeep > 0 && (multi(e) || (e->tj.active && !e->keep_tj))) return fail(LPP_ERR_STATE, "lpp_engine_keep_states: not on a partitioned or hole-major t-J engine");
 	const bool want_vectors = ritz_vectors != nullptr || nkeep > 0;
 	lpp_status st = begin_run(e, init, want_vectors, dev_init);
 	if (st != LPP_OK) return st;
@@ -770,11 +771,11 @@ lpp_status lpp_engine_lanczos_device(lpp_engine* e, const void* d_init, int32_t 
 	return lanczos_impl(e, d_init, true, nstates, eigs, ritz_vectors, stats);
 }
 
-static lpp_status decomposition_impl(lpp_engine* e, const void* init, bool dev_init, int32_t* nsteps, double* a, double* b, lpp_stats* stats)
+static lpp_status decomposition_impl(lpp_engine* e, const void* init, bool dev_init, int32_t* nsteps, double* a, double* b, lpp_stats* stats, bool tj_ok = false)
 {
 	if (!e || !nsteps || !a || !b) return fail(LPP_ERR_INVALID, "lpp_engine_decomposition: bad argument");
 	const auto t0 = std::chrono::steady_clock::now();
-	lpp_status st = begin_run(e, init, false, dev_init);
+	lpp_status st = begin_run(e, init, false, dev_init, tj_ok);
 	if (st != LPP_OK) return st;
 	SolveResult res;
 	st = run_recurrence(e, res);
@@ -801,3 +802,11 @@ lpp_status lpp_engine_decomposition_device(lpp_engine* e, const void* d_init, in
 }
 
 } // extern "C"
+
+namespace lpp {
+lpp_status decomposition_device_any(lpp_engine* e, const void* d_init, int32_t* nsteps, double* a, double* b, lpp_stats* stats)
+{
+	if (!d_init) return fail(LPP_ERR_INVALID, "lpp_engine_decomposition_device: null start vector");
+	return decomposition_impl(e, d_init, true, nsteps, a, b, stats, true);
+}
+} // namespace lpp

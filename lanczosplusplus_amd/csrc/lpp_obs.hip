@@ -1,4 +1,4 @@
-// lpp_obs.hip -- ground-state observables of the Hubbard product basis on one GPU: one-site operators applied to device vectors
+// lpp_obs.hip -- ground-state observables of the Hubbard product basis and of the one-orbital t-J basis (one body per entry point, ObsBasis) on one GPU: one-site operators applied to device vectors
 // (Engine::accModifiedState_, reference src/Engine/Engine.h:416-458), the two-point matrix (Engine::twoPoint :266-338) and the modified
 // state + decomposition of one spectral-function type (Engine::spectralFunction :134-206, getModifiedState :494-533, calcSpectral :460-490).
 //
@@ -17,6 +17,7 @@
 
 #include "lpp_engine_impl.h"
 #include "lpp_obs_kernels.h"
+#include "lpp_obs_tj_kernels.h"
 
 using namespace lpp;
 
@@ -171,33 +172,209 @@ lpp_status obs_plan(int op, int site, int spin, int L, int nup, int ndn, bool* h
 	return LPP_OK;
 }
 
+
+// ---- the one-orbital t-J basis (BasisTjMultiOrbLanczos; kernel and lookup: lpp_obs_tj_kernels.h) ---------------------------------------
+
+// TjMultiOrb::hasNewParts (TjMultiOrb.h:140-159, :538-584) for c / cdagger / splus / sminus: the Hubbard rules, the spin read by splus / sminus as well,
+// no (0,0) sector for either pair, and no sector with more electrons than sites
+bool new_parts_tj(int op, int spin, int L, int nup, int ndn, int* n1, int* n2)
+{
+	int p1 = nup, p2 = ndn;
+	if (op == LPP_OP_C || op == LPP_OP_CDAGGER) {
+		const int c = (op == LPP_OP_CDAGGER) ? 1 : -1;
+		if (spin == LPP_SPIN_UP) p1 += c;
+		else p2 += c;
+	} else {
+		const int c = (op == LPP_OP_SPLUS) ? 1 : -1;
+		if (spin == LPP_SPIN_UP) {
+			p1 += c;
+			p2 -= c;
+		} else {
+			p2 += c;
+			p1 -= c;
+		}
+	}
+	if (p1 < 0 || p2 < 0) return false;
+	if (p1 > L || p2 > L) return false;
+	if (p1 == 0 && p2 == 0) return false;
+	if (p1 + p2 > L) return false; // no double occupancy
+	*n1 = p1;
+	*n2 = p2;
+	return true;
+}
+
+int64_t tj_sector_size(int L, int nup, int ndn) { return (L < 1 || L > 30 || nup < 0 || ndn < 0 || nup + ndn > L) ? -1 : binom(L, ndn) * binom(L - ndn, nup); }
+int64_t hubbard_sector_size(int L, int nup, int ndn) { return (L < 1 || L > 30 || nup < 0 || ndn < 0 || nup > L || ndn > L) ? -1 : binom(L, nup) * binom(L, ndn); }
+
+struct ObsTjPlan {
+	int nup2 = 0, ndn2 = 0, up = TJ_UP_SAME, lb = 0;
+	int64_t n_up_src = 0, n_dn_src = 0, n_up_dst = 0, n_dn_dst = 0;
+	std::vector<ObsTjDown> dn;
+	std::vector<uint32_t> pat;
+	std::vector<int32_t> hi_base;
+	std::vector<uint16_t> lo_rank;
+};
+
+// what the operator asks of the destination's down word d' and what the source's down word is
+enum { DN_KEEP_OUT, DN_KEEP_IN, DN_ADD, DN_REMOVE }; // site not in d', source d' | site in d', source d' | not in d', source d' + site | in d', source d' - site
+
+lpp_status obs_plan_tj(int op, int site, int spin, int L, int nup, int ndn, bool* has, ObsTjPlan& P)
+{
+	*has = false;
+	if (!valid_op(op)) return fail(LPP_ERR_INVALID, "t-J observables: unknown operator (LPP_OP_*)");
+	if (spin != LPP_SPIN_UP && spin != LPP_SPIN_DOWN) return fail(LPP_ERR_INVALID, "t-J observables: spin must be LPP_SPIN_UP or LPP_SPIN_DOWN");
+	if (site < 0 || site >= L || tj_sector_size(L, nup, ndn) < 0) return fail(LPP_ERR_INVALID, "t-J observables: bad sites / site / sector (nup + ndown <= sites <= 30)");
+	if ((op == LPP_OP_SPLUS || op == LPP_OP_SMINUS) && spin != LPP_SPIN_UP)
+		return fail(LPP_ERR_INVALID, "t-J observables: splus / sminus with spin DOWN: the reference's hasNewParts names the sector (nup -+ 1, ndown +- 1) while its getBraIndex "
+		                             "ignores the spin and makes states of (nup +- 1, ndown -+ 1), so it ranks words that are not in the basis; pass LPP_SPIN_UP");
+	P = ObsTjPlan();
+	P.nup2 = nup;
+	P.ndn2 = ndn;
+	if (needs_new_basis(op) && !new_parts_tj(op, spin, L, nup, ndn, &P.nup2, &P.ndn2)) return LPP_OK;
+	const int Ws = L - ndn, Wd = L - P.ndn2; // pattern widths: the sites free of down electrons
+	P.n_up_src = binom(Ws, nup);
+	P.n_dn_src = binom(L, ndn);
+	P.n_up_dst = binom(Wd, P.nup2);
+	P.n_dn_dst = binom(L, P.ndn2);
+	if (P.n_up_src >= (int64_t)INT32_MAX - 4096 || P.n_dn_src >= (int64_t)INT32_MAX - 4096 || P.n_up_dst >= (int64_t)INT32_MAX - 4096 || P.n_dn_dst >= (int64_t)INT32_MAX - 4096)
+		return fail(LPP_ERR_INVALID, "t-J observables: a species with 2^31 states or more");
+	int dkind = DN_KEEP_OUT;
+	bool down_sign = false;
+	switch (op) {
+	case LPP_OP_C:
+	case LPP_OP_CDAGGER:
+		if (spin == LPP_SPIN_UP) {
+			P.up = (op == LPP_OP_C) ? TJ_UP_SET : TJ_UP_CLEAR;
+		} else {
+			P.up = (op == LPP_OP_C) ? TJ_UP_DEL0 : TJ_UP_INS0;
+			dkind = (op == LPP_OP_C) ? DN_ADD : DN_REMOVE;
+			down_sign = true;
+		}
+		break;
+	case LPP_OP_N:
+	case LPP_OP_SZ: // getBraSzOrN (:456-469): the occupancy of `spin` for both
+		P.up = (spin == LPP_SPIN_UP) ? TJ_UP_TEST : TJ_UP_SAME;
+		dkind = (spin == LPP_SPIN_UP) ? DN_KEEP_OUT : DN_KEEP_IN;
+		break;
+	case LPP_OP_SPLUS:
+		P.up = TJ_UP_DEL1;
+		dkind = DN_ADD;
+		break;
+	case LPP_OP_SMINUS:
+		P.up = TJ_UP_INS1;
+		dkind = DN_REMOVE;
+		break;
+	}
+	if (P.up != TJ_UP_SAME) {
+		if (Ws > 2 * kObsTjMaxHalf) return fail(LPP_ERR_INVALID, "t-J observables: more than 24 sites free of down electrons (the pattern rank tables are kept in LDS)");
+		// rank(s) among the Ws-bit words of nup set bits, ascending = by the high half, then by the low half
+		P.lb = Ws / 2;
+		const int hb = Ws - P.lb;
+		std::vector<int> seen((size_t)P.lb + 1, 0);
+		P.lo_rank.resize((size_t)1 << P.lb);
+		for (uint32_t lo = 0; lo < (1u << P.lb); lo++) P.lo_rank[lo] = (uint16_t)seen[(size_t)__builtin_popcount(lo)]++;
+		P.hi_base.resize((size_t)1 << hb);
+		int64_t acc = 0;
+		for (uint32_t hi = 0; hi < (1u << hb); hi++) {
+			P.hi_base[hi] = (int32_t)acc;
+			acc += binom(P.lb, nup - __builtin_popcount(hi));
+		}
+		// the destination's patterns, ascending
+		P.pat.reserve((size_t)P.n_up_dst);
+		uint32_t w = (P.nup2 == 0) ? 0 : ((1u << P.nup2) - 1);
+		for (int64_t i = 0; i < P.n_up_dst; i++) {
+			P.pat.push_back(w);
+			if (P.nup2 > 0 && i + 1 < P.n_up_dst) {
+				const uint32_t c = w & (~w + 1), r = w + c;
+				w = (((r ^ w) >> 2) / c) | r;
+			}
+		}
+	}
+	const Ranker R(L);
+	P.dn.assign((size_t)P.n_dn_dst, ObsTjDown { 0, 0 });
+	const uint64_t bit = 1ull << site;
+	uint64_t d = (P.ndn2 == 0) ? 0 : ((1ull << P.ndn2) - 1);
+	for (int64_t i = 0; i < P.n_dn_dst; i++) {
+		const bool in = (d & bit) != 0;
+		const bool ok = (dkind == DN_KEEP_IN || dkind == DN_REMOVE) ? in : !in;
+		ObsTjDown& e = P.dn[(size_t)i];
+		e.p = __builtin_popcountll(~d & (bit - 1));
+		if (ok) {
+			const uint64_t sd = (dkind == DN_ADD || dkind == DN_REMOVE) ? (d ^ bit) : d;
+			int s = 1; // doSignGf, SPIN_DOWN (:180-191): the parity of the up electrons at EVERY site, times the parity of the down bits below the site
+			if (down_sign && ((nup + __builtin_popcountll(d & (bit - 1))) & 1)) s = -1;
+			e.src = (int32_t)(s * (R.rank(sd) + 1));
+		}
+		if (P.ndn2 > 0 && i + 1 < P.n_dn_dst) {
+			const uint64_t c = d & (~d + 1), r = d + c;
+			d = (((r ^ d) >> 2) / c) | r;
+		}
+	}
+	*has = true;
+	return LPP_OK;
+}
+
+// the plan expanded as the kernel walks it: action[dst] = +-(src + 1) or 0 (action may be null); *touched = destinations with a source
+void tj_expand(const ObsTjPlan& P, int64_t* action, int64_t* touched)
+{
+	int64_t cnt = 0;
+	for (int64_t dd = 0; dd < P.n_dn_dst; dd++)
+		for (int64_t du = 0; du < P.n_up_dst; du++) {
+			const int64_t k = obs_tj_source(P.up, P.dn[(size_t)dd], (uint32_t)du, P.pat.data(), P.hi_base.data(), P.lo_rank.data(), P.lb, P.n_up_src);
+			if (action) action[du + dd * P.n_up_dst] = k;
+			cnt += (k != 0);
+		}
+	if (touched) *touched = cnt;
+}
+
 // ---- device side ---------------------------------------------------------------------------------------------------------------------
 
 struct DevPlan {
 	ObsPlan host; // tables dropped after the upload
 	bool has = false;
 	int32_t *tu = nullptr, *td = nullptr;
+	// the t-J basis: the plan (tables dropped after the upload likewise) and its four device tables
+	ObsTjPlan tj;
+	ObsTjDown* tj_dn = nullptr;
+	uint32_t* tj_pat = nullptr;
+	int32_t* tj_hi = nullptr;
+	uint16_t* tj_lo = nullptr;
+	int tj_nhi = 0, tj_nlo = 0;
 };
 
-typedef std::tuple<int, int, int, int, int, int> PlanKey;
+enum { BASIS_HUBBARD = 0, BASIS_TJ = 1 };
+typedef std::tuple<int, int, int, int, int, int, int> PlanKey; // basis, operator, site, spin, sites, nup, ndown
 struct ObsCache {
 	std::map<PlanKey, DevPlan> plans;
 };
 
 inline bool multi(const lpp_engine* e) { return e->has_comm && e->comm.nranks > 1; }
 
-lpp_status refuse(const lpp_engine* e, const char* who)
+lpp_status refuse(const lpp_engine* e, const char* who, bool hole_major_ok = false)
 {
 	if (multi(e)) return fail(LPP_ERR_STATE, std::string(who) + ": not on a partitioned (multi-rank) engine");
-	if (e->tj.active) return fail(LPP_ERR_STATE, std::string(who) + ": not on a hole-major t-J engine");
+	if (e->tj.active && !hole_major_ok) return fail(LPP_ERR_STATE, std::string(who) + ": not on a hole-major t-J engine");
 	return LPP_OK;
 }
 
 void free_plan(DevPlan& D)
 {
-	if (D.tu) (void)hipFree(D.tu);
-	if (D.td) (void)hipFree(D.td);
+	for (void* p : { (void*)D.tu, (void*)D.td, (void*)D.tj_dn, (void*)D.tj_pat, (void*)D.tj_hi, (void*)D.tj_lo })
+		if (p) (void)hipFree(p);
 	D.tu = D.td = nullptr;
+	D.tj_dn = nullptr;
+	D.tj_pat = nullptr;
+	D.tj_hi = nullptr;
+	D.tj_lo = nullptr;
+}
+
+// one table to the device (at least one element is allocated); the host copy is dropped
+template <typename V> hipError_t upload(V** dst, std::vector<V>& src)
+{
+	hipError_t err = hipMalloc((void**)dst, sizeof(V) * std::max<size_t>(src.size(), 1));
+	if (err == hipSuccess && !src.empty()) err = hipMemcpy(*dst, src.data(), sizeof(V) * src.size(), hipMemcpyHostToDevice);
+	if (err == hipSuccess) std::vector<V>().swap(src);
+	return err;
 }
 
 // The tables of one (operator, site, spin, sites, sector), uploaded once and kept with the engine.  The key is what the caller passes -- the engine
@@ -205,35 +382,38 @@ void free_plan(DevPlan& D)
 // per operator; past kMaxPlans entries everything is dropped and rebuilt on demand.  The returned pointer is valid until the next get_plan.
 constexpr size_t kMaxPlans = 256;
 
-lpp_status get_plan(lpp_engine* e, int op, int site, int spin, int L, int nup, int ndn, const DevPlan** out)
+lpp_status get_plan(lpp_engine* e, int basis, int op, int site, int spin, int L, int nup, int ndn, const DevPlan** out)
 {
 	if (!e->obs) e->obs = new ObsCache();
 	ObsCache* C = (ObsCache*)e->obs;
-	const PlanKey key(op, site, spin, L, nup, ndn);
+	const PlanKey key(basis, op, site, spin, L, nup, ndn);
 	auto it = C->plans.find(key);
 	if (it == C->plans.end()) {
 		DevPlan D;
 		bool has = false;
-		lpp_status st = obs_plan(op, site, spin, L, nup, ndn, &has, D.host);
+		lpp_status st = (basis == BASIS_TJ) ? obs_plan_tj(op, site, spin, L, nup, ndn, &has, D.tj) : obs_plan(op, site, spin, L, nup, ndn, &has, D.host);
 		if (st != LPP_OK) return st;
 		D.has = has;
 		if (has) {
-			for (int s = 0; s < 2; s++) {
-				std::vector<int32_t>& t = s ? D.host.td : D.host.tu;
-				if (t.empty()) continue;
-				int32_t* d = nullptr;
-				hipError_t err = hipMalloc(&d, sizeof(int32_t) * t.size());
-				(s ? D.td : D.tu) = d;
-				if (err == hipSuccess) err = hipMemcpy(d, t.data(), sizeof(int32_t) * t.size(), hipMemcpyHostToDevice);
-				if (err != hipSuccess) {
-					free_plan(D); // the other species' table too
-					if (err == hipErrorOutOfMemory) {
-						(void)hipGetLastError();
-						return fail(LPP_ERR_NOMEM, "observables: no device memory for the operator tables");
-					}
-					HIP_TRY(err);
+			hipError_t err = hipSuccess;
+			if (basis == BASIS_TJ) {
+				D.tj_nhi = (int)D.tj.hi_base.size();
+				D.tj_nlo = (int)D.tj.lo_rank.size();
+				err = upload(&D.tj_dn, D.tj.dn);
+				if (err == hipSuccess) err = upload(&D.tj_pat, D.tj.pat);
+				if (err == hipSuccess) err = upload(&D.tj_hi, D.tj.hi_base);
+				if (err == hipSuccess) err = upload(&D.tj_lo, D.tj.lo_rank);
+			} else { // an empty table stays null: the species is untouched
+				if (!D.host.tu.empty()) err = upload(&D.tu, D.host.tu);
+				if (err == hipSuccess && !D.host.td.empty()) err = upload(&D.td, D.host.td);
+			}
+			if (err != hipSuccess) {
+				free_plan(D); // the tables uploaded so far
+				if (err == hipErrorOutOfMemory) {
+					(void)hipGetLastError();
+					return fail(LPP_ERR_NOMEM, "observables: no device memory for the operator tables");
 				}
-				std::vector<int32_t>().swap(t);
+				HIP_TRY(err);
 			}
 		}
 		if (C->plans.size() >= kMaxPlans) {
@@ -253,22 +433,28 @@ int obs_grid(const lpp_engine* e, int64_t units)
 	return (int)std::max<int64_t>(1, std::min<int64_t>(tiles, (int64_t)e->num_cus * 32));
 }
 
-// z (+)= factor * A src on device vectors in the basis order; *has == false: no such sector, nothing was launched
-lpp_status apply_dev(lpp_engine* e, int op, int site, int spin, int L, int nup, int ndn, double fr, double fi, const void* d_src, void* d_dst, bool acc, bool* has,
-                     int64_t* n_dst)
+lpp_status check_vectors(const lpp_engine* e, double fi, const void* d_src, const void* d_dst)
 {
-	const DevPlan* D = nullptr;
-	lpp_status st = get_plan(e, op, site, spin, L, nup, ndn, &D);
-	if (st != LPP_OK) return st;
-	*has = D->has;
-	if (!D->has) return LPP_OK;
-	const ObsPlan& P = D->host;
-	if (n_dst) *n_dst = P.n_up_dst * P.n_dn_dst;
 	if (!d_src || !d_dst) return fail(LPP_ERR_INVALID, "observables: null vector");
 	// the destination is written in 16-byte units; a c128 source element is read as one double2, an f64 source element as one double
 	if (((uintptr_t)d_dst & 15) != 0) return fail(LPP_ERR_INVALID, "observables: the destination must be 16-byte aligned");
 	if (((uintptr_t)d_src & (e->is_complex ? 15 : 7)) != 0) return fail(LPP_ERR_INVALID, "observables: the source must be aligned to its element size (8 bytes f64, 16 bytes c128)");
 	if (!e->is_complex && fi != 0.0) return fail(LPP_ERR_INVALID, "observables: complex factor on a real engine");
+	return LPP_OK;
+}
+
+// z (+)= factor * A src on device vectors in the basis order; *has == false: no such sector, nothing was launched
+lpp_status apply_dev(lpp_engine* e, int op, int site, int spin, int L, int nup, int ndn, double fr, double fi, const void* d_src, void* d_dst, bool acc, bool* has,
+                     int64_t* n_dst)
+{
+	const DevPlan* D = nullptr;
+	lpp_status st = get_plan(e, BASIS_HUBBARD, op, site, spin, L, nup, ndn, &D);
+	if (st != LPP_OK) return st;
+	*has = D->has;
+	if (!D->has) return LPP_OK;
+	const ObsPlan& P = D->host;
+	if (n_dst) *n_dst = P.n_up_dst * P.n_dn_dst;
+	if ((st = check_vectors(e, fi, d_src, d_dst)) != LPP_OK) return st;
 	const int64_t nd = P.n_up_dst * P.n_dn_dst;
 	if (nd == 0) return LPP_OK;
 	ObsArgs A { D->tu, D->td, P.n_up_dst, P.n_dn_dst, P.n_up_src, P.sz ? 1 : 0, fr, fi };
@@ -285,15 +471,88 @@ lpp_status apply_dev(lpp_engine* e, int op, int site, int spin, int L, int nup, 
 	return LPP_OK;
 }
 
+// the same in the t-J basis (k_obs_apply_tj)
+lpp_status apply_dev_tj(lpp_engine* e, int op, int site, int spin, int L, int nup, int ndn, double fr, double fi, const void* d_src, void* d_dst, bool acc, bool* has,
+                        int64_t* n_dst)
+{
+	const DevPlan* D = nullptr;
+	lpp_status st = get_plan(e, BASIS_TJ, op, site, spin, L, nup, ndn, &D);
+	if (st != LPP_OK) return st;
+	*has = D->has;
+	if (!D->has) return LPP_OK;
+	const ObsTjPlan& P = D->tj;
+	const int64_t nd = P.n_up_dst * P.n_dn_dst;
+	if (n_dst) *n_dst = nd;
+	if ((st = check_vectors(e, fi, d_src, d_dst)) != LPP_OK) return st;
+	if (nd == 0) return LPP_OK;
+	ObsTjArgs A { D->tj_dn, D->tj_pat, D->tj_hi, D->tj_lo, P.up, P.lb, D->tj_nhi, D->tj_nlo, P.n_up_dst, P.n_dn_dst, P.n_up_src, fr, fi };
+	const int64_t units = e->is_complex ? nd : (nd + 1) / 2;
+	const int g = obs_grid(e, units);
+	const size_t lds = obs_tj_lds_bytes(A.nhi, A.nlo);
+	if (e->is_complex) {
+		if (acc) k_obs_apply_tj<true, true><<<g, kObsBlock, lds, e->stream>>>((double*)d_dst, (const double*)d_src, A);
+		else k_obs_apply_tj<true, false><<<g, kObsBlock, lds, e->stream>>>((double*)d_dst, (const double*)d_src, A);
+	} else {
+		if (acc) k_obs_apply_tj<false, true><<<g, kObsBlock, lds, e->stream>>>((double*)d_dst, (const double*)d_src, A);
+		else k_obs_apply_tj<false, false><<<g, kObsBlock, lds, e->stream>>>((double*)d_dst, (const double*)d_src, A);
+	}
+	HIP_TRY(hipGetLastError());
+	return LPP_OK;
+}
+
+// Everything the entry points below need to know about a basis: they are written once and run for both families.
+struct ObsBasis {
+	int id;
+	bool hole_major_ok; // a hole-major t-J engine is admitted (its resident states and start vectors pass through S.perm)
+	int64_t (*sector_size)(int L, int nup, int ndn); // < 0: not a sector
+	bool (*new_parts)(int op, int spin, int L, int nup, int ndn, int* n1, int* n2);
+	lpp_status (*apply)(lpp_engine* e, int op, int site, int spin, int L, int nup, int ndn, double fr, double fi, const void* d_src, void* d_dst, bool acc, bool* has,
+	                    int64_t* n_dst);
+};
+const ObsBasis kHubbard { BASIS_HUBBARD, false, hubbard_sector_size, new_parts, apply_dev };
+const ObsBasis kTj { BASIS_TJ, true, tj_sector_size, new_parts_tj, apply_dev_tj };
+
+// sizes of the plan's two sectors, and (touched != null) the destinations that have a source
+lpp_status plan_sizes(lpp_engine* e, const ObsBasis& B, int op, int site, int spin, int L, int nup, int ndn, bool* has, int64_t* ns, int64_t* nd, int64_t* touched)
+{
+	const DevPlan* D = nullptr;
+	lpp_status st = get_plan(e, B.id, op, site, spin, L, nup, ndn, &D);
+	if (st != LPP_OK) return st;
+	*has = D->has;
+	if (!D->has) return LPP_OK;
+	if (B.id == BASIS_TJ) {
+		*ns = D->tj.n_up_src * D->tj.n_dn_src;
+		*nd = D->tj.n_up_dst * D->tj.n_dn_dst;
+	} else {
+		*ns = D->host.n_up_src * D->host.n_dn_src;
+		*nd = D->host.n_up_dst * D->host.n_dn_dst;
+	}
+	if (!touched) return LPP_OK;
+	bool hh = false;
+	if (B.id == BASIS_TJ) {
+		ObsTjPlan P;
+		if ((st = obs_plan_tj(op, site, spin, L, nup, ndn, &hh, P)) != LPP_OK) return st;
+		tj_expand(P, nullptr, touched);
+	} else {
+		ObsPlan P;
+		if ((st = obs_plan(op, site, spin, L, nup, ndn, &hh, P)) != LPP_OK) return st;
+		int64_t cu = P.n_up_dst, cd = P.n_dn_dst;
+		if (!P.tu.empty()) cu = (int64_t)std::count_if(P.tu.begin(), P.tu.end(), [](int32_t v) { return v != 0; });
+		if (!P.td.empty()) cd = (int64_t)std::count_if(P.td.begin(), P.td.end(), [](int32_t v) { return v != 0; });
+		*touched = cu * cd;
+	}
+	return LPP_OK;
+}
+
 // the operator Engine::accModifiedState applies (Engine.h:535-599): n directly, sz as n_up/2 - n_down/2, the others as given
-lpp_status acc_modified_dev(lpp_engine* e, int op, int site, int spin, int L, int nup, int ndn, double isign, const void* d_src, void* d_dst, bool acc, bool* has)
+lpp_status acc_modified_dev(lpp_engine* e, const ObsBasis& B, int op, int site, int spin, int L, int nup, int ndn, double isign, const void* d_src, void* d_dst, bool acc, bool* has)
 {
 	if (op == LPP_OP_SZ) {
-		lpp_status st = apply_dev(e, LPP_OP_N, site, LPP_SPIN_UP, L, nup, ndn, isign * 0.5, 0.0, d_src, d_dst, acc, has, nullptr);
+		lpp_status st = B.apply(e, LPP_OP_N, site, LPP_SPIN_UP, L, nup, ndn, isign * 0.5, 0.0, d_src, d_dst, acc, has, nullptr);
 		if (st != LPP_OK) return st;
-		return apply_dev(e, LPP_OP_N, site, LPP_SPIN_DOWN, L, nup, ndn, -isign * 0.5, 0.0, d_src, d_dst, true, has, nullptr);
+		return B.apply(e, LPP_OP_N, site, LPP_SPIN_DOWN, L, nup, ndn, -isign * 0.5, 0.0, d_src, d_dst, true, has, nullptr);
 	}
-	return apply_dev(e, op, site, spin, L, nup, ndn, isign, 0.0, d_src, d_dst, acc, has, nullptr);
+	return B.apply(e, op, site, spin, L, nup, ndn, isign, 0.0, d_src, d_dst, acc, has, nullptr);
 }
 
 int blas_blocks(int64_t n2)
@@ -307,6 +566,224 @@ lpp_status state_ptr(lpp_engine* e, int k, const char* who, double** p)
 	if (k < 0 || k >= e->resident_n || !e->resident) return fail(LPP_ERR_STATE, std::string(who) + ": no such resident state (lpp_engine_keep_states before lpp_engine_lanczos)");
 	*p = e->resident + (int64_t)k * e->resident_stride;
 	return LPP_OK;
+}
+
+lpp_status apply_operator_body(const ObsBasis& B, const char* who, lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown,
+                               double factor_re, double factor_im, const void* d_src, void* d_dst, int32_t accumulate, int32_t* has)
+{
+	if (!e || !has) return fail(LPP_ERR_INVALID, std::string(who) + ": null argument");
+	lpp_status st = refuse(e, who, B.hole_major_ok);
+	if (st != LPP_OK) return st;
+	HIP_TRY(hipSetDevice(e->cfg.device));
+	bool h = false;
+	st = B.apply(e, op, site, spin, nsites, nup, ndown, factor_re, factor_im, d_src, d_dst, accumulate != 0, &h, nullptr);
+	*has = h ? 1 : 0;
+	return st;
+}
+
+lpp_status apply_operator_host_body(const ObsBasis& B, const char* who, lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown,
+                                    double factor_re, double factor_im, const void* src, void* dst, int32_t accumulate, int32_t* has)
+{
+	if (!e || !has || !src || !dst) return fail(LPP_ERR_INVALID, std::string(who) + ": null argument");
+	lpp_status st = refuse(e, who, B.hole_major_ok);
+	if (st != LPP_OK) return st;
+	HIP_TRY(hipSetDevice(e->cfg.device));
+	bool planned = false;
+	int64_t es = 0, ed = 0;
+	st = plan_sizes(e, B, op, site, spin, nsites, nup, ndown, &planned, &es, &ed, nullptr);
+	if (st != LPP_OK) return st;
+	*has = planned ? 1 : 0;
+	if (!planned) return LPP_OK;
+	const size_t ns = e->esz * (size_t)es, nd = e->esz * (size_t)ed;
+	DevBuf ds, dd;
+	HIP_TRY_MEM(hipMalloc(&ds.p, std::max<size_t>(ns, 16)));
+	HIP_TRY_MEM(hipMalloc(&dd.p, std::max<size_t>(nd, 16) + 16));
+	HIP_TRY(hipMemcpyAsync(ds.p, src, ns, hipMemcpyHostToDevice, e->stream));
+	if (accumulate) HIP_TRY(hipMemcpyAsync(dd.p, dst, nd, hipMemcpyHostToDevice, e->stream));
+	bool h = false;
+	st = B.apply(e, op, site, spin, nsites, nup, ndown, factor_re, factor_im, ds.p, dd.p, accumulate != 0, &h, nullptr);
+	if (st != LPP_OK) return st;
+	HIP_TRY(hipMemcpyAsync(dst, dd.p, nd, hipMemcpyDeviceToHost, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	return LPP_OK;
+}
+
+lpp_status bench_operator_body(const ObsBasis& B, const char* who, lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown,
+                               int32_t warmup, int32_t iters, double* ms_per_launch, double* model_bytes)
+{
+	if (!e || !ms_per_launch || iters < 1 || warmup < 0) return fail(LPP_ERR_INVALID, std::string(who) + ": bad argument");
+	lpp_status st = refuse(e, who, B.hole_major_ok);
+	if (st != LPP_OK) return st;
+	HIP_TRY(hipSetDevice(e->cfg.device));
+	bool planned = false;
+	int64_t ns = 0, nd = 0, touched = 0;
+	st = plan_sizes(e, B, op, site, spin, nsites, nup, ndown, &planned, &ns, &nd, &touched); // touched: the byte model below
+	if (st != LPP_OK) return st;
+	if (!planned) return fail(LPP_ERR_INVALID, std::string(who) + ": the operator leads to no sector");
+	DevBuf ds, dd;
+	HIP_TRY_MEM(hipMalloc(&ds.p, std::max<size_t>(e->esz * (size_t)ns, 16)));
+	HIP_TRY_MEM(hipMalloc(&dd.p, std::max<size_t>(e->esz * (size_t)nd, 16) + 16));
+	HIP_TRY(hipMemsetAsync(ds.p, 0, e->esz * (size_t)ns, e->stream));
+	HIP_TRY(hipMemsetAsync(dd.p, 0, e->esz * (size_t)nd, e->stream));
+	hipEvent_t t0 = nullptr, t1 = nullptr;
+	HIP_TRY(hipEventCreate(&t0));
+	HIP_TRY(hipEventCreate(&t1));
+	bool h = false;
+	for (int i = 0; i < warmup + iters && st == LPP_OK; i++) {
+		if (i == warmup) (void)hipEventRecord(t0, e->stream);
+		st = B.apply(e, op, site, spin, nsites, nup, ndown, 1.0, 0.0, ds.p, dd.p, true, &h, nullptr);
+	}
+	(void)hipEventRecord(t1, e->stream);
+	hipError_t err = hipEventSynchronize(t1);
+	float ms = 0;
+	if (err == hipSuccess) err = hipEventElapsedTime(&ms, t0, t1);
+	(void)hipEventDestroy(t0);
+	(void)hipEventDestroy(t1);
+	if (st != LPP_OK) return st;
+	HIP_TRY(err);
+	*ms_per_launch = ms / iters;
+	// the issue's byte model of z += A src: destination read + write, source entries read once
+	if (model_bytes) *model_bytes = (double)e->esz * (2.0 * (double)nd + (double)touched);
+	return LPP_OK;
+}
+
+lpp_status two_point_body(const ObsBasis& Bs, const std::string& who, lpp_engine* e, int32_t op, int32_t spin1, int32_t spin2, int32_t nsites, int32_t nup, int32_t ndown,
+                          int32_t bra_state, int32_t ket_state, void* result, void* trace)
+{
+	if (!e || !result) return fail(LPP_ERR_INVALID, who + ": null argument");
+	lpp_status st = refuse(e, who.c_str(), Bs.hole_major_ok);
+	if (st != LPP_OK) return st;
+	if (!valid_op(op)) return fail(LPP_ERR_INVALID, who + ": unknown operator");
+	if ((spin1 != 0 && spin1 != 1) || (spin2 != 0 && spin2 != 1)) return fail(LPP_ERR_INVALID, who + ": bad spin");
+	const int L = nsites;
+	if (Bs.sector_size(L, nup, ndown) < 0) return fail(LPP_ERR_INVALID, who + ": bad sites / sector");
+	double *bra = nullptr, *ket = nullptr;
+	if ((st = state_ptr(e, bra_state, who.c_str(), &bra)) != LPP_OK) return st;
+	if ((st = state_ptr(e, ket_state, who.c_str(), &ket)) != LPP_OK) return st;
+	if (e->resident_len != Bs.sector_size(L, nup, ndown)) return fail(LPP_ERR_INVALID, who + ": (sites, nup, ndown) is not the sector of the resident states");
+	HIP_TRY(hipSetDevice(e->cfg.device));
+	const int w = e->is_complex ? 2 : 1;
+	double* res = (double*)result;
+	for (int64_t i = 0; i < (int64_t)L * L; i++) { // Engine.h:303-305
+		res[w * i] = -100.0;
+		if (w == 2) res[w * i + 1] = 0.0;
+	}
+	if (trace) {
+		((double*)trace)[0] = 0.0;
+		if (w == 2) ((double*)trace)[1] = 0.0;
+	}
+	int nup2 = nup, ndn2 = ndown;
+	if (needs_new_basis(op)) {
+		if (spin1 != spin2) return fail(LPP_ERR_INVALID, "twoPoint: no support yet for off-diagonal spin when needs new basis"); // Engine.h:276-282
+		if (!Bs.new_parts(op, spin1, L, nup, ndown, &nup2, &ndn2)) return LPP_OK; // no such sector: the matrix keeps its fill
+	}
+	const int64_t ndst = Bs.sector_size(L, nup2, ndn2);
+	if (ndst <= 0) return LPP_OK;
+	const int64_t stride = ((ndst * w + 1) & ~(int64_t)1) + 0; // doubles per modified vector, 16-byte aligned columns
+	const int64_t ld2 = stride / 2, n2 = stride / 2;
+	const bool same = (bra == ket) && (spin1 == spin2);
+	// panels of bra vectors sized to the free memory; the ket vectors are one scratch vector each unless they ARE the bra vectors
+	size_t free_b = 0, total_b = 0;
+	HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+	const size_t vec_bytes = sizeof(double) * (size_t)stride;
+	int64_t fit = (int64_t)((double)free_b * 0.8 / (double)vec_bytes) - 1;
+	if (fit < 1) return fail(LPP_ERR_NOMEM, who + ": no room for two modified vectors");
+	const int panel = (int)std::min<int64_t>(L, fit);
+	DevBuf B, K, part, out;
+	HIP_TRY_MEM(hipMalloc(&B.p, vec_bytes * (size_t)panel));
+	HIP_TRY_MEM(hipMalloc(&K.p, vec_bytes));
+	const int nb = blas_blocks(n2);
+	HIP_TRY_MEM(hipMalloc(&part.p, sizeof(double) * (size_t)nb * 2 * kPanel));
+	HIP_TRY_MEM(hipMalloc(&out.p, sizeof(double) * 2 * (size_t)L * (size_t)L));
+	HIP_TRY(hipMemsetAsync(out.p, 0, sizeof(double) * 2 * (size_t)L * (size_t)L, e->stream));
+	HIP_TRY(hipMemsetAsync(B.p, 0, vec_bytes * (size_t)panel, e->stream)); // the padding element of an odd length stays 0
+	HIP_TRY(hipMemsetAsync(K.p, 0, vec_bytes, e->stream));
+	bool has = false;
+	for (int j0 = 0; j0 < L; j0 += panel) {
+		const int nj = std::min(panel, L - j0);
+		for (int j = 0; j < nj; j++) {
+			st = acc_modified_dev(e, Bs, op, j0 + j, spin2, L, nup, ndown, 1.0, bra, (double*)B.p + (int64_t)j * stride, false, &has);
+			if (st != LPP_OK) return st;
+		}
+		for (int i = 0; i < L; i++) {
+			const double* xi = nullptr;
+			if (same && i >= j0 && i < j0 + nj) {
+				xi = (const double*)B.p + (int64_t)(i - j0) * stride;
+			} else {
+				st = acc_modified_dev(e, Bs, op, i, spin1, L, nup, ndown, 1.0, ket, K.p, false, &has);
+				if (st != LPP_OK) return st;
+				xi = (const double*)K.p;
+			}
+			for (int p0 = 0; p0 < nj; p0 += kPanel) {
+				const int np = std::min(kPanel, nj - p0);
+				const double2* v0 = (const double2*)((double*)B.p + (int64_t)p0 * stride);
+				// coef_p = sum conj(v_p) x: the bra side (the left factor of modifVector2 * modifVector1) is conjugated
+				if (e->is_complex) k_multi_dot<true><<<nb, kBlock, 0, e->stream>>>((const double2*)xi, v0, ld2, np, n2, (double*)part.p);
+				else k_multi_dot<false><<<nb, kBlock, 0, e->stream>>>((const double2*)xi, v0, ld2, np, n2, (double*)part.p);
+				k_reduce_final<<<1, kBlock, 0, e->stream>>>((const double*)part.p, nb, 2 * kPanel, 2 * np, (double*)out.p + 2 * ((int64_t)i * L + j0 + p0));
+			}
+		}
+	}
+	HIP_TRY(hipGetLastError());
+	std::vector<double> h(2 * (size_t)L * (size_t)L);
+	HIP_TRY(hipMemcpyAsync(h.data(), out.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	double tr = 0, ti = 0;
+	for (int i = 0; i < L; i++)
+		for (int j = 0; j < L; j++) {
+			const size_t q = (size_t)i * L + j;
+			res[w * q] = h[2 * q];
+			if (w == 2) res[w * q + 1] = h[2 * q + 1];
+			if (i == j) {
+				tr += h[2 * q];
+				ti += h[2 * q + 1];
+			}
+		}
+	if (trace) {
+		((double*)trace)[0] = tr;
+		if (w == 2) ((double*)trace)[1] = ti;
+	}
+	return LPP_OK;
+}
+
+lpp_status spectral_body(const ObsBasis& B, const std::string& who, lpp_engine* e, int32_t state, lpp_engine* sector, int32_t op, int32_t isite, int32_t jsite, int32_t spin,
+                         double isign, int32_t nsites, int32_t nup, int32_t ndown, double* weight, int32_t* nsteps, double* a, double* b, lpp_stats* stats)
+{
+	if (!e || !sector || !weight || !nsteps || !a || !b) return fail(LPP_ERR_INVALID, who + ": null argument");
+	lpp_status st = refuse(e, who.c_str(), B.hole_major_ok);
+	if (st != LPP_OK) return st;
+	if ((st = refuse(sector, (who + " (sector engine)").c_str(), B.hole_major_ok)) != LPP_OK) return st;
+	if (e->cfg.device != sector->cfg.device || e->is_complex != sector->is_complex) return fail(LPP_ERR_INVALID, who + ": the sector engine must share device and dtype");
+	if (!sector->has_matrix()) return fail(LPP_ERR_STATE, who + ": the sector engine has no matrix");
+	double* gs = nullptr;
+	if ((st = state_ptr(e, state, who.c_str(), &gs)) != LPP_OK) return st;
+	const int L = nsites;
+	if (B.sector_size(L, nup, ndown) < 0 || e->resident_len != B.sector_size(L, nup, ndown))
+		return fail(LPP_ERR_INVALID, who + ": (sites, nup, ndown) is not the sector of the resident state");
+	int nup2 = nup, ndn2 = ndown;
+	if (needs_new_basis(op) && !B.new_parts(op, spin, L, nup, ndown, &nup2, &ndn2)) return fail(LPP_ERR_INVALID, who + ": the operator leads to no sector (lpp_obs_new_parts)");
+	const int64_t ndst = B.sector_size(L, nup2, ndn2);
+	if (ndst != sector->n_global) return fail(LPP_ERR_INVALID, who + ": the sector engine does not hold the operator's sector");
+	HIP_TRY(hipSetDevice(e->cfg.device));
+	const int w = e->is_complex ? 2 : 1;
+	const int64_t stride = (ndst * w + 1) & ~(int64_t)1;
+	DevBuf M, part;
+	HIP_TRY_MEM(hipMalloc(&M.p, sizeof(double) * (size_t)stride + 16));
+	const int nb = blas_blocks(stride / 2);
+	HIP_TRY_MEM(hipMalloc(&part.p, sizeof(double) * (size_t)(nb + 1)));
+	HIP_TRY(hipMemsetAsync(M.p, 0, sizeof(double) * (size_t)stride, e->stream));
+	bool has = false;
+	// getModifiedState (Engine.h:494-533): A_i gs, then isign A_j gs on top -- for i == j the state is accumulated twice
+	st = B.apply(e, op, isite, spin, L, nup, ndown, 1.0, 0.0, gs, M.p, true, &has, nullptr);
+	if (st != LPP_OK) return st;
+	st = B.apply(e, op, jsite, spin, L, nup, ndown, isign, 0.0, gs, M.p, true, &has, nullptr);
+	if (st != LPP_OK) return st;
+	k_dot<<<nb, kBlock, 0, e->stream>>>((const double2*)M.p, (const double2*)M.p, stride / 2, (double*)part.p);
+	k_reduce_final<<<1, kBlock, 0, e->stream>>>((const double*)part.p, nb, 1, 1, (double*)part.p + nb);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(weight, (double*)part.p + nb, sizeof(double), hipMemcpyDeviceToHost, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream)); // the sector engine runs on a stream of its own
+	return decomposition_device_any(sector, M.p, nsteps, a, b, stats); // (a hole-major sector engine takes the vector through its permutation)
 }
 
 } // namespace
@@ -368,6 +845,38 @@ lpp_status lpp_obs_plan(int32_t op, int32_t site, int32_t spin, int32_t nsites, 
 	return LPP_OK;
 }
 
+lpp_status lpp_obs_new_parts_tj(int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t* has, int32_t* nup_new, int32_t* ndown_new)
+{
+	if (!has) return fail(LPP_ERR_INVALID, "lpp_obs_new_parts_tj: null argument");
+	*has = 0;
+	if (spin != LPP_SPIN_UP && spin != LPP_SPIN_DOWN) return fail(LPP_ERR_INVALID, "lpp_obs_new_parts_tj: bad spin");
+	if (nsites < 1 || nup < 0 || ndown < 0 || nup + ndown > nsites) return fail(LPP_ERR_INVALID, "lpp_obs_new_parts_tj: bad sector");
+	if (!needs_new_basis(op)) return fail(LPP_ERR_INVALID, "hasNewParts: unsupported operator"); // the reference throws for n and sz (TjMultiOrb.h:154-158)
+	int n1 = 0, n2 = 0;
+	if (!new_parts_tj(op, spin, nsites, nup, ndown, &n1, &n2)) return LPP_OK;
+	*has = 1;
+	if (nup_new) *nup_new = n1;
+	if (ndown_new) *ndown_new = n2;
+	return LPP_OK;
+}
+
+lpp_status lpp_obs_plan_tj(int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t* has, int32_t* nup_new, int32_t* ndown_new,
+                           int64_t* n_dst, int64_t* action)
+{
+	if (!has) return fail(LPP_ERR_INVALID, "lpp_obs_plan_tj: null argument");
+	ObsTjPlan P;
+	bool h = false;
+	lpp_status st = obs_plan_tj(op, site, spin, nsites, nup, ndown, &h, P);
+	if (st != LPP_OK) return st;
+	*has = h ? 1 : 0;
+	if (!h) return LPP_OK;
+	if (nup_new) *nup_new = P.nup2;
+	if (ndown_new) *ndown_new = P.ndn2;
+	if (n_dst) *n_dst = P.n_up_dst * P.n_dn_dst;
+	if (action) tj_expand(P, action, nullptr);
+	return LPP_OK;
+}
+
 lpp_status lpp_continued_fraction(int32_t n, const double* a, const double* b, double eg, double weight, double sigma, double z_re, double z_im, double* out)
 {
 	if (n < 1 || !a || !b || !out) return fail(LPP_ERR_INVALID, "lpp_continued_fraction: bad argument");
@@ -383,90 +892,34 @@ lpp_status lpp_continued_fraction(int32_t n, const double* a, const double* b, d
 lpp_status lpp_engine_apply_operator(lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, double factor_re,
                                      double factor_im, const void* d_src, void* d_dst, int32_t accumulate, int32_t* has)
 {
-	if (!e || !has) return fail(LPP_ERR_INVALID, "lpp_engine_apply_operator: null argument");
-	lpp_status st = refuse(e, "lpp_engine_apply_operator");
-	if (st != LPP_OK) return st;
-	HIP_TRY(hipSetDevice(e->cfg.device));
-	bool h = false;
-	st = apply_dev(e, op, site, spin, nsites, nup, ndown, factor_re, factor_im, d_src, d_dst, accumulate != 0, &h, nullptr);
-	*has = h ? 1 : 0;
-	return st;
+	return apply_operator_body(kHubbard, "lpp_engine_apply_operator", e, op, site, spin, nsites, nup, ndown, factor_re, factor_im, d_src, d_dst, accumulate, has);
+}
+lpp_status lpp_engine_apply_operator_tj(lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, double factor_re,
+                                        double factor_im, const void* d_src, void* d_dst, int32_t accumulate, int32_t* has)
+{
+	return apply_operator_body(kTj, "lpp_engine_apply_operator_tj", e, op, site, spin, nsites, nup, ndown, factor_re, factor_im, d_src, d_dst, accumulate, has);
 }
 
 lpp_status lpp_engine_apply_operator_host(lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, double factor_re,
                                           double factor_im, const void* src, void* dst, int32_t accumulate, int32_t* has)
 {
-	if (!e || !has || !src || !dst) return fail(LPP_ERR_INVALID, "lpp_engine_apply_operator_host: null argument");
-	lpp_status st = refuse(e, "lpp_engine_apply_operator_host");
-	if (st != LPP_OK) return st;
-	HIP_TRY(hipSetDevice(e->cfg.device));
-	const DevPlan* D = nullptr;
-	st = get_plan(e, op, site, spin, nsites, nup, ndown, &D);
-	if (st != LPP_OK) return st;
-	*has = D->has ? 1 : 0;
-	if (!D->has) return LPP_OK;
-	const size_t ns = e->esz * (size_t)(D->host.n_up_src * D->host.n_dn_src), nd = e->esz * (size_t)(D->host.n_up_dst * D->host.n_dn_dst);
-	DevBuf ds, dd;
-	HIP_TRY_MEM(hipMalloc(&ds.p, std::max<size_t>(ns, 16)));
-	HIP_TRY_MEM(hipMalloc(&dd.p, std::max<size_t>(nd, 16) + 16));
-	HIP_TRY(hipMemcpyAsync(ds.p, src, ns, hipMemcpyHostToDevice, e->stream));
-	if (accumulate) HIP_TRY(hipMemcpyAsync(dd.p, dst, nd, hipMemcpyHostToDevice, e->stream));
-	bool h = false;
-	st = apply_dev(e, op, site, spin, nsites, nup, ndown, factor_re, factor_im, ds.p, dd.p, accumulate != 0, &h, nullptr);
-	if (st != LPP_OK) return st;
-	HIP_TRY(hipMemcpyAsync(dst, dd.p, nd, hipMemcpyDeviceToHost, e->stream));
-	HIP_TRY(hipStreamSynchronize(e->stream));
-	return LPP_OK;
+	return apply_operator_host_body(kHubbard, "lpp_engine_apply_operator_host", e, op, site, spin, nsites, nup, ndown, factor_re, factor_im, src, dst, accumulate, has);
+}
+lpp_status lpp_engine_apply_operator_tj_host(lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, double factor_re,
+                                             double factor_im, const void* src, void* dst, int32_t accumulate, int32_t* has)
+{
+	return apply_operator_host_body(kTj, "lpp_engine_apply_operator_tj_host", e, op, site, spin, nsites, nup, ndown, factor_re, factor_im, src, dst, accumulate, has);
 }
 
 lpp_status lpp_engine_bench_operator(lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t warmup, int32_t iters,
                                      double* ms_per_launch, double* model_bytes)
 {
-	if (!e || !ms_per_launch || iters < 1 || warmup < 0) return fail(LPP_ERR_INVALID, "lpp_engine_bench_operator: bad argument");
-	lpp_status st = refuse(e, "lpp_engine_bench_operator");
-	if (st != LPP_OK) return st;
-	HIP_TRY(hipSetDevice(e->cfg.device));
-	const DevPlan* D = nullptr;
-	st = get_plan(e, op, site, spin, nsites, nup, ndown, &D);
-	if (st != LPP_OK) return st;
-	if (!D->has) return fail(LPP_ERR_INVALID, "lpp_engine_bench_operator: the operator leads to no sector");
-	const int64_t ns = D->host.n_up_src * D->host.n_dn_src, nd = D->host.n_up_dst * D->host.n_dn_dst;
-	DevBuf ds, dd;
-	HIP_TRY_MEM(hipMalloc(&ds.p, std::max<size_t>(e->esz * (size_t)ns, 16)));
-	HIP_TRY_MEM(hipMalloc(&dd.p, std::max<size_t>(e->esz * (size_t)nd, 16) + 16));
-	HIP_TRY(hipMemsetAsync(ds.p, 0, e->esz * (size_t)ns, e->stream));
-	HIP_TRY(hipMemsetAsync(dd.p, 0, e->esz * (size_t)nd, e->stream));
-	hipEvent_t t0 = nullptr, t1 = nullptr;
-	HIP_TRY(hipEventCreate(&t0));
-	HIP_TRY(hipEventCreate(&t1));
-	bool h = false;
-	for (int i = 0; i < warmup + iters && st == LPP_OK; i++) {
-		if (i == warmup) (void)hipEventRecord(t0, e->stream);
-		st = apply_dev(e, op, site, spin, nsites, nup, ndown, 1.0, 0.0, ds.p, dd.p, true, &h, nullptr);
-	}
-	(void)hipEventRecord(t1, e->stream);
-	hipError_t err = hipEventSynchronize(t1);
-	float ms = 0;
-	if (err == hipSuccess) err = hipEventElapsedTime(&ms, t0, t1);
-	(void)hipEventDestroy(t0);
-	(void)hipEventDestroy(t1);
-	if (st != LPP_OK) return st;
-	HIP_TRY(err);
-	*ms_per_launch = ms / iters;
-	// the issue's byte model of z += A src: destination read + write, source entries read once
-	int64_t touched = 0;
-	{
-		ObsPlan P;
-		bool hh = false;
-		st = obs_plan(op, site, spin, nsites, nup, ndown, &hh, P);
-		if (st != LPP_OK) return st;
-		int64_t cu = P.n_up_dst, cd = P.n_dn_dst;
-		if (!P.tu.empty()) cu = (int64_t)std::count_if(P.tu.begin(), P.tu.end(), [](int32_t v) { return v != 0; });
-		if (!P.td.empty()) cd = (int64_t)std::count_if(P.td.begin(), P.td.end(), [](int32_t v) { return v != 0; });
-		touched = cu * cd;
-	}
-	if (model_bytes) *model_bytes = (double)e->esz * (2.0 * (double)nd + (double)touched);
-	return LPP_OK;
+	return bench_operator_body(kHubbard, "lpp_engine_bench_operator", e, op, site, spin, nsites, nup, ndown, warmup, iters, ms_per_launch, model_bytes);
+}
+lpp_status lpp_engine_bench_operator_tj(lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t warmup, int32_t iters,
+                                        double* ms_per_launch, double* model_bytes)
+{
+	return bench_operator_body(kTj, "lpp_engine_bench_operator_tj", e, op, site, spin, nsites, nup, ndown, warmup, iters, ms_per_launch, model_bytes);
 }
 
 lpp_status lpp_engine_keep_states(lpp_engine* e, int32_t k)
@@ -478,6 +931,20 @@ lpp_status lpp_engine_keep_states(lpp_engine* e, int32_t k)
 		if (st != LPP_OK) return st;
 	}
 	e->keep_k = k;
+	e->keep_tj = false;
+	return LPP_OK;
+}
+
+lpp_status lpp_engine_keep_states_tj(lpp_engine* e, int32_t k)
+{
+	if (!e || k < 0) return fail(LPP_ERR_INVALID, "lpp_engine_keep_states_tj: bad argument");
+	if (e->active) return fail(LPP_ERR_STATE, "lpp_engine_keep_states_tj: a Lanczos run is active");
+	if (k > 0) {
+		lpp_status st = refuse(e, "lpp_engine_keep_states_tj", true);
+		if (st != LPP_OK) return st;
+	}
+	e->keep_k = k;
+	e->keep_tj = true; // the solve lets a hole-major engine through (lanczos_impl)
 	return LPP_OK;
 }
 
@@ -507,140 +974,23 @@ lpp_status lpp_engine_state_to_host(lpp_engine* e, int32_t k, void* host)
 lpp_status lpp_engine_two_point(lpp_engine* e, int32_t op, int32_t spin1, int32_t spin2, int32_t nsites, int32_t nup, int32_t ndown, int32_t bra_state,
                                 int32_t ket_state, void* result, void* trace)
 {
-	if (!e || !result) return fail(LPP_ERR_INVALID, "lpp_engine_two_point: null argument");
-	lpp_status st = refuse(e, "lpp_engine_two_point");
-	if (st != LPP_OK) return st;
-	if (!valid_op(op)) return fail(LPP_ERR_INVALID, "lpp_engine_two_point: unknown operator");
-	if ((spin1 != 0 && spin1 != 1) || (spin2 != 0 && spin2 != 1)) return fail(LPP_ERR_INVALID, "lpp_engine_two_point: bad spin");
-	const int L = nsites;
-	if (L < 1 || L > 30 || nup < 0 || ndown < 0 || nup > L || ndown > L) return fail(LPP_ERR_INVALID, "lpp_engine_two_point: bad sites / sector");
-	double *bra = nullptr, *ket = nullptr;
-	if ((st = state_ptr(e, bra_state, "lpp_engine_two_point", &bra)) != LPP_OK) return st;
-	if ((st = state_ptr(e, ket_state, "lpp_engine_two_point", &ket)) != LPP_OK) return st;
-	if (e->resident_len != binom(L, nup) * binom(L, ndown)) return fail(LPP_ERR_INVALID, "lpp_engine_two_point: (sites, nup, ndown) is not the sector of the resident states");
-	HIP_TRY(hipSetDevice(e->cfg.device));
-	const int w = e->is_complex ? 2 : 1;
-	double* res = (double*)result;
-	for (int64_t i = 0; i < (int64_t)L * L; i++) { // Engine.h:303-305
-		res[w * i] = -100.0;
-		if (w == 2) res[w * i + 1] = 0.0;
-	}
-	if (trace) {
-		((double*)trace)[0] = 0.0;
-		if (w == 2) ((double*)trace)[1] = 0.0;
-	}
-	int nup2 = nup, ndn2 = ndown;
-	if (needs_new_basis(op)) {
-		if (spin1 != spin2) return fail(LPP_ERR_INVALID, "twoPoint: no support yet for off-diagonal spin when needs new basis"); // Engine.h:276-282
-		if (!new_parts(op, spin1, L, nup, ndown, &nup2, &ndn2)) return LPP_OK; // no such sector: the matrix keeps its fill
-	}
-	const int64_t ndst = binom(L, nup2) * binom(L, ndn2);
-	if (ndst == 0) return LPP_OK;
-	const int64_t stride = ((ndst * w + 1) & ~(int64_t)1) + 0; // doubles per modified vector, 16-byte aligned columns
-	const int64_t ld2 = stride / 2, n2 = stride / 2;
-	const bool same = (bra == ket) && (spin1 == spin2);
-	// panels of bra vectors sized to the free memory; the ket vectors are one scratch vector each unless they ARE the bra vectors
-	size_t free_b = 0, total_b = 0;
-	HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-	const size_t vec_bytes = sizeof(double) * (size_t)stride;
-	int64_t fit = (int64_t)((double)free_b * 0.8 / (double)vec_bytes) - 1;
-	if (fit < 1) return fail(LPP_ERR_NOMEM, "lpp_engine_two_point: no room for two modified vectors");
-	const int panel = (int)std::min<int64_t>(L, fit);
-	DevBuf B, K, part, out;
-	HIP_TRY_MEM(hipMalloc(&B.p, vec_bytes * (size_t)panel));
-	HIP_TRY_MEM(hipMalloc(&K.p, vec_bytes));
-	const int nb = blas_blocks(n2);
-	HIP_TRY_MEM(hipMalloc(&part.p, sizeof(double) * (size_t)nb * 2 * kPanel));
-	HIP_TRY_MEM(hipMalloc(&out.p, sizeof(double) * 2 * (size_t)L * (size_t)L));
-	HIP_TRY(hipMemsetAsync(out.p, 0, sizeof(double) * 2 * (size_t)L * (size_t)L, e->stream));
-	HIP_TRY(hipMemsetAsync(B.p, 0, vec_bytes * (size_t)panel, e->stream)); // the padding element of an odd length stays 0
-	HIP_TRY(hipMemsetAsync(K.p, 0, vec_bytes, e->stream));
-	bool has = false;
-	for (int j0 = 0; j0 < L; j0 += panel) {
-		const int nj = std::min(panel, L - j0);
-		for (int j = 0; j < nj; j++) {
-			st = acc_modified_dev(e, op, j0 + j, spin2, L, nup, ndown, 1.0, bra, (double*)B.p + (int64_t)j * stride, false, &has);
-			if (st != LPP_OK) return st;
-		}
-		for (int i = 0; i < L; i++) {
-			const double* xi = nullptr;
-			if (same && i >= j0 && i < j0 + nj) {
-				xi = (const double*)B.p + (int64_t)(i - j0) * stride;
-			} else {
-				st = acc_modified_dev(e, op, i, spin1, L, nup, ndown, 1.0, ket, K.p, false, &has);
-				if (st != LPP_OK) return st;
-				xi = (const double*)K.p;
-			}
-			for (int p0 = 0; p0 < nj; p0 += kPanel) {
-				const int np = std::min(kPanel, nj - p0);
-				const double2* v0 = (const double2*)((double*)B.p + (int64_t)p0 * stride);
-				// coef_p = sum conj(v_p) x: the bra side (the left factor of modifVector2 * modifVector1) is conjugated
-				if (e->is_complex) k_multi_dot<true><<<nb, kBlock, 0, e->stream>>>((const double2*)xi, v0, ld2, np, n2, (double*)part.p);
-				else k_multi_dot<false><<<nb, kBlock, 0, e->stream>>>((const double2*)xi, v0, ld2, np, n2, (double*)part.p);
-				k_reduce_final<<<1, kBlock, 0, e->stream>>>((const double*)part.p, nb, 2 * kPanel, 2 * np, (double*)out.p + 2 * ((int64_t)i * L + j0 + p0));
-			}
-		}
-	}
-	HIP_TRY(hipGetLastError());
-	std::vector<double> h(2 * (size_t)L * (size_t)L);
-	HIP_TRY(hipMemcpyAsync(h.data(), out.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, e->stream));
-	HIP_TRY(hipStreamSynchronize(e->stream));
-	double tr = 0, ti = 0;
-	for (int i = 0; i < L; i++)
-		for (int j = 0; j < L; j++) {
-			const size_t q = (size_t)i * L + j;
-			res[w * q] = h[2 * q];
-			if (w == 2) res[w * q + 1] = h[2 * q + 1];
-			if (i == j) {
-				tr += h[2 * q];
-				ti += h[2 * q + 1];
-			}
-		}
-	if (trace) {
-		((double*)trace)[0] = tr;
-		if (w == 2) ((double*)trace)[1] = ti;
-	}
-	return LPP_OK;
+	return two_point_body(kHubbard, "lpp_engine_two_point", e, op, spin1, spin2, nsites, nup, ndown, bra_state, ket_state, result, trace);
+}
+lpp_status lpp_engine_two_point_tj(lpp_engine* e, int32_t op, int32_t spin1, int32_t spin2, int32_t nsites, int32_t nup, int32_t ndown, int32_t bra_state,
+                                   int32_t ket_state, void* result, void* trace)
+{
+	return two_point_body(kTj, "lpp_engine_two_point_tj", e, op, spin1, spin2, nsites, nup, ndown, bra_state, ket_state, result, trace);
 }
 
 lpp_status lpp_engine_spectral_decomposition(lpp_engine* e, int32_t state, lpp_engine* sector, int32_t op, int32_t isite, int32_t jsite, int32_t spin, double isign,
                                              int32_t nsites, int32_t nup, int32_t ndown, double* weight, int32_t* nsteps, double* a, double* b, lpp_stats* stats)
 {
-	if (!e || !sector || !weight || !nsteps || !a || !b) return fail(LPP_ERR_INVALID, "lpp_engine_spectral_decomposition: null argument");
-	lpp_status st = refuse(e, "lpp_engine_spectral_decomposition");
-	if (st != LPP_OK) return st;
-	if ((st = refuse(sector, "lpp_engine_spectral_decomposition (sector engine)")) != LPP_OK) return st;
-	if (e->cfg.device != sector->cfg.device || e->is_complex != sector->is_complex) return fail(LPP_ERR_INVALID, "lpp_engine_spectral_decomposition: the sector engine must share device and dtype");
-	if (!sector->has_matrix()) return fail(LPP_ERR_STATE, "lpp_engine_spectral_decomposition: the sector engine has no matrix");
-	double* gs = nullptr;
-	if ((st = state_ptr(e, state, "lpp_engine_spectral_decomposition", &gs)) != LPP_OK) return st;
-	const int L = nsites;
-	if (L < 1 || L > 30 || nup < 0 || ndown < 0 || nup > L || ndown > L || e->resident_len != binom(L, nup) * binom(L, ndown))
-		return fail(LPP_ERR_INVALID, "lpp_engine_spectral_decomposition: (sites, nup, ndown) is not the sector of the resident state");
-	int nup2 = nup, ndn2 = ndown;
-	if (needs_new_basis(op) && !new_parts(op, spin, L, nup, ndown, &nup2, &ndn2)) return fail(LPP_ERR_INVALID, "lpp_engine_spectral_decomposition: the operator leads to no sector (lpp_obs_new_parts)");
-	const int64_t ndst = binom(L, nup2) * binom(L, ndn2);
-	if (ndst != sector->n_global) return fail(LPP_ERR_INVALID, "lpp_engine_spectral_decomposition: the sector engine does not hold the operator's sector");
-	HIP_TRY(hipSetDevice(e->cfg.device));
-	const int w = e->is_complex ? 2 : 1;
-	const int64_t stride = (ndst * w + 1) & ~(int64_t)1;
-	DevBuf M, part;
-	HIP_TRY_MEM(hipMalloc(&M.p, sizeof(double) * (size_t)stride + 16));
-	const int nb = blas_blocks(stride / 2);
-	HIP_TRY_MEM(hipMalloc(&part.p, sizeof(double) * (size_t)(nb + 1)));
-	HIP_TRY(hipMemsetAsync(M.p, 0, sizeof(double) * (size_t)stride, e->stream));
-	bool has = false;
-	// getModifiedState (Engine.h:494-533): A_i gs, then isign A_j gs on top -- for i == j the state is accumulated twice
-	st = apply_dev(e, op, isite, spin, L, nup, ndown, 1.0, 0.0, gs, M.p, true, &has, nullptr);
-	if (st != LPP_OK) return st;
-	st = apply_dev(e, op, jsite, spin, L, nup, ndown, isign, 0.0, gs, M.p, true, &has, nullptr);
-	if (st != LPP_OK) return st;
-	k_dot<<<nb, kBlock, 0, e->stream>>>((const double2*)M.p, (const double2*)M.p, stride / 2, (double*)part.p);
-	k_reduce_final<<<1, kBlock, 0, e->stream>>>((const double*)part.p, nb, 1, 1, (double*)part.p + nb);
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipMemcpyAsync(weight, (double*)part.p + nb, sizeof(double), hipMemcpyDeviceToHost, e->stream));
-	HIP_TRY(hipStreamSynchronize(e->stream)); // the sector engine runs on a stream of its own
-	return lpp_engine_decomposition_device(sector, M.p, nsteps, a, b, stats);
+	return spectral_body(kHubbard, "lpp_engine_spectral_decomposition", e, state, sector, op, isite, jsite, spin, isign, nsites, nup, ndown, weight, nsteps, a, b, stats);
+}
+lpp_status lpp_engine_spectral_decomposition_tj(lpp_engine* e, int32_t state, lpp_engine* sector, int32_t op, int32_t isite, int32_t jsite, int32_t spin, double isign,
+                                                int32_t nsites, int32_t nup, int32_t ndown, double* weight, int32_t* nsteps, double* a, double* b, lpp_stats* stats)
+{
+	return spectral_body(kTj, "lpp_engine_spectral_decomposition_tj", e, state, sector, op, isite, jsite, spin, isign, nsites, nup, ndown, weight, nsteps, a, b, stats);
 }
 
 } // extern "C"

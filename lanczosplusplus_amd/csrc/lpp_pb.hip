@@ -1515,16 +1515,17 @@ static lpp_status vec_out(lpp_engine* e, void* dst, const double* dev, hipMemcpy
 	return LPP_OK;
 }
 
-// the hole-major t-J layout has host copies of its own and no device-side ones
+// the hole-major t-J layout has copies of its own (through its permutation).  Which public entry points hand a device vector to a hole-major
+// engine is decided by their callers (begin_run, lanczos_impl), not here.
 lpp_status vec_from_host(lpp_engine* e, double* dev, const void* host) { return e->tj.active ? tj_vec_from_host(e, dev, host) : vec_in(e, dev, host, hipMemcpyHostToDevice); }
 lpp_status vec_to_host(lpp_engine* e, void* host, const double* dev) { return e->tj.active ? tj_vec_to_host(e, host, dev) : vec_out(e, host, dev, hipMemcpyDeviceToHost); }
 lpp_status vec_from_device(lpp_engine* e, double* dev, const void* basis)
 {
-	return e->tj.active ? fail(LPP_ERR_STATE, "device vectors: not on a hole-major t-J engine") : vec_in(e, dev, basis, hipMemcpyDeviceToDevice);
+	return e->tj.active ? tj_vec_from_device(e, dev, basis) : vec_in(e, dev, basis, hipMemcpyDeviceToDevice);
 }
 lpp_status vec_to_device(lpp_engine* e, void* basis, const double* dev)
 {
-	return e->tj.active ? fail(LPP_ERR_STATE, "device vectors: not on a hole-major t-J engine") : vec_out(e, basis, dev, hipMemcpyDeviceToDevice);
+	return e->tj.active ? tj_vec_to_device(e, basis, dev) : vec_out(e, basis, dev, hipMemcpyDeviceToDevice);
 }
 
 void vec_fill_random(lpp_engine* e, double* dev, uint64_t seed)

@@ -205,6 +205,31 @@ lpp_status tj_vec_to_host(lpp_engine* e, void* host, const double* dev)
 	return LPP_OK;
 }
 
+lpp_status tj_vec_from_device(lpp_engine* e, double* dev, const void* basis)
+{
+	const TjState& S = e->tj;
+	HIP_TRY(hipMemsetAsync(dev, 0, sizeof(double) * (size_t)e->nd_pad, e->stream));
+	const int nb = blocks_for((int64_t)S.nblk * S.ns);
+	if (e->is_complex)
+		k_tj_gather<cplx><<<nb, 256, 0, e->stream>>>((cplx*)dev, (const cplx*)basis, S.perm, S.nblk, S.ns, S.pitch);
+	else
+		k_tj_gather<double><<<nb, 256, 0, e->stream>>>(dev, (const double*)basis, S.perm, S.nblk, S.ns, S.pitch);
+	HIP_TRY(hipGetLastError());
+	return LPP_OK;
+}
+
+lpp_status tj_vec_to_device(lpp_engine* e, void* basis, const double* dev)
+{
+	const TjState& S = e->tj;
+	const int nb = blocks_for((int64_t)S.nblk * S.ns);
+	if (e->is_complex)
+		k_tj_scatter<cplx><<<nb, 256, 0, e->stream>>>((cplx*)basis, (const cplx*)dev, S.perm, S.nblk, S.ns, S.pitch);
+	else
+		k_tj_scatter<double><<<nb, 256, 0, e->stream>>>((double*)basis, dev, S.perm, S.nblk, S.ns, S.pitch);
+	HIP_TRY(hipGetLastError());
+	return LPP_OK;
+}
+
 void tj_fill_random(lpp_engine* e, double* dev, uint64_t seed)
 {
 	const TjState& S = e->tj;

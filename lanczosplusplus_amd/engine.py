@@ -200,7 +200,8 @@ class LanczosEngine:
         hr = _mat(hop.real, L)
         hi = _mat(hop.imag, L) if np.iscomplexobj(hop) else None
         pv = None if potentialV is None else np.ascontiguousarray(potentialV, np.float64)
-        self._basis = None
+        self._basis = None  # the reference's ReducedDensityMatrix does not know this basis
+        self._set_model_tj(L, nup, ndown, hop, jpm, jzz, w, potentialV)
         check(self._lib.lpp_engine_assemble_tj(self._h, L, nup, ndown, _vp(hr), _vp(hi), _vp(_mat(jpm, L)),
                                                _vp(_mat(jzz, L)), _vp(_mat(w, L)), _vp(pv),
                                                0 if pv is None else len(pv)))
@@ -314,6 +315,20 @@ class LanczosEngine:
             eng.close()
         self._sectors = {}
 
+    def _set_model_tj(self, L, nup, ndown, hop, jpm, jzz, w, potentialV):
+        self._model = dict(how="assemble_tj", L=L, nup=nup, ndown=ndown, hop=np.array(hop, copy=True), jpm=np.array(jpm, copy=True), jzz=np.array(jzz, copy=True),
+                           w=np.array(w, copy=True), potentialV=None if potentialV is None else np.array(potentialV, copy=True))
+        for eng in self._sectors.values():
+            eng.close()
+        self._sectors = {}
+
+    def _is_tj(self):
+        return self._model is not None and self._model["how"] == "assemble_tj"
+
+    def keep_states_tj(self, k=1):
+        """keep_states that also accepts a hole-major t-J engine (lpp_engine_keep_states_tj): state(k) is then the host Ritz vector bit for bit"""
+        check(self._lib.lpp_engine_keep_states_tj(self._h, int(k)))
+
     def keep_states(self, k=1):
         """Keep the lowest k Ritz vectors of the next lanczos() on the device, in the basis order (lpp_engine_keep_states)."""
         check(self._lib.lpp_engine_keep_states(self._h, int(k)))
@@ -331,18 +346,22 @@ class LanczosEngine:
         check(self._lib.lpp_engine_state_to_host(self._h, int(k), _vp(out)))
         return out
 
-    def apply_operator(self, op, site, spin, L, nup, ndown, src, factor=1.0, out=None):
+    def apply_operator(self, op, site, spin, L, nup, ndown, src, factor=1.0, out=None, basis="hubbard"):
         """Engine::accModifiedState_ (Engine.h:416-458) on the GPU: returns (z, (nup', ndown')) with z[bra] += factor*sign*value*src[ket],
         z starting from `out` (new sector's length) or from zero; (None, None) where the operator leads to no sector.  src: host vector of the
-        (nup, ndown) sector in the basis order."""
+        (nup, ndown) sector in the basis order.  basis: "hubbard" (BasisHubbardLanczos) or "tj" (BasisTjMultiOrbLanczos, one orbital)."""
         oid = _op_id(op)
+        tj = _obs_basis(basis)
         src = np.ascontiguousarray(src, self.np_dtype)
         has, n1, n2 = C.c_int32(), C.c_int32(), C.c_int32()
-        nu, nd = C.c_int64(), C.c_int64()
-        check(self._lib.lpp_obs_plan(oid, site, spin, L, nup, ndown, C.byref(has), C.byref(n1), C.byref(n2), C.byref(nu), C.byref(nd), None, None))
+        nu, nd = C.c_int64(1), C.c_int64()
+        if tj:
+            check(self._lib.lpp_obs_plan_tj(oid, site, spin, L, nup, ndown, C.byref(has), C.byref(n1), C.byref(n2), C.byref(nd), None))
+        else:
+            check(self._lib.lpp_obs_plan(oid, site, spin, L, nup, ndown, C.byref(has), C.byref(n1), C.byref(n2), C.byref(nu), C.byref(nd), None, None))
         if not has.value:
             return None, None
-        if len(src) != sector_size(L, nup, ndown):
+        if len(src) != sector_size(L, nup, ndown, basis):
             raise ValueError("src does not have the length of sector (%d, %d)" % (nup, ndown))
         n = nu.value * nd.value
         if out is None:
@@ -352,13 +371,15 @@ class LanczosEngine:
             if len(z) != n:
                 raise ValueError("out does not have the length of sector (%d, %d)" % (n1.value, n2.value))
         f = complex(factor)
-        check(self._lib.lpp_engine_apply_operator_host(self._h, oid, site, spin, L, nup, ndown, f.real, f.imag, _vp(src), _vp(z), int(out is not None), C.byref(has)))
+        call = self._lib.lpp_engine_apply_operator_tj_host if tj else self._lib.lpp_engine_apply_operator_host
+        check(call(self._h, oid, site, spin, L, nup, ndown, f.real, f.imag, _vp(src), _vp(z), int(out is not None), C.byref(has)))
         return z, (n1.value, n2.value)
 
-    def bench_operator(self, op, site, spin, L, nup, ndown, warmup=2, iters=10):
+    def bench_operator(self, op, site, spin, L, nup, ndown, warmup=2, iters=10, basis="hubbard"):
         """(ms per launch, bytes of the byte model) of the operator kernel on resident vectors"""
         ms, by = C.c_double(), C.c_double()
-        check(self._lib.lpp_engine_bench_operator(self._h, _op_id(op), site, spin, L, nup, ndown, warmup, iters, C.byref(ms), C.byref(by)))
+        call = self._lib.lpp_engine_bench_operator_tj if _obs_basis(basis) else self._lib.lpp_engine_bench_operator
+        check(call(self._h, _op_id(op), site, spin, L, nup, ndown, warmup, iters, C.byref(ms), C.byref(by)))
         return ms.value, by.value
 
     # ---- reduced density matrix of the low `split` sites (lpp_rdm.hip) ---------------------------------------
@@ -421,7 +442,7 @@ class LanczosEngine:
 
     def _need_model(self, who):
         if self._model is None:
-            raise _capi.LppError(_capi.LPP_ERR_STATE, "%s needs a single-GPU Hubbard engine set up by assemble_hubbard / setup_hubbard_onthefly" % who)
+            raise _capi.LppError(_capi.LPP_ERR_STATE, "%s needs a single-GPU engine set up by assemble_hubbard / setup_hubbard_onthefly / assemble_tj" % who)
         return self._model
 
     def two_point(self, op, spins=(0, 0), bra=0, ket=0):
@@ -431,7 +452,8 @@ class LanczosEngine:
         L = m["L"]
         res = np.zeros((L, L), self.np_dtype)
         tr = np.zeros(1, self.np_dtype)
-        check(self._lib.lpp_engine_two_point(self._h, _op_id(op), int(spins[0]), int(spins[1]), L, m["nup"], m["ndown"], int(bra), int(ket), _vp(res), _vp(tr)))
+        call = self._lib.lpp_engine_two_point_tj if self._is_tj() else self._lib.lpp_engine_two_point
+        check(call(self._h, _op_id(op), int(spins[0]), int(spins[1]), L, m["nup"], m["ndown"], int(bra), int(ket), _vp(res), _vp(tr)))
         return res, tr[0]
 
     def _sector_engine(self, nup, ndown, solver):
@@ -439,7 +461,10 @@ class LanczosEngine:
         if eng is None:
             m = self._model
             eng = LanczosEngine(**self._ctor)
-            getattr(eng, m["how"])(m["L"], nup, ndown, m["hop"], m["U"], m["V"], ninj=m["ninj"], jcoup=m["jcoup"])
+            if self._is_tj():
+                eng.assemble_tj(m["L"], nup, ndown, m["hop"], m["jpm"], m["jzz"], m["w"], m["potentialV"])
+            else:
+                getattr(eng, m["how"])(m["L"], nup, ndown, m["hop"], m["U"], m["V"], ninj=m["ninj"], jcoup=m["jcoup"])
             self._sectors[(nup, ndown)] = eng
             self.sector_assemblies += 1
         eng.set_solver(**solver)
@@ -462,6 +487,11 @@ class LanczosEngine:
             energy = float(self._energies[0])
         op2 = _TRANSPOSE_CONJUGATE[op]
         diagonal = isite == jsite
+        tj = self._is_tj()
+        parts_call = self._lib.lpp_obs_new_parts_tj if tj else self._lib.lpp_obs_new_parts
+        decomp_call = self._lib.lpp_engine_spectral_decomposition_tj if tj else self._lib.lpp_engine_spectral_decomposition
+        if tj and op in ("splus", "sminus") and spin != _capi.LPP_SPIN_UP:  # before any sector engine is assembled
+            raise _capi.LppError(_capi.LPP_ERR_INVALID, "spectral_function: splus / sminus of the t-J basis take spin UP (the reference ranks words outside the basis otherwise)")
         solver = dict(max_steps=max_steps, min_steps=min_steps, eps=eps, reortho=reortho, save_vectors=0)
         records = []
         for typ in range(4):  # LabeledOperator::numberOfTypes
@@ -470,7 +500,7 @@ class LanczosEngine:
             o = op if (typ & 1) else op2
             oid = OPERATORS[o]
             has, c1, c2 = C.c_int32(), C.c_int32(), C.c_int32()
-            check(self._lib.lpp_obs_new_parts(oid, spin, L, nup, ndown, C.byref(has), C.byref(c1), C.byref(c2)))
+            check(parts_call(oid, spin, L, nup, ndown, C.byref(has), C.byref(c1), C.byref(c2)))
             if not has.value:
                 continue
             n1, n2 = c1.value, c2.value
@@ -479,8 +509,7 @@ class LanczosEngine:
             b = np.zeros(max_steps + 2)
             n, w, st = C.c_int32(), C.c_double(), Stats()
             isign = -1.0 if typ > 1 else 1.0
-            check(self._lib.lpp_engine_spectral_decomposition(self._h, int(state), eng._h, oid, isite, jsite, spin, isign, L, nup, ndown,
-                                                              C.byref(w), C.byref(n), _vp(a), _vp(b), C.byref(st)))
+            check(decomp_call(self._h, int(state), eng._h, oid, isite, jsite, spin, isign, L, nup, ndown, C.byref(w), C.byref(n), _vp(a), _vp(b), C.byref(st)))
             s = -1 if (typ & 1) else 1  # calcSpectral, Engine.h:481-489
             s2 = -1.0 if typ > 1 else 1.0
             if o not in _FERMIONIC:
@@ -557,16 +586,44 @@ def _rdm_dense(blocks, plan, dtype):
     return out
 
 
-def sector_size(L, nup, ndown):
+OBS_BASES = ("hubbard", "tj")
+
+
+def _obs_basis(basis):
+    """True for the t-J basis"""
+    if basis not in OBS_BASES:
+        raise ValueError("unsupported basis %r (one of %s)" % (basis, ", ".join(OBS_BASES)))
+    return basis == "tj"
+
+
+def sector_size(L, nup, ndown, basis="hubbard"):
     from math import comb
+    if _obs_basis(basis):
+        return comb(L, ndown) * comb(L - ndown, nup) if nup + ndown <= L else 0
     return comb(L, nup) * comb(L, ndown)
 
 
-def new_parts(op, spin, L, nup, ndown):
-    """HubbardOneOrbital::hasNewParts: the new (nup, ndown), or None where the reference returns false (LPP_ERR_INVALID for n: it throws)."""
+def new_parts(op, spin, L, nup, ndown, basis="hubbard"):
+    """HubbardOneOrbital::hasNewParts (basis="tj": TjMultiOrb::hasNewParts): the new (nup, ndown), or None where the reference returns false
+    (LPP_ERR_INVALID where it throws: n, and for the t-J model sz)."""
     has, n1, n2 = C.c_int32(), C.c_int32(), C.c_int32()
-    check(_capi.lib().lpp_obs_new_parts(_op_id(op), spin, L, nup, ndown, C.byref(has), C.byref(n1), C.byref(n2)))
+    call = _capi.lib().lpp_obs_new_parts_tj if _obs_basis(basis) else _capi.lib().lpp_obs_new_parts
+    check(call(_op_id(op), spin, L, nup, ndown, C.byref(has), C.byref(n1), C.byref(n2)))
     return (n1.value, n2.value) if has.value else None
+
+
+def operator_plan_tj(op, site, spin, L, nup, ndown):
+    """The expanded plan of one operator application in the t-J basis (lpp_obs_plan_tj): None where the operator leads to no sector, else a dict with
+    the new sector and action[dst] = +-(src + 1) or 0, expanded on the host through the tables and the lookup function the kernel uses."""
+    lib = _capi.lib()
+    oid = _op_id(op)
+    has, n1, n2, n = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+    check(lib.lpp_obs_plan_tj(oid, site, spin, L, nup, ndown, C.byref(has), C.byref(n1), C.byref(n2), C.byref(n), None))
+    if not has.value:
+        return None
+    action = np.zeros(n.value, np.int64)
+    check(lib.lpp_obs_plan_tj(oid, site, spin, L, nup, ndown, C.byref(has), C.byref(n1), C.byref(n2), C.byref(n), _vp(action)))
+    return dict(nup=n1.value, ndown=n2.value, action=action)
 
 
 def operator_plan(op, site, spin, L, nup, ndown):

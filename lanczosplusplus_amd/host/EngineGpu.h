@@ -512,8 +512,8 @@ public:
 		std::vector<ComplexOrRealType> flat(total * total);
 		ComplexOrRealType sum = 0;
 		std::cout << "orbs=" << orbs.first << " " << orbs.second << "\n";
-		lppCheck(lpp_engine_two_point(e, lOperator.id(), (int32_t)spins.first, (int32_t)spins.second, (int32_t)total, (int32_t)parts.first, (int32_t)parts.second,
-		                              (int32_t)braAndKet.first, (int32_t)braAndKet.second, flat.data(), &sum));
+		lppCheck((tjModel() ? lpp_engine_two_point_tj : lpp_engine_two_point)(e, lOperator.id(), (int32_t)spins.first, (int32_t)spins.second, (int32_t)total, (int32_t)parts.first, (int32_t)parts.second,
+		                                                                      (int32_t)braAndKet.first, (int32_t)braAndKet.second, flat.data(), &sum));
 		for (SizeType i = 0; i < total; i++)
 			for (SizeType j = 0; j < total; j++) result(i, j) = flat[i * total + j];
 		std::cout << "MatrixDiagonal = " << sum << "\n";
@@ -549,15 +549,16 @@ public:
 			if (isDiagonal && type > 1) continue;
 			const LabeledOperatorType& lOperator = (type & 1) ? lOperator1 : lOperator2;
 			int32_t has = 0, nup2 = 0, ndown2 = 0;
-			lppCheck(lpp_obs_new_parts(lOperator.id(), (int32_t)spins.first, n, (int32_t)oldParts.first, (int32_t)oldParts.second, &has, &nup2, &ndown2));
+			lppCheck((tjModel() ? lpp_obs_new_parts_tj : lpp_obs_new_parts)(lOperator.id(), (int32_t)spins.first, n, (int32_t)oldParts.first, (int32_t)oldParts.second, &has, &nup2, &ndown2));
 			if (!has) continue;
 			lpp_engine* sector = sectorEngine(nup2, ndown2, params);
 			TridiagonalMatrixType ab;
 			ab.resize(params.steps + 2);
 			double weight = 0;
 			int32_t nsteps = 0;
-			lppCheck(lpp_engine_spectral_decomposition(e, 0, sector, lOperator.id(), isite, jsite, (int32_t)spins.first, type > 1 ? -1.0 : 1.0, n, (int32_t)oldParts.first,
-			                                           (int32_t)oldParts.second, &weight, &nsteps, &ab.a(0), &ab.b(0), nullptr));
+			lppCheck((tjModel() ? lpp_engine_spectral_decomposition_tj : lpp_engine_spectral_decomposition)(e, 0, sector, lOperator.id(), isite, jsite, (int32_t)spins.first,
+			                                                                                                type > 1 ? -1.0 : 1.0, n, (int32_t)oldParts.first, (int32_t)oldParts.second,
+			                                                                                                &weight, &nsteps, &ab.a(0), &ab.b(0), nullptr));
 			ab.a_.resize(nsteps);
 			ab.b_.resize(nsteps);
 			if (std::sqrt(weight) < 1e-10) std::cerr << "spectralFunction: modifVector==0, type=" << type << "\n";
@@ -583,7 +584,7 @@ public:
 
 	void reducedDensityMatrix(std::vector<RdmBlockType>& blocks, SizeType split) const
 	{
-		lpp_engine* e = observableEngine("reducedDensityMatrix");
+		lpp_engine* e = observableEngine("reducedDensityMatrix", true); // (the reference's ReducedDensityMatrix does not know the t-J basis)
 		const int32_t n = (int32_t)model_.geometry().numberOfSites();
 		const typename ModelType::BasisBaseType::PairIntType parts = model_.basis().parts();
 		const int32_t nup = (int32_t)parts.first, ndown = (int32_t)parts.second, cut = (int32_t)split;
@@ -616,34 +617,46 @@ private:
 		if (ind >= vectors_.size()) throw std::runtime_error(std::string("Engine: ") + what + " index exceeds the states computed (Excited=)\n");
 	}
 
-	// the GPU engine that holds the resident states: the Hubbard family on one GPU, a one-sector symmetry, states from the device solver
-	lpp_engine* observableEngine(const char* who) const
+	// the GPU engine that holds the resident states: the Hubbard family or (unless hubbardOnly) the one-orbital t-J model on one GPU, a one-sector
+	// symmetry, states from the device solver
+	lpp_engine* observableEngine(const char* who, bool hubbardOnly = false) const
 	{
-		if (!hubbard() || !hamiltonian_ || !statesResident_)
+		if (hubbardOnly && !hubbard())
 			throw std::runtime_error(std::string(who) + ": needs a Model of the HubbardOneOrbital family solved by the GPU Lanczos (no symmetry sectors, no dense fallback)\n");
+		if (!(hubbard() || tjModel()) || !hamiltonian_ || !statesResident_)
+			throw std::runtime_error(std::string(who) + ": needs a Model of the HubbardOneOrbital family or TjMultiOrb with Orbitals=1 solved by the GPU Lanczos (no symmetry sectors, no dense fallback)\n");
 		return hamiltonian_->engine();
 	}
 
 	const HubbardOneOrbital<ComplexOrRealType>* hubbard() const { return dynamic_cast<const HubbardOneOrbital<ComplexOrRealType>*>(&model_); }
+	const TjMultiOrb<ComplexOrRealType>* tjModel() const { return dynamic_cast<const TjMultiOrb<ComplexOrRealType>*>(&model_); } // (Orbitals=1: the only one the shim builds)
 
 	lpp_engine* sectorEngine(int nup, int ndown, const ParametersForSolverType& params) const
 	{
 		std::unique_ptr<EngineHandle>& slot = sectorEngines_[PairType(nup, ndown)];
 		if (!slot) {
 			const HubbardOneOrbital<ComplexOrRealType>* hub = hubbard();
+			const TjMultiOrb<ComplexOrRealType>* tj = tjModel();
 			const SizeType n = model_.geometry().numberOfSites();
 			std::vector<double> hr(n * n), hi(n * n);
 			for (SizeType k = 0; k < n * n; k++) {
-				hr[k] = LppHost::real(hub->hoppings()[k]);
-				hi[k] = LppHost::imag(hub->hoppings()[k]);
+				hr[k] = LppHost::real(hub ? hub->hoppings()[k] : tj->hoppings()[k]);
+				hi[k] = LppHost::imag(hub ? hub->hoppings()[k] : tj->hoppings()[k]);
 			}
 			lpp_config cfg;
 			lpp_config_default(&cfg);
 			cfg.device = device_;
 			cfg.dtype = LppDtype<ComplexOrRealType>::value;
 			std::unique_ptr<EngineHandle> fresh(new EngineHandle(cfg));
-			lppCheck(lpp_engine_assemble_hubbard_super(fresh->get(), nullptr, (int32_t)n, nup, ndown, hr.data(), sizeof(ComplexOrRealType) == 16 ? hi.data() : nullptr,
-			                                           hub->hubbardU.data(), hub->potentialEffective.data(), hub->coulombCoupling(), hub->jCoupling()));
+			if (hub) {
+				lppCheck(lpp_engine_assemble_hubbard_super(fresh->get(), nullptr, (int32_t)n, nup, ndown, hr.data(), sizeof(ComplexOrRealType) == 16 ? hi.data() : nullptr,
+				                                           hub->hubbardU.data(), hub->potentialEffective.data(), hub->coulombCoupling(), hub->jCoupling()));
+			} else {
+				const std::vector<RealType>& pv = tj->potentialV; // (as describeModel hands it over)
+				const bool havePv = pv.size() >= (size_t)2 * n;
+				lppCheck(lpp_engine_assemble_tj(fresh->get(), (int32_t)n, nup, ndown, hr.data(), sizeof(ComplexOrRealType) == 16 ? hi.data() : nullptr, tj->jpm().data(),
+				                                tj->jzz().data(), tj->w().data(), havePv ? pv.data() : nullptr, havePv ? (int32_t)pv.size() : 0));
+			}
 			slot.swap(fresh);
 			sectorAssemblies_++;
 		}
@@ -700,8 +713,9 @@ private:
 		SpecialSymmetryType& rs = *rs_;
 		InternalProductType& hamiltonian = *hamiltonian_;
 		LanczosSolverType lanczosSolver(hamiltonian, params); // pushes params into the engine
-		const bool keep = hubbard() && rs.sectors() == 1;
-		if (keep) lppCheck(lpp_engine_keep_states(hamiltonian.engine(), (int32_t)nstates));
+		const bool keep = (hubbard() || tjModel()) && rs.sectors() == 1;
+		// (a t-J matrix may be held in the hole-major form, which only the _tj call lets keep its states)
+		if (keep) lppCheck((tjModel() ? lpp_engine_keep_states_tj : lpp_engine_keep_states)(hamiltonian.engine(), (int32_t)nstates));
 		energies_.assign(nstates, 0);
 		vectors_.assign(nstates, VectorType());
 		bool have = false;

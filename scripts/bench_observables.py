@@ -8,8 +8,13 @@
   two_point(c, up)  total seconds
   density of states 16 sites, spin up: total seconds, sector assemblies
   step time         ms_per_step of a spectral decomposition next to the ground-state solve of the same sector's engine
+--model tj: the same figures for the one-orbital t-J model (c128, t = -1, J = 0.4, W = -0.1 as bench.py's t-J workloads; committed for BASELINE
+config 4 -- --lx 5 --ly 4 --nup 9 --ndown 9 -- as profiles/observables_tj_c4.json), the operator kernel being k_obs_apply_tj, plus
+  hubbard_yardstick k_obs_apply's c up in the same process and dtype on the Hubbard sector L = 14 (7, 6): 1.03e7 states, about config 4's
+                    vector bytes.
+A vector of config 4 (148 MB) fits the MI355X's 256 MB Infinity Cache while calib_stream reads 4 GiB from HBM: the stream yardstick is flattered.
 Usage: hipcc --offload-arch=gfx950 -O3 -o scripts/calib_stream scripts/calib_stream.hip
-       python scripts/bench_observables.py [--lx 4 --ly 4 --nup 8 --ndown 8] [--calib-stream scripts/calib_stream] [--spectral-steps 40]"""
+       python scripts/bench_observables.py [--model hubbard|tj] [--lx 4 --ly 4 --nup 8 --ndown 8] [--calib-stream scripts/calib_stream] [--spectral-steps 40]"""
 import argparse
 import json
 import os
@@ -39,6 +44,7 @@ def square(lx, ly, v):
 
 
 CALIB_LINE = "stream16"
+YARD = (14, 7, 6)  # the Hubbard sector of --model tj's yardstick: 1.03e7 states, about config 4's vector bytes
 
 
 def stream_rate(exe):
@@ -61,30 +67,47 @@ def main():
     ap.add_argument("--calib-stream", default="", help="path of the calib_stream binary; empty: no ratio")
     ap.add_argument("--spectral-steps", type=int, default=40)
     ap.add_argument("--gs-steps", type=int, default=200)
+    ap.add_argument("--model", choices=("hubbard", "tj"), default="hubbard")
     a = ap.parse_args()
     L = a.lx * a.ly
+    tj = a.model == "tj"
     hop, U = square(a.lx, a.ly, -1.0), np.full(L, 4.0)
     rate = stream_rate(a.calib_stream) if a.calib_stream else 0.0
-    out = dict(config="%dx%d %dup %ddown U=4" % (a.lx, a.ly, a.nup, a.ndown),
+    out = dict(config=("t-J %dx%d %dup %ddown t=-1 J=0.4 W=-0.1 c128" if tj else "%dx%d %dup %ddown U=4") % (a.lx, a.ly, a.nup, a.ndown),
                stream_rate=dict(tool="scripts/calib_stream.hip", line=CALIB_LINE, kind="read, 16 bytes per lane, 4 GiB", gbs=rate) if rate else None)
-    with LanczosEngine(max_steps=a.gs_steps, save_vectors=0) as e:
+    basis = "tj" if tj else "hubbard"
+    with LanczosEngine(dtype="c128" if tj else "f64", max_steps=a.gs_steps, save_vectors=0) as e:
+
+        def bench(op, site, spin, sites, nup, ndown, basis):
+            ms, by = e.bench_operator(op, site, spin, sites, nup, ndown, warmup=2, iters=10, basis=basis)
+            gbs = by / ms * 1e-6
+            return dict(ms=round(ms, 4), model_bytes=by, gbs=round(gbs, 1), ratio_to_stream=round(gbs / rate, 3) if rate else None)
+
         ops = {}
         for name, (op, spin) in (("c_up", ("c", 0)), ("c_down", ("c", 1)), ("splus", ("splus", 0))):
-            ms, by = e.bench_operator(op, L // 2, spin, L, a.nup, a.ndown, warmup=2, iters=10)
-            gbs = by / ms * 1e-6
-            ops[name] = dict(ms=round(ms, 4), model_bytes=by, gbs=round(gbs, 1), ratio_to_stream=round(gbs / rate, 3) if rate else None)
+            ops[name] = bench(op, L // 2, spin, L, a.nup, a.ndown, basis)
         out["operator"] = ops
+        if tj:
+            yard = bench("c", YARD[0] // 2, 0, YARD[0], YARD[1], YARD[2], "hubbard")
+            yard["sector"] = list(YARD)
+            out["hubbard_yardstick_c_up"] = yard
+            out["c_up_ratio_to_hubbard_kernel"] = round(ops["c_up"]["gbs"] / yard["gbs"], 3)
+            out["note"] = "a 148 MB vector fits the 256 MB Infinity Cache; calib_stream reads 4 GiB from HBM, so ratio_to_stream is flattered"
         t0 = time.time()
-        e.assemble_hubbard(L, a.nup, a.ndown, hop, U)
+        if tj:
+            e.assemble_tj(L, a.nup, a.ndown, hop, square(a.lx, a.ly, 0.4), square(a.lx, a.ly, 0.4), square(a.lx, a.ly, -0.1))
+            out["layout_kernel"] = e.layout()["kernel"]
+        else:
+            e.assemble_hubbard(L, a.nup, a.ndown, hop, U)
         out["assemble_s"] = round(time.time() - t0, 3)
         out["states"] = e.rows()
-        e.keep_states(1)
+        (e.keep_states_tj if tj else e.keep_states)(1)
         t0 = time.time()
         eg, _, st = e.lanczos(1, want_vectors=False)
         out["ground_state"] = dict(E0=eg[0], steps=st["steps"], seconds=round(time.time() - t0, 3))
         t0 = time.time()
         res, tr = e.two_point("c", (0, 0))
-        out["two_point_c_up"] = dict(seconds=round(time.time() - t0, 3), trace=float(tr))
+        out["two_point_c_up"] = dict(seconds=round(time.time() - t0, 3), trace=float(np.real(tr)))
         t0 = time.time()
         recs = []
         for site in range(L):
@@ -92,14 +115,18 @@ def main():
         out["density_of_states"] = dict(sites=L, decompositions=len(recs), seconds=round(time.time() - t0, 3), assemblies=e.sector_assemblies,
                                         spectral_steps=a.spectral_steps, weight_sum_site0=recs[0]["weight"] + recs[1]["weight"])
         # the same kernels: a spectral decomposition and the ground-state solve of the SAME sector engine
-        sector = recs[0]["sector"]
-        eng = e._sectors[sector]
-        rec = e.spectral_function("c", 0, 0, 0, max_steps=a.spectral_steps, eps=0.0)[0]
-        eng.set_solver(max_steps=a.spectral_steps, min_steps=4, eps=0.0, reortho=False, save_vectors=0)
-        _, _, sg = eng.lanczos(1, want_vectors=False)
-        gs_ms = 1e3 * sg["seconds_total"] / max(sg["steps_enqueued"], 1)
-        out["step_time"] = dict(sector=list(sector), spectral_ms_per_step=round(rec["ms_per_step"], 4), ground_state_ms_per_step=round(gs_ms, 4),
-                                ratio=round(rec["ms_per_step"] / gs_ms, 4))
+        def step_time(rec):
+            eng = e._sectors[rec["sector"]]
+            eng.set_solver(max_steps=a.spectral_steps, min_steps=4, eps=0.0, reortho=False, save_vectors=0)
+            _, _, sg = eng.lanczos(1, want_vectors=False)
+            gs_ms = 1e3 * sg["seconds_total"] / max(sg["steps_enqueued"], 1)
+            return dict(sector=list(rec["sector"]), states=eng.rows(), layout_kernel=eng.layout()["kernel"], spectral_ms_per_step=round(rec["ms_per_step"], 4),
+                        ground_state_ms_per_step=round(gs_ms, 4), ratio=round(rec["ms_per_step"] / gs_ms, 4))
+
+        again = e.spectral_function("c", 0, 0, 0, max_steps=a.spectral_steps, eps=0.0)
+        out["step_time"] = step_time(again[0])
+        if tj:  # the N - 1 sector as well: the one a single-hole spectral function runs in
+            out["step_time_c_sector"] = step_time(again[1])
     print(json.dumps(out))
 
 
