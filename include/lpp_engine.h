@@ -482,6 +482,53 @@ lpp_status lpp_engine_two_point_tj(lpp_engine* e, int32_t op, int32_t spin1, int
 lpp_status lpp_engine_spectral_decomposition_tj(lpp_engine* e, int32_t state, lpp_engine* sector, int32_t op, int32_t isite, int32_t jsite, int32_t spin, double isign,
                                                 int32_t nsites, int32_t nup, int32_t ndown, double* weight, int32_t* nsteps, double* a, double* b, lpp_stats* stats);
 
+/* ---- observables of the S = 1/2 Heisenberg basis (entry points added under ABI 7, no struct changes; one GPU; csrc/lpp_obs.hip, csrc/lpp_obs_heis_kernels.h) ----
+ * The same three user-level results for Model=Heisenberg with HeisenbergTwiceS=1 (BasisHeisenberg: the nsites-bit words with szPlusConst set bits, ascending;
+ * a set bit is an up spin; index = position in that list).  Arguments as the _tj calls with nup = szPlusConst; ndown is not read, and a new sector is reported
+ * as (szPlusConst', 0) -- the convention of LPP_BASIS_SPIN_HALF.  Operators n, sz, splus, sminus (BasisHeisenberg.h:123-139, :230-280).  Semantics, as the
+ * reference RUNS:
+ *   - splus / sminus flip the bit, value 1, no sign (the operators are not fermionic, doSignSpSm is BasisBase's 1); the spin argument is not read;
+ *   - n keeps the index, value = bit for LPP_SPIN_UP and 1 - bit for LPP_SPIN_DOWN (a value of 0 leaves the destination untouched);
+ *   - a RAW application of sz (lpp_engine_apply_operator_heis, and so the modified state of lpp_engine_spectral_decomposition_heis, which is what `-g sz`
+ *     decomposes) has the value 1 - 2 bit = -2 S^z (getBraIndex_ :273-276): the spectral weights of `-g sz` are 4 times those of S^z;
+ *   - lpp_engine_two_point_heis builds sz as n_up/2 - n_down/2 = bit - 1/2, the true S^z (Engine.h:568-587);
+ *   - c / cdagger -> LPP_ERR_INVALID from every call (hasNewParts and getBraIndex_ throw);
+ *   - S+ on szPlusConst = nsites and S- on szPlusConst = 0 -> LPP_ERR_INVALID from every call, not "no sector": the reference throws (Heisenberg.h:239);
+ *   - n and sz stay in the sector (needsNewBasis() is false), so lpp_engine_spectral_decomposition_heis accepts them, unlike the two families above: `sector`
+ *     then holds the model's own sector and may be `e` itself (a decomposition does not touch the resident states); the transpose-conjugate of sz is sz,
+ *     all four types apply, a diagonal pair keeps types 0 and 1 and accumulates the state twice; s2 *= s (:483) since the operator is not fermionic.
+ * Spins above 1/2 have no observables in the reference (BasisHeisenberg.h:130, Heisenberg.h:223 throw): these calls describe one bit per site, and resident
+ * states of any other length are refused with LPP_ERR_INVALID.  nsites <= 62; a sector with more than 2^22 runs of equal high part (see the kernel header)
+ * -> LPP_ERR_INVALID.  A partitioned engine is refused (LPP_ERR_STATE), and so is a hole-major t-J engine, which cannot hold a state of this basis.
+ * The plan cache drops its entries past 1 GiB of run tables (24 MB each at 32 sites).  lpp_engine_keep_states is used as it is: the chain form and the general layout
+ * both deliver basis-order vectors.  Every entry point above keeps its behaviour, refusals included. */
+
+/* Heisenberg::hasNewParts (Heisenberg.h:116-134, :218-240), host only: sz -> *has = 0; splus / sminus -> *has = 1 and (szPlusConst +- 1, 0), or LPP_ERR_INVALID
+ * at the two throwing ends; every other operator: the reference throws -> LPP_ERR_INVALID. */
+lpp_status lpp_obs_new_parts_heis(int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t* has, int32_t* nup_new, int32_t* ndown_new);
+
+/* The plan of one operator application, expanded (host only; exposed for the CPU test-suite): action[dst] = +-(src + 1), or 0 where the reference does not
+ * touch destination dst; *n_dst entries.  Expanded through the same run table and the same lookup function (obs_heis_source) the kernel uses.  *low_bits:
+ * the cut of the word in use -- a site below it gathers inside the runs of equal high part, a site at or above it maps run onto run.  action == NULL: sizes
+ * only.  *has is 1 whenever the call succeeds (this model has no "no sector"). */
+lpp_status lpp_obs_plan_heis(int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t* has, int32_t* nup_new, int32_t* ndown_new,
+                             int64_t* n_dst, int32_t* low_bits, int64_t* action);
+
+/* lpp_engine_apply_operator / _host / lpp_engine_bench_operator in the Heisenberg basis: arguments and contracts as those calls (basis-order vectors, 16-byte
+ * aligned destination, one launch on the engine's stream, no sync; the same byte model).  The engine needs no matrix. */
+lpp_status lpp_engine_apply_operator_heis(lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, double factor_re,
+                                          double factor_im, const void* d_src, void* d_dst, int32_t accumulate, int32_t* has);
+lpp_status lpp_engine_apply_operator_heis_host(lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, double factor_re,
+                                               double factor_im, const void* src, void* dst, int32_t accumulate, int32_t* has);
+lpp_status lpp_engine_bench_operator_heis(lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t warmup, int32_t iters,
+                                          double* ms_per_launch, double* model_bytes);
+
+/* lpp_engine_two_point / lpp_engine_spectral_decomposition in the Heisenberg basis, arguments as those calls; one body serves every family. */
+lpp_status lpp_engine_two_point_heis(lpp_engine* e, int32_t op, int32_t spin1, int32_t spin2, int32_t nsites, int32_t nup, int32_t ndown, int32_t bra_state,
+                                     int32_t ket_state, void* result, void* trace);
+lpp_status lpp_engine_spectral_decomposition_heis(lpp_engine* e, int32_t state, lpp_engine* sector, int32_t op, int32_t isite, int32_t jsite, int32_t spin, double isign,
+                                                  int32_t nsites, int32_t nup, int32_t ndown, double* weight, int32_t* nsteps, double* a, double* b, lpp_stats* stats);
+
 /* ---- reduced density matrix of the lattice cut at a site (ABI 7; one GPU; csrc/lpp_rdm.hip) ----
  * The reference's `-r siteForSplit` (ReducedDensityMatrix.h, LanczosDriver1.h:201-206): part A = sites 0 .. split-1 = the low `split` bits of a species'
  * word, rdm(alpha, alpha') = sum over the environment of conj(psi(alpha, beta)) psi(alpha', beta) -- the conjugate on the ROW index, as the

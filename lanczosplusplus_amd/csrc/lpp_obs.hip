@@ -1,4 +1,4 @@
-// lpp_obs.hip -- ground-state observables of the Hubbard product basis and of the one-orbital t-J basis (one body per entry point, ObsBasis) on one GPU: one-site operators applied to device vectors
+// lpp_obs.hip -- ground-state observables of the Hubbard product basis, of the one-orbital t-J basis and of the S = 1/2 Heisenberg basis (one body per entry point, ObsBasis) on one GPU: one-site operators applied to device vectors
 // (Engine::accModifiedState_, reference src/Engine/Engine.h:416-458), the two-point matrix (Engine::twoPoint :266-338) and the modified
 // state + decomposition of one spectral-function type (Engine::spectralFunction :134-206, getModifiedState :494-533, calcSpectral :460-490).
 //
@@ -18,6 +18,7 @@
 #include "lpp_engine_impl.h"
 #include "lpp_obs_kernels.h"
 #include "lpp_obs_tj_kernels.h"
+#include "lpp_obs_heis_kernels.h"
 
 using namespace lpp;
 
@@ -327,6 +328,161 @@ void tj_expand(const ObsTjPlan& P, int64_t* action, int64_t* touched)
 	if (touched) *touched = cnt;
 }
 
+// ---- the S = 1/2 Heisenberg basis (BasisHeisenberg, twiceS = 1; kernel and lookup: lpp_obs_heis_kernels.h) --------------------------------
+
+constexpr int kHeisMaxSites = 62; // as lpp_engine_assemble_heisenberg admits
+constexpr int64_t kHeisMaxRuns = (int64_t)1 << 22; // entries of the run table (24 bytes each)
+
+// C(n, k) in integers for n <= 62 (binom above goes through long double, which is not exact that far)
+int64_t heis_binom(int n, int k)
+{
+	static const std::vector<int64_t> tab = [] {
+		std::vector<int64_t> t((size_t)(kHeisMaxSites + 1) * (kHeisMaxSites + 1), 0);
+		for (int i = 0; i <= kHeisMaxSites; i++) {
+			t[(size_t)i * (kHeisMaxSites + 1)] = 1;
+			for (int j = 1; j <= i; j++) t[(size_t)i * (kHeisMaxSites + 1) + j] = t[(size_t)(i - 1) * (kHeisMaxSites + 1) + j - 1] + (j <= i - 1 ? t[(size_t)(i - 1) * (kHeisMaxSites + 1) + j] : 0);
+		}
+		return t;
+	}();
+	return (n < 0 || n > kHeisMaxSites || k < 0 || k > n) ? 0 : tab[(size_t)n * (kHeisMaxSites + 1) + k];
+}
+
+int64_t heis_sector_size(int L, int m, int) { return (L < 1 || L > kHeisMaxSites || m < 0 || m > L) ? -1 : heis_binom(L, m); }
+
+// Heisenberg::hasNewPartsSplusOrMinus (Heisenberg.h:218-240): szPlusConst +- 1, reported as (szPlusConst', 0).  false: S+ on all ups, S- on all downs --
+// the reference THROWS there (:239), and so it does for every other operator but sz (:129-133); the callers turn false into LPP_ERR_INVALID.
+bool new_parts_heis(int op, int, int L, int m, int, int* n1, int* n2)
+{
+	if (op != LPP_OP_SPLUS && op != LPP_OP_SMINUS) return false;
+	const int m2 = m + (op == LPP_OP_SPLUS ? 1 : -1);
+	if (m2 < 0 || m2 > L) return false;
+	*n1 = m2;
+	*n2 = 0;
+	return true;
+}
+
+// the low part of the word: 12 bits (two 16-bit tables of 4096 entries = 16 KiB of LDS, several workgroups per CU), more for long chains so that the
+// run table stays small
+int heis_low_bits(int L) { return std::min(L, std::max(12, std::min(kObsHeisMaxLow, L - 20))); }
+
+// index of the first word with high part h among the L-bit words of k set bits: the words below h << lb
+int64_t heis_run_start(uint64_t h, int hb, int lb, int k)
+{
+	int64_t n = 0;
+	int c = 0;
+	for (int b = hb - 1; b >= 0; b--)
+		if ((h >> b) & 1) n += heis_binom(b + lb, k - c++);
+	return n;
+}
+
+struct ObsHeisPlan {
+	int m2 = 0, mode = HEIS_RUN, lb = 0;
+	uint32_t bit = 0;
+	int64_t n_src = 0, n_dst = 0;
+	std::vector<ObsHeisRun> runs; // one closing entry at the end
+	std::vector<uint16_t> word, rank; // empty for HEIS_RUN
+};
+
+lpp_status obs_plan_heis(int op, int site, int spin, int L, int m, ObsHeisPlan& P)
+{
+	if (!valid_op(op)) return fail(LPP_ERR_INVALID, "Heisenberg observables: unknown operator (LPP_OP_*)");
+	if (op == LPP_OP_C || op == LPP_OP_CDAGGER) return fail(LPP_ERR_INVALID, "Heisenberg observables: c / cdagger are no operators of this model (the reference throws)");
+	if (spin != LPP_SPIN_UP && spin != LPP_SPIN_DOWN) return fail(LPP_ERR_INVALID, "Heisenberg observables: spin must be LPP_SPIN_UP or LPP_SPIN_DOWN");
+	if (site < 0 || site >= L || heis_sector_size(L, m, 0) < 0) return fail(LPP_ERR_INVALID, "Heisenberg observables: bad sites / site / sector (szPlusConst <= sites <= 62)");
+	P = ObsHeisPlan();
+	P.m2 = m;
+	int dummy = 0;
+	if (needs_new_basis(op) && !new_parts_heis(op, spin, L, m, 0, &P.m2, &dummy))
+		return fail(LPP_ERR_INVALID, "Heisenberg observables: S+ to all ups or S- to all downs (the reference throws)");
+	P.n_src = heis_binom(L, m);
+	P.n_dst = heis_binom(L, P.m2);
+	const int lb = P.lb = heis_low_bits(L), hb = L - lb;
+	const bool high = site >= lb, flip = needs_new_basis(op);
+	const uint64_t hbit = high ? 1ull << (site - lb) : 0;
+	if (!high) {
+		P.bit = 1u << site;
+		P.mode = (op == LPP_OP_SPLUS) ? HEIS_FLIP_SET : (op == LPP_OP_SMINUS) ? HEIS_FLIP_CLEAR : (op == LPP_OP_SZ) ? HEIS_SZ : (spin == LPP_SPIN_UP) ? HEIS_TEST_SET : HEIS_TEST_CLEAR;
+	}
+	// the non-empty runs: high parts whose popcount leaves 0 .. lb set bits to the low part, ascending
+	const int p_lo = std::max(0, P.m2 - lb), p_hi = std::min(hb, P.m2);
+	int64_t nruns = 0;
+	for (int p = p_lo; p <= p_hi && nruns <= kHeisMaxRuns; p++) nruns += heis_binom(hb, p);
+	if (nruns > kHeisMaxRuns) return fail(LPP_ERR_INVALID, "Heisenberg observables: the sector has more than 2^22 runs of equal high part (the run table's limit)");
+	std::vector<uint64_t> highs;
+	highs.reserve((size_t)nruns);
+	if (hb <= 22) {
+		for (uint64_t h = 0; h < (1ull << hb); h++) {
+			const int p = __builtin_popcountll(h);
+			if (p >= p_lo && p <= p_hi) highs.push_back(h);
+		}
+	} else { // few of very many: class by class (the next word of the same popcount, BasisOneSpin.h:53-61), then sorted
+		for (int p = p_lo; p <= p_hi; p++) {
+			uint64_t h = (p == 0) ? 0 : ((1ull << p) - 1);
+			for (int64_t i = 0, cnt = heis_binom(hb, p); i < cnt; i++) {
+				highs.push_back(h);
+				if (p > 0 && i + 1 < cnt) {
+					const uint64_t c = h & (~h + 1), r = h + c;
+					h = (((r ^ h) >> 2) / c) | r;
+				}
+			}
+		}
+		std::sort(highs.begin(), highs.end());
+	}
+	std::vector<int32_t> base((size_t)lb + 2, 0); // word[base[p] + r]
+	for (int p = 0; p <= lb; p++) base[(size_t)p + 1] = base[(size_t)p] + (int32_t)heis_binom(lb, p);
+	P.runs.reserve(highs.size() + 1);
+	int64_t acc = 0;
+	for (const uint64_t h : highs) {
+		const int ph = __builtin_popcountll(h), pl = P.m2 - ph;
+		ObsHeisRun R { acc, 0, pl, base[(size_t)pl] };
+		const bool set = (h & hbit) != 0;
+		if (flip) { // the destination (bra) has the bit set for splus and clear for sminus; the source is the word with the bit flipped, in sector m
+			const bool want = op == LPP_OP_SPLUS;
+			if (high) {
+				if (set == want) R.src = heis_run_start(h ^ hbit, hb, lb, m) + 1;
+			} else if (want ? pl >= 1 : pl <= lb - 1) { // (otherwise no low word of the run has the bit as asked)
+				R.src = heis_run_start(h, hb, lb, m) + 1;
+			}
+		} else if (!high) {
+			R.src = acc + 1;
+		} else if (op == LPP_OP_SZ) {
+			R.src = set ? -(acc + 1) : acc + 1;
+		} else if (set == (spin == LPP_SPIN_UP)) {
+			R.src = acc + 1;
+		}
+		P.runs.push_back(R);
+		acc += heis_binom(lb, pl);
+	}
+	if (acc != P.n_dst) return fail(LPP_ERR_INVALID, "Heisenberg observables: internal error, the runs do not add up to the sector");
+	P.runs.push_back(ObsHeisRun { P.n_dst, 0, 0, 0 });
+	if (P.mode != HEIS_RUN) {
+		P.word.resize((size_t)1 << lb);
+		P.rank.resize((size_t)1 << lb);
+		std::vector<int32_t> seen((size_t)lb + 1, 0);
+		for (uint32_t w = 0; w < (1u << lb); w++) {
+			const int p = __builtin_popcount(w);
+			P.rank[w] = (uint16_t)seen[(size_t)p];
+			P.word[(size_t)(base[(size_t)p] + seen[(size_t)p]++)] = (uint16_t)w;
+		}
+	}
+	return LPP_OK;
+}
+
+// the plan expanded as the kernel walks it (action may be null); *touched = destinations with a source
+void heis_expand(const ObsHeisPlan& P, int64_t* action, int64_t* touched)
+{
+	int64_t cnt = 0;
+	for (size_t k = 0; k + 1 < P.runs.size(); k++) {
+		const ObsHeisRun& R = P.runs[k];
+		for (int64_t r = 0, len = P.runs[k + 1].dst0 - R.dst0; r < len; r++) {
+			const int64_t s = obs_heis_source(P.mode, R, r, P.bit, P.word.data(), P.rank.data());
+			if (action) action[R.dst0 + r] = s;
+			cnt += (s != 0);
+		}
+	}
+	if (touched) *touched = cnt;
+}
+
 // ---- device side ---------------------------------------------------------------------------------------------------------------------
 
 struct DevPlan {
@@ -340,12 +496,19 @@ struct DevPlan {
 	int32_t* tj_hi = nullptr;
 	uint16_t* tj_lo = nullptr;
 	int tj_nhi = 0, tj_nlo = 0;
+	// the Heisenberg basis: the plan (the run table and the low-word tables dropped after the upload) and its three device tables
+	ObsHeisPlan heis;
+	ObsHeisRun* hs_runs = nullptr;
+	uint16_t *hs_word = nullptr, *hs_rank = nullptr;
+	int64_t hs_nruns = 0;
+	int hs_nlo = 0;
 };
 
-enum { BASIS_HUBBARD = 0, BASIS_TJ = 1 };
+enum { BASIS_HUBBARD = 0, BASIS_TJ = 1, BASIS_HEIS = 2 };
 typedef std::tuple<int, int, int, int, int, int, int> PlanKey; // basis, operator, site, spin, sites, nup, ndown
 struct ObsCache {
 	std::map<PlanKey, DevPlan> plans;
+	size_t heis_bytes = 0; // device bytes of the Heisenberg run tables held (24 MB each at 32 sites)
 };
 
 inline bool multi(const lpp_engine* e) { return e->has_comm && e->comm.nranks > 1; }
@@ -359,13 +522,15 @@ lpp_status refuse(const lpp_engine* e, const char* who, bool hole_major_ok = fal
 
 void free_plan(DevPlan& D)
 {
-	for (void* p : { (void*)D.tu, (void*)D.td, (void*)D.tj_dn, (void*)D.tj_pat, (void*)D.tj_hi, (void*)D.tj_lo })
+	for (void* p : { (void*)D.tu, (void*)D.td, (void*)D.tj_dn, (void*)D.tj_pat, (void*)D.tj_hi, (void*)D.tj_lo, (void*)D.hs_runs, (void*)D.hs_word, (void*)D.hs_rank })
 		if (p) (void)hipFree(p);
 	D.tu = D.td = nullptr;
 	D.tj_dn = nullptr;
 	D.tj_pat = nullptr;
 	D.tj_hi = nullptr;
 	D.tj_lo = nullptr;
+	D.hs_runs = nullptr;
+	D.hs_word = D.hs_rank = nullptr;
 }
 
 // one table to the device (at least one element is allocated); the host copy is dropped
@@ -381,22 +546,32 @@ template <typename V> hipError_t upload(V** dst, std::vector<V>& src)
 // needs no model for lpp_engine_apply_operator -- so the cache is bounded: a density of states or a two-point matrix uses at most 2 * sites entries
 // per operator; past kMaxPlans entries everything is dropped and rebuilt on demand.  The returned pointer is valid until the next get_plan.
 constexpr size_t kMaxPlans = 256;
+constexpr size_t kMaxHeisBytes = (size_t)1 << 30; // ... or past 1 GiB of Heisenberg run tables: a two-point sweep over 32 sites holds 0.8 GB of them
 
 lpp_status get_plan(lpp_engine* e, int basis, int op, int site, int spin, int L, int nup, int ndn, const DevPlan** out)
 {
 	if (!e->obs) e->obs = new ObsCache();
 	ObsCache* C = (ObsCache*)e->obs;
+	if (basis == BASIS_HEIS) ndn = 0; // not read: one entry per sector
 	const PlanKey key(basis, op, site, spin, L, nup, ndn);
 	auto it = C->plans.find(key);
 	if (it == C->plans.end()) {
 		DevPlan D;
-		bool has = false;
-		lpp_status st = (basis == BASIS_TJ) ? obs_plan_tj(op, site, spin, L, nup, ndn, &has, D.tj) : obs_plan(op, site, spin, L, nup, ndn, &has, D.host);
+		bool has = basis == BASIS_HEIS; // (this basis has no "no sector": the plan refuses where the reference throws)
+		lpp_status st = (basis == BASIS_HEIS) ? obs_plan_heis(op, site, spin, L, nup, D.heis)
+		                : (basis == BASIS_TJ) ? obs_plan_tj(op, site, spin, L, nup, ndn, &has, D.tj)
+		                                      : obs_plan(op, site, spin, L, nup, ndn, &has, D.host);
 		if (st != LPP_OK) return st;
 		D.has = has;
 		if (has) {
 			hipError_t err = hipSuccess;
-			if (basis == BASIS_TJ) {
+			if (basis == BASIS_HEIS) {
+				D.hs_nruns = (int64_t)D.heis.runs.size() - 1;
+				D.hs_nlo = (int)D.heis.word.size();
+				err = upload(&D.hs_runs, D.heis.runs);
+				if (err == hipSuccess) err = upload(&D.hs_word, D.heis.word);
+				if (err == hipSuccess) err = upload(&D.hs_rank, D.heis.rank);
+			} else if (basis == BASIS_TJ) {
 				D.tj_nhi = (int)D.tj.hi_base.size();
 				D.tj_nlo = (int)D.tj.lo_rank.size();
 				err = upload(&D.tj_dn, D.tj.dn);
@@ -416,11 +591,14 @@ lpp_status get_plan(lpp_engine* e, int basis, int op, int site, int spin, int L,
 				HIP_TRY(err);
 			}
 		}
-		if (C->plans.size() >= kMaxPlans) {
+		const size_t run_bytes = (basis == BASIS_HEIS) ? sizeof(ObsHeisRun) * (size_t)(D.hs_nruns + 1) : 0;
+		if (C->plans.size() >= kMaxPlans || C->heis_bytes + run_bytes > kMaxHeisBytes) {
 			HIP_TRY(hipStreamSynchronize(e->stream)); // launches that still read the old tables
 			for (auto& kv : C->plans) free_plan(kv.second);
 			C->plans.clear();
+			C->heis_bytes = 0;
 		}
+		C->heis_bytes += run_bytes;
 		it = C->plans.emplace(key, D).first;
 	}
 	*out = &it->second;
@@ -500,7 +678,34 @@ lpp_status apply_dev_tj(lpp_engine* e, int op, int site, int spin, int L, int nu
 	return LPP_OK;
 }
 
-// Everything the entry points below need to know about a basis: they are written once and run for both families.
+// the same in the S = 1/2 Heisenberg basis (k_obs_apply_heis); nup = szPlusConst, ndown is not read
+lpp_status apply_dev_heis(lpp_engine* e, int op, int site, int spin, int L, int nup, int, double fr, double fi, const void* d_src, void* d_dst, bool acc, bool* has,
+                          int64_t* n_dst)
+{
+	const DevPlan* D = nullptr;
+	lpp_status st = get_plan(e, BASIS_HEIS, op, site, spin, L, nup, 0, &D);
+	if (st != LPP_OK) return st;
+	*has = true;
+	const ObsHeisPlan& P = D->heis;
+	const int64_t nd = P.n_dst;
+	if (n_dst) *n_dst = nd;
+	if ((st = check_vectors(e, fi, d_src, d_dst)) != LPP_OK) return st;
+	ObsHeisArgs A { D->hs_runs, D->hs_word, D->hs_rank, P.mode, D->hs_nlo, P.bit, D->hs_nruns, nd, fr, fi };
+	const int64_t units = e->is_complex ? nd : (nd + 1) / 2;
+	const int g = obs_grid(e, units);
+	const size_t lds = obs_heis_lds_bytes(A.mode, A.nlo);
+	if (e->is_complex) {
+		if (acc) k_obs_apply_heis<true, true><<<g, kObsBlock, lds, e->stream>>>((double*)d_dst, (const double*)d_src, A);
+		else k_obs_apply_heis<true, false><<<g, kObsBlock, lds, e->stream>>>((double*)d_dst, (const double*)d_src, A);
+	} else {
+		if (acc) k_obs_apply_heis<false, true><<<g, kObsBlock, lds, e->stream>>>((double*)d_dst, (const double*)d_src, A);
+		else k_obs_apply_heis<false, false><<<g, kObsBlock, lds, e->stream>>>((double*)d_dst, (const double*)d_src, A);
+	}
+	HIP_TRY(hipGetLastError());
+	return LPP_OK;
+}
+
+// Everything the entry points below need to know about a basis: they are written once and run for every family.
 struct ObsBasis {
 	int id;
 	bool hole_major_ok; // a hole-major t-J engine is admitted (its resident states and start vectors pass through S.perm)
@@ -508,9 +713,11 @@ struct ObsBasis {
 	bool (*new_parts)(int op, int spin, int L, int nup, int ndn, int* n1, int* n2);
 	lpp_status (*apply)(lpp_engine* e, int op, int site, int spin, int L, int nup, int ndn, double fr, double fi, const void* d_src, void* d_dst, bool acc, bool* has,
 	                    int64_t* n_dst);
+	bool no_sector_throws; // new_parts == false is where the reference throws: LPP_ERR_INVALID instead of "no such sector"
 };
-const ObsBasis kHubbard { BASIS_HUBBARD, false, hubbard_sector_size, new_parts, apply_dev };
-const ObsBasis kTj { BASIS_TJ, true, tj_sector_size, new_parts_tj, apply_dev_tj };
+const ObsBasis kHubbard { BASIS_HUBBARD, false, hubbard_sector_size, new_parts, apply_dev, false };
+const ObsBasis kTj { BASIS_TJ, true, tj_sector_size, new_parts_tj, apply_dev_tj, false };
+const ObsBasis kHeis { BASIS_HEIS, false, heis_sector_size, new_parts_heis, apply_dev_heis, true };
 
 // sizes of the plan's two sectors, and (touched != null) the destinations that have a source
 lpp_status plan_sizes(lpp_engine* e, const ObsBasis& B, int op, int site, int spin, int L, int nup, int ndn, bool* has, int64_t* ns, int64_t* nd, int64_t* touched)
@@ -520,7 +727,10 @@ lpp_status plan_sizes(lpp_engine* e, const ObsBasis& B, int op, int site, int sp
 	if (st != LPP_OK) return st;
 	*has = D->has;
 	if (!D->has) return LPP_OK;
-	if (B.id == BASIS_TJ) {
+	if (B.id == BASIS_HEIS) {
+		*ns = D->heis.n_src;
+		*nd = D->heis.n_dst;
+	} else if (B.id == BASIS_TJ) {
 		*ns = D->tj.n_up_src * D->tj.n_dn_src;
 		*nd = D->tj.n_up_dst * D->tj.n_dn_dst;
 	} else {
@@ -529,7 +739,11 @@ lpp_status plan_sizes(lpp_engine* e, const ObsBasis& B, int op, int site, int sp
 	}
 	if (!touched) return LPP_OK;
 	bool hh = false;
-	if (B.id == BASIS_TJ) {
+	if (B.id == BASIS_HEIS) { // sz touches every destination; splus / sminus / n those with the site's bit as asked: the other L - 1 bits are free
+		const int m2 = D->heis.m2;
+		const bool bit_set = op == LPP_OP_SPLUS || (op == LPP_OP_N && spin == LPP_SPIN_UP);
+		*touched = (op == LPP_OP_SZ) ? D->heis.n_dst : heis_binom(L - 1, bit_set ? m2 - 1 : m2);
+	} else if (B.id == BASIS_TJ) {
 		ObsTjPlan P;
 		if ((st = obs_plan_tj(op, site, spin, L, nup, ndn, &hh, P)) != LPP_OK) return st;
 		tj_expand(P, nullptr, touched);
@@ -675,7 +889,8 @@ lpp_status two_point_body(const ObsBasis& Bs, const std::string& who, lpp_engine
 	int nup2 = nup, ndn2 = ndown;
 	if (needs_new_basis(op)) {
 		if (spin1 != spin2) return fail(LPP_ERR_INVALID, "twoPoint: no support yet for off-diagonal spin when needs new basis"); // Engine.h:276-282
-		if (!Bs.new_parts(op, spin1, L, nup, ndown, &nup2, &ndn2)) return LPP_OK; // no such sector: the matrix keeps its fill
+		if (!Bs.new_parts(op, spin1, L, nup, ndown, &nup2, &ndn2)) // no such sector: the matrix keeps its fill
+			return Bs.no_sector_throws ? fail(LPP_ERR_INVALID, who + ": the operator leads to no sector, and the reference throws for this model") : LPP_OK;
 	}
 	const int64_t ndst = Bs.sector_size(L, nup2, ndn2);
 	if (ndst <= 0) return LPP_OK;
@@ -877,6 +1092,41 @@ lpp_status lpp_obs_plan_tj(int32_t op, int32_t site, int32_t spin, int32_t nsite
 	return LPP_OK;
 }
 
+lpp_status lpp_obs_new_parts_heis(int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t* has, int32_t* nup_new, int32_t* ndown_new)
+{
+	(void)ndown;
+	if (!has) return fail(LPP_ERR_INVALID, "lpp_obs_new_parts_heis: null argument");
+	*has = 0;
+	if (spin != LPP_SPIN_UP && spin != LPP_SPIN_DOWN) return fail(LPP_ERR_INVALID, "lpp_obs_new_parts_heis: bad spin");
+	if (heis_sector_size(nsites, nup, 0) < 0) return fail(LPP_ERR_INVALID, "lpp_obs_new_parts_heis: bad sector");
+	if (op == LPP_OP_SZ) return LPP_OK; // Heisenberg.h:122-123
+	if (op != LPP_OP_SPLUS && op != LPP_OP_SMINUS) return fail(LPP_ERR_INVALID, "hasNewParts: unsupported operator"); // the reference throws (:129-133)
+	int n1 = 0, n2 = 0;
+	if (!new_parts_heis(op, spin, nsites, nup, 0, &n1, &n2)) return fail(LPP_ERR_INVALID, "hasNewParts: S+ to all ups or S- to all downs"); // the reference throws (:239)
+	*has = 1;
+	if (nup_new) *nup_new = n1;
+	if (ndown_new) *ndown_new = n2;
+	return LPP_OK;
+}
+
+lpp_status lpp_obs_plan_heis(int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t* has, int32_t* nup_new, int32_t* ndown_new,
+                             int64_t* n_dst, int32_t* low_bits, int64_t* action)
+{
+	(void)ndown;
+	if (!has) return fail(LPP_ERR_INVALID, "lpp_obs_plan_heis: null argument");
+	*has = 0;
+	ObsHeisPlan P;
+	lpp_status st = obs_plan_heis(op, site, spin, nsites, nup, P);
+	if (st != LPP_OK) return st;
+	*has = 1;
+	if (nup_new) *nup_new = P.m2;
+	if (ndown_new) *ndown_new = 0;
+	if (n_dst) *n_dst = P.n_dst;
+	if (low_bits) *low_bits = P.lb;
+	if (action) heis_expand(P, action, nullptr);
+	return LPP_OK;
+}
+
 lpp_status lpp_continued_fraction(int32_t n, const double* a, const double* b, double eg, double weight, double sigma, double z_re, double z_im, double* out)
 {
 	if (n < 1 || !a || !b || !out) return fail(LPP_ERR_INVALID, "lpp_continued_fraction: bad argument");
@@ -900,6 +1150,12 @@ lpp_status lpp_engine_apply_operator_tj(lpp_engine* e, int32_t op, int32_t site,
 	return apply_operator_body(kTj, "lpp_engine_apply_operator_tj", e, op, site, spin, nsites, nup, ndown, factor_re, factor_im, d_src, d_dst, accumulate, has);
 }
 
+lpp_status lpp_engine_apply_operator_heis(lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, double factor_re,
+                                          double factor_im, const void* d_src, void* d_dst, int32_t accumulate, int32_t* has)
+{
+	return apply_operator_body(kHeis, "lpp_engine_apply_operator_heis", e, op, site, spin, nsites, nup, ndown, factor_re, factor_im, d_src, d_dst, accumulate, has);
+}
+
 lpp_status lpp_engine_apply_operator_host(lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, double factor_re,
                                           double factor_im, const void* src, void* dst, int32_t accumulate, int32_t* has)
 {
@@ -911,6 +1167,12 @@ lpp_status lpp_engine_apply_operator_tj_host(lpp_engine* e, int32_t op, int32_t 
 	return apply_operator_host_body(kTj, "lpp_engine_apply_operator_tj_host", e, op, site, spin, nsites, nup, ndown, factor_re, factor_im, src, dst, accumulate, has);
 }
 
+lpp_status lpp_engine_apply_operator_heis_host(lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, double factor_re,
+                                               double factor_im, const void* src, void* dst, int32_t accumulate, int32_t* has)
+{
+	return apply_operator_host_body(kHeis, "lpp_engine_apply_operator_heis_host", e, op, site, spin, nsites, nup, ndown, factor_re, factor_im, src, dst, accumulate, has);
+}
+
 lpp_status lpp_engine_bench_operator(lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t warmup, int32_t iters,
                                      double* ms_per_launch, double* model_bytes)
 {
@@ -920,6 +1182,12 @@ lpp_status lpp_engine_bench_operator_tj(lpp_engine* e, int32_t op, int32_t site,
                                         double* ms_per_launch, double* model_bytes)
 {
 	return bench_operator_body(kTj, "lpp_engine_bench_operator_tj", e, op, site, spin, nsites, nup, ndown, warmup, iters, ms_per_launch, model_bytes);
+}
+
+lpp_status lpp_engine_bench_operator_heis(lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t warmup, int32_t iters,
+                                          double* ms_per_launch, double* model_bytes)
+{
+	return bench_operator_body(kHeis, "lpp_engine_bench_operator_heis", e, op, site, spin, nsites, nup, ndown, warmup, iters, ms_per_launch, model_bytes);
 }
 
 lpp_status lpp_engine_keep_states(lpp_engine* e, int32_t k)
@@ -982,6 +1250,12 @@ lpp_status lpp_engine_two_point_tj(lpp_engine* e, int32_t op, int32_t spin1, int
 	return two_point_body(kTj, "lpp_engine_two_point_tj", e, op, spin1, spin2, nsites, nup, ndown, bra_state, ket_state, result, trace);
 }
 
+lpp_status lpp_engine_two_point_heis(lpp_engine* e, int32_t op, int32_t spin1, int32_t spin2, int32_t nsites, int32_t nup, int32_t ndown, int32_t bra_state,
+                                     int32_t ket_state, void* result, void* trace)
+{
+	return two_point_body(kHeis, "lpp_engine_two_point_heis", e, op, spin1, spin2, nsites, nup, ndown, bra_state, ket_state, result, trace);
+}
+
 lpp_status lpp_engine_spectral_decomposition(lpp_engine* e, int32_t state, lpp_engine* sector, int32_t op, int32_t isite, int32_t jsite, int32_t spin, double isign,
                                              int32_t nsites, int32_t nup, int32_t ndown, double* weight, int32_t* nsteps, double* a, double* b, lpp_stats* stats)
 {
@@ -991,6 +1265,12 @@ lpp_status lpp_engine_spectral_decomposition_tj(lpp_engine* e, int32_t state, lp
                                                 int32_t nsites, int32_t nup, int32_t ndown, double* weight, int32_t* nsteps, double* a, double* b, lpp_stats* stats)
 {
 	return spectral_body(kTj, "lpp_engine_spectral_decomposition_tj", e, state, sector, op, isite, jsite, spin, isign, nsites, nup, ndown, weight, nsteps, a, b, stats);
+}
+
+lpp_status lpp_engine_spectral_decomposition_heis(lpp_engine* e, int32_t state, lpp_engine* sector, int32_t op, int32_t isite, int32_t jsite, int32_t spin, double isign,
+                                                  int32_t nsites, int32_t nup, int32_t ndown, double* weight, int32_t* nsteps, double* a, double* b, lpp_stats* stats)
+{
+	return spectral_body(kHeis, "lpp_engine_spectral_decomposition_heis", e, state, sector, op, isite, jsite, spin, isign, nsites, nup, ndown, weight, nsteps, a, b, stats);
 }
 
 } // extern "C"

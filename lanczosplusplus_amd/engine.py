@@ -187,6 +187,7 @@ class LanczosEngine:
         f = None if field is None else np.ascontiguousarray(field, np.float64)
         # ReducedDensityMatrix::unpackHeisenberg reads one bit per site: S = 1/2 only
         self._basis = ("spin_half", L, szPlusConst, 0) if twiceS == 1 else "the reduced density matrix of a Heisenberg model needs twiceS = 1 (one bit per site)"
+        self._set_model_heisenberg(L, szPlusConst, jpm, jzz, field, twiceS, anisotropy)
         if twiceS == 1 and anisotropy is None:
             check(self._lib.lpp_engine_assemble_heisenberg(self._h, L, szPlusConst, _vp(_mat(jpm, L)), _vp(_mat(jzz, L)),
                                                            _vp(f), 0 if f is None else len(f)))
@@ -322,8 +323,29 @@ class LanczosEngine:
             eng.close()
         self._sectors = {}
 
+    def _set_model_heisenberg(self, L, szPlusConst, jpm, jzz, field, twiceS, anisotropy):
+        """nup = szPlusConst, ndown = 0: the sector as the _heis calls and LPP_BASIS_SPIN_HALF take it"""
+        self._model = dict(how="assemble_heisenberg", L=L, nup=szPlusConst, ndown=0, jpm=np.array(jpm, copy=True), jzz=np.array(jzz, copy=True),
+                           field=None if field is None else np.array(field, copy=True), twiceS=twiceS,
+                           anisotropy=None if anisotropy is None else np.array(anisotropy, copy=True))
+        for eng in self._sectors.values():
+            eng.close()
+        self._sectors = {}
+
     def _is_tj(self):
         return self._model is not None and self._model["how"] == "assemble_tj"
+
+    def _is_heis(self, who=None):
+        """True on an engine set up by assemble_heisenberg; with `who`, spins above 1/2 raise as the reference throws (BasisHeisenberg.h:130, Heisenberg.h:223)"""
+        if self._model is None or self._model["how"] != "assemble_heisenberg":
+            return False
+        if who is not None and self._model["twiceS"] != 1:
+            raise _capi.LppError(_capi.LPP_ERR_INVALID, "%s: the observables of a Heisenberg model need twiceS = 1 (the reference throws for higher spins)" % who)
+        return True
+
+    def _obs_call(self, stem):
+        """the entry point of the engine's model: stem, stem_tj or stem_heis"""
+        return getattr(self._lib, stem + ("_tj" if self._is_tj() else "_heis" if self._is_heis() else ""))
 
     def keep_states_tj(self, k=1):
         """keep_states that also accepts a hole-major t-J engine (lpp_engine_keep_states_tj): state(k) is then the host Ritz vector bit for bit"""
@@ -349,13 +371,17 @@ class LanczosEngine:
     def apply_operator(self, op, site, spin, L, nup, ndown, src, factor=1.0, out=None, basis="hubbard"):
         """Engine::accModifiedState_ (Engine.h:416-458) on the GPU: returns (z, (nup', ndown')) with z[bra] += factor*sign*value*src[ket],
         z starting from `out` (new sector's length) or from zero; (None, None) where the operator leads to no sector.  src: host vector of the
-        (nup, ndown) sector in the basis order.  basis: "hubbard" (BasisHubbardLanczos) or "tj" (BasisTjMultiOrbLanczos, one orbital)."""
+        (nup, ndown) sector in the basis order.  basis: "hubbard" (BasisHubbardLanczos), "tj" (BasisTjMultiOrbLanczos, one orbital) or "spin_half"
+        (BasisHeisenberg with twiceS = 1: nup = szPlusConst, ndown is not read; sz is the reference's raw 1 - 2 bit = -2 S^z, and where the reference
+        throws -- c, cdagger, S+ on all ups, S- on all downs -- LppError is raised)."""
         oid = _op_id(op)
         tj = _obs_basis(basis)
         src = np.ascontiguousarray(src, self.np_dtype)
         has, n1, n2 = C.c_int32(), C.c_int32(), C.c_int32()
         nu, nd = C.c_int64(1), C.c_int64()
-        if tj:
+        if basis == "spin_half":
+            check(self._lib.lpp_obs_plan_heis(oid, site, spin, L, nup, ndown, C.byref(has), C.byref(n1), C.byref(n2), C.byref(nd), None, None))
+        elif tj:
             check(self._lib.lpp_obs_plan_tj(oid, site, spin, L, nup, ndown, C.byref(has), C.byref(n1), C.byref(n2), C.byref(nd), None))
         else:
             check(self._lib.lpp_obs_plan(oid, site, spin, L, nup, ndown, C.byref(has), C.byref(n1), C.byref(n2), C.byref(nu), C.byref(nd), None, None))
@@ -371,14 +397,15 @@ class LanczosEngine:
             if len(z) != n:
                 raise ValueError("out does not have the length of sector (%d, %d)" % (n1.value, n2.value))
         f = complex(factor)
-        call = self._lib.lpp_engine_apply_operator_tj_host if tj else self._lib.lpp_engine_apply_operator_host
+        call = getattr(self._lib, "lpp_engine_apply_operator" + _OBS_SUFFIX[basis] + "_host")
         check(call(self._h, oid, site, spin, L, nup, ndown, f.real, f.imag, _vp(src), _vp(z), int(out is not None), C.byref(has)))
         return z, (n1.value, n2.value)
 
     def bench_operator(self, op, site, spin, L, nup, ndown, warmup=2, iters=10, basis="hubbard"):
         """(ms per launch, bytes of the byte model) of the operator kernel on resident vectors"""
         ms, by = C.c_double(), C.c_double()
-        call = self._lib.lpp_engine_bench_operator_tj if _obs_basis(basis) else self._lib.lpp_engine_bench_operator
+        _obs_basis(basis)
+        call = getattr(self._lib, "lpp_engine_bench_operator" + _OBS_SUFFIX[basis])
         check(call(self._h, _op_id(op), site, spin, L, nup, ndown, warmup, iters, C.byref(ms), C.byref(by)))
         return ms.value, by.value
 
@@ -442,17 +469,18 @@ class LanczosEngine:
 
     def _need_model(self, who):
         if self._model is None:
-            raise _capi.LppError(_capi.LPP_ERR_STATE, "%s needs a single-GPU engine set up by assemble_hubbard / setup_hubbard_onthefly / assemble_tj" % who)
+            raise _capi.LppError(_capi.LPP_ERR_STATE, "%s needs a single-GPU engine set up by assemble_hubbard / setup_hubbard_onthefly / assemble_tj / assemble_heisenberg" % who)
         return self._model
 
     def two_point(self, op, spins=(0, 0), bra=0, ket=0):
         """Engine::twoPoint (Engine.h:266-338): (L x L matrix, trace) with result[i, j] = (A_j^{spins[1]} bra) . (A_i^{spins[0]} ket) for resident
         states bra / ket (keep_states before lanczos); -100 everywhere where the operator leads to no sector."""
         m = self._need_model("two_point")
+        self._is_heis("two_point")
         L = m["L"]
         res = np.zeros((L, L), self.np_dtype)
         tr = np.zeros(1, self.np_dtype)
-        call = self._lib.lpp_engine_two_point_tj if self._is_tj() else self._lib.lpp_engine_two_point
+        call = self._obs_call("lpp_engine_two_point")
         check(call(self._h, _op_id(op), int(spins[0]), int(spins[1]), L, m["nup"], m["ndown"], int(bra), int(ket), _vp(res), _vp(tr)))
         return res, tr[0]
 
@@ -463,6 +491,8 @@ class LanczosEngine:
             eng = LanczosEngine(**self._ctor)
             if self._is_tj():
                 eng.assemble_tj(m["L"], nup, ndown, m["hop"], m["jpm"], m["jzz"], m["w"], m["potentialV"])
+            elif self._is_heis():
+                eng.assemble_heisenberg(m["L"], nup, m["jpm"], m["jzz"], field=m["field"], twiceS=1, anisotropy=m["anisotropy"])
             else:
                 getattr(eng, m["how"])(m["L"], nup, ndown, m["hop"], m["U"], m["V"], ninj=m["ninj"], jcoup=m["jcoup"])
             self._sectors[(nup, ndown)] = eng
@@ -477,9 +507,10 @@ class LanczosEngine:
         ms_per_step and `assemblies` = sector Hamiltonians assembled by this engine so far (the N+-1 engines are kept, keyed by (nup, ndown)).
         max_steps .. reortho: ParametersForSolver(io, "Spectral").  energy: Eg, default the lowest eigenvalue of the last lanczos()."""
         m = self._need_model("spectral_function")
+        heis = self._is_heis("spectral_function")
         L, nup, ndown = m["L"], m["nup"], m["ndown"]
         _op_id(op)
-        if op in ("n", "sz"):  # before any sector engine is assembled
+        if op in ("n", "sz") and not heis:  # before any sector engine is assembled (Heisenberg: needsNewBasis() is false, the new basis is the model's own)
             raise _capi.LppError(_capi.LPP_ERR_INVALID, "spectral_function: operators that stay in the sector (n, sz) are not supported")
         if energy is None:
             if self._energies is None:
@@ -488,8 +519,8 @@ class LanczosEngine:
         op2 = _TRANSPOSE_CONJUGATE[op]
         diagonal = isite == jsite
         tj = self._is_tj()
-        parts_call = self._lib.lpp_obs_new_parts_tj if tj else self._lib.lpp_obs_new_parts
-        decomp_call = self._lib.lpp_engine_spectral_decomposition_tj if tj else self._lib.lpp_engine_spectral_decomposition
+        parts_call = self._obs_call("lpp_obs_new_parts")
+        decomp_call = self._obs_call("lpp_engine_spectral_decomposition")
         if tj and op in ("splus", "sminus") and spin != _capi.LPP_SPIN_UP:  # before any sector engine is assembled
             raise _capi.LppError(_capi.LPP_ERR_INVALID, "spectral_function: splus / sminus of the t-J basis take spin UP (the reference ranks words outside the basis otherwise)")
         solver = dict(max_steps=max_steps, min_steps=min_steps, eps=eps, reortho=reortho, save_vectors=0)
@@ -499,8 +530,9 @@ class LanczosEngine:
                 continue
             o = op if (typ & 1) else op2
             oid = OPERATORS[o]
-            has, c1, c2 = C.c_int32(), C.c_int32(), C.c_int32()
-            check(parts_call(oid, spin, L, nup, ndown, C.byref(has), C.byref(c1), C.byref(c2)))
+            has, c1, c2 = C.c_int32(1), C.c_int32(nup), C.c_int32(ndown)
+            if not (heis and o in ("n", "sz")):  # (those stay in the sector, which gets an engine of its own: self keeps its solver parameters)
+                check(parts_call(oid, spin, L, nup, ndown, C.byref(has), C.byref(c1), C.byref(c2)))
             if not has.value:
                 continue
             n1, n2 = c1.value, c2.value
@@ -586,7 +618,8 @@ def _rdm_dense(blocks, plan, dtype):
     return out
 
 
-OBS_BASES = ("hubbard", "tj")
+OBS_BASES = ("hubbard", "tj", "spin_half")
+_OBS_SUFFIX = {"hubbard": "", "tj": "_tj", "spin_half": "_heis"}  # of the C entry points
 
 
 def _obs_basis(basis):
@@ -600,14 +633,18 @@ def sector_size(L, nup, ndown, basis="hubbard"):
     from math import comb
     if _obs_basis(basis):
         return comb(L, ndown) * comb(L - ndown, nup) if nup + ndown <= L else 0
+    if basis == "spin_half":
+        return comb(L, nup)
     return comb(L, nup) * comb(L, ndown)
 
 
 def new_parts(op, spin, L, nup, ndown, basis="hubbard"):
-    """HubbardOneOrbital::hasNewParts (basis="tj": TjMultiOrb::hasNewParts): the new (nup, ndown), or None where the reference returns false
-    (LPP_ERR_INVALID where it throws: n, and for the t-J model sz)."""
+    """HubbardOneOrbital::hasNewParts (basis="tj": TjMultiOrb::hasNewParts, basis="spin_half": Heisenberg::hasNewParts with nup = szPlusConst, the new
+    sector as (szPlusConst', 0)): the new (nup, ndown), or None where the reference returns false (LPP_ERR_INVALID where it throws: n, for the t-J model
+    sz, for the Heisenberg model c, cdagger, S+ on all ups and S- on all downs)."""
     has, n1, n2 = C.c_int32(), C.c_int32(), C.c_int32()
-    call = _capi.lib().lpp_obs_new_parts_tj if _obs_basis(basis) else _capi.lib().lpp_obs_new_parts
+    _obs_basis(basis)
+    call = getattr(_capi.lib(), "lpp_obs_new_parts" + _OBS_SUFFIX[basis])
     check(call(_op_id(op), spin, L, nup, ndown, C.byref(has), C.byref(n1), C.byref(n2)))
     return (n1.value, n2.value) if has.value else None
 
@@ -624,6 +661,19 @@ def operator_plan_tj(op, site, spin, L, nup, ndown):
     action = np.zeros(n.value, np.int64)
     check(lib.lpp_obs_plan_tj(oid, site, spin, L, nup, ndown, C.byref(has), C.byref(n1), C.byref(n2), C.byref(n), _vp(action)))
     return dict(nup=n1.value, ndown=n2.value, action=action)
+
+
+def operator_plan_heis(op, site, spin, L, szPlusConst):
+    """The expanded plan of one operator application in the S = 1/2 Heisenberg basis (lpp_obs_plan_heis): a dict with the new sector (nup = szPlusConst',
+    ndown = 0), action[dst] = +-(src + 1) or 0, expanded on the host through the run table and the lookup function the kernel uses, and lb: the cut of
+    the word (a site below it gathers inside the runs of equal high part, a site at or above it maps run onto run).  Raises where the reference throws."""
+    lib = _capi.lib()
+    oid = _op_id(op)
+    has, n1, n2, n, lb = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64(), C.c_int32()
+    check(lib.lpp_obs_plan_heis(oid, site, spin, L, szPlusConst, 0, C.byref(has), C.byref(n1), C.byref(n2), C.byref(n), C.byref(lb), None))
+    action = np.zeros(n.value, np.int64)
+    check(lib.lpp_obs_plan_heis(oid, site, spin, L, szPlusConst, 0, C.byref(has), C.byref(n1), C.byref(n2), C.byref(n), C.byref(lb), _vp(action)))
+    return dict(nup=n1.value, ndown=n2.value, action=action, lb=lb.value)
 
 
 def operator_plan(op, site, spin, L, nup, ndown):

@@ -508,11 +508,11 @@ public:
 		checkBraOrKet("ket", braAndKet.second);
 		const SizeType total = model_.geometry().numberOfSites();
 		if (result.n_row() != total || result.n_col() != total) result.resize(total, total);
-		const typename ModelType::BasisBaseType::PairIntType parts = model_.basis().parts();
+		const PairType parts = obsParts();
 		std::vector<ComplexOrRealType> flat(total * total);
 		ComplexOrRealType sum = 0;
 		std::cout << "orbs=" << orbs.first << " " << orbs.second << "\n";
-		lppCheck((tjModel() ? lpp_engine_two_point_tj : lpp_engine_two_point)(e, lOperator.id(), (int32_t)spins.first, (int32_t)spins.second, (int32_t)total, (int32_t)parts.first, (int32_t)parts.second,
+		lppCheck((heisModel() ? lpp_engine_two_point_heis : tjModel() ? lpp_engine_two_point_tj : lpp_engine_two_point)(e, lOperator.id(), (int32_t)spins.first, (int32_t)spins.second, (int32_t)total, (int32_t)parts.first, (int32_t)parts.second,
 		                                                                      (int32_t)braAndKet.first, (int32_t)braAndKet.second, flat.data(), &sum));
 		for (SizeType i = 0; i < total; i++)
 			for (SizeType j = 0; j < total; j++) result(i, j) = flat[i * total + j];
@@ -538,25 +538,27 @@ public:
 		if (orbs.first != 0 || orbs.second != 0) throw std::runtime_error("spectralFunction: one orbital only\n");
 		lpp_engine* e = observableEngine("spectralFunction");
 		const LabeledOperatorType lOperator2 = lOperator1.transposeConjugate();
-		// refused before any sector engine is assembled
-		if (!lOperator1.needsNewBasis()) throw std::runtime_error("spectralFunction: operators that stay in the sector (n, sz) are not supported\n");
+		// refused before any sector engine is assembled; the Heisenberg model decomposes them in its own sector (needsNewBasis() is false, Engine.h:172-174)
+		if (!lOperator1.needsNewBasis() && !heisModel()) throw std::runtime_error("spectralFunction: operators that stay in the sector (n, sz) are not supported\n");
 		const int n = (int)model_.geometry().numberOfSites();
 		if (isite < 0 || jsite < 0 || isite >= n || jsite >= n) throw std::runtime_error("spectralFunction: site out of range\n");
 		const bool isDiagonal = (isite == jsite);
-		const typename ModelType::BasisBaseType::PairIntType oldParts = model_.basis().parts();
+		const PairType oldParts = obsParts();
 		ParametersForSolverType params(io_, "Spectral");
 		for (SizeType type = 0; type < lOperator1.numberOfTypes(); ++type) {
 			if (isDiagonal && type > 1) continue;
 			const LabeledOperatorType& lOperator = (type & 1) ? lOperator1 : lOperator2;
-			int32_t has = 0, nup2 = 0, ndown2 = 0;
-			lppCheck((tjModel() ? lpp_obs_new_parts_tj : lpp_obs_new_parts)(lOperator.id(), (int32_t)spins.first, n, (int32_t)oldParts.first, (int32_t)oldParts.second, &has, &nup2, &ndown2));
+			int32_t has = 1, nup2 = (int32_t)oldParts.first, ndown2 = (int32_t)oldParts.second;
+			if (lOperator.needsNewBasis())
+				lppCheck((heisModel() ? lpp_obs_new_parts_heis : tjModel() ? lpp_obs_new_parts_tj : lpp_obs_new_parts)(lOperator.id(), (int32_t)spins.first, n, (int32_t)oldParts.first,
+				                                                                                                      (int32_t)oldParts.second, &has, &nup2, &ndown2));
 			if (!has) continue;
 			lpp_engine* sector = sectorEngine(nup2, ndown2, params);
 			TridiagonalMatrixType ab;
 			ab.resize(params.steps + 2);
 			double weight = 0;
 			int32_t nsteps = 0;
-			lppCheck((tjModel() ? lpp_engine_spectral_decomposition_tj : lpp_engine_spectral_decomposition)(e, 0, sector, lOperator.id(), isite, jsite, (int32_t)spins.first,
+			lppCheck((heisModel() ? lpp_engine_spectral_decomposition_heis : tjModel() ? lpp_engine_spectral_decomposition_tj : lpp_engine_spectral_decomposition)(e, 0, sector, lOperator.id(), isite, jsite, (int32_t)spins.first,
 			                                                                                                type > 1 ? -1.0 : 1.0, n, (int32_t)oldParts.first, (int32_t)oldParts.second,
 			                                                                                                &weight, &nsteps, &ab.a(0), &ab.b(0), nullptr));
 			ab.a_.resize(nsteps);
@@ -617,19 +619,32 @@ private:
 		if (ind >= vectors_.size()) throw std::runtime_error(std::string("Engine: ") + what + " index exceeds the states computed (Excited=)\n");
 	}
 
-	// the GPU engine that holds the resident states: the Hubbard family or (unless hubbardOnly) the one-orbital t-J model on one GPU, a one-sector
-	// symmetry, states from the device solver
+	// the GPU engine that holds the resident states: the Hubbard family or (unless hubbardOnly) the one-orbital t-J model or the S = 1/2 Heisenberg model
+	// on one GPU, a one-sector symmetry, states from the device solver
 	lpp_engine* observableEngine(const char* who, bool hubbardOnly = false) const
 	{
 		if (hubbardOnly && !hubbard())
 			throw std::runtime_error(std::string(who) + ": needs a Model of the HubbardOneOrbital family solved by the GPU Lanczos (no symmetry sectors, no dense fallback)\n");
-		if (!(hubbard() || tjModel()) || !hamiltonian_ || !statesResident_)
-			throw std::runtime_error(std::string(who) + ": needs a Model of the HubbardOneOrbital family or TjMultiOrb with Orbitals=1 solved by the GPU Lanczos (no symmetry sectors, no dense fallback)\n");
+		if (!(hubbard() || tjModel() || heisModel()) || !hamiltonian_ || !statesResident_)
+			throw std::runtime_error(std::string(who) + ": needs a Model of the HubbardOneOrbital family, TjMultiOrb with Orbitals=1 or Heisenberg with HeisenbergTwiceS=1 and no AnisotropyD solved by the GPU Lanczos (no symmetry sectors, no dense fallback)\n");
 		return hamiltonian_->engine();
 	}
 
 	const HubbardOneOrbital<ComplexOrRealType>* hubbard() const { return dynamic_cast<const HubbardOneOrbital<ComplexOrRealType>*>(&model_); }
 	const TjMultiOrb<ComplexOrRealType>* tjModel() const { return dynamic_cast<const TjMultiOrb<ComplexOrRealType>*>(&model_); } // (Orbitals=1: the only one the shim builds)
+	// S = 1/2 only: the reference throws for higher spins (BasisHeisenberg.h:130, Heisenberg.h:223).  An input with AnisotropyD is not admitted here yet:
+	// its sector engines would come from the any-spin assembler, and no driver test covers that (the Python layer does both, and is tested)
+	const Heisenberg<ComplexOrRealType>* heisModel() const
+	{
+		const Heisenberg<ComplexOrRealType>* hs = dynamic_cast<const Heisenberg<ComplexOrRealType>*>(&model_);
+		return (hs && hs->twiceTheSpin() == 1 && hs->anisotropy.empty()) ? hs : nullptr;
+	}
+	// the sector as the observable entry points take it: (nup, ndown), for the Heisenberg model (szPlusConst, 0) -- its parts() are (twiceS, szPlusConst)
+	PairType obsParts() const
+	{
+		const typename ModelType::BasisBaseType::PairIntType parts = model_.basis().parts();
+		return heisModel() ? PairType(parts.second, 0) : PairType(parts.first, parts.second);
+	}
 
 	lpp_engine* sectorEngine(int nup, int ndown, const ParametersForSolverType& params) const
 	{
@@ -637,9 +652,10 @@ private:
 		if (!slot) {
 			const HubbardOneOrbital<ComplexOrRealType>* hub = hubbard();
 			const TjMultiOrb<ComplexOrRealType>* tj = tjModel();
+			const Heisenberg<ComplexOrRealType>* hs = heisModel();
 			const SizeType n = model_.geometry().numberOfSites();
 			std::vector<double> hr(n * n), hi(n * n);
-			for (SizeType k = 0; k < n * n; k++) {
+			for (SizeType k = 0; k < n * n && !hs; k++) {
 				hr[k] = LppHost::real(hub ? hub->hoppings()[k] : tj->hoppings()[k]);
 				hi[k] = LppHost::imag(hub ? hub->hoppings()[k] : tj->hoppings()[k]);
 			}
@@ -648,7 +664,10 @@ private:
 			cfg.device = device_;
 			cfg.dtype = LppDtype<ComplexOrRealType>::value;
 			std::unique_ptr<EngineHandle> fresh(new EngineHandle(cfg));
-			if (hub) {
+			if (hs) {
+				const double* field = hs->magneticField.empty() ? nullptr : hs->magneticField.data();
+				lppCheck(lpp_engine_assemble_heisenberg(fresh->get(), (int32_t)n, nup, hs->jpm().data(), hs->jzz().data(), field, (int32_t)hs->magneticField.size()));
+			} else if (hub) {
 				lppCheck(lpp_engine_assemble_hubbard_super(fresh->get(), nullptr, (int32_t)n, nup, ndown, hr.data(), sizeof(ComplexOrRealType) == 16 ? hi.data() : nullptr,
 				                                           hub->hubbardU.data(), hub->potentialEffective.data(), hub->coulombCoupling(), hub->jCoupling()));
 			} else {
@@ -713,7 +732,7 @@ private:
 		SpecialSymmetryType& rs = *rs_;
 		InternalProductType& hamiltonian = *hamiltonian_;
 		LanczosSolverType lanczosSolver(hamiltonian, params); // pushes params into the engine
-		const bool keep = (hubbard() || tjModel()) && rs.sectors() == 1;
+		const bool keep = (hubbard() || tjModel() || heisModel()) && rs.sectors() == 1;
 		// (a t-J matrix may be held in the hole-major form, which only the _tj call lets keep its states)
 		if (keep) lppCheck((tjModel() ? lpp_engine_keep_states_tj : lpp_engine_keep_states)(hamiltonian.engine(), (int32_t)nstates));
 		energies_.assign(nstates, 0);

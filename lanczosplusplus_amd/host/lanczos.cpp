@@ -4,7 +4,7 @@
 //   lanczos -f input.inp [-p precision] [-d device] [-g operator] [-c operator] [-s "s1,s2;..."] [-r siteForSplit]
 // SolverOptions=useComplex selects complex<double> (lanczos.cpp:194-226).  -c prints the two-point matrix of the ground state, -g writes the
 // continued fractions of the spectral function for the site pairs the input names (TSPSites, TSPCenter=, DoAllPairs=,
-// ComputeDensityOfStates=) into <input basename><counter>.comb (LanczosDriver1.h:81-199; Hubbard family and TjMultiOrb with Orbitals=1, one GPU).  -r prints the reduced density
+// ComputeDensityOfStates=) into <input basename><counter>.comb (LanczosDriver1.h:81-199; Hubbard family, TjMultiOrb with Orbitals=1 and Heisenberg with HeisenbergTwiceS=1 -- where `-g sz` decomposes the reference's raw 1 - 2 bit = -2 S^z --, one GPU).  -r prints the reduced density
 // matrix of the lattice cut at a site, its eigenvectors, eigenvalues and the entanglement entropy (LanczosDriver1.h:201-206).  -m, -M are out of scope.
 #include <getopt.h>
 #include <sys/stat.h>

@@ -13,8 +13,15 @@ config 4 -- --lx 5 --ly 4 --nup 9 --ndown 9 -- as profiles/observables_tj_c4.jso
   hubbard_yardstick k_obs_apply's c up in the same process and dtype on the Hubbard sector L = 14 (7, 6): 1.03e7 states, about config 4's
                     vector bytes.
 A vector of config 4 (148 MB) fits the MI355X's 256 MB Infinity Cache while calib_stream reads 4 GiB from HBM: the stream yardstick is flattered.
+--model heisenberg --sites L --m M: the S = 1/2 Heisenberg chain (f64, J = 1, open ends as BASELINE config 3; committed for (28;14) and (32;16) as
+profiles/observables_heis_L28.json / _L32.json), the operator kernel being k_obs_apply_heis:
+  operator          splus at site 0 (a gather inside the runs of equal high part), splus at site L-1 (run onto run), sz at site 0 and at site L-1
+  hubbard_yardstick k_obs_apply's c up on config 2 (16 sites, 8 up 8 down) in the same process, and `bar`: every launch's share of the stream rate
+                    against half of the share that yardstick gets
+  unless --operators-only: two_point(sz), two_point(splus), the -g sz set of one centre site (L pairs) and the step times as above
 Usage: hipcc --offload-arch=gfx950 -O3 -o scripts/calib_stream scripts/calib_stream.hip
-       python scripts/bench_observables.py [--model hubbard|tj] [--lx 4 --ly 4 --nup 8 --ndown 8] [--calib-stream scripts/calib_stream] [--spectral-steps 40]"""
+       python scripts/bench_observables.py [--model hubbard|tj] [--lx 4 --ly 4 --nup 8 --ndown 8] [--calib-stream scripts/calib_stream] [--spectral-steps 40]
+       python scripts/bench_observables.py --model heisenberg --sites 28 --m 14 [--operators-only] [--calib-stream scripts/calib_stream]"""
 import argparse
 import json
 import os
@@ -58,6 +65,68 @@ def stream_rate(exe):
     return float(m.group(1))
 
 
+def chain(L, v):
+    m = np.zeros((L, L))
+    for i in range(L - 1):
+        m[i, i + 1] = m[i + 1, i] = v
+    return m
+
+
+def heisenberg(a, rate):
+    """--model heisenberg: one JSON line"""
+    L, m = a.sites, a.m
+    out = dict(config="Heisenberg S=1/2 chain L=%d szPlusConst=%d J=1 open f64" % (L, m),
+               stream_rate=dict(tool="scripts/calib_stream.hip", line=CALIB_LINE, kind="read, 16 bytes per lane, 4 GiB", gbs=rate) if rate else None)
+    with LanczosEngine(max_steps=a.gs_steps, save_vectors=0) as e:
+
+        def bench(op, site, spin, sites, nup, ndown, basis):
+            ms, by = e.bench_operator(op, site, spin, sites, nup, ndown, warmup=2, iters=10, basis=basis)
+            gbs = by / ms * 1e-6
+            return dict(ms=round(ms, 4), model_bytes=by, gbs=round(gbs, 1), ratio_to_stream=round(gbs / rate, 3) if rate else None)
+
+        ops = {}
+        for name, (op, site) in (("splus_site0", ("splus", 0)), ("splus_last_site", ("splus", L - 1)), ("sz_site0", ("sz", 0)), ("sz_last_site", ("sz", L - 1))):
+            ops[name] = bench(op, site, 0, L, m, 0, "spin_half")
+        out["operator"] = ops
+        yard = bench("c", 8, 0, 16, 8, 8, "hubbard")
+        yard["sector"] = [16, 8, 8]
+        out["hubbard_yardstick_c_up"] = yard
+        worst = min(ops, key=lambda k: ops[k]["gbs"])
+        out["bar"] = dict(rule="every launch >= half of the Hubbard c up launch's share of the stream rate (same run)", worst=worst,
+                          worst_over_yardstick=round(ops[worst]["gbs"] / yard["gbs"], 3), met=bool(ops[worst]["gbs"] >= 0.5 * yard["gbs"]))
+        if a.operators_only:
+            print(json.dumps(out))
+            return
+        j = chain(L, 1.0)
+        t0 = time.time()
+        e.assemble_heisenberg(L, m, j, j)
+        out["assemble_s"] = round(time.time() - t0, 3)
+        out["layout_kernel"] = e.layout()["kernel"]
+        out["states"] = e.rows()
+        e.keep_states(1)
+        t0 = time.time()
+        eg, _, st = e.lanczos(1, want_vectors=False)
+        out["ground_state"] = dict(E0=eg[0], steps=st["steps"], seconds=round(time.time() - t0, 3))
+        for op in ("sz", "splus"):
+            t0 = time.time()
+            res, tr = e.two_point(op, (0, 0))
+            out["two_point_" + op] = dict(seconds=round(time.time() - t0, 3), trace=float(tr))
+        t0 = time.time()
+        recs = []
+        for site in range(L):
+            recs += e.spectral_function("sz", L // 2, site, 0, max_steps=a.spectral_steps, eps=0.0)
+        out["spectral_sz_centre_set"] = dict(pairs=L, decompositions=len(recs), seconds=round(time.time() - t0, 3), assemblies=e.sector_assemblies,
+                                             spectral_steps=a.spectral_steps, note="-g sz decomposes the raw 1 - 2 bit = -2 S^z")
+        again = e.spectral_function("sz", 0, 0, 0, max_steps=a.spectral_steps, eps=0.0)
+        eng = e._sectors[again[0]["sector"]]
+        eng.set_solver(max_steps=a.spectral_steps, min_steps=4, eps=0.0, reortho=False, save_vectors=0)
+        _, _, sg = eng.lanczos(1, want_vectors=False)
+        gs_ms = 1e3 * sg["seconds_total"] / max(sg["steps_enqueued"], 1)
+        out["step_time"] = dict(sector=list(again[0]["sector"]), states=eng.rows(), layout_kernel=eng.layout()["kernel"], spectral_ms_per_step=round(again[0]["ms_per_step"], 4),
+                                ground_state_ms_per_step=round(gs_ms, 4), ratio=round(again[0]["ms_per_step"] / gs_ms, 4))
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lx", type=int, default=4)
@@ -67,12 +136,17 @@ def main():
     ap.add_argument("--calib-stream", default="", help="path of the calib_stream binary; empty: no ratio")
     ap.add_argument("--spectral-steps", type=int, default=40)
     ap.add_argument("--gs-steps", type=int, default=200)
-    ap.add_argument("--model", choices=("hubbard", "tj"), default="hubbard")
+    ap.add_argument("--model", choices=("hubbard", "tj", "heisenberg"), default="hubbard")
+    ap.add_argument("--sites", type=int, default=28, help="--model heisenberg: chain length")
+    ap.add_argument("--m", type=int, default=14, help="--model heisenberg: szPlusConst")
+    ap.add_argument("--operators-only", action="store_true", help="--model heisenberg: the operator launches and the yardstick only (no matrix)")
     a = ap.parse_args()
     L = a.lx * a.ly
     tj = a.model == "tj"
     hop, U = square(a.lx, a.ly, -1.0), np.full(L, 4.0)
     rate = stream_rate(a.calib_stream) if a.calib_stream else 0.0
+    if a.model == "heisenberg":
+        return heisenberg(a, rate)
     out = dict(config=("t-J %dx%d %dup %ddown t=-1 J=0.4 W=-0.1 c128" if tj else "%dx%d %dup %ddown U=4") % (a.lx, a.ly, a.nup, a.ndown),
                stream_rate=dict(tool="scripts/calib_stream.hip", line=CALIB_LINE, kind="read, 16 bytes per lane, 4 GiB", gbs=rate) if rate else None)
     basis = "tj" if tj else "hubbard"
