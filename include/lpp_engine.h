@@ -572,6 +572,57 @@ lpp_status lpp_engine_state_reduced_density_matrix(lpp_engine* e, int32_t state,
 lpp_status lpp_engine_bench_rdm(lpp_engine* e, int32_t basis, int32_t nsites, int32_t nup, int32_t ndown, int32_t split, int32_t warmup, int32_t iters, double* ms_per_call,
                                 double* macs);
 
+/* ---- products of one-site operators: many-point correlations and measure brackets (entry points added under ABI 7, no struct changes; one GPU;
+ *      Hubbard product basis; csrc/lpp_obs.hip, csrc/lpp_obs_string_kernels.h) ----
+ * The reference's -M "op?site?spin;..." (Engine::manyPoint, Engine.h:341-389) and -m "<gs|op;op;...|gs>" (Engine::measure :208-249 through
+ * ModelBase::rahulMethod, ModelBase.h:89-141, RahulOperator.h).  A string of 1 .. 16 operators is composed ON THE HOST into one pair of per-species
+ * tables in the format of lpp_obs_plan, so <bra| string |ket> is one pass that reads bra and ket once and writes no vector.
+ * LPP_STRING_MANY_POINT: ops[] are LPP_OP_* with site and spin; ops[0] acts first on the ket; each step is accModifiedState_ with factor 1 (bra index
+ *   and value of getBraIndex, doSignGf for c / cdagger -- the down species drops the up parity for site > 0 --, doSignSpSm for splus / sminus, sz with
+ *   value +1 / -1 / absent); the sector walks by hasNewParts (lpp_obs_new_parts) step by step, the (0,0) refusal included: no sector -> *has = 0.
+ *   DEVIATION: n and sz act in the CURRENT sector.  The reference's getNeededBasis (:397-400) hands them the basis of the ORIGINAL sector even after
+ *   earlier operators have left it and ranks words of another particle number in it (a wrong index or a throw).  Strings whose n / sz occur only
+ *   while the sector is the original one are reference-exact.
+ * LPP_STRING_MEASURE: ops[] are LPP_OP_C (flags[] bit 0: transpose = c-dagger), LPP_OP_N, LPP_OP_SZ, LPP_OP_IDENTITY; spins[] is the dof (0 up, 1 down);
+ *   ops[nops-1] acts first; n keeps occupied bits; sz is -1/2 on an occupied and +1/2 on an empty bit of that species (RahulOperator.h:38-40 as
+ *   written); c flips the bit, sign ProgramGlobals::doSign(word after the flip, site) times (-1)^(up electrons) for dof = down.  The result lives in the
+ *   original sector: a string that does not conserve both numbers -> LPP_ERR_INVALID.
+ * An engine holding a hole-major t-J model -> LPP_ERR_INVALID naming the model; the Python layer and the C++ shim, which know the model of every
+ * engine they set up, refuse t-J and Heisenberg engines the same way.  A partitioned engine -> LPP_ERR_STATE. */
+enum { LPP_OP_IDENTITY = 0 };
+enum { LPP_STRING_MANY_POINT = 0, LPP_STRING_MEASURE = 1 };
+
+/* The plan of one string (host only; exposed for the CPU test-suite): *has, the final parts, *scale (the product of the 1/2 magnitudes of measure's
+ * sz), the two composed tables -- table[destination species rank] = +-(source species rank + 1), 0 = none, every sign carried by the entries --
+ * and, for many-point, the sz entries: sz[3k .. 3k+2] = (site, flip_up, flip_down), factor (bit_up(src, site) ^ flip_up) - (bit_down(src, site) ^ flip_down)
+ * on the SOURCE words, a destination with a zero factor is not reached.  table_up[*n_up_dst], table_down[*n_down_dst], sz[3 * 16]; NULL: not written. */
+lpp_status lpp_obs_string_plan(int32_t convention, int32_t nops, const int32_t* ops, const int32_t* sites, const int32_t* spins, const int32_t* flags, int32_t nsites,
+                               int32_t nup, int32_t ndown, int32_t* has, int32_t* nup_new, int32_t* ndown_new, double* scale, int64_t* n_up_dst, int64_t* n_down_dst,
+                               int32_t* table_up, int32_t* table_down, int32_t* nsz, int32_t* sz);
+
+/* z (+)= factor * string src on device vectors of the engine's GPU and dtype in the basis order, contracts of lpp_engine_apply_operator (16-byte aligned
+ * destination; accumulate = 0 writes 0 where the string does not reach).  One launch of k_obs_string_apply, then a stream sync (the tables are the
+ * call's own).  *has = 0: no such sector, nothing was done; otherwise the final parts.  _host: host vectors, copied in and out. */
+lpp_status lpp_engine_apply_string(lpp_engine* e, int32_t convention, int32_t nops, const int32_t* ops, const int32_t* sites, const int32_t* spins, const int32_t* flags,
+                                   int32_t nsites, int32_t nup, int32_t ndown, double factor_re, double factor_im, const void* d_src, void* d_dst, int32_t accumulate,
+                                   int32_t* has, int32_t* nup_new, int32_t* ndown_new);
+lpp_status lpp_engine_apply_string_host(lpp_engine* e, int32_t convention, int32_t nops, const int32_t* ops, const int32_t* sites, const int32_t* spins, const int32_t* flags,
+                                        int32_t nsites, int32_t nup, int32_t ndown, double factor_re, double factor_im, const void* src, void* dst, int32_t accumulate,
+                                        int32_t* has, int32_t* nup_new, int32_t* ndown_new);
+
+/* result[2 s], result[2 s + 1] = re, im of conj(bra) . (string_s ket) for resident states of sector (nup, ndown); string s is entries offsets[s] ..
+ * offsets[s+1] - 1 of ops / sites / spins / flags (flags may be NULL).  A string that leads to no sector or ends in another sector gives 0 and launches
+ * nothing (Engine.h:364, :382-383).  The others go 8 per launch through k_obs_string_dot (bra read once for the 8) and a fixed-order reduction: a
+ * value does not depend on the batch it is computed in, and two calls return the same bits.  _host: bra and ket are host vectors of the sector. */
+lpp_status lpp_engine_many_point(lpp_engine* e, int32_t convention, int32_t nstrings, const int64_t* offsets, const int32_t* ops, const int32_t* sites, const int32_t* spins,
+                                 const int32_t* flags, int32_t nsites, int32_t nup, int32_t ndown, int32_t bra_state, int32_t ket_state, double* result);
+lpp_status lpp_engine_many_point_host(lpp_engine* e, int32_t convention, int32_t nstrings, const int64_t* offsets, const int32_t* ops, const int32_t* sites, const int32_t* spins,
+                                      const int32_t* flags, int32_t nsites, int32_t nup, int32_t ndown, const void* bra, const void* ket, double* result);
+/* Time `iters` launches (bracket kernel + reduction) of ONE batch of 1 .. 8 strings on zeroed vectors with HIP events;
+ * model_bytes = sizeof(value) * (N + sum over the strings of the destinations they reach): bra once, one ket element per string and destination. */
+lpp_status lpp_engine_bench_string_dot(lpp_engine* e, int32_t convention, int32_t nstrings, const int64_t* offsets, const int32_t* ops, const int32_t* sites, const int32_t* spins,
+                                       const int32_t* flags, int32_t nsites, int32_t nup, int32_t ndown, int32_t warmup, int32_t iters, double* ms_per_launch, double* model_bytes);
+
 #ifdef __cplusplus
 }
 #endif

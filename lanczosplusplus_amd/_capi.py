@@ -16,6 +16,8 @@ LPP_F64, LPP_C128 = 0, 1
 LPP_SPMV_AUTO, LPP_SPMV_ROWGROUP, LPP_SPMV_SLICED, LPP_SPMV_WINDOW = 0, 1, 2, 3
 LPP_OP_C, LPP_OP_SZ, LPP_OP_CDAGGER, LPP_OP_N, LPP_OP_SPLUS, LPP_OP_SMINUS = 1, 2, 3, 4, 5, 6
 LPP_SPIN_UP, LPP_SPIN_DOWN = 0, 1
+LPP_OP_IDENTITY = 0
+LPP_STRING_MANY_POINT, LPP_STRING_MEASURE = 0, 1
 LPP_BASIS_HUBBARD, LPP_BASIS_SPIN_HALF = 0, 1
 
 STATUS_NAMES = {0: "LPP_OK", 1: "LPP_ERR_INVALID", 2: "LPP_ERR_HIP", 3: "LPP_ERR_NOMEM", 4: "LPP_ERR_NOCONV",
@@ -158,6 +160,15 @@ SYMBOLS = {
     "lpp_engine_reduced_density_matrix_host": (C.c_int32, [_P] + [C.c_int32] * 5 + [_P, _P]),
     "lpp_engine_state_reduced_density_matrix": (C.c_int32, [_P] + [C.c_int32] * 6 + [_P]),
     "lpp_engine_bench_rdm": (C.c_int32, [_P] + [C.c_int32] * 7 + [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "lpp_obs_string_plan": (C.c_int32, [C.c_int32, C.c_int32, _P, _P, _P, _P] + [C.c_int32] * 3 + [C.POINTER(C.c_int32)] * 3 + [C.POINTER(C.c_double)]
+                            + [C.POINTER(C.c_int64)] * 2 + [_P, _P, C.POINTER(C.c_int32), _P]),
+    "lpp_engine_apply_string": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P] + [C.c_int32] * 3 + [C.c_double, C.c_double, _P, _P, C.c_int32]
+                                + [C.POINTER(C.c_int32)] * 3),
+    "lpp_engine_apply_string_host": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P] + [C.c_int32] * 3 + [C.c_double, C.c_double, _P, _P, C.c_int32]
+                                     + [C.POINTER(C.c_int32)] * 3),
+    "lpp_engine_many_point": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P] + [C.c_int32] * 5 + [_P]),
+    "lpp_engine_many_point_host": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P] + [C.c_int32] * 3 + [_P, _P, _P]),
+    "lpp_engine_bench_string_dot": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P] + [C.c_int32] * 5 + [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 }
 
 _lib = None

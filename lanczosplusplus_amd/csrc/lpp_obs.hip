@@ -17,65 +17,17 @@
 
 #include "lpp_engine_impl.h"
 #include "lpp_obs_kernels.h"
+#include "lpp_obs_string_plan.h"
+#include "lpp_obs_string_kernels.h"
 #include "lpp_obs_tj_kernels.h"
 #include "lpp_obs_heis_kernels.h"
 
 using namespace lpp;
+using namespace lpp::obs_host;
 
 namespace {
 
-inline bool needs_new_basis(int op) { return op == LPP_OP_C || op == LPP_OP_CDAGGER || op == LPP_OP_SPLUS || op == LPP_OP_SMINUS; } // LabeledOperator.h:83-90
-inline bool valid_op(int op) { return op == LPP_OP_C || op == LPP_OP_SZ || op == LPP_OP_CDAGGER || op == LPP_OP_N || op == LPP_OP_SPLUS || op == LPP_OP_SMINUS; }
-
-int64_t binom(int n, int k)
-{
-	if (k < 0 || k > n) return 0;
-	long double r = 1;
-	for (int i = 1; i <= k; i++) r = r * (n - k + i) / i;
-	return (int64_t)(r + 0.5L);
-}
-
-// HubbardOneOrbital::hasNewParts for c / cdagger / splus / sminus
-bool new_parts(int op, int spin, int L, int nup, int ndn, int* n1, int* n2)
-{
-	int p1 = nup, p2 = ndn;
-	if (op == LPP_OP_C || op == LPP_OP_CDAGGER) { // hasNewPartsCorCdagger :212-230
-		const int c = (op == LPP_OP_C) ? -1 : 1;
-		if (spin == LPP_SPIN_UP) p1 += c;
-		else p2 += c;
-		if (p1 < 0 || p2 < 0) return false;
-		if (p1 > L || p2 > L) return false;
-		if (p1 == 0 && p2 == 0) return false;
-	} else { // hasNewPartsSplusOrSminus :232-253
-		const int c = (op == LPP_OP_SPLUS) ? 1 : -1;
-		p1 += c;
-		p2 -= c;
-		if (p1 < 0 || p2 < 0) return false;
-		if (p1 > L || p2 > L) return false;
-	}
-	*n1 = p1;
-	*n2 = p2;
-	return true;
-}
-
-// BasisOneSpin::perfectIndex (BasisOneSpin.h:73-81): the rank of a word among the ascending words of its popcount
-struct Ranker {
-	int L;
-	std::vector<int64_t> comb; // comb[b * (L + 2) + c]
-	explicit Ranker(int L_) : L(L_), comb((size_t)(L_ + 1) * (L_ + 2))
-	{
-		for (int b = 0; b <= L; b++)
-			for (int c = 0; c <= L + 1; c++) comb[(size_t)b * (L + 2) + c] = binom(b, c);
-	}
-	int64_t rank(uint64_t w) const
-	{
-		int64_t n = 0;
-		int c = 1;
-		for (int b = 0; w; b++, w >>= 1)
-			if (w & 1) n += comb[(size_t)b * (L + 2) + c++];
-		return n;
-	}
-};
+// needs_new_basis, valid_op, binom, new_parts (HubbardOneOrbital::hasNewParts), Ranker (BasisOneSpin::perfectIndex): lpp_obs_string_plan.h
 
 enum { SP_C, SP_CDAGGER, SP_N };
 
@@ -173,6 +125,13 @@ lpp_status obs_plan(int op, int site, int spin, int L, int nup, int ndn, bool* h
 	return LPP_OK;
 }
 
+// ---- a product of one-site operators composed into ONE pair of tables (planner: lpp_obs_string_plan.h, kernels: lpp_obs_string_kernels.h) ----
+lpp_status string_plan(int conv, int nops, const int32_t* ops, const int32_t* sites, const int32_t* spins, const int32_t* flags, int L, int nup, int ndn, StringPlan& P)
+{
+	const char* why = nullptr;
+	if (!plan_string(conv, nops, ops, sites, spins, flags, L, nup, ndn, P, &why)) return fail(LPP_ERR_INVALID, why);
+	return LPP_OK;
+}
 
 // ---- the one-orbital t-J basis (BasisTjMultiOrbLanczos; kernel and lookup: lpp_obs_tj_kernels.h) ---------------------------------------
 
@@ -1001,6 +960,180 @@ lpp_status spectral_body(const ObsBasis& B, const std::string& who, lpp_engine* 
 	return decomposition_device_any(sector, M.p, nsteps, a, b, stats); // (a hole-major sector engine takes the vector through its permutation)
 }
 
+// ---- operator strings on the device (Hubbard product basis) -----------------------------------------------------------------------------
+
+// t-J and Heisenberg engines set up through the Python layer or the C++ shim are refused there, by the model's name; here what the engine itself knows
+lpp_status refuse_string(const lpp_engine* e, const char* who)
+{
+	if (multi(e)) return fail(LPP_ERR_STATE, std::string(who) + ": not on a partitioned (multi-rank) engine");
+	if (e->tj.active) return fail(LPP_ERR_INVALID, std::string(who) + ": the t-J model (TjMultiOrb) is not supported, operator strings are built for the Hubbard product basis");
+	return LPP_OK;
+}
+
+inline ObsString dev_string(const StringPlan& P, const int32_t* tu, const int32_t* td)
+{
+	ObsString S { tu, td, 0, 0, P.nsz, 0 };
+	for (int k = 0; k < P.nsz; k++) ((k < 8) ? S.sz_lo : S.sz_hi) |= (uint64_t)P.sz[k] << (8 * (k & 7));
+	return S;
+}
+
+// z (+)= factor * scale * string src on device vectors in the basis order.  One launch; the tables are this call's own, so it ends with a stream sync.
+lpp_status apply_string_dev(lpp_engine* e, const StringPlan& P, int L, int nup, int ndn, double fr, double fi, const void* d_src, void* d_dst, bool acc)
+{
+	lpp_status st = check_vectors(e, fi, d_src, d_dst);
+	if (st != LPP_OK) return st;
+	const int64_t nd = P.n_up_dst * P.n_dn_dst;
+	std::vector<uint32_t> wu, wd;
+	if (P.nsz > 0) {
+		species_words(L, nup, wu);
+		species_words(L, ndn, wd);
+	}
+	const size_t ntu = P.tu.size(), ntd = P.td.size();
+	std::vector<int32_t> img(ntu + ntd + wu.size() + wd.size() + 4);
+	std::memcpy(img.data(), P.tu.data(), 4 * ntu);
+	std::memcpy(img.data() + ntu, P.td.data(), 4 * ntd);
+	if (!wu.empty()) std::memcpy(img.data() + ntu + ntd, wu.data(), 4 * wu.size());
+	if (!wd.empty()) std::memcpy(img.data() + ntu + ntd + wu.size(), wd.data(), 4 * wd.size());
+	DevBuf T;
+	HIP_TRY_MEM(hipMalloc(&T.p, 4 * img.size()));
+	HIP_TRY(hipMemcpyAsync(T.p, img.data(), 4 * img.size(), hipMemcpyHostToDevice, e->stream));
+	const int32_t* d = (const int32_t*)T.p;
+	ObsStringApplyArgs A { dev_string(P, d, d + ntu), (const uint32_t*)(d + ntu + ntd), (const uint32_t*)(d + ntu + ntd + wu.size()), P.n_up_dst, P.n_dn_dst, P.n_up_src,
+		                   fr * P.scale, fi * P.scale };
+	const int64_t units = e->is_complex ? nd : (nd + 1) / 2;
+	const int g = obs_grid(e, units);
+	if (e->is_complex) {
+		if (acc) k_obs_string_apply<true, true><<<g, kObsBlock, 0, e->stream>>>((double*)d_dst, (const double*)d_src, A);
+		else k_obs_string_apply<true, false><<<g, kObsBlock, 0, e->stream>>>((double*)d_dst, (const double*)d_src, A);
+	} else {
+		if (acc) k_obs_string_apply<false, true><<<g, kObsBlock, 0, e->stream>>>((double*)d_dst, (const double*)d_src, A);
+		else k_obs_string_apply<false, false><<<g, kObsBlock, 0, e->stream>>>((double*)d_dst, (const double*)d_src, A);
+	}
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	return LPP_OK;
+}
+
+// strings as offsets into flat arrays: string s is entries offsets[s] .. offsets[s+1]-1
+struct StringList {
+	int32_t n;
+	const int64_t* off;
+	const int32_t *ops, *sites, *spins, *flags;
+};
+
+lpp_status check_list(const StringList& S, const char* who)
+{
+	if (S.n < 0 || !S.off || !S.ops || !S.sites || !S.spins) return fail(LPP_ERR_INVALID, std::string(who) + ": null argument");
+	for (int s = 0; s < S.n; s++)
+		if (S.off[s] < 0 || S.off[s + 1] - S.off[s] < 1 || S.off[s + 1] - S.off[s] > kObsStringMaxOps) return fail(LPP_ERR_INVALID, std::string(who) + ": 1 to 16 operators per string");
+	return LPP_OK;
+}
+
+// The brackets of strings [first, first + count) that stay in the sector, kObsStringBatch per launch: device workspace for one batch, reused after a sync.
+struct DotWork {
+	DevBuf tabs, part, out;
+	std::vector<int32_t> img;
+	int64_t nu = 0, nd = 0;
+	int grid = 1;
+};
+
+lpp_status dot_work(lpp_engine* e, int L, int nup, int ndn, int64_t nstrings, DotWork& W)
+{
+	W.nu = binom(L, nup);
+	W.nd = binom(L, ndn);
+	const int64_t n = W.nu * W.nd, units = e->is_complex ? n : (n + 1) / 2;
+	W.grid = obs_grid(e, units);
+	const size_t per = (size_t)(W.nu + W.nd);
+	W.img.assign(per * (kObsStringBatch + 1), 0); // kObsStringBatch pairs of tables, then the two word lists
+	HIP_TRY_MEM(hipMalloc(&W.tabs.p, 4 * W.img.size()));
+	HIP_TRY_MEM(hipMalloc(&W.part.p, sizeof(double) * 2 * kObsStringBatch * (size_t)W.grid));
+	HIP_TRY_MEM(hipMalloc(&W.out.p, sizeof(double) * 2 * (size_t)std::max<int64_t>(nstrings, 1)));
+	std::vector<uint32_t> wu, wd;
+	species_words(L, nup, wu);
+	species_words(L, ndn, wd);
+	std::memcpy(W.img.data() + per * kObsStringBatch, wu.data(), 4 * wu.size());
+	std::memcpy(W.img.data() + per * kObsStringBatch + W.nu, wd.data(), 4 * wd.size());
+	return LPP_OK;
+}
+
+// plans[0 .. ns) into the image and the kernel's arguments (the image is uploaded by the caller)
+ObsStringDotArgs dot_args(DotWork& W, const StringPlan* plans, int ns)
+{
+	const size_t per = (size_t)(W.nu + W.nd);
+	const int32_t* d = (const int32_t*)W.tabs.p;
+	ObsStringDotArgs A {};
+	for (int s = 0; s < ns; s++) {
+		std::memcpy(W.img.data() + per * s, plans[s].tu.data(), 4 * (size_t)W.nu);
+		std::memcpy(W.img.data() + per * s + W.nu, plans[s].td.data(), 4 * (size_t)W.nd);
+		A.s[s] = dev_string(plans[s], d + per * s, d + per * s + W.nu);
+	}
+	A.words_up = (const uint32_t*)(d + per * kObsStringBatch);
+	A.words_dn = A.words_up + W.nu;
+	A.n_up = W.nu;
+	A.n_dn = W.nd;
+	A.partial = (double*)W.part.p;
+	A.ns = ns;
+	return A;
+}
+
+void launch_dot(lpp_engine* e, const DotWork& W, const ObsStringDotArgs& A, const double* bra, const double* ket, double* d_out)
+{
+	if (e->is_complex) k_obs_string_dot<true><<<W.grid, kObsBlock, 0, e->stream>>>(bra, ket, A);
+	else k_obs_string_dot<false><<<W.grid, kObsBlock, 0, e->stream>>>(bra, ket, A);
+	k_reduce_final<<<1, kBlock, 0, e->stream>>>((const double*)W.part.p, W.grid, 2 * kObsStringBatch, 2 * A.ns, d_out);
+}
+
+// result[2 s], result[2 s + 1] = re, im of conj(bra) . (string_s ket); 0 where the string leads to no sector or ends in another one (nothing launched for it)
+lpp_status many_point_dev(lpp_engine* e, int conv, const StringList& S, int L, int nup, int ndn, const double* bra, const double* ket, double* result)
+{
+	std::vector<StringPlan> plans;
+	std::vector<int> slot; // the string of each plan
+	DotWork W;
+	bool ready = false;
+	std::vector<double> scale((size_t)S.n, 0.0);
+	int launched = 0;
+	auto flush = [&]() -> lpp_status {
+		if (plans.empty()) return LPP_OK;
+		if (!ready) {
+			lpp_status st = dot_work(e, L, nup, ndn, S.n, W);
+			if (st != LPP_OK) return st;
+			ready = true;
+		} else {
+			HIP_TRY(hipStreamSynchronize(e->stream)); // the launch that still reads the tables of the batch before
+		}
+		const ObsStringDotArgs A = dot_args(W, plans.data(), (int)plans.size());
+		HIP_TRY(hipMemcpyAsync(W.tabs.p, W.img.data(), 4 * W.img.size(), hipMemcpyHostToDevice, e->stream));
+		launch_dot(e, W, A, bra, ket, (double*)W.out.p + 2 * launched);
+		HIP_TRY(hipGetLastError());
+		launched += (int)plans.size();
+		plans.clear();
+		return LPP_OK;
+	};
+	for (int s = 0; s < S.n; s++) {
+		StringPlan P;
+		const int64_t o = S.off[s];
+		lpp_status st = string_plan(conv, (int)(S.off[s + 1] - o), S.ops + o, S.sites + o, S.spins + o, S.flags ? S.flags + o : nullptr, L, nup, ndn, P);
+		if (st != LPP_OK) return st;
+		result[2 * s] = result[2 * s + 1] = 0.0;
+		if (!P.has || P.nup2 != nup || P.ndn2 != ndn) continue; // Engine.h:364, :382-383
+		scale[(size_t)slot.size()] = P.scale;
+		slot.push_back(s);
+		plans.push_back(std::move(P));
+		if ((int)plans.size() == kObsStringBatch && (st = flush()) != LPP_OK) return st;
+	}
+	lpp_status st = flush();
+	if (st != LPP_OK) return st;
+	if (launched == 0) return LPP_OK;
+	std::vector<double> h(2 * (size_t)launched);
+	HIP_TRY(hipMemcpyAsync(h.data(), W.out.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	for (int k = 0; k < launched; k++) {
+		result[2 * slot[(size_t)k]] = scale[(size_t)k] * h[2 * (size_t)k];
+		result[2 * slot[(size_t)k] + 1] = scale[(size_t)k] * h[2 * (size_t)k + 1];
+	}
+	return LPP_OK;
+}
+
 } // namespace
 
 namespace lpp {
@@ -1057,6 +1190,173 @@ lpp_status lpp_obs_plan(int32_t op, int32_t site, int32_t spin, int32_t nsites, 
 		const int64_t n = s ? P.n_dn_dst : P.n_up_dst;
 		for (int64_t i = 0; i < n; i++) out[i] = t.empty() ? (int32_t)(i + 1) : t[(size_t)i];
 	}
+	return LPP_OK;
+}
+
+lpp_status lpp_obs_string_plan(int32_t convention, int32_t nops, const int32_t* ops, const int32_t* sites, const int32_t* spins, const int32_t* flags, int32_t nsites,
+                               int32_t nup, int32_t ndown, int32_t* has, int32_t* nup_new, int32_t* ndown_new, double* scale, int64_t* n_up_dst, int64_t* n_down_dst,
+                               int32_t* table_up, int32_t* table_down, int32_t* nsz, int32_t* sz)
+{
+	if (!has) return fail(LPP_ERR_INVALID, "lpp_obs_string_plan: null argument");
+	*has = 0;
+	StringPlan P;
+	lpp_status st = string_plan(convention, nops, ops, sites, spins, flags, nsites, nup, ndown, P);
+	if (st != LPP_OK) return st;
+	*has = P.has ? 1 : 0;
+	if (!P.has) return LPP_OK;
+	if (nup_new) *nup_new = P.nup2;
+	if (ndown_new) *ndown_new = P.ndn2;
+	if (scale) *scale = P.scale;
+	if (n_up_dst) *n_up_dst = P.n_up_dst;
+	if (n_down_dst) *n_down_dst = P.n_dn_dst;
+	if (table_up) std::memcpy(table_up, P.tu.data(), 4 * P.tu.size());
+	if (table_down) std::memcpy(table_down, P.td.data(), 4 * P.td.size());
+	if (nsz) *nsz = P.nsz;
+	if (sz)
+		for (int k = 0; k < P.nsz; k++) {
+			sz[3 * k] = P.sz[k] & 31;
+			sz[3 * k + 1] = (P.sz[k] >> 5) & 1;
+			sz[3 * k + 2] = (P.sz[k] >> 6) & 1;
+		}
+	return LPP_OK;
+}
+
+lpp_status lpp_engine_apply_string(lpp_engine* e, int32_t convention, int32_t nops, const int32_t* ops, const int32_t* sites, const int32_t* spins, const int32_t* flags,
+                                   int32_t nsites, int32_t nup, int32_t ndown, double factor_re, double factor_im, const void* d_src, void* d_dst, int32_t accumulate,
+                                   int32_t* has, int32_t* nup_new, int32_t* ndown_new)
+{
+	if (!e || !has) return fail(LPP_ERR_INVALID, "lpp_engine_apply_string: null argument");
+	*has = 0;
+	lpp_status st = refuse_string(e, "lpp_engine_apply_string");
+	if (st != LPP_OK) return st;
+	StringPlan P;
+	if ((st = string_plan(convention, nops, ops, sites, spins, flags, nsites, nup, ndown, P)) != LPP_OK) return st;
+	if (!P.has) return LPP_OK;
+	*has = 1;
+	if (nup_new) *nup_new = P.nup2;
+	if (ndown_new) *ndown_new = P.ndn2;
+	HIP_TRY(hipSetDevice(e->cfg.device));
+	return apply_string_dev(e, P, nsites, nup, ndown, factor_re, factor_im, d_src, d_dst, accumulate != 0);
+}
+
+lpp_status lpp_engine_apply_string_host(lpp_engine* e, int32_t convention, int32_t nops, const int32_t* ops, const int32_t* sites, const int32_t* spins, const int32_t* flags,
+                                        int32_t nsites, int32_t nup, int32_t ndown, double factor_re, double factor_im, const void* src, void* dst, int32_t accumulate,
+                                        int32_t* has, int32_t* nup_new, int32_t* ndown_new)
+{
+	if (!e || !has || !src || !dst) return fail(LPP_ERR_INVALID, "lpp_engine_apply_string_host: null argument");
+	*has = 0;
+	lpp_status st = refuse_string(e, "lpp_engine_apply_string_host");
+	if (st != LPP_OK) return st;
+	StringPlan P;
+	if ((st = string_plan(convention, nops, ops, sites, spins, flags, nsites, nup, ndown, P)) != LPP_OK) return st;
+	if (!P.has) return LPP_OK;
+	*has = 1;
+	if (nup_new) *nup_new = P.nup2;
+	if (ndown_new) *ndown_new = P.ndn2;
+	HIP_TRY(hipSetDevice(e->cfg.device));
+	const size_t ns = e->esz * (size_t)(P.n_up_src * P.n_dn_src), nd = e->esz * (size_t)(P.n_up_dst * P.n_dn_dst);
+	DevBuf ds, dd;
+	HIP_TRY_MEM(hipMalloc(&ds.p, std::max<size_t>(ns, 16)));
+	HIP_TRY_MEM(hipMalloc(&dd.p, std::max<size_t>(nd, 16) + 16));
+	HIP_TRY(hipMemcpyAsync(ds.p, src, ns, hipMemcpyHostToDevice, e->stream));
+	if (accumulate) HIP_TRY(hipMemcpyAsync(dd.p, dst, nd, hipMemcpyHostToDevice, e->stream));
+	if ((st = apply_string_dev(e, P, nsites, nup, ndown, factor_re, factor_im, ds.p, dd.p, accumulate != 0)) != LPP_OK) return st;
+	HIP_TRY(hipMemcpyAsync(dst, dd.p, nd, hipMemcpyDeviceToHost, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	return LPP_OK;
+}
+
+lpp_status lpp_engine_many_point(lpp_engine* e, int32_t convention, int32_t nstrings, const int64_t* offsets, const int32_t* ops, const int32_t* sites, const int32_t* spins,
+                                 const int32_t* flags, int32_t nsites, int32_t nup, int32_t ndown, int32_t bra_state, int32_t ket_state, double* result)
+{
+	const char* who = "lpp_engine_many_point";
+	if (!e || !result) return fail(LPP_ERR_INVALID, std::string(who) + ": null argument");
+	lpp_status st = refuse_string(e, who);
+	if (st != LPP_OK) return st;
+	const StringList S { nstrings, offsets, ops, sites, spins, flags };
+	if ((st = check_list(S, who)) != LPP_OK) return st;
+	if (hubbard_sector_size(nsites, nup, ndown) < 0) return fail(LPP_ERR_INVALID, std::string(who) + ": bad sites / sector");
+	double *bra = nullptr, *ket = nullptr;
+	if ((st = state_ptr(e, bra_state, who, &bra)) != LPP_OK) return st;
+	if ((st = state_ptr(e, ket_state, who, &ket)) != LPP_OK) return st;
+	if (e->resident_len != hubbard_sector_size(nsites, nup, ndown)) return fail(LPP_ERR_INVALID, std::string(who) + ": (sites, nup, ndown) is not the sector of the resident states");
+	HIP_TRY(hipSetDevice(e->cfg.device));
+	return many_point_dev(e, convention, S, nsites, nup, ndown, bra, ket, result);
+}
+
+lpp_status lpp_engine_many_point_host(lpp_engine* e, int32_t convention, int32_t nstrings, const int64_t* offsets, const int32_t* ops, const int32_t* sites, const int32_t* spins,
+                                      const int32_t* flags, int32_t nsites, int32_t nup, int32_t ndown, const void* bra, const void* ket, double* result)
+{
+	const char* who = "lpp_engine_many_point_host";
+	if (!e || !result || !bra || !ket) return fail(LPP_ERR_INVALID, std::string(who) + ": null argument");
+	lpp_status st = refuse_string(e, who);
+	if (st != LPP_OK) return st;
+	const StringList S { nstrings, offsets, ops, sites, spins, flags };
+	if ((st = check_list(S, who)) != LPP_OK) return st;
+	const int64_t n = hubbard_sector_size(nsites, nup, ndown);
+	if (n < 0) return fail(LPP_ERR_INVALID, std::string(who) + ": bad sites / sector");
+	HIP_TRY(hipSetDevice(e->cfg.device));
+	const size_t bytes = e->esz * (size_t)n;
+	DevBuf db, dk;
+	HIP_TRY_MEM(hipMalloc(&db.p, bytes + 16));
+	HIP_TRY_MEM(hipMalloc(&dk.p, bytes + 16));
+	HIP_TRY(hipMemcpyAsync(db.p, bra, bytes, hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipMemcpyAsync(dk.p, ket, bytes, hipMemcpyHostToDevice, e->stream));
+	st = many_point_dev(e, convention, S, nsites, nup, ndown, (const double*)db.p, (const double*)dk.p, result);
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	return st;
+}
+
+lpp_status lpp_engine_bench_string_dot(lpp_engine* e, int32_t convention, int32_t nstrings, const int64_t* offsets, const int32_t* ops, const int32_t* sites, const int32_t* spins,
+                                       const int32_t* flags, int32_t nsites, int32_t nup, int32_t ndown, int32_t warmup, int32_t iters, double* ms_per_launch, double* model_bytes)
+{
+	const char* who = "lpp_engine_bench_string_dot";
+	if (!e || !ms_per_launch || iters < 1 || warmup < 0) return fail(LPP_ERR_INVALID, std::string(who) + ": bad argument");
+	lpp_status st = refuse_string(e, who);
+	if (st != LPP_OK) return st;
+	const StringList S { nstrings, offsets, ops, sites, spins, flags };
+	if ((st = check_list(S, who)) != LPP_OK) return st;
+	if (nstrings < 1 || nstrings > kObsStringBatch) return fail(LPP_ERR_INVALID, std::string(who) + ": 1 to 8 strings (one launch)");
+	const int64_t n = hubbard_sector_size(nsites, nup, ndown);
+	if (n < 0) return fail(LPP_ERR_INVALID, std::string(who) + ": bad sites / sector");
+	std::vector<StringPlan> plans((size_t)nstrings);
+	double reached = 0;
+	for (int s = 0; s < nstrings; s++) {
+		StringPlan& P = plans[(size_t)s];
+		const int64_t o = offsets[s];
+		if ((st = string_plan(convention, (int)(offsets[s + 1] - o), ops + o, sites + o, spins + o, flags ? flags + o : nullptr, nsites, nup, ndown, P)) != LPP_OK) return st;
+		if (!P.has || P.nup2 != nup || P.ndn2 != ndown) return fail(LPP_ERR_INVALID, std::string(who) + ": a string that leaves the sector launches nothing");
+		reached += (double)std::count_if(P.tu.begin(), P.tu.end(), [](int32_t v) { return v != 0; }) * (double)std::count_if(P.td.begin(), P.td.end(), [](int32_t v) { return v != 0; });
+	}
+	HIP_TRY(hipSetDevice(e->cfg.device));
+	const size_t bytes = e->esz * (size_t)n;
+	DevBuf db, dk;
+	HIP_TRY_MEM(hipMalloc(&db.p, bytes + 16));
+	HIP_TRY_MEM(hipMalloc(&dk.p, bytes + 16));
+	HIP_TRY(hipMemsetAsync(db.p, 0, bytes + 16, e->stream));
+	HIP_TRY(hipMemsetAsync(dk.p, 0, bytes + 16, e->stream));
+	DotWork W;
+	if ((st = dot_work(e, nsites, nup, ndown, nstrings, W)) != LPP_OK) return st;
+	const ObsStringDotArgs A = dot_args(W, plans.data(), nstrings);
+	HIP_TRY(hipMemcpyAsync(W.tabs.p, W.img.data(), 4 * W.img.size(), hipMemcpyHostToDevice, e->stream));
+	hipEvent_t t0 = nullptr, t1 = nullptr;
+	HIP_TRY(hipEventCreate(&t0));
+	HIP_TRY(hipEventCreate(&t1));
+	for (int i = 0; i < warmup + iters; i++) {
+		if (i == warmup) (void)hipEventRecord(t0, e->stream);
+		launch_dot(e, W, A, (const double*)db.p, (const double*)dk.p, (double*)W.out.p);
+	}
+	(void)hipEventRecord(t1, e->stream);
+	hipError_t err = hipEventSynchronize(t1);
+	float ms = 0;
+	if (err == hipSuccess) err = hipEventElapsedTime(&ms, t0, t1);
+	if (err == hipSuccess) err = hipGetLastError();
+	(void)hipEventDestroy(t0);
+	(void)hipEventDestroy(t1);
+	HIP_TRY(err);
+	*ms_per_launch = ms / iters;
+	// bra read once, one ket element per string and destination it reaches (the tables stay in L2)
+	if (model_bytes) *model_bytes = (double)e->esz * ((double)n + reached);
 	return LPP_OK;
 }
 

@@ -409,6 +409,80 @@ class LanczosEngine:
         check(call(self._h, _op_id(op), site, spin, L, nup, ndown, warmup, iters, C.byref(ms), C.byref(by)))
         return ms.value, by.value
 
+    # ---- products of one-site operators: -M many-point correlations and -m measure brackets (Hubbard product basis) ------------
+    def _refuse_strings(self, who):
+        """t-J and Heisenberg engines: LPP_ERR_INVALID naming the model (their bases are a follow-up, as they were for the observables)"""
+        if self._is_tj() or self._is_heis():
+            raise _capi.LppError(_capi.LPP_ERR_INVALID, "%s: not for the %s model, operator strings are built for the Hubbard product basis"
+                                 % (who, "t-J (TjMultiOrb)" if self._is_tj() else "Heisenberg"))
+
+    def apply_operator_string(self, ops, L, nup, ndown, src, factor=1.0, out=None, convention="many_point"):
+        """z (+)= factor * (the whole string applied to src) in ONE launch (lpp_engine_apply_string_host): returns (z, (nup', ndown')), z starting from `out`
+        or from zero, or (None, None) where the string leads to no sector.  ops and convention as operator_string_plan."""
+        self._refuse_strings("apply_operator_string")
+        conv, off, o, s, sp, fl = _string_arrays([ops], convention)
+        plan = operator_string_plan(ops, L, nup, ndown, convention)
+        if plan is None:
+            return None, None
+        src = np.ascontiguousarray(src, self.np_dtype)
+        if len(src) != sector_size(L, nup, ndown):
+            raise ValueError("src does not have the length of sector (%d, %d)" % (nup, ndown))
+        n = len(plan["table_up"]) * len(plan["table_down"])
+        if out is None:
+            z = np.zeros(n, self.np_dtype)
+        else:
+            z = np.ascontiguousarray(out, self.np_dtype)
+            if len(z) != n:
+                raise ValueError("out does not have the length of sector (%d, %d)" % (plan["nup"], plan["ndown"]))
+        f = complex(factor)
+        has, n1, n2 = C.c_int32(), C.c_int32(), C.c_int32()
+        check(self._lib.lpp_engine_apply_string_host(self._h, conv, int(off[-1]), _vp(o), _vp(s), _vp(sp), _vp(fl), L, nup, ndown, f.real, f.imag, _vp(src), _vp(z),
+                                                     int(out is not None), C.byref(has), C.byref(n1), C.byref(n2)))
+        return z, (n1.value, n2.value)
+
+    def _brackets(self, res):
+        return (res[:, 0] + 1j * res[:, 1]) if self.is_complex else res[:, 0].copy()
+
+    def many_point(self, strings, bra=0, ket=0, convention="many_point"):
+        """Engine::manyPoint (Engine.h:341-389) for a list of strings on resident states bra / ket (keep_states before lanczos): one value per string,
+        conj(bra) . (O_{n-1} ... O_0 ket), the FIRST listed operator acting first.  A string is a list of (op, site, spin) or the reference's text
+        "c?0?0;cdagger?1?0".  0 where a step leads to no sector (the (0,0) sector included) or the string ends in another sector; nothing is launched
+        for those.  n and sz act in the sector the string has reached (the reference hands them the original sector's basis, which is ill-defined
+        once the string has left it).  8 strings share one read of bra; a value does not depend on the batch it is computed in."""
+        self._refuse_strings("many_point")
+        m = self._need_model("many_point")
+        conv, off, o, s, sp, fl = _string_arrays(strings, convention)
+        res = np.zeros((len(off) - 1, 2))
+        check(self._lib.lpp_engine_many_point(self._h, conv, len(off) - 1, _vp(off), _vp(o), _vp(s), _vp(sp), _vp(fl), m["L"], m["nup"], m["ndown"], int(bra), int(ket), _vp(res)))
+        return self._brackets(res)
+
+    def many_point_of(self, strings, L, nup, ndown, bra, ket, convention="many_point"):
+        """the same for host vectors bra / ket of sector (nup, ndown) in the basis order; the engine needs no matrix"""
+        self._refuse_strings("many_point_of")
+        conv, off, o, s, sp, fl = _string_arrays(strings, convention)
+        bra = np.ascontiguousarray(bra, self.np_dtype)
+        ket = np.ascontiguousarray(ket, self.np_dtype)
+        if len(bra) != sector_size(L, nup, ndown) or len(ket) != len(bra):
+            raise ValueError("bra / ket do not have the length of sector (%d, %d)" % (nup, ndown))
+        res = np.zeros((len(off) - 1, 2))
+        check(self._lib.lpp_engine_many_point_host(self._h, conv, len(off) - 1, _vp(off), _vp(o), _vp(s), _vp(sp), _vp(fl), L, nup, ndown, _vp(bra), _vp(ket), _vp(res)))
+        return self._brackets(res)
+
+    def measure(self, ops, bra=0, ket=0):
+        """Engine::measure (Engine.h:208-249) through ModelBase::rahulMethod: conj(bra) . (O_0 ... O_{n-1} ket), the LAST listed operator acting first, for
+        resident states.  ops: (label, site, dof, transpose) with label c / n / sz / identity, dof 0 = up, 1 = down, transpose making c into c-dagger;
+        sz is -1/2 on an occupied bit of that species and +1/2 on an empty one, as RahulOperator.h has it.  A string that does not conserve both
+        particle numbers raises LppError (the reference would index outside the sector)."""
+        return self.many_point([ops], bra, ket, convention="measure")[0]
+
+    def bench_string_dot(self, strings, L, nup, ndown, warmup=2, iters=10, convention="many_point"):
+        """(ms per launch, bytes of the byte model) of the bracket kernel + reduction on one batch of 1 .. 8 strings, zeroed vectors"""
+        conv, off, o, s, sp, fl = _string_arrays(strings, convention)
+        ms, by = C.c_double(), C.c_double()
+        check(self._lib.lpp_engine_bench_string_dot(self._h, conv, len(off) - 1, _vp(off), _vp(o), _vp(s), _vp(sp), _vp(fl), L, nup, ndown, warmup, iters,
+                                                    C.byref(ms), C.byref(by)))
+        return ms.value, by.value
+
     # ---- reduced density matrix of the low `split` sites (lpp_rdm.hip) ---------------------------------------
     def _rdm_call(self, call, plan, dense):
         """two calls: every refusal first (out = NULL launches nothing), then the packed result"""
@@ -689,6 +763,74 @@ def operator_plan(op, site, spin, L, nup, ndown):
     tu, td = np.zeros(nu.value, np.int32), np.zeros(nd.value, np.int32)
     check(lib.lpp_obs_plan(oid, site, spin, L, nup, ndown, C.byref(has), C.byref(n1), C.byref(n2), C.byref(nu), C.byref(nd), _vp(tu), _vp(td)))
     return dict(nup=n1.value, ndown=n2.value, table_up=tu, table_down=td)
+
+
+# RahulOperator::fromString (RahulOperator.h:56-63)
+MEASURE_LABELS = {"c": _capi.LPP_OP_C, "n": _capi.LPP_OP_N, "sz": _capi.LPP_OP_SZ, "identity": _capi.LPP_OP_IDENTITY}
+STRING_CONVENTIONS = {"many_point": _capi.LPP_STRING_MANY_POINT, "measure": _capi.LPP_STRING_MEASURE}
+
+
+def parse_many_point(text):
+    """the reference's -M text (LanczosDriver1.h:24-40): "op?site?spin[?orbital];..." -> [(op, site, spin), ...]; orbital 0 only"""
+    out = []
+    for tok in text.split(";"):
+        parts = tok.split("?")
+        if len(parts) < 3 or len(parts) > 4:
+            raise ValueError("-M option malformed: %r" % tok)
+        if len(parts) == 4 and int(parts[3]) != 0:
+            raise ValueError("orbital 0 only: %r" % tok)
+        out.append((parts[0], int(parts[1]), int(parts[2])))
+    return out
+
+
+def _string_arrays(strings, convention):
+    """(convention id, offsets, ops, sites, spins, flags) as the C entry points take a list of strings"""
+    try:
+        conv = STRING_CONVENTIONS[convention]
+    except KeyError:
+        raise ValueError("unsupported convention %r (one of %s)" % (convention, ", ".join(sorted(STRING_CONVENTIONS))))
+    off, ops, sites, spins, flags = [0], [], [], [], []
+    for string in strings:
+        if isinstance(string, str):
+            if convention != "many_point":
+                raise ValueError("text strings are the -M form; pass measure operators as (label, site, dof, transpose)")
+            string = parse_many_point(string)
+        for item in string:
+            if convention == "measure":
+                label, site, dof = item[0], item[1], item[2]
+                if label not in MEASURE_LABELS:
+                    raise ValueError("unsupported label %r (one of %s)" % (label, ", ".join(sorted(MEASURE_LABELS))))
+                ops.append(MEASURE_LABELS[label])
+                flags.append(int(bool(item[3])) if len(item) > 3 else 0)
+            else:
+                label, site, dof = item
+                ops.append(_op_id(label))
+                flags.append(0)
+            sites.append(int(site))
+            spins.append(int(dof))
+        off.append(len(ops))
+    pad = [0] if not ops else []  # (a valid pointer for an empty list)
+    return (conv, np.array(off, np.int64), np.array(ops + pad, np.int32), np.array(sites + pad, np.int32), np.array(spins + pad, np.int32),
+            np.array(flags + pad, np.int32))
+
+
+def operator_string_plan(ops, L, nup, ndown, convention="many_point"):
+    """The plan of a product of one-site operators (lpp_obs_string_plan, host only): None where the string leads to no sector, else a dict with the
+    final sector (nup, ndown), scale, the two composed tables table[destination species rank] = +-(source species rank + 1) or 0, and sz: a list of
+    (site, flip_up, flip_down) whose factors (bit_up(src, site) ^ flip_up) - (bit_down(src, site) ^ flip_down) multiply the coefficient.
+    convention "many_point": ops = (op, site, spin), the first acts first (Engine::manyPoint); "measure": ops = (label, site, dof, transpose), the
+    last acts first (ModelBase::rahulMethod)."""
+    lib = _capi.lib()
+    conv, off, o, s, sp, fl = _string_arrays([ops], convention)
+    has, n1, n2, nsz = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+    nu, nd, scale = C.c_int64(), C.c_int64(), C.c_double()
+    args = (conv, int(off[-1]), _vp(o), _vp(s), _vp(sp), _vp(fl), int(L), int(nup), int(ndown), C.byref(has), C.byref(n1), C.byref(n2), C.byref(scale), C.byref(nu), C.byref(nd))
+    check(lib.lpp_obs_string_plan(*args, None, None, C.byref(nsz), None))
+    if not has.value:
+        return None
+    tu, td, sz = np.zeros(nu.value, np.int32), np.zeros(nd.value, np.int32), np.zeros(3 * 16, np.int32)
+    check(lib.lpp_obs_string_plan(*args, _vp(tu), _vp(td), C.byref(nsz), _vp(sz)))
+    return dict(nup=n1.value, ndown=n2.value, scale=scale.value, table_up=tu, table_down=td, sz=[tuple(int(v) for v in sz[3 * k:3 * k + 3]) for k in range(nsz.value)])
 
 
 def continued_fraction(record, z):

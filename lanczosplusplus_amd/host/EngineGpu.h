@@ -519,6 +519,83 @@ public:
 		std::cout << "MatrixDiagonal = " << sum << "\n";
 	}
 
+	typedef std::vector<SizeType> VectorSizeType;
+
+	// Engine::manyPoint (Engine.h:341-389) on the resident states: conj(bra) . (what[n-1] ... what[0] ket), what[0] acting first, each step
+	// accModifiedState_ through the sectors of hasNewParts; 0 where a step leads to no sector or the string ends in another sector.  The whole string
+	// is ONE pass of the bracket kernel (lpp_engine_many_point), no intermediate vector.  n and sz act in the sector the string has reached (the
+	// reference's getNeededBasis hands them the original sector's basis, ill-defined once the string has left it).  Orbital 0 only.
+	ComplexOrRealType manyPoint(const VectorSizeType& sites, const std::vector<LabeledOperatorType>& what, const VectorSizeType& spins, const VectorSizeType& orbs,
+	                            const PairType& braAndKet) const
+	{
+		lpp_engine* e = stringEngine("manyPoint");
+		if (what.size() != sites.size() || spins.size() != sites.size() || orbs.size() != sites.size()) throw std::runtime_error("manyPoint: sites, operators, spins and orbitals differ in number\n");
+		checkBraOrKet("ket", braAndKet.second);
+		checkBraOrKet("bra", braAndKet.first);
+		std::vector<int32_t> ops(sites.size()), st(sites.size()), sp(sites.size());
+		for (SizeType i = 0; i < sites.size(); i++) {
+			if (orbs[i] != 0) throw std::runtime_error("manyPoint: one orbital only\n");
+			ops[i] = what[i].id();
+			st[i] = (int32_t)sites[i];
+			sp[i] = (int32_t)spins[i];
+		}
+		return bracket(e, LPP_STRING_MANY_POINT, ops, st, sp, std::vector<int32_t>(sites.size(), 0), braAndKet);
+	}
+
+	// Engine::measure (Engine.h:208-249): braOpKet = { "<bra", "op;op;...", "ket>" } as the driver splits "<gs|op;op|gs>" at '|'; the product goes through
+	// ModelBase::rahulMethod's rules (the LAST operator acts first) in one pass of the bracket kernel, and "bra|meas|ket = value" is printed (:248).
+	// Token grammar (PsimagLite's OneOperatorSpec was not at hand; restated from its use in :221-232, UNVERIFIED): label, an optional ?dof, an optional '
+	// for transpose (after the label or after the dof), the site in square brackets -- n?0[0], c'[2], c?1'[3].  bra and ket: gs.
+	void measure(const VectorStringType& braOpKet) const
+	{
+		if (braOpKet.size() != 3) throw std::runtime_error("LanczosDriver1: Only dressed brakets allowed (FATAL ERROR)\n");
+		lpp_engine* e = stringEngine("measure");
+		const LppHost::String meas = braOpKet[1];
+		std::vector<int32_t> ops, st, sp, fl;
+		std::istringstream all(meas);
+		LppHost::String tok;
+		while (std::getline(all, tok, ';')) {
+			const SizeType open = tok.find('['), close = tok.find(']');
+			if (open == LppHost::String::npos || close == LppHost::String::npos || close < open + 2 || close + 1 != tok.size())
+				throw std::runtime_error("Operator " + tok + " needs a site in brackets\n");
+			const LppHost::String siteString = tok.substr(open + 1, close - open - 1);
+			if (siteString.find_first_not_of("0123456789") != LppHost::String::npos) throw std::runtime_error("Operator " + tok + ": the site must be a number\n");
+			LppHost::String root = tok.substr(0, open);
+			bool transpose = false;
+			if (!root.empty() && root.back() == '\'') {
+				transpose = true;
+				root.pop_back();
+			}
+			int dof = 0;
+			const SizeType q = root.find('?');
+			if (q != LppHost::String::npos) {
+				const LppHost::String d = root.substr(q + 1);
+				if (d != "0" && d != "1") throw std::runtime_error("Operator " + tok + ": the dof is 0 (up) or 1 (down)\n");
+				dof = d == "1";
+				root = root.substr(0, q);
+			}
+			if (!root.empty() && root.back() == '\'') {
+				transpose = true;
+				root.pop_back();
+			}
+			int label = -1; // RahulOperator::fromString (RahulOperator.h:56-63)
+			if (root == "c") label = LPP_OP_C;
+			else if (root == "identity") label = LPP_OP_IDENTITY;
+			else if (root == "sz") label = LPP_OP_SZ;
+			else if (root == "n") label = LPP_OP_N;
+			else throw std::runtime_error("RahulOperator: Unknow label " + root + "\n");
+			ops.push_back(label);
+			st.push_back(atoi(siteString.c_str()));
+			sp.push_back(dof);
+			fl.push_back(transpose ? 1 : 0);
+		}
+		const SizeType ketIndex = levelIndex(braOpKet[2], '>'), braIndex = levelIndex(braOpKet[0], '<');
+		checkBraOrKet("ket", ketIndex);
+		checkBraOrKet("bra", braIndex);
+		const ComplexOrRealType result = bracket(e, LPP_STRING_MEASURE, ops, st, sp, fl, PairType(braIndex, ketIndex));
+		std::cout << braOpKet[0] << "|" << meas << "|" << braOpKet[2] << " = " << result << "\n";
+	}
+
 	// Engine::spectralFunction for a list of spin pairs, as the driver calls it (LanczosDriver1.h:165-171)
 	template <typename ContinuedFractionCollectionType>
 	void spectralFunction(ContinuedFractionCollectionType& cfCollection, VectorStringType& vstr, const LabeledOperatorType& lOperator1, int isite, int jsite,
@@ -628,6 +705,36 @@ private:
 		if (!(hubbard() || tjModel() || heisModel()) || !hamiltonian_ || !statesResident_)
 			throw std::runtime_error(std::string(who) + ": needs a Model of the HubbardOneOrbital family, TjMultiOrb with Orbitals=1 or Heisenberg with HeisenbergTwiceS=1 and no AnisotropyD solved by the GPU Lanczos (no symmetry sectors, no dense fallback)\n");
 		return hamiltonian_->engine();
+	}
+
+	// manyPoint / measure: the Hubbard product basis only; the t-J and Heisenberg models are refused as LPP_ERR_INVALID by the model's name
+	lpp_engine* stringEngine(const char* who) const
+	{
+		lpp_engine* e = observableEngine(who);
+		if (tjModel() || heisModel())
+			throw std::runtime_error(std::string("LPP_ERR_INVALID: ") + who + ": not for the " + (tjModel() ? "TjMultiOrb" : "Heisenberg") + " model, operator strings are built for the Hubbard product basis\n");
+		return e;
+	}
+
+	ComplexOrRealType bracket(lpp_engine* e, int convention, const std::vector<int32_t>& ops, const std::vector<int32_t>& sites, const std::vector<int32_t>& spins,
+	                          const std::vector<int32_t>& flags, const PairType& braAndKet) const
+	{
+		const PairType parts = obsParts();
+		const int64_t off[2] = { 0, (int64_t)ops.size() };
+		double out[2] = { 0, 0 };
+		lppCheck(lpp_engine_many_point(e, convention, 1, off, ops.data(), sites.data(), spins.data(), flags.data(), (int32_t)model_.geometry().numberOfSites(), (int32_t)parts.first,
+		                               (int32_t)parts.second, (int32_t)braAndKet.first, (int32_t)braAndKet.second, out));
+		if constexpr (std::is_same<ComplexOrRealType, double>::value) return out[0];
+		else return ComplexOrRealType(out[0], out[1]);
+	}
+
+	// PsimagLite::GetBraOrKet as Engine::measure uses it (:234-244): "gs" is level 0; nothing else is restated here
+	static SizeType levelIndex(const LppHost::String& s, char bracket)
+	{
+		LppHost::String name = s;
+		name.erase(std::remove(name.begin(), name.end(), bracket), name.end());
+		if (name != "gs") throw std::runtime_error("measure: bra and ket must be gs, not " + name + "\n");
+		return 0;
 	}
 
 	const HubbardOneOrbital<ComplexOrRealType>* hubbard() const { return dynamic_cast<const HubbardOneOrbital<ComplexOrRealType>*>(&model_); }

@@ -1,11 +1,13 @@
 // lanczos.cpp -- driver with the reference's command line for this path (src/lanczos.cpp:99-226,
 // src/Engine/LanczosDriver1.h:47-66): reads an InputNg-style file (the reference's TestSuite inputs work
 // unmodified for the in-scope models), builds the model, runs the GPU engine, prints "Energy=".
-//   lanczos -f input.inp [-p precision] [-d device] [-g operator] [-c operator] [-s "s1,s2;..."] [-r siteForSplit]
+//   lanczos -f input.inp [-p precision] [-d device] [-g operator] [-c operator] [-s "s1,s2;..."] [-r siteForSplit] [-M "op?site?spin;...,..."] [-m "<gs|op;op|gs>,..."]
 // SolverOptions=useComplex selects complex<double> (lanczos.cpp:194-226).  -c prints the two-point matrix of the ground state, -g writes the
 // continued fractions of the spectral function for the site pairs the input names (TSPSites, TSPCenter=, DoAllPairs=,
 // ComputeDensityOfStates=) into <input basename><counter>.comb (LanczosDriver1.h:81-199; Hubbard family, TjMultiOrb with Orbitals=1 and Heisenberg with HeisenbergTwiceS=1 -- where `-g sz` decomposes the reference's raw 1 - 2 bit = -2 S^z --, one GPU).  -r prints the reduced density
-// matrix of the lattice cut at a site, its eigenvectors, eigenvalues and the entanglement entropy (LanczosDriver1.h:201-206).  -m, -M are out of scope.
+// matrix of the lattice cut at a site, its eigenvectors, eigenvalues and the entanglement entropy (LanczosDriver1.h:201-206).  -M prints static many-point
+// correlations of the ground state, one "<gs|STRING|gs>=value" per comma-separated string (LanczosDriver1.h:17-45, :208-213); -m prints measure brackets,
+// "bra|meas|ket = value" (LanczosDriver1.h:69-79, Engine.h:248).  Both are for the Hubbard family on one GPU.
 #include <getopt.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -33,7 +35,37 @@ struct LanczosOptions {
 	std::vector<SizeType> sites;
 	std::vector<PairSizeType> spins;
 	int split = -1; // -r siteForSplit (LanczosOptions.h), -1: no reduced density matrix
+	LppHost::String extendedStatic; // -M
+	std::vector<LppHost::String> measure; // -m, one entry per occurrence
 };
+
+static std::vector<LppHost::String> splitString(const LppHost::String& s, char sep)
+{
+	std::vector<LppHost::String> out;
+	std::istringstream all(s);
+	LppHost::String item;
+	while (std::getline(all, item, sep))
+		if (!item.empty()) out.push_back(item); // (PsimagLite::split drops empty tokens)
+	return out;
+}
+
+// extendedStatic (LanczosDriver1.h:17-45): "op?site?spin[?orbital];..." -> Engine::manyPoint, printed as "<gs|STRING|gs>=value"
+template <typename EngineType> static void extendedStatic(const LppHost::String& manypoint, const EngineType& engine, const typename EngineType::PairType& braAndKet)
+{
+	typename EngineType::VectorSizeType sites, spins, orbs;
+	std::vector<LabeledOperator> whats;
+	for (const LppHost::String& item : splitString(manypoint, ';')) {
+		const std::vector<LppHost::String> str2 = splitString(item, '?');
+		if (str2.size() < 3) throw std::runtime_error("-M option malformed\n");
+		whats.push_back(LabeledOperator(str2[0]));
+		sites.push_back((SizeType)atoi(str2[1].c_str()));
+		spins.push_back((SizeType)atoi(str2[2].c_str()));
+		orbs.push_back(str2.size() == 4 ? (SizeType)atoi(str2[3].c_str()) : 0);
+	}
+	std::cout << "<gs|" << manypoint << "|gs>=";
+	std::cout << engine.manyPoint(sites, whats, spins, orbs, braAndKet);
+	std::cout << "\n";
+}
 
 // -s "s1,s2;s1,s2;..." (lanczos.cpp:17-34, :147-152)
 static void fillSpins(std::vector<LanczosOptions::PairSizeType>& spins, const LppHost::String& arg)
@@ -121,6 +153,10 @@ int mainLoop3(const ModelType& model, LppHost::InputReadable& io, int device, in
 	const LppHost::String filename = basenameOf(io.filename());
 	const SizeType n = model.geometry().numberOfSites();
 
+	// -m (LanczosDriver1.h:69-79): comma-separated brackets, each split at '|' into bra, operators, ket
+	for (SizeType i = 0; i < lanczosOptions.measure.size(); ++i)
+		for (const LppHost::String& token : splitString(lanczosOptions.measure[i], ',')) engine.measure(splitString(token, '|'));
+
 	// the site pairs of -g (LanczosDriver1.h:81-136)
 	bool needsDos = false;
 	if (io.has("ComputeDensityOfStates=")) {
@@ -194,6 +230,10 @@ int mainLoop3(const ModelType& model, LppHost::InputReadable& io, int device, in
 
 	// -r (LanczosDriver1.h:201-206)
 	if (lanczosOptions.split >= 0) printReducedDensityMatrix(std::cout, engine, (SizeType)lanczosOptions.split);
+
+	// -M (LanczosDriver1.h:208-213)
+	if (lanczosOptions.extendedStatic != "")
+		for (const LppHost::String& str : splitString(lanczosOptions.extendedStatic, ',')) extendedStatic(str, engine, PairSizeType(0, 0));
 	return 0;
 }
 
@@ -415,17 +455,19 @@ int main(int argc, char** argv)
 	LppHost::String file;
 	int device = 0, precision = 8, opt = 0;
 	bool partitioned = false;
-	const char* usage = " -f filename [-p precision] [-d device] [-P] [-g operator] [-c operator] [-s \"s1,s2;...\"] [-r siteForSplit]\n";
+	const char* usage = " -f filename [-p precision] [-d device] [-P] [-g operator] [-c operator] [-s \"s1,s2;...\"] [-r siteForSplit] [-M \"op?site?spin;...\"] [-m \"<gs|op;op|gs>\"]\n";
 	LanczosOptions lanczosOptions;
 	LppHost::String spinsArg;
 	std::vector<LppHost::String> gfArgs, cicjArgs;
-	while ((opt = getopt(argc, argv, "f:p:d:Pg:c:s:r:")) != -1) {
+	while ((opt = getopt(argc, argv, "f:p:d:Pg:c:s:r:M:m:")) != -1) {
 		switch (opt) {
 		case 'f': file = optarg; break;
 		case 'g': gfArgs.push_back(optarg); break;
 		case 'c': cicjArgs.push_back(optarg); break;
 		case 's': spinsArg = optarg; break;
 		case 'r': lanczosOptions.split = atoi(optarg); break;
+		case 'M': lanczosOptions.extendedStatic = optarg; break;
+		case 'm': lanczosOptions.measure.push_back(optarg); break;
 		case 'p': precision = atoi(optarg); break;
 		case 'd': device = atoi(optarg); break;
 		case 'P': partitioned = true; break;
@@ -440,7 +482,8 @@ int main(int argc, char** argv)
 		for (const LppHost::String& g : gfArgs) lanczosOptions.gf.push_back(LabeledOperator(g));
 		for (const LppHost::String& c : cicjArgs) lanczosOptions.cicj.push_back(LabeledOperator(c));
 		if (!spinsArg.empty()) fillSpins(lanczosOptions.spins, spinsArg);
-		if (partitioned && (!gfArgs.empty() || !cicjArgs.empty() || lanczosOptions.split >= 0)) throw std::runtime_error("-g / -c / -r run on one GPU: not with -P\n");
+		if (partitioned && (!gfArgs.empty() || !cicjArgs.empty() || lanczosOptions.split >= 0 || !lanczosOptions.extendedStatic.empty() || !lanczosOptions.measure.empty()))
+			throw std::runtime_error("-g / -c / -r / -M / -m run on one GPU: not with -P\n");
 		LppHost::InputReadable io(file);
 		LppHost::String options("none");
 		if (io.has("SolverOptions=")) io.readline(options, "SolverOptions=");
