@@ -1,9 +1,12 @@
-// lpp_obs.hip -- ground-state observables of the Hubbard product basis, of the one-orbital t-J basis and of the S = 1/2 Heisenberg basis (one body per entry point, ObsBasis) on one GPU: one-site operators applied to device vectors
-// (Engine::accModifiedState_, reference src/Engine/Engine.h:416-458), the two-point matrix (Engine::twoPoint :266-338) and the modified
-// state + decomposition of one spectral-function type (Engine::spectralFunction :134-206, getModifiedState :494-533, calcSpectral :460-490).
+// lpp_obs.hip -- ground-state observables of the Hubbard product basis, of the one-orbital t-J basis and of the S = 1/2 Heisenberg basis on one GPU:
+// one-site operators applied to device vectors (Engine::accModifiedState_, reference src/Engine/Engine.h:416-458), the two-point matrix
+// (Engine::twoPoint :266-338), the modified state + decomposition of one spectral-function type (Engine::spectralFunction :134-206, getModifiedState
+// :494-533, calcSpectral :460-490), operator strings (Engine::manyPoint :341-389) and the continued-fraction evaluator.
 //
-// Host part (no GPU): sector arithmetic (HubbardOneOrbital::hasNewParts, HubbardOneOrbital.h:87-109,212-253), the per-species tables the
-// kernel of lpp_obs_kernels.h reads, and the continued-fraction evaluator.
+// The device side only.  Each family is one ObsBasis: how its plan is built and uploaded (a DevPlan of its own in the engine's cache) and how it is
+// launched; every entry point is one body over an ObsBasis, and the four destination-driven apply kernels go through one launch (OBS_LAUNCH).
+// The host planners (no GPU, plain C++) are lpp_obs_plan.h (shared sector arithmetic, Hubbard), lpp_obs_tj_plan.h, lpp_obs_heis_plan.h and
+// lpp_obs_string_plan.h; the kernels are lpp_obs_kernels.h, lpp_obs_tj_kernels.h, lpp_obs_heis_kernels.h and lpp_obs_string_kernels.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -12,6 +15,7 @@
 #include <complex>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <tuple>
 #include <vector>
 
@@ -27,469 +31,33 @@ using namespace lpp::obs_host;
 
 namespace {
 
-// needs_new_basis, valid_op, binom, new_parts (HubbardOneOrbital::hasNewParts), Ranker (BasisOneSpin::perfectIndex): lpp_obs_string_plan.h
+// a planner's refusal (lpp_obs_plan.h, lpp_obs_tj_plan.h, lpp_obs_heis_plan.h, lpp_obs_string_plan.h) as a status
+inline lpp_status plan_status(bool ok, const char* why) { return ok ? LPP_OK : fail(LPP_ERR_INVALID, why); }
 
-enum { SP_C, SP_CDAGGER, SP_N };
-
-// one species: destination rank -> +-(source rank + 1) or 0.  kind: what the operator does to the KET word (BasisOneSpin::getBra :121-149);
-// with_sign: the parity of the ket's bits below `site` (doSignGf :112-136 for ind > 0 and both species; ProgramGlobals::doSign :109-114)
-void species_table(const Ranker& R, int L, int n_dst, int kind, int site, bool with_sign, int global_sign, std::vector<int32_t>& tab)
-{
-	const int64_t cnt = binom(L, n_dst);
-	tab.assign((size_t)cnt, 0);
-	if (cnt == 0) return;
-	const uint64_t bit = 1ull << site;
-	uint64_t w = (n_dst == 0) ? 0 : ((1ull << n_dst) - 1);
-	for (int64_t i = 0; i < cnt; i++) {
-		uint64_t ket = 0;
-		bool ok = false;
-		if (kind == SP_C) { // the bra lacks the bit the ket had
-			ok = !(w & bit);
-			ket = w | bit;
-		} else if (kind == SP_CDAGGER) {
-			ok = (w & bit) != 0;
-			ket = w ^ bit;
-		} else {
-			ok = (w & bit) != 0;
-			ket = w;
-		}
-		if (ok) {
-			int s = global_sign;
-			if (with_sign && (__builtin_popcountll(ket & (bit - 1)) & 1)) s = -s;
-			tab[(size_t)i] = (int32_t)(s * (R.rank(ket) + 1));
-		}
-		if (n_dst > 0 && i + 1 < cnt) { // next word of the same popcount (BasisOneSpin.h:53-61)
-			const uint64_t c = w & (~w + 1), r = w + c;
-			w = (((r ^ w) >> 2) / c) | r;
-		}
-	}
-}
-
-struct ObsPlan {
-	int nup2 = 0, ndn2 = 0;
-	int64_t n_up_src = 0, n_dn_src = 0, n_up_dst = 0, n_dn_dst = 0;
-	bool sz = false;
-	std::vector<int32_t> tu, td; // empty: the species is untouched
-};
-
-// has == false: the operator leads to no sector (hasNewParts refused)
-lpp_status obs_plan(int op, int site, int spin, int L, int nup, int ndn, bool* has, ObsPlan& P)
-{
-	*has = false;
-	if (!valid_op(op)) return fail(LPP_ERR_INVALID, "observables: unknown operator (LPP_OP_*)");
-	if (spin != LPP_SPIN_UP && spin != LPP_SPIN_DOWN) return fail(LPP_ERR_INVALID, "observables: spin must be LPP_SPIN_UP or LPP_SPIN_DOWN");
-	if (L < 1 || L > 30 || site < 0 || site >= L || nup < 0 || ndn < 0 || nup > L || ndn > L) return fail(LPP_ERR_INVALID, "observables: bad sites / site / sector");
-	P = ObsPlan();
-	P.nup2 = nup;
-	P.ndn2 = ndn;
-	if (needs_new_basis(op) && !new_parts(op, spin, L, nup, ndn, &P.nup2, &P.ndn2)) return LPP_OK;
-	P.n_up_src = binom(L, nup);
-	P.n_dn_src = binom(L, ndn);
-	P.n_up_dst = binom(L, P.nup2);
-	P.n_dn_dst = binom(L, P.ndn2);
-	if (P.n_up_src >= (int64_t)INT32_MAX - 4096 || P.n_dn_src >= (int64_t)INT32_MAX - 4096 || P.n_up_dst >= (int64_t)INT32_MAX - 4096 || P.n_dn_dst >= (int64_t)INT32_MAX - 4096)
-		return fail(LPP_ERR_INVALID, "observables: a species with 2^31 states or more");
-	const Ranker R(L);
-	const int kind = (op == LPP_OP_C) ? SP_C : SP_CDAGGER;
-	switch (op) {
-	case LPP_OP_C:
-	case LPP_OP_CDAGGER:
-		if (spin == LPP_SPIN_UP) {
-			species_table(R, L, P.nup2, kind, site, true, 1, P.tu);
-		} else {
-			// doSignGf, SPIN_DOWN: for ind > 0 the up parity computed first is overwritten by the parity of the down bits below ind;
-			// for ind == 0 the up parity is the whole sign (BasisHubbardLanczos.h:125-136) -- a constant of the source sector
-			const int up_parity = (site == 0 && (nup & 1)) ? -1 : 1;
-			species_table(R, L, P.ndn2, kind, site, site > 0, up_parity, P.td);
-		}
-		break;
-	case LPP_OP_N:
-		if (spin == LPP_SPIN_UP) species_table(R, L, nup, SP_N, site, false, 1, P.tu);
-		else species_table(R, L, ndn, SP_N, site, false, 1, P.td);
-		break;
-	case LPP_OP_SZ: // getBraIndexSz :210-223: +1 up only, -1 down only
-		species_table(R, L, nup, SP_N, site, false, 1, P.tu);
-		species_table(R, L, ndn, SP_N, site, false, 1, P.td);
-		P.sz = true;
-		break;
-	case LPP_OP_SPLUS: // getBraIndexSplusSminus :225-246: cdagger on the up word, c on the down word; sign doSignSpSm :151-160
-		species_table(R, L, P.nup2, SP_CDAGGER, site, true, 1, P.tu);
-		species_table(R, L, P.ndn2, SP_C, site, true, 1, P.td);
-		break;
-	case LPP_OP_SMINUS:
-		species_table(R, L, P.nup2, SP_C, site, true, 1, P.tu);
-		species_table(R, L, P.ndn2, SP_CDAGGER, site, true, 1, P.td);
-		break;
-	}
-	*has = true;
-	return LPP_OK;
-}
-
-// ---- a product of one-site operators composed into ONE pair of tables (planner: lpp_obs_string_plan.h, kernels: lpp_obs_string_kernels.h) ----
+// a product of one-site operators composed into ONE pair of tables (planner: lpp_obs_string_plan.h, kernels: lpp_obs_string_kernels.h)
 lpp_status string_plan(int conv, int nops, const int32_t* ops, const int32_t* sites, const int32_t* spins, const int32_t* flags, int L, int nup, int ndn, StringPlan& P)
 {
 	const char* why = nullptr;
-	if (!plan_string(conv, nops, ops, sites, spins, flags, L, nup, ndn, P, &why)) return fail(LPP_ERR_INVALID, why);
-	return LPP_OK;
-}
-
-// ---- the one-orbital t-J basis (BasisTjMultiOrbLanczos; kernel and lookup: lpp_obs_tj_kernels.h) ---------------------------------------
-
-// TjMultiOrb::hasNewParts (TjMultiOrb.h:140-159, :538-584) for c / cdagger / splus / sminus: the Hubbard rules, the spin read by splus / sminus as well,
-// no (0,0) sector for either pair, and no sector with more electrons than sites
-bool new_parts_tj(int op, int spin, int L, int nup, int ndn, int* n1, int* n2)
-{
-	int p1 = nup, p2 = ndn;
-	if (op == LPP_OP_C || op == LPP_OP_CDAGGER) {
-		const int c = (op == LPP_OP_CDAGGER) ? 1 : -1;
-		if (spin == LPP_SPIN_UP) p1 += c;
-		else p2 += c;
-	} else {
-		const int c = (op == LPP_OP_SPLUS) ? 1 : -1;
-		if (spin == LPP_SPIN_UP) {
-			p1 += c;
-			p2 -= c;
-		} else {
-			p2 += c;
-			p1 -= c;
-		}
-	}
-	if (p1 < 0 || p2 < 0) return false;
-	if (p1 > L || p2 > L) return false;
-	if (p1 == 0 && p2 == 0) return false;
-	if (p1 + p2 > L) return false; // no double occupancy
-	*n1 = p1;
-	*n2 = p2;
-	return true;
-}
-
-int64_t tj_sector_size(int L, int nup, int ndn) { return (L < 1 || L > 30 || nup < 0 || ndn < 0 || nup + ndn > L) ? -1 : binom(L, ndn) * binom(L - ndn, nup); }
-int64_t hubbard_sector_size(int L, int nup, int ndn) { return (L < 1 || L > 30 || nup < 0 || ndn < 0 || nup > L || ndn > L) ? -1 : binom(L, nup) * binom(L, ndn); }
-
-struct ObsTjPlan {
-	int nup2 = 0, ndn2 = 0, up = TJ_UP_SAME, lb = 0;
-	int64_t n_up_src = 0, n_dn_src = 0, n_up_dst = 0, n_dn_dst = 0;
-	std::vector<ObsTjDown> dn;
-	std::vector<uint32_t> pat;
-	std::vector<int32_t> hi_base;
-	std::vector<uint16_t> lo_rank;
-};
-
-// what the operator asks of the destination's down word d' and what the source's down word is
-enum { DN_KEEP_OUT, DN_KEEP_IN, DN_ADD, DN_REMOVE }; // site not in d', source d' | site in d', source d' | not in d', source d' + site | in d', source d' - site
-
-lpp_status obs_plan_tj(int op, int site, int spin, int L, int nup, int ndn, bool* has, ObsTjPlan& P)
-{
-	*has = false;
-	if (!valid_op(op)) return fail(LPP_ERR_INVALID, "t-J observables: unknown operator (LPP_OP_*)");
-	if (spin != LPP_SPIN_UP && spin != LPP_SPIN_DOWN) return fail(LPP_ERR_INVALID, "t-J observables: spin must be LPP_SPIN_UP or LPP_SPIN_DOWN");
-	if (site < 0 || site >= L || tj_sector_size(L, nup, ndn) < 0) return fail(LPP_ERR_INVALID, "t-J observables: bad sites / site / sector (nup + ndown <= sites <= 30)");
-	if ((op == LPP_OP_SPLUS || op == LPP_OP_SMINUS) && spin != LPP_SPIN_UP)
-		return fail(LPP_ERR_INVALID, "t-J observables: splus / sminus with spin DOWN: the reference's hasNewParts names the sector (nup -+ 1, ndown +- 1) while its getBraIndex "
-		                             "ignores the spin and makes states of (nup +- 1, ndown -+ 1), so it ranks words that are not in the basis; pass LPP_SPIN_UP");
-	P = ObsTjPlan();
-	P.nup2 = nup;
-	P.ndn2 = ndn;
-	if (needs_new_basis(op) && !new_parts_tj(op, spin, L, nup, ndn, &P.nup2, &P.ndn2)) return LPP_OK;
-	const int Ws = L - ndn, Wd = L - P.ndn2; // pattern widths: the sites free of down electrons
-	P.n_up_src = binom(Ws, nup);
-	P.n_dn_src = binom(L, ndn);
-	P.n_up_dst = binom(Wd, P.nup2);
-	P.n_dn_dst = binom(L, P.ndn2);
-	if (P.n_up_src >= (int64_t)INT32_MAX - 4096 || P.n_dn_src >= (int64_t)INT32_MAX - 4096 || P.n_up_dst >= (int64_t)INT32_MAX - 4096 || P.n_dn_dst >= (int64_t)INT32_MAX - 4096)
-		return fail(LPP_ERR_INVALID, "t-J observables: a species with 2^31 states or more");
-	int dkind = DN_KEEP_OUT;
-	bool down_sign = false;
-	switch (op) {
-	case LPP_OP_C:
-	case LPP_OP_CDAGGER:
-		if (spin == LPP_SPIN_UP) {
-			P.up = (op == LPP_OP_C) ? TJ_UP_SET : TJ_UP_CLEAR;
-		} else {
-			P.up = (op == LPP_OP_C) ? TJ_UP_DEL0 : TJ_UP_INS0;
-			dkind = (op == LPP_OP_C) ? DN_ADD : DN_REMOVE;
-			down_sign = true;
-		}
-		break;
-	case LPP_OP_N:
-	case LPP_OP_SZ: // getBraSzOrN (:456-469): the occupancy of `spin` for both
-		P.up = (spin == LPP_SPIN_UP) ? TJ_UP_TEST : TJ_UP_SAME;
-		dkind = (spin == LPP_SPIN_UP) ? DN_KEEP_OUT : DN_KEEP_IN;
-		break;
-	case LPP_OP_SPLUS:
-		P.up = TJ_UP_DEL1;
-		dkind = DN_ADD;
-		break;
-	case LPP_OP_SMINUS:
-		P.up = TJ_UP_INS1;
-		dkind = DN_REMOVE;
-		break;
-	}
-	if (P.up != TJ_UP_SAME) {
-		if (Ws > 2 * kObsTjMaxHalf) return fail(LPP_ERR_INVALID, "t-J observables: more than 24 sites free of down electrons (the pattern rank tables are kept in LDS)");
-		// rank(s) among the Ws-bit words of nup set bits, ascending = by the high half, then by the low half
-		P.lb = Ws / 2;
-		const int hb = Ws - P.lb;
-		std::vector<int> seen((size_t)P.lb + 1, 0);
-		P.lo_rank.resize((size_t)1 << P.lb);
-		for (uint32_t lo = 0; lo < (1u << P.lb); lo++) P.lo_rank[lo] = (uint16_t)seen[(size_t)__builtin_popcount(lo)]++;
-		P.hi_base.resize((size_t)1 << hb);
-		int64_t acc = 0;
-		for (uint32_t hi = 0; hi < (1u << hb); hi++) {
-			P.hi_base[hi] = (int32_t)acc;
-			acc += binom(P.lb, nup - __builtin_popcount(hi));
-		}
-		// the destination's patterns, ascending
-		P.pat.reserve((size_t)P.n_up_dst);
-		uint32_t w = (P.nup2 == 0) ? 0 : ((1u << P.nup2) - 1);
-		for (int64_t i = 0; i < P.n_up_dst; i++) {
-			P.pat.push_back(w);
-			if (P.nup2 > 0 && i + 1 < P.n_up_dst) {
-				const uint32_t c = w & (~w + 1), r = w + c;
-				w = (((r ^ w) >> 2) / c) | r;
-			}
-		}
-	}
-	const Ranker R(L);
-	P.dn.assign((size_t)P.n_dn_dst, ObsTjDown { 0, 0 });
-	const uint64_t bit = 1ull << site;
-	uint64_t d = (P.ndn2 == 0) ? 0 : ((1ull << P.ndn2) - 1);
-	for (int64_t i = 0; i < P.n_dn_dst; i++) {
-		const bool in = (d & bit) != 0;
-		const bool ok = (dkind == DN_KEEP_IN || dkind == DN_REMOVE) ? in : !in;
-		ObsTjDown& e = P.dn[(size_t)i];
-		e.p = __builtin_popcountll(~d & (bit - 1));
-		if (ok) {
-			const uint64_t sd = (dkind == DN_ADD || dkind == DN_REMOVE) ? (d ^ bit) : d;
-			int s = 1; // doSignGf, SPIN_DOWN (:180-191): the parity of the up electrons at EVERY site, times the parity of the down bits below the site
-			if (down_sign && ((nup + __builtin_popcountll(d & (bit - 1))) & 1)) s = -1;
-			e.src = (int32_t)(s * (R.rank(sd) + 1));
-		}
-		if (P.ndn2 > 0 && i + 1 < P.n_dn_dst) {
-			const uint64_t c = d & (~d + 1), r = d + c;
-			d = (((r ^ d) >> 2) / c) | r;
-		}
-	}
-	*has = true;
-	return LPP_OK;
-}
-
-// the plan expanded as the kernel walks it: action[dst] = +-(src + 1) or 0 (action may be null); *touched = destinations with a source
-void tj_expand(const ObsTjPlan& P, int64_t* action, int64_t* touched)
-{
-	int64_t cnt = 0;
-	for (int64_t dd = 0; dd < P.n_dn_dst; dd++)
-		for (int64_t du = 0; du < P.n_up_dst; du++) {
-			const int64_t k = obs_tj_source(P.up, P.dn[(size_t)dd], (uint32_t)du, P.pat.data(), P.hi_base.data(), P.lo_rank.data(), P.lb, P.n_up_src);
-			if (action) action[du + dd * P.n_up_dst] = k;
-			cnt += (k != 0);
-		}
-	if (touched) *touched = cnt;
-}
-
-// ---- the S = 1/2 Heisenberg basis (BasisHeisenberg, twiceS = 1; kernel and lookup: lpp_obs_heis_kernels.h) --------------------------------
-
-constexpr int kHeisMaxSites = 62; // as lpp_engine_assemble_heisenberg admits
-constexpr int64_t kHeisMaxRuns = (int64_t)1 << 22; // entries of the run table (24 bytes each)
-
-// C(n, k) in integers for n <= 62 (binom above goes through long double, which is not exact that far)
-int64_t heis_binom(int n, int k)
-{
-	static const std::vector<int64_t> tab = [] {
-		std::vector<int64_t> t((size_t)(kHeisMaxSites + 1) * (kHeisMaxSites + 1), 0);
-		for (int i = 0; i <= kHeisMaxSites; i++) {
-			t[(size_t)i * (kHeisMaxSites + 1)] = 1;
-			for (int j = 1; j <= i; j++) t[(size_t)i * (kHeisMaxSites + 1) + j] = t[(size_t)(i - 1) * (kHeisMaxSites + 1) + j - 1] + (j <= i - 1 ? t[(size_t)(i - 1) * (kHeisMaxSites + 1) + j] : 0);
-		}
-		return t;
-	}();
-	return (n < 0 || n > kHeisMaxSites || k < 0 || k > n) ? 0 : tab[(size_t)n * (kHeisMaxSites + 1) + k];
-}
-
-int64_t heis_sector_size(int L, int m, int) { return (L < 1 || L > kHeisMaxSites || m < 0 || m > L) ? -1 : heis_binom(L, m); }
-
-// Heisenberg::hasNewPartsSplusOrMinus (Heisenberg.h:218-240): szPlusConst +- 1, reported as (szPlusConst', 0).  false: S+ on all ups, S- on all downs --
-// the reference THROWS there (:239), and so it does for every other operator but sz (:129-133); the callers turn false into LPP_ERR_INVALID.
-bool new_parts_heis(int op, int, int L, int m, int, int* n1, int* n2)
-{
-	if (op != LPP_OP_SPLUS && op != LPP_OP_SMINUS) return false;
-	const int m2 = m + (op == LPP_OP_SPLUS ? 1 : -1);
-	if (m2 < 0 || m2 > L) return false;
-	*n1 = m2;
-	*n2 = 0;
-	return true;
-}
-
-// the low part of the word: 12 bits (two 16-bit tables of 4096 entries = 16 KiB of LDS, several workgroups per CU), more for long chains so that the
-// run table stays small
-int heis_low_bits(int L) { return std::min(L, std::max(12, std::min(kObsHeisMaxLow, L - 20))); }
-
-// index of the first word with high part h among the L-bit words of k set bits: the words below h << lb
-int64_t heis_run_start(uint64_t h, int hb, int lb, int k)
-{
-	int64_t n = 0;
-	int c = 0;
-	for (int b = hb - 1; b >= 0; b--)
-		if ((h >> b) & 1) n += heis_binom(b + lb, k - c++);
-	return n;
-}
-
-struct ObsHeisPlan {
-	int m2 = 0, mode = HEIS_RUN, lb = 0;
-	uint32_t bit = 0;
-	int64_t n_src = 0, n_dst = 0;
-	std::vector<ObsHeisRun> runs; // one closing entry at the end
-	std::vector<uint16_t> word, rank; // empty for HEIS_RUN
-};
-
-lpp_status obs_plan_heis(int op, int site, int spin, int L, int m, ObsHeisPlan& P)
-{
-	if (!valid_op(op)) return fail(LPP_ERR_INVALID, "Heisenberg observables: unknown operator (LPP_OP_*)");
-	if (op == LPP_OP_C || op == LPP_OP_CDAGGER) return fail(LPP_ERR_INVALID, "Heisenberg observables: c / cdagger are no operators of this model (the reference throws)");
-	if (spin != LPP_SPIN_UP && spin != LPP_SPIN_DOWN) return fail(LPP_ERR_INVALID, "Heisenberg observables: spin must be LPP_SPIN_UP or LPP_SPIN_DOWN");
-	if (site < 0 || site >= L || heis_sector_size(L, m, 0) < 0) return fail(LPP_ERR_INVALID, "Heisenberg observables: bad sites / site / sector (szPlusConst <= sites <= 62)");
-	P = ObsHeisPlan();
-	P.m2 = m;
-	int dummy = 0;
-	if (needs_new_basis(op) && !new_parts_heis(op, spin, L, m, 0, &P.m2, &dummy))
-		return fail(LPP_ERR_INVALID, "Heisenberg observables: S+ to all ups or S- to all downs (the reference throws)");
-	P.n_src = heis_binom(L, m);
-	P.n_dst = heis_binom(L, P.m2);
-	const int lb = P.lb = heis_low_bits(L), hb = L - lb;
-	const bool high = site >= lb, flip = needs_new_basis(op);
-	const uint64_t hbit = high ? 1ull << (site - lb) : 0;
-	if (!high) {
-		P.bit = 1u << site;
-		P.mode = (op == LPP_OP_SPLUS) ? HEIS_FLIP_SET : (op == LPP_OP_SMINUS) ? HEIS_FLIP_CLEAR : (op == LPP_OP_SZ) ? HEIS_SZ : (spin == LPP_SPIN_UP) ? HEIS_TEST_SET : HEIS_TEST_CLEAR;
-	}
-	// the non-empty runs: high parts whose popcount leaves 0 .. lb set bits to the low part, ascending
-	const int p_lo = std::max(0, P.m2 - lb), p_hi = std::min(hb, P.m2);
-	int64_t nruns = 0;
-	for (int p = p_lo; p <= p_hi && nruns <= kHeisMaxRuns; p++) nruns += heis_binom(hb, p);
-	if (nruns > kHeisMaxRuns) return fail(LPP_ERR_INVALID, "Heisenberg observables: the sector has more than 2^22 runs of equal high part (the run table's limit)");
-	std::vector<uint64_t> highs;
-	highs.reserve((size_t)nruns);
-	if (hb <= 22) {
-		for (uint64_t h = 0; h < (1ull << hb); h++) {
-			const int p = __builtin_popcountll(h);
-			if (p >= p_lo && p <= p_hi) highs.push_back(h);
-		}
-	} else { // few of very many: class by class (the next word of the same popcount, BasisOneSpin.h:53-61), then sorted
-		for (int p = p_lo; p <= p_hi; p++) {
-			uint64_t h = (p == 0) ? 0 : ((1ull << p) - 1);
-			for (int64_t i = 0, cnt = heis_binom(hb, p); i < cnt; i++) {
-				highs.push_back(h);
-				if (p > 0 && i + 1 < cnt) {
-					const uint64_t c = h & (~h + 1), r = h + c;
-					h = (((r ^ h) >> 2) / c) | r;
-				}
-			}
-		}
-		std::sort(highs.begin(), highs.end());
-	}
-	std::vector<int32_t> base((size_t)lb + 2, 0); // word[base[p] + r]
-	for (int p = 0; p <= lb; p++) base[(size_t)p + 1] = base[(size_t)p] + (int32_t)heis_binom(lb, p);
-	P.runs.reserve(highs.size() + 1);
-	int64_t acc = 0;
-	for (const uint64_t h : highs) {
-		const int ph = __builtin_popcountll(h), pl = P.m2 - ph;
-		ObsHeisRun R { acc, 0, pl, base[(size_t)pl] };
-		const bool set = (h & hbit) != 0;
-		if (flip) { // the destination (bra) has the bit set for splus and clear for sminus; the source is the word with the bit flipped, in sector m
-			const bool want = op == LPP_OP_SPLUS;
-			if (high) {
-				if (set == want) R.src = heis_run_start(h ^ hbit, hb, lb, m) + 1;
-			} else if (want ? pl >= 1 : pl <= lb - 1) { // (otherwise no low word of the run has the bit as asked)
-				R.src = heis_run_start(h, hb, lb, m) + 1;
-			}
-		} else if (!high) {
-			R.src = acc + 1;
-		} else if (op == LPP_OP_SZ) {
-			R.src = set ? -(acc + 1) : acc + 1;
-		} else if (set == (spin == LPP_SPIN_UP)) {
-			R.src = acc + 1;
-		}
-		P.runs.push_back(R);
-		acc += heis_binom(lb, pl);
-	}
-	if (acc != P.n_dst) return fail(LPP_ERR_INVALID, "Heisenberg observables: internal error, the runs do not add up to the sector");
-	P.runs.push_back(ObsHeisRun { P.n_dst, 0, 0, 0 });
-	if (P.mode != HEIS_RUN) {
-		P.word.resize((size_t)1 << lb);
-		P.rank.resize((size_t)1 << lb);
-		std::vector<int32_t> seen((size_t)lb + 1, 0);
-		for (uint32_t w = 0; w < (1u << lb); w++) {
-			const int p = __builtin_popcount(w);
-			P.rank[w] = (uint16_t)seen[(size_t)p];
-			P.word[(size_t)(base[(size_t)p] + seen[(size_t)p]++)] = (uint16_t)w;
-		}
-	}
-	return LPP_OK;
-}
-
-// the plan expanded as the kernel walks it (action may be null); *touched = destinations with a source
-void heis_expand(const ObsHeisPlan& P, int64_t* action, int64_t* touched)
-{
-	int64_t cnt = 0;
-	for (size_t k = 0; k + 1 < P.runs.size(); k++) {
-		const ObsHeisRun& R = P.runs[k];
-		for (int64_t r = 0, len = P.runs[k + 1].dst0 - R.dst0; r < len; r++) {
-			const int64_t s = obs_heis_source(P.mode, R, r, P.bit, P.word.data(), P.rank.data());
-			if (action) action[R.dst0 + r] = s;
-			cnt += (s != 0);
-		}
-	}
-	if (touched) *touched = cnt;
+	return plan_status(plan_string(conv, nops, ops, sites, spins, flags, L, nup, ndn, P, &why), why);
 }
 
 // ---- device side ---------------------------------------------------------------------------------------------------------------------
 
+// What the cache keeps of one planned operator: the sizes, and in the family's own struct (below) its host plan without the uploaded tables and the
+// device tables, freed by the destructor.
 struct DevPlan {
-	ObsPlan host; // tables dropped after the upload
-	bool has = false;
-	int32_t *tu = nullptr, *td = nullptr;
-	// the t-J basis: the plan (tables dropped after the upload likewise) and its four device tables
-	ObsTjPlan tj;
-	ObsTjDown* tj_dn = nullptr;
-	uint32_t* tj_pat = nullptr;
-	int32_t* tj_hi = nullptr;
-	uint16_t* tj_lo = nullptr;
-	int tj_nhi = 0, tj_nlo = 0;
-	// the Heisenberg basis: the plan (the run table and the low-word tables dropped after the upload) and its three device tables
-	ObsHeisPlan heis;
-	ObsHeisRun* hs_runs = nullptr;
-	uint16_t *hs_word = nullptr, *hs_rank = nullptr;
-	int64_t hs_nruns = 0;
-	int hs_nlo = 0;
+	bool has = false; // false: the operator leads to no sector
+	int64_t n_src = 0, n_dst = 0;
+	int64_t touched = 0; // destinations that have a source, for the byte model
+	size_t bytes = 0; // device bytes that count toward kMaxPlanBytes
+	virtual ~DevPlan() {}
 };
+typedef std::unique_ptr<DevPlan> DevPlanPtr;
 
-enum { BASIS_HUBBARD = 0, BASIS_TJ = 1, BASIS_HEIS = 2 };
-typedef std::tuple<int, int, int, int, int, int, int> PlanKey; // basis, operator, site, spin, sites, nup, ndown
-struct ObsCache {
-	std::map<PlanKey, DevPlan> plans;
-	size_t heis_bytes = 0; // device bytes of the Heisenberg run tables held (24 MB each at 32 sites)
-};
-
-inline bool multi(const lpp_engine* e) { return e->has_comm && e->comm.nranks > 1; }
-
-lpp_status refuse(const lpp_engine* e, const char* who, bool hole_major_ok = false)
+inline void free_tables(std::initializer_list<void*> tables)
 {
-	if (multi(e)) return fail(LPP_ERR_STATE, std::string(who) + ": not on a partitioned (multi-rank) engine");
-	if (e->tj.active && !hole_major_ok) return fail(LPP_ERR_STATE, std::string(who) + ": not on a hole-major t-J engine");
-	return LPP_OK;
-}
-
-void free_plan(DevPlan& D)
-{
-	for (void* p : { (void*)D.tu, (void*)D.td, (void*)D.tj_dn, (void*)D.tj_pat, (void*)D.tj_hi, (void*)D.tj_lo, (void*)D.hs_runs, (void*)D.hs_word, (void*)D.hs_rank })
+	for (void* p : tables)
 		if (p) (void)hipFree(p);
-	D.tu = D.td = nullptr;
-	D.tj_dn = nullptr;
-	D.tj_pat = nullptr;
-	D.tj_hi = nullptr;
-	D.tj_lo = nullptr;
-	D.hs_runs = nullptr;
-	D.hs_word = D.hs_rank = nullptr;
 }
 
 // one table to the device (at least one element is allocated); the host copy is dropped
@@ -501,66 +69,12 @@ template <typename V> hipError_t upload(V** dst, std::vector<V>& src)
 	return err;
 }
 
-// The tables of one (operator, site, spin, sites, sector), uploaded once and kept with the engine.  The key is what the caller passes -- the engine
-// needs no model for lpp_engine_apply_operator -- so the cache is bounded: a density of states or a two-point matrix uses at most 2 * sites entries
-// per operator; past kMaxPlans entries everything is dropped and rebuilt on demand.  The returned pointer is valid until the next get_plan.
-constexpr size_t kMaxPlans = 256;
-constexpr size_t kMaxHeisBytes = (size_t)1 << 30; // ... or past 1 GiB of Heisenberg run tables: a two-point sweep over 32 sites holds 0.8 GB of them
+inline bool multi(const lpp_engine* e) { return e->has_comm && e->comm.nranks > 1; }
 
-lpp_status get_plan(lpp_engine* e, int basis, int op, int site, int spin, int L, int nup, int ndn, const DevPlan** out)
+lpp_status refuse(const lpp_engine* e, const char* who, bool hole_major_ok = false)
 {
-	if (!e->obs) e->obs = new ObsCache();
-	ObsCache* C = (ObsCache*)e->obs;
-	if (basis == BASIS_HEIS) ndn = 0; // not read: one entry per sector
-	const PlanKey key(basis, op, site, spin, L, nup, ndn);
-	auto it = C->plans.find(key);
-	if (it == C->plans.end()) {
-		DevPlan D;
-		bool has = basis == BASIS_HEIS; // (this basis has no "no sector": the plan refuses where the reference throws)
-		lpp_status st = (basis == BASIS_HEIS) ? obs_plan_heis(op, site, spin, L, nup, D.heis)
-		                : (basis == BASIS_TJ) ? obs_plan_tj(op, site, spin, L, nup, ndn, &has, D.tj)
-		                                      : obs_plan(op, site, spin, L, nup, ndn, &has, D.host);
-		if (st != LPP_OK) return st;
-		D.has = has;
-		if (has) {
-			hipError_t err = hipSuccess;
-			if (basis == BASIS_HEIS) {
-				D.hs_nruns = (int64_t)D.heis.runs.size() - 1;
-				D.hs_nlo = (int)D.heis.word.size();
-				err = upload(&D.hs_runs, D.heis.runs);
-				if (err == hipSuccess) err = upload(&D.hs_word, D.heis.word);
-				if (err == hipSuccess) err = upload(&D.hs_rank, D.heis.rank);
-			} else if (basis == BASIS_TJ) {
-				D.tj_nhi = (int)D.tj.hi_base.size();
-				D.tj_nlo = (int)D.tj.lo_rank.size();
-				err = upload(&D.tj_dn, D.tj.dn);
-				if (err == hipSuccess) err = upload(&D.tj_pat, D.tj.pat);
-				if (err == hipSuccess) err = upload(&D.tj_hi, D.tj.hi_base);
-				if (err == hipSuccess) err = upload(&D.tj_lo, D.tj.lo_rank);
-			} else { // an empty table stays null: the species is untouched
-				if (!D.host.tu.empty()) err = upload(&D.tu, D.host.tu);
-				if (err == hipSuccess && !D.host.td.empty()) err = upload(&D.td, D.host.td);
-			}
-			if (err != hipSuccess) {
-				free_plan(D); // the tables uploaded so far
-				if (err == hipErrorOutOfMemory) {
-					(void)hipGetLastError();
-					return fail(LPP_ERR_NOMEM, "observables: no device memory for the operator tables");
-				}
-				HIP_TRY(err);
-			}
-		}
-		const size_t run_bytes = (basis == BASIS_HEIS) ? sizeof(ObsHeisRun) * (size_t)(D.hs_nruns + 1) : 0;
-		if (C->plans.size() >= kMaxPlans || C->heis_bytes + run_bytes > kMaxHeisBytes) {
-			HIP_TRY(hipStreamSynchronize(e->stream)); // launches that still read the old tables
-			for (auto& kv : C->plans) free_plan(kv.second);
-			C->plans.clear();
-			C->heis_bytes = 0;
-		}
-		C->heis_bytes += run_bytes;
-		it = C->plans.emplace(key, D).first;
-	}
-	*out = &it->second;
+	if (multi(e)) return fail(LPP_ERR_STATE, std::string(who) + ": not on a partitioned (multi-rank) engine");
+	if (e->tj.active && !hole_major_ok) return fail(LPP_ERR_STATE, std::string(who) + ": not on a hole-major t-J engine");
 	return LPP_OK;
 }
 
@@ -568,6 +82,208 @@ int obs_grid(const lpp_engine* e, int64_t units)
 {
 	const int64_t tiles = (units + kObsTile - 1) / kObsTile;
 	return (int)std::max<int64_t>(1, std::min<int64_t>(tiles, (int64_t)e->num_cus * 32));
+}
+
+// The one launch of a destination-driven kernel template <CPLX, ACC>(dst, src, args) over n destination elements: 16-byte units in tiles of kObsTile,
+// at most 32 blocks per CU, on the engine's stream.  Returns from the calling function on a launch error.
+#define OBS_LAUNCH(kernel, e, acc, n, lds, d_dst, d_src, args)                                                                     \
+	do {                                                                                                                           \
+		const int64_t n_ = (n);                                                                                                    \
+		const int g_ = obs_grid((e), (e)->is_complex ? n_ : (n_ + 1) / 2);                                                         \
+		if ((e)->is_complex) {                                                                                                     \
+			if (acc) kernel<true, true><<<g_, kObsBlock, (lds), (e)->stream>>>((double*)(d_dst), (const double*)(d_src), (args));  \
+			else kernel<true, false><<<g_, kObsBlock, (lds), (e)->stream>>>((double*)(d_dst), (const double*)(d_src), (args));     \
+		} else {                                                                                                                   \
+			if (acc) kernel<false, true><<<g_, kObsBlock, (lds), (e)->stream>>>((double*)(d_dst), (const double*)(d_src), (args)); \
+			else kernel<false, false><<<g_, kObsBlock, (lds), (e)->stream>>>((double*)(d_dst), (const double*)(d_src), (args));    \
+		}                                                                                                                          \
+		HIP_TRY(hipGetLastError());                                                                                                \
+	} while (0)
+
+// Everything the entry points below need to know about a basis: they are written once and run for every family.
+struct ObsBasis {
+	int id;
+	bool hole_major_ok; // a hole-major t-J engine is admitted (its resident states and start vectors pass through S.perm)
+	bool reads_ndown; // false: one count names the sector, ndown is not read (one cache entry per sector)
+	bool fermions; // c / cdagger are operators of the model
+	bool no_sector_throws; // new_parts == false is where the reference throws: LPP_ERR_INVALID instead of "no such sector"
+	bool sz_has_no_parts; // lpp_obs_new_parts*: sz answers "no new sector" (otherwise it is unsupported like n)
+	bool (*counts_ok)(int L, int nup, int ndn); // lpp_obs_new_parts*: the sector check
+	int64_t (*sector_size)(int L, int nup, int ndn); // < 0: not a sector
+	bool (*new_parts)(int op, int spin, int L, int nup, int ndn, int* n1, int* n2);
+	// the plan of one operator, sizes and touched count filled in, its tables uploaded; *err: what the upload met (the caller frees the partial plan)
+	lpp_status (*build)(int op, int site, int spin, int L, int nup, int ndn, DevPlanPtr& out, hipError_t* err);
+	// z (+)= factor * A src through a plan with has and n_dst > 0
+	lpp_status (*launch)(lpp_engine* e, const DevPlan& D, double fr, double fi, const void* d_src, void* d_dst, bool acc);
+};
+
+// ---- the Hubbard product basis (plan: lpp_obs_plan.h, kernel: lpp_obs_kernels.h) ---------------------------------------------------------------
+struct HubbardDev : DevPlan {
+	ObsPlan host; // tables dropped after the upload
+	int32_t *tu = nullptr, *td = nullptr; // null: the species is untouched
+	~HubbardDev() override { free_tables({ tu, td }); }
+};
+
+lpp_status build_hubbard(int op, int site, int spin, int L, int nup, int ndn, DevPlanPtr& out, hipError_t* err)
+{
+	std::unique_ptr<HubbardDev> D(new HubbardDev());
+	ObsPlan& P = D->host;
+	const char* why = nullptr;
+	lpp_status st = plan_status(obs_plan(op, site, spin, L, nup, ndn, &D->has, P, &why), why);
+	if (st != LPP_OK) return st;
+	D->n_src = P.n_up_src * P.n_dn_src;
+	D->n_dst = P.n_up_dst * P.n_dn_dst;
+	if (D->has) {
+		D->touched = obs_touched(P);
+		if (!P.tu.empty()) *err = upload(&D->tu, P.tu);
+		if (*err == hipSuccess && !P.td.empty()) *err = upload(&D->td, P.td);
+	}
+	out = std::move(D);
+	return LPP_OK;
+}
+
+lpp_status launch_hubbard(lpp_engine* e, const DevPlan& D0, double fr, double fi, const void* d_src, void* d_dst, bool acc)
+{
+	const HubbardDev& D = static_cast<const HubbardDev&>(D0);
+	const ObsPlan& P = D.host;
+	ObsArgs A { D.tu, D.td, P.n_up_dst, P.n_dn_dst, P.n_up_src, P.sz ? 1 : 0, fr, fi };
+	OBS_LAUNCH(k_obs_apply, e, acc, D.n_dst, 0, d_dst, d_src, A);
+	return LPP_OK;
+}
+
+// ---- the one-orbital t-J basis (plan: lpp_obs_tj_plan.h, kernel: lpp_obs_tj_kernels.h) -------------------------------------------------------
+struct TjDev : DevPlan {
+	ObsTjPlan host; // tables dropped after the upload
+	ObsTjDown* dn = nullptr;
+	uint32_t* pat = nullptr;
+	int32_t* hi = nullptr;
+	uint16_t* lo = nullptr;
+	int nhi = 0, nlo = 0;
+	~TjDev() override { free_tables({ dn, pat, hi, lo }); }
+};
+
+lpp_status build_tj(int op, int site, int spin, int L, int nup, int ndn, DevPlanPtr& out, hipError_t* err)
+{
+	std::unique_ptr<TjDev> D(new TjDev());
+	ObsTjPlan& P = D->host;
+	const char* why = nullptr;
+	lpp_status st = plan_status(obs_plan_tj(op, site, spin, L, nup, ndn, &D->has, P, &why), why);
+	if (st != LPP_OK) return st;
+	D->n_src = P.n_up_src * P.n_dn_src;
+	D->n_dst = P.n_up_dst * P.n_dn_dst;
+	if (D->has) {
+		D->touched = tj_touched(op, spin, L, P.nup2, P.ndn2);
+		D->nhi = (int)P.hi_base.size();
+		D->nlo = (int)P.lo_rank.size();
+		*err = upload(&D->dn, P.dn);
+		if (*err == hipSuccess) *err = upload(&D->pat, P.pat);
+		if (*err == hipSuccess) *err = upload(&D->hi, P.hi_base);
+		if (*err == hipSuccess) *err = upload(&D->lo, P.lo_rank);
+	}
+	out = std::move(D);
+	return LPP_OK;
+}
+
+lpp_status launch_tj(lpp_engine* e, const DevPlan& D0, double fr, double fi, const void* d_src, void* d_dst, bool acc)
+{
+	const TjDev& D = static_cast<const TjDev&>(D0);
+	const ObsTjPlan& P = D.host;
+	ObsTjArgs A { D.dn, D.pat, D.hi, D.lo, P.up, P.lb, D.nhi, D.nlo, P.n_up_dst, P.n_dn_dst, P.n_up_src, fr, fi };
+	OBS_LAUNCH(k_obs_apply_tj, e, acc, D.n_dst, obs_tj_lds_bytes(A.nhi, A.nlo), d_dst, d_src, A);
+	return LPP_OK;
+}
+
+// ---- the S = 1/2 Heisenberg basis (plan: lpp_obs_heis_plan.h, kernel: lpp_obs_heis_kernels.h); nup = szPlusConst -----------------------------
+struct HeisDev : DevPlan {
+	ObsHeisPlan host; // the run table and the low-word tables dropped after the upload
+	ObsHeisRun* runs = nullptr;
+	uint16_t *word = nullptr, *rank = nullptr;
+	int64_t nruns = 0;
+	int nlo = 0;
+	~HeisDev() override { free_tables({ runs, word, rank }); }
+};
+
+lpp_status build_heis(int op, int site, int spin, int L, int nup, int, DevPlanPtr& out, hipError_t* err)
+{
+	std::unique_ptr<HeisDev> D(new HeisDev());
+	ObsHeisPlan& P = D->host;
+	const char* why = nullptr;
+	lpp_status st = plan_status(obs_plan_heis(op, site, spin, L, nup, P, &why), why);
+	if (st != LPP_OK) return st;
+	D->has = true; // (this basis has no "no sector": the plan refuses where the reference throws)
+	D->n_src = P.n_src;
+	D->n_dst = P.n_dst;
+	D->touched = heis_touched(op, spin, L, P.m2);
+	D->nruns = (int64_t)P.runs.size() - 1;
+	D->nlo = (int)P.word.size();
+	D->bytes = sizeof(ObsHeisRun) * P.runs.size(); // 24 MB at 32 sites
+	*err = upload(&D->runs, P.runs);
+	if (*err == hipSuccess) *err = upload(&D->word, P.word);
+	if (*err == hipSuccess) *err = upload(&D->rank, P.rank);
+	out = std::move(D);
+	return LPP_OK;
+}
+
+lpp_status launch_heis(lpp_engine* e, const DevPlan& D0, double fr, double fi, const void* d_src, void* d_dst, bool acc)
+{
+	const HeisDev& D = static_cast<const HeisDev&>(D0);
+	const ObsHeisPlan& P = D.host;
+	ObsHeisArgs A { D.runs, D.word, D.rank, P.mode, D.nlo, P.bit, D.nruns, D.n_dst, fr, fi };
+	OBS_LAUNCH(k_obs_apply_heis, e, acc, D.n_dst, obs_heis_lds_bytes(A.mode, A.nlo), d_dst, d_src, A);
+	return LPP_OK;
+}
+
+enum { BASIS_HUBBARD = 0, BASIS_TJ = 1, BASIS_HEIS = 2 };
+const ObsBasis kHubbard { BASIS_HUBBARD, false, true, true, false, true, [](int L, int nup, int ndn) { return L >= 1 && nup >= 0 && ndn >= 0 && nup <= L && ndn <= L; },
+	                      hubbard_sector_size, new_parts, build_hubbard, launch_hubbard };
+const ObsBasis kTj { BASIS_TJ, true, true, true, false, false, [](int L, int nup, int ndn) { return L >= 1 && nup >= 0 && ndn >= 0 && nup + ndn <= L; },
+	                 tj_sector_size, new_parts_tj, build_tj, launch_tj };
+const ObsBasis kHeis { BASIS_HEIS, false, false, false, true, true, [](int L, int nup, int) { return heis_sector_size(L, nup, 0) >= 0; },
+	                   heis_sector_size, new_parts_heis, build_heis, launch_heis };
+
+// The tables of one (operator, site, spin, sites, sector), uploaded once and kept with the engine.  The key is what the caller passes -- the engine
+// needs no model for lpp_engine_apply_operator -- so the cache is bounded: a density of states or a two-point matrix uses at most 2 * sites entries
+// per operator; past kMaxPlans entries everything is dropped and rebuilt on demand.  The returned pointer is valid until the next get_plan.
+constexpr size_t kMaxPlans = 256;
+// ... or past 1 GiB of DevPlan::bytes, which counts the Heisenberg run tables alone: a two-point sweep over 32 sites holds 0.8 GB of them, every
+// other table is a species' or a half word's size
+constexpr size_t kMaxPlanBytes = (size_t)1 << 30;
+typedef std::tuple<int, int, int, int, int, int, int> PlanKey; // basis, operator, site, spin, sites, nup, ndown
+struct ObsCache {
+	std::map<PlanKey, DevPlanPtr> plans;
+	size_t bytes = 0; // DevPlan::bytes summed over the plans
+};
+
+lpp_status get_plan(lpp_engine* e, const ObsBasis& B, int op, int site, int spin, int L, int nup, int ndn, const DevPlan** out)
+{
+	if (!e->obs) e->obs = new ObsCache();
+	ObsCache* C = (ObsCache*)e->obs;
+	if (!B.reads_ndown) ndn = 0;
+	const PlanKey key(B.id, op, site, spin, L, nup, ndn);
+	auto it = C->plans.find(key);
+	if (it == C->plans.end()) {
+		DevPlanPtr D;
+		hipError_t err = hipSuccess;
+		lpp_status st = B.build(op, site, spin, L, nup, ndn, D, &err);
+		if (st != LPP_OK) return st;
+		if (err != hipSuccess) {
+			D.reset(); // the tables uploaded so far
+			if (err == hipErrorOutOfMemory) {
+				(void)hipGetLastError();
+				return fail(LPP_ERR_NOMEM, "observables: no device memory for the operator tables");
+			}
+			HIP_TRY(err);
+		}
+		if (C->plans.size() >= kMaxPlans || C->bytes + D->bytes > kMaxPlanBytes) {
+			HIP_TRY(hipStreamSynchronize(e->stream)); // launches that still read the old tables
+			C->plans.clear();
+			C->bytes = 0;
+		}
+		C->bytes += D->bytes;
+		it = C->plans.emplace(key, std::move(D)).first;
+	}
+	*out = it->second.get();
+	return LPP_OK;
 }
 
 lpp_status check_vectors(const lpp_engine* e, double fi, const void* d_src, const void* d_dst)
@@ -581,151 +297,28 @@ lpp_status check_vectors(const lpp_engine* e, double fi, const void* d_src, cons
 }
 
 // z (+)= factor * A src on device vectors in the basis order; *has == false: no such sector, nothing was launched
-lpp_status apply_dev(lpp_engine* e, int op, int site, int spin, int L, int nup, int ndn, double fr, double fi, const void* d_src, void* d_dst, bool acc, bool* has,
-                     int64_t* n_dst)
+lpp_status apply_dev(lpp_engine* e, const ObsBasis& B, int op, int site, int spin, int L, int nup, int ndn, double fr, double fi, const void* d_src, void* d_dst, bool acc,
+                     bool* has)
 {
 	const DevPlan* D = nullptr;
-	lpp_status st = get_plan(e, BASIS_HUBBARD, op, site, spin, L, nup, ndn, &D);
+	lpp_status st = get_plan(e, B, op, site, spin, L, nup, ndn, &D);
 	if (st != LPP_OK) return st;
 	*has = D->has;
 	if (!D->has) return LPP_OK;
-	const ObsPlan& P = D->host;
-	if (n_dst) *n_dst = P.n_up_dst * P.n_dn_dst;
 	if ((st = check_vectors(e, fi, d_src, d_dst)) != LPP_OK) return st;
-	const int64_t nd = P.n_up_dst * P.n_dn_dst;
-	if (nd == 0) return LPP_OK;
-	ObsArgs A { D->tu, D->td, P.n_up_dst, P.n_dn_dst, P.n_up_src, P.sz ? 1 : 0, fr, fi };
-	const int64_t units = e->is_complex ? nd : (nd + 1) / 2;
-	const int g = obs_grid(e, units);
-	if (e->is_complex) {
-		if (acc) k_obs_apply<true, true><<<g, kObsBlock, 0, e->stream>>>((double*)d_dst, (const double*)d_src, A);
-		else k_obs_apply<true, false><<<g, kObsBlock, 0, e->stream>>>((double*)d_dst, (const double*)d_src, A);
-	} else {
-		if (acc) k_obs_apply<false, true><<<g, kObsBlock, 0, e->stream>>>((double*)d_dst, (const double*)d_src, A);
-		else k_obs_apply<false, false><<<g, kObsBlock, 0, e->stream>>>((double*)d_dst, (const double*)d_src, A);
-	}
-	HIP_TRY(hipGetLastError());
-	return LPP_OK;
-}
-
-// the same in the t-J basis (k_obs_apply_tj)
-lpp_status apply_dev_tj(lpp_engine* e, int op, int site, int spin, int L, int nup, int ndn, double fr, double fi, const void* d_src, void* d_dst, bool acc, bool* has,
-                        int64_t* n_dst)
-{
-	const DevPlan* D = nullptr;
-	lpp_status st = get_plan(e, BASIS_TJ, op, site, spin, L, nup, ndn, &D);
-	if (st != LPP_OK) return st;
-	*has = D->has;
-	if (!D->has) return LPP_OK;
-	const ObsTjPlan& P = D->tj;
-	const int64_t nd = P.n_up_dst * P.n_dn_dst;
-	if (n_dst) *n_dst = nd;
-	if ((st = check_vectors(e, fi, d_src, d_dst)) != LPP_OK) return st;
-	if (nd == 0) return LPP_OK;
-	ObsTjArgs A { D->tj_dn, D->tj_pat, D->tj_hi, D->tj_lo, P.up, P.lb, D->tj_nhi, D->tj_nlo, P.n_up_dst, P.n_dn_dst, P.n_up_src, fr, fi };
-	const int64_t units = e->is_complex ? nd : (nd + 1) / 2;
-	const int g = obs_grid(e, units);
-	const size_t lds = obs_tj_lds_bytes(A.nhi, A.nlo);
-	if (e->is_complex) {
-		if (acc) k_obs_apply_tj<true, true><<<g, kObsBlock, lds, e->stream>>>((double*)d_dst, (const double*)d_src, A);
-		else k_obs_apply_tj<true, false><<<g, kObsBlock, lds, e->stream>>>((double*)d_dst, (const double*)d_src, A);
-	} else {
-		if (acc) k_obs_apply_tj<false, true><<<g, kObsBlock, lds, e->stream>>>((double*)d_dst, (const double*)d_src, A);
-		else k_obs_apply_tj<false, false><<<g, kObsBlock, lds, e->stream>>>((double*)d_dst, (const double*)d_src, A);
-	}
-	HIP_TRY(hipGetLastError());
-	return LPP_OK;
-}
-
-// the same in the S = 1/2 Heisenberg basis (k_obs_apply_heis); nup = szPlusConst, ndown is not read
-lpp_status apply_dev_heis(lpp_engine* e, int op, int site, int spin, int L, int nup, int, double fr, double fi, const void* d_src, void* d_dst, bool acc, bool* has,
-                          int64_t* n_dst)
-{
-	const DevPlan* D = nullptr;
-	lpp_status st = get_plan(e, BASIS_HEIS, op, site, spin, L, nup, 0, &D);
-	if (st != LPP_OK) return st;
-	*has = true;
-	const ObsHeisPlan& P = D->heis;
-	const int64_t nd = P.n_dst;
-	if (n_dst) *n_dst = nd;
-	if ((st = check_vectors(e, fi, d_src, d_dst)) != LPP_OK) return st;
-	ObsHeisArgs A { D->hs_runs, D->hs_word, D->hs_rank, P.mode, D->hs_nlo, P.bit, D->hs_nruns, nd, fr, fi };
-	const int64_t units = e->is_complex ? nd : (nd + 1) / 2;
-	const int g = obs_grid(e, units);
-	const size_t lds = obs_heis_lds_bytes(A.mode, A.nlo);
-	if (e->is_complex) {
-		if (acc) k_obs_apply_heis<true, true><<<g, kObsBlock, lds, e->stream>>>((double*)d_dst, (const double*)d_src, A);
-		else k_obs_apply_heis<true, false><<<g, kObsBlock, lds, e->stream>>>((double*)d_dst, (const double*)d_src, A);
-	} else {
-		if (acc) k_obs_apply_heis<false, true><<<g, kObsBlock, lds, e->stream>>>((double*)d_dst, (const double*)d_src, A);
-		else k_obs_apply_heis<false, false><<<g, kObsBlock, lds, e->stream>>>((double*)d_dst, (const double*)d_src, A);
-	}
-	HIP_TRY(hipGetLastError());
-	return LPP_OK;
-}
-
-// Everything the entry points below need to know about a basis: they are written once and run for every family.
-struct ObsBasis {
-	int id;
-	bool hole_major_ok; // a hole-major t-J engine is admitted (its resident states and start vectors pass through S.perm)
-	int64_t (*sector_size)(int L, int nup, int ndn); // < 0: not a sector
-	bool (*new_parts)(int op, int spin, int L, int nup, int ndn, int* n1, int* n2);
-	lpp_status (*apply)(lpp_engine* e, int op, int site, int spin, int L, int nup, int ndn, double fr, double fi, const void* d_src, void* d_dst, bool acc, bool* has,
-	                    int64_t* n_dst);
-	bool no_sector_throws; // new_parts == false is where the reference throws: LPP_ERR_INVALID instead of "no such sector"
-};
-const ObsBasis kHubbard { BASIS_HUBBARD, false, hubbard_sector_size, new_parts, apply_dev, false };
-const ObsBasis kTj { BASIS_TJ, true, tj_sector_size, new_parts_tj, apply_dev_tj, false };
-const ObsBasis kHeis { BASIS_HEIS, false, heis_sector_size, new_parts_heis, apply_dev_heis, true };
-
-// sizes of the plan's two sectors, and (touched != null) the destinations that have a source
-lpp_status plan_sizes(lpp_engine* e, const ObsBasis& B, int op, int site, int spin, int L, int nup, int ndn, bool* has, int64_t* ns, int64_t* nd, int64_t* touched)
-{
-	const DevPlan* D = nullptr;
-	lpp_status st = get_plan(e, B.id, op, site, spin, L, nup, ndn, &D);
-	if (st != LPP_OK) return st;
-	*has = D->has;
-	if (!D->has) return LPP_OK;
-	if (B.id == BASIS_HEIS) {
-		*ns = D->heis.n_src;
-		*nd = D->heis.n_dst;
-	} else if (B.id == BASIS_TJ) {
-		*ns = D->tj.n_up_src * D->tj.n_dn_src;
-		*nd = D->tj.n_up_dst * D->tj.n_dn_dst;
-	} else {
-		*ns = D->host.n_up_src * D->host.n_dn_src;
-		*nd = D->host.n_up_dst * D->host.n_dn_dst;
-	}
-	if (!touched) return LPP_OK;
-	bool hh = false;
-	if (B.id == BASIS_HEIS) { // sz touches every destination; splus / sminus / n those with the site's bit as asked: the other L - 1 bits are free
-		const int m2 = D->heis.m2;
-		const bool bit_set = op == LPP_OP_SPLUS || (op == LPP_OP_N && spin == LPP_SPIN_UP);
-		*touched = (op == LPP_OP_SZ) ? D->heis.n_dst : heis_binom(L - 1, bit_set ? m2 - 1 : m2);
-	} else if (B.id == BASIS_TJ) {
-		ObsTjPlan P;
-		if ((st = obs_plan_tj(op, site, spin, L, nup, ndn, &hh, P)) != LPP_OK) return st;
-		tj_expand(P, nullptr, touched);
-	} else {
-		ObsPlan P;
-		if ((st = obs_plan(op, site, spin, L, nup, ndn, &hh, P)) != LPP_OK) return st;
-		int64_t cu = P.n_up_dst, cd = P.n_dn_dst;
-		if (!P.tu.empty()) cu = (int64_t)std::count_if(P.tu.begin(), P.tu.end(), [](int32_t v) { return v != 0; });
-		if (!P.td.empty()) cd = (int64_t)std::count_if(P.td.begin(), P.td.end(), [](int32_t v) { return v != 0; });
-		*touched = cu * cd;
-	}
-	return LPP_OK;
+	if (D->n_dst == 0) return LPP_OK;
+	return B.launch(e, *D, fr, fi, d_src, d_dst, acc);
 }
 
 // the operator Engine::accModifiedState applies (Engine.h:535-599): n directly, sz as n_up/2 - n_down/2, the others as given
 lpp_status acc_modified_dev(lpp_engine* e, const ObsBasis& B, int op, int site, int spin, int L, int nup, int ndn, double isign, const void* d_src, void* d_dst, bool acc, bool* has)
 {
 	if (op == LPP_OP_SZ) {
-		lpp_status st = B.apply(e, LPP_OP_N, site, LPP_SPIN_UP, L, nup, ndn, isign * 0.5, 0.0, d_src, d_dst, acc, has, nullptr);
+		lpp_status st = apply_dev(e, B, LPP_OP_N, site, LPP_SPIN_UP, L, nup, ndn, isign * 0.5, 0.0, d_src, d_dst, acc, has);
 		if (st != LPP_OK) return st;
-		return B.apply(e, LPP_OP_N, site, LPP_SPIN_DOWN, L, nup, ndn, -isign * 0.5, 0.0, d_src, d_dst, true, has, nullptr);
+		return apply_dev(e, B, LPP_OP_N, site, LPP_SPIN_DOWN, L, nup, ndn, -isign * 0.5, 0.0, d_src, d_dst, true, has);
 	}
-	return B.apply(e, op, site, spin, L, nup, ndn, isign, 0.0, d_src, d_dst, acc, has, nullptr);
+	return apply_dev(e, B, op, site, spin, L, nup, ndn, isign, 0.0, d_src, d_dst, acc, has);
 }
 
 int blas_blocks(int64_t n2)
@@ -749,9 +342,24 @@ lpp_status apply_operator_body(const ObsBasis& B, const char* who, lpp_engine* e
 	if (st != LPP_OK) return st;
 	HIP_TRY(hipSetDevice(e->cfg.device));
 	bool h = false;
-	st = B.apply(e, op, site, spin, nsites, nup, ndown, factor_re, factor_im, d_src, d_dst, accumulate != 0, &h, nullptr);
+	st = apply_dev(e, B, op, site, spin, nsites, nup, ndown, factor_re, factor_im, d_src, d_dst, accumulate != 0, &h);
 	*has = h ? 1 : 0;
 	return st;
+}
+
+// host vectors of ns / nd bytes staged on the device around run(d_src, d_dst): the source up, the destination up where it is accumulated into, and back
+template <typename Run> lpp_status staged(lpp_engine* e, size_t ns, size_t nd, const void* src, void* dst, int32_t accumulate, Run&& run)
+{
+	DevBuf ds, dd;
+	HIP_TRY_MEM(hipMalloc(&ds.p, std::max<size_t>(ns, 16)));
+	HIP_TRY_MEM(hipMalloc(&dd.p, std::max<size_t>(nd, 16) + 16));
+	HIP_TRY(hipMemcpyAsync(ds.p, src, ns, hipMemcpyHostToDevice, e->stream));
+	if (accumulate) HIP_TRY(hipMemcpyAsync(dd.p, dst, nd, hipMemcpyHostToDevice, e->stream));
+	lpp_status st = run(ds.p, dd.p);
+	if (st != LPP_OK) return st;
+	HIP_TRY(hipMemcpyAsync(dst, dd.p, nd, hipMemcpyDeviceToHost, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	return LPP_OK;
 }
 
 lpp_status apply_operator_host_body(const ObsBasis& B, const char* who, lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown,
@@ -761,23 +369,44 @@ lpp_status apply_operator_host_body(const ObsBasis& B, const char* who, lpp_engi
 	lpp_status st = refuse(e, who, B.hole_major_ok);
 	if (st != LPP_OK) return st;
 	HIP_TRY(hipSetDevice(e->cfg.device));
-	bool planned = false;
-	int64_t es = 0, ed = 0;
-	st = plan_sizes(e, B, op, site, spin, nsites, nup, ndown, &planned, &es, &ed, nullptr);
+	const DevPlan* D = nullptr;
+	if ((st = get_plan(e, B, op, site, spin, nsites, nup, ndown, &D)) != LPP_OK) return st;
+	*has = D->has ? 1 : 0;
+	if (!D->has) return LPP_OK;
+	return staged(e, e->esz * (size_t)D->n_src, e->esz * (size_t)D->n_dst, src, dst, accumulate, [&](const void* d_src, void* d_dst) {
+		bool h = false;
+		return apply_dev(e, B, op, site, spin, nsites, nup, ndown, factor_re, factor_im, d_src, d_dst, accumulate != 0, &h);
+	});
+}
+
+// milliseconds per step over `iters` steps after `warmup` untimed ones, between two events on the engine's stream; a failing step ends the loop
+struct EventPair {
+	hipEvent_t a = nullptr, b = nullptr;
+	~EventPair()
+	{
+		if (a) (void)hipEventDestroy(a);
+		if (b) (void)hipEventDestroy(b);
+	}
+};
+template <typename Step> lpp_status timed_steps(lpp_engine* e, int warmup, int iters, double* ms_per_step, Step&& step)
+{
+	EventPair ev;
+	hipEvent_t &t0 = ev.a, &t1 = ev.b;
+	HIP_TRY(hipEventCreate(&t0));
+	HIP_TRY(hipEventCreate(&t1));
+	lpp_status st = LPP_OK;
+	for (int i = 0; i < warmup + iters && st == LPP_OK; i++) {
+		if (i == warmup) (void)hipEventRecord(t0, e->stream);
+		st = step();
+	}
+	(void)hipEventRecord(t1, e->stream);
+	hipError_t err = hipEventSynchronize(t1);
+	float ms = 0;
+	if (err == hipSuccess) err = hipEventElapsedTime(&ms, t0, t1);
+	if (err == hipSuccess) err = hipGetLastError();
 	if (st != LPP_OK) return st;
-	*has = planned ? 1 : 0;
-	if (!planned) return LPP_OK;
-	const size_t ns = e->esz * (size_t)es, nd = e->esz * (size_t)ed;
-	DevBuf ds, dd;
-	HIP_TRY_MEM(hipMalloc(&ds.p, std::max<size_t>(ns, 16)));
-	HIP_TRY_MEM(hipMalloc(&dd.p, std::max<size_t>(nd, 16) + 16));
-	HIP_TRY(hipMemcpyAsync(ds.p, src, ns, hipMemcpyHostToDevice, e->stream));
-	if (accumulate) HIP_TRY(hipMemcpyAsync(dd.p, dst, nd, hipMemcpyHostToDevice, e->stream));
-	bool h = false;
-	st = B.apply(e, op, site, spin, nsites, nup, ndown, factor_re, factor_im, ds.p, dd.p, accumulate != 0, &h, nullptr);
-	if (st != LPP_OK) return st;
-	HIP_TRY(hipMemcpyAsync(dst, dd.p, nd, hipMemcpyDeviceToHost, e->stream));
-	HIP_TRY(hipStreamSynchronize(e->stream));
+	HIP_TRY(err);
+	*ms_per_step = ms / iters;
 	return LPP_OK;
 }
 
@@ -788,33 +417,18 @@ lpp_status bench_operator_body(const ObsBasis& B, const char* who, lpp_engine* e
 	lpp_status st = refuse(e, who, B.hole_major_ok);
 	if (st != LPP_OK) return st;
 	HIP_TRY(hipSetDevice(e->cfg.device));
-	bool planned = false;
-	int64_t ns = 0, nd = 0, touched = 0;
-	st = plan_sizes(e, B, op, site, spin, nsites, nup, ndown, &planned, &ns, &nd, &touched); // touched: the byte model below
-	if (st != LPP_OK) return st;
-	if (!planned) return fail(LPP_ERR_INVALID, std::string(who) + ": the operator leads to no sector");
+	const DevPlan* D = nullptr;
+	if ((st = get_plan(e, B, op, site, spin, nsites, nup, ndown, &D)) != LPP_OK) return st;
+	if (!D->has) return fail(LPP_ERR_INVALID, std::string(who) + ": the operator leads to no sector");
+	const int64_t ns = D->n_src, nd = D->n_dst, touched = D->touched; // (the plan is valid until the next get_plan; touched: the byte model below)
 	DevBuf ds, dd;
 	HIP_TRY_MEM(hipMalloc(&ds.p, std::max<size_t>(e->esz * (size_t)ns, 16)));
 	HIP_TRY_MEM(hipMalloc(&dd.p, std::max<size_t>(e->esz * (size_t)nd, 16) + 16));
 	HIP_TRY(hipMemsetAsync(ds.p, 0, e->esz * (size_t)ns, e->stream));
 	HIP_TRY(hipMemsetAsync(dd.p, 0, e->esz * (size_t)nd, e->stream));
-	hipEvent_t t0 = nullptr, t1 = nullptr;
-	HIP_TRY(hipEventCreate(&t0));
-	HIP_TRY(hipEventCreate(&t1));
 	bool h = false;
-	for (int i = 0; i < warmup + iters && st == LPP_OK; i++) {
-		if (i == warmup) (void)hipEventRecord(t0, e->stream);
-		st = B.apply(e, op, site, spin, nsites, nup, ndown, 1.0, 0.0, ds.p, dd.p, true, &h, nullptr);
-	}
-	(void)hipEventRecord(t1, e->stream);
-	hipError_t err = hipEventSynchronize(t1);
-	float ms = 0;
-	if (err == hipSuccess) err = hipEventElapsedTime(&ms, t0, t1);
-	(void)hipEventDestroy(t0);
-	(void)hipEventDestroy(t1);
+	st = timed_steps(e, warmup, iters, ms_per_launch, [&] { return apply_dev(e, B, op, site, spin, nsites, nup, ndown, 1.0, 0.0, ds.p, dd.p, true, &h); });
 	if (st != LPP_OK) return st;
-	HIP_TRY(err);
-	*ms_per_launch = ms / iters;
 	// the issue's byte model of z += A src: destination read + write, source entries read once
 	if (model_bytes) *model_bytes = (double)e->esz * (2.0 * (double)nd + (double)touched);
 	return LPP_OK;
@@ -948,9 +562,9 @@ lpp_status spectral_body(const ObsBasis& B, const std::string& who, lpp_engine* 
 	HIP_TRY(hipMemsetAsync(M.p, 0, sizeof(double) * (size_t)stride, e->stream));
 	bool has = false;
 	// getModifiedState (Engine.h:494-533): A_i gs, then isign A_j gs on top -- for i == j the state is accumulated twice
-	st = B.apply(e, op, isite, spin, L, nup, ndown, 1.0, 0.0, gs, M.p, true, &has, nullptr);
+	st = apply_dev(e, B, op, isite, spin, L, nup, ndown, 1.0, 0.0, gs, M.p, true, &has);
 	if (st != LPP_OK) return st;
-	st = B.apply(e, op, jsite, spin, L, nup, ndown, isign, 0.0, gs, M.p, true, &has, nullptr);
+	st = apply_dev(e, B, op, jsite, spin, L, nup, ndown, isign, 0.0, gs, M.p, true, &has);
 	if (st != LPP_OK) return st;
 	k_dot<<<nb, kBlock, 0, e->stream>>>((const double2*)M.p, (const double2*)M.p, stride / 2, (double*)part.p);
 	k_reduce_final<<<1, kBlock, 0, e->stream>>>((const double*)part.p, nb, 1, 1, (double*)part.p + nb);
@@ -1000,17 +614,24 @@ lpp_status apply_string_dev(lpp_engine* e, const StringPlan& P, int L, int nup, 
 	const int32_t* d = (const int32_t*)T.p;
 	ObsStringApplyArgs A { dev_string(P, d, d + ntu), (const uint32_t*)(d + ntu + ntd), (const uint32_t*)(d + ntu + ntd + wu.size()), P.n_up_dst, P.n_dn_dst, P.n_up_src,
 		                   fr * P.scale, fi * P.scale };
-	const int64_t units = e->is_complex ? nd : (nd + 1) / 2;
-	const int g = obs_grid(e, units);
-	if (e->is_complex) {
-		if (acc) k_obs_string_apply<true, true><<<g, kObsBlock, 0, e->stream>>>((double*)d_dst, (const double*)d_src, A);
-		else k_obs_string_apply<true, false><<<g, kObsBlock, 0, e->stream>>>((double*)d_dst, (const double*)d_src, A);
-	} else {
-		if (acc) k_obs_string_apply<false, true><<<g, kObsBlock, 0, e->stream>>>((double*)d_dst, (const double*)d_src, A);
-		else k_obs_string_apply<false, false><<<g, kObsBlock, 0, e->stream>>>((double*)d_dst, (const double*)d_src, A);
-	}
-	HIP_TRY(hipGetLastError());
+	OBS_LAUNCH(k_obs_string_apply, e, acc, nd, 0, d_dst, d_src, A);
 	HIP_TRY(hipStreamSynchronize(e->stream));
+	return LPP_OK;
+}
+
+// what lpp_engine_apply_string and its _host form do before they launch: the plan, the new sector reported, the device set.  !P.has: nothing to launch
+lpp_status apply_string_front(lpp_engine* e, const std::string& who, bool args_ok, int conv, int nops, const int32_t* ops, const int32_t* sites, const int32_t* spins,
+                              const int32_t* flags, int L, int nup, int ndn, StringPlan& P, int32_t* has, int32_t* nup_new, int32_t* ndown_new)
+{
+	if (!args_ok) return fail(LPP_ERR_INVALID, who + ": null argument");
+	*has = 0;
+	lpp_status st = refuse_string(e, who.c_str());
+	if (st != LPP_OK) return st;
+	if ((st = string_plan(conv, nops, ops, sites, spins, flags, L, nup, ndn, P)) != LPP_OK || !P.has) return st;
+	*has = 1;
+	if (nup_new) *nup_new = P.nup2;
+	if (ndown_new) *ndown_new = P.ndn2;
+	HIP_TRY(hipSetDevice(e->cfg.device));
 	return LPP_OK;
 }
 
@@ -1134,15 +755,47 @@ lpp_status many_point_dev(lpp_engine* e, int conv, const StringList& S, int L, i
 	return LPP_OK;
 }
 
+// hasNewParts of the basis for the host (lpp_obs_new_parts*): *has = 0 where the operator leads to no sector
+lpp_status new_parts_body(const ObsBasis& B, const std::string& who, int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t* has, int32_t* nup_new,
+                          int32_t* ndown_new)
+{
+	if (!has) return fail(LPP_ERR_INVALID, who + ": null argument");
+	*has = 0;
+	if (spin != LPP_SPIN_UP && spin != LPP_SPIN_DOWN) return fail(LPP_ERR_INVALID, who + ": bad spin");
+	if (!B.counts_ok(nsites, nup, ndown)) return fail(LPP_ERR_INVALID, who + ": bad sector");
+	if (op == LPP_OP_SZ && B.sz_has_no_parts) return LPP_OK; // HubbardOneOrbital.h:101-102, Heisenberg.h:122-123
+	// the reference throws: HubbardOneOrbital.h:104-108, for n and sz TjMultiOrb.h:154-158, for all but splus / sminus Heisenberg.h:129-133
+	if (!needs_new_basis(op) || (!B.fermions && (op == LPP_OP_C || op == LPP_OP_CDAGGER))) return fail(LPP_ERR_INVALID, "hasNewParts: unsupported operator");
+	int n1 = 0, n2 = 0;
+	if (!B.new_parts(op, spin, nsites, nup, B.reads_ndown ? ndown : 0, &n1, &n2))
+		return B.no_sector_throws ? fail(LPP_ERR_INVALID, "hasNewParts: S+ to all ups or S- to all downs") : LPP_OK; // the reference throws (Heisenberg.h:239)
+	*has = 1;
+	if (nup_new) *nup_new = n1;
+	if (ndown_new) *ndown_new = n2;
+	return LPP_OK;
+}
+
+// keep_tj: the solve lets a hole-major engine through (lanczos_impl)
+lpp_status keep_states_body(const std::string& who, lpp_engine* e, int32_t k, bool keep_tj)
+{
+	if (!e || k < 0) return fail(LPP_ERR_INVALID, who + ": bad argument");
+	if (e->active) return fail(LPP_ERR_STATE, who + ": a Lanczos run is active");
+	if (k > 0) {
+		lpp_status st = refuse(e, who.c_str(), keep_tj);
+		if (st != LPP_OK) return st;
+	}
+	e->keep_k = k;
+	e->keep_tj = keep_tj;
+	return LPP_OK;
+}
+
 } // namespace
 
 namespace lpp {
 void free_obs(lpp_engine* e)
 {
 	if (e->obs) {
-		ObsCache* C = (ObsCache*)e->obs;
-		for (auto& kv : C->plans) free_plan(kv.second);
-		delete C;
+		delete (ObsCache*)e->obs; // the plans free their tables
 		e->obs = nullptr;
 	}
 	if (e->resident) (void)hipFree(e->resident);
@@ -1153,21 +806,11 @@ void free_obs(lpp_engine* e)
 
 extern "C" {
 
-lpp_status lpp_obs_new_parts(int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t* has, int32_t* nup_new, int32_t* ndown_new)
-{
-	if (!has) return fail(LPP_ERR_INVALID, "lpp_obs_new_parts: null argument");
-	*has = 0;
-	if (spin != LPP_SPIN_UP && spin != LPP_SPIN_DOWN) return fail(LPP_ERR_INVALID, "lpp_obs_new_parts: bad spin");
-	if (nsites < 1 || nup < 0 || ndown < 0 || nup > nsites || ndown > nsites) return fail(LPP_ERR_INVALID, "lpp_obs_new_parts: bad sector");
-	if (op == LPP_OP_SZ) return LPP_OK; // HubbardOneOrbital.h:101-102
-	if (!needs_new_basis(op)) return fail(LPP_ERR_INVALID, "hasNewParts: unsupported operator"); // the reference throws (:104-108)
-	int n1 = 0, n2 = 0;
-	if (!new_parts(op, spin, nsites, nup, ndown, &n1, &n2)) return LPP_OK;
-	*has = 1;
-	if (nup_new) *nup_new = n1;
-	if (ndown_new) *ndown_new = n2;
-	return LPP_OK;
-}
+// One entry point per family over one body(basis, name, arguments...): the Hubbard product basis, the one-orbital t-J basis, the S = 1/2 Heisenberg basis
+#define OBS_ENTRY(body, hubbard, tj, heis, params, ...)                           \
+	lpp_status hubbard params { return body(kHubbard, #hubbard, __VA_ARGS__); } \
+	lpp_status tj params { return body(kTj, #tj, __VA_ARGS__); }                \
+	lpp_status heis params { return body(kHeis, #heis, __VA_ARGS__); }
 
 lpp_status lpp_obs_plan(int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t* has, int32_t* nup_new, int32_t* ndown_new,
                         int64_t* n_up_dst, int64_t* n_down_dst, int32_t* table_up, int32_t* table_down)
@@ -1175,7 +818,8 @@ lpp_status lpp_obs_plan(int32_t op, int32_t site, int32_t spin, int32_t nsites, 
 	if (!has) return fail(LPP_ERR_INVALID, "lpp_obs_plan: null argument");
 	ObsPlan P;
 	bool h = false;
-	lpp_status st = obs_plan(op, site, spin, nsites, nup, ndown, &h, P);
+	const char* why = nullptr;
+	lpp_status st = plan_status(obs_plan(op, site, spin, nsites, nup, ndown, &h, P, &why), why);
 	if (st != LPP_OK) return st;
 	*has = h ? 1 : 0;
 	if (!h) return LPP_OK;
@@ -1225,17 +869,9 @@ lpp_status lpp_engine_apply_string(lpp_engine* e, int32_t convention, int32_t no
                                    int32_t nsites, int32_t nup, int32_t ndown, double factor_re, double factor_im, const void* d_src, void* d_dst, int32_t accumulate,
                                    int32_t* has, int32_t* nup_new, int32_t* ndown_new)
 {
-	if (!e || !has) return fail(LPP_ERR_INVALID, "lpp_engine_apply_string: null argument");
-	*has = 0;
-	lpp_status st = refuse_string(e, "lpp_engine_apply_string");
-	if (st != LPP_OK) return st;
 	StringPlan P;
-	if ((st = string_plan(convention, nops, ops, sites, spins, flags, nsites, nup, ndown, P)) != LPP_OK) return st;
-	if (!P.has) return LPP_OK;
-	*has = 1;
-	if (nup_new) *nup_new = P.nup2;
-	if (ndown_new) *ndown_new = P.ndn2;
-	HIP_TRY(hipSetDevice(e->cfg.device));
+	lpp_status st = apply_string_front(e, "lpp_engine_apply_string", e && has, convention, nops, ops, sites, spins, flags, nsites, nup, ndown, P, has, nup_new, ndown_new);
+	if (st != LPP_OK || !P.has) return st;
 	return apply_string_dev(e, P, nsites, nup, ndown, factor_re, factor_im, d_src, d_dst, accumulate != 0);
 }
 
@@ -1243,27 +879,13 @@ lpp_status lpp_engine_apply_string_host(lpp_engine* e, int32_t convention, int32
                                         int32_t nsites, int32_t nup, int32_t ndown, double factor_re, double factor_im, const void* src, void* dst, int32_t accumulate,
                                         int32_t* has, int32_t* nup_new, int32_t* ndown_new)
 {
-	if (!e || !has || !src || !dst) return fail(LPP_ERR_INVALID, "lpp_engine_apply_string_host: null argument");
-	*has = 0;
-	lpp_status st = refuse_string(e, "lpp_engine_apply_string_host");
-	if (st != LPP_OK) return st;
 	StringPlan P;
-	if ((st = string_plan(convention, nops, ops, sites, spins, flags, nsites, nup, ndown, P)) != LPP_OK) return st;
-	if (!P.has) return LPP_OK;
-	*has = 1;
-	if (nup_new) *nup_new = P.nup2;
-	if (ndown_new) *ndown_new = P.ndn2;
-	HIP_TRY(hipSetDevice(e->cfg.device));
-	const size_t ns = e->esz * (size_t)(P.n_up_src * P.n_dn_src), nd = e->esz * (size_t)(P.n_up_dst * P.n_dn_dst);
-	DevBuf ds, dd;
-	HIP_TRY_MEM(hipMalloc(&ds.p, std::max<size_t>(ns, 16)));
-	HIP_TRY_MEM(hipMalloc(&dd.p, std::max<size_t>(nd, 16) + 16));
-	HIP_TRY(hipMemcpyAsync(ds.p, src, ns, hipMemcpyHostToDevice, e->stream));
-	if (accumulate) HIP_TRY(hipMemcpyAsync(dd.p, dst, nd, hipMemcpyHostToDevice, e->stream));
-	if ((st = apply_string_dev(e, P, nsites, nup, ndown, factor_re, factor_im, ds.p, dd.p, accumulate != 0)) != LPP_OK) return st;
-	HIP_TRY(hipMemcpyAsync(dst, dd.p, nd, hipMemcpyDeviceToHost, e->stream));
-	HIP_TRY(hipStreamSynchronize(e->stream));
-	return LPP_OK;
+	lpp_status st = apply_string_front(e, "lpp_engine_apply_string_host", e && has && src && dst, convention, nops, ops, sites, spins, flags, nsites, nup, ndown, P, has, nup_new,
+	                                   ndown_new);
+	if (st != LPP_OK || !P.has) return st;
+	return staged(e, e->esz * (size_t)(P.n_up_src * P.n_dn_src), e->esz * (size_t)(P.n_up_dst * P.n_dn_dst), src, dst, accumulate, [&](const void* d_src, void* d_dst) {
+		return apply_string_dev(e, P, nsites, nup, ndown, factor_re, factor_im, d_src, d_dst, accumulate != 0);
+	});
 }
 
 lpp_status lpp_engine_many_point(lpp_engine* e, int32_t convention, int32_t nstrings, const int64_t* offsets, const int32_t* ops, const int32_t* sites, const int32_t* spins,
@@ -1339,39 +961,13 @@ lpp_status lpp_engine_bench_string_dot(lpp_engine* e, int32_t convention, int32_
 	if ((st = dot_work(e, nsites, nup, ndown, nstrings, W)) != LPP_OK) return st;
 	const ObsStringDotArgs A = dot_args(W, plans.data(), nstrings);
 	HIP_TRY(hipMemcpyAsync(W.tabs.p, W.img.data(), 4 * W.img.size(), hipMemcpyHostToDevice, e->stream));
-	hipEvent_t t0 = nullptr, t1 = nullptr;
-	HIP_TRY(hipEventCreate(&t0));
-	HIP_TRY(hipEventCreate(&t1));
-	for (int i = 0; i < warmup + iters; i++) {
-		if (i == warmup) (void)hipEventRecord(t0, e->stream);
+	st = timed_steps(e, warmup, iters, ms_per_launch, [&] {
 		launch_dot(e, W, A, (const double*)db.p, (const double*)dk.p, (double*)W.out.p);
-	}
-	(void)hipEventRecord(t1, e->stream);
-	hipError_t err = hipEventSynchronize(t1);
-	float ms = 0;
-	if (err == hipSuccess) err = hipEventElapsedTime(&ms, t0, t1);
-	if (err == hipSuccess) err = hipGetLastError();
-	(void)hipEventDestroy(t0);
-	(void)hipEventDestroy(t1);
-	HIP_TRY(err);
-	*ms_per_launch = ms / iters;
+		return LPP_OK;
+	});
+	if (st != LPP_OK) return st;
 	// bra read once, one ket element per string and destination it reaches (the tables stay in L2)
 	if (model_bytes) *model_bytes = (double)e->esz * ((double)n + reached);
-	return LPP_OK;
-}
-
-lpp_status lpp_obs_new_parts_tj(int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t* has, int32_t* nup_new, int32_t* ndown_new)
-{
-	if (!has) return fail(LPP_ERR_INVALID, "lpp_obs_new_parts_tj: null argument");
-	*has = 0;
-	if (spin != LPP_SPIN_UP && spin != LPP_SPIN_DOWN) return fail(LPP_ERR_INVALID, "lpp_obs_new_parts_tj: bad spin");
-	if (nsites < 1 || nup < 0 || ndown < 0 || nup + ndown > nsites) return fail(LPP_ERR_INVALID, "lpp_obs_new_parts_tj: bad sector");
-	if (!needs_new_basis(op)) return fail(LPP_ERR_INVALID, "hasNewParts: unsupported operator"); // the reference throws for n and sz (TjMultiOrb.h:154-158)
-	int n1 = 0, n2 = 0;
-	if (!new_parts_tj(op, spin, nsites, nup, ndown, &n1, &n2)) return LPP_OK;
-	*has = 1;
-	if (nup_new) *nup_new = n1;
-	if (ndown_new) *ndown_new = n2;
 	return LPP_OK;
 }
 
@@ -1381,7 +977,8 @@ lpp_status lpp_obs_plan_tj(int32_t op, int32_t site, int32_t spin, int32_t nsite
 	if (!has) return fail(LPP_ERR_INVALID, "lpp_obs_plan_tj: null argument");
 	ObsTjPlan P;
 	bool h = false;
-	lpp_status st = obs_plan_tj(op, site, spin, nsites, nup, ndown, &h, P);
+	const char* why = nullptr;
+	lpp_status st = plan_status(obs_plan_tj(op, site, spin, nsites, nup, ndown, &h, P, &why), why);
 	if (st != LPP_OK) return st;
 	*has = h ? 1 : 0;
 	if (!h) return LPP_OK;
@@ -1392,23 +989,6 @@ lpp_status lpp_obs_plan_tj(int32_t op, int32_t site, int32_t spin, int32_t nsite
 	return LPP_OK;
 }
 
-lpp_status lpp_obs_new_parts_heis(int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t* has, int32_t* nup_new, int32_t* ndown_new)
-{
-	(void)ndown;
-	if (!has) return fail(LPP_ERR_INVALID, "lpp_obs_new_parts_heis: null argument");
-	*has = 0;
-	if (spin != LPP_SPIN_UP && spin != LPP_SPIN_DOWN) return fail(LPP_ERR_INVALID, "lpp_obs_new_parts_heis: bad spin");
-	if (heis_sector_size(nsites, nup, 0) < 0) return fail(LPP_ERR_INVALID, "lpp_obs_new_parts_heis: bad sector");
-	if (op == LPP_OP_SZ) return LPP_OK; // Heisenberg.h:122-123
-	if (op != LPP_OP_SPLUS && op != LPP_OP_SMINUS) return fail(LPP_ERR_INVALID, "hasNewParts: unsupported operator"); // the reference throws (:129-133)
-	int n1 = 0, n2 = 0;
-	if (!new_parts_heis(op, spin, nsites, nup, 0, &n1, &n2)) return fail(LPP_ERR_INVALID, "hasNewParts: S+ to all ups or S- to all downs"); // the reference throws (:239)
-	*has = 1;
-	if (nup_new) *nup_new = n1;
-	if (ndown_new) *ndown_new = n2;
-	return LPP_OK;
-}
-
 lpp_status lpp_obs_plan_heis(int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t* has, int32_t* nup_new, int32_t* ndown_new,
                              int64_t* n_dst, int32_t* low_bits, int64_t* action)
 {
@@ -1416,7 +996,8 @@ lpp_status lpp_obs_plan_heis(int32_t op, int32_t site, int32_t spin, int32_t nsi
 	if (!has) return fail(LPP_ERR_INVALID, "lpp_obs_plan_heis: null argument");
 	*has = 0;
 	ObsHeisPlan P;
-	lpp_status st = obs_plan_heis(op, site, spin, nsites, nup, P);
+	const char* why = nullptr;
+	lpp_status st = plan_status(obs_plan_heis(op, site, spin, nsites, nup, P, &why), why);
 	if (st != LPP_OK) return st;
 	*has = 1;
 	if (nup_new) *nup_new = P.m2;
@@ -1439,82 +1020,24 @@ lpp_status lpp_continued_fraction(int32_t n, const double* a, const double* b, d
 	return LPP_OK;
 }
 
-lpp_status lpp_engine_apply_operator(lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, double factor_re,
-                                     double factor_im, const void* d_src, void* d_dst, int32_t accumulate, int32_t* has)
-{
-	return apply_operator_body(kHubbard, "lpp_engine_apply_operator", e, op, site, spin, nsites, nup, ndown, factor_re, factor_im, d_src, d_dst, accumulate, has);
-}
-lpp_status lpp_engine_apply_operator_tj(lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, double factor_re,
-                                        double factor_im, const void* d_src, void* d_dst, int32_t accumulate, int32_t* has)
-{
-	return apply_operator_body(kTj, "lpp_engine_apply_operator_tj", e, op, site, spin, nsites, nup, ndown, factor_re, factor_im, d_src, d_dst, accumulate, has);
-}
+OBS_ENTRY(apply_operator_body, lpp_engine_apply_operator, lpp_engine_apply_operator_tj, lpp_engine_apply_operator_heis,
+          (lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, double factor_re, double factor_im, const void* d_src, void* d_dst,
+           int32_t accumulate, int32_t* has),
+          e, op, site, spin, nsites, nup, ndown, factor_re, factor_im, d_src, d_dst, accumulate, has)
+OBS_ENTRY(apply_operator_host_body, lpp_engine_apply_operator_host, lpp_engine_apply_operator_tj_host, lpp_engine_apply_operator_heis_host,
+          (lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, double factor_re, double factor_im, const void* src, void* dst,
+           int32_t accumulate, int32_t* has),
+          e, op, site, spin, nsites, nup, ndown, factor_re, factor_im, src, dst, accumulate, has)
+OBS_ENTRY(bench_operator_body, lpp_engine_bench_operator, lpp_engine_bench_operator_tj, lpp_engine_bench_operator_heis,
+          (lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t warmup, int32_t iters, double* ms_per_launch,
+           double* model_bytes),
+          e, op, site, spin, nsites, nup, ndown, warmup, iters, ms_per_launch, model_bytes)
+OBS_ENTRY(new_parts_body, lpp_obs_new_parts, lpp_obs_new_parts_tj, lpp_obs_new_parts_heis,
+          (int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t* has, int32_t* nup_new, int32_t* ndown_new), op, spin, nsites, nup, ndown, has, nup_new,
+          ndown_new)
 
-lpp_status lpp_engine_apply_operator_heis(lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, double factor_re,
-                                          double factor_im, const void* d_src, void* d_dst, int32_t accumulate, int32_t* has)
-{
-	return apply_operator_body(kHeis, "lpp_engine_apply_operator_heis", e, op, site, spin, nsites, nup, ndown, factor_re, factor_im, d_src, d_dst, accumulate, has);
-}
-
-lpp_status lpp_engine_apply_operator_host(lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, double factor_re,
-                                          double factor_im, const void* src, void* dst, int32_t accumulate, int32_t* has)
-{
-	return apply_operator_host_body(kHubbard, "lpp_engine_apply_operator_host", e, op, site, spin, nsites, nup, ndown, factor_re, factor_im, src, dst, accumulate, has);
-}
-lpp_status lpp_engine_apply_operator_tj_host(lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, double factor_re,
-                                             double factor_im, const void* src, void* dst, int32_t accumulate, int32_t* has)
-{
-	return apply_operator_host_body(kTj, "lpp_engine_apply_operator_tj_host", e, op, site, spin, nsites, nup, ndown, factor_re, factor_im, src, dst, accumulate, has);
-}
-
-lpp_status lpp_engine_apply_operator_heis_host(lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, double factor_re,
-                                               double factor_im, const void* src, void* dst, int32_t accumulate, int32_t* has)
-{
-	return apply_operator_host_body(kHeis, "lpp_engine_apply_operator_heis_host", e, op, site, spin, nsites, nup, ndown, factor_re, factor_im, src, dst, accumulate, has);
-}
-
-lpp_status lpp_engine_bench_operator(lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t warmup, int32_t iters,
-                                     double* ms_per_launch, double* model_bytes)
-{
-	return bench_operator_body(kHubbard, "lpp_engine_bench_operator", e, op, site, spin, nsites, nup, ndown, warmup, iters, ms_per_launch, model_bytes);
-}
-lpp_status lpp_engine_bench_operator_tj(lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t warmup, int32_t iters,
-                                        double* ms_per_launch, double* model_bytes)
-{
-	return bench_operator_body(kTj, "lpp_engine_bench_operator_tj", e, op, site, spin, nsites, nup, ndown, warmup, iters, ms_per_launch, model_bytes);
-}
-
-lpp_status lpp_engine_bench_operator_heis(lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t warmup, int32_t iters,
-                                          double* ms_per_launch, double* model_bytes)
-{
-	return bench_operator_body(kHeis, "lpp_engine_bench_operator_heis", e, op, site, spin, nsites, nup, ndown, warmup, iters, ms_per_launch, model_bytes);
-}
-
-lpp_status lpp_engine_keep_states(lpp_engine* e, int32_t k)
-{
-	if (!e || k < 0) return fail(LPP_ERR_INVALID, "lpp_engine_keep_states: bad argument");
-	if (e->active) return fail(LPP_ERR_STATE, "lpp_engine_keep_states: a Lanczos run is active");
-	if (k > 0) {
-		lpp_status st = refuse(e, "lpp_engine_keep_states");
-		if (st != LPP_OK) return st;
-	}
-	e->keep_k = k;
-	e->keep_tj = false;
-	return LPP_OK;
-}
-
-lpp_status lpp_engine_keep_states_tj(lpp_engine* e, int32_t k)
-{
-	if (!e || k < 0) return fail(LPP_ERR_INVALID, "lpp_engine_keep_states_tj: bad argument");
-	if (e->active) return fail(LPP_ERR_STATE, "lpp_engine_keep_states_tj: a Lanczos run is active");
-	if (k > 0) {
-		lpp_status st = refuse(e, "lpp_engine_keep_states_tj", true);
-		if (st != LPP_OK) return st;
-	}
-	e->keep_k = k;
-	e->keep_tj = true; // the solve lets a hole-major engine through (lanczos_impl)
-	return LPP_OK;
-}
+lpp_status lpp_engine_keep_states(lpp_engine* e, int32_t k) { return keep_states_body("lpp_engine_keep_states", e, k, false); }
+lpp_status lpp_engine_keep_states_tj(lpp_engine* e, int32_t k) { return keep_states_body("lpp_engine_keep_states_tj", e, k, true); }
 
 lpp_status lpp_engine_state_device(lpp_engine* e, int32_t k, void** d_ptr, int64_t* len)
 {
@@ -1539,38 +1062,12 @@ lpp_status lpp_engine_state_to_host(lpp_engine* e, int32_t k, void* host)
 	return LPP_OK;
 }
 
-lpp_status lpp_engine_two_point(lpp_engine* e, int32_t op, int32_t spin1, int32_t spin2, int32_t nsites, int32_t nup, int32_t ndown, int32_t bra_state,
-                                int32_t ket_state, void* result, void* trace)
-{
-	return two_point_body(kHubbard, "lpp_engine_two_point", e, op, spin1, spin2, nsites, nup, ndown, bra_state, ket_state, result, trace);
-}
-lpp_status lpp_engine_two_point_tj(lpp_engine* e, int32_t op, int32_t spin1, int32_t spin2, int32_t nsites, int32_t nup, int32_t ndown, int32_t bra_state,
-                                   int32_t ket_state, void* result, void* trace)
-{
-	return two_point_body(kTj, "lpp_engine_two_point_tj", e, op, spin1, spin2, nsites, nup, ndown, bra_state, ket_state, result, trace);
-}
-
-lpp_status lpp_engine_two_point_heis(lpp_engine* e, int32_t op, int32_t spin1, int32_t spin2, int32_t nsites, int32_t nup, int32_t ndown, int32_t bra_state,
-                                     int32_t ket_state, void* result, void* trace)
-{
-	return two_point_body(kHeis, "lpp_engine_two_point_heis", e, op, spin1, spin2, nsites, nup, ndown, bra_state, ket_state, result, trace);
-}
-
-lpp_status lpp_engine_spectral_decomposition(lpp_engine* e, int32_t state, lpp_engine* sector, int32_t op, int32_t isite, int32_t jsite, int32_t spin, double isign,
-                                             int32_t nsites, int32_t nup, int32_t ndown, double* weight, int32_t* nsteps, double* a, double* b, lpp_stats* stats)
-{
-	return spectral_body(kHubbard, "lpp_engine_spectral_decomposition", e, state, sector, op, isite, jsite, spin, isign, nsites, nup, ndown, weight, nsteps, a, b, stats);
-}
-lpp_status lpp_engine_spectral_decomposition_tj(lpp_engine* e, int32_t state, lpp_engine* sector, int32_t op, int32_t isite, int32_t jsite, int32_t spin, double isign,
-                                                int32_t nsites, int32_t nup, int32_t ndown, double* weight, int32_t* nsteps, double* a, double* b, lpp_stats* stats)
-{
-	return spectral_body(kTj, "lpp_engine_spectral_decomposition_tj", e, state, sector, op, isite, jsite, spin, isign, nsites, nup, ndown, weight, nsteps, a, b, stats);
-}
-
-lpp_status lpp_engine_spectral_decomposition_heis(lpp_engine* e, int32_t state, lpp_engine* sector, int32_t op, int32_t isite, int32_t jsite, int32_t spin, double isign,
-                                                  int32_t nsites, int32_t nup, int32_t ndown, double* weight, int32_t* nsteps, double* a, double* b, lpp_stats* stats)
-{
-	return spectral_body(kHeis, "lpp_engine_spectral_decomposition_heis", e, state, sector, op, isite, jsite, spin, isign, nsites, nup, ndown, weight, nsteps, a, b, stats);
-}
+OBS_ENTRY(two_point_body, lpp_engine_two_point, lpp_engine_two_point_tj, lpp_engine_two_point_heis,
+          (lpp_engine* e, int32_t op, int32_t spin1, int32_t spin2, int32_t nsites, int32_t nup, int32_t ndown, int32_t bra_state, int32_t ket_state, void* result, void* trace),
+          e, op, spin1, spin2, nsites, nup, ndown, bra_state, ket_state, result, trace)
+OBS_ENTRY(spectral_body, lpp_engine_spectral_decomposition, lpp_engine_spectral_decomposition_tj, lpp_engine_spectral_decomposition_heis,
+          (lpp_engine* e, int32_t state, lpp_engine* sector, int32_t op, int32_t isite, int32_t jsite, int32_t spin, double isign, int32_t nsites, int32_t nup, int32_t ndown,
+           double* weight, int32_t* nsteps, double* a, double* b, lpp_stats* stats),
+          e, state, sector, op, isite, jsite, spin, isign, nsites, nup, ndown, weight, nsteps, a, b, stats)
 
 } // extern "C"

@@ -14,35 +14,20 @@
 //   a site in the low part    stays inside the run of h and gathers through the rank of the low word with the bit flipped;
 //   n and sz                  read the bit and keep the index.
 // The kernel keeps k_obs_apply's design: DESTINATION driven, one lane owns one 16-byte unit of z, looks its source up and writes the unit once --
-// no atomics.  The host plans one table entry per non-empty destination run (lpp_obs.hip, obs_plan_heis): { first destination index, +-(first
+// no atomics.  The host plans one table entry per non-empty destination run (lpp_obs_heis_plan.h, obs_plan_heis): { first destination index, +-(first
 // source index + 1) or 0, popcount of the low part } -- everything that depends on the high part is resolved there.  The low words by (popcount,
 // rank) and the rank of every lb-bit word, 16 bits each, are staged in LDS (4 * 2^lb bytes; nothing is staged for a site in the high part).
 // A tile finds the runs of its first and last element by bisection (the same for every lane), a lane then bisects between those two.
-// obs_heis_source below is the ONE lookup: the kernel calls it per element, lpp_obs_plan_heis expands the plan with it on the host.
+// obs_heis_source (lpp_obs_heis_plan.h, with the plan the host makes) is the ONE lookup: the kernel calls it per element, lpp_obs_plan_heis expands the
+// plan with it on the host.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lpp_obs_heis_plan.h"
 #include "lpp_obs_kernels.h"
 
 namespace lpp {
-
-// what decides the source of a destination element inside its run
-enum {
-	HEIS_RUN = 0, // the run's entry alone: source = first source + position (a site in the high part; the entry's sign is the value's)
-	HEIS_FLIP_SET, // site in the low part, the destination's bit must be set, the source has it cleared (splus)
-	HEIS_FLIP_CLEAR, // ... must be clear, the source has it set (sminus)
-	HEIS_TEST_SET, // same index where the bit is set (n, SPIN_UP)
-	HEIS_TEST_CLEAR, // same index where the bit is clear (n, SPIN_DOWN)
-	HEIS_SZ // same index, value 1 - 2 bit (the raw sz)
-};
-
-constexpr int kObsHeisMaxLow = 14; // lb at most: two 16-bit tables of 2^lb entries in LDS (64 KiB), ranks below C(14, 7)
-struct ObsHeisRun { // 24 bytes per non-empty destination run, ascending; one closing entry with dst0 = N_dst
-	int64_t dst0; // index of the run's first element
-	int64_t src; // +-(index of the source run's first element + 1), 0: no element of the run is touched
-	int32_t pl, wbase; // popcount p of the low part of the run's words; word[wbase + r] is the low word of popcount p and rank r
-};
 
 struct ObsHeisArgs {
 	const ObsHeisRun* runs; // nruns + 1 entries
@@ -53,27 +38,6 @@ struct ObsHeisArgs {
 	int64_t nruns, n_dst;
 	double fr, fi; // factor
 };
-
-// destination = element r of run R -> +-(source index + 1), 0 = the reference does not touch it.  word / rank wherever the caller keeps them.
-__host__ __device__ __forceinline__ int64_t obs_heis_source(int mode, const ObsHeisRun& R, int64_t r, uint32_t bit, const uint16_t* word, const uint16_t* rank)
-{
-	if (R.src == 0) return 0;
-	if (mode == HEIS_RUN) return R.src < 0 ? R.src - r : R.src + r;
-	const uint32_t w = word[R.wbase + (int32_t)r];
-	const bool set = (w & bit) != 0;
-	switch (mode) {
-	case HEIS_FLIP_SET:
-	case HEIS_FLIP_CLEAR:
-		if (set != (mode == HEIS_FLIP_SET)) return 0;
-		return R.src + (int64_t)rank[w ^ bit];
-	case HEIS_TEST_SET:
-		return set ? R.src + r : 0;
-	case HEIS_TEST_CLEAR:
-		return set ? 0 : R.src + r;
-	default: // HEIS_SZ
-		return set ? -(R.src + r) : R.src + r;
-	}
-}
 
 // the run that holds element el, between runs lo and hi (both inclusive; runs[lo].dst0 <= el)
 __device__ __forceinline__ int64_t obs_heis_run_of(const ObsHeisRun* __restrict__ runs, int64_t lo, int64_t hi, int64_t el)

@@ -5,7 +5,7 @@
 // with bra / value from getBraIndex (BasisHubbardLanczos.h:162-246), sign from doSignGf (:106-137) and doSignSpSm (:151-160).
 // Both vectors are in the reference's basis order, index = rank(up) + rank(down) * N_up (:59-63).
 //
-// Every operator of LabeledOperator.h:36-59 factorises per species, so the host plans two small tables (lpp_obs.hip, obs_plan):
+// Every operator of LabeledOperator.h:36-59 factorises per species, so the host plans two small tables (lpp_obs_plan.h, obs_plan):
 //     table[destination species rank] = +-(source species rank + 1), 0 = no source; the sign of the entry is the species' part of the sign.
 // The kernel is DESTINATION driven: one lane owns one 16-byte unit of z (two f64 elements, or one c128 element), looks its source up through
 // the two tables and writes the unit once -- no atomics, z streams through with 16-byte accesses, the tables (at most C(L, L/2) entries each)

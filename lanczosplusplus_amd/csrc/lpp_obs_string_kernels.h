@@ -3,7 +3,7 @@
 //
 // GPU restatement of Engine::manyPoint (reference src/Engine/Engine.h:341-389: accModifiedState_ step by step through the sectors) and of
 // ModelBase::rahulMethod (src/Engine/ModelBase.h:89-141, the -m brackets).  Every one-site operator factorises per species (lpp_obs_kernels.h), so a
-// product does: the host composes the whole string into the two tables of lpp_obs_kernels.h (lpp_obs.hip, string_plan),
+// product does: the host composes the whole string into the two tables of lpp_obs_kernels.h (lpp_obs_string_plan.h, plan_string),
 //     table[destination species rank] = +-(source species rank + 1), 0 = no source,
 // with every fermionic sign carried by the entries.  The one thing that does not factorise is the value of sz in the many-point convention, +1 / -1 /
 // absent = (up occupied) - (down occupied) of the word the operator meets: a difference, not a product.  The word it meets is the SOURCE word with

@@ -1,78 +1,19 @@
-// lpp_obs_string_plan.h -- host-only planning of the Hubbard product basis observables: sector arithmetic, species ranks, and the composition of a
-// PRODUCT of one-site operators into one pair of per-species tables (the kernels that read them: lpp_obs_string_kernels.h).  Plain C++, no HIP: the
-// sanitizer test of the planner (host/test_string_plan.cpp) compiles this header alone.
+// lpp_obs_string_plan.h -- host-only planning of operator strings in the Hubbard product basis: the composition of a PRODUCT of one-site operators
+// into one pair of per-species tables (the kernels that read them: lpp_obs_string_kernels.h; sector arithmetic and species ranks: lpp_obs_plan.h).
+// Plain C++, no HIP: the sanitizer test of the planner (host/test_string_plan.cpp) compiles this header alone.
 #pragma once
 #include <stdint.h>
 
 #include <vector>
 
 #include "lpp_engine.h"
+#include "lpp_obs_plan.h"
 
 namespace lpp {
 
 constexpr int kObsStringMaxOps = 16; // operators per string (so at most 16 sz entries)
 
 namespace obs_host {
-
-inline bool needs_new_basis(int op) { return op == LPP_OP_C || op == LPP_OP_CDAGGER || op == LPP_OP_SPLUS || op == LPP_OP_SMINUS; } // LabeledOperator.h:83-90
-inline bool valid_op(int op) { return op == LPP_OP_C || op == LPP_OP_SZ || op == LPP_OP_CDAGGER || op == LPP_OP_N || op == LPP_OP_SPLUS || op == LPP_OP_SMINUS; }
-
-inline int64_t binom(int n, int k)
-{
-	if (k < 0 || k > n) return 0;
-	long double r = 1;
-	for (int i = 1; i <= k; i++) r = r * (n - k + i) / i;
-	return (int64_t)(r + 0.5L);
-}
-
-// HubbardOneOrbital::hasNewParts for c / cdagger / splus / sminus
-inline bool new_parts(int op, int spin, int L, int nup, int ndn, int* n1, int* n2)
-{
-	int p1 = nup, p2 = ndn;
-	if (op == LPP_OP_C || op == LPP_OP_CDAGGER) { // hasNewPartsCorCdagger :212-230
-		const int c = (op == LPP_OP_C) ? -1 : 1;
-		if (spin == LPP_SPIN_UP) p1 += c;
-		else p2 += c;
-		if (p1 < 0 || p2 < 0) return false;
-		if (p1 > L || p2 > L) return false;
-		if (p1 == 0 && p2 == 0) return false;
-	} else { // hasNewPartsSplusOrSminus :232-253
-		const int c = (op == LPP_OP_SPLUS) ? 1 : -1;
-		p1 += c;
-		p2 -= c;
-		if (p1 < 0 || p2 < 0) return false;
-		if (p1 > L || p2 > L) return false;
-	}
-	*n1 = p1;
-	*n2 = p2;
-	return true;
-}
-
-// BasisOneSpin::perfectIndex (BasisOneSpin.h:73-81): the rank of a word among the ascending words of its popcount
-struct Ranker {
-	int L;
-	std::vector<int64_t> comb; // comb[b * (L + 2) + c]
-	explicit Ranker(int L_) : L(L_), comb((size_t)(L_ + 1) * (L_ + 2))
-	{
-		for (int b = 0; b <= L; b++)
-			for (int c = 0; c <= L + 1; c++) comb[(size_t)b * (L + 2) + c] = binom(b, c);
-	}
-	int64_t rank(uint64_t w) const
-	{
-		int64_t n = 0;
-		int c = 1;
-		for (int b = 0; w; b++, w >>= 1)
-			if (w & 1) n += comb[(size_t)b * (L + 2) + c++];
-		return n;
-	}
-};
-
-// next word of the same popcount (BasisOneSpin.h:53-61)
-inline uint64_t next_word(uint64_t w)
-{
-	const uint64_t c = w & (~w + 1), r = w + c;
-	return (((r ^ w) >> 2) / c) | r;
-}
 
 // what one operator does to a word of one species, walking FORWARD from the ket
 enum { FW_REMOVE, FW_ADD, FW_KEEP_SET, FW_SIGN_SET }; // needs the bit, clears it | needs it clear, sets it | needs the bit | -1 where the bit is set
@@ -99,7 +40,7 @@ inline void compose_table(const Ranker& R, int L, int n_src, int n_dst, const st
 	tab.assign((size_t)binom(L, n_dst), 0);
 	if (dead) return;
 	const int64_t cnt = binom(L, n_src);
-	uint64_t w = (n_src == 0) ? 0 : ((1ull << n_src) - 1);
+	uint64_t w = first_word(n_src);
 	for (int64_t i = 0; i < cnt; i++) {
 		uint64_t x = w;
 		int s = 1;
@@ -120,7 +61,7 @@ inline void compose_table(const Ranker& R, int L, int n_src, int n_dst, const st
 			if (f.kind != FW_KEEP_SET) x ^= bit;
 		}
 		if (ok) tab[(size_t)R.rank(x)] = (int32_t)(s * (i + 1));
-		if (n_src > 0 && i + 1 < cnt) w = next_word(w);
+		if (i + 1 < cnt) w = next_word(w);
 	}
 }
 
@@ -141,7 +82,7 @@ inline bool plan_string(int conv, int nops, const int32_t* ops, const int32_t* s
 	if (nops < 1 || nops > kObsStringMaxOps) return refuse("operator string: 1 to 16 operators per string");
 	if (!ops || !sites || !spins) return refuse("operator string: null argument");
 	if (L < 1 || L > 30 || nup < 0 || ndn < 0 || nup > L || ndn > L) return refuse("operator string: bad sites / sector");
-	if (binom(L, L / 2) >= (int64_t)INT32_MAX - 4096) return refuse("operator string: a species with 2^31 states or more");
+	if (too_many_states(binom(L, L / 2))) return refuse("operator string: a species with 2^31 states or more");
 	const bool meas = conv == LPP_STRING_MEASURE;
 	for (int i = 0; i < nops; i++) {
 		const bool known = meas ? (ops[i] == LPP_OP_C || ops[i] == LPP_OP_N || ops[i] == LPP_OP_SZ || ops[i] == LPP_OP_IDENTITY) : valid_op(ops[i]);
@@ -224,10 +165,10 @@ inline void species_words(int L, int n, std::vector<uint32_t>& out)
 {
 	const int64_t cnt = binom(L, n);
 	out.resize((size_t)cnt);
-	uint64_t w = (n == 0) ? 0 : ((1ull << n) - 1);
+	uint64_t w = first_word(n);
 	for (int64_t i = 0; i < cnt; i++) {
 		out[(size_t)i] = (uint32_t)w;
-		if (n > 0 && i + 1 < cnt) w = next_word(w);
+		if (i + 1 < cnt) w = next_word(w);
 	}
 }
 

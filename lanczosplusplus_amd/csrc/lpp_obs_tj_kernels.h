@@ -15,32 +15,16 @@
 //                     insert, or only a test for n), and the rank of the resulting source pattern through the split rank tables
 //                     rank(s) = hi_base[s >> lb] + lo_rank[s & ((1 << lb) - 1)], staged in LDS (the form k_tj_apply ranks its patterns with).
 // Only the pattern words (C(L - ndown', nup') of them) and the down table (8 bytes per down word) are read from L2.
-// obs_tj_source below is the ONE lookup: the kernel calls it per element, lpp_obs_plan_tj expands the plan with it on the host.
+// obs_tj_source (lpp_obs_tj_plan.h, with the plan the host makes) is the ONE lookup: the kernel calls it per element, lpp_obs_plan_tj expands the plan
+// with it on the host.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "lpp_obs_kernels.h"
+#include "lpp_obs_tj_plan.h"
 
 namespace lpp {
-
-// what the operator does to the destination's pattern at position p to give the source's pattern
-enum {
-	TJ_UP_SAME = 0, // nothing, no condition: the source has the same pattern rank (n of the down species)
-	TJ_UP_TEST, // bit p set, the same pattern (n of the up species)
-	TJ_UP_SET, // bit p clear -> set (c up); sign: the parity of the bits below p
-	TJ_UP_CLEAR, // bit p set -> cleared (cdagger up); the same sign
-	TJ_UP_DEL0, // bit p clear -> deleted (c down: the source holds a down electron there, the site leaves the free sites)
-	TJ_UP_DEL1, // bit p set -> deleted (splus)
-	TJ_UP_INS0, // a 0 inserted at p (cdagger down: the site is free in the source, and empty)
-	TJ_UP_INS1 // a 1 inserted at p (sminus)
-};
-
-constexpr int kObsTjMaxHalf = 12; // bits of a half pattern: the rank tables take 4096 x (4 + 2) bytes of LDS at most
-struct ObsTjDown { // 8 bytes per destination down word
-	int32_t src; // +-(rank of the source down word + 1), 0: the destination is not touched
-	int32_t p; // position of the site among the sites the destination's down word leaves free
-};
 
 struct ObsTjArgs {
 	const ObsTjDown* dn; // n_dn_dst entries
@@ -51,43 +35,6 @@ struct ObsTjArgs {
 	int64_t n_up_dst, n_dn_dst, n_up_src;
 	double fr, fi; // factor
 };
-
-// destination (du, dd) -> +-(source index + 1), 0 = the reference does not touch it.  d = dn[dd]; hi_base / lo_rank wherever the caller keeps them.
-__host__ __device__ __forceinline__ int64_t obs_tj_source(int up, ObsTjDown d, uint32_t du, const uint32_t* __restrict__ pat, const int32_t* hi_base,
-                                                          const uint16_t* lo_rank, int lb, int64_t n_up_src)
-{
-	if (d.src == 0) return 0;
-	bool neg = d.src < 0;
-	const int64_t sd = (int64_t)(neg ? -d.src : d.src) - 1;
-	int64_t su = du;
-	if (up != TJ_UP_SAME) {
-		const uint32_t cu = pat[du], bit = 1u << d.p, low = bit - 1u;
-		const bool set = (cu & bit) != 0;
-		uint32_t s = cu;
-		switch (up) {
-		case TJ_UP_TEST:
-			if (!set) return 0;
-			break;
-		case TJ_UP_SET:
-		case TJ_UP_CLEAR:
-			if (set != (up == TJ_UP_CLEAR)) return 0;
-			s = cu ^ bit;
-			if (__builtin_popcount(cu & low) & 1) neg = !neg;
-			break;
-		case TJ_UP_DEL0:
-		case TJ_UP_DEL1:
-			if (set != (up == TJ_UP_DEL1)) return 0;
-			s = (cu & low) | ((cu >> (d.p + 1)) << d.p);
-			break;
-		default: // TJ_UP_INS0, TJ_UP_INS1
-			s = (cu & low) | ((cu >> d.p) << (d.p + 1)) | (up == TJ_UP_INS1 ? bit : 0u);
-			break;
-		}
-		su = (int64_t)hi_base[s >> lb] + (int64_t)lo_rank[s & ((1u << lb) - 1u)];
-	}
-	const int64_t k = su + sd * n_up_src + 1;
-	return neg ? -k : k;
-}
 
 template <bool CPLX> __device__ __forceinline__ bool obs_tj_contrib(const ObsTjArgs& A, const double* __restrict__ src, const int32_t* hi, const uint16_t* lo, uint32_t du,
                                                                     int64_t dd, double& re, double& im)

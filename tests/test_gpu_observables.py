@@ -392,3 +392,68 @@ def test_spectral_function_refuses_operators_that_stay_in_the_sector():
             with pytest.raises(LppError):
                 e.spectral_function(op, 0, 0)
         assert e.sector_assemblies == 0
+
+
+# ---- the plan cache turning over ------------------------------------------------------------------------------------------------------------------
+def test_plan_cache_turnover():
+    """more than 256 distinct (basis, operator, site, spin, sites, sector) keys through one engine: past 256 cached plans everything is dropped after a
+    sync and rebuilt on demand.  Every result equals the CPU restatement bit for bit (factor 1: each element is +-src or 0), and operators applied again
+    after the turnover give their first result bit for bit.  t-J and Heisenberg keys are interleaved with the Hubbard keys, some planned before the
+    turnover and some after it, so plans of different families live and die together."""
+    import heis_obs_reference as heis
+    import tj_obs_reference as tj
+
+    L = 6
+    sources = {}
+
+    def apply(e, key):
+        basis, op, site, spin, sites, parts = key
+        if basis == "hubbard":
+            n, new = ref.comb(sites, parts[0]) * ref.comb(sites, parts[1]), ref.new_sector(op, spin, sites, *parts)
+        elif basis == "tj":
+            n, new = tj.size(sites, *parts), tj.new_sector(op, spin, sites, *parts)
+        else:
+            n, new = heis.size(sites, parts[0]), heis.new_sector(op, spin, sites, parts[0])
+        assert n <= 400
+        src = sources.setdefault((basis, parts), oracle.fill_random(n, 21 + len(sources)))
+        z, got = e.apply_operator(op, site, spin, sites, parts[0], parts[1], src, basis=basis)
+        if new is None:
+            assert z is None and got is None
+            return None
+        if basis == "hubbard":
+            want = ref.acc_modified_state_(np.zeros(len(z)), op, sites, parts, new, src, site, spin, 1.0)
+        elif basis == "tj":
+            want = tj.acc_modified_state_(np.zeros(len(z)), op, sites, parts, new, src, site, spin, 1.0)
+        else:
+            want = heis.acc_modified_state_(np.zeros(len(z)), op, sites, parts[0], new, src, site, spin, 1.0)
+        assert got == (new if basis != "spin_half" else (new, 0)) and np.array_equal(z, want), key
+        return z
+
+    def same(a, b):
+        return (a is None and b is None) or np.array_equal(a.view(np.uint64), b.view(np.uint64))
+
+    def hubbard_keys(parts):
+        return [("hubbard", op, site, spin, L, parts) for op in ref.OPS for spin in (ref.UP, ref.DOWN) for site in range(L)]
+
+    others = [("tj", op, site, spin, 6, (2, 2)) for op in ("c", "cdagger", "n", "sz") for spin in (ref.UP, ref.DOWN) for site in (0, 5)]
+    others += [("tj", op, site, ref.UP, 6, (2, 2)) for op in ("splus", "sminus") for site in (0, 5)]
+    others += [("spin_half", op, site, spin, 12, (2, 0)) for op in ("n", "sz", "splus", "sminus") for spin in (ref.UP, ref.DOWN) for site in (0, 5, 11)]
+    assert len(others) == 20 + 24
+    first, planned = {}, set()
+    with LanczosEngine(dtype="f64") as e:
+        for parts in ((3, 3), (2, 3), (3, 2)):
+            for key in hubbard_keys(parts):
+                first[key] = apply(e, key)
+                planned.add(key)
+        assert len(planned) == 216  # below the limit: nothing has been dropped yet
+        later = hubbard_keys((2, 2)) + hubbard_keys((1, 3))
+        for i, key in enumerate(later):  # one key of another family after every third Hubbard key: the limit is met among them
+            first[key] = apply(e, key)
+            planned.add(key)
+            if i % 3 == 2 and i // 3 < len(others):
+                first[others[i // 3]] = apply(e, others[i // 3])
+                planned.add(others[i // 3])
+        assert len(planned) == 216 + 144 + 44 > 256 and all(k in first for k in others)
+        assert all(z is not None and np.any(z != 0) for z in first.values())
+        for key in hubbard_keys((3, 3)) + others:  # dropped at the turnover (the later ones of `others` are still cached)
+            assert same(apply(e, key), first[key]), key

@@ -86,3 +86,21 @@ def test_continued_fraction_against_dense_resolvent():
     zs = np.array([0.3 + 0.1j, 1.0 + 0.1j])
     both = continued_fraction(rec, zs)
     assert both.shape == (2,) and both[0] == continued_fraction(rec, zs[0])
+
+
+def test_planners_under_sanitizers(tmp_path):
+    """the one-operator planners of the three bases in a stand-alone program (its own main) built with the address and undefined-behaviour sanitizers:
+    for every operator, spin and site of small, odd and limiting sectors the expanded plan stays inside the source sector, uses no source twice and
+    touches as many destinations as a closed form or a brute-force word list says; the program prints `ok`"""
+    import os
+    import subprocess
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src = os.path.join(root, "lanczosplusplus_amd", "host", "test_obs_plan.cpp")
+    exe = str(tmp_path / "test_obs_plan")
+    out = subprocess.run([os.environ.get("CXX", "g++"), "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                          "-I" + os.path.join(root, "include"), "-I" + os.path.join(root, "lanczosplusplus_amd", "csrc"), "-o", exe, src],
+                         stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert out.returncode == 0, out.stdout
+    run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert run.returncode == 0 and run.stdout.strip().endswith("ok"), run.stdout
