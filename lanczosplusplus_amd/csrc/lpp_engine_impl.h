@@ -11,6 +11,7 @@
 #include "lpp_host.h"
 #include "lpp_kernels.h"
 #include "lpp_pb_kernels.h"
+#include "lpp_pb_plan.h"
 #include "lpp_pbig_kernels.h"
 #include "lpp_tj.h"
 #include "lpp_txgeom.h"
@@ -134,18 +135,12 @@ struct KronState {
 
 // product-basis stored matrix  H = 1 (x) T + C (x) 1 + D  (lpp_pb_kernels.h): everything the 5.8e9-entry CSR of BASELINE
 // config 2 needs is T, C, a 256-entry dictionary and one code per row
-struct PbState {
+struct PbState : PbForm { // (PbForm, lpp_pb_plan.h: the scalars the planner fills; here: what lives on the device or comes after the build)
 	bool active = false;
-	int64_t n_up = 0, n_blk = 0, pitch = 0;
-	int64_t nnz = 0; // entries of the CSR this stands for
 	// in-block matrix T (off-diagonal part): packed for k_pb_up + plain CSR for lpp_engine_get_csr
-	int G = 0;
-	double gval[8] = { 0 };
-	int spb = 0;
 	uint32_t* tw = nullptr;
 	int32_t* tw_off = nullptr;
 	uint16_t* tw_len = nullptr;
-	int64_t tw_words = 0, t_entries = 0, t_slots = 0;
 	int64_t* t_ptr = nullptr;
 	int32_t* t_col = nullptr;
 	double* t_val = nullptr;
@@ -153,58 +148,32 @@ struct PbState {
 	int64_t* c_ptr = nullptr;
 	int32_t* c_col = nullptr;
 	uint8_t* c_code = nullptr;
-	int64_t c_nnz = 0;
-	int rowcap = 0, ids_per_wg = 0, down_grid = 0;
-	int down_rounds = 1, ids_per_round = 0; // k_pb_down: pieces of a workgroup's block range per panel (one LDS image each)
 	void* down_image = nullptr; // rounds > 1: the images, prepared once (k_pb_down_image)
-	size_t down_lds = 0;
-	size_t down_lds_pf = 0; // k_pb_down's PF form: the image plus the task sums
 	int32_t* order = nullptr; // blocks of every workgroup's range by decreasing list length
 	int* pace = nullptr;
-	// launch forms, resolved at the end of pb_build from the LPP_PB_* launch switches and from what was built; the launches read only these
-	bool chain_ok = false; // the chained scale-free step serves this layout (LPP_PB_CHAIN; pb_chain_ok adds: no plain-stream diagonal)
-	bool down_tasks = false; // plain coupling kernel: tasks handed out by the LDS counter, no pacing (LPP_PB_DOWN_TASKS)
-	bool down_pf = false; // chained coupling kernel: the counter form with the u lines touched ahead (LPP_PB_DOWN_PF)
-	bool chain_drop_pace = false; // ... and without the pacing (LPP_PB_CHAIN_PACE=1 keeps it)
-	bool lazy_tx = false; // transposition exchange: the update rides in the next step's pack kernel (LPP_PB_LAZY_TX)
 	double* z = nullptr; // alpha C y of the product in flight (n_blk * pitch doubles)
 	double* u = nullptr; // alpha (T y + D y) of the product in flight
 	double* xy = nullptr; // device scalar: Re<x|y> left by the last combine pass = the next step's <y | x_old>
-	// several GPUs, transposition exchange (pb_tx_*): this rank holds the in-block part for its own blocks [blk0, blk0 + nblk_loc)
-	// (vectors, u and dcode cover those only) and applies the block couplings to the received transposed slice: all n_blk blocks,
-	// rows of pitch_dn positions (= the up-index range of this rank, a multiple of 16)
-	bool tx = false;
-	int64_t blk0 = 0, nblk_loc = 0, pitch_dn = 0;
-	int64_t nnz_loc = 0; // entries of the CSR rows this rank holds (== nnz on one GPU)
 	// chained scale-free steps (pb_launch_chain): the pass r_{j+1} = w_j - g r_j of the last step has not been run yet;
 	// ycur holds w_j, xcur holds r_j, g = *pend_a / *pend_b2
 	bool pending = false;
 	const double* pend_a = nullptr;
 	const double* pend_b2 = nullptr;
-	// rows beyond one LDS window / vectors beyond 4 GiB (lpp_pbig_kernels.h)
-	bool big = false; // in-block part by pieces of W positions (k_pb_up_big)
-	bool big2 = false; // ... two blocks per workgroup and template read (k_pb_up_big2)
-	int W = 0, npieces = 1;
-	uint32_t* fw = nullptr; // entries that leave their piece
+	// rows beyond one LDS window (lpp_pbig_kernels.h): entries that leave their piece
+	uint32_t* fw = nullptr;
 	int32_t* f_off = nullptr;
 	uint16_t* f_len = nullptr;
-	int64_t f_words = 0, f_entries = 0;
 	// positions of a block stored in the order of their list lengths (single-GPU, one-window form): stored position p holds the
 	// basis state perm[p] of the species, inv[perm[p]] = p.  Null: natural order.  Only the boundary knows (vec_from_host / _to_host,
 	// the start vector, the diagonal's assembly, lpp_engine_get_csr); every kernel of a step is position-blind.
 	int32_t* perm = nullptr;
 	int32_t* inv = nullptr;
-	// rows beyond one LDS window, segmented form (lpp_pbseg.h, k_pb_up_seg): T decomposed by the high sites of the species' basis word;
-	// the stored order of the positions (perm / inv) is then the segments by length
-	bool seg = false;
-	bool seg_one = false; // one block per workgroup (pb_chain)
 	// a chain (pb_chain) is planned from the model's parameters alone: no CSR is ever held, lpp_engine_get_csr re-runs the device assembler
 	// from this host copy of what lpp_engine_assemble_heisenberg was given
 	bool chain_model = false;
 	int chain_L = 0, chain_m = 0, chain_nfield = 0;
 	std::vector<double> chain_jpm, chain_jzz, chain_field;
-	int seg_nitems = 0, seg_nsegs = 0, seg_ws = 0, seg_wmax = 0, seg_nc = 0, seg_nh = 0, seg_pre0 = 4;
-	int64_t seg_bytes = 0; // description of T held on the device
+	// segmented form (lpp_pbseg.h, k_pb_up_seg)
 	void* seg_items = nullptr;
 	void* seg_segs = nullptr;
 	void* seg_cross = nullptr;
@@ -212,22 +181,10 @@ struct PbState {
 	void* seg_slices = nullptr;
 	uint32_t* seg_tw = nullptr;
 	uint32_t* seg_xw = nullptr;
-	// complex hoppings: the vectors are complex, a block holds 2 n_c real positions (re, im interleaved; n_up, pitch count doubles), T is
-	// stored REALIFIED (row 2i: (2c, Re t), (2c+1, -Im t); row 2i+1: (2c, Im t), (2c+1, Re t)) so that k_pb_up is the real kernel, the couplings
-	// keep complex values (cdict, k_pb_down<CPLX>), the diagonal code of a position is stored for both of its doubles.  t_ptr / t_col / t_val
-	// keep the complex T of n_c rows ((re, im) pairs) for lpp_engine_get_csr.
-	bool cplx = false;
-	int64_t n_c = 0; // complex positions per block
-	double* cdict = nullptr; // 256 complex coupling values
-	int pre0 = 4; // chained step, two value groups: chunks of group 0 requested one slice ahead (group 1: 8 - pre0)
-	bool wide = false; // vector beyond 4 GiB: k_pb_down<WIDE> (64-bit addresses from line numbers)
-	bool parts = false; // couplings over parts of the source range (k_pb_down_parts; 64-bit addresses too)
-	int nparts = 1, ent_cap = 0, pace_stride = 0, maxr = 0;
-	int64_t part_blocks = 0;
-	int32_t* c_pstart = nullptr;
+	double* cdict = nullptr; // complex hoppings: 256 complex coupling values
+	int32_t* c_pstart = nullptr; // parts form
 	// diagonal
 	double* dict = nullptr; // 256 doubles
-	int ndict = 0;
 	uint8_t* dcode = nullptr; // n_blk * pitch codes
 	double* dval = nullptr; // the diagonal as a plain f64 stream (n_blk * pitch doubles) when it has more than 256 distinct values; the codes are then all 0
 	int64_t* blockbase = nullptr; // first CSR entry of every block (n_blk + 1), for get_csr
@@ -365,32 +322,7 @@ lpp_status finish_setup(lpp_engine* e, int64_t n_local, int64_t n_global, int64_
 int spmv_launch(lpp_engine* e, const DevCsr& A, const void* src, void* x, const void* ydot, double* partial, const EpiScale& sc = EpiScale { nullptr, nullptr, 0 });
 // product-basis layout (lpp_pb.hip)
 void free_pb(lpp_engine* e);
-// complex hoppings (PbState::cplx): pb_build then gets the REALIFIED in-block matrix (2 n_c rows) as t_rp / t_ci / t_va and the couplings'
-// structure as c_rp / c_ci (c_va unused); the complex matrices themselves come through this
-struct PbCplxInput {
-	int64_t n_c; // complex positions per block
-	const int64_t* t_rp; // the complex in-block matrix, n_c rows, values as (re, im) pairs
-	const int32_t* t_ci;
-	const double* t_va;
-	const double* c_va; // complex coupling values, (re, im) pairs, aligned with c_ci
-};
-// complex in-block matrix (n rows, (re, im) pairs, diagonal skipped) -> the realified one of 2n rows (PbState::cplx)
-void pb_realify(int64_t n, const int64_t* rp, const int32_t* ci, const double* va, std::vector<int64_t>& rrp, std::vector<int32_t>& rci, std::vector<double>& rva);
-// What pb_build is given: T and C as host CSRs over one species each (diagonal entries are ignored), sorted 256-entry dictionary holding
-// every coupling value; the caller fills pb.dcode (n_blk*pitch codes) afterwards.  Whatever a caller does not set keeps its default.
-struct PbBuildInput {
-	int64_t n_up = 0, n_blk = 0; // positions per block, blocks
-	const int64_t *t_rp = nullptr, *c_rp = nullptr; // the in-block CSR T (null with `pre`) and the coupling CSR C
-	const int32_t *t_ci = nullptr, *c_ci = nullptr;
-	const double *t_va = nullptr, *c_va = nullptr;
-	const double* dict256 = nullptr;
-	int ndict = 0;
-	// several GPUs (transposition exchange): the rank's block range, the row length of its transposed slice, the blocks of that slice
-	int64_t blk0 = 0, nblk_loc = -1, pitch_dn = 0, nblk_padded = 0;
-	const PbCplxInput* cx = nullptr; // complex hoppings
-	struct SegPlan* pre = nullptr; // a ready-made plan of the segmented form (pb_chain; moved from) standing for pre_nnz entries
-	int64_t pre_nnz = 0;
-};
+// (PbCplxInput, PbBuildInput -- what pb_build is given: lpp_pb_plan.h)
 lpp_status pb_build(lpp_engine* e, const PbBuildInput& in);
 // ... from T and C as the caller holds them: n_up positions, (re, im) values when cplx -- T then goes in realified, the complex matrices as `cx`
 lpp_status pb_build_host(lpp_engine* e, PbBuildInput in, bool cplx);
@@ -458,7 +390,6 @@ int pb_combine_axpy(lpp_engine* e, void* x, const void* y, const EpiScale& sc, c
 lpp_status pb_get_csr(lpp_engine* e, int64_t* rowptr, int32_t* colind, void* values);
 // a handed-over CSR of product-basis form -> the product-basis layout (verified row by row); *done == false: keep the general layout
 lpp_status pb_from_csr(lpp_engine* e, const DevCsr& A, int64_t n_up, bool* done);
-int64_t pb_pitch_for(int64_t n_up);
 // t-J without a stored matrix (lpp_tj.hip).  tj_build: P = the assembler's parameters of the same model (device pointers valid during the
 // call); *done == false: the layout does not apply, the caller assembles the CSR
 void free_tj(lpp_engine* e);

@@ -296,8 +296,8 @@ int edge_colour(const std::vector<std::pair<int, int>>& edges, int nright, std::
 lpp_status pb_pack_template(int64_t rows, int64_t pitch, const int64_t* rp, const int32_t* ci, const double* va, PbTemplate& out, int bank_ways, int64_t window)
 {
 	if (rows <= 0 || pitch < rows || (pitch & 15) != 0) return fail(LPP_ERR_INVALID, "pb_pack_template: bad shape");
-	if (window == 0 && pitch + kPbZeroSlotsHost > 65536) return fail(LPP_ERR_INVALID, "pb_pack_template: bad shape");
-	if (window != 0 && (window < 64 || (window & 63) != 0 || window + kPbZeroSlotsHost > 65536 || rows >= ((int64_t)1 << 24)))
+	if (window == 0 && pitch + kPbZeroSlots > 65536) return fail(LPP_ERR_INVALID, "pb_pack_template: bad shape");
+	if (window != 0 && (window < 64 || (window & 63) != 0 || window + kPbZeroSlots > 65536 || rows >= ((int64_t)1 << 24)))
 		return fail(LPP_ERR_INVALID, "pb_pack_template: window must be a multiple of 64 below 65504, rows below 2^24");
 	if (bank_ways < 1 || bank_ways > 4) return fail(LPP_ERR_INVALID, "pb_pack_template: bank_ways must be 1..4");
 	out = PbTemplate();
@@ -313,7 +313,7 @@ lpp_status pb_pack_template(int64_t rows, int64_t pitch, const int64_t* rp, cons
 			std::memcpy(&k, &va[p], 8);
 			if (std::find(keys.begin(), keys.end(), k) == keys.end()) {
 				keys.push_back(k);
-				if ((int)keys.size() > kPbGroupsMax) return fail(LPP_ERR_INVALID, "pb_pack_template: more than 8 distinct in-block values");
+				if ((int)keys.size() > kPbMaxGroups) return fail(LPP_ERR_INVALID, "pb_pack_template: more than 8 distinct in-block values");
 			}
 		}
 	std::sort(keys.begin(), keys.end());
@@ -487,7 +487,7 @@ extern "C" lpp_status lpp_pb_pack_template(int64_t rows, int64_t pitch, const in
 	if (slices) *slices = t.spb;
 	if (entries) *entries = t.entries;
 	if (slots) *slots = t.slots;
-	if (group_values) std::memcpy(group_values, t.gval, sizeof(double) * lpp::kPbGroupsMax);
+	if (group_values) std::memcpy(group_values, t.gval, sizeof(double) * lpp::kPbMaxGroups);
 	if (off) std::memcpy(off, t.off.data(), sizeof(int32_t) * t.off.size());
 	if (len) std::memcpy(len, t.len.data(), sizeof(uint16_t) * t.len.size());
 	if (words) std::memcpy(words, t.words.data(), sizeof(uint32_t) * t.words.size());

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/lpp_engine.h"
+#include "lpp_pb_geom.h"
 
 namespace lpp {
 
@@ -35,12 +36,9 @@ bool tridiag_qr(int n, const double* d, const double* e, double* w, double* z);
 // ---------------------------------------------------------------------------------------------
 namespace lpp {
 
-constexpr int kPbGroupsMax = 8;
-constexpr int kPbZeroSlotsHost = 32;
-
 struct PbTemplate {
 	int G = 0; // value groups
-	double gval[kPbGroupsMax] = { 0 };
+	double gval[kPbMaxGroups] = { 0 };
 	int spb = 0; // 64-row slices
 	std::vector<int32_t> off; // [spb*G] first chunk of (slice, group)
 	std::vector<uint16_t> len; // [spb*G] chunks (a chunk = 4 slots)
@@ -62,7 +60,7 @@ struct PbTemplate {
 
 // rows x rows CSR (rp, ci, va); entries with ci == row (the diagonal) are skipped.  pitch: the zero slots start at window
 // index `pitch` (a multiple of 16, >= rows; pitch + 32 <= 65536).  Fails (LPP_ERR_INVALID) when the off-diagonal part has more
-// than kPbGroupsMax distinct values.
+// than kPbMaxGroups distinct values.
 // window > 0: pieces of `window` positions (see PbTemplate::W); the zero slots then sit at window index `window`.
 lpp_status pb_pack_template(int64_t rows, int64_t pitch, const int64_t* rp, const int32_t* ci, const double* va, PbTemplate& out, int bank_ways = 2,
                             int64_t window = 0);
@@ -76,14 +74,13 @@ int edge_colour(const std::vector<std::pair<int, int>>& edges, int nright, std::
 // ---------------------------------------------------------------------------------------------
 // Segmented in-block form for rows beyond one LDS window (lpp_pbseg.h): the host-side plan.
 // ---------------------------------------------------------------------------------------------
-#include "lpp_pbseg.h"
 namespace lpp {
 
 struct SegPlan {
 	int L = 0, n = 0, s = 0; // sites, particles of the species; high sites
 	int64_t n_up = 0;
 	int G = 1; // value groups of the low-low hops (1 or 2)
-	double gval[kPbGroupsMax] = { 0 };
+	double gval[kPbMaxGroups] = { 0 };
 	std::vector<int32_t> perm, inv; // stored position -> basis index and back
 	std::vector<SegInst> segs;
 	std::vector<SegCross> cross;

@@ -17,12 +17,9 @@
 // Vectors are PITCHED: block b starts at element b*pitch, pitch = N_up rounded up to a multiple of 16 (padding stays zero).
 #pragma once
 #include "lpp_kernels.h"
+#include "lpp_pb_geom.h"
 
 namespace lpp {
-
-constexpr int kPbMaxGroups = 8; // distinct off-diagonal values of the in-block matrix
-constexpr int kPbZeroSlots = 32; // zero-valued window elements behind the row (one per LDS bank) that padding entries read
-constexpr int kPbUpThreads = 1024;
 
 // ---------------------------------------------------------------------------------------------
 // in-block part + diagonal:  x[b][i] = beta' x[b][i] + alpha ( sum_k T[i][c_k] y[b][c_k] + D[b][i] y[b][i] )   (+ Re<y|x> partial)
@@ -50,8 +47,6 @@ struct PbUpArgs {
 	const double* g_b2; // b_{j-2}^2
 };
 
-constexpr int kPbPre = 4; // chunks (of 4 slots) of every (slice, group) requested one slice ahead
-
 // A wave's vector-memory results return IN ORDER (s_waitcnt vmcnt): a wait for an L2 load is also a wait for every HBM load
 // issued before it, whatever the look-ahead (measured on a version that read-modify-wrote x here: 77 % of the wave cycles
 // spent waiting; 47 % with a four-slice look-ahead, which the in-order queue defeats).  So this kernel touches HBM only in
@@ -65,14 +60,9 @@ constexpr int kPbPre = 4; // chunks (of 4 slots) of every (slice, group) request
 // One-window form: the chunks of a list are stored in PAIRS (lane l's words of chunks 2q and 2q+1 side by side, pb_build) and requested with
 // one 16-byte load per pair.  A wave-level load of 8 or of 16 bytes per lane occupies a CU's vector-memory pipeline for the same ~17 cycles
 // (scripts/experiments/r04_tcp_rate.hip: 70 against 130-140 GB/s per CU), and the number of template loads was what the gather phase of
-// this kernel waited for.  Look-ahead depths are then even.
-#ifndef LPP_PB_PAIRS
-#define LPP_PB_PAIRS 1
-#endif
-constexpr bool kPbPairs = LPP_PB_PAIRS != 0;
+// this kernel waited for.
+// Look-ahead depths are then even (kPbPairs, pb_depth: lpp_pb_geom.h).
 constexpr int kPbPreMax = 6; // deepest look-ahead of one value group (k_pb_up's PRE0)
-// look-ahead depth of value group g (two groups share 8 chunks as PRE0 + (8 - PRE0); with pairs PRE0 = 6 leaves group 1 four)
-__host__ __device__ constexpr int pb_depth(int GG, int g, int PRE0) { return GG == 2 ? (g == 0 ? PRE0 : (kPbPairs && PRE0 >= 6 ? 4 : 2 * kPbPre - PRE0)) : kPbPre; }
 constexpr int kPbPreMin = 1; // chunks of a group requested whatever its list length (no branch)
 template <int GT> struct PbWords {
 	uint2 w[GT][kPbPreMax]; // only the first `depth(g)` chunks of group g are ever touched (the others take no register)
@@ -97,15 +87,7 @@ __device__ __forceinline__ uint32_t pb_hi8(uint32_t w)
 typedef __attribute__((address_space(3))) const double pb_lds_cdouble;
 __device__ __forceinline__ double pb_lds_abs(uint32_t byte_addr) { return *(pb_lds_cdouble*)(uintptr_t)byte_addr; }
 
-// LDS layout (all dynamic, so that the window starts at LDS address 0 and a template word IS the address):
-//   [0, (pitch+32)*8) window + zero slots | dcode_s[pitch] | off_s[spb*G] | len_s[spb*G] | dict_s[256] | smem[16] | (pad)
-__host__ __device__ inline size_t pb_up_meta_offset(int64_t pitch) { return sizeof(double) * (size_t)(pitch + kPbZeroSlots) + (size_t)pitch; }
-__host__ __device__ inline size_t pb_up_dict_offset(int64_t pitch, int spb, int G) { return (pb_up_meta_offset(pitch) + (size_t)spb * (size_t)G * 6 + 15) & ~(size_t)15; }
-__host__ __device__ inline size_t pb_up_lds_bytes(int64_t pitch, int spb, int G)
-{
-	return pb_up_dict_offset(pitch, spb, G) + 256 * sizeof(double) + (kPbUpThreads / 64) * sizeof(double) + 16;
-}
-
+// (LDS layout and size: pb_up_lds_bytes, lpp_pb_geom.h)
 // GT = number of value groups (1 or 2: unrolled, with look-ahead; 0: any G <= 8, plain loop).
 // CHAIN: the chained form of the scale-free Lanczos step (pb_launch_chain).  The previous step left w = H r/b - (b/b') r' complete
 // in wbuf and its own vector r in ybuf, but did NOT run the pass  r_next = w - g r  (g = raw / b^2): this kernel does it while it
@@ -397,13 +379,7 @@ template <bool DOT, int GT, bool CHAIN = false, int PRE0 = kPbPre> __global__ __
 // The kernel only READS y (L2 hits after the first touch of a line) and WRITES z (non-temporal): no HBM load sits in the
 // in-order return queue in front of the gathers (an x read-modify-write here cost an HBM round trip per task).
 // ---------------------------------------------------------------------------------------------
-// LDS image of k_pb_down: one 32-bit word per place of a block's coupling list (source block | value code << 24), rows of
-// `stride` words.  A lane reads the 4 places of a chunk with ONE 16-byte LDS read (the 8 blocks of a task sit `stride` words
-// apart: stride / 4 odd puts their 16-byte segments on different bank groups); separate 2-byte index and 1-byte code arrays
-// cost 8 LDS instructions per chunk instead, and the LDS pipeline was what the kernel's instruction skeleton waited for
-// (0.8 of its 0.875 ms at config 2: scripts/experiments/r03_down_parts_ab.sh).
-__host__ __device__ inline int pb_down_stride(int rowcap) { return ((rowcap >> 2) & 1) ? rowcap : rowcap + 4; }
-__host__ __device__ inline size_t pb_down_lds_bytes(int ids_per_wg, int rowcap) { return (((size_t)ids_per_wg * 8 + 15) & ~(size_t)15) + (size_t)ids_per_wg * (size_t)pb_down_stride(rowcap) * 4 + 16; }
+// (the LDS image of the coupling lists: pb_down_stride / pb_down_lds_bytes, lpp_pb_geom.h)
 // sum over the wave in a fixed order without LDS traffic (wave_sum's shuffles are LDS instructions, and the coupling kernel's
 // instruction skeleton waits on the LDS pipeline): DPP shifts inside each row of 16 lanes, then the four row sums in lane order
 template <int CTRL> __device__ __forceinline__ double dpp_shr(double v)
@@ -426,8 +402,6 @@ __device__ __forceinline__ double wave_sum_rows(double v)
 	};
 	return ((lane_val(15) + lane_val(31)) + lane_val(47)) + lane_val(63);
 }
-// the PF form's task sums behind the image in k_pb_down's dynamic LDS: two buffers of (Re<y|z>, |z - s y|^2) per task of 8 blocks
-__host__ __device__ inline size_t pb_down_task_sum_bytes(int ids_per_wg) { return (size_t)((ids_per_wg + 7) / 8) * 4 * sizeof(double); }
 
 // The image of `nown` blocks order[b0 ...]: row[il] = block * rowmul, len[il] = its list length, place[il * stride + k] = source block | code << 24.
 // Places beyond a list carry code 0 (+0.0) and the address the task's first block (the longest list) reads at this place, so the filling

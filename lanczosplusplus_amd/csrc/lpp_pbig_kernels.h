@@ -24,11 +24,6 @@
 
 namespace lpp {
 
-constexpr int kPbMaxParts = 8;
-constexpr int kPbBigThreads = 512;
-// the coupling kernel keeps one double2 per task round and lane for the whole panel: 512 threads (8 waves, up to 256 registers
-// each) per CU rather than 1024 with 128 -- ten rounds of sums, two chunks of gathers and the addresses spill at 128
-constexpr int kPbPartsThreads = 512;
 #ifndef LPP_PB_PARTS_DEPTH
 #define LPP_PB_PARTS_DEPTH 4
 #endif
@@ -54,12 +49,6 @@ struct PbUpBigArgs {
 	double* partial; // per-workgroup Re<y|u> (null: not wanted)
 	EpiScale sc; // only alpha is used
 };
-
-// LDS: window (W + 32 zero slots) | dcode[W] | dict[256] | gval[9] | smem[THREADS/64]
-__host__ __device__ inline size_t pb_big_lds_bytes(int W)
-{
-	return ((sizeof(double) * (size_t)(W + kPbZeroSlots) + (size_t)W + 15) & ~(size_t)15) + sizeof(double) * (256 + kPbMaxGroups + 1 + kPbBigThreads / 64) + 16;
-}
 
 // Per slice a wave needs: the list heads (scalars), the template words of every value group and the far words (vector loads
 // that depend on the heads), the far elements (loads that depend on the far words) and the LDS gathers (which depend on the
@@ -306,13 +295,7 @@ template <bool DOT, int GT, int PRE = kBigPre> __global__ __launch_bounds__(kPbB
 // second one within the 64 KB reach of an LDS instruction's offset field, so a template entry still is the address) and applies every
 // word it loads to both: half the template traffic and half the word decoding per output row.
 // ---------------------------------------------------------------------------------------------
-constexpr int kPbBig2Threads = 1024;
 constexpr int kBig2FarPre = 4;
-
-__host__ __device__ inline size_t pb_big2_lds_bytes(int W)
-{
-	return ((2 * sizeof(double) * (size_t)(W + kPbZeroSlots) + 2 * (size_t)W + 15) & ~(size_t)15) + sizeof(double) * (256 + kPbMaxGroups + 1 + kPbBig2Threads / 64) + 16;
-}
 
 template <int GG> struct Big2Words {
 	uint2 w[GG][kPbPreMax]; // only the first depth(g) chunks of group g are touched
@@ -566,14 +549,7 @@ struct PbDownPartsArgs {
 	int pace_stride; // counters per group
 };
 
-// LDS image of a workgroup's coupling lists, compact (a padded image -- every part of every list as long as the longest --
-// is 170 KB at N_dn = 38760 in four parts; this one 82 KB): line[ids] | pstart[ids][NH+1] (places) | n4[tasks][NH] | idx[ent] | code[ent]
-__host__ __device__ inline size_t pb_parts_lds_bytes(int ids_per_wg, int ent_cap, int nparts)
-{
-	const size_t ngroups = (size_t)(ids_per_wg + 7) / 8;
-	return (size_t)ids_per_wg * (4 + 2 * ((size_t)nparts + 1)) + ((ngroups * (size_t)nparts + 1) & ~(size_t)1) + (size_t)(ent_cap + 8) * 3 + 64;
-}
-
+// (its LDS image, line[ids] | pstart[ids][NH+1] (places) | n4[tasks][NH] | idx[ent] | code[ent]: pb_parts_lds_bytes, lpp_pb_geom.h)
 template <int THREADS, int MAXR> __global__ __launch_bounds__(THREADS) void k_pb_down_parts(PbDownPartsArgs a)
 {
 	extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];

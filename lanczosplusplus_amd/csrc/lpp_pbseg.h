@@ -23,11 +23,18 @@
 #pragma once
 #include <stdint.h>
 
+// size formulas shared by kernels and plain-C++ planning (here and in lpp_pb_geom.h)
+#ifdef __HIPCC__
+#define LPP_PB_HD __host__ __device__
+#else
+#define LPP_PB_HD
+#endif
+
 namespace lpp {
 
 constexpr int kSegMaxCross = 6; // PAIRS of cross hops per segment the kernel carries (every segment's list is padded to the instance's NC with value 0.0)
 constexpr int kSegMaxHh = 16; // high-high entries per segment (one block per workgroup -- chains up to 17 high sites; two blocks per workgroup: 12)
-__host__ __device__ constexpr int pb_seg_hh_cap(int rows) { return rows == 1 ? kSegMaxHh : 12; } // entries per segment in the LDS copy
+LPP_PB_HD constexpr int pb_seg_hh_cap(int rows) { return rows == 1 ? kSegMaxHh : 12; } // entries per segment in the LDS copy
 constexpr int kSegMaxSegs = 16; // segments per item (LDS tables)
 constexpr int kSegWinPad = 2; // window index of an item's first position (the staged run starts at an even element)
 

@@ -325,7 +325,7 @@ lpp_status pb_seg_plan_model(int L, int n, const std::vector<double>& hv, const 
 			TypeInfo TI;
 			TI.slice_first = (int32_t)P.slices.size();
 			TI.zero_at = (int32_t)((kSegWinPad + wl + 2 + 31) & ~(int64_t)31);
-			if (TI.zero_at + kPbZeroSlotsHost > 8192) return LPP_OK; // 16-bit window indices x 8 stay below 64 KB
+			if (TI.zero_at + kPbZeroSlots > 8192) return LPP_OK; // 16-bit window indices x 8 stay below 64 KB
 			// slices: 64 consecutive positions of one segment; in-window lists per (slice, group)
 			int64_t oa = 0;
 			for (size_t i = i0; i < i1; i++) {
@@ -457,7 +457,7 @@ lpp_status pb_seg_plan_model(int L, int n, const std::vector<double>& hv, const 
 		for (size_t j = 0; j < P.slices.size(); j++) longer += P.slices[j].nc[0] > 2 ? 1 : 0;
 		if (longer * 8 <= (int64_t)P.slices.size()) P.pre0 = 2;
 	}
-	P.ws = P.zmax + kPbZeroSlotsHost; // window stride in elements (even)
+	P.ws = P.zmax + kPbZeroSlots; // window stride in elements (even)
 	P.words.resize(P.words.size() + 256 * 4, (uint32_t)P.zmax | ((uint32_t)P.zmax << 16)); // slack for the look-ahead loads
 	const int32_t zero_table = (int32_t)P.xwords.size(); // 8192 + 64 zero words: the table of the filling entries (any offset of any segment stays inside)
 	P.xwords.resize(P.xwords.size() + 8192 + 64, 0);

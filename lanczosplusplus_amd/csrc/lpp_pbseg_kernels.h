@@ -40,18 +40,10 @@ struct PbSegArgs {
 	int flat;
 };
 
-constexpr int kSegThreads = 512; // 8 waves of up to 256 registers: two slices' loads from the rows in flight per wave
 constexpr int kSegPre = 4; // in-window chunks of every (slice, group) requested one slice ahead
 constexpr int kSegStage = 16; // 16-byte pieces per thread that stage the two windows: ALL in flight together (2 x 8128 elements at most)
 
-// LDS: [0, 2 ws) windows | dcode[2][wmax + 32] | 2 x slice heads[160] | 2 x cross[16 * 6] | 2 x hh[16 * 12] | dict[256] | smem[8] | per wave 64 x 2 doubles (high-high sums)
-__host__ __device__ inline size_t pb_seg_dcode_stride(int wmax) { return ((size_t)wmax + 32 + 15) & ~(size_t)15; }
-__host__ __device__ inline size_t pb_seg_tab_offset(int ws, int wmax) { return (2 * sizeof(double) * (size_t)ws + 2 * pb_seg_dcode_stride(wmax) + 15) & ~(size_t)15; }
-// (rows: blocks per workgroup; one block per workgroup alternates between TWO sets of tables)
-__host__ __device__ inline size_t pb_seg_lds_bytes(int ws, int wmax, int rows)
-{
-	return pb_seg_tab_offset(ws, wmax) + (rows == 1 ? 2 : 1) * (sizeof(SegSlice) * kSegMaxSlices + sizeof(SegCross) * kSegMaxSegs * kSegMaxCross + sizeof(SegHh) * kSegMaxSegs * pb_seg_hh_cap(rows)) + sizeof(double) * (256 + kSegThreads / 64 + 2 * kSegThreads) + 16;
-}
+// (LDS layout and size: pb_seg_lds_bytes, lpp_pb_geom.h; kSegThreads = 512 lives there with it)
 
 template <int GG> struct SegHeads { // wave-uniform
 	int nc[GG], off[GG];

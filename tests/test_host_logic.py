@@ -382,3 +382,23 @@ def test_tj_hole_major_plan_reproduces_the_oracle_matrix():
     k = int(A.rowptr[100]) + (0 if A.colind[A.rowptr[100]] != 100 else 1)
     vals[k] = -vals[k]
     assert plan(L, nup, ndown, hop, jpm, oracle.Csr(A.rowptr, A.colind, vals))[0] == 0
+
+
+def test_product_basis_planner_under_sanitizers(tmp_path):
+    """the planner of the product-basis build (csrc/lpp_pb_plan.cpp) in a stand-alone program (its own main) built with the address and
+    undefined-behaviour sanitizers: over small species, block counts, CU counts, the exchange on and off and every forced form each plan has
+    its permutations, repacked template, coupling codes, block bases, block order, rounds, part starts and LDS sizes right, the launch forms
+    at the 2x6 ladder's sizes are those of test_gpu_parity.LAUNCH_FORMS, and every refusal these sizes reach keeps its text; the program
+    prints `ok`"""
+    import subprocess
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    csrc = os.path.join(root, "lanczosplusplus_amd", "csrc")
+    srcs = [os.path.join(root, "lanczosplusplus_amd", "host", "test_pb_plan.cpp")] + [os.path.join(csrc, f) for f in ("lpp_host.cpp", "lpp_pbseg_host.cpp", "lpp_pb_plan.cpp")]
+    exe = str(tmp_path / "test_pb_plan")
+    out = subprocess.run([os.environ.get("CXX", "g++"), "-O1", "-g1", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                          "-I" + os.path.join(root, "include"), "-I" + csrc, "-o", exe] + srcs,
+                         stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert out.returncode == 0, out.stdout
+    run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert run.returncode == 0 and run.stdout.strip().endswith("ok"), run.stdout
