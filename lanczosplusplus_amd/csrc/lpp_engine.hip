@@ -8,13 +8,12 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
-#include <numeric>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "lpp_assemble_kernels.h"
@@ -23,50 +22,6 @@
 using namespace lpp;
 
 namespace lpp {
-
-// ---------------------------------------------------------------------------------------------
-// small helpers
-// ---------------------------------------------------------------------------------------------
-void free_csr(DevCsr& A)
-{
-	if (A.owned) {
-		if (A.rowptr) (void)hipFree(A.rowptr);
-		if (A.col) (void)hipFree(A.col);
-		if (A.val) (void)hipFree(A.val);
-	}
-	if (A.slice_ptr) (void)hipFree(A.slice_ptr);
-	if (A.row_len) (void)hipFree(A.row_len);
-	if (A.scol) (void)hipFree(A.scol);
-	if (A.sval) (void)hipFree(A.sval);
-	if (A.codes) (void)hipFree(A.codes);
-	if (A.code_ptr) (void)hipFree(A.code_ptr);
-	if (A.dict) (void)hipFree(A.dict);
-	if (A.rrowptr) (void)hipFree(A.rrowptr);
-	if (A.dia_off) (void)hipFree(A.dia_off);
-	if (A.dia_val) (void)hipFree(A.dia_val);
-	if (A.dcode) (void)hipFree(A.dcode);
-	if (A.tw) (void)hipFree(A.tw);
-	if (A.tw_off) (void)hipFree(A.tw_off);
-	if (A.tw_len) (void)hipFree(A.tw_len);
-	if (A.out_part) {
-		for (int q = 0; q < A.split_parts; q++) free_csr(A.out_part[q]);
-		delete[] A.out_part;
-	}
-	if (A.out_rowmap) (void)hipFree(A.out_rowmap);
-	A = DevCsr();
-}
-
-static int pick_group(int64_t nrows, int64_t nnz)
-{
-	if (const char* s = getenv("LPP_SPMV_G")) {
-		int g = atoi(s);
-		if (g == 4 || g == 8 || g == 16 || g == 32 || g == 64) return g;
-	}
-	const double avg = nrows > 0 ? (double)nnz / (double)nrows : 1.0;
-	int g = 4;
-	while (g < 64 && g * 2 <= avg / 2.0 + 1e-9) g *= 2; // largest power of two <= avg/2, in [4,64]
-	return g;
-}
 
 template <typename T, bool DOT>
 static void launch_rowgroup(const DevCsr& A, const T* src, T* x, const T* ydot, double* partial, int nblocks,
@@ -84,6 +39,63 @@ static void launch_rowgroup(const DevCsr& A, const T* src, T* x, const T* ydot, 
 	}
 }
 
+// the kernel arguments of a sliced matrix; rowmap: the rows of an out part of the split-panel layout (null: rows in place)
+template <typename T>
+static SlicedArgs<T> sliced_args(const DevCsr& A, const void* src, void* x, const void* ydot, double* partial, const EpiScale& sc, int xcd_map, const int32_t* rowmap)
+{
+	SlicedArgs<T> a {};
+	a.g = A.geom;
+	a.slice_ptr = A.slice_ptr;
+	a.row_len = A.row_len;
+	a.col = A.scol;
+	a.val = (const T*)A.sval;
+	a.codes = A.codes;
+	a.code_ptr = A.code_ptr;
+	a.dict = A.dict;
+	a.src = (const T*)src;
+	a.x = (T*)x;
+	a.ydot = (const T*)ydot;
+	a.partial = partial;
+	a.xcd_map = xcd_map;
+	a.sc = sc;
+	a.dia_stride = A.dia_stride;
+	a.dia_off = A.dia_off;
+	a.dia_val = (const T*)A.dia_val;
+	a.tmpl = A.tmpl;
+	a.dcode = A.dcode;
+	a.tw = A.tw;
+	a.tw_off = A.tw_off;
+	a.tw_len = A.tw_len;
+	a.rowmap = rowmap;
+	a.pad = A.pad;
+	return a;
+}
+
+// the (DOT, CODED, U) instantiation of a sliced kernel: launch(dot, coded, u) gets them as integral constants
+template <typename F> static void with_sliced_variant(bool dot, bool coded, bool u8, F&& launch)
+{
+	using No = std::false_type;
+	using Yes = std::true_type;
+	using U4 = std::integral_constant<int, 4>;
+	using U8 = std::integral_constant<int, 8>;
+	switch ((dot ? 4 : 0) | (coded ? 2 : 0) | (u8 ? 1 : 0)) {
+	case 0: launch(No {}, No {}, U4 {}); break;
+	case 1: launch(No {}, No {}, U8 {}); break;
+	case 2: launch(No {}, Yes {}, U4 {}); break;
+	case 3: launch(No {}, Yes {}, U8 {}); break;
+	case 4: launch(Yes {}, No {}, U4 {}); break;
+	case 5: launch(Yes {}, No {}, U8 {}); break;
+	case 6: launch(Yes {}, Yes {}, U4 {}); break;
+	default: launch(Yes {}, Yes {}, U8 {}); break;
+	}
+}
+
+template <typename T, bool DOT, bool CODED, int U, bool L16> static void launch_window(const SlicedArgs<T>& a, int nb, size_t lds_bytes, hipStream_t st)
+{
+	(void)hipFuncSetAttribute((const void*)k_spmv_window<T, DOT, CODED, U, L16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+	k_spmv_window<T, DOT, CODED, U, L16><<<nb, kWinThreads, lds_bytes, st>>>(a);
+}
+
 // x += A * src ; if partial != nullptr also partial[b] = block sums of Re<ydot|x>.
 // Returns the number of partials written (0 when partial == nullptr).
 template <typename T> static int spmv_launch_t(lpp_engine* e, const DevCsr& A, const void* src, void* x, const void* ydot, double* partial, const EpiScale& sc)
@@ -91,77 +103,27 @@ template <typename T> static int spmv_launch_t(lpp_engine* e, const DevCsr& A, c
 	hipStream_t st = e->stream;
 	if (A.nrows == 0) return 0;
 	if (A.sliced) {
-		SlicedArgs<T> a;
-		a.g = A.geom;
-		a.slice_ptr = A.slice_ptr;
-		a.row_len = A.row_len;
-		a.col = A.scol;
-		a.val = (const T*)A.sval;
-		a.codes = A.codes;
-		a.code_ptr = A.code_ptr;
-		a.dict = A.dict;
-		a.src = (const T*)src;
-		a.x = (T*)x;
-		a.ydot = (const T*)ydot;
-		a.partial = partial;
-		a.xcd_map = (e->k2_variant >> 1) & 1;
-		a.sc = sc;
-		a.dia_stride = A.dia_stride;
-		a.dia_off = A.dia_off;
-		a.dia_val = (const T*)A.dia_val;
-		a.tmpl = A.tmpl;
-		a.dcode = A.dcode;
-		a.tw = A.tw;
-		a.tw_off = A.tw_off;
-		a.tw_len = A.tw_len;
-		a.rowmap = nullptr;
-		a.pad = A.pad;
-		const bool dot = partial != nullptr;
+		const SlicedArgs<T> a = sliced_args<T>(A, src, x, ydot, partial, sc, (e->k2_variant >> 1) & 1, nullptr);
 		const bool u8 = (e->k2_variant & 4) != 0;
-		const int sel = (dot ? 4 : 0) | (A.coded ? 2 : 0) | (u8 ? 1 : 0);
 		int nb;
 		if (A.window) {
 			const size_t lds_bytes = sizeof(T) * (size_t)std::max<int64_t>(A.geom.B, 64);
 			const int per_cu = std::max(1, std::min(2, (int)((160 * 1024 - 4096) / (lds_bytes + 1))));
 			nb = (int)std::max<int64_t>(1, std::min<int64_t>(A.geom.nblocks, (int64_t)e->num_cus * per_cu));
 			if (nb >= 8) nb &= ~7;
-#define LPP_K3(DOT_, CODED_, U_)                                                                                      \
-	do {                                                                                                              \
-		if (A.local16) {                                                                                              \
-			(void)hipFuncSetAttribute((const void*)k_spmv_window<T, DOT_, CODED_, U_, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); \
-			k_spmv_window<T, DOT_, CODED_, U_, true><<<nb, kWinThreads, lds_bytes, st>>>(a);                            \
-		} else {                                                                                                      \
-			(void)hipFuncSetAttribute((const void*)k_spmv_window<T, DOT_, CODED_, U_, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); \
-			k_spmv_window<T, DOT_, CODED_, U_, false><<<nb, kWinThreads, lds_bytes, st>>>(a);                           \
-		}                                                                                                             \
-	} while (0)
-			switch (sel) {
-			case 0: LPP_K3(false, false, 4); break;
-			case 1: LPP_K3(false, false, 8); break;
-			case 2: LPP_K3(false, true, 4); break;
-			case 3: LPP_K3(false, true, 8); break;
-			case 4: LPP_K3(true, false, 4); break;
-			case 5: LPP_K3(true, false, 8); break;
-			case 6: LPP_K3(true, true, 4); break;
-			default: LPP_K3(true, true, 8); break;
-			}
-#undef LPP_K3
+			with_sliced_variant(partial != nullptr, A.coded, u8, [&](auto dot, auto coded, auto u) {
+				if (A.local16)
+					launch_window<T, decltype(dot)::value, decltype(coded)::value, decltype(u)::value, true>(a, nb, lds_bytes, st);
+				else
+					launch_window<T, decltype(dot)::value, decltype(coded)::value, decltype(u)::value, false>(a, nb, lds_bytes, st);
+			});
 		} else {
 			const int64_t need = (A.geom.nslices + (kBlock / 64) - 1) / (kBlock / 64);
 			nb = (int)std::max<int64_t>(1, std::min<int64_t>(need, e->spmv_max_blocks));
 			if (nb >= 8) nb &= ~7; // multiple of 8 so the XCD-contiguous mapping applies
-#define LPP_K2(DOT_, CODED_, U_) k_spmv_sliced<T, DOT_, CODED_, U_><<<nb, kBlock, 0, st>>>(a)
-			switch (sel) {
-			case 0: LPP_K2(false, false, 4); break;
-			case 1: LPP_K2(false, false, 8); break;
-			case 2: LPP_K2(false, true, 4); break;
-			case 3: LPP_K2(false, true, 8); break;
-			case 4: LPP_K2(true, false, 4); break;
-			case 5: LPP_K2(true, false, 8); break;
-			case 6: LPP_K2(true, true, 4); break;
-			default: LPP_K2(true, true, 8); break;
-			}
-#undef LPP_K2
+			with_sliced_variant(partial != nullptr, A.coded, u8, [&](auto dot, auto coded, auto u) {
+				k_spmv_sliced<T, decltype(dot)::value, decltype(coded)::value, decltype(u)::value><<<nb, kBlock, 0, st>>>(a);
+			});
 		}
 		return partial ? nb : 0;
 	}
@@ -180,35 +142,16 @@ template <typename T> static int spmv_launch_t(lpp_engine* e, const DevCsr& A, c
 template <typename T> static int spmv_launch_out_t(lpp_engine* e, const DevCsr& A, const int32_t* rowmap, const void* src, void* x, const void* ydot, double* partial, const EpiScale& sc)
 {
 	if (A.nrows == 0) return 0;
-	SlicedArgs<T> a {};
-	a.g = A.geom;
-	a.slice_ptr = A.slice_ptr;
-	a.row_len = A.row_len;
-	a.col = A.scol;
-	a.val = (const T*)A.sval;
-	a.codes = A.codes;
-	a.code_ptr = A.code_ptr;
-	a.dict = A.dict;
-	a.src = (const T*)src;
-	a.x = (T*)x;
-	a.ydot = (const T*)ydot;
-	a.partial = partial;
-	a.xcd_map = 1;
-	a.sc = sc;
-	a.rowmap = rowmap;
+	const SlicedArgs<T> a = sliced_args<T>(A, src, x, ydot, partial, sc, 1, rowmap);
 	// two resident workgroups per CU walk the panels together (measured at BASELINE config 2, scripts/experiments/r03_generic_ab.sh:
 	// 512 workgroups 9.85 ms and 60.7 GB of fabric reads, 2048 11.1 ms / 66.1 GB, 4096 11.3 ms / 66.2 GB)
 	const int64_t need = (A.geom.nslices + (kBlock / 64) - 1) / (kBlock / 64);
 	int nb = (int)std::max<int64_t>(1, std::min<int64_t>(need, std::min<int64_t>(e->spmv_max_blocks, 2 * (int64_t)e->num_cus)));
 	if (nb >= 8) nb &= ~7;
 	hipStream_t st = e->stream;
-	const int sel = (partial ? 2 : 0) | (A.coded ? 1 : 0);
-	switch (sel) {
-	case 0: k_spmv_sliced<T, false, false, 8><<<nb, kBlock, 0, st>>>(a); break;
-	case 1: k_spmv_sliced<T, false, true, 8><<<nb, kBlock, 0, st>>>(a); break;
-	case 2: k_spmv_sliced<T, true, false, 8><<<nb, kBlock, 0, st>>>(a); break;
-	default: k_spmv_sliced<T, true, true, 8><<<nb, kBlock, 0, st>>>(a); break;
-	}
+	with_sliced_variant(partial != nullptr, A.coded, true, [&](auto dot, auto coded, auto u) {
+		k_spmv_sliced<T, decltype(dot)::value, decltype(coded)::value, decltype(u)::value><<<nb, kBlock, 0, st>>>(a);
+	});
 	return partial ? nb : 0;
 }
 
@@ -229,677 +172,6 @@ int spmv_launch(lpp_engine* e, const DevCsr& A, const void* src, void* x, const 
 		return np;
 	}
 	return e->is_complex ? spmv_launch_t<cplx>(e, A, src, x, ydot, partial, sc) : spmv_launch_t<double>(e, A, src, x, ydot, partial, sc);
-}
-
-// distinct values of A.val -> sorted dictionary on the device; returns false when there are more than 256
-template <typename T> static lpp_status try_build_dict(lpp_engine* e, DevCsr& A, const T* vals, int64_t nvals, bool* ok)
-{
-	*ok = false;
-	if (nvals == 0) return LPP_OK;
-	unsigned long long* table = nullptr;
-	int* overflow = nullptr;
-	HIP_TRY_MEM(hipMalloc(&table, sizeof(unsigned long long) * kDictTable));
-	if (hipMalloc(&overflow, sizeof(int)) != hipSuccess) {
-		(void)hipFree(table);
-		return fail(LPP_ERR_NOMEM, "dictionary scratch allocation failed");
-	}
-	(void)hipMemsetAsync(table, 0xff, sizeof(unsigned long long) * kDictTable, e->stream);
-	(void)hipMemsetAsync(overflow, 0, sizeof(int), e->stream);
-	const int64_t nd = nvals * (int64_t)(sizeof(T) / sizeof(double));
-	k_dict_collect<<<2048, kBlock, 0, e->stream>>>((const double*)vals, nd, table, overflow);
-	std::vector<unsigned long long> host(kDictTable);
-	int ov = 0;
-	hipError_t e1 = hipMemcpyAsync(host.data(), table, sizeof(unsigned long long) * kDictTable, hipMemcpyDeviceToHost, e->stream);
-	hipError_t e2 = hipMemcpyAsync(&ov, overflow, sizeof(int), hipMemcpyDeviceToHost, e->stream);
-	hipError_t e3 = hipStreamSynchronize(e->stream);
-	(void)hipFree(table);
-	(void)hipFree(overflow);
-	if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return fail(LPP_ERR_HIP, "dictionary collection failed");
-	std::vector<unsigned long long> keys;
-	keys.push_back(0ull); // code 0 is reserved for +0.0: padded / inactive slots decode to an exact zero
-	for (unsigned long long k : host)
-		if (k != kDictEmpty && k != 0ull) keys.push_back(k);
-	if (ov || keys.size() > 256) return LPP_OK;
-	std::sort(keys.begin(), keys.end());
-	std::vector<double> dict(256);
-	for (size_t i = 0; i < 256; i++) {
-		const unsigned long long k = keys[std::min(i, keys.size() - 1)];
-		std::memcpy(&dict[i], &k, sizeof(double));
-	}
-	HIP_TRY_MEM(hipMalloc(&A.dict, sizeof(double) * 256));
-	HIP_TRY(hipMemcpyAsync(A.dict, dict.data(), sizeof(double) * 256, hipMemcpyHostToDevice, e->stream));
-	HIP_TRY(hipStreamSynchronize(e->stream));
-	A.ndict = (int)keys.size();
-	*ok = true;
-	return LPP_OK;
-}
-
-// LPP_VERBOSE=1: wall-clock of the one-off layout stages on stderr
-struct StageTimer {
-	const char* what;
-	bool on;
-	std::chrono::steady_clock::time_point t0;
-	explicit StageTimer(const char* w) : what(w), on(getenv("LPP_VERBOSE") != nullptr), t0(std::chrono::steady_clock::now()) { }
-	~StageTimer()
-	{
-		if (on) fprintf(stderr, "lpp: %-28s %8.1f ms\n", what, 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
-	}
-};
-
-// in-place exclusive scan of arr[0..n) (arr[n-1] must be 0 on entry and receives the total, also returned)
-static lpp_status scan_exclusive(lpp_engine* e, int64_t* arr, int64_t n, int64_t* total_out)
-{
-	const int64_t nblk = (n + kScanChunk - 1) / kScanChunk;
-	int64_t *sums = nullptr, *total = nullptr;
-	HIP_TRY_MEM(hipMalloc(&sums, sizeof(int64_t) * (size_t)nblk));
-	if (hipMalloc(&total, sizeof(int64_t)) != hipSuccess) {
-		(void)hipFree(sums);
-		return fail(LPP_ERR_NOMEM, "scan scratch allocation failed");
-	}
-	k_scan_block_sums<<<(int)nblk, kBlock, 0, e->stream>>>(arr, n, sums);
-	k_scan_sums<<<1, kBlock, 0, e->stream>>>(sums, nblk, total);
-	k_scan_apply<<<(int)nblk, kBlock, 0, e->stream>>>(arr, n, sums, arr);
-	hipError_t e1 = hipMemcpyAsync(total_out, total, sizeof(int64_t), hipMemcpyDeviceToHost, e->stream);
-	hipError_t e2 = hipStreamSynchronize(e->stream);
-	(void)hipFree(sums);
-	(void)hipFree(total);
-	if (e1 != hipSuccess || e2 != hipSuccess) return fail(LPP_ERR_HIP, "device scan failed");
-	return LPP_OK;
-}
-
-static void drop_dia(DevCsr& A)
-{
-	for (void* p : { (void*)A.rrowptr, (void*)A.dia_off, A.dia_val, (void*)A.dcode })
-		if (p) (void)hipFree(p);
-	A.rrowptr = nullptr;
-	A.dcode = nullptr;
-	A.dia_off = nullptr;
-	A.dia_val = nullptr;
-	A.rnnz = A.ndia = 0;
-	A.dia_stride = 0;
-}
-
-// Split the shared-offset entries off the plain CSR of A (see k_dia_split).  On success with A.rrowptr != nullptr the
-// rest CSR is (A.rrowptr, *rcol, *rval) -- the caller frees rcol / rval -- and A.dia_* hold the shared lists.
-// Leaves A untouched (rrowptr == nullptr) when rows are unsorted or fewer than 10 % of the entries are shared.
-// xdiag: also split the diagonal off (needs the value dictionary: its codes go to A.dcode, one per real component and row)
-template <typename T> static lpp_status split_dia_t(lpp_engine* e, DevCsr& A, const SliceGeom& g, bool for_window, bool xdiag, int32_t** rcol, T** rval)
-{
-	*rcol = nullptr;
-	*rval = nullptr;
-	unsigned long long* flags = nullptr; // [0] unsorted, [1] max shared per slice, [2] total shared, [3] rows without a diagonal
-	HIP_TRY_MEM(hipMalloc(&flags, sizeof(unsigned long long) * 4));
-	struct Free {
-		void* p;
-		~Free() { (void)hipFree(p); }
-	} free_flags { flags };
-	HIP_TRY(hipMemsetAsync(flags, 0, sizeof(unsigned long long) * 4, e->stream));
-	unsigned long long h[4] = { 0, 0, 0, 0 };
-	if (!A.known_sorted) {
-		k_rows_sorted<<<(int)((A.nrows + 255) / 256), 256, 0, e->stream>>>(A.nrows, A.rowptr, A.col, (int*)flags);
-		HIP_TRY(hipMemcpyAsync(h, flags, sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
-		HIP_TRY(hipStreamSynchronize(e->stream));
-		if (h[0] != 0) return LPP_OK;
-	}
-	HIP_TRY_MEM(hipMalloc(&A.rrowptr, sizeof(int64_t) * (size_t)(A.nrows + 1)));
-	HIP_TRY(hipMemsetAsync(A.rrowptr, 0, sizeof(int64_t) * (size_t)(A.nrows + 1), e->stream));
-	const int nbw = (int)std::max<int64_t>(1, std::min<int64_t>((g.nslices + 3) / 4, 16384));
-	const int win = for_window ? 1 : 0;
-	int xd = xdiag ? 1 : 0;
-	StageTimer* t_count = new StageTimer("  split: count pass");
-	for (;;) {
-		k_dia_split<T, false><<<nbw, kBlock, 0, e->stream>>>(g, A.rowptr, A.col, (const T*)A.val, win, 0, A.rrowptr, flags + 1, nullptr, nullptr,
-		                                                    nullptr, nullptr, nullptr, xd, nullptr, 0, nullptr);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpyAsync(h, flags, sizeof(unsigned long long) * 4, hipMemcpyDeviceToHost, e->stream));
-		HIP_TRY(hipStreamSynchronize(e->stream));
-		if (!xd || h[3] == 0) break;
-		// some row has no diagonal entry: count again with the diagonal left where it is
-		xd = 0;
-		HIP_TRY(hipMemsetAsync(A.rrowptr, 0, sizeof(int64_t) * (size_t)(A.nrows + 1), e->stream));
-		HIP_TRY(hipMemsetAsync(flags + 1, 0, sizeof(unsigned long long) * 3, e->stream));
-	}
-	delete t_count;
-	lpp_status st = scan_exclusive(e, A.rrowptr, A.nrows + 1, &A.rnnz);
-	if (st != LPP_OK) return st;
-	A.ndia = (int64_t)h[2];
-	A.dia_stride = (int)((h[1] + 3) & ~3ull);
-	if (getenv("LPP_VERBOSE"))
-		fprintf(stderr, "lpp: shared-offset split: nnz %lld -> per-row %lld + %lld per-slice entries (%lld slices, <= %d per slice)%s\n",
-		        (long long)A.nnz, (long long)A.rnnz, (long long)A.ndia, (long long)g.nslices, (int)h[1], xd ? " + diagonal codes" : "");
-	if ((double)(A.nnz - A.rnnz) < 0.10 * (double)A.nnz || (A.dia_stride == 0 && !xd)) {
-		drop_dia(A);
-		return LPP_OK;
-	}
-	if (xd) {
-		HIP_TRY_MEM(hipMalloc(&A.dcode, (size_t)A.nrows * (sizeof(T) / sizeof(double))));
-		HIP_TRY(hipMemsetAsync(A.dcode, 0, (size_t)A.nrows * (sizeof(T) / sizeof(double)), e->stream));
-	}
-	StageTimer* t_alloc = new StageTimer("  split: allocations");
-	const size_t places = std::max<size_t>((size_t)g.nslices * (size_t)A.dia_stride, 1);
-	HIP_TRY_MEM(hipMalloc(rcol, sizeof(int32_t) * (size_t)std::max<int64_t>(A.rnnz, 1)));
-	HIP_TRY_MEM(hipMalloc(rval, sizeof(T) * (size_t)std::max<int64_t>(A.rnnz, 1)));
-	HIP_TRY_MEM(hipMalloc(&A.dia_off, sizeof(int32_t) * places));
-	HIP_TRY_MEM(hipMalloc(&A.dia_val, sizeof(T) * places));
-	HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)A.dia_off, (int)kDiaNone, places, e->stream));
-	HIP_TRY(hipMemsetAsync(A.dia_val, 0, sizeof(T) * places, e->stream));
-	HIP_TRY(hipStreamSynchronize(e->stream));
-	delete t_alloc;
-	StageTimer t_fill("  split: fill pass");
-	k_dia_split<T, true><<<nbw, kBlock, 0, e->stream>>>(g, A.rowptr, A.col, (const T*)A.val, win, A.dia_stride, nullptr, nullptr, A.rrowptr,
-	                                                   *rcol, *rval, A.dia_off, (T*)A.dia_val, xd, A.dict, A.ndict, A.dcode);
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipStreamSynchronize(e->stream));
-	return LPP_OK;
-}
-
-// build the sliced layout of A on the device for row blocks of B rows
-template <typename T> static lpp_status build_sliced_t(lpp_engine* e, DevCsr& A, int64_t B, bool for_window)
-{
-	SliceGeom g;
-	g.nrows = A.nrows;
-	g.B = std::max<int64_t>(1, std::min<int64_t>(B, std::max<int64_t>(A.nrows, 1)));
-	g.spb = (int32_t)((g.B + 63) / 64);
-	g.nblocks = (A.nrows + g.B - 1) / g.B;
-	g.nslices = g.nblocks * g.spb;
-	A.geom = g;
-	// entries shared by all rows of a slice are split off first; the sliced arrays then hold the rest
-	const int64_t* rp = A.rowptr;
-	const int32_t* cc = A.col;
-	const T* vv = (const T*)A.val;
-	int64_t nz = A.nnz;
-	int32_t* rcol = nullptr;
-	T* rval = nullptr;
-	struct Scratch {
-		int32_t*& c;
-		T*& v;
-		~Scratch()
-		{
-			if (c) (void)hipFree(c);
-			if (v) (void)hipFree(v);
-		}
-	} scratch { rcol, rval };
-	// the value dictionary is built from the whole matrix first: the diagonal codes below need it
-	int want = e->cfg.compress_values;
-	if (const char* s = getenv("LPP_COMPRESS_VALUES")) want = atoi(s);
-	bool coded = false;
-	if (want != 0) {
-		StageTimer tm("value dictionary");
-		lpp_status st = try_build_dict<T>(e, A, vv, nz, &coded);
-		if (st != LPP_OK) return st;
-	}
-	int want_dia = A.no_dia ? 0 : 1;
-	if (const char* s = getenv("LPP_SHARED_OFFSETS")) want_dia = A.no_dia ? 0 : atoi(s);
-	const bool xdiag = for_window && coded && !(getenv("LPP_DIAG_CODES") && atoi(getenv("LPP_DIAG_CODES")) == 0);
-	if (want_dia && A.nnz > 0) {
-		StageTimer tm("shared-offset split");
-		lpp_status st = split_dia_t<T>(e, A, g, for_window, xdiag, &rcol, &rval);
-		if (st != LPP_OK) return st;
-		if (A.rrowptr) {
-			rp = A.rrowptr;
-			cc = rcol;
-			vv = rval;
-			nz = A.rnnz;
-		}
-	}
-	// window kernel: 16-bit window-local columns when every per-row entry stays inside its row block
-	bool l16 = false;
-	if (for_window && g.B <= 65536 && nz > 0 && !(getenv("LPP_LOCAL16") && atoi(getenv("LPP_LOCAL16")) == 0)) {
-		int* outside = nullptr;
-		HIP_TRY_MEM(hipMalloc(&outside, sizeof(int)));
-		(void)hipMemsetAsync(outside, 0, sizeof(int), e->stream);
-		k_cols_local<<<(int)((A.nrows + 255) / 256), 256, 0, e->stream>>>(g, rp, cc, outside);
-		int bad = 0;
-		hipError_t e1 = hipMemcpyAsync(&bad, outside, sizeof(int), hipMemcpyDeviceToHost, e->stream);
-		hipError_t e2 = hipStreamSynchronize(e->stream);
-		(void)hipFree(outside);
-		if (e1 != hipSuccess || e2 != hipSuccess) return fail(LPP_ERR_HIP, "column locality check failed");
-		l16 = !bad;
-	}
-	A.local16 = l16;
-	// +64 entries of slack: the pipelined kernel reads (and discards) the entry after a slice's last one
-	HIP_TRY_MEM(hipMalloc(&A.slice_ptr, sizeof(int64_t) * (size_t)(g.nslices + 1)));
-	HIP_TRY_MEM(hipMalloc(&A.row_len, sizeof(int32_t) * (size_t)std::max<int64_t>(A.nrows, 1)));
-	const size_t colsz = l16 ? sizeof(uint16_t) : sizeof(int32_t);
-	HIP_TRY_MEM(hipMalloc(&A.scol, colsz * (size_t)(nz + 64)));
-	HIP_TRY(hipMemsetAsync((char*)A.scol + colsz * (size_t)nz, 0, colsz * 64, e->stream));
-	if (coded) HIP_TRY_MEM(hipMalloc(&A.code_ptr, sizeof(int64_t) * (size_t)(g.nslices + 1)));
-	const int64_t nthreads = std::max<int64_t>(A.nrows, g.nslices + 1);
-	const int nb = (int)((nthreads + 255) / 256);
-	k_slice_meta<<<nb, 256, 0, e->stream>>>(g, rp, A.slice_ptr, A.row_len, A.code_ptr, CodeTraits<T>::kSlotsPerWord);
-	const int64_t need = (g.nslices + 3) / 4;
-	const int nb2 = (int)std::max<int64_t>(1, std::min<int64_t>(need, 8192));
-	if (coded) {
-		// exclusive scan of the per-slice word counts -> code_ptr; the grand total sizes the code array
-		int64_t nwords = 0;
-		lpp_status st = scan_exclusive(e, A.code_ptr, g.nslices + 1, &nwords);
-		if (st != LPP_OK) return st;
-		A.code_words = nwords;
-		HIP_TRY_MEM(hipMalloc(&A.codes, sizeof(uint32_t) * (size_t)(nwords + 64 * 16)));
-		HIP_TRY(hipMemsetAsync(A.codes + nwords, 0, sizeof(uint32_t) * 64 * 16, e->stream));
-		if (l16)
-			k_slice_fill<T, false, true><<<nb2, kBlock, 0, e->stream>>>(g, rp, cc, (const T*)nullptr, A.scol, (T*)nullptr);
-		else
-			k_slice_fill<T, false><<<nb2, kBlock, 0, e->stream>>>(g, rp, cc, (const T*)nullptr, A.scol, (T*)nullptr);
-		k_slice_codes<T><<<nb2, kBlock, 0, e->stream>>>(g, rp, vv, A.code_ptr, A.dict, A.ndict, A.codes);
-		A.coded = true;
-	} else {
-		HIP_TRY_MEM(hipMalloc(&A.sval, sizeof(T) * (size_t)(nz + 64)));
-		HIP_TRY(hipMemsetAsync((T*)A.sval + nz, 0, sizeof(T) * 64, e->stream));
-		// plain values, window kernel, no shared-offset split: the entries that leave a row's block go into the row's first slots, so that
-		// every 512-byte run of the source vector is gathered by one load (k_slice_fill); needs rows sorted by column
-		bool outs = for_window && !l16 && rp == A.rowptr && g.nblocks >= 2 && nz > 0 && !(getenv("LPP_OUTS_FIRST") && atoi(getenv("LPP_OUTS_FIRST")) == 0);
-		if (outs && !A.known_sorted) {
-			int* unsorted = nullptr;
-			HIP_TRY_MEM(hipMalloc(&unsorted, sizeof(int)));
-			(void)hipMemsetAsync(unsorted, 0, sizeof(int), e->stream);
-			k_rows_sorted<<<(int)((A.nrows + 255) / 256), 256, 0, e->stream>>>(A.nrows, A.rowptr, A.col, unsorted);
-			int bad = 1;
-			hipError_t e1 = hipMemcpyAsync(&bad, unsorted, sizeof(int), hipMemcpyDeviceToHost, e->stream);
-			hipError_t e2 = hipStreamSynchronize(e->stream);
-			(void)hipFree(unsorted);
-			if (e1 != hipSuccess || e2 != hipSuccess) return fail(LPP_ERR_HIP, "row order check failed");
-			outs = bad == 0;
-		}
-		A.outs_first = outs;
-		// ... and the vectors pitched to 128-byte lines per row block (whole matrix on one GPU, real, blocks not line-aligned by themselves, from
-		// 256 MB per vector on): the runs gathered from other blocks then start on a line -- 4 lines per run instead of 4.9 at config 2
-		// (N_up = 12870 = 6 mod 16).  LPP_PITCH_ROWS=0/1: never / wherever it applies.
-		int pad = 0;
-		{
-			const int64_t line = 128 / (int64_t)sizeof(T);
-			bool want = (size_t)A.nrows * sizeof(T) >= ((size_t)256 << 20);
-			if (const char* sp = getenv("LPP_PITCH_ROWS")) want = atoi(sp) != 0;
-			const int64_t pitched = (g.B + line - 1) / line * line;
-			if (outs && want && &A == &e->A_loc && !A.out_part && !e->has_comm && !e->is_complex && A.src_elems == 0 && g.nrows == g.nblocks * g.B && g.B % line != 0
-			    && pitched * g.nblocks < ((int64_t)1 << 31) && (size_t)(pitched * g.nblocks) * sizeof(T) < ((size_t)1 << 32))
-				pad = (int)(pitched - g.B);
-		}
-		A.pad = pad;
-		if (pad) {
-			e->pitch = g.B + pad;
-			e->pitch_rows = g.B;
-			e->pitch_blocks = g.nblocks;
-		}
-		if (l16)
-			k_slice_fill<T, false, true><<<nb2, kBlock, 0, e->stream>>>(g, rp, cc, vv, A.scol, (T*)A.sval);
-		else
-			k_slice_fill<T, false><<<nb2, kBlock, 0, e->stream>>>(g, rp, cc, vv, A.scol, (T*)A.sval, 0, outs ? 1 : 0, pad);
-	}
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipStreamSynchronize(e->stream));
-	A.sliced = true;
-	// Block-periodic structure: when every row block repeats block 0's row lengths and local columns (the in-block
-	// part of a product basis is the same one-species matrix in every block) only block 0's copy is kept; it stays
-	// in L2 instead of streaming 2 bytes per entry + 4 per row from HBM.  Values (codes) remain per block.
-	if (l16 && coded && g.nblocks >= 2 && g.nrows == g.nblocks * g.B && !(getenv("LPP_BLOCK_TEMPLATE") && atoi(getenv("LPP_BLOCK_TEMPLATE")) == 0)) {
-		int* differs = nullptr;
-		HIP_TRY_MEM(hipMalloc(&differs, sizeof(int) * 2));
-		(void)hipMemsetAsync(differs, 0, sizeof(int) * 2, e->stream);
-		k_tmpl_check<<<nb2, kBlock, 0, e->stream>>>(g, A.slice_ptr, A.row_len, (const uint16_t*)A.scol, A.code_ptr, A.codes, differs);
-		int hd[2] = { 1, 1 };
-		hipError_t e1 = hipMemcpyAsync(hd, differs, sizeof(int) * 2, hipMemcpyDeviceToHost, e->stream);
-		hipError_t e2 = hipStreamSynchronize(e->stream);
-		(void)hipFree(differs);
-		if (e1 != hipSuccess || e2 != hipSuccess) return fail(LPP_ERR_HIP, "block-template check failed");
-		const int bad = hd[0];
-		if (!bad && !hd[1]) {
-			// the value codes repeat as well (the diagonal travels apart): keep block 0's code words only
-			int64_t w0 = 0;
-			HIP_TRY(hipMemcpy(&w0, A.code_ptr + g.spb, sizeof(int64_t), hipMemcpyDeviceToHost));
-			int64_t* cp = nullptr;
-			uint32_t* cw = nullptr;
-			HIP_TRY_MEM(hipMalloc(&cp, sizeof(int64_t) * (size_t)(g.spb + 1)));
-			HIP_TRY_MEM(hipMalloc(&cw, sizeof(uint32_t) * (size_t)(w0 + 64 * 16)));
-			HIP_TRY(hipMemcpyAsync(cp, A.code_ptr, sizeof(int64_t) * (size_t)(g.spb + 1), hipMemcpyDeviceToDevice, e->stream));
-			HIP_TRY(hipMemcpyAsync(cw, A.codes, sizeof(uint32_t) * (size_t)w0, hipMemcpyDeviceToDevice, e->stream));
-			HIP_TRY(hipMemsetAsync(cw + w0, 0, sizeof(uint32_t) * 64 * 16, e->stream));
-			HIP_TRY(hipStreamSynchronize(e->stream));
-			(void)hipFree(A.code_ptr);
-			(void)hipFree(A.codes);
-			A.code_ptr = cp;
-			A.codes = cw;
-			A.code_words = w0;
-		}
-		if (!bad) {
-			int64_t n0 = 0; // entries of block 0
-			HIP_TRY(hipMemcpy(&n0, A.slice_ptr + g.spb, sizeof(int64_t), hipMemcpyDeviceToHost));
-			int64_t* sp = nullptr;
-			int32_t* rl = nullptr;
-			int32_t* sc = nullptr;
-			HIP_TRY_MEM(hipMalloc(&sp, sizeof(int64_t) * (size_t)(g.spb + 1)));
-			HIP_TRY_MEM(hipMalloc(&rl, sizeof(int32_t) * (size_t)g.B));
-			HIP_TRY_MEM(hipMalloc(&sc, sizeof(uint16_t) * (size_t)(n0 + 64)));
-			HIP_TRY(hipMemcpyAsync(sp, A.slice_ptr, sizeof(int64_t) * (size_t)(g.spb + 1), hipMemcpyDeviceToDevice, e->stream));
-			HIP_TRY(hipMemcpyAsync(rl, A.row_len, sizeof(int32_t) * (size_t)g.B, hipMemcpyDeviceToDevice, e->stream));
-			HIP_TRY(hipMemcpyAsync(sc, A.scol, sizeof(uint16_t) * (size_t)n0, hipMemcpyDeviceToDevice, e->stream));
-			HIP_TRY(hipMemsetAsync((char*)sc + sizeof(uint16_t) * (size_t)n0, 0, sizeof(uint16_t) * 64, e->stream));
-			HIP_TRY(hipStreamSynchronize(e->stream));
-			(void)hipFree(A.slice_ptr);
-			(void)hipFree(A.row_len);
-			(void)hipFree(A.scol);
-			A.slice_ptr = sp;
-			A.row_len = rl;
-			A.scol = sc;
-			A.tmpl = hd[1] ? 1 : 2;
-			if (A.tmpl == 2 && !(getenv("LPP_TEMPLATE_PACK") && atoi(getenv("LPP_TEMPLATE_PACK")) == 0)) {
-				// packed padded copy of the template for the inner loop (the compact copy stays for get_csr)
-				HIP_TRY_MEM(hipMalloc(&A.tw_len, sizeof(int32_t) * (size_t)g.spb));
-				HIP_TRY_MEM(hipMalloc(&A.tw_off, sizeof(int32_t) * (size_t)g.spb));
-				const int nbp = (int)std::max<int64_t>(1, (g.spb + 3) / 4);
-				k_tmpl_pack<T, 0><<<nbp, kBlock, 0, e->stream>>>(g, A.slice_ptr, A.row_len, (const uint16_t*)A.scol, A.code_ptr, A.codes, A.tw_len,
-				                                                 nullptr, nullptr);
-				std::vector<int32_t> hl((size_t)g.spb), ho((size_t)g.spb);
-				HIP_TRY(hipMemcpyAsync(hl.data(), A.tw_len, sizeof(int32_t) * (size_t)g.spb, hipMemcpyDeviceToHost, e->stream));
-				HIP_TRY(hipStreamSynchronize(e->stream));
-				int64_t tot = 0;
-				for (int32_t j2 = 0; j2 < g.spb; j2++) {
-					ho[(size_t)j2] = (int32_t)tot;
-					tot += (int64_t)hl[(size_t)j2] * 64;
-				}
-				if (tot < ((int64_t)1 << 30)) {
-					HIP_TRY_MEM(hipMalloc(&A.tw, sizeof(uint32_t) * (size_t)std::max<int64_t>(tot, 1)));
-					HIP_TRY(hipMemcpyAsync(A.tw_off, ho.data(), sizeof(int32_t) * (size_t)g.spb, hipMemcpyHostToDevice, e->stream));
-					k_tmpl_pack<T, 1><<<nbp, kBlock, 0, e->stream>>>(g, A.slice_ptr, A.row_len, (const uint16_t*)A.scol, A.code_ptr, A.codes, A.tw_len,
-					                                                 A.tw_off, A.tw);
-					HIP_TRY(hipGetLastError());
-					HIP_TRY(hipStreamSynchronize(e->stream));
-				}
-			}
-		}
-	}
-	return LPP_OK;
-}
-
-// Basis block of an uploaded matrix nobody described (lpp_engine_set_row_block not called): product bases show up as
-// couplings at offsets k*B that are identical for 64 consecutive rows.  A sample of 64-row slices is copied to the
-// host; per slice the largest offset shared by all its rows (same value in every row) is a block shift, B = the gcd of
-// those over the sample.  Accepted only when every sampled entry is then either inside its row's block or a whole
-// number of blocks away, and B fits the LDS window.  Returns 0 when no such structure is found.
-template <typename T> static int64_t detect_row_block_t(lpp_engine* e, const DevCsr& A, int64_t lds_cap_elems)
-{
-	const int64_t nsl = A.nrows / 64;
-	if (nsl < 64 || !A.col || !A.val || A.nnz == 0) return 0;
-	const int samples = 48;
-	std::vector<int64_t> rp(65);
-	std::vector<int32_t> ci;
-	std::vector<T> va;
-	struct Slice {
-		int64_t row0;
-		std::vector<int64_t> rp;
-		std::vector<int32_t> ci;
-	};
-	std::vector<Slice> kept;
-	int64_t G = 0;
-	for (int sidx = 0; sidx < samples; sidx++) {
-		const int64_t row0 = ((nsl * (2 * sidx + 1)) / (2 * samples)) * 64;
-		if (hipMemcpy(rp.data(), A.rowptr + row0, sizeof(int64_t) * 65, hipMemcpyDeviceToHost) != hipSuccess) return 0;
-		const int64_t p0 = rp[0], n = rp[64] - rp[0];
-		if (n <= 0 || n > (int64_t)1 << 20) continue;
-		ci.resize((size_t)n);
-		va.resize((size_t)n);
-		if (hipMemcpy(ci.data(), A.col + p0, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) return 0;
-		if (hipMemcpy(va.data(), (const T*)A.val + p0, sizeof(T) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) return 0;
-		int64_t best = 0; // largest |offset| shared by all 64 rows with the same value
-		for (int64_t q = rp[0]; q < rp[1]; q++) {
-			const int64_t off = (int64_t)ci[(size_t)(q - p0)] - row0;
-			if (std::llabs(off) < 64 || std::llabs(off) <= best) continue;
-			bool all = true;
-			for (int r = 1; r < 64 && all; r++) {
-				bool found = false;
-				for (int64_t t = rp[r]; t < rp[r + 1]; t++)
-					if ((int64_t)ci[(size_t)(t - p0)] - (row0 + r) == off) {
-						found = std::memcmp(&va[(size_t)(t - p0)], &va[(size_t)(q - p0)], sizeof(T)) == 0;
-						break;
-					}
-				all = found;
-			}
-			if (all) best = std::llabs(off);
-		}
-		if (best > 0) G = G == 0 ? best : std::gcd(G, best);
-		Slice sl;
-		sl.row0 = row0;
-		sl.rp.assign(rp.begin(), rp.end());
-		sl.ci = ci;
-		kept.push_back(std::move(sl));
-	}
-	if (G < 64 || G > lds_cap_elems || kept.empty()) return 0;
-	for (const Slice& sl : kept) {
-		const int64_t p0 = sl.rp[0];
-		for (int r = 0; r < 64; r++) {
-			const int64_t row = sl.row0 + r, b0 = (row / G) * G;
-			for (int64_t t = sl.rp[r]; t < sl.rp[r + 1]; t++) {
-				const int64_t c = sl.ci[(size_t)(t - p0)];
-				if (!((c >= b0 && c < b0 + G) || (c - row) % G == 0)) return 0;
-			}
-		}
-	}
-	return G;
-}
-
-// Split-panel layout (k_split_count): A keeps the entries inside its row blocks, *A.out_part takes the others in panel-major row
-// order.  Only for plain-format matrices (shared offsets off: they take the leaving entries out of the rows in their own way),
-// rows sorted by column, whole blocks, and a leaving part worth a second launch (>= 20 % of the entries).
-template <typename T> static lpp_status split_panel_t(lpp_engine* e, DevCsr& A, int64_t B, bool* did)
-{
-	*did = false;
-	const int64_t nb = A.nrows / B;
-	if (nb < 64 || nb * B != A.nrows || !A.col || !A.val || A.nnz == 0) return LPP_OK;
-	hipStream_t st = e->stream;
-	if (!A.known_sorted) {
-		int* flag = nullptr;
-		HIP_TRY_MEM(hipMalloc(&flag, sizeof(int)));
-		(void)hipMemsetAsync(flag, 0, sizeof(int), st);
-		k_rows_sorted<<<(int)((A.nrows + 255) / 256), 256, 0, st>>>(A.nrows, A.rowptr, A.col, flag);
-		int h = 1;
-		hipError_t e1 = hipMemcpyAsync(&h, flag, sizeof(int), hipMemcpyDeviceToHost, st);
-		hipError_t e2 = hipStreamSynchronize(st);
-		(void)hipFree(flag);
-		if (e1 != hipSuccess || e2 != hipSuccess) return fail(LPP_ERR_HIP, "split-panel layout: sortedness check failed");
-		if (h) return LPP_OK;
-	}
-	StageTimer tm("split-panel layout");
-	// parts by source block range: what one part gathers from while a panel is walked -- two 128-byte lines per source block
-	// when the rows are not line-aligned (B not a multiple of 16), one when they are -- is kept near 1.7 MB
-	SplitParams P;
-	P.nrows = A.nrows;
-	P.B = B;
-	P.nb = nb;
-	const size_t foot = (size_t)nb * ((B & 15) ? 256 : 128);
-	P.nparts = (int)std::max<size_t>(1, std::min<size_t>(kSplitMaxParts, (foot + ((size_t)1700 << 10) - 1) / ((size_t)1700 << 10)));
-	P.nparts = 1; // measured: parts do not raise the L2 hit rate here (2 parts: 6.0 + 6.2 ms and 32 + 34 GB against 9.9 ms and 61 GB in one)
-	(void)foot;
-	if (const char* s2 = getenv("LPP_SPLIT_PARTS")) P.nparts = std::max(1, std::min(atoi(s2), kSplitMaxParts));
-	P.pblk = (nb + P.nparts - 1) / P.nparts;
-	const int nbk = (int)((A.nrows + 255) / 256);
-	DevCsr* O = new DevCsr[P.nparts];
-	struct Guard {
-		DevCsr*& o;
-		int n;
-		int64_t* rpi = nullptr;
-		int32_t* ci = nullptr;
-		void* vi = nullptr;
-		int32_t* map = nullptr;
-		void* ptrs = nullptr;
-		~Guard()
-		{
-			if (o) {
-				for (int q = 0; q < n; q++) free_csr(o[q]);
-				delete[] o;
-			}
-			for (void* p : { (void*)rpi, (void*)ci, vi, (void*)map, ptrs })
-				if (p) (void)hipFree(p);
-		}
-	} g { O, P.nparts };
-	HIP_TRY_MEM(hipMalloc(&g.rpi, sizeof(int64_t) * (size_t)(A.nrows + 1)));
-	HIP_TRY_MEM(hipMalloc(&g.map, sizeof(int32_t) * (size_t)A.nrows));
-	HIP_TRY(hipMemsetAsync(g.rpi, 0, sizeof(int64_t) * (size_t)(A.nrows + 1), st));
-	int64_t* lens[kSplitMaxParts] = { nullptr, nullptr, nullptr, nullptr };
-	for (int q = 0; q < P.nparts; q++) {
-		O[q].nrows = A.nrows;
-		O[q].owned = true;
-		O[q].known_sorted = true;
-		O[q].no_dia = true;
-		HIP_TRY_MEM(hipMalloc(&O[q].rowptr, sizeof(int64_t) * (size_t)(A.nrows + 1)));
-		HIP_TRY(hipMemsetAsync(O[q].rowptr, 0, sizeof(int64_t) * (size_t)(A.nrows + 1), st));
-		lens[q] = O[q].rowptr;
-	}
-	HIP_TRY_MEM(hipMalloc(&g.ptrs, sizeof(lens)));
-	HIP_TRY(hipMemcpyAsync(g.ptrs, lens, sizeof(lens), hipMemcpyHostToDevice, st));
-	k_split_count<<<nbk, 256, 0, st>>>(P, A.rowptr, A.col, g.rpi, (int64_t* const*)g.ptrs, g.map);
-	int64_t nin = 0, nout = 0;
-	lpp_status rc = scan_exclusive(e, g.rpi, A.nrows + 1, &nin);
-	if (rc != LPP_OK) return rc;
-	for (int q = 0; q < P.nparts; q++) {
-		int64_t n = 0;
-		rc = scan_exclusive(e, O[q].rowptr, A.nrows + 1, &n);
-		if (rc != LPP_OK) return rc;
-		O[q].nnz = n;
-		nout += n;
-	}
-	if (nin + nout != A.nnz) return fail(LPP_ERR_HIP, "split-panel layout: entry count mismatch");
-	if ((double)nout < 0.20 * (double)A.nnz) return LPP_OK; // not worth the extra launches
-	HIP_TRY_MEM(hipMalloc(&g.ci, sizeof(int32_t) * (size_t)std::max<int64_t>(nin, 1)));
-	HIP_TRY_MEM(hipMalloc(&g.vi, sizeof(T) * (size_t)std::max<int64_t>(nin, 1)));
-	SplitOut SO {};
-	for (int q = 0; q < P.nparts; q++) {
-		HIP_TRY_MEM(hipMalloc(&O[q].col, sizeof(int32_t) * (size_t)std::max<int64_t>(O[q].nnz, 1)));
-		HIP_TRY_MEM(hipMalloc(&O[q].val, sizeof(T) * (size_t)std::max<int64_t>(O[q].nnz, 1)));
-		SO.rp[q] = O[q].rowptr;
-		SO.col[q] = O[q].col;
-		SO.val[q] = O[q].val;
-	}
-	k_split_fill<T><<<nbk, 256, 0, st>>>(P, A.rowptr, A.col, (const T*)A.val, g.rpi, g.ci, (T*)g.vi, SO);
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipStreamSynchronize(st));
-	// the in-block part replaces the matrix in A
-	(void)hipFree(A.rowptr);
-	(void)hipFree(A.col);
-	(void)hipFree(A.val);
-	A.rowptr = g.rpi;
-	A.col = g.ci;
-	A.val = g.vi;
-	g.rpi = nullptr;
-	g.ci = nullptr;
-	g.vi = nullptr;
-	A.nnz = nin;
-	A.known_sorted = true;
-	// the leaving parts: sliced layout over ALL rows in panel-major order (one "block" = the whole matrix)
-	for (int q = 0; q < P.nparts; q++) {
-		rc = finalize_csr(e, O[q], true, LPP_SPMV_SLICED, 0);
-		if (rc != LPP_OK) return rc;
-	}
-	A.out_part = O;
-	A.split_parts = P.nparts;
-	g.o = nullptr;
-	O = nullptr;
-	A.out_rowmap = g.map;
-	g.map = nullptr;
-	A.split_B = B;
-	A.split_nb = nb;
-	A.split_pblk = P.pblk;
-	*did = true;
-	return LPP_OK;
-}
-
-// Choose the SpMV kernel and build its layout.  hint_block (rows) is the basis' natural block
-// (N_up for the Hubbard product basis): when a whole number of such blocks fits the LDS window,
-// the window kernel serves every in-block gather (diagonal + up-hops) from LDS.
-lpp_status finalize_csr(lpp_engine* e, DevCsr& A, bool allow_drop_plain, int force_mode, int64_t force_block)
-{
-	A.G = pick_group(A.nrows, A.nnz);
-	int mode = e->cfg.spmv_kernel;
-	if (const char* s = getenv("LPP_SPMV_KERNEL")) mode = atoi(s);
-	if (force_mode) mode = force_mode;
-	// the sliced kernels address the source vector with 32-bit byte offsets
-	const size_t src_elems = (size_t)std::max<int64_t>(A.src_elems, A.nrows);
-	const bool fits32 = src_elems * e->esz < ((size_t)1 << 32);
-	const int64_t lds_cap_elems = (int64_t)((156 * 1024) / e->esz);
-	int64_t win_rows = 0;
-	if (A.hint_block == 0 && mode == LPP_SPMV_AUTO && !e->is_complex && fits32 && A.src_elems == 0
-	    && !(getenv("LPP_DETECT_BLOCK") && atoi(getenv("LPP_DETECT_BLOCK")) == 0)) {
-		StageTimer tm("basis block detection");
-		A.hint_block = detect_row_block_t<double>(e, A, lds_cap_elems);
-		if (A.hint_block && getenv("LPP_VERBOSE")) fprintf(stderr, "lpp: detected a basis block of %lld rows\n", (long long)A.hint_block);
-	}
-	if (A.hint_block > 0 && A.hint_block <= lds_cap_elems) {
-		// one basis block per window whenever it gives the 16 waves of a workgroup something to do: only then do all
-		// row blocks repeat the same in-block structure (block template); tiny basis blocks are grouped
-		const int64_t k = A.hint_block >= 512 ? 1 : std::max<int64_t>(1, std::min<int64_t>(lds_cap_elems / A.hint_block, (1024 + A.hint_block - 1) / A.hint_block));
-		win_rows = A.hint_block * k;
-	}
-	if (mode == LPP_SPMV_AUTO) {
-		// the LDS window pays when in-block gathers dominate (Hubbard up-hops), the matrix is large enough to give every
-		// CU several blocks, and a window element is 8 bytes (measured: complex t-J windows lose).  With the block
-		// template and 16-bit local columns it also wins when the whole vector fits the Infinity Cache
-		// (Hubbard chains L=12: 31.6 vs 33.1 us, L=14: 0.306 vs 0.372 ms).
-		bool window_ok = win_rows > 0 && !e->is_complex && (A.nrows + win_rows - 1) / win_rows >= 2 * (int64_t)e->num_cus;
-		if (!window_ok && win_rows == 0 && !e->is_complex && fits32 && A.col && A.nnz > 0) {
-			// no natural block: a plain diagonal window of 16384 rows pays when enough gathers land inside it (bases in
-			// ascending word order couple mostly nearby ranks: Heisenberg L=28 0.95 vs 1.22 ms); measured here
-			const int64_t gw = std::min<int64_t>(lds_cap_elems, 16384);
-			if ((A.nrows + gw - 1) / gw >= 2 * (int64_t)e->num_cus) {
-				unsigned long long* inside = nullptr;
-				HIP_TRY_MEM(hipMalloc(&inside, sizeof(unsigned long long)));
-				(void)hipMemsetAsync(inside, 0, sizeof(unsigned long long), e->stream);
-				k_count_local<<<(int)((A.nrows + 255) / 256), 256, 0, e->stream>>>(A.nrows, gw, A.rowptr, A.col, inside);
-				unsigned long long h = 0;
-				hipError_t e1 = hipMemcpyAsync(&h, inside, sizeof(h), hipMemcpyDeviceToHost, e->stream);
-				hipError_t e2 = hipStreamSynchronize(e->stream);
-				(void)hipFree(inside);
-				if (e1 != hipSuccess || e2 != hipSuccess) return fail(LPP_ERR_HIP, "window locality count failed");
-				if ((double)h >= 0.35 * (double)A.nnz) {
-					window_ok = true;
-					win_rows = gw;
-				}
-			}
-		}
-		mode = window_ok ? LPP_SPMV_WINDOW : LPP_SPMV_SLICED;
-	}
-	if (mode == LPP_SPMV_WINDOW && win_rows == 0) {
-		// no natural block: a generic diagonal window (captures near-diagonal columns)
-		win_rows = std::min<int64_t>(lds_cap_elems, 16384);
-	}
-	if (!force_mode)
-		if (const char* s = getenv("LPP_WINDOW_ROWS")) win_rows = std::max<int64_t>(64, std::min<int64_t>(atoll(s), lds_cap_elems));
-	if (!fits32 && (mode == LPP_SPMV_AUTO || mode == LPP_SPMV_SLICED || mode == LPP_SPMV_WINDOW)) mode = LPP_SPMV_ROWGROUP;
-	if ((mode == LPP_SPMV_SLICED || mode == LPP_SPMV_WINDOW) && A.nrows > 0) {
-		const int64_t B = force_block > 0 ? force_block : ((mode == LPP_SPMV_WINDOW) ? win_rows : A.nrows);
-		const bool win = (mode == LPP_SPMV_WINDOW);
-		// plain-format matrix with a basis block: the entries that leave the row blocks go panel-major (split_panel_t)
-		{
-			int want_dia = A.no_dia ? 0 : 1;
-			if (const char* s2 = getenv("LPP_SHARED_OFFSETS")) want_dia = A.no_dia ? 0 : atoi(s2);
-			// Taken by itself where a panel of 16 positions is ONE 128-byte line of every source block -- basis blocks of a multiple of 16
-			// rows (vectors are not pitched in the general layout) -- from 256 MB per vector on.  Measured on the 4x4 cluster with
-			// 7 + 7 electrons (N_up = 11440 = 16 x 715, 1.3e8 rows, 58.6 GB algorithmic): 6.2 + 7.0 = 13.2 ms and 72 GB of fabric reads in two
-			// launches against 13.9 ms / 85.6 GB in one kernel (4.45 against 4.2 TB/s algorithmic = 0.56 of 8 TB/s; both launches stream at
-			// 5.2-5.75 TB/s: the 12-byte format's ceiling on this matrix).  At BASELINE config 2 (N_up = 12870 = 6 mod 16: two lines per
-			// source block and panel, which no longer fit the L2 beside the entry streams) it loses, 8.1 + 9.9 ms against 18.3-18.7 ms in
-			// one kernel, and is not taken.  LPP_SPLIT_PANEL=0 / 1: never / wherever a basis block is known.
-			// (real matrices only: 16 complex positions are two lines, and no complex shape has been measured)
-			bool off = e->is_complex || (A.hint_block & 15) != 0 || (size_t)A.nrows * e->esz < ((size_t)256 << 20);
-			if (const char* sp = getenv("LPP_SPLIT_PANEL")) off = atoi(sp) == 0;
-			if (win && !force_mode && !want_dia && !off && A.hint_block > 0 && B == A.hint_block && !A.out_part && A.src_elems == 0) {
-				bool did = false;
-				lpp_status st2 = e->is_complex ? split_panel_t<cplx>(e, A, B, &did) : split_panel_t<double>(e, A, B, &did);
-				if (st2 != LPP_OK) return st2;
-			}
-		}
-		StageTimer tm("sliced layout (total)");
-		lpp_status st = e->is_complex ? build_sliced_t<cplx>(e, A, B, win) : build_sliced_t<double>(e, A, B, win);
-		if (st != LPP_OK) return st;
-		A.window = (mode == LPP_SPMV_WINDOW);
-		if (allow_drop_plain && getenv("LPP_KEEP_PLAIN_CSR") == nullptr && A.owned) {
-			StageTimer tm("release plain CSR");
-			// the sliced copy is the resident one; release the plain arrays (frees ~12 B/nnz)
-			(void)hipFree(A.col);
-			(void)hipFree(A.val);
-			A.col = nullptr;
-			A.val = nullptr;
-		}
-	}
-	return LPP_OK;
 }
 
 void set_spmv_bytes(lpp_engine* e)
@@ -970,39 +242,6 @@ lpp_status finish_setup(lpp_engine* e, int64_t n_local, int64_t n_global, int64_
 }
 
 } // namespace lpp
-
-// Plain CSR order (columns, values) of a matrix whose only resident form is the sliced layout: undo the slot-major
-// order (template-aware), decode the value codes, then merge the per-slice shared entries and the diagonal codes back.
-template <typename T> static lpp_status rebuild_csr_t(lpp_engine* e, const DevCsr& A, DevBuf& col_out, DevBuf& val_out)
-{
-	const int64_t* rp = A.rrowptr ? A.rrowptr : A.rowptr; // the sliced arrays hold the rest CSR when entries were split off
-	const int64_t nz = A.rrowptr ? A.rnnz : A.nnz;
-	DevBuf tcol, tval;
-	if (tcol.alloc(sizeof(int32_t) * (size_t)nz) != hipSuccess || tval.alloc(sizeof(T) * (size_t)nz) != hipSuccess)
-		return fail(LPP_ERR_NOMEM, "lpp_engine_get_csr: scratch allocation failed");
-	const int nb2 = (int)std::max<int64_t>(1, std::min<int64_t>((A.geom.nslices + 3) / 4, 8192));
-	T* plain_vals = A.coded ? nullptr : (T*)tval.p;
-	if (A.local16)
-		k_slice_fill<T, true, true><<<nb2, kBlock, 0, e->stream>>>(A.geom, rp, A.scol, (const T*)A.sval, (int32_t*)tcol.p, plain_vals, A.tmpl ? 1 : 0);
-	else
-		k_slice_fill<T, true><<<nb2, kBlock, 0, e->stream>>>(A.geom, rp, A.scol, (const T*)A.sval, (int32_t*)tcol.p, plain_vals, 0, A.outs_first ? 1 : 0, A.pad);
-	if (A.coded) k_slice_decode<T><<<nb2, kBlock, 0, e->stream>>>(A.geom, rp, A.codes, A.code_ptr, A.dict, (T*)tval.p, A.tmpl == 2 ? 1 : 0);
-	if (A.rrowptr) {
-		DevBuf fcol, fval;
-		if (fcol.alloc(sizeof(int32_t) * (size_t)A.nnz) != hipSuccess || fval.alloc(sizeof(T) * (size_t)A.nnz) != hipSuccess)
-			return fail(LPP_ERR_NOMEM, "lpp_engine_get_csr: scratch allocation failed");
-		k_dia_merge<T><<<(int)((A.nrows + 255) / 256), 256, 0, e->stream>>>(A.geom, A.rowptr, rp, (const int32_t*)tcol.p, (const T*)tval.p, A.dia_stride,
-		                                                                   A.dia_off, (const T*)A.dia_val, (int32_t*)fcol.p, (T*)fval.p, A.dcode, A.dict);
-		HIP_TRY(hipStreamSynchronize(e->stream)); // the merge reads tcol / tval, which are released next
-		tcol.take(fcol);
-		tval.take(fval);
-	}
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipStreamSynchronize(e->stream));
-	col_out.take(tcol);
-	val_out.take(tval);
-	return LPP_OK;
-}
 
 // ---------------------------------------------------------------------------------------------
 // C ABI
@@ -1101,8 +340,9 @@ static lpp_status try_product_layout(lpp_engine* e, DevCsr& A, bool* as_product)
 {
 	*as_product = false;
 	if (A.nrows == 0 || A.nnz == 0) return LPP_OK;
+	const CsrSwitches sw = csr_switches_from_env();
 	if (e->hint.kind) { // the caller described the model behind this matrix (lpp_engine_set_model_*): its structured form, if the description is this CSR
-		StageTimer tm("structured form from the model description");
+		StageTimer tm("structured form from the model description", sw.verbose);
 		bool done = false;
 		lpp_status st = model_layout_from_hint(e, A, &done);
 		e->hint = ModelHint(); // one matrix per description
@@ -1114,14 +354,14 @@ static lpp_status try_product_layout(lpp_engine* e, DevCsr& A, bool* as_product)
 		}
 	}
 	int64_t hb = A.hint_block;
-	if (hb == 0 && !(getenv("LPP_DETECT_BLOCK") && atoi(getenv("LPP_DETECT_BLOCK")) == 0) && (size_t)A.nrows * e->esz < ((size_t)1 << 32)) {
-		StageTimer tm("basis block detection");
-		hb = e->is_complex ? detect_row_block_t<cplx>(e, A, (int64_t)1 << 23) : detect_row_block_t<double>(e, A, (int64_t)1 << 23);
-		if (hb && getenv("LPP_VERBOSE")) fprintf(stderr, "lpp: detected a basis block of %lld rows\n", (long long)hb);
-		if (hb > 0 && hb <= (int64_t)((156 * 1024) / e->esz)) A.hint_block = hb; // finalize_csr need not look again
+	if (hb == 0 && !sw.detect_block.off() && (size_t)A.nrows * e->esz < ((size_t)1 << 32)) {
+		StageTimer tm("basis block detection", sw.verbose);
+		hb = detect_row_block(e, A, e->esz, (int64_t)1 << 23); // (the product-basis layout holds blocks beyond the LDS window)
+		if (hb && sw.verbose) fprintf(stderr, "lpp: detected a basis block of %lld rows\n", (long long)hb);
+		if (hb > 0 && hb <= lds_cap_elems(e->esz)) A.hint_block = hb; // finalize_csr need not look again
 	}
 	if (hb <= 0) return LPP_OK;
-	StageTimer tm("product-basis layout from the CSR");
+	StageTimer tm("product-basis layout from the CSR", sw.verbose);
 	lpp_status st = pb_from_csr(e, A, hb, as_product);
 	if (st != LPP_OK) return st;
 	if (*as_product) free_csr(A);
@@ -1327,7 +567,7 @@ lpp_status lpp_engine_get_csr(lpp_engine* e, int32_t which, int64_t* nrows, int6
 		dval = X.val;
 		if (X.nnz == 0 || (dcol && dval)) return LPP_OK;
 		if (!X.sliced) return fail(LPP_ERR_STATE, "lpp_engine_get_csr: matrix arrays missing");
-		lpp_status st = e->is_complex ? rebuild_csr_t<cplx>(e, X, scol, sval) : rebuild_csr_t<double>(e, X, scol, sval);
+		lpp_status st = rebuild_csr(e, X, scol, sval);
 		if (st != LPP_OK) return st;
 		dcol = (const int32_t*)scol.p;
 		dval = sval.p;
@@ -1521,39 +761,18 @@ lpp_status lpp_engine_get_layout(lpp_engine* e, int32_t which, lpp_layout* out)
 	size_t stream = 0; // what one product must read of the matrix (see lpp_layout::stream_bytes)
 	if (A.col) bytes += sizeof(int32_t) * (size_t)A.nnz;
 	if (A.val) bytes += s * (size_t)A.nnz;
-	if (A.sliced) {
-		const size_t nz = (size_t)L.per_row_entries;
-		const size_t struct_slices = A.tmpl ? (size_t)A.geom.spb : (size_t)A.geom.nslices; // block-periodic: block 0 only
-		const size_t struct_rows = A.tmpl ? (size_t)A.geom.B : (size_t)A.nrows;
-		const size_t struct_nz = A.tmpl ? nz / (size_t)A.geom.nblocks : nz;
-		const size_t b_struct = sizeof(int64_t) * (struct_slices + 1) + sizeof(int32_t) * struct_rows // slice_ptr, row_len
-		    + (A.local16 ? sizeof(uint16_t) : sizeof(int32_t)) * (struct_nz + 64);
-		bytes += b_struct;
-		size_t b_val;
-		if (A.coded)
-			b_val = sizeof(int64_t) * ((A.tmpl == 2 ? (size_t)A.geom.spb : (size_t)A.geom.nslices) + 1) + 256 * sizeof(double) + sizeof(uint32_t) * (size_t)A.code_words;
-		else
-			b_val = s * (nz + 64);
-		bytes += b_val;
-		stream += b_struct + b_val; // a template (block 0 only) is counted once: it stays in L2 after the first block
-		if (A.rrowptr) {
-			const size_t lists = (size_t)A.geom.nslices * (size_t)A.dia_stride * (sizeof(int32_t) + s);
-			bytes += sizeof(int64_t) * (size_t)(A.nrows + 1) + lists;
-			stream += lists;
-		}
-		if (A.dcode) {
-			bytes += (size_t)A.nrows * (s / 8);
-			stream += (size_t)A.nrows * (s / 8);
-		}
+	if (A.sliced) { // the arrays build_sliced allocated (lpp_csr_plan.h)
+		const SlicedSizes z = sliced_sizes(sliced_shape(A, s));
+		bytes += z.resident_bytes();
+		stream += z.stream_bytes();
 	} else {
 		stream = bytes; // row-group kernel: row pointers, columns and values are all read
 	}
 	if (A.out_part) { // split-panel layout: the leaving entries as further (sliced, panel-major) matrices + the row map
 		for (int q = 0; q < A.split_parts; q++) {
 			const DevCsr& O = A.out_part[q];
-			const size_t nz = (size_t)O.nnz;
-			size_t b = sizeof(int64_t) * (size_t)(O.geom.nslices + 1) + sizeof(int32_t) * (size_t)O.nrows + sizeof(int32_t) * (nz + 64) + sizeof(int32_t) * (size_t)O.nrows;
-			b += O.coded ? sizeof(int64_t) * (size_t)(O.geom.nslices + 1) + 256 * sizeof(double) + sizeof(uint32_t) * (size_t)O.code_words : s * (nz + 64);
+			const SlicedSizes z = sliced_sizes(sliced_shape(O, s));
+			const size_t b = z.structure() + z.values() + sizeof(int32_t) * (size_t)O.nrows; // + its share of the row map
 			stream += b;
 			bytes += b + sizeof(int64_t) * (size_t)(O.nrows + 1);
 			L.nnz += O.nnz;

@@ -3,11 +3,13 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <initializer_list>
 #include <string>
 #include <utility>
 #include <vector>
 
+#include "lpp_csr_plan.h"
 #include "lpp_host.h"
 #include "lpp_kernels.h"
 #include "lpp_pb_kernels.h"
@@ -308,8 +310,26 @@ struct lpp_engine {
 
 namespace lpp {
 struct AsmParams; // lpp_assemble_kernels.h
+// ---- the general CSR layout (lpp_csr_layout.hip; its decisions: lpp_csr_plan.h) ----
 void free_csr(DevCsr& A);
+// choose the SpMV kernel of A and build its layout; the switches are read here, or are the ones the caller's own build has read
 lpp_status finalize_csr(lpp_engine* e, DevCsr& A, bool allow_drop_plain, int force_mode = 0, int64_t force_block = 0);
+lpp_status finalize_csr(lpp_engine* e, DevCsr& A, const CsrSwitches& sw, bool allow_drop_plain, int force_mode, int64_t force_block);
+// the basis block of a matrix nobody described, from a sample of its slices (elements of esz bytes; 0: none of at most cap_elems rows)
+int64_t detect_row_block(lpp_engine* e, const DevCsr& A, size_t esz, int64_t cap_elems);
+// plain columns and values of a matrix whose only resident form is the sliced layout
+lpp_status rebuild_csr(lpp_engine* e, const DevCsr& A, DevBuf& col_out, DevBuf& val_out);
+SlicedShape sliced_shape(const DevCsr& A, size_t esz); // what the sizes of A's sliced arrays follow from (sliced_sizes)
+lpp_status scan_exclusive(lpp_engine* e, int64_t* arr, int64_t n, int64_t* total_out); // in place; arr[n-1] must be 0 and receives the total
+// LPP_VERBOSE: wall-clock of a one-off set-up stage on stderr, at the end of its scope
+struct StageTimer {
+	const char* what;
+	bool on;
+	std::chrono::steady_clock::time_point t0;
+	StageTimer(const char* w, bool verbose) : what(w), on(verbose), t0(std::chrono::steady_clock::now()) { }
+	StageTimer(const StageTimer&) = delete;
+	~StageTimer();
+};
 void free_kron(lpp_engine* e);
 void drop_product(lpp_engine* e); // matrix-free state, split flags: called by every matrix setup
 int kron_launch(lpp_engine* e, const void* ywin, const void* ydown, void* x, double* partial, const EpiScale& sc = EpiScale { nullptr, nullptr, 0 }, int part = 0,
@@ -341,10 +361,10 @@ struct DropUnlessDone {
 // The admission gate.  `force_switch` (LPP_PRODUCT_LAYOUT, LPP_TJ_LAYOUT): 0 = never, any other value = forced, unset = by size (the
 // thresholds are the caller's).  An explicit kernel choice, uncompressed values and the switches of the general layout mean "measure that
 // one": never.  Read at every call.  The four callers' rules had drifted apart; the differences are inherited as found:
-//   extra: further switches of the general layout (pb_chain and tj_applies list LPP_KEEP_PLAIN_CSR, the other two nothing)
+//   keep_plain_csr_refuses: LPP_KEEP_PLAIN_CSR counts among the general layout's switches (pb_chain and tj_applies; not the other two)
 //   any_compress_value: LPP_COMPRESS_VALUES refuses whatever its value (tj_applies); otherwise only when it resolves to 0
 enum class LayoutGate { Never, Forced, BySize };
-LayoutGate layout_gate(const lpp_engine* e, const char* force_switch, std::initializer_list<const char*> extra = {}, bool any_compress_value = false);
+LayoutGate layout_gate(const lpp_engine* e, const char* force_switch, bool keep_plain_csr_refuses = false, bool any_compress_value = false);
 // The diagonal's dictionary, device part: the table of distinct 64-bit patterns and its overflow flag, allocated and cleared by init();
 // after the caller's collect kernel fetch() enqueues the copies into `host` / `ov` (the caller synchronises)
 struct DictTable {

@@ -41,21 +41,21 @@ template <typename V> lpp_status to_device(V** dst, const std::vector<V>& src, h
 } // namespace
 
 // ---- shared by the builders of the special layouts (lpp_engine_impl.h) -----------------------------------------------------------------
-LayoutGate layout_gate(const lpp_engine* e, const char* force_switch, std::initializer_list<const char*> extra, bool any_compress_value)
+LayoutGate layout_gate(const lpp_engine* e, const char* force_switch, bool keep_plain_csr_refuses, bool any_compress_value)
 {
 	bool forced = false;
 	if (const char* s = getenv(force_switch)) {
 		if (atoi(s) == 0) return LayoutGate::Never;
 		forced = true;
 	}
-	if (e->cfg.spmv_kernel != LPP_SPMV_AUTO || getenv("LPP_SPMV_KERNEL")) return LayoutGate::Never;
+	const CsrSwitches sw = csr_switches_from_env();
+	if (e->cfg.spmv_kernel != LPP_SPMV_AUTO || sw.spmv_kernel.set) return LayoutGate::Never;
 	int want = e->cfg.compress_values;
-	if (const char* s = getenv("LPP_COMPRESS_VALUES")) want = any_compress_value ? 0 : atoi(s);
+	if (sw.compress_values.set) want = any_compress_value ? 0 : sw.compress_values.v;
 	if (want == 0) return LayoutGate::Never;
-	for (const char* k : { "LPP_SHARED_OFFSETS", "LPP_LOCAL16", "LPP_DIAG_CODES", "LPP_BLOCK_TEMPLATE", "LPP_WINDOW_ROWS" })
-		if (getenv(k)) return LayoutGate::Never; // switches of the general layout: measure that one
-	for (const char* k : extra)
-		if (getenv(k)) return LayoutGate::Never;
+	// switches of the general layout: measure that one
+	if (sw.shared_offsets.set || sw.local16.set || sw.diag_codes.set || sw.block_template.set || sw.window_rows.set) return LayoutGate::Never;
+	if (keep_plain_csr_refuses && sw.keep_plain_csr.set) return LayoutGate::Never;
 	return forced ? LayoutGate::Forced : LayoutGate::BySize;
 }
 
@@ -82,11 +82,7 @@ lpp_status DictTable::fetch(hipStream_t st)
 PbDict pb_diag_dict(const DictTable& t, bool honour_switch, const double* extra, size_t n_extra)
 {
 	PbDict d;
-	std::vector<unsigned long long> keys;
-	keys.push_back(0ull); // code 0 = +0.0 (padding places of k_pb_down)
-	auto add_key = [&](unsigned long long k) {
-		if (std::find(keys.begin(), keys.end(), k) == keys.end()) keys.push_back(k);
-	};
+	std::vector<unsigned long long> keys; // (code 0 = +0.0, the padding places of k_pb_down: dict256_from_keys)
 	size_t ndiag = 0;
 	for (unsigned long long k : t.host)
 		if (k != kDictEmpty) ndiag++;
@@ -95,18 +91,14 @@ PbDict pb_diag_dict(const DictTable& t, bool honour_switch, const double* extra,
 	if (d.plain_diag && sw && atoi(sw) == 0) return d; // switched off: general layout
 	if (!d.plain_diag)
 		for (unsigned long long k : t.host)
-			if (k != kDictEmpty) add_key(k);
-	for (size_t p = 0; p < n_extra && keys.size() <= 256; p++) {
+			if (k != kDictEmpty) keys.push_back(k);
+	for (size_t p = 0; p < n_extra; p++) {
 		unsigned long long k;
 		std::memcpy(&k, &extra[p], 8);
-		add_key(k);
+		keys.push_back(k);
 	}
-	if (keys.size() > 256) return d;
-	std::sort(keys.begin(), keys.end());
-	d.dict.resize(256);
-	for (size_t i = 0; i < 256; i++) std::memcpy(&d.dict[i], &keys[std::min(i, keys.size() - 1)], 8);
-	d.ndict = (int)keys.size();
-	d.applies = true;
+	d.ndict = dict256_from_keys(std::move(keys), d.dict);
+	d.applies = d.ndict > 0;
 	return d;
 }
 
@@ -892,7 +884,7 @@ lpp_status pb_chain(lpp_engine* e, const AsmParams& P, int L, int n, const std::
 {
 	*done = false;
 	if (e->is_complex || P.nloc <= 0 || P.model != ASM_HEISENBERG) return LPP_OK;
-	const LayoutGate gate = layout_gate(e, "LPP_PRODUCT_LAYOUT", { "LPP_KEEP_PLAIN_CSR" }); // (the extra switch: inherited as found)
+	const LayoutGate gate = layout_gate(e, "LPP_PRODUCT_LAYOUT", true); // (the extra switch: inherited as found)
 	if (gate == LayoutGate::Never) return LPP_OK;
 	const int64_t n_up = P.nloc, pitch = pb_pitch_for(n_up);
 	if (gate == LayoutGate::BySize && (size_t)n_up * sizeof(double) < ((size_t)32 << 20)) return LPP_OK; // as for the Hubbard matrices (assemble_hubbard_pb)

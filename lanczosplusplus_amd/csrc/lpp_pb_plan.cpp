@@ -11,21 +11,14 @@ namespace lpp {
 
 PbSwitches pb_switches_from_env()
 {
-	auto rd = [](const char* k) {
-		PbSwitch s;
-		if (const char* t = getenv(k)) {
-			s.set = true;
-			s.v = (int)std::max<long long>(INT_MIN, std::min<long long>(atoll(t), INT_MAX));
-		}
-		return s;
-	};
+	auto rd = env_switch;
 	PbSwitches sw;
 	sw.big2 = rd("LPP_PB_BIG2"), sw.big2_four = rd("LPP_PB_BIG2_FOUR"), sw.piece_rows = rd("LPP_PB_PIECE_ROWS"), sw.parts = rd("LPP_PB_PARTS");
 	sw.wide = rd("LPP_PB_WIDE"), sw.bank_ways = rd("LPP_PB_BANK_WAYS"), sw.perm = rd("LPP_PB_PERM"), sw.seg = rd("LPP_PB_SEG"), sw.pre0 = rd("LPP_PB_PRE0");
 	sw.down_rounds = rd("LPP_PB_DOWN_ROUNDS"), sw.order_window = rd("LPP_PB_ORDER_WINDOW"), sw.down_image = rd("LPP_PB_DOWN_IMAGE"), sw.pace = rd("LPP_PB_PACE");
 	sw.chain = rd("LPP_PB_CHAIN"), sw.down_tasks = rd("LPP_PB_DOWN_TASKS"), sw.down_pf = rd("LPP_PB_DOWN_PF"), sw.chain_pace = rd("LPP_PB_CHAIN_PACE");
 	sw.lazy_tx = rd("LPP_PB_LAZY_TX");
-	sw.verbose = getenv("LPP_VERBOSE") != nullptr;
+	sw.verbose = rd("LPP_VERBOSE").set;
 	return sw;
 }
 

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "lpp_host.h"
+#include "lpp_switch.h"
 
 namespace lpp {
 
@@ -34,15 +35,8 @@ struct PbBuildInput {
 	int64_t pre_nnz = 0;
 };
 
-// an LPP_PB_* switch as the planner sees it: unset, or the integer it was set to
-struct PbSwitch {
-	bool set = false;
-	int v = 0;
-	int value_or(int dflt) const { return set ? v : dflt; }
-	bool off() const { return set && v == 0; } // "=0 switches it off"
-};
-struct PbSwitches { // LPP_PB_<NAME>, in the order pb_plan consults them
-	PbSwitch big2, big2_four, piece_rows, parts, wide, bank_ways, perm, seg, pre0, down_rounds, order_window, down_image, pace, chain, down_tasks, down_pf,
+struct PbSwitches { // LPP_PB_<NAME> (EnvSwitch, lpp_switch.h), in the order pb_plan consults them
+	EnvSwitch big2, big2_four, piece_rows, parts, wide, bank_ways, perm, seg, pre0, down_rounds, order_window, down_image, pace, chain, down_tasks, down_pf,
 	    chain_pace, lazy_tx;
 	bool verbose = false; // LPP_VERBOSE
 };

@@ -2,6 +2,7 @@
 // with the value dictionary, shared-offset entries, 16-bit block-local columns and the block template.
 #pragma once
 #include "lpp_common.h"
+#include "lpp_csr_plan.h"
 
 namespace lpp {
 
@@ -92,13 +93,7 @@ __global__ __launch_bounds__(kBlock) void k_spmv_rowgroup(int64_t nrows, const i
 // discarded by a select): predicated loads made hipcc emit a branch and s_waitcnt vmcnt(0) per
 // load, i.e. a single load in flight per wave.
 // ---------------------------------------------------------------------------------------------
-struct SliceGeom {
-	int64_t nrows;
-	int64_t B; // rows per block
-	int32_t spb; // slices per block = ceil(B/64)
-	int64_t nblocks;
-	int64_t nslices; // nblocks * spb
-};
+// (struct SliceGeom: lpp_csr_plan.h, with the function that fills it)
 
 __device__ __forceinline__ void slice_rows(const SliceGeom& g, int64_t s, int64_t& row0, int& nvalid)
 {

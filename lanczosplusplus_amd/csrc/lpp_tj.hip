@@ -245,7 +245,7 @@ void tj_fill_random(lpp_engine* e, double* dev, uint64_t seed)
 bool tj_applies(const lpp_engine* e, const TjModel& M)
 {
 	// (LPP_KEEP_PLAIN_CSR listed, LPP_COMPRESS_VALUES refusing whatever its value: both inherited as found)
-	const LayoutGate gate = layout_gate(e, "LPP_TJ_LAYOUT", { "LPP_KEEP_PLAIN_CSR" }, true);
+	const LayoutGate gate = layout_gate(e, "LPP_TJ_LAYOUT", true, true);
 	if (gate == LayoutGate::Never) return false;
 	const int L = M.L, nup = M.nup, ndown = M.ndown, Lo = nup + ndown, nholes = L - Lo;
 	if (Lo < 2 || Lo > 2 * kTjMaxHalf || nup < 1 || ndown < 1 || L > 31 || nholes < 0) return false;

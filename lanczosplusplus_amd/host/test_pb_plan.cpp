@@ -274,9 +274,9 @@ void check_plan(const PbBuildInput& in, const PbSwitches& sw, int num_cus, const
 	CHECK(B.lazy_tx == (B.tx && sw.lazy_tx.value_or(1) != 0));
 }
 
-PbSwitch on(int v)
+EnvSwitch on(int v)
 {
-	PbSwitch s;
+	EnvSwitch s;
 	s.set = true;
 	s.v = v;
 	return s;
@@ -453,7 +453,7 @@ void check_launch_forms()
 	make_problem(p, S, S, false);
 	struct Row {
 		const char* name;
-		PbSwitch PbSwitches::*sw;
+		EnvSwitch PbSwitches::*sw;
 		int v;
 		bool chain, down_tasks, down_pf, drop_pace, lazy;
 	};

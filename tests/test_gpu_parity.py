@@ -1688,3 +1688,130 @@ def test_plain_format_window_layout_outs_first_and_pitched(source, pitched, monk
             assert np.linalg.norm(r) < 1e-5 and abs(np.linalg.norm(zg[0]) - 1) < 1e-8
             ag, bg, _ = e.decomposition(init)
             assert len(ag) == steps_o and rel(ag, ao) < 1e-8 and rel(bg, bo) < 1e-8
+
+
+# The Hubbard chain of test_plain_format_window_layout_outs_first_and_pitched kept in the general layout: 792 row blocks of 924 rows (more
+# than twice the CU count: the window kernel is taken without forcing; 924 = 12 mod 16: pitching has something to do).
+_PLAIN_FORMAT = dict(LPP_COMPRESS_VALUES="0", LPP_SHARED_OFFSETS="0", LPP_LOCAL16="0")
+GENERAL_SWITCH_ROWS = {
+    "defaults": {},
+    "local16_0": dict(LPP_LOCAL16="0"),
+    "diag_codes_0": dict(LPP_DIAG_CODES="0"),
+    "block_template_0": dict(LPP_BLOCK_TEMPLATE="0"),
+    "template_pack_0": dict(LPP_TEMPLATE_PACK="0"),
+    "shared_offsets_0": dict(LPP_SHARED_OFFSETS="0"),
+    "compress_values_0": dict(LPP_COMPRESS_VALUES="0"),
+    "plain_outs_first_0": dict(_PLAIN_FORMAT, LPP_OUTS_FIRST="0"),
+    "plain_pitch_rows_1": dict(_PLAIN_FORMAT, LPP_PITCH_ROWS="1"),
+    "spmv_kernel_1": dict(LPP_SPMV_KERNEL="1"),
+    "spmv_kernel_2": dict(LPP_SPMV_KERNEL="2"),
+    "spmv_kernel_3": dict(LPP_SPMV_KERNEL="3"),
+    "window_rows_4096": dict(LPP_WINDOW_ROWS="4096"),
+    "spmv_g_32_kernel_1": dict(LPP_SPMV_G="32", LPP_SPMV_KERNEL="1"),
+    "keep_plain_csr_1": dict(LPP_KEEP_PLAIN_CSR="1"),
+    "detect_block_0": dict(LPP_DETECT_BLOCK="0"),  # on the uploaded matrix without set_row_block
+}
+_GENERAL_ORACLE = {}
+
+
+def _general_oracle():
+    if not _GENERAL_ORACLE:
+        L, nup, ndown = 12, 6, 5
+        hop, U, V = chain(L, -1.0, True), np.where(np.arange(L) % 3 == 0, 2.0, 4.0), np.tile([0.25, -0.5, 0.0], 8)
+        A = oracle.hubbard_csr(L, nup, ndown, hop, U, V)
+        x0, y = oracle.fill_random(A.nrows, 7), oracle.fill_random(A.nrows, 8)
+        _GENERAL_ORACLE.update(model=(L, nup, ndown, hop, U, V), A=A, x0=x0, y=y, xo=oracle.spmv_acc(A, x0.copy(), y))
+        for a in (A.rowptr, A.colind, A.values, x0, y, _GENERAL_ORACLE["xo"]):
+            a.setflags(write=False)
+    return _GENERAL_ORACLE
+
+
+def _general_build(e, source):
+    """assembled / uploaded (with set_row_block) / unhinted (uploaded, nobody names the basis block)"""
+    O = _general_oracle()
+    L, nup, ndown, hop, U, V = O["model"]
+    A = O["A"]
+    if source == "assembled":
+        e.assemble_hubbard(L, nup, ndown, hop, U, V)
+    else:
+        if source == "uploaded":
+            e.set_row_block(comb(L, nup))
+        e.set_csr(A.rowptr, A.colind, A.values)
+
+
+def _general_sources(row):
+    return ("unhinted",) if row == "detect_block_0" else ("assembled", "uploaded")
+
+
+# layout() of every row above, recorded from a run of this test at the commit BEFORE the general layout's build moved into lpp_csr_plan.h /
+# lpp_csr_layout.hip; both sources of a row gave the same dictionary.  Written as the fields that differ from the defaults' row.
+_GENERAL_DEFAULTS = dict(kernel=3, coded=1, local16=1, shared_stride=16, block_template=2, diagonal_codes=1, nnz=10178784, per_row_entries=4283136,
+                         shared_entries=83520, rows_per_block=924, resident_bytes=14751456, stream_bytes=3042512, pieces=0, coupling_parts=0,
+                         diagonal_plain=0, chained_step=0, split_panel=0, rows_by_list_length=0, segments=0, coupling_rounds=0)
+_GENERAL_PLAIN = dict(coded=0, local16=0, shared_stride=0, block_template=0, diagonal_codes=0, per_row_entries=10178784, shared_entries=0)
+_GENERAL_ONE_BLOCK = dict(kernel=2, local16=0, block_template=0, diagonal_codes=0, per_row_entries=5064992, shared_entries=79904, rows_per_block=731808,
+                          resident_bytes=48828176, stream_bytes=37119232)
+GENERAL_LAYOUTS = {
+    "defaults": dict(),
+    "local16_0": dict(local16=0, block_template=0, resident_bytes=45111488, stream_bytes=33402544),
+    "diag_codes_0": dict(block_template=1, diagonal_codes=0, per_row_entries=5014944, resident_bytes=25863232, stream_bytes=14154288),
+    "block_template_0": dict(block_template=0, resident_bytes=36545088, stream_bytes=24836144),
+    "template_pack_0": dict(),  # the packed copy is counted in neither byte figure: only the product shows it
+    "shared_offsets_0": dict(local16=0, shared_stride=0, block_template=0, diagonal_codes=0, per_row_entries=10178784, shared_entries=0,
+                             resident_bytes=66026136, stream_bytes=60171664),
+    "compress_values_0": dict(coded=0, block_template=0, diagonal_codes=0, per_row_entries=5014944, resident_bytes=67162264, stream_bytes=55453320),
+    "plain_outs_first_0": dict(_GENERAL_PLAIN, resident_bytes=131022928, stream_bytes=125168456),  # the order inside a row and the pitch are
+    "plain_pitch_rows_1": dict(_GENERAL_PLAIN, resident_bytes=131022928, stream_bytes=125168456),  # invisible here: get_csr and the product
+    "spmv_kernel_1": dict(_GENERAL_PLAIN, kernel=1, rows_per_block=0, resident_bytes=127999880, stream_bytes=127999880),
+    "spmv_kernel_2": _GENERAL_ONE_BLOCK,
+    "spmv_kernel_3": dict(),
+    "window_rows_4096": dict(local16=0, block_template=0, per_row_entries=4333184, shared_entries=79904, rows_per_block=4096, resident_bytes=45089344,
+                             stream_bytes=33380400),
+    "spmv_g_32_kernel_1": dict(_GENERAL_PLAIN, kernel=1, rows_per_block=0, resident_bytes=127999880, stream_bytes=127999880),
+    "keep_plain_csr_1": dict(resident_bytes=136896864),
+    "detect_block_0": _GENERAL_ONE_BLOCK,  # no block: the locality count of a 16384-row window stays below 0.35, one block of all rows
+}
+
+
+def _general_expected(row):
+    return dict(_GENERAL_DEFAULTS, **GENERAL_LAYOUTS[row])
+
+
+def _general_check(e, row, source):
+    O = _general_oracle()
+    A = O["A"]
+    lay = e.layout()
+    print(row, source, lay)
+    assert lay == _general_expected(row), (row, source, lay)
+    rp, ci, va = e.get_csr()
+    assert np.array_equal(rp, A.rowptr) and np.array_equal(ci, A.colind) and np.array_equal(_bits(va), _bits(A.values)), (row, source)
+    err = rel(e.matrixVectorProduct(O["x0"].copy(), O["y"]), O["xo"])
+    print(row, source, "error", err)
+    assert err < SPMV_TOL, (row, source, err)
+    return lay
+
+
+@pytest.mark.parametrize("row", list(GENERAL_SWITCH_ROWS) + ["per_build_pair"])
+def test_general_layout_switches_select_their_forms(row, monkeypatch):
+    """Characterisation of the general CSR layout's build (finalize_csr and what it calls): under every switch the build reads, the matrix
+    gets exactly the layout the table records -- the whole layout() dictionary, byte figures included, which is all that shows
+    LPP_TEMPLATE_PACK -- lpp_engine_get_csr returns the oracle's CSR bit for bit and x += H y is the oracle's.  The last case builds two
+    engines in one process with a switch changed between them: the switches are read at every build, never once per process."""
+    monkeypatch.setenv("LPP_PRODUCT_LAYOUT", "0")
+    if row == "per_build_pair":
+        monkeypatch.setenv("LPP_LOCAL16", "0")
+        with LanczosEngine() as first:
+            _general_build(first, "uploaded")
+            monkeypatch.delenv("LPP_LOCAL16")
+            with LanczosEngine() as second:
+                _general_build(second, "uploaded")
+                l1 = _general_check(first, "local16_0", "uploaded")
+                l2 = _general_check(second, "defaults", "uploaded")
+        assert l1 != l2 and (l1["local16"], l2["local16"]) == (0, 1)
+        return
+    for k, v in GENERAL_SWITCH_ROWS[row].items():
+        monkeypatch.setenv(k, v)
+    for source in _general_sources(row):
+        with LanczosEngine() as e:
+            _general_build(e, source)
+            _general_check(e, row, source)

@@ -402,3 +402,21 @@ def test_product_basis_planner_under_sanitizers(tmp_path):
     assert out.returncode == 0, out.stdout
     run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert run.returncode == 0 and run.stdout.strip().endswith("ok"), run.stdout
+
+
+def test_general_layout_planner_under_sanitizers(tmp_path):
+    """the decisions of the general CSR layout (csrc/lpp_csr_plan.h) in a stand-alone program (its own main) built with the address and
+    undefined-behaviour sanitizers: lanes per row, the slice geometry, window rows, the kernel mode table, the split-panel gate and the
+    pitch pad at their thresholds and under every switch, the basis-block detection on matrices the program builds, the byte size of every
+    array of the sliced layout against sums written out by hand, and the 256-entry dictionary; the program prints `ok`"""
+    import subprocess
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    csrc = os.path.join(root, "lanczosplusplus_amd", "csrc")
+    exe = str(tmp_path / "test_csr_plan")
+    out = subprocess.run([os.environ.get("CXX", "g++"), "-O1", "-g1", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                          "-I" + os.path.join(root, "include"), "-I" + csrc, "-o", exe, os.path.join(root, "lanczosplusplus_amd", "host", "test_csr_plan.cpp")],
+                         stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert out.returncode == 0, out.stdout
+    run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert run.returncode == 0 and run.stdout.strip().endswith("ok"), run.stdout
