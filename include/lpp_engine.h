@@ -588,7 +588,9 @@ lpp_status lpp_engine_bench_rdm(lpp_engine* e, int32_t basis, int32_t nsites, in
  *   written); c flips the bit, sign ProgramGlobals::doSign(word after the flip, site) times (-1)^(up electrons) for dof = down.  The result lives in the
  *   original sector: a string that does not conserve both numbers -> LPP_ERR_INVALID.
  * An engine holding a hole-major t-J model -> LPP_ERR_INVALID naming the model; the Python layer and the C++ shim, which know the model of every
- * engine they set up, refuse t-J and Heisenberg engines the same way.  A partitioned engine -> LPP_ERR_STATE. */
+ * engine they set up, refuse t-J engines the same way and take Heisenberg engines (twiceS = 1) to the _heis entry points of the next block: the C++ shim
+ * by the model, the Python layer where the caller passes basis="spin_half" (without it a Heisenberg engine is refused by the model's name, with that
+ * hint).  A partitioned engine -> LPP_ERR_STATE. */
 enum { LPP_OP_IDENTITY = 0 };
 enum { LPP_STRING_MANY_POINT = 0, LPP_STRING_MEASURE = 1 };
 
@@ -622,6 +624,53 @@ lpp_status lpp_engine_many_point_host(lpp_engine* e, int32_t convention, int32_t
  * model_bytes = sizeof(value) * (N + sum over the strings of the destinations they reach): bra once, one ket element per string and destination. */
 lpp_status lpp_engine_bench_string_dot(lpp_engine* e, int32_t convention, int32_t nstrings, const int64_t* offsets, const int32_t* ops, const int32_t* sites, const int32_t* spins,
                                        const int32_t* flags, int32_t nsites, int32_t nup, int32_t ndown, int32_t warmup, int32_t iters, double* ms_per_launch, double* model_bytes);
+
+/* ---- many-point correlations of the S = 1/2 Heisenberg basis (entry points added under ABI 7, no struct changes; one GPU; csrc/lpp_obs.hip,
+ *      csrc/lpp_obs_heis_string_plan.h, csrc/lpp_obs_heis_string_kernels.h) ----
+ * The reference's -M for Model=Heisenberg with HeisenbergTwiceS=1: Engine::manyPoint chains accModifiedState_ with factor 1, which
+ * BasisHeisenberg::getBraIndex serves for n, sz, splus and sminus (BasisHeisenberg.h:123-139, :230-280).  Argument lists as the calls above; nup =
+ * szPlusConst, ndown and flags are not read, the final sector is reported as (szPlusConst', 0).  LPP_STRING_MANY_POINT only: the measure convention's
+ * labels are per fermion species -> LPP_ERR_INVALID.  ops[0] acts first:
+ *   splus / sminus flip the site's bit where it is clear / set, value 1, the spin is not read; n keeps the index with value bit (LPP_SPIN_UP) or
+ *   1 - bit (LPP_SPIN_DOWN); sz keeps it with the reference's raw value 1 - 2 bit = -2 S^z; there is no sign anywhere.  The sector walks by
+ *   hasNewPartsSplusOrMinus, szPlusConst +- 1.
+ * A whole string composes on the host into five words and no table: result[d] = sign * (-1)^popcount((d ^ flip) & zmask) * src[rank(d ^ flip)] where
+ * ((d ^ flip) & need) == want, else 0 -- the conditions and the sz parity are on the SOURCE word.  A string whose conditions contradict each other
+ * (splus twice on a site, n up and n down of a site) is identically zero: "dead".
+ * LPP_ERR_INVALID, as lpp_engine_apply_operator_heis has it: c / cdagger in a string, S+ met in the all-up sector, S- met in the all-down one (refused at
+ * the step that meets it), a site >= nsites, 0 or more than 16 operators.  Engines of spins above 1/2 are refused by the callers that know the model.
+ * DEVIATIONS, both where the reference is ill-defined: (1) n and sz act in the sector the string has reached; the reference's getNeededBasis
+ * (Engine.h:397-400) hands them the original sector's basis even after the string has left it.  (2) S- is refused when the CURRENT sector is the all-down
+ * one; the reference tests the original sector's szPlusConst (Heisenberg.h:233) and otherwise wraps an unsigned number.
+ * A partitioned engine -> LPP_ERR_STATE; a hole-major t-J engine -> LPP_ERR_INVALID.  The entry points of the block above keep their behaviour; the Python
+ * layer and the C++ shim choose between the two blocks by the engine's model (Python: the explicit basis="spin_half"). */
+
+/* The plan of one string (host only; exposed for the CPU test-suite): the final szPlusConst, *dead, the five words, *low_bits (the cut of the word,
+ * lpp_obs_plan_heis) and, where action is not NULL, action[dst] = +-(src + 1) or 0 for the *n_dst destinations, expanded through the per-run entries
+ * and the same lookup function (obs_heis_string_source) the kernels use.  All zero for a dead string.  NULL: not written. */
+lpp_status lpp_obs_string_plan_heis(int32_t convention, int32_t nops, const int32_t* ops, const int32_t* sites, const int32_t* spins, const int32_t* flags, int32_t nsites,
+                                    int32_t nup, int32_t ndown, int32_t* nup_new, int32_t* dead, uint64_t* flip, uint64_t* need, uint64_t* want, uint64_t* zmask, int32_t* sign,
+                                    int32_t* low_bits, int64_t* n_dst, int64_t* action);
+
+/* lpp_engine_apply_string / _host in the Heisenberg basis, contracts as those calls: one launch of k_obs_string_apply_heis, then a stream sync.  *has = 1
+ * whenever the call succeeds (this basis has no "no sector"); a dead string launches nothing and gives z = 0 (accumulate: z unchanged). */
+lpp_status lpp_engine_apply_string_heis(lpp_engine* e, int32_t convention, int32_t nops, const int32_t* ops, const int32_t* sites, const int32_t* spins, const int32_t* flags,
+                                        int32_t nsites, int32_t nup, int32_t ndown, double factor_re, double factor_im, const void* d_src, void* d_dst, int32_t accumulate,
+                                        int32_t* has, int32_t* nup_new, int32_t* ndown_new);
+lpp_status lpp_engine_apply_string_heis_host(lpp_engine* e, int32_t convention, int32_t nops, const int32_t* ops, const int32_t* sites, const int32_t* spins,
+                                             const int32_t* flags, int32_t nsites, int32_t nup, int32_t ndown, double factor_re, double factor_im, const void* src, void* dst,
+                                             int32_t accumulate, int32_t* has, int32_t* nup_new, int32_t* ndown_new);
+
+/* lpp_engine_many_point / _host / lpp_engine_bench_string_dot in the Heisenberg basis, contracts as those calls: a dead string and one that ends in another
+ * sector give exactly 0 and launch nothing (Engine.h:382-383); the others go 8 per launch through k_obs_string_dot_heis and a fixed-order reduction, so
+ * a value does not depend on the batch it is computed in, and two calls return the same bits. */
+lpp_status lpp_engine_many_point_heis(lpp_engine* e, int32_t convention, int32_t nstrings, const int64_t* offsets, const int32_t* ops, const int32_t* sites, const int32_t* spins,
+                                      const int32_t* flags, int32_t nsites, int32_t nup, int32_t ndown, int32_t bra_state, int32_t ket_state, double* result);
+lpp_status lpp_engine_many_point_heis_host(lpp_engine* e, int32_t convention, int32_t nstrings, const int64_t* offsets, const int32_t* ops, const int32_t* sites,
+                                           const int32_t* spins, const int32_t* flags, int32_t nsites, int32_t nup, int32_t ndown, const void* bra, const void* ket, double* result);
+lpp_status lpp_engine_bench_string_dot_heis(lpp_engine* e, int32_t convention, int32_t nstrings, const int64_t* offsets, const int32_t* ops, const int32_t* sites,
+                                            const int32_t* spins, const int32_t* flags, int32_t nsites, int32_t nup, int32_t ndown, int32_t warmup, int32_t iters,
+                                            double* ms_per_launch, double* model_bytes);
 
 #ifdef __cplusplus
 }

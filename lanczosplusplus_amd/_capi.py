@@ -169,6 +169,15 @@ SYMBOLS = {
     "lpp_engine_many_point": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P] + [C.c_int32] * 5 + [_P]),
     "lpp_engine_many_point_host": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P] + [C.c_int32] * 3 + [_P, _P, _P]),
     "lpp_engine_bench_string_dot": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P] + [C.c_int32] * 5 + [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "lpp_obs_string_plan_heis": (C.c_int32, [C.c_int32, C.c_int32, _P, _P, _P, _P] + [C.c_int32] * 3 + [C.POINTER(C.c_int32)] * 2 + [C.POINTER(C.c_uint64)] * 4
+                                 + [C.POINTER(C.c_int32)] * 2 + [C.POINTER(C.c_int64), _P]),
+    "lpp_engine_apply_string_heis": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P] + [C.c_int32] * 3 + [C.c_double, C.c_double, _P, _P, C.c_int32]
+                                     + [C.POINTER(C.c_int32)] * 3),
+    "lpp_engine_apply_string_heis_host": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P] + [C.c_int32] * 3 + [C.c_double, C.c_double, _P, _P, C.c_int32]
+                                          + [C.POINTER(C.c_int32)] * 3),
+    "lpp_engine_many_point_heis": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P] + [C.c_int32] * 5 + [_P]),
+    "lpp_engine_many_point_heis_host": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P] + [C.c_int32] * 3 + [_P, _P, _P]),
+    "lpp_engine_bench_string_dot_heis": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P] + [C.c_int32] * 5 + [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 }
 
 _lib = None

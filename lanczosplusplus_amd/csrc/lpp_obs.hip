@@ -6,7 +6,8 @@
 // The device side only.  Each family is one ObsBasis: how its plan is built and uploaded (a DevPlan of its own in the engine's cache) and how it is
 // launched; every entry point is one body over an ObsBasis, and the four destination-driven apply kernels go through one launch (OBS_LAUNCH).
 // The host planners (no GPU, plain C++) are lpp_obs_plan.h (shared sector arithmetic, Hubbard), lpp_obs_tj_plan.h, lpp_obs_heis_plan.h and
-// lpp_obs_string_plan.h; the kernels are lpp_obs_kernels.h, lpp_obs_tj_kernels.h, lpp_obs_heis_kernels.h and lpp_obs_string_kernels.h.
+// lpp_obs_string_plan.h, for strings in the Heisenberg basis lpp_obs_heis_string_plan.h; the kernels are lpp_obs_kernels.h, lpp_obs_tj_kernels.h,
+// lpp_obs_heis_kernels.h, lpp_obs_string_kernels.h and lpp_obs_heis_string_kernels.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -25,6 +26,7 @@
 #include "lpp_obs_string_kernels.h"
 #include "lpp_obs_tj_kernels.h"
 #include "lpp_obs_heis_kernels.h"
+#include "lpp_obs_heis_string_kernels.h"
 
 using namespace lpp;
 using namespace lpp::obs_host;
@@ -755,6 +757,189 @@ lpp_status many_point_dev(lpp_engine* e, int conv, const StringList& S, int L, i
 	return LPP_OK;
 }
 
+// ---- operator strings on the device (S = 1/2 Heisenberg basis; plan: lpp_obs_heis_string_plan.h, kernels: lpp_obs_heis_string_kernels.h) -------
+
+lpp_status refuse_string_heis(const lpp_engine* e, const char* who, int conv)
+{
+	if (multi(e)) return fail(LPP_ERR_STATE, std::string(who) + ": not on a partitioned (multi-rank) engine");
+	if (e->tj.active) return fail(LPP_ERR_INVALID, std::string(who) + ": the t-J model (TjMultiOrb) is not supported, its operator strings are not built yet");
+	if (conv != LPP_STRING_MANY_POINT)
+		return fail(LPP_ERR_INVALID, std::string(who) + ": the Heisenberg basis has the many-point convention only (the labels of the measure convention are per fermion species)");
+	return LPP_OK;
+}
+
+lpp_status heis_string_plan(int nops, const int32_t* ops, const int32_t* sites, const int32_t* spins, int L, int m, HeisStringPlan& P)
+{
+	const char* why = nullptr;
+	return plan_status(plan_heis_string(nops, ops, sites, spins, L, m, P, &why), why);
+}
+
+// One destination sector on the device: its runs, the two low tables and room for `slots` strings' entries per run.  The host copies stay until the
+// struct goes: the uploads are asynchronous.
+struct HeisStringWork {
+	DevBuf runs, low, src, part, out;
+	std::vector<ObsHeisRun> h_runs;
+	std::vector<uint64_t> highs;
+	std::vector<uint16_t> h_low; // word, then rank
+	std::vector<int64_t> h_src, one;
+	int64_t nruns = 0, n_dst = 0;
+	int nlo = 0, grid = 1;
+};
+
+lpp_status heis_string_work(lpp_engine* e, int L, int m2, int slots, HeisStringWork& W)
+{
+	std::vector<uint16_t> word, rank;
+	if (!heis_string_runs(L, m2, true, W.h_runs, W.highs, word, rank))
+		return fail(LPP_ERR_INVALID, "Heisenberg operator string: the sector has more than 2^22 runs of equal high part (the run table's limit)");
+	W.nruns = (int64_t)W.highs.size();
+	W.n_dst = W.h_runs.back().dst0;
+	W.nlo = (int)word.size();
+	W.grid = obs_grid(e, e->is_complex ? W.n_dst : (W.n_dst + 1) / 2);
+	W.h_low = word;
+	W.h_low.insert(W.h_low.end(), rank.begin(), rank.end());
+	W.h_src.assign((size_t)slots * (size_t)W.nruns, 0);
+	HIP_TRY_MEM(W.runs.alloc(sizeof(ObsHeisRun) * W.h_runs.size()));
+	HIP_TRY_MEM(W.low.alloc(sizeof(uint16_t) * W.h_low.size()));
+	HIP_TRY_MEM(W.src.alloc(sizeof(int64_t) * W.h_src.size()));
+	HIP_TRY(hipMemcpyAsync(W.runs.p, W.h_runs.data(), sizeof(ObsHeisRun) * W.h_runs.size(), hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipMemcpyAsync(W.low.p, W.h_low.data(), sizeof(uint16_t) * W.h_low.size(), hipMemcpyHostToDevice, e->stream));
+	return LPP_OK;
+}
+
+// plans[0 .. ns) (none dead) of source sector m into the slots of W and uploaded; B.nlo = 0 where none of them has low-part work
+lpp_status heis_string_slots(lpp_engine* e, HeisStringWork& W, const HeisStringPlan* plans, int ns, int L, int m, ObsHeisStringBase& B, const int64_t** src, ObsHeisStringLow* low)
+{
+	bool low_work = false;
+	for (int s = 0; s < ns; s++) {
+		heis_string_sources(plans[s], L, m, W.highs, W.one);
+		std::copy(W.one.begin(), W.one.end(), W.h_src.begin() + (size_t)s * (size_t)W.nruns);
+		src[s] = (const int64_t*)W.src.p + (size_t)s * (size_t)W.nruns;
+		low[s] = plans[s].low();
+		low_work = low_work || obs_heis_string_low_work(low[s]);
+	}
+	HIP_TRY(hipMemcpyAsync(W.src.p, W.h_src.data(), sizeof(int64_t) * (size_t)ns * (size_t)W.nruns, hipMemcpyHostToDevice, e->stream));
+	B = ObsHeisStringBase { (const ObsHeisRun*)W.runs.p, (const uint16_t*)W.low.p, (const uint16_t*)W.low.p + W.nlo, W.nruns, W.n_dst, low_work ? W.nlo : 0 };
+	return LPP_OK;
+}
+
+// z (+)= factor * string src on device vectors in the basis order.  One launch (none for a dead string: z = 0 or z untouched); the tables are this
+// call's own, so it ends with a stream sync.
+lpp_status apply_string_heis_dev(lpp_engine* e, const HeisStringPlan& P, int L, int m, double fr, double fi, const void* d_src, void* d_dst, bool acc)
+{
+	lpp_status st = check_vectors(e, fi, d_src, d_dst);
+	if (st != LPP_OK) return st;
+	if (P.dead) {
+		if (!acc) HIP_TRY(hipMemsetAsync(d_dst, 0, e->esz * (size_t)P.n_dst, e->stream));
+		HIP_TRY(hipStreamSynchronize(e->stream));
+		return LPP_OK;
+	}
+	HeisStringWork W;
+	if ((st = heis_string_work(e, L, P.m2, 1, W)) != LPP_OK) return st;
+	ObsHeisStringApplyArgs A {};
+	if ((st = heis_string_slots(e, W, &P, 1, L, m, A.b, &A.src, &A.low)) != LPP_OK) return st;
+	A.fr = fr;
+	A.fi = fi;
+	OBS_LAUNCH(k_obs_string_apply_heis, e, acc, P.n_dst, obs_heis_string_lds_bytes(A.b.nlo), d_dst, d_src, A);
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	return LPP_OK;
+}
+
+// what lpp_engine_apply_string_heis and its _host form do before they launch: the refusals, the plan, the new sector reported, the device set
+lpp_status apply_string_heis_front(lpp_engine* e, const std::string& who, bool args_ok, int conv, int nops, const int32_t* ops, const int32_t* sites, const int32_t* spins,
+                                   int L, int m, HeisStringPlan& P, int32_t* has, int32_t* nup_new, int32_t* ndown_new)
+{
+	if (!args_ok) return fail(LPP_ERR_INVALID, who + ": null argument");
+	*has = 0;
+	lpp_status st = refuse_string_heis(e, who.c_str(), conv);
+	if (st != LPP_OK) return st;
+	if ((st = heis_string_plan(nops, ops, sites, spins, L, m, P)) != LPP_OK) return st;
+	*has = 1; // (this basis has no "no sector": the plan refuses where the reference throws)
+	if (nup_new) *nup_new = P.m2;
+	if (ndown_new) *ndown_new = 0;
+	HIP_TRY(hipSetDevice(e->cfg.device));
+	return LPP_OK;
+}
+
+void launch_dot_heis(lpp_engine* e, const HeisStringWork& W, const ObsHeisStringDotArgs& A, const double* bra, const double* ket, double* d_out)
+{
+	const size_t lds = obs_heis_string_lds_bytes(A.b.nlo);
+	if (e->is_complex) k_obs_string_dot_heis<true><<<W.grid, kObsBlock, lds, e->stream>>>(bra, ket, A);
+	else k_obs_string_dot_heis<false><<<W.grid, kObsBlock, lds, e->stream>>>(bra, ket, A);
+	k_reduce_final<<<1, kBlock, 0, e->stream>>>((const double*)W.part.p, W.grid, 2 * kObsStringBatch, 2 * A.ns, d_out);
+}
+
+// the workspace of the bracket kernel on sector (L; m): the runs and tables, kObsStringBatch slots, the partial sums and the results
+lpp_status dot_work_heis(lpp_engine* e, int L, int m, int64_t nstrings, HeisStringWork& W)
+{
+	lpp_status st = heis_string_work(e, L, m, kObsStringBatch, W);
+	if (st != LPP_OK) return st;
+	HIP_TRY_MEM(W.part.alloc(sizeof(double) * 2 * kObsStringBatch * (size_t)W.grid));
+	HIP_TRY_MEM(W.out.alloc(sizeof(double) * 2 * (size_t)std::max<int64_t>(nstrings, 1)));
+	return LPP_OK;
+}
+
+// result[2 s], result[2 s + 1] = re, im of conj(bra) . (string_s ket); 0 for a dead string and for one that ends in another sector (nothing launched for it)
+lpp_status many_point_heis_dev(lpp_engine* e, const StringList& S, int L, int m, const double* bra, const double* ket, double* result)
+{
+	std::vector<HeisStringPlan> plans;
+	std::vector<int> slot; // the string of each plan
+	HeisStringWork W;
+	bool ready = false;
+	int launched = 0;
+	auto flush = [&]() -> lpp_status {
+		if (plans.empty()) return LPP_OK;
+		lpp_status st = LPP_OK;
+		if (!ready) {
+			if ((st = dot_work_heis(e, L, m, S.n, W)) != LPP_OK) return st;
+			ready = true;
+		} else {
+			HIP_TRY(hipStreamSynchronize(e->stream)); // the launch that still reads the entries of the batch before
+		}
+		ObsHeisStringDotArgs A {};
+		if ((st = heis_string_slots(e, W, plans.data(), (int)plans.size(), L, m, A.b, A.src, A.low)) != LPP_OK) return st;
+		A.partial = (double*)W.part.p;
+		A.ns = (int)plans.size();
+		launch_dot_heis(e, W, A, bra, ket, (double*)W.out.p + 2 * launched);
+		HIP_TRY(hipGetLastError());
+		launched += (int)plans.size();
+		plans.clear();
+		return LPP_OK;
+	};
+	for (int s = 0; s < S.n; s++) {
+		HeisStringPlan P;
+		const int64_t o = S.off[s];
+		lpp_status st = heis_string_plan((int)(S.off[s + 1] - o), S.ops + o, S.sites + o, S.spins + o, L, m, P);
+		if (st != LPP_OK) return st;
+		result[2 * s] = result[2 * s + 1] = 0.0;
+		if (P.dead || P.m2 != m) continue; // Engine.h:382-383
+		slot.push_back(s);
+		plans.push_back(P);
+		if ((int)plans.size() == kObsStringBatch && (st = flush()) != LPP_OK) return st;
+	}
+	lpp_status st = flush();
+	if (st != LPP_OK) return st;
+	if (launched == 0) return LPP_OK;
+	std::vector<double> h(2 * (size_t)launched);
+	HIP_TRY(hipMemcpyAsync(h.data(), W.out.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	for (int k = 0; k < launched; k++) {
+		result[2 * slot[(size_t)k]] = h[2 * (size_t)k];
+		result[2 * slot[(size_t)k] + 1] = h[2 * (size_t)k + 1];
+	}
+	return LPP_OK;
+}
+
+// the checks lpp_engine_many_point_heis, its _host form and the bench share; *n = the sector's size
+lpp_status many_point_heis_front(lpp_engine* e, const char* who, bool args_ok, int conv, const StringList& S, int L, int m, int64_t* n)
+{
+	if (!args_ok) return fail(LPP_ERR_INVALID, std::string(who) + ": null argument");
+	lpp_status st = refuse_string_heis(e, who, conv);
+	if (st != LPP_OK) return st;
+	if ((st = check_list(S, who)) != LPP_OK) return st;
+	if ((*n = heis_sector_size(L, m, 0)) < 0) return fail(LPP_ERR_INVALID, std::string(who) + ": bad sites / sector (szPlusConst <= sites <= 62)");
+	return LPP_OK;
+}
+
 // hasNewParts of the basis for the host (lpp_obs_new_parts*): *has = 0 where the operator leads to no sector
 lpp_status new_parts_body(const ObsBasis& B, const std::string& who, int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t* has, int32_t* nup_new,
                           int32_t* ndown_new)
@@ -967,6 +1152,146 @@ lpp_status lpp_engine_bench_string_dot(lpp_engine* e, int32_t convention, int32_
 	});
 	if (st != LPP_OK) return st;
 	// bra read once, one ket element per string and destination it reaches (the tables stay in L2)
+	if (model_bytes) *model_bytes = (double)e->esz * ((double)n + reached);
+	return LPP_OK;
+}
+
+lpp_status lpp_obs_string_plan_heis(int32_t convention, int32_t nops, const int32_t* ops, const int32_t* sites, const int32_t* spins, const int32_t* flags, int32_t nsites,
+                                    int32_t nup, int32_t ndown, int32_t* nup_new, int32_t* dead, uint64_t* flip, uint64_t* need, uint64_t* want, uint64_t* zmask, int32_t* sign,
+                                    int32_t* low_bits, int64_t* n_dst, int64_t* action)
+{
+	(void)flags;
+	(void)ndown;
+	if (convention != LPP_STRING_MANY_POINT) return fail(LPP_ERR_INVALID, "lpp_obs_string_plan_heis: the Heisenberg basis has the many-point convention only");
+	HeisStringPlan P;
+	lpp_status st = heis_string_plan(nops, ops, sites, spins, nsites, nup, P);
+	if (st != LPP_OK) return st;
+	if (nup_new) *nup_new = P.m2;
+	if (dead) *dead = P.dead ? 1 : 0;
+	if (flip) *flip = P.flip;
+	if (need) *need = P.need;
+	if (want) *want = P.want;
+	if (zmask) *zmask = P.zmask;
+	if (sign) *sign = P.sign;
+	if (low_bits) *low_bits = P.lb;
+	if (n_dst) *n_dst = P.n_dst;
+	if (action) {
+		std::vector<ObsHeisRun> runs;
+		std::vector<uint64_t> highs;
+		std::vector<uint16_t> word, rank;
+		std::vector<int64_t> src;
+		if (!heis_string_runs(nsites, P.m2, true, runs, highs, word, rank))
+			return fail(LPP_ERR_INVALID, "lpp_obs_string_plan_heis: the sector has more than 2^22 runs of equal high part (the run table's limit)");
+		heis_string_sources(P, nsites, nup, highs, src);
+		heis_string_expand(P, runs, src, word, rank, action);
+	}
+	return LPP_OK;
+}
+
+lpp_status lpp_engine_apply_string_heis(lpp_engine* e, int32_t convention, int32_t nops, const int32_t* ops, const int32_t* sites, const int32_t* spins, const int32_t* flags,
+                                        int32_t nsites, int32_t nup, int32_t ndown, double factor_re, double factor_im, const void* d_src, void* d_dst, int32_t accumulate,
+                                        int32_t* has, int32_t* nup_new, int32_t* ndown_new)
+{
+	(void)flags;
+	(void)ndown;
+	HeisStringPlan P;
+	lpp_status st = apply_string_heis_front(e, "lpp_engine_apply_string_heis", e && has, convention, nops, ops, sites, spins, nsites, nup, P, has, nup_new, ndown_new);
+	if (st != LPP_OK) return st;
+	return apply_string_heis_dev(e, P, nsites, nup, factor_re, factor_im, d_src, d_dst, accumulate != 0);
+}
+
+lpp_status lpp_engine_apply_string_heis_host(lpp_engine* e, int32_t convention, int32_t nops, const int32_t* ops, const int32_t* sites, const int32_t* spins,
+                                             const int32_t* flags, int32_t nsites, int32_t nup, int32_t ndown, double factor_re, double factor_im, const void* src, void* dst,
+                                             int32_t accumulate, int32_t* has, int32_t* nup_new, int32_t* ndown_new)
+{
+	(void)flags;
+	(void)ndown;
+	HeisStringPlan P;
+	lpp_status st = apply_string_heis_front(e, "lpp_engine_apply_string_heis_host", e && has && src && dst, convention, nops, ops, sites, spins, nsites, nup, P, has, nup_new,
+	                                        ndown_new);
+	if (st != LPP_OK) return st;
+	return staged(e, e->esz * (size_t)P.n_src, e->esz * (size_t)P.n_dst, src, dst, accumulate, [&](const void* d_src, void* d_dst) {
+		return apply_string_heis_dev(e, P, nsites, nup, factor_re, factor_im, d_src, d_dst, accumulate != 0);
+	});
+}
+
+lpp_status lpp_engine_many_point_heis(lpp_engine* e, int32_t convention, int32_t nstrings, const int64_t* offsets, const int32_t* ops, const int32_t* sites, const int32_t* spins,
+                                      const int32_t* flags, int32_t nsites, int32_t nup, int32_t ndown, int32_t bra_state, int32_t ket_state, double* result)
+{
+	(void)ndown;
+	const char* who = "lpp_engine_many_point_heis";
+	const StringList S { nstrings, offsets, ops, sites, spins, flags };
+	int64_t n = 0;
+	lpp_status st = many_point_heis_front(e, who, e && result, convention, S, nsites, nup, &n);
+	if (st != LPP_OK) return st;
+	double *bra = nullptr, *ket = nullptr;
+	if ((st = state_ptr(e, bra_state, who, &bra)) != LPP_OK) return st;
+	if ((st = state_ptr(e, ket_state, who, &ket)) != LPP_OK) return st;
+	if (e->resident_len != n) return fail(LPP_ERR_INVALID, std::string(who) + ": (sites, szPlusConst) is not the sector of the resident states");
+	HIP_TRY(hipSetDevice(e->cfg.device));
+	return many_point_heis_dev(e, S, nsites, nup, bra, ket, result);
+}
+
+lpp_status lpp_engine_many_point_heis_host(lpp_engine* e, int32_t convention, int32_t nstrings, const int64_t* offsets, const int32_t* ops, const int32_t* sites,
+                                           const int32_t* spins, const int32_t* flags, int32_t nsites, int32_t nup, int32_t ndown, const void* bra, const void* ket, double* result)
+{
+	(void)ndown;
+	const char* who = "lpp_engine_many_point_heis_host";
+	const StringList S { nstrings, offsets, ops, sites, spins, flags };
+	int64_t n = 0;
+	lpp_status st = many_point_heis_front(e, who, e && result && bra && ket, convention, S, nsites, nup, &n);
+	if (st != LPP_OK) return st;
+	HIP_TRY(hipSetDevice(e->cfg.device));
+	const size_t bytes = e->esz * (size_t)n;
+	DevBuf db, dk;
+	HIP_TRY_MEM(hipMalloc(&db.p, bytes + 16));
+	HIP_TRY_MEM(hipMalloc(&dk.p, bytes + 16));
+	HIP_TRY(hipMemcpyAsync(db.p, bra, bytes, hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipMemcpyAsync(dk.p, ket, bytes, hipMemcpyHostToDevice, e->stream));
+	st = many_point_heis_dev(e, S, nsites, nup, (const double*)db.p, (const double*)dk.p, result);
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	return st;
+}
+
+lpp_status lpp_engine_bench_string_dot_heis(lpp_engine* e, int32_t convention, int32_t nstrings, const int64_t* offsets, const int32_t* ops, const int32_t* sites,
+                                            const int32_t* spins, const int32_t* flags, int32_t nsites, int32_t nup, int32_t ndown, int32_t warmup, int32_t iters,
+                                            double* ms_per_launch, double* model_bytes)
+{
+	(void)ndown;
+	const char* who = "lpp_engine_bench_string_dot_heis";
+	const StringList S { nstrings, offsets, ops, sites, spins, flags };
+	int64_t n = 0;
+	lpp_status st = many_point_heis_front(e, who, e && ms_per_launch && iters >= 1 && warmup >= 0, convention, S, nsites, nup, &n);
+	if (st != LPP_OK) return st;
+	if (nstrings < 1 || nstrings > kObsStringBatch) return fail(LPP_ERR_INVALID, std::string(who) + ": 1 to 8 strings (one launch)");
+	std::vector<HeisStringPlan> plans((size_t)nstrings);
+	double reached = 0;
+	for (int s = 0; s < nstrings; s++) {
+		HeisStringPlan& P = plans[(size_t)s];
+		const int64_t o = offsets[s];
+		if ((st = heis_string_plan((int)(offsets[s + 1] - o), ops + o, sites + o, spins + o, nsites, nup, P)) != LPP_OK) return st;
+		if (P.dead || P.m2 != nup) return fail(LPP_ERR_INVALID, std::string(who) + ": a string that is identically zero or leaves the sector launches nothing");
+		reached += (double)heis_string_touched(P, nsites, nup);
+	}
+	HIP_TRY(hipSetDevice(e->cfg.device));
+	const size_t bytes = e->esz * (size_t)n;
+	DevBuf db, dk;
+	HIP_TRY_MEM(hipMalloc(&db.p, bytes + 16));
+	HIP_TRY_MEM(hipMalloc(&dk.p, bytes + 16));
+	HIP_TRY(hipMemsetAsync(db.p, 0, bytes + 16, e->stream));
+	HIP_TRY(hipMemsetAsync(dk.p, 0, bytes + 16, e->stream));
+	HeisStringWork W;
+	if ((st = dot_work_heis(e, nsites, nup, nstrings, W)) != LPP_OK) return st;
+	ObsHeisStringDotArgs A {};
+	if ((st = heis_string_slots(e, W, plans.data(), nstrings, nsites, nup, A.b, A.src, A.low)) != LPP_OK) return st;
+	A.partial = (double*)W.part.p;
+	A.ns = nstrings;
+	st = timed_steps(e, warmup, iters, ms_per_launch, [&] {
+		launch_dot_heis(e, W, A, (const double*)db.p, (const double*)dk.p, (double*)W.out.p);
+		return LPP_OK;
+	});
+	if (st != LPP_OK) return st;
+	// bra read once, one ket element per string and destination it reaches (the run entries stay in L2)
 	if (model_bytes) *model_bytes = (double)e->esz * ((double)n + reached);
 	return LPP_OK;
 }

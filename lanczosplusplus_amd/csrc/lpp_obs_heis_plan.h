@@ -79,6 +79,53 @@ inline int64_t heis_run_start(uint64_t h, int hb, int lb, int k)
 	return n;
 }
 
+// the high parts of the non-empty runs of sector m2, ascending: those whose popcount leaves 0 .. lb set bits to the low part.  false: more than kHeisMaxRuns
+inline bool heis_highs(int hb, int lb, int m2, std::vector<uint64_t>& highs)
+{
+	const int p_lo = std::max(0, m2 - lb), p_hi = std::min(hb, m2);
+	int64_t nruns = 0;
+	for (int p = p_lo; p <= p_hi && nruns <= kHeisMaxRuns; p++) nruns += binom(hb, p);
+	if (nruns > kHeisMaxRuns) return false;
+	highs.clear();
+	highs.reserve((size_t)nruns);
+	if (hb <= 22) {
+		for (uint64_t h = 0; h < (1ull << hb); h++) {
+			const int p = __builtin_popcountll(h);
+			if (p >= p_lo && p <= p_hi) highs.push_back(h);
+		}
+	} else { // few of very many: class by class, then sorted
+		for (int p = p_lo; p <= p_hi; p++) {
+			uint64_t h = first_word(p);
+			for (int64_t i = 0, cnt = binom(hb, p); i < cnt; i++) {
+				highs.push_back(h);
+				if (i + 1 < cnt) h = next_word(h);
+			}
+		}
+		std::sort(highs.begin(), highs.end());
+	}
+	return true;
+}
+
+// word[base[p] + r]: the lb-bit word of popcount p and rank r; base has lb + 2 entries
+inline void heis_low_base(int lb, std::vector<int32_t>& base)
+{
+	base.assign((size_t)lb + 2, 0);
+	for (int p = 0; p <= lb; p++) base[(size_t)p + 1] = base[(size_t)p] + (int32_t)binom(lb, p);
+}
+
+// the two low tables: the lb-bit words ordered by (popcount, rank), and the rank of every lb-bit word among the words of its popcount
+inline void heis_low_tables(int lb, const std::vector<int32_t>& base, std::vector<uint16_t>& word, std::vector<uint16_t>& rank)
+{
+	word.resize((size_t)1 << lb);
+	rank.resize((size_t)1 << lb);
+	std::vector<int32_t> seen((size_t)lb + 1, 0);
+	for (uint32_t w = 0; w < (1u << lb); w++) {
+		const int p = __builtin_popcount(w);
+		rank[w] = (uint16_t)seen[(size_t)p];
+		word[(size_t)(base[(size_t)p] + seen[(size_t)p]++)] = (uint16_t)w;
+	}
+}
+
 struct ObsHeisPlan {
 	int m2 = 0, mode = HEIS_RUN, lb = 0;
 	uint32_t bit = 0;
@@ -112,29 +159,10 @@ inline bool obs_plan_heis(int op, int site, int spin, int L, int m, ObsHeisPlan&
 		P.mode = (op == LPP_OP_SPLUS) ? HEIS_FLIP_SET : (op == LPP_OP_SMINUS) ? HEIS_FLIP_CLEAR : (op == LPP_OP_SZ) ? HEIS_SZ : (spin == LPP_SPIN_UP) ? HEIS_TEST_SET : HEIS_TEST_CLEAR;
 	}
 	// the non-empty runs: high parts whose popcount leaves 0 .. lb set bits to the low part, ascending
-	const int p_lo = std::max(0, P.m2 - lb), p_hi = std::min(hb, P.m2);
-	int64_t nruns = 0;
-	for (int p = p_lo; p <= p_hi && nruns <= kHeisMaxRuns; p++) nruns += binom(hb, p);
-	if (nruns > kHeisMaxRuns) return refuse("Heisenberg observables: the sector has more than 2^22 runs of equal high part (the run table's limit)");
 	std::vector<uint64_t> highs;
-	highs.reserve((size_t)nruns);
-	if (hb <= 22) {
-		for (uint64_t h = 0; h < (1ull << hb); h++) {
-			const int p = __builtin_popcountll(h);
-			if (p >= p_lo && p <= p_hi) highs.push_back(h);
-		}
-	} else { // few of very many: class by class, then sorted
-		for (int p = p_lo; p <= p_hi; p++) {
-			uint64_t h = first_word(p);
-			for (int64_t i = 0, cnt = binom(hb, p); i < cnt; i++) {
-				highs.push_back(h);
-				if (i + 1 < cnt) h = next_word(h);
-			}
-		}
-		std::sort(highs.begin(), highs.end());
-	}
-	std::vector<int32_t> base((size_t)lb + 2, 0); // word[base[p] + r]
-	for (int p = 0; p <= lb; p++) base[(size_t)p + 1] = base[(size_t)p] + (int32_t)binom(lb, p);
+	if (!heis_highs(hb, lb, P.m2, highs)) return refuse("Heisenberg observables: the sector has more than 2^22 runs of equal high part (the run table's limit)");
+	std::vector<int32_t> base;
+	heis_low_base(lb, base);
 	P.runs.reserve(highs.size() + 1);
 	int64_t acc = 0;
 	for (const uint64_t h : highs) {
@@ -160,16 +188,7 @@ inline bool obs_plan_heis(int op, int site, int spin, int L, int m, ObsHeisPlan&
 	}
 	if (acc != P.n_dst) return refuse("Heisenberg observables: internal error, the runs do not add up to the sector");
 	P.runs.push_back(ObsHeisRun { P.n_dst, 0, 0, 0 });
-	if (P.mode != HEIS_RUN) {
-		P.word.resize((size_t)1 << lb);
-		P.rank.resize((size_t)1 << lb);
-		std::vector<int32_t> seen((size_t)lb + 1, 0);
-		for (uint32_t w = 0; w < (1u << lb); w++) {
-			const int p = __builtin_popcount(w);
-			P.rank[w] = (uint16_t)seen[(size_t)p];
-			P.word[(size_t)(base[(size_t)p] + seen[(size_t)p]++)] = (uint16_t)w;
-		}
-	}
+	if (P.mode != HEIS_RUN) heis_low_tables(lb, base, P.word, P.rank);
 	return true;
 }
 

@@ -409,63 +409,82 @@ class LanczosEngine:
         check(call(self._h, _op_id(op), site, spin, L, nup, ndown, warmup, iters, C.byref(ms), C.byref(by)))
         return ms.value, by.value
 
-    # ---- products of one-site operators: -M many-point correlations and -m measure brackets (Hubbard product basis) ------------
-    def _refuse_strings(self, who):
-        """t-J and Heisenberg engines: LPP_ERR_INVALID naming the model (their bases are a follow-up, as they were for the observables)"""
-        if self._is_tj() or self._is_heis():
-            raise _capi.LppError(_capi.LPP_ERR_INVALID, "%s: not for the %s model, operator strings are built for the Hubbard product basis"
-                                 % (who, "t-J (TjMultiOrb)" if self._is_tj() else "Heisenberg"))
+    # ---- products of one-site operators: -M many-point correlations and -m measure brackets (Hubbard product basis; basis="spin_half": S = 1/2 words) ----
+    def _refuse_strings(self, who, basis="hubbard"):
+        """t-J engines: LPP_ERR_INVALID naming the model (its basis is a follow-up).  Heisenberg engines likewise unless the caller opts into the spin
+        basis: there sz is the raw 1 - 2 bit and n reads a spin direction, so a Hubbard string carried over would silently mean something else."""
+        _string_basis(basis)
+        if self._is_tj():
+            raise _capi.LppError(_capi.LPP_ERR_INVALID, "%s: not for the t-J (TjMultiOrb) model, operator strings are built for the Hubbard product basis" % who)
+        if self._is_heis() and basis != "spin_half":
+            raise _capi.LppError(_capi.LPP_ERR_INVALID, "%s: not for the Heisenberg model, operator strings are built for the Hubbard product basis; pass "
+                                 "basis=\"spin_half\" for strings of n, sz, splus, sminus in the spin basis (sz is then the raw 1 - 2 bit = -2 S^z)" % who)
 
-    def apply_operator_string(self, ops, L, nup, ndown, src, factor=1.0, out=None, convention="many_point"):
+    def apply_operator_string(self, ops, L, nup, ndown, src, factor=1.0, out=None, convention="many_point", basis="hubbard"):
         """z (+)= factor * (the whole string applied to src) in ONE launch (lpp_engine_apply_string_host): returns (z, (nup', ndown')), z starting from `out`
-        or from zero, or (None, None) where the string leads to no sector.  ops and convention as operator_string_plan."""
-        self._refuse_strings("apply_operator_string")
-        conv, off, o, s, sp, fl = _string_arrays([ops], convention)
-        plan = operator_string_plan(ops, L, nup, ndown, convention)
-        if plan is None:
-            return None, None
+        or from zero, or (None, None) where the string leads to no sector.  ops and convention as operator_string_plan.  basis="spin_half": the S = 1/2
+        words of BasisHeisenberg (lpp_engine_apply_string_heis_host; ops as operator_string_plan_heis, nup = szPlusConst, ndown is not read, the
+        many-point convention only); a string that is identically zero returns zeros, and LppError is raised where the reference throws."""
+        self._refuse_strings("apply_operator_string", basis)
+        conv, off, o, s, sp, fl = _string_arrays([ops], _string_convention(convention, basis))
+        if basis == "spin_half":
+            plan = operator_string_plan_heis(ops, L, nup, action=False)
+            n, parts = plan["n_dst"], "%d" % plan["szPlusConst"]
+        else:
+            plan = operator_string_plan(ops, L, nup, ndown, convention)
+            if plan is None:
+                return None, None
+            n, parts = len(plan["table_up"]) * len(plan["table_down"]), "%d, %d" % (plan["nup"], plan["ndown"])
         src = np.ascontiguousarray(src, self.np_dtype)
-        if len(src) != sector_size(L, nup, ndown):
+        if len(src) != sector_size(L, nup, ndown, basis):
             raise ValueError("src does not have the length of sector (%d, %d)" % (nup, ndown))
-        n = len(plan["table_up"]) * len(plan["table_down"])
         if out is None:
             z = np.zeros(n, self.np_dtype)
         else:
             z = np.ascontiguousarray(out, self.np_dtype)
             if len(z) != n:
-                raise ValueError("out does not have the length of sector (%d, %d)" % (plan["nup"], plan["ndown"]))
+                raise ValueError("out does not have the length of sector (%s)" % parts)
         f = complex(factor)
         has, n1, n2 = C.c_int32(), C.c_int32(), C.c_int32()
-        check(self._lib.lpp_engine_apply_string_host(self._h, conv, int(off[-1]), _vp(o), _vp(s), _vp(sp), _vp(fl), L, nup, ndown, f.real, f.imag, _vp(src), _vp(z),
-                                                     int(out is not None), C.byref(has), C.byref(n1), C.byref(n2)))
+        call = getattr(self._lib, "lpp_engine_apply_string" + _OBS_SUFFIX[basis] + "_host")
+        check(call(self._h, conv, int(off[-1]), _vp(o), _vp(s), _vp(sp), _vp(fl), L, nup, ndown, f.real, f.imag, _vp(src), _vp(z), int(out is not None), C.byref(has),
+                   C.byref(n1), C.byref(n2)))
         return z, (n1.value, n2.value)
 
     def _brackets(self, res):
         return (res[:, 0] + 1j * res[:, 1]) if self.is_complex else res[:, 0].copy()
 
-    def many_point(self, strings, bra=0, ket=0, convention="many_point"):
+    def many_point(self, strings, bra=0, ket=0, convention="many_point", basis=None):
         """Engine::manyPoint (Engine.h:341-389) for a list of strings on resident states bra / ket (keep_states before lanczos): one value per string,
         conj(bra) . (O_{n-1} ... O_0 ket), the FIRST listed operator acting first.  A string is a list of (op, site, spin) or the reference's text
         "c?0?0;cdagger?1?0".  0 where a step leads to no sector (the (0,0) sector included) or the string ends in another sector; nothing is launched
         for those.  n and sz act in the sector the string has reached (the reference hands them the original sector's basis, which is ill-defined
-        once the string has left it).  8 strings share one read of bra; a value does not depend on the batch it is computed in."""
-        self._refuse_strings("many_point")
+        once the string has left it).  8 strings share one read of bra; a value does not depend on the batch it is computed in.
+        basis="spin_half", on an engine set up by assemble_heisenberg with twiceS = 1 only: strings of n, sz, splus, sminus in the S = 1/2 basis
+        (lpp_engine_many_point_heis; operator_string_plan_heis has the semantics: sz is the raw 1 - 2 bit = -2 S^z, n UP / DOWN is bit / 1 - bit).
+        Without it a Heisenberg engine is refused."""
+        self._refuse_strings("many_point", "hubbard" if basis is None else basis)
+        spin = basis == "spin_half"
+        if spin and not self._is_heis("many_point"):
+            raise _capi.LppError(_capi.LPP_ERR_INVALID, "many_point: basis=\"spin_half\" is for engines set up by assemble_heisenberg (twiceS = 1)")
         m = self._need_model("many_point")
-        conv, off, o, s, sp, fl = _string_arrays(strings, convention)
+        conv, off, o, s, sp, fl = _string_arrays(strings, _string_convention(convention, basis))
         res = np.zeros((len(off) - 1, 2))
-        check(self._lib.lpp_engine_many_point(self._h, conv, len(off) - 1, _vp(off), _vp(o), _vp(s), _vp(sp), _vp(fl), m["L"], m["nup"], m["ndown"], int(bra), int(ket), _vp(res)))
+        call = self._lib.lpp_engine_many_point_heis if spin else self._lib.lpp_engine_many_point
+        check(call(self._h, conv, len(off) - 1, _vp(off), _vp(o), _vp(s), _vp(sp), _vp(fl), m["L"], m["nup"], m["ndown"], int(bra), int(ket), _vp(res)))
         return self._brackets(res)
 
-    def many_point_of(self, strings, L, nup, ndown, bra, ket, convention="many_point"):
-        """the same for host vectors bra / ket of sector (nup, ndown) in the basis order; the engine needs no matrix"""
-        self._refuse_strings("many_point_of")
-        conv, off, o, s, sp, fl = _string_arrays(strings, convention)
+    def many_point_of(self, strings, L, nup, ndown, bra, ket, convention="many_point", basis="hubbard"):
+        """the same for host vectors bra / ket of sector (nup, ndown) in the basis order; the engine needs no matrix.  basis="spin_half": nup = szPlusConst"""
+        self._refuse_strings("many_point_of", basis)
+        conv, off, o, s, sp, fl = _string_arrays(strings, _string_convention(convention, basis))
         bra = np.ascontiguousarray(bra, self.np_dtype)
         ket = np.ascontiguousarray(ket, self.np_dtype)
-        if len(bra) != sector_size(L, nup, ndown) or len(ket) != len(bra):
+        if len(bra) != sector_size(L, nup, ndown, basis) or len(ket) != len(bra):
             raise ValueError("bra / ket do not have the length of sector (%d, %d)" % (nup, ndown))
         res = np.zeros((len(off) - 1, 2))
-        check(self._lib.lpp_engine_many_point_host(self._h, conv, len(off) - 1, _vp(off), _vp(o), _vp(s), _vp(sp), _vp(fl), L, nup, ndown, _vp(bra), _vp(ket), _vp(res)))
+        call = getattr(self._lib, "lpp_engine_many_point" + _OBS_SUFFIX[basis] + "_host")
+        check(call(self._h, conv, len(off) - 1, _vp(off), _vp(o), _vp(s), _vp(sp), _vp(fl), L, nup, ndown, _vp(bra), _vp(ket), _vp(res)))
         return self._brackets(res)
 
     def measure(self, ops, bra=0, ket=0):
@@ -475,12 +494,13 @@ class LanczosEngine:
         particle numbers raises LppError (the reference would index outside the sector)."""
         return self.many_point([ops], bra, ket, convention="measure")[0]
 
-    def bench_string_dot(self, strings, L, nup, ndown, warmup=2, iters=10, convention="many_point"):
+    def bench_string_dot(self, strings, L, nup, ndown, warmup=2, iters=10, convention="many_point", basis="hubbard"):
         """(ms per launch, bytes of the byte model) of the bracket kernel + reduction on one batch of 1 .. 8 strings, zeroed vectors"""
-        conv, off, o, s, sp, fl = _string_arrays(strings, convention)
+        _string_basis(basis)
+        conv, off, o, s, sp, fl = _string_arrays(strings, _string_convention(convention, basis))
         ms, by = C.c_double(), C.c_double()
-        check(self._lib.lpp_engine_bench_string_dot(self._h, conv, len(off) - 1, _vp(off), _vp(o), _vp(s), _vp(sp), _vp(fl), L, nup, ndown, warmup, iters,
-                                                    C.byref(ms), C.byref(by)))
+        call = getattr(self._lib, "lpp_engine_bench_string_dot" + _OBS_SUFFIX[basis])
+        check(call(self._h, conv, len(off) - 1, _vp(off), _vp(o), _vp(s), _vp(sp), _vp(fl), L, nup, ndown, warmup, iters, C.byref(ms), C.byref(by)))
         return ms.value, by.value
 
     # ---- reduced density matrix of the low `split` sites (lpp_rdm.hip) ---------------------------------------
@@ -812,6 +832,44 @@ def _string_arrays(strings, convention):
     pad = [0] if not ops else []  # (a valid pointer for an empty list)
     return (conv, np.array(off, np.int64), np.array(ops + pad, np.int32), np.array(sites + pad, np.int32), np.array(spins + pad, np.int32),
             np.array(flags + pad, np.int32))
+
+
+STRING_BASES = ("hubbard", "spin_half")
+
+
+def _string_basis(basis):
+    if basis not in STRING_BASES:
+        raise ValueError("unsupported basis %r for operator strings (one of %s)" % (basis, ", ".join(STRING_BASES)))
+
+
+def _string_convention(convention, basis):
+    """the convention as given; the spin basis has the many-point one only (RahulOperator's labels are per fermion species)"""
+    if basis == "spin_half" and convention != "many_point":
+        raise ValueError("basis=\"spin_half\" has convention=\"many_point\" only, not %r" % (convention,))
+    return convention
+
+
+def operator_string_plan_heis(ops, L, szPlusConst, action=True):
+    """The plan of a product of n, sz, splus, sminus in the S = 1/2 Heisenberg basis (lpp_obs_string_plan_heis, host only), ops = (op, site, spin) or the
+    -M text, the first acting first (Engine::manyPoint with BasisHeisenberg::getBraIndex): splus / sminus flip the site's bit where it is clear / set
+    (value 1, the spin is not read), n is bit (spin UP) or 1 - bit (DOWN), sz is 1 - 2 bit; no sign.  A dict with the final szPlusConst, dead (the
+    string is identically zero), the five words of
+        result[d] = sign * (-1)^popcount((d ^ flip) & zmask) * src[rank(d ^ flip)]   where ((d ^ flip) & need) == want,
+    lb (the cut of the word), n_dst and, with action, action[dst] = +-(src + 1) or 0 expanded through the run entries and the lookup function the
+    kernels use.  Raises where the reference throws: c / cdagger, S+ met in the all-up sector, S- met in the all-down one."""
+    lib = _capi.lib()
+    conv, off, o, s, sp, fl = _string_arrays([ops], "many_point")
+    m2, dead, sign, lb, n = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+    words = [C.c_uint64() for _ in range(4)]
+    args = (conv, int(off[-1]), _vp(o), _vp(s), _vp(sp), _vp(fl), int(L), int(szPlusConst), 0, C.byref(m2), C.byref(dead)) + tuple(C.byref(w) for w in words) + (
+        C.byref(sign), C.byref(lb), C.byref(n))
+    check(lib.lpp_obs_string_plan_heis(*args, None))
+    out = dict(szPlusConst=m2.value, dead=bool(dead.value), flip=words[0].value, need=words[1].value, want=words[2].value, zmask=words[3].value, sign=sign.value,
+               lb=lb.value, n_dst=n.value)
+    if action:
+        out["action"] = np.zeros(n.value, np.int64)
+        check(lib.lpp_obs_string_plan_heis(*args, _vp(out["action"])))
+    return out
 
 
 def operator_string_plan(ops, L, nup, ndown, convention="many_point"):

@@ -525,10 +525,12 @@ public:
 	// accModifiedState_ through the sectors of hasNewParts; 0 where a step leads to no sector or the string ends in another sector.  The whole string
 	// is ONE pass of the bracket kernel (lpp_engine_many_point), no intermediate vector.  n and sz act in the sector the string has reached (the
 	// reference's getNeededBasis hands them the original sector's basis, ill-defined once the string has left it).  Orbital 0 only.
+	// Model=Heisenberg with HeisenbergTwiceS=1: the same through lpp_engine_many_point_heis -- n, sz, splus, sminus as BasisHeisenberg::getBraIndex has them
+	// (sz is the raw 1 - 2 bit); where the reference throws (c / cdagger, S+ met in the all-up sector, S- in the all-down one) LPP_ERR_INVALID is thrown.
 	ComplexOrRealType manyPoint(const VectorSizeType& sites, const std::vector<LabeledOperatorType>& what, const VectorSizeType& spins, const VectorSizeType& orbs,
 	                            const PairType& braAndKet) const
 	{
-		lpp_engine* e = stringEngine("manyPoint");
+		lpp_engine* e = stringEngine("manyPoint", true);
 		if (what.size() != sites.size() || spins.size() != sites.size() || orbs.size() != sites.size()) throw std::runtime_error("manyPoint: sites, operators, spins and orbitals differ in number\n");
 		checkBraOrKet("ket", braAndKet.second);
 		checkBraOrKet("bra", braAndKet.first);
@@ -707,11 +709,12 @@ private:
 		return hamiltonian_->engine();
 	}
 
-	// manyPoint / measure: the Hubbard product basis only; the t-J and Heisenberg models are refused as LPP_ERR_INVALID by the model's name
-	lpp_engine* stringEngine(const char* who) const
+	// manyPoint / measure: the Hubbard product basis, and for manyPoint (heisOk) the S = 1/2 Heisenberg basis; otherwise the t-J and Heisenberg models are
+	// refused as LPP_ERR_INVALID by the model's name
+	lpp_engine* stringEngine(const char* who, bool heisOk = false) const
 	{
 		lpp_engine* e = observableEngine(who);
-		if (tjModel() || heisModel())
+		if (tjModel() || (heisModel() && !heisOk))
 			throw std::runtime_error(std::string("LPP_ERR_INVALID: ") + who + ": not for the " + (tjModel() ? "TjMultiOrb" : "Heisenberg") + " model, operator strings are built for the Hubbard product basis\n");
 		return e;
 	}
@@ -722,8 +725,9 @@ private:
 		const PairType parts = obsParts();
 		const int64_t off[2] = { 0, (int64_t)ops.size() };
 		double out[2] = { 0, 0 };
-		lppCheck(lpp_engine_many_point(e, convention, 1, off, ops.data(), sites.data(), spins.data(), flags.data(), (int32_t)model_.geometry().numberOfSites(), (int32_t)parts.first,
-		                               (int32_t)parts.second, (int32_t)braAndKet.first, (int32_t)braAndKet.second, out));
+		lppCheck((heisModel() ? lpp_engine_many_point_heis : lpp_engine_many_point)(e, convention, 1, off, ops.data(), sites.data(), spins.data(), flags.data(),
+		                                                                            (int32_t)model_.geometry().numberOfSites(), (int32_t)parts.first, (int32_t)parts.second,
+		                                                                            (int32_t)braAndKet.first, (int32_t)braAndKet.second, out));
 		if constexpr (std::is_same<ComplexOrRealType, double>::value) return out[0];
 		else return ComplexOrRealType(out[0], out[1]);
 	}

@@ -7,7 +7,8 @@
 // ComputeDensityOfStates=) into <input basename><counter>.comb (LanczosDriver1.h:81-199; Hubbard family, TjMultiOrb with Orbitals=1 and Heisenberg with HeisenbergTwiceS=1 -- where `-g sz` decomposes the reference's raw 1 - 2 bit = -2 S^z --, one GPU).  -r prints the reduced density
 // matrix of the lattice cut at a site, its eigenvectors, eigenvalues and the entanglement entropy (LanczosDriver1.h:201-206).  -M prints static many-point
 // correlations of the ground state, one "<gs|STRING|gs>=value" per comma-separated string (LanczosDriver1.h:17-45, :208-213); -m prints measure brackets,
-// "bra|meas|ket = value" (LanczosDriver1.h:69-79, Engine.h:248).  Both are for the Hubbard family on one GPU.
+// "bra|meas|ket = value" (LanczosDriver1.h:69-79, Engine.h:248).  Both are for the Hubbard family on one GPU; -M also serves Heisenberg with
+// HeisenbergTwiceS=1 (strings of n, sz, splus, sminus; sz is the raw 1 - 2 bit = -2 S^z).
 #include <getopt.h>
 #include <sys/stat.h>
 #include <unistd.h>
