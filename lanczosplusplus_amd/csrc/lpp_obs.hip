@@ -5,6 +5,7 @@
 //
 // The device side only.  Each family is one ObsBasis: how its plan is built and uploaded (a DevPlan of its own in the engine's cache) and how it is
 // launched; every entry point is one body over an ObsBasis, and the four destination-driven apply kernels go through one launch (OBS_LAUNCH).
+// Operator strings have two families (HubbardStrings, HeisStrings) under one driver and one set of entry-point bodies (STRING_ENTRY).
 // The host planners (no GPU, plain C++) are lpp_obs_plan.h (shared sector arithmetic, Hubbard), lpp_obs_tj_plan.h, lpp_obs_heis_plan.h and
 // lpp_obs_string_plan.h, for strings in the Heisenberg basis lpp_obs_heis_string_plan.h; the kernels are lpp_obs_kernels.h, lpp_obs_tj_kernels.h,
 // lpp_obs_heis_kernels.h, lpp_obs_string_kernels.h and lpp_obs_heis_string_kernels.h.
@@ -35,13 +36,6 @@ namespace {
 
 // a planner's refusal (lpp_obs_plan.h, lpp_obs_tj_plan.h, lpp_obs_heis_plan.h, lpp_obs_string_plan.h) as a status
 inline lpp_status plan_status(bool ok, const char* why) { return ok ? LPP_OK : fail(LPP_ERR_INVALID, why); }
-
-// a product of one-site operators composed into ONE pair of tables (planner: lpp_obs_string_plan.h, kernels: lpp_obs_string_kernels.h)
-lpp_status string_plan(int conv, int nops, const int32_t* ops, const int32_t* sites, const int32_t* spins, const int32_t* flags, int L, int nup, int ndn, StringPlan& P)
-{
-	const char* why = nullptr;
-	return plan_status(plan_string(conv, nops, ops, sites, spins, flags, L, nup, ndn, P, &why), why);
-}
 
 // ---- device side ---------------------------------------------------------------------------------------------------------------------
 
@@ -576,66 +570,22 @@ lpp_status spectral_body(const ObsBasis& B, const std::string& who, lpp_engine* 
 	return decomposition_device_any(sector, M.p, nsteps, a, b, stats); // (a hole-major sector engine takes the vector through its permutation)
 }
 
-// ---- operator strings on the device (Hubbard product basis) -----------------------------------------------------------------------------
-
-// t-J and Heisenberg engines set up through the Python layer or the C++ shim are refused there, by the model's name; here what the engine itself knows
-lpp_status refuse_string(const lpp_engine* e, const char* who)
-{
-	if (multi(e)) return fail(LPP_ERR_STATE, std::string(who) + ": not on a partitioned (multi-rank) engine");
-	if (e->tj.active) return fail(LPP_ERR_INVALID, std::string(who) + ": the t-J model (TjMultiOrb) is not supported, operator strings are built for the Hubbard product basis");
-	return LPP_OK;
-}
-
-inline ObsString dev_string(const StringPlan& P, const int32_t* tu, const int32_t* td)
-{
-	ObsString S { tu, td, 0, 0, P.nsz, 0 };
-	for (int k = 0; k < P.nsz; k++) ((k < 8) ? S.sz_lo : S.sz_hi) |= (uint64_t)P.sz[k] << (8 * (k & 7));
-	return S;
-}
-
-// z (+)= factor * scale * string src on device vectors in the basis order.  One launch; the tables are this call's own, so it ends with a stream sync.
-lpp_status apply_string_dev(lpp_engine* e, const StringPlan& P, int L, int nup, int ndn, double fr, double fi, const void* d_src, void* d_dst, bool acc)
-{
-	lpp_status st = check_vectors(e, fi, d_src, d_dst);
-	if (st != LPP_OK) return st;
-	const int64_t nd = P.n_up_dst * P.n_dn_dst;
-	std::vector<uint32_t> wu, wd;
-	if (P.nsz > 0) {
-		species_words(L, nup, wu);
-		species_words(L, ndn, wd);
-	}
-	const size_t ntu = P.tu.size(), ntd = P.td.size();
-	std::vector<int32_t> img(ntu + ntd + wu.size() + wd.size() + 4);
-	std::memcpy(img.data(), P.tu.data(), 4 * ntu);
-	std::memcpy(img.data() + ntu, P.td.data(), 4 * ntd);
-	if (!wu.empty()) std::memcpy(img.data() + ntu + ntd, wu.data(), 4 * wu.size());
-	if (!wd.empty()) std::memcpy(img.data() + ntu + ntd + wu.size(), wd.data(), 4 * wd.size());
-	DevBuf T;
-	HIP_TRY_MEM(hipMalloc(&T.p, 4 * img.size()));
-	HIP_TRY(hipMemcpyAsync(T.p, img.data(), 4 * img.size(), hipMemcpyHostToDevice, e->stream));
-	const int32_t* d = (const int32_t*)T.p;
-	ObsStringApplyArgs A { dev_string(P, d, d + ntu), (const uint32_t*)(d + ntu + ntd), (const uint32_t*)(d + ntu + ntd + wu.size()), P.n_up_dst, P.n_dn_dst, P.n_up_src,
-		                   fr * P.scale, fi * P.scale };
-	OBS_LAUNCH(k_obs_string_apply, e, acc, nd, 0, d_dst, d_src, A);
-	HIP_TRY(hipStreamSynchronize(e->stream));
-	return LPP_OK;
-}
-
-// what lpp_engine_apply_string and its _host form do before they launch: the plan, the new sector reported, the device set.  !P.has: nothing to launch
-lpp_status apply_string_front(lpp_engine* e, const std::string& who, bool args_ok, int conv, int nops, const int32_t* ops, const int32_t* sites, const int32_t* spins,
-                              const int32_t* flags, int L, int nup, int ndn, StringPlan& P, int32_t* has, int32_t* nup_new, int32_t* ndown_new)
-{
-	if (!args_ok) return fail(LPP_ERR_INVALID, who + ": null argument");
-	*has = 0;
-	lpp_status st = refuse_string(e, who.c_str());
-	if (st != LPP_OK) return st;
-	if ((st = string_plan(conv, nops, ops, sites, spins, flags, L, nup, ndn, P)) != LPP_OK || !P.has) return st;
-	*has = 1;
-	if (nup_new) *nup_new = P.nup2;
-	if (ndown_new) *ndown_new = P.ndn2;
-	HIP_TRY(hipSetDevice(e->cfg.device));
-	return LPP_OK;
-}
+// ---- operator strings on the device: two families, one driver -------------------------------------------------------------------------------------
+//
+// A family of strings is a struct (HubbardStrings and HeisStrings below) with
+//   Plan                                  the host plan of one string
+//   kBadSector, kNotResident, kLeaves     its wording of three refusals
+//   refuse(e, who, conv)                  what the engine or the convention rules out
+//   plan(conv, nops, ops, sites, spins, flags, L, nup, ndn, P)    its planner, the refusal as a status
+//   sector_size(L, nup, ndn)              < 0: not a sector
+//   has_sector(P)                         false: the string leads to no sector; apply reports that and launches nothing
+//   new_sector(P, &nup, &ndn), n_src(P), n_dst(P)    the sector apply reports, the lengths of its vectors
+//   apply(e, P, L, nup, ndn, fr, fi, d_src, d_dst, acc)    z (+)= factor * string src: the tables are the call's own, so it ends with a stream sync
+//   stays(P, nup, ndn)                    the bracket kernel launches for it: it is not identically zero and ends in (nup, ndn)
+//   scale(P), reached(P, L, nup)          the factor on its bracket; the destinations it reaches, for the byte model
+//   Work                                  the bracket kernel's device workspace for kObsStringBatch strings, a DotOut with
+//                                         prepare(e, L, nup, ndn, nstrings), load(e, plans, ns, L, nup, ndn) and launch(e, bra, ket, d_out)
+// Everything after the two structs is written once over F.  A third family is one more struct and one more name per STRING_ENTRY.
 
 // strings as offsets into flat arrays: string s is entries offsets[s] .. offsets[s+1]-1
 struct StringList {
@@ -652,94 +602,277 @@ lpp_status check_list(const StringList& S, const char* who)
 	return LPP_OK;
 }
 
-// The brackets of strings [first, first + count) that stay in the sector, kObsStringBatch per launch: device workspace for one batch, reused after a sync.
-struct DotWork {
-	DevBuf tabs, part, out;
-	std::vector<int32_t> img;
-	int64_t nu = 0, nd = 0;
+// what a bracket workspace of either family ends in: the partial sums of one launch over a sector of n states and the brackets of all the call's strings
+struct DotOut {
+	DevBuf part, out;
 	int grid = 1;
+	lpp_status alloc_out(const lpp_engine* e, int64_t n, int64_t nstrings)
+	{
+		grid = obs_grid(e, e->is_complex ? n : (n + 1) / 2);
+		HIP_TRY_MEM(part.alloc(sizeof(double) * 2 * kObsStringBatch * (size_t)grid));
+		HIP_TRY_MEM(out.alloc(sizeof(double) * 2 * (size_t)std::max<int64_t>(nstrings, 1)));
+		return LPP_OK;
+	}
+	// the tail of every launch: the fixed-order sum of the partials of ns strings into d_out[0 .. 2 ns)
+	void reduce(lpp_engine* e, int ns, double* d_out) const
+	{
+		k_reduce_final<<<1, kBlock, 0, e->stream>>>((const double*)part.p, grid, 2 * kObsStringBatch, 2 * ns, d_out);
+	}
 };
 
-lpp_status dot_work(lpp_engine* e, int L, int nup, int ndn, int64_t nstrings, DotWork& W)
-{
-	W.nu = binom(L, nup);
-	W.nd = binom(L, ndn);
-	const int64_t n = W.nu * W.nd, units = e->is_complex ? n : (n + 1) / 2;
-	W.grid = obs_grid(e, units);
-	const size_t per = (size_t)(W.nu + W.nd);
-	W.img.assign(per * (kObsStringBatch + 1), 0); // kObsStringBatch pairs of tables, then the two word lists
-	HIP_TRY_MEM(hipMalloc(&W.tabs.p, 4 * W.img.size()));
-	HIP_TRY_MEM(hipMalloc(&W.part.p, sizeof(double) * 2 * kObsStringBatch * (size_t)W.grid));
-	HIP_TRY_MEM(hipMalloc(&W.out.p, sizeof(double) * 2 * (size_t)std::max<int64_t>(nstrings, 1)));
-	std::vector<uint32_t> wu, wd;
-	species_words(L, nup, wu);
-	species_words(L, ndn, wd);
-	std::memcpy(W.img.data() + per * kObsStringBatch, wu.data(), 4 * wu.size());
-	std::memcpy(W.img.data() + per * kObsStringBatch + W.nu, wd.data(), 4 * wd.size());
-	return LPP_OK;
-}
+// the Hubbard product basis: a string is ONE pair of tables and up to 16 sz entries (plan and upload image: lpp_obs_string_plan.h, kernels:
+// lpp_obs_string_kernels.h)
+struct HubbardStrings {
+	typedef StringPlan Plan;
+	static constexpr const char* kBadSector = ": bad sites / sector";
+	static constexpr const char* kNotResident = ": (sites, nup, ndown) is not the sector of the resident states";
+	static constexpr const char* kLeaves = ": a string that leaves the sector launches nothing";
 
-// plans[0 .. ns) into the image and the kernel's arguments (the image is uploaded by the caller)
-ObsStringDotArgs dot_args(DotWork& W, const StringPlan* plans, int ns)
-{
-	const size_t per = (size_t)(W.nu + W.nd);
-	const int32_t* d = (const int32_t*)W.tabs.p;
-	ObsStringDotArgs A {};
-	for (int s = 0; s < ns; s++) {
-		std::memcpy(W.img.data() + per * s, plans[s].tu.data(), 4 * (size_t)W.nu);
-		std::memcpy(W.img.data() + per * s + W.nu, plans[s].td.data(), 4 * (size_t)W.nd);
-		A.s[s] = dev_string(plans[s], d + per * s, d + per * s + W.nu);
+	// t-J and Heisenberg engines set up through the Python layer or the C++ shim are refused there, by the model's name; here what the engine itself knows
+	static lpp_status refuse(const lpp_engine* e, const char* who, int)
+	{
+		if (multi(e)) return fail(LPP_ERR_STATE, std::string(who) + ": not on a partitioned (multi-rank) engine");
+		if (e->tj.active) return fail(LPP_ERR_INVALID, std::string(who) + ": the t-J model (TjMultiOrb) is not supported, operator strings are built for the Hubbard product basis");
+		return LPP_OK;
 	}
-	A.words_up = (const uint32_t*)(d + per * kObsStringBatch);
-	A.words_dn = A.words_up + W.nu;
-	A.n_up = W.nu;
-	A.n_dn = W.nd;
-	A.partial = (double*)W.part.p;
-	A.ns = ns;
-	return A;
+	static lpp_status plan(int conv, int nops, const int32_t* ops, const int32_t* sites, const int32_t* spins, const int32_t* flags, int L, int nup, int ndn, Plan& P)
+	{
+		const char* why = nullptr;
+		return plan_status(plan_string(conv, nops, ops, sites, spins, flags, L, nup, ndn, P, &why), why);
+	}
+	static int64_t sector_size(int L, int nup, int ndn) { return hubbard_sector_size(L, nup, ndn); }
+	static bool has_sector(const Plan& P) { return P.has; }
+	static void new_sector(const Plan& P, int32_t* nup, int32_t* ndn) { *nup = P.nup2, *ndn = P.ndn2; }
+	static int64_t n_src(const Plan& P) { return P.n_up_src * P.n_dn_src; }
+	static int64_t n_dst(const Plan& P) { return P.n_up_dst * P.n_dn_dst; }
+	static bool stays(const Plan& P, int nup, int ndn) { return P.has && P.nup2 == nup && P.ndn2 == ndn; } // Engine.h:364, :382-383
+	static double scale(const Plan& P) { return P.scale; }
+	static double reached(const Plan& P, int, int)
+	{
+		const auto live = [](int32_t v) { return v != 0; };
+		return (double)std::count_if(P.tu.begin(), P.tu.end(), live) * (double)std::count_if(P.td.begin(), P.td.end(), live);
+	}
+
+	// slot s of an uploaded image at d as the kernels take a string
+	static ObsString dev_string(const Plan& P, const StringImage& G, const int32_t* d, int s)
+	{
+		const StringSzWords sz = pack_sz(P);
+		return ObsString { d + G.tab_up(s), d + G.tab_dn(s), sz.lo, sz.hi, P.nsz, 0 };
+	}
+
+	// one launch, the scale folded into the factor; the word lists are uploaded only for a string with sz entries
+	static lpp_status apply(lpp_engine* e, const Plan& P, int L, int nup, int ndn, double fr, double fi, const void* d_src, void* d_dst, bool acc)
+	{
+		lpp_status st = check_vectors(e, fi, d_src, d_dst);
+		if (st != LPP_OK) return st;
+		const bool words = P.nsz > 0;
+		const StringImage G { P.n_up_dst, P.n_dn_dst, 1, words ? P.n_up_src : 0, words ? P.n_dn_src : 0 };
+		std::vector<int32_t> img;
+		const char* why = nullptr;
+		if (!string_image_begin(G, L, nup, ndn, img, &why) || !string_image_tables(G, &P, 1, img, &why)) return fail(LPP_ERR_INVALID, why);
+		DevBuf T;
+		HIP_TRY_MEM(T.alloc(4 * img.size()));
+		HIP_TRY(hipMemcpyAsync(T.p, img.data(), 4 * img.size(), hipMemcpyHostToDevice, e->stream));
+		const int32_t* d = (const int32_t*)T.p;
+		ObsStringApplyArgs A { dev_string(P, G, d, 0), (const uint32_t*)(d + G.words_up()), (const uint32_t*)(d + G.words_dn()), P.n_up_dst, P.n_dn_dst, P.n_up_src,
+			                   fr * P.scale, fi * P.scale };
+		OBS_LAUNCH(k_obs_string_apply, e, acc, n_dst(P), 0, d_dst, d_src, A);
+		HIP_TRY(hipStreamSynchronize(e->stream));
+		return LPP_OK;
+	}
+
+	// kObsStringBatch pairs of tables and the sector's two word lists in one image, uploaded whole per batch
+	struct Work : DotOut {
+		DevBuf tabs;
+		std::vector<int32_t> img;
+		StringImage G;
+		ObsStringDotArgs A;
+		lpp_status prepare(lpp_engine* e, int L, int nup, int ndn, int64_t nstrings)
+		{
+			const int64_t nu = binom(L, nup), nd = binom(L, ndn);
+			G = StringImage { nu, nd, kObsStringBatch, nu, nd };
+			const char* why = nullptr;
+			if (!string_image_begin(G, L, nup, ndn, img, &why)) return fail(LPP_ERR_INVALID, why);
+			HIP_TRY_MEM(tabs.alloc(4 * img.size()));
+			return alloc_out(e, nu * nd, nstrings);
+		}
+		lpp_status load(lpp_engine* e, const Plan* plans, int ns, int, int, int)
+		{
+			const char* why = nullptr;
+			if (!string_image_tables(G, plans, ns, img, &why)) return fail(LPP_ERR_INVALID, why);
+			const int32_t* d = (const int32_t*)tabs.p;
+			A = ObsStringDotArgs {};
+			for (int s = 0; s < ns; s++) A.s[s] = dev_string(plans[s], G, d, s);
+			A.words_up = (const uint32_t*)(d + G.words_up());
+			A.words_dn = (const uint32_t*)(d + G.words_dn());
+			A.n_up = G.ntu;
+			A.n_dn = G.ntd;
+			A.partial = (double*)part.p;
+			A.ns = ns;
+			HIP_TRY(hipMemcpyAsync(tabs.p, img.data(), 4 * img.size(), hipMemcpyHostToDevice, e->stream));
+			return LPP_OK;
+		}
+		void launch(lpp_engine* e, const double* bra, const double* ket, double* d_out) const
+		{
+			if (e->is_complex) k_obs_string_dot<true><<<grid, kObsBlock, 0, e->stream>>>(bra, ket, A);
+			else k_obs_string_dot<false><<<grid, kObsBlock, 0, e->stream>>>(bra, ket, A);
+			reduce(e, A.ns, d_out);
+		}
+	};
+};
+
+// the S = 1/2 Heisenberg basis: a string is five masks and a sign, per destination run one source entry (plan and packing:
+// lpp_obs_heis_string_plan.h, kernels: lpp_obs_heis_string_kernels.h); nup = szPlusConst, ndown is not read
+struct HeisStrings {
+	typedef HeisStringPlan Plan;
+	static constexpr const char* kBadSector = ": bad sites / sector (szPlusConst <= sites <= 62)";
+	static constexpr const char* kNotResident = ": (sites, szPlusConst) is not the sector of the resident states";
+	static constexpr const char* kLeaves = ": a string that is identically zero or leaves the sector launches nothing";
+
+	static lpp_status refuse(const lpp_engine* e, const char* who, int conv)
+	{
+		if (multi(e)) return fail(LPP_ERR_STATE, std::string(who) + ": not on a partitioned (multi-rank) engine");
+		if (e->tj.active) return fail(LPP_ERR_INVALID, std::string(who) + ": the t-J model (TjMultiOrb) is not supported, its operator strings are not built yet");
+		if (conv != LPP_STRING_MANY_POINT)
+			return fail(LPP_ERR_INVALID, std::string(who) + ": the Heisenberg basis has the many-point convention only (the labels of the measure convention are per fermion species)");
+		return LPP_OK;
+	}
+	static lpp_status plan(int, int nops, const int32_t* ops, const int32_t* sites, const int32_t* spins, const int32_t*, int L, int m, int, Plan& P)
+	{
+		const char* why = nullptr;
+		return plan_status(plan_heis_string(nops, ops, sites, spins, L, m, P, &why), why);
+	}
+	static int64_t sector_size(int L, int m, int) { return heis_sector_size(L, m, 0); }
+	static bool has_sector(const Plan&) { return true; } // (this basis has no "no sector": the plan refuses where the reference throws)
+	static void new_sector(const Plan& P, int32_t* nup, int32_t* ndn) { *nup = P.m2, *ndn = 0; }
+	static int64_t n_src(const Plan& P) { return P.n_src; }
+	static int64_t n_dst(const Plan& P) { return P.n_dst; }
+	static bool stays(const Plan& P, int m, int) { return !P.dead && P.m2 == m; } // Engine.h:382-383
+	static double scale(const Plan&) { return 1.0; }
+	static double reached(const Plan& P, int L, int m) { return (double)heis_string_touched(P, L, m); }
+
+	// one launch; none for a dead string: z = 0 or z untouched
+	static lpp_status apply(lpp_engine* e, const Plan& P, int L, int m, int, double fr, double fi, const void* d_src, void* d_dst, bool acc)
+	{
+		lpp_status st = check_vectors(e, fi, d_src, d_dst);
+		if (st != LPP_OK) return st;
+		if (P.dead) {
+			if (!acc) HIP_TRY(hipMemsetAsync(d_dst, 0, e->esz * (size_t)P.n_dst, e->stream));
+			HIP_TRY(hipStreamSynchronize(e->stream));
+			return LPP_OK;
+		}
+		Work W;
+		if ((st = W.sector(e, L, P.m2, 1)) != LPP_OK) return st;
+		ObsHeisStringApplyArgs A {};
+		if ((st = W.fill(e, &P, 1, L, m, A.b, &A.src, &A.low)) != LPP_OK) return st;
+		A.fr = fr;
+		A.fi = fi;
+		OBS_LAUNCH(k_obs_string_apply_heis, e, acc, P.n_dst, obs_heis_string_lds_bytes(A.b.nlo), d_dst, d_src, A);
+		HIP_TRY(hipStreamSynchronize(e->stream));
+		return LPP_OK;
+	}
+
+	// One destination sector on the device: its runs, the two low tables and room for `slots` strings' entries per run.  The host copies stay until the
+	// struct goes: the uploads are asynchronous.
+	struct Work : DotOut {
+		DevBuf runs, low, src;
+		std::vector<ObsHeisRun> h_runs;
+		std::vector<uint64_t> highs;
+		std::vector<uint16_t> h_low; // word, then rank
+		std::vector<int64_t> h_src;
+		int64_t nruns = 0, n_dst = 0;
+		int nlo = 0;
+		ObsHeisStringDotArgs A;
+		lpp_status sector(lpp_engine* e, int L, int m2, int slots)
+		{
+			std::vector<uint16_t> rank;
+			if (!heis_string_runs(L, m2, true, h_runs, highs, h_low, rank))
+				return fail(LPP_ERR_INVALID, "Heisenberg operator string: the sector has more than 2^22 runs of equal high part (the run table's limit)");
+			nruns = (int64_t)highs.size();
+			n_dst = h_runs.back().dst0;
+			nlo = (int)h_low.size();
+			h_low.insert(h_low.end(), rank.begin(), rank.end());
+			h_src.assign((size_t)slots * (size_t)nruns, 0);
+			HIP_TRY_MEM(runs.alloc(sizeof(ObsHeisRun) * h_runs.size()));
+			HIP_TRY_MEM(low.alloc(sizeof(uint16_t) * h_low.size()));
+			HIP_TRY_MEM(src.alloc(sizeof(int64_t) * h_src.size()));
+			HIP_TRY(hipMemcpyAsync(runs.p, h_runs.data(), sizeof(ObsHeisRun) * h_runs.size(), hipMemcpyHostToDevice, e->stream));
+			HIP_TRY(hipMemcpyAsync(low.p, h_low.data(), sizeof(uint16_t) * h_low.size(), hipMemcpyHostToDevice, e->stream));
+			return LPP_OK;
+		}
+		// plans[0 .. ns) (none dead) of source sector m packed into the slots and uploaded; B.nlo = 0 where none of them has low-part work
+		lpp_status fill(lpp_engine* e, const Plan* plans, int ns, int L, int m, ObsHeisStringBase& B, const int64_t** d_src, ObsHeisStringLow* d_low)
+		{
+			bool low_work = false;
+			const char* why = nullptr;
+			if (!heis_string_pack(plans, ns, L, m, highs, h_src, d_low, &low_work, &why)) return fail(LPP_ERR_INVALID, why);
+			for (int s = 0; s < ns; s++) d_src[s] = (const int64_t*)src.p + (size_t)s * (size_t)nruns;
+			HIP_TRY(hipMemcpyAsync(src.p, h_src.data(), sizeof(int64_t) * (size_t)ns * (size_t)nruns, hipMemcpyHostToDevice, e->stream));
+			B = ObsHeisStringBase { (const ObsHeisRun*)runs.p, (const uint16_t*)low.p, (const uint16_t*)low.p + nlo, nruns, n_dst, low_work ? nlo : 0 };
+			return LPP_OK;
+		}
+		lpp_status prepare(lpp_engine* e, int L, int m, int, int64_t nstrings)
+		{
+			lpp_status st = sector(e, L, m, kObsStringBatch);
+			return st != LPP_OK ? st : alloc_out(e, n_dst, nstrings);
+		}
+		lpp_status load(lpp_engine* e, const Plan* plans, int ns, int L, int m, int)
+		{
+			A = ObsHeisStringDotArgs {};
+			A.partial = (double*)part.p;
+			A.ns = ns;
+			return fill(e, plans, ns, L, m, A.b, A.src, A.low);
+		}
+		void launch(lpp_engine* e, const double* bra, const double* ket, double* d_out) const
+		{
+			const size_t lds = obs_heis_string_lds_bytes(A.b.nlo);
+			if (e->is_complex) k_obs_string_dot_heis<true><<<grid, kObsBlock, lds, e->stream>>>(bra, ket, A);
+			else k_obs_string_dot_heis<false><<<grid, kObsBlock, lds, e->stream>>>(bra, ket, A);
+			reduce(e, A.ns, d_out);
+		}
+	};
+};
+
+// string s of a list planned on sector (L; nup, ndn)
+template <typename F> lpp_status plan_of(int conv, const StringList& S, int s, int L, int nup, int ndn, typename F::Plan& P)
+{
+	const int64_t o = S.off[s];
+	return F::plan(conv, (int)(S.off[s + 1] - o), S.ops + o, S.sites + o, S.spins + o, S.flags ? S.flags + o : nullptr, L, nup, ndn, P);
 }
 
-void launch_dot(lpp_engine* e, const DotWork& W, const ObsStringDotArgs& A, const double* bra, const double* ket, double* d_out)
+// result[2 s], result[2 s + 1] = re, im of conj(bra) . (string_s ket); 0 for a string the family does not launch (no sector, identically zero, or it
+// ends in another sector).  kObsStringBatch strings per launch; the workspace of one batch is reused after a sync; one readback.
+template <typename F> lpp_status many_point_dev(lpp_engine* e, int conv, const StringList& S, int L, int nup, int ndn, const double* bra, const double* ket, double* result)
 {
-	if (e->is_complex) k_obs_string_dot<true><<<W.grid, kObsBlock, 0, e->stream>>>(bra, ket, A);
-	else k_obs_string_dot<false><<<W.grid, kObsBlock, 0, e->stream>>>(bra, ket, A);
-	k_reduce_final<<<1, kBlock, 0, e->stream>>>((const double*)W.part.p, W.grid, 2 * kObsStringBatch, 2 * A.ns, d_out);
-}
-
-// result[2 s], result[2 s + 1] = re, im of conj(bra) . (string_s ket); 0 where the string leads to no sector or ends in another one (nothing launched for it)
-lpp_status many_point_dev(lpp_engine* e, int conv, const StringList& S, int L, int nup, int ndn, const double* bra, const double* ket, double* result)
-{
-	std::vector<StringPlan> plans;
-	std::vector<int> slot; // the string of each plan
-	DotWork W;
+	std::vector<typename F::Plan> plans;
+	std::vector<int> slot; // the string of each launched plan
+	std::vector<double> scale;
+	typename F::Work W;
 	bool ready = false;
-	std::vector<double> scale((size_t)S.n, 0.0);
 	int launched = 0;
 	auto flush = [&]() -> lpp_status {
 		if (plans.empty()) return LPP_OK;
+		lpp_status st = LPP_OK;
 		if (!ready) {
-			lpp_status st = dot_work(e, L, nup, ndn, S.n, W);
-			if (st != LPP_OK) return st;
+			if ((st = W.prepare(e, L, nup, ndn, S.n)) != LPP_OK) return st;
 			ready = true;
 		} else {
-			HIP_TRY(hipStreamSynchronize(e->stream)); // the launch that still reads the tables of the batch before
+			HIP_TRY(hipStreamSynchronize(e->stream)); // the launch that still reads the uploads of the batch before
 		}
-		const ObsStringDotArgs A = dot_args(W, plans.data(), (int)plans.size());
-		HIP_TRY(hipMemcpyAsync(W.tabs.p, W.img.data(), 4 * W.img.size(), hipMemcpyHostToDevice, e->stream));
-		launch_dot(e, W, A, bra, ket, (double*)W.out.p + 2 * launched);
+		if ((st = W.load(e, plans.data(), (int)plans.size(), L, nup, ndn)) != LPP_OK) return st;
+		W.launch(e, bra, ket, (double*)W.out.p + 2 * launched);
 		HIP_TRY(hipGetLastError());
 		launched += (int)plans.size();
 		plans.clear();
 		return LPP_OK;
 	};
 	for (int s = 0; s < S.n; s++) {
-		StringPlan P;
-		const int64_t o = S.off[s];
-		lpp_status st = string_plan(conv, (int)(S.off[s + 1] - o), S.ops + o, S.sites + o, S.spins + o, S.flags ? S.flags + o : nullptr, L, nup, ndn, P);
+		typename F::Plan P;
+		lpp_status st = plan_of<F>(conv, S, s, L, nup, ndn, P);
 		if (st != LPP_OK) return st;
 		result[2 * s] = result[2 * s + 1] = 0.0;
-		if (!P.has || P.nup2 != nup || P.ndn2 != ndn) continue; // Engine.h:364, :382-383
-		scale[(size_t)slot.size()] = P.scale;
+		if (!F::stays(P, nup, ndn)) continue;
+		scale.push_back(F::scale(P));
 		slot.push_back(s);
 		plans.push_back(std::move(P));
 		if ((int)plans.size() == kObsStringBatch && (st = flush()) != LPP_OK) return st;
@@ -750,193 +883,125 @@ lpp_status many_point_dev(lpp_engine* e, int conv, const StringList& S, int L, i
 	std::vector<double> h(2 * (size_t)launched);
 	HIP_TRY(hipMemcpyAsync(h.data(), W.out.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, e->stream));
 	HIP_TRY(hipStreamSynchronize(e->stream));
-	for (int k = 0; k < launched; k++) {
-		result[2 * slot[(size_t)k]] = scale[(size_t)k] * h[2 * (size_t)k];
-		result[2 * slot[(size_t)k] + 1] = scale[(size_t)k] * h[2 * (size_t)k + 1];
+	for (size_t k = 0; k < (size_t)launched; k++) {
+		result[2 * slot[k]] = scale[k] * h[2 * k];
+		result[2 * slot[k] + 1] = scale[k] * h[2 * k + 1];
 	}
 	return LPP_OK;
 }
 
-// ---- operator strings on the device (S = 1/2 Heisenberg basis; plan: lpp_obs_heis_string_plan.h, kernels: lpp_obs_heis_string_kernels.h) -------
-
-lpp_status refuse_string_heis(const lpp_engine* e, const char* who, int conv)
+// the checks the resident-state form, the host-vector form and the bench share, in this order; *n = the sector's size.  The bench says "bad argument"
+// and takes one launch's strings
+template <typename F> lpp_status many_point_front(lpp_engine* e, const char* who, bool args_ok, bool bench, int conv, const StringList& S, int L, int nup, int ndn, int64_t* n)
 {
-	if (multi(e)) return fail(LPP_ERR_STATE, std::string(who) + ": not on a partitioned (multi-rank) engine");
-	if (e->tj.active) return fail(LPP_ERR_INVALID, std::string(who) + ": the t-J model (TjMultiOrb) is not supported, its operator strings are not built yet");
-	if (conv != LPP_STRING_MANY_POINT)
-		return fail(LPP_ERR_INVALID, std::string(who) + ": the Heisenberg basis has the many-point convention only (the labels of the measure convention are per fermion species)");
-	return LPP_OK;
-}
-
-lpp_status heis_string_plan(int nops, const int32_t* ops, const int32_t* sites, const int32_t* spins, int L, int m, HeisStringPlan& P)
-{
-	const char* why = nullptr;
-	return plan_status(plan_heis_string(nops, ops, sites, spins, L, m, P, &why), why);
-}
-
-// One destination sector on the device: its runs, the two low tables and room for `slots` strings' entries per run.  The host copies stay until the
-// struct goes: the uploads are asynchronous.
-struct HeisStringWork {
-	DevBuf runs, low, src, part, out;
-	std::vector<ObsHeisRun> h_runs;
-	std::vector<uint64_t> highs;
-	std::vector<uint16_t> h_low; // word, then rank
-	std::vector<int64_t> h_src, one;
-	int64_t nruns = 0, n_dst = 0;
-	int nlo = 0, grid = 1;
-};
-
-lpp_status heis_string_work(lpp_engine* e, int L, int m2, int slots, HeisStringWork& W)
-{
-	std::vector<uint16_t> word, rank;
-	if (!heis_string_runs(L, m2, true, W.h_runs, W.highs, word, rank))
-		return fail(LPP_ERR_INVALID, "Heisenberg operator string: the sector has more than 2^22 runs of equal high part (the run table's limit)");
-	W.nruns = (int64_t)W.highs.size();
-	W.n_dst = W.h_runs.back().dst0;
-	W.nlo = (int)word.size();
-	W.grid = obs_grid(e, e->is_complex ? W.n_dst : (W.n_dst + 1) / 2);
-	W.h_low = word;
-	W.h_low.insert(W.h_low.end(), rank.begin(), rank.end());
-	W.h_src.assign((size_t)slots * (size_t)W.nruns, 0);
-	HIP_TRY_MEM(W.runs.alloc(sizeof(ObsHeisRun) * W.h_runs.size()));
-	HIP_TRY_MEM(W.low.alloc(sizeof(uint16_t) * W.h_low.size()));
-	HIP_TRY_MEM(W.src.alloc(sizeof(int64_t) * W.h_src.size()));
-	HIP_TRY(hipMemcpyAsync(W.runs.p, W.h_runs.data(), sizeof(ObsHeisRun) * W.h_runs.size(), hipMemcpyHostToDevice, e->stream));
-	HIP_TRY(hipMemcpyAsync(W.low.p, W.h_low.data(), sizeof(uint16_t) * W.h_low.size(), hipMemcpyHostToDevice, e->stream));
-	return LPP_OK;
-}
-
-// plans[0 .. ns) (none dead) of source sector m into the slots of W and uploaded; B.nlo = 0 where none of them has low-part work
-lpp_status heis_string_slots(lpp_engine* e, HeisStringWork& W, const HeisStringPlan* plans, int ns, int L, int m, ObsHeisStringBase& B, const int64_t** src, ObsHeisStringLow* low)
-{
-	bool low_work = false;
-	for (int s = 0; s < ns; s++) {
-		heis_string_sources(plans[s], L, m, W.highs, W.one);
-		std::copy(W.one.begin(), W.one.end(), W.h_src.begin() + (size_t)s * (size_t)W.nruns);
-		src[s] = (const int64_t*)W.src.p + (size_t)s * (size_t)W.nruns;
-		low[s] = plans[s].low();
-		low_work = low_work || obs_heis_string_low_work(low[s]);
-	}
-	HIP_TRY(hipMemcpyAsync(W.src.p, W.h_src.data(), sizeof(int64_t) * (size_t)ns * (size_t)W.nruns, hipMemcpyHostToDevice, e->stream));
-	B = ObsHeisStringBase { (const ObsHeisRun*)W.runs.p, (const uint16_t*)W.low.p, (const uint16_t*)W.low.p + W.nlo, W.nruns, W.n_dst, low_work ? W.nlo : 0 };
-	return LPP_OK;
-}
-
-// z (+)= factor * string src on device vectors in the basis order.  One launch (none for a dead string: z = 0 or z untouched); the tables are this
-// call's own, so it ends with a stream sync.
-lpp_status apply_string_heis_dev(lpp_engine* e, const HeisStringPlan& P, int L, int m, double fr, double fi, const void* d_src, void* d_dst, bool acc)
-{
-	lpp_status st = check_vectors(e, fi, d_src, d_dst);
-	if (st != LPP_OK) return st;
-	if (P.dead) {
-		if (!acc) HIP_TRY(hipMemsetAsync(d_dst, 0, e->esz * (size_t)P.n_dst, e->stream));
-		HIP_TRY(hipStreamSynchronize(e->stream));
-		return LPP_OK;
-	}
-	HeisStringWork W;
-	if ((st = heis_string_work(e, L, P.m2, 1, W)) != LPP_OK) return st;
-	ObsHeisStringApplyArgs A {};
-	if ((st = heis_string_slots(e, W, &P, 1, L, m, A.b, &A.src, &A.low)) != LPP_OK) return st;
-	A.fr = fr;
-	A.fi = fi;
-	OBS_LAUNCH(k_obs_string_apply_heis, e, acc, P.n_dst, obs_heis_string_lds_bytes(A.b.nlo), d_dst, d_src, A);
-	HIP_TRY(hipStreamSynchronize(e->stream));
-	return LPP_OK;
-}
-
-// what lpp_engine_apply_string_heis and its _host form do before they launch: the refusals, the plan, the new sector reported, the device set
-lpp_status apply_string_heis_front(lpp_engine* e, const std::string& who, bool args_ok, int conv, int nops, const int32_t* ops, const int32_t* sites, const int32_t* spins,
-                                   int L, int m, HeisStringPlan& P, int32_t* has, int32_t* nup_new, int32_t* ndown_new)
-{
-	if (!args_ok) return fail(LPP_ERR_INVALID, who + ": null argument");
-	*has = 0;
-	lpp_status st = refuse_string_heis(e, who.c_str(), conv);
-	if (st != LPP_OK) return st;
-	if ((st = heis_string_plan(nops, ops, sites, spins, L, m, P)) != LPP_OK) return st;
-	*has = 1; // (this basis has no "no sector": the plan refuses where the reference throws)
-	if (nup_new) *nup_new = P.m2;
-	if (ndown_new) *ndown_new = 0;
-	HIP_TRY(hipSetDevice(e->cfg.device));
-	return LPP_OK;
-}
-
-void launch_dot_heis(lpp_engine* e, const HeisStringWork& W, const ObsHeisStringDotArgs& A, const double* bra, const double* ket, double* d_out)
-{
-	const size_t lds = obs_heis_string_lds_bytes(A.b.nlo);
-	if (e->is_complex) k_obs_string_dot_heis<true><<<W.grid, kObsBlock, lds, e->stream>>>(bra, ket, A);
-	else k_obs_string_dot_heis<false><<<W.grid, kObsBlock, lds, e->stream>>>(bra, ket, A);
-	k_reduce_final<<<1, kBlock, 0, e->stream>>>((const double*)W.part.p, W.grid, 2 * kObsStringBatch, 2 * A.ns, d_out);
-}
-
-// the workspace of the bracket kernel on sector (L; m): the runs and tables, kObsStringBatch slots, the partial sums and the results
-lpp_status dot_work_heis(lpp_engine* e, int L, int m, int64_t nstrings, HeisStringWork& W)
-{
-	lpp_status st = heis_string_work(e, L, m, kObsStringBatch, W);
-	if (st != LPP_OK) return st;
-	HIP_TRY_MEM(W.part.alloc(sizeof(double) * 2 * kObsStringBatch * (size_t)W.grid));
-	HIP_TRY_MEM(W.out.alloc(sizeof(double) * 2 * (size_t)std::max<int64_t>(nstrings, 1)));
-	return LPP_OK;
-}
-
-// result[2 s], result[2 s + 1] = re, im of conj(bra) . (string_s ket); 0 for a dead string and for one that ends in another sector (nothing launched for it)
-lpp_status many_point_heis_dev(lpp_engine* e, const StringList& S, int L, int m, const double* bra, const double* ket, double* result)
-{
-	std::vector<HeisStringPlan> plans;
-	std::vector<int> slot; // the string of each plan
-	HeisStringWork W;
-	bool ready = false;
-	int launched = 0;
-	auto flush = [&]() -> lpp_status {
-		if (plans.empty()) return LPP_OK;
-		lpp_status st = LPP_OK;
-		if (!ready) {
-			if ((st = dot_work_heis(e, L, m, S.n, W)) != LPP_OK) return st;
-			ready = true;
-		} else {
-			HIP_TRY(hipStreamSynchronize(e->stream)); // the launch that still reads the entries of the batch before
-		}
-		ObsHeisStringDotArgs A {};
-		if ((st = heis_string_slots(e, W, plans.data(), (int)plans.size(), L, m, A.b, A.src, A.low)) != LPP_OK) return st;
-		A.partial = (double*)W.part.p;
-		A.ns = (int)plans.size();
-		launch_dot_heis(e, W, A, bra, ket, (double*)W.out.p + 2 * launched);
-		HIP_TRY(hipGetLastError());
-		launched += (int)plans.size();
-		plans.clear();
-		return LPP_OK;
-	};
-	for (int s = 0; s < S.n; s++) {
-		HeisStringPlan P;
-		const int64_t o = S.off[s];
-		lpp_status st = heis_string_plan((int)(S.off[s + 1] - o), S.ops + o, S.sites + o, S.spins + o, L, m, P);
-		if (st != LPP_OK) return st;
-		result[2 * s] = result[2 * s + 1] = 0.0;
-		if (P.dead || P.m2 != m) continue; // Engine.h:382-383
-		slot.push_back(s);
-		plans.push_back(P);
-		if ((int)plans.size() == kObsStringBatch && (st = flush()) != LPP_OK) return st;
-	}
-	lpp_status st = flush();
-	if (st != LPP_OK) return st;
-	if (launched == 0) return LPP_OK;
-	std::vector<double> h(2 * (size_t)launched);
-	HIP_TRY(hipMemcpyAsync(h.data(), W.out.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, e->stream));
-	HIP_TRY(hipStreamSynchronize(e->stream));
-	for (int k = 0; k < launched; k++) {
-		result[2 * slot[(size_t)k]] = h[2 * (size_t)k];
-		result[2 * slot[(size_t)k] + 1] = h[2 * (size_t)k + 1];
-	}
-	return LPP_OK;
-}
-
-// the checks lpp_engine_many_point_heis, its _host form and the bench share; *n = the sector's size
-lpp_status many_point_heis_front(lpp_engine* e, const char* who, bool args_ok, int conv, const StringList& S, int L, int m, int64_t* n)
-{
-	if (!args_ok) return fail(LPP_ERR_INVALID, std::string(who) + ": null argument");
-	lpp_status st = refuse_string_heis(e, who, conv);
+	if (!args_ok) return fail(LPP_ERR_INVALID, std::string(who) + (bench ? ": bad argument" : ": null argument"));
+	lpp_status st = F::refuse(e, who, conv);
 	if (st != LPP_OK) return st;
 	if ((st = check_list(S, who)) != LPP_OK) return st;
-	if ((*n = heis_sector_size(L, m, 0)) < 0) return fail(LPP_ERR_INVALID, std::string(who) + ": bad sites / sector (szPlusConst <= sites <= 62)");
+	if (bench && (S.n < 1 || S.n > kObsStringBatch)) return fail(LPP_ERR_INVALID, std::string(who) + ": 1 to 8 strings (one launch)");
+	if ((*n = F::sector_size(L, nup, ndn)) < 0) return fail(LPP_ERR_INVALID, std::string(who) + F::kBadSector);
+	return LPP_OK;
+}
+
+// bra and ket of `bytes` bytes on the device, 16 spare bytes each: copies of two host vectors, or zeros where there are none
+lpp_status stage_pair(lpp_engine* e, size_t bytes, const void* bra, const void* ket, DevBuf& db, DevBuf& dk)
+{
+	HIP_TRY_MEM(db.alloc(bytes + 16));
+	HIP_TRY_MEM(dk.alloc(bytes + 16));
+	if (bra) {
+		HIP_TRY(hipMemcpyAsync(db.p, bra, bytes, hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(dk.p, ket, bytes, hipMemcpyHostToDevice, e->stream));
+	} else {
+		HIP_TRY(hipMemsetAsync(db.p, 0, bytes + 16, e->stream));
+		HIP_TRY(hipMemsetAsync(dk.p, 0, bytes + 16, e->stream));
+	}
+	return LPP_OK;
+}
+
+// lpp_engine_apply_string* (host == false: device vectors) and lpp_engine_apply_string*_host (host vectors staged around the launch)
+template <typename F>
+lpp_status apply_string_body(const std::string& who, bool host, lpp_engine* e, int32_t conv, int32_t nops, const int32_t* ops, const int32_t* sites, const int32_t* spins,
+                             const int32_t* flags, int32_t L, int32_t nup, int32_t ndn, double fr, double fi, const void* src, void* dst, int32_t accumulate, int32_t* has,
+                             int32_t* nup_new, int32_t* ndown_new)
+{
+	if (!e || !has || (host && (!src || !dst))) return fail(LPP_ERR_INVALID, who + ": null argument");
+	*has = 0;
+	lpp_status st = F::refuse(e, who.c_str(), conv);
+	if (st != LPP_OK) return st;
+	typename F::Plan P;
+	if ((st = F::plan(conv, nops, ops, sites, spins, flags, L, nup, ndn, P)) != LPP_OK || !F::has_sector(P)) return st;
+	*has = 1;
+	int32_t n1 = 0, n2 = 0;
+	F::new_sector(P, &n1, &n2);
+	if (nup_new) *nup_new = n1;
+	if (ndown_new) *ndown_new = n2;
+	HIP_TRY(hipSetDevice(e->cfg.device));
+	const auto run = [&](const void* d_src, void* d_dst) { return F::apply(e, P, L, nup, ndn, fr, fi, d_src, d_dst, accumulate != 0); };
+	return host ? staged(e, e->esz * (size_t)F::n_src(P), e->esz * (size_t)F::n_dst(P), src, dst, accumulate, run) : run(src, dst);
+}
+
+template <typename F>
+lpp_status many_point_body(const char* who, lpp_engine* e, int32_t conv, int32_t nstrings, const int64_t* offsets, const int32_t* ops, const int32_t* sites, const int32_t* spins,
+                           const int32_t* flags, int32_t L, int32_t nup, int32_t ndn, int32_t bra_state, int32_t ket_state, double* result)
+{
+	const StringList S { nstrings, offsets, ops, sites, spins, flags };
+	int64_t n = 0;
+	lpp_status st = many_point_front<F>(e, who, e && result, false, conv, S, L, nup, ndn, &n);
+	if (st != LPP_OK) return st;
+	double *bra = nullptr, *ket = nullptr;
+	if ((st = state_ptr(e, bra_state, who, &bra)) != LPP_OK) return st;
+	if ((st = state_ptr(e, ket_state, who, &ket)) != LPP_OK) return st;
+	if (e->resident_len != n) return fail(LPP_ERR_INVALID, std::string(who) + F::kNotResident);
+	HIP_TRY(hipSetDevice(e->cfg.device));
+	return many_point_dev<F>(e, conv, S, L, nup, ndn, bra, ket, result);
+}
+
+template <typename F>
+lpp_status many_point_host_body(const char* who, lpp_engine* e, int32_t conv, int32_t nstrings, const int64_t* offsets, const int32_t* ops, const int32_t* sites,
+                                const int32_t* spins, const int32_t* flags, int32_t L, int32_t nup, int32_t ndn, const void* bra, const void* ket, double* result)
+{
+	const StringList S { nstrings, offsets, ops, sites, spins, flags };
+	int64_t n = 0;
+	lpp_status st = many_point_front<F>(e, who, e && result && bra && ket, false, conv, S, L, nup, ndn, &n);
+	if (st != LPP_OK) return st;
+	HIP_TRY(hipSetDevice(e->cfg.device));
+	DevBuf db, dk;
+	if ((st = stage_pair(e, e->esz * (size_t)n, bra, ket, db, dk)) != LPP_OK) return st;
+	st = many_point_dev<F>(e, conv, S, L, nup, ndn, (const double*)db.p, (const double*)dk.p, result);
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	return st;
+}
+
+// the bracket kernel and its reduction on one batch of strings that all stay in the sector, zeroed vectors
+template <typename F>
+lpp_status bench_string_dot_body(const char* who, lpp_engine* e, int32_t conv, int32_t nstrings, const int64_t* offsets, const int32_t* ops, const int32_t* sites,
+                                 const int32_t* spins, const int32_t* flags, int32_t L, int32_t nup, int32_t ndn, int32_t warmup, int32_t iters, double* ms_per_launch,
+                                 double* model_bytes)
+{
+	const StringList S { nstrings, offsets, ops, sites, spins, flags };
+	int64_t n = 0;
+	lpp_status st = many_point_front<F>(e, who, e && ms_per_launch && iters >= 1 && warmup >= 0, true, conv, S, L, nup, ndn, &n);
+	if (st != LPP_OK) return st;
+	std::vector<typename F::Plan> plans((size_t)nstrings);
+	double reached = 0;
+	for (int s = 0; s < nstrings; s++) {
+		if ((st = plan_of<F>(conv, S, s, L, nup, ndn, plans[(size_t)s])) != LPP_OK) return st;
+		if (!F::stays(plans[(size_t)s], nup, ndn)) return fail(LPP_ERR_INVALID, std::string(who) + F::kLeaves);
+		reached += F::reached(plans[(size_t)s], L, nup);
+	}
+	HIP_TRY(hipSetDevice(e->cfg.device));
+	DevBuf db, dk;
+	if ((st = stage_pair(e, e->esz * (size_t)n, nullptr, nullptr, db, dk)) != LPP_OK) return st;
+	typename F::Work W;
+	if ((st = W.prepare(e, L, nup, ndn, nstrings)) != LPP_OK) return st;
+	if ((st = W.load(e, plans.data(), nstrings, L, nup, ndn)) != LPP_OK) return st;
+	st = timed_steps(e, warmup, iters, ms_per_launch, [&] {
+		W.launch(e, (const double*)db.p, (const double*)dk.p, (double*)W.out.p);
+		return LPP_OK;
+	});
+	if (st != LPP_OK) return st;
+	// bra read once, one ket element per string and destination it reaches (the tables or run entries stay in L2)
+	if (model_bytes) *model_bytes = (double)e->esz * ((double)n + reached);
 	return LPP_OK;
 }
 
@@ -1029,7 +1094,7 @@ lpp_status lpp_obs_string_plan(int32_t convention, int32_t nops, const int32_t* 
 	if (!has) return fail(LPP_ERR_INVALID, "lpp_obs_string_plan: null argument");
 	*has = 0;
 	StringPlan P;
-	lpp_status st = string_plan(convention, nops, ops, sites, spins, flags, nsites, nup, ndown, P);
+	lpp_status st = HubbardStrings::plan(convention, nops, ops, sites, spins, flags, nsites, nup, ndown, P);
 	if (st != LPP_OK) return st;
 	*has = P.has ? 1 : 0;
 	if (!P.has) return LPP_OK;
@@ -1050,121 +1115,14 @@ lpp_status lpp_obs_string_plan(int32_t convention, int32_t nops, const int32_t* 
 	return LPP_OK;
 }
 
-lpp_status lpp_engine_apply_string(lpp_engine* e, int32_t convention, int32_t nops, const int32_t* ops, const int32_t* sites, const int32_t* spins, const int32_t* flags,
-                                   int32_t nsites, int32_t nup, int32_t ndown, double factor_re, double factor_im, const void* d_src, void* d_dst, int32_t accumulate,
-                                   int32_t* has, int32_t* nup_new, int32_t* ndown_new)
-{
-	StringPlan P;
-	lpp_status st = apply_string_front(e, "lpp_engine_apply_string", e && has, convention, nops, ops, sites, spins, flags, nsites, nup, ndown, P, has, nup_new, ndown_new);
-	if (st != LPP_OK || !P.has) return st;
-	return apply_string_dev(e, P, nsites, nup, ndown, factor_re, factor_im, d_src, d_dst, accumulate != 0);
-}
-
-lpp_status lpp_engine_apply_string_host(lpp_engine* e, int32_t convention, int32_t nops, const int32_t* ops, const int32_t* sites, const int32_t* spins, const int32_t* flags,
-                                        int32_t nsites, int32_t nup, int32_t ndown, double factor_re, double factor_im, const void* src, void* dst, int32_t accumulate,
-                                        int32_t* has, int32_t* nup_new, int32_t* ndown_new)
-{
-	StringPlan P;
-	lpp_status st = apply_string_front(e, "lpp_engine_apply_string_host", e && has && src && dst, convention, nops, ops, sites, spins, flags, nsites, nup, ndown, P, has, nup_new,
-	                                   ndown_new);
-	if (st != LPP_OK || !P.has) return st;
-	return staged(e, e->esz * (size_t)(P.n_up_src * P.n_dn_src), e->esz * (size_t)(P.n_up_dst * P.n_dn_dst), src, dst, accumulate, [&](const void* d_src, void* d_dst) {
-		return apply_string_dev(e, P, nsites, nup, ndown, factor_re, factor_im, d_src, d_dst, accumulate != 0);
-	});
-}
-
-lpp_status lpp_engine_many_point(lpp_engine* e, int32_t convention, int32_t nstrings, const int64_t* offsets, const int32_t* ops, const int32_t* sites, const int32_t* spins,
-                                 const int32_t* flags, int32_t nsites, int32_t nup, int32_t ndown, int32_t bra_state, int32_t ket_state, double* result)
-{
-	const char* who = "lpp_engine_many_point";
-	if (!e || !result) return fail(LPP_ERR_INVALID, std::string(who) + ": null argument");
-	lpp_status st = refuse_string(e, who);
-	if (st != LPP_OK) return st;
-	const StringList S { nstrings, offsets, ops, sites, spins, flags };
-	if ((st = check_list(S, who)) != LPP_OK) return st;
-	if (hubbard_sector_size(nsites, nup, ndown) < 0) return fail(LPP_ERR_INVALID, std::string(who) + ": bad sites / sector");
-	double *bra = nullptr, *ket = nullptr;
-	if ((st = state_ptr(e, bra_state, who, &bra)) != LPP_OK) return st;
-	if ((st = state_ptr(e, ket_state, who, &ket)) != LPP_OK) return st;
-	if (e->resident_len != hubbard_sector_size(nsites, nup, ndown)) return fail(LPP_ERR_INVALID, std::string(who) + ": (sites, nup, ndown) is not the sector of the resident states");
-	HIP_TRY(hipSetDevice(e->cfg.device));
-	return many_point_dev(e, convention, S, nsites, nup, ndown, bra, ket, result);
-}
-
-lpp_status lpp_engine_many_point_host(lpp_engine* e, int32_t convention, int32_t nstrings, const int64_t* offsets, const int32_t* ops, const int32_t* sites, const int32_t* spins,
-                                      const int32_t* flags, int32_t nsites, int32_t nup, int32_t ndown, const void* bra, const void* ket, double* result)
-{
-	const char* who = "lpp_engine_many_point_host";
-	if (!e || !result || !bra || !ket) return fail(LPP_ERR_INVALID, std::string(who) + ": null argument");
-	lpp_status st = refuse_string(e, who);
-	if (st != LPP_OK) return st;
-	const StringList S { nstrings, offsets, ops, sites, spins, flags };
-	if ((st = check_list(S, who)) != LPP_OK) return st;
-	const int64_t n = hubbard_sector_size(nsites, nup, ndown);
-	if (n < 0) return fail(LPP_ERR_INVALID, std::string(who) + ": bad sites / sector");
-	HIP_TRY(hipSetDevice(e->cfg.device));
-	const size_t bytes = e->esz * (size_t)n;
-	DevBuf db, dk;
-	HIP_TRY_MEM(hipMalloc(&db.p, bytes + 16));
-	HIP_TRY_MEM(hipMalloc(&dk.p, bytes + 16));
-	HIP_TRY(hipMemcpyAsync(db.p, bra, bytes, hipMemcpyHostToDevice, e->stream));
-	HIP_TRY(hipMemcpyAsync(dk.p, ket, bytes, hipMemcpyHostToDevice, e->stream));
-	st = many_point_dev(e, convention, S, nsites, nup, ndown, (const double*)db.p, (const double*)dk.p, result);
-	HIP_TRY(hipStreamSynchronize(e->stream));
-	return st;
-}
-
-lpp_status lpp_engine_bench_string_dot(lpp_engine* e, int32_t convention, int32_t nstrings, const int64_t* offsets, const int32_t* ops, const int32_t* sites, const int32_t* spins,
-                                       const int32_t* flags, int32_t nsites, int32_t nup, int32_t ndown, int32_t warmup, int32_t iters, double* ms_per_launch, double* model_bytes)
-{
-	const char* who = "lpp_engine_bench_string_dot";
-	if (!e || !ms_per_launch || iters < 1 || warmup < 0) return fail(LPP_ERR_INVALID, std::string(who) + ": bad argument");
-	lpp_status st = refuse_string(e, who);
-	if (st != LPP_OK) return st;
-	const StringList S { nstrings, offsets, ops, sites, spins, flags };
-	if ((st = check_list(S, who)) != LPP_OK) return st;
-	if (nstrings < 1 || nstrings > kObsStringBatch) return fail(LPP_ERR_INVALID, std::string(who) + ": 1 to 8 strings (one launch)");
-	const int64_t n = hubbard_sector_size(nsites, nup, ndown);
-	if (n < 0) return fail(LPP_ERR_INVALID, std::string(who) + ": bad sites / sector");
-	std::vector<StringPlan> plans((size_t)nstrings);
-	double reached = 0;
-	for (int s = 0; s < nstrings; s++) {
-		StringPlan& P = plans[(size_t)s];
-		const int64_t o = offsets[s];
-		if ((st = string_plan(convention, (int)(offsets[s + 1] - o), ops + o, sites + o, spins + o, flags ? flags + o : nullptr, nsites, nup, ndown, P)) != LPP_OK) return st;
-		if (!P.has || P.nup2 != nup || P.ndn2 != ndown) return fail(LPP_ERR_INVALID, std::string(who) + ": a string that leaves the sector launches nothing");
-		reached += (double)std::count_if(P.tu.begin(), P.tu.end(), [](int32_t v) { return v != 0; }) * (double)std::count_if(P.td.begin(), P.td.end(), [](int32_t v) { return v != 0; });
-	}
-	HIP_TRY(hipSetDevice(e->cfg.device));
-	const size_t bytes = e->esz * (size_t)n;
-	DevBuf db, dk;
-	HIP_TRY_MEM(hipMalloc(&db.p, bytes + 16));
-	HIP_TRY_MEM(hipMalloc(&dk.p, bytes + 16));
-	HIP_TRY(hipMemsetAsync(db.p, 0, bytes + 16, e->stream));
-	HIP_TRY(hipMemsetAsync(dk.p, 0, bytes + 16, e->stream));
-	DotWork W;
-	if ((st = dot_work(e, nsites, nup, ndown, nstrings, W)) != LPP_OK) return st;
-	const ObsStringDotArgs A = dot_args(W, plans.data(), nstrings);
-	HIP_TRY(hipMemcpyAsync(W.tabs.p, W.img.data(), 4 * W.img.size(), hipMemcpyHostToDevice, e->stream));
-	st = timed_steps(e, warmup, iters, ms_per_launch, [&] {
-		launch_dot(e, W, A, (const double*)db.p, (const double*)dk.p, (double*)W.out.p);
-		return LPP_OK;
-	});
-	if (st != LPP_OK) return st;
-	// bra read once, one ket element per string and destination it reaches (the tables stay in L2)
-	if (model_bytes) *model_bytes = (double)e->esz * ((double)n + reached);
-	return LPP_OK;
-}
 
 lpp_status lpp_obs_string_plan_heis(int32_t convention, int32_t nops, const int32_t* ops, const int32_t* sites, const int32_t* spins, const int32_t* flags, int32_t nsites,
                                     int32_t nup, int32_t ndown, int32_t* nup_new, int32_t* dead, uint64_t* flip, uint64_t* need, uint64_t* want, uint64_t* zmask, int32_t* sign,
                                     int32_t* low_bits, int64_t* n_dst, int64_t* action)
 {
-	(void)flags;
-	(void)ndown;
 	if (convention != LPP_STRING_MANY_POINT) return fail(LPP_ERR_INVALID, "lpp_obs_string_plan_heis: the Heisenberg basis has the many-point convention only");
 	HeisStringPlan P;
-	lpp_status st = heis_string_plan(nops, ops, sites, spins, nsites, nup, P);
+	lpp_status st = HeisStrings::plan(convention, nops, ops, sites, spins, flags, nsites, nup, ndown, P);
 	if (st != LPP_OK) return st;
 	if (nup_new) *nup_new = P.m2;
 	if (dead) *dead = P.dead ? 1 : 0;
@@ -1188,113 +1146,31 @@ lpp_status lpp_obs_string_plan_heis(int32_t convention, int32_t nops, const int3
 	return LPP_OK;
 }
 
-lpp_status lpp_engine_apply_string_heis(lpp_engine* e, int32_t convention, int32_t nops, const int32_t* ops, const int32_t* sites, const int32_t* spins, const int32_t* flags,
-                                        int32_t nsites, int32_t nup, int32_t ndown, double factor_re, double factor_im, const void* d_src, void* d_dst, int32_t accumulate,
-                                        int32_t* has, int32_t* nup_new, int32_t* ndown_new)
-{
-	(void)flags;
-	(void)ndown;
-	HeisStringPlan P;
-	lpp_status st = apply_string_heis_front(e, "lpp_engine_apply_string_heis", e && has, convention, nops, ops, sites, spins, nsites, nup, P, has, nup_new, ndown_new);
-	if (st != LPP_OK) return st;
-	return apply_string_heis_dev(e, P, nsites, nup, factor_re, factor_im, d_src, d_dst, accumulate != 0);
-}
+// One entry point per string family over one body<family>(name, arguments...): the Hubbard product basis, the S = 1/2 Heisenberg basis
+#define STRING_ENTRY(body, hubbard, heis, params, ...)                                 \
+	lpp_status hubbard params { return body<HubbardStrings>(#hubbard, __VA_ARGS__); } \
+	lpp_status heis params { return body<HeisStrings>(#heis, __VA_ARGS__); }
 
-lpp_status lpp_engine_apply_string_heis_host(lpp_engine* e, int32_t convention, int32_t nops, const int32_t* ops, const int32_t* sites, const int32_t* spins,
-                                             const int32_t* flags, int32_t nsites, int32_t nup, int32_t ndown, double factor_re, double factor_im, const void* src, void* dst,
-                                             int32_t accumulate, int32_t* has, int32_t* nup_new, int32_t* ndown_new)
-{
-	(void)flags;
-	(void)ndown;
-	HeisStringPlan P;
-	lpp_status st = apply_string_heis_front(e, "lpp_engine_apply_string_heis_host", e && has && src && dst, convention, nops, ops, sites, spins, nsites, nup, P, has, nup_new,
-	                                        ndown_new);
-	if (st != LPP_OK) return st;
-	return staged(e, e->esz * (size_t)P.n_src, e->esz * (size_t)P.n_dst, src, dst, accumulate, [&](const void* d_src, void* d_dst) {
-		return apply_string_heis_dev(e, P, nsites, nup, factor_re, factor_im, d_src, d_dst, accumulate != 0);
-	});
-}
-
-lpp_status lpp_engine_many_point_heis(lpp_engine* e, int32_t convention, int32_t nstrings, const int64_t* offsets, const int32_t* ops, const int32_t* sites, const int32_t* spins,
-                                      const int32_t* flags, int32_t nsites, int32_t nup, int32_t ndown, int32_t bra_state, int32_t ket_state, double* result)
-{
-	(void)ndown;
-	const char* who = "lpp_engine_many_point_heis";
-	const StringList S { nstrings, offsets, ops, sites, spins, flags };
-	int64_t n = 0;
-	lpp_status st = many_point_heis_front(e, who, e && result, convention, S, nsites, nup, &n);
-	if (st != LPP_OK) return st;
-	double *bra = nullptr, *ket = nullptr;
-	if ((st = state_ptr(e, bra_state, who, &bra)) != LPP_OK) return st;
-	if ((st = state_ptr(e, ket_state, who, &ket)) != LPP_OK) return st;
-	if (e->resident_len != n) return fail(LPP_ERR_INVALID, std::string(who) + ": (sites, szPlusConst) is not the sector of the resident states");
-	HIP_TRY(hipSetDevice(e->cfg.device));
-	return many_point_heis_dev(e, S, nsites, nup, bra, ket, result);
-}
-
-lpp_status lpp_engine_many_point_heis_host(lpp_engine* e, int32_t convention, int32_t nstrings, const int64_t* offsets, const int32_t* ops, const int32_t* sites,
-                                           const int32_t* spins, const int32_t* flags, int32_t nsites, int32_t nup, int32_t ndown, const void* bra, const void* ket, double* result)
-{
-	(void)ndown;
-	const char* who = "lpp_engine_many_point_heis_host";
-	const StringList S { nstrings, offsets, ops, sites, spins, flags };
-	int64_t n = 0;
-	lpp_status st = many_point_heis_front(e, who, e && result && bra && ket, convention, S, nsites, nup, &n);
-	if (st != LPP_OK) return st;
-	HIP_TRY(hipSetDevice(e->cfg.device));
-	const size_t bytes = e->esz * (size_t)n;
-	DevBuf db, dk;
-	HIP_TRY_MEM(hipMalloc(&db.p, bytes + 16));
-	HIP_TRY_MEM(hipMalloc(&dk.p, bytes + 16));
-	HIP_TRY(hipMemcpyAsync(db.p, bra, bytes, hipMemcpyHostToDevice, e->stream));
-	HIP_TRY(hipMemcpyAsync(dk.p, ket, bytes, hipMemcpyHostToDevice, e->stream));
-	st = many_point_heis_dev(e, S, nsites, nup, (const double*)db.p, (const double*)dk.p, result);
-	HIP_TRY(hipStreamSynchronize(e->stream));
-	return st;
-}
-
-lpp_status lpp_engine_bench_string_dot_heis(lpp_engine* e, int32_t convention, int32_t nstrings, const int64_t* offsets, const int32_t* ops, const int32_t* sites,
-                                            const int32_t* spins, const int32_t* flags, int32_t nsites, int32_t nup, int32_t ndown, int32_t warmup, int32_t iters,
-                                            double* ms_per_launch, double* model_bytes)
-{
-	(void)ndown;
-	const char* who = "lpp_engine_bench_string_dot_heis";
-	const StringList S { nstrings, offsets, ops, sites, spins, flags };
-	int64_t n = 0;
-	lpp_status st = many_point_heis_front(e, who, e && ms_per_launch && iters >= 1 && warmup >= 0, convention, S, nsites, nup, &n);
-	if (st != LPP_OK) return st;
-	if (nstrings < 1 || nstrings > kObsStringBatch) return fail(LPP_ERR_INVALID, std::string(who) + ": 1 to 8 strings (one launch)");
-	std::vector<HeisStringPlan> plans((size_t)nstrings);
-	double reached = 0;
-	for (int s = 0; s < nstrings; s++) {
-		HeisStringPlan& P = plans[(size_t)s];
-		const int64_t o = offsets[s];
-		if ((st = heis_string_plan((int)(offsets[s + 1] - o), ops + o, sites + o, spins + o, nsites, nup, P)) != LPP_OK) return st;
-		if (P.dead || P.m2 != nup) return fail(LPP_ERR_INVALID, std::string(who) + ": a string that is identically zero or leaves the sector launches nothing");
-		reached += (double)heis_string_touched(P, nsites, nup);
-	}
-	HIP_TRY(hipSetDevice(e->cfg.device));
-	const size_t bytes = e->esz * (size_t)n;
-	DevBuf db, dk;
-	HIP_TRY_MEM(hipMalloc(&db.p, bytes + 16));
-	HIP_TRY_MEM(hipMalloc(&dk.p, bytes + 16));
-	HIP_TRY(hipMemsetAsync(db.p, 0, bytes + 16, e->stream));
-	HIP_TRY(hipMemsetAsync(dk.p, 0, bytes + 16, e->stream));
-	HeisStringWork W;
-	if ((st = dot_work_heis(e, nsites, nup, nstrings, W)) != LPP_OK) return st;
-	ObsHeisStringDotArgs A {};
-	if ((st = heis_string_slots(e, W, plans.data(), nstrings, nsites, nup, A.b, A.src, A.low)) != LPP_OK) return st;
-	A.partial = (double*)W.part.p;
-	A.ns = nstrings;
-	st = timed_steps(e, warmup, iters, ms_per_launch, [&] {
-		launch_dot_heis(e, W, A, (const double*)db.p, (const double*)dk.p, (double*)W.out.p);
-		return LPP_OK;
-	});
-	if (st != LPP_OK) return st;
-	// bra read once, one ket element per string and destination it reaches (the run entries stay in L2)
-	if (model_bytes) *model_bytes = (double)e->esz * ((double)n + reached);
-	return LPP_OK;
-}
+STRING_ENTRY(apply_string_body, lpp_engine_apply_string, lpp_engine_apply_string_heis,
+             (lpp_engine* e, int32_t convention, int32_t nops, const int32_t* ops, const int32_t* sites, const int32_t* spins, const int32_t* flags, int32_t nsites, int32_t nup,
+              int32_t ndown, double factor_re, double factor_im, const void* d_src, void* d_dst, int32_t accumulate, int32_t* has, int32_t* nup_new, int32_t* ndown_new),
+             false, e, convention, nops, ops, sites, spins, flags, nsites, nup, ndown, factor_re, factor_im, d_src, d_dst, accumulate, has, nup_new, ndown_new)
+STRING_ENTRY(apply_string_body, lpp_engine_apply_string_host, lpp_engine_apply_string_heis_host,
+             (lpp_engine* e, int32_t convention, int32_t nops, const int32_t* ops, const int32_t* sites, const int32_t* spins, const int32_t* flags, int32_t nsites, int32_t nup,
+              int32_t ndown, double factor_re, double factor_im, const void* src, void* dst, int32_t accumulate, int32_t* has, int32_t* nup_new, int32_t* ndown_new),
+             true, e, convention, nops, ops, sites, spins, flags, nsites, nup, ndown, factor_re, factor_im, src, dst, accumulate, has, nup_new, ndown_new)
+STRING_ENTRY(many_point_body, lpp_engine_many_point, lpp_engine_many_point_heis,
+             (lpp_engine* e, int32_t convention, int32_t nstrings, const int64_t* offsets, const int32_t* ops, const int32_t* sites, const int32_t* spins, const int32_t* flags,
+              int32_t nsites, int32_t nup, int32_t ndown, int32_t bra_state, int32_t ket_state, double* result),
+             e, convention, nstrings, offsets, ops, sites, spins, flags, nsites, nup, ndown, bra_state, ket_state, result)
+STRING_ENTRY(many_point_host_body, lpp_engine_many_point_host, lpp_engine_many_point_heis_host,
+             (lpp_engine* e, int32_t convention, int32_t nstrings, const int64_t* offsets, const int32_t* ops, const int32_t* sites, const int32_t* spins, const int32_t* flags,
+              int32_t nsites, int32_t nup, int32_t ndown, const void* bra, const void* ket, double* result),
+             e, convention, nstrings, offsets, ops, sites, spins, flags, nsites, nup, ndown, bra, ket, result)
+STRING_ENTRY(bench_string_dot_body, lpp_engine_bench_string_dot, lpp_engine_bench_string_dot_heis,
+             (lpp_engine* e, int32_t convention, int32_t nstrings, const int64_t* offsets, const int32_t* ops, const int32_t* sites, const int32_t* spins, const int32_t* flags,
+              int32_t nsites, int32_t nup, int32_t ndown, int32_t warmup, int32_t iters, double* ms_per_launch, double* model_bytes),
+             e, convention, nstrings, offsets, ops, sites, spins, flags, nsites, nup, ndown, warmup, iters, ms_per_launch, model_bytes)
 
 lpp_status lpp_obs_plan_tj(int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t* has, int32_t* nup_new, int32_t* ndown_new,
                            int64_t* n_dst, int64_t* action)

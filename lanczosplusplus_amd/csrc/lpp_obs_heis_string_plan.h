@@ -1,6 +1,7 @@
 // lpp_obs_heis_string_plan.h -- host-only planning of operator strings in the S = 1/2 Heisenberg basis (BasisHeisenberg, twiceS = 1): a PRODUCT of n,
 // sz, splus, sminus composed into five bit masks and a sign (no tables at all), the per-run source entries the kernels read
-// (lpp_obs_heis_string_kernels.h) and obs_heis_string_source, the ONE lookup the kernels call per element and the host expands a plan with.
+// (lpp_obs_heis_string_kernels.h), their packing into the slots of one upload (heis_string_pack) and obs_heis_string_source, the ONE lookup the
+// kernels call per element and the host expands a plan with.
 // Plain C++, no HIP (host/test_heis_string_plan.cpp).  The run structure, the low tables and the sector arithmetic are lpp_obs_heis_plan.h's.
 //
 // Engine::manyPoint (reference src/Engine/Engine.h:341-389) chains accModifiedState_ with factor 1; for this basis every step either flips the site's
@@ -12,6 +13,8 @@
 // the original sector's basis), and S- is refused when the CURRENT sector is the all-down one (Heisenberg.h:233 tests the original szPlusConst and
 // otherwise wraps an unsigned number).
 #pragma once
+#include <algorithm>
+
 #include "lpp_obs_heis_plan.h"
 #include "lpp_obs_string_plan.h"
 
@@ -128,11 +131,11 @@ inline bool heis_string_runs(int L, int m2, bool tables, std::vector<ObsHeisRun>
 
 // per destination run (high part highs[k]) of a string that is not dead: +-(first index of the source run of h ^ flip_hi in sector m + 1), the sign
 // carrying P.sign and the parity of the source's high part under zmask_hi; 0 where the high conditions fail
-inline void heis_string_sources(const HeisStringPlan& P, int L, int m, const std::vector<uint64_t>& highs, std::vector<int64_t>& src)
+inline void heis_string_sources(const HeisStringPlan& P, int L, int m, const std::vector<uint64_t>& highs, int64_t* src)
 {
 	const int lb = P.lb, hb = L - lb;
 	const uint64_t fh = P.flip >> lb, nh = P.need >> lb, wh = P.want >> lb, zh = P.zmask >> lb;
-	src.assign(highs.size(), 0);
+	std::fill(src, src + highs.size(), (int64_t)0);
 	if (P.dead) return;
 	const bool same = fh == 0 && P.m2 == m; // the source run is the destination run: its start is the running sum of the run lengths
 	int64_t acc = 0;
@@ -145,6 +148,33 @@ inline void heis_string_sources(const HeisStringPlan& P, int L, int m, const std
 		const int64_t first = (same ? here : heis_run_start(hs, hb, lb, m)) + 1;
 		src[k] = ((P.sign < 0) != ((__builtin_popcountll(hs & zh) & 1) != 0)) ? -first : first;
 	}
+}
+
+inline void heis_string_sources(const HeisStringPlan& P, int L, int m, const std::vector<uint64_t>& highs, std::vector<int64_t>& src)
+{
+	src.resize(highs.size());
+	heis_string_sources(P, L, m, highs, src.data());
+}
+
+// What a launch of plans[0 .. ns) of source sector m uploads, packed on the host: slot s of `entries` (highs.size() entries each) takes the source
+// entries of plans[s], low[s] its low descriptor; *low_work: whether any of them has low-part work (none: the kernels stage no tables).
+// false, and nothing written: more plans than `entries` has slots, or a dead plan (nothing is launched for those)
+inline bool heis_string_pack(const HeisStringPlan* plans, int ns, int L, int m, const std::vector<uint64_t>& highs, std::vector<int64_t>& entries, ObsHeisStringLow* low,
+                             bool* low_work, const char** why)
+{
+	bool fits = ns >= 0 && (size_t)ns * highs.size() <= entries.size();
+	for (int s = 0; s < ns && fits; s++) fits = !plans[s].dead;
+	if (!fits) {
+		*why = "Heisenberg operator string: more plans than the upload has slots, or a dead plan among them";
+		return false;
+	}
+	*low_work = false;
+	for (int s = 0; s < ns; s++) {
+		heis_string_sources(plans[s], L, m, highs, entries.data() + (size_t)s * highs.size());
+		low[s] = plans[s].low();
+		*low_work = *low_work || obs_heis_string_low_work(low[s]);
+	}
+	return true;
 }
 
 // the plan expanded as the kernels walk it; word / rank may be empty without low work

@@ -1,9 +1,11 @@
 // lpp_obs_string_plan.h -- host-only planning of operator strings in the Hubbard product basis: the composition of a PRODUCT of one-site operators
-// into one pair of per-species tables (the kernels that read them: lpp_obs_string_kernels.h; sector arithmetic and species ranks: lpp_obs_plan.h).
-// Plain C++, no HIP: the sanitizer test of the planner (host/test_string_plan.cpp) compiles this header alone.
+// into one pair of per-species tables (the kernels that read them: lpp_obs_string_kernels.h; sector arithmetic and species ranks: lpp_obs_plan.h),
+// and the packing of a launch's tables and word lists into one upload image (StringImage).  Plain C++, no HIP: the sanitizer test of the planner (host/test_string_plan.cpp) compiles this header alone.
 #pragma once
 #include <stdint.h>
 
+#include <algorithm>
+#include <cstddef>
 #include <vector>
 
 #include "lpp_engine.h"
@@ -170,6 +172,68 @@ inline void species_words(int L, int n, std::vector<uint32_t>& out)
 		out[(size_t)i] = (uint32_t)w;
 		if (i + 1 < cnt) w = next_word(w);
 	}
+}
+
+// ---- what is uploaded for a launch, packed on the host -----------------------------------------------------------------------------------
+
+// the sz entries of a plan as the kernels read them: entry k is 8 bits of lo (k < 8) or of hi
+struct StringSzWords {
+	uint64_t lo = 0, hi = 0;
+	uint8_t entry(int k) const { return (uint8_t)(((k < 8) ? lo : hi) >> (8 * (k & 7))); }
+};
+inline StringSzWords pack_sz(const StringPlan& P)
+{
+	StringSzWords W;
+	for (int k = 0; k < P.nsz; k++) ((k < 8) ? W.lo : W.hi) |= (uint64_t)P.sz[k] << (8 * (k & 7));
+	return W;
+}
+
+// One upload image of 32-bit words: `slots` pairs of tables (up: ntu entries, down: ntd, the DESTINATION sector's species counts), then the SOURCE
+// sector's species words by rank, up (nwu) then down (nwd); 0, 0: no word lists (a string without sz reads none).  The offsets are in words.
+struct StringImage {
+	int64_t ntu = 0, ntd = 0;
+	int slots = 0;
+	int64_t nwu = 0, nwd = 0;
+	size_t tab_up(int s) const { return (size_t)(ntu + ntd) * (size_t)s; }
+	size_t tab_dn(int s) const { return tab_up(s) + (size_t)ntu; }
+	size_t words_up() const { return tab_up(slots); }
+	size_t words_dn() const { return words_up() + (size_t)nwu; }
+	size_t size() const { return words_dn() + (size_t)nwd + 4; } // (4 spare words: the word pointers of an image without lists stay inside it)
+};
+
+// a fresh image: zeros, and the word lists of source sector (L; nup, ndn) where the image has them.  false: the lists are not of the image's lengths
+inline bool string_image_begin(const StringImage& G, int L, int nup, int ndn, std::vector<int32_t>& img, const char** why)
+{
+	img.assign(G.size(), 0);
+	std::vector<uint32_t> w;
+	for (int sp = 0; sp < 2; sp++) {
+		const int64_t len = sp ? G.nwd : G.nwu;
+		if (len == 0) continue;
+		species_words(L, sp ? ndn : nup, w);
+		if ((int64_t)w.size() != len) {
+			*why = "operator string: the word lists are not of the upload image's sector";
+			return false;
+		}
+		std::copy(w.begin(), w.end(), img.begin() + (std::ptrdiff_t)(sp ? G.words_dn() : G.words_up()));
+	}
+	return true;
+}
+
+// the tables of plans[0 .. ns) into slots 0 .. ns-1 of the image.  false, and nothing copied: more plans than slots, or a table whose length is not
+// the image's species count -- copying it would write, and the kernel would read, outside its slot
+inline bool string_image_tables(const StringImage& G, const StringPlan* plans, int ns, std::vector<int32_t>& img, const char** why)
+{
+	bool fits = ns >= 0 && ns <= G.slots && img.size() == G.size();
+	for (int s = 0; s < ns && fits; s++) fits = (int64_t)plans[s].tu.size() == G.ntu && (int64_t)plans[s].td.size() == G.ntd;
+	if (!fits) {
+		*why = "operator string: a plan's tables are not of the upload image's sector";
+		return false;
+	}
+	for (int s = 0; s < ns; s++) {
+		std::copy(plans[s].tu.begin(), plans[s].tu.end(), img.begin() + (std::ptrdiff_t)G.tab_up(s));
+		std::copy(plans[s].td.begin(), plans[s].td.end(), img.begin() + (std::ptrdiff_t)G.tab_dn(s));
+	}
+	return true;
 }
 
 } // namespace obs_host

@@ -3,6 +3,8 @@
 //   - that the composed plan of a string, expanded as the kernels walk it, IS the composition of the one-operator plans (csrc/lpp_obs_heis_plan.h)
 //     through the sectors, destination by destination, on the sectors of the tests and at (40;3), where the cut of the word is at 14 bits;
 //   - the invariants: every entry a source of the first sector, no source used twice, the count of heis_string_touched;
+//   - what a launch uploads (heis_string_pack): one string in apply's one slot and batches of 1, 8 and 5 in the bracket kernel's 8, every slot and low
+//     descriptor against its plan; a dead plan or more plans than slots is refused, nothing written;
 //   - the refusals, and the planning alone of a 16-operator string at 32 sites (2^20 runs).
 // Prints `ok` and returns 0, or says what failed and returns 1.
 #include <cstdio>
@@ -124,11 +126,79 @@ bool check_string(const std::vector<Op>& s, int L, int m)
 	return reached > 0;
 }
 
+// What a launch uploads (heis_string_pack) on sector (L; m): every live string alone into the one slot apply has, on the runs of the sector it ends in,
+// and 1, 8 and 5 of the strings that stay in the sector into the 8 slots of the bracket kernel -- each slot and low descriptor against the plan it came
+// from, the slot expanded against the plan's own expansion; then the refusals.  Returns the number of strings that stay.
+int check_pack(int L, int m)
+{
+	const char* why = nullptr;
+	std::vector<HeisStringPlan> stay;
+	HeisStringPlan dead;
+	for (const auto& s : strings(L)) {
+		HeisStringPlan P;
+		CHECK(plan(s, L, m, P, &why));
+		if (P.dead) {
+			dead = P;
+			continue;
+		}
+		std::vector<ObsHeisRun> runs;
+		std::vector<uint64_t> highs;
+		std::vector<uint16_t> word, rank;
+		CHECK(heis_string_runs(L, P.m2, true, runs, highs, word, rank));
+		std::vector<int64_t> entries(highs.size(), 77), src, got((size_t)P.n_dst, 0), want;
+		ObsHeisStringLow low {};
+		bool low_work = false;
+		CHECK(heis_string_pack(&P, 1, L, m, highs, entries, &low, &low_work, &why));
+		heis_string_sources(P, L, m, highs, src);
+		CHECK(entries == src && low_work == obs_heis_string_low_work(P.low()));
+		CHECK(low.flip == P.low().flip && low.need == P.low().need && low.want == P.low().want && low.zmask == P.low().zmask);
+		heis_string_expand(P, runs, entries, word, rank, got.data());
+		CHECK(expand(P, L, m, want) && got == want);
+		if (P.m2 == m) stay.push_back(P);
+	}
+	CHECK(dead.dead);
+	std::vector<ObsHeisRun> runs;
+	std::vector<uint64_t> highs;
+	std::vector<uint16_t> word, rank;
+	CHECK(heis_string_runs(L, m, true, runs, highs, word, rank));
+	const size_t nr = highs.size();
+	std::vector<int64_t> entries(8 * nr, 77), src;
+	for (int ns : { 1, 8, 5 }) {
+		const std::vector<int64_t> before = entries;
+		std::vector<HeisStringPlan> batch;
+		for (int s = 0; s < ns; s++) batch.push_back(stay[(size_t)(s + ns) % stay.size()]);
+		ObsHeisStringLow low[8] = {};
+		bool low_work = false, any = false;
+		CHECK(heis_string_pack(batch.data(), ns, L, m, highs, entries, low, &low_work, &why));
+		for (int s = 0; s < ns; s++) {
+			heis_string_sources(batch[(size_t)s], L, m, highs, src);
+			CHECK(std::vector<int64_t>(entries.begin() + (std::ptrdiff_t)(s * nr), entries.begin() + (std::ptrdiff_t)((s + 1) * nr)) == src);
+			CHECK(low[s].flip == batch[(size_t)s].low().flip && low[s].need == batch[(size_t)s].low().need && low[s].want == batch[(size_t)s].low().want &&
+			      low[s].zmask == batch[(size_t)s].low().zmask);
+			any = any || obs_heis_string_low_work(low[s]);
+		}
+		CHECK(low_work == any);
+		CHECK(std::equal(entries.begin() + (std::ptrdiff_t)(ns * nr), entries.end(), before.begin() + (std::ptrdiff_t)(ns * nr))); // the later slots stay
+	}
+	// refusals: a dead plan in the batch, more plans than slots -- nothing is written
+	const std::vector<int64_t> before = entries;
+	ObsHeisStringLow low[9] = {};
+	bool low_work = false;
+	const std::vector<HeisStringPlan> with_dead { stay[0], dead }, nine(9, stay[0]);
+	why = nullptr;
+	CHECK(!heis_string_pack(with_dead.data(), 2, L, m, highs, entries, low, &low_work, &why) && why && entries == before);
+	CHECK(!heis_string_pack(nine.data(), 9, L, m, highs, entries, low, &low_work, &why) && entries == before);
+	std::vector<int64_t> one_slot(nr, 0);
+	CHECK(!heis_string_pack(nine.data(), 2, L, m, highs, one_slot, low, &low_work, &why));
+	return (int)stay.size();
+}
+
 } // namespace
 
 int main()
 {
 	const int sectors[6][2] = { { 7, 2 }, { 7, 3 }, { 14, 7 }, { 16, 7 }, { 16, 8 }, { 18, 9 } };
+	for (const auto& sec : sectors) CHECK(check_pack(sec[0], sec[1]) == 10);
 	for (const auto& sec : sectors) {
 		int nonzero = 0, k = 0;
 		for (const auto& s : strings(sec[0])) {

@@ -3,6 +3,8 @@
 //   - the tables' invariants: sizes, every entry a rank of the source sector, no source used twice;
 //   - that the composed plan of a many-point string IS the composition of the one-operator plans through the sectors, destination by destination,
 //     sz factors included (evaluated on the words of the sector each operator meets);
+//   - the upload images (StringImage): one string as apply uploads it and batches of 1, 8 and 5 in the 8 slots of the bracket kernel, every table,
+//     word list and sz word read back against its plan; a table that is not of the image's species count is refused, not copied;
 //   - measure strings by hand-worked cases, and the refusals.
 // Prints `ok` and returns 0, or says what failed and returns 1.
 #include <cstdio>
@@ -127,6 +129,68 @@ void check_many_point(const std::vector<Op>& s, int L, int nup, int ndn)
 const int C = LPP_OP_C, D = LPP_OP_CDAGGER, N = LPP_OP_N, Z = LPP_OP_SZ, P_ = LPP_OP_SPLUS, M = LPP_OP_SMINUS, I = LPP_OP_IDENTITY;
 const int U = LPP_SPIN_UP, W = LPP_SPIN_DOWN;
 
+// slot s of an image read back against the plan it came from, and the sz words against P.sz
+void check_slot(const StringImage& G, const std::vector<int32_t>& img, int s, const StringPlan& P)
+{
+	CHECK(G.tab_dn(s) + P.td.size() <= G.words_up());
+	CHECK(std::vector<int32_t>(img.begin() + (std::ptrdiff_t)G.tab_up(s), img.begin() + (std::ptrdiff_t)G.tab_dn(s)) == P.tu);
+	CHECK(std::vector<int32_t>(img.begin() + (std::ptrdiff_t)G.tab_dn(s), img.begin() + (std::ptrdiff_t)(G.tab_dn(s) + P.td.size())) == P.td);
+	const StringSzWords sz = pack_sz(P);
+	for (int k = 0; k < kObsStringMaxOps; k++) CHECK(sz.entry(k) == (k < P.nsz ? P.sz[k] : 0));
+}
+
+// the word lists of an image against the species words of (L; nup, ndn); absent lists: nothing between the tables and the spare words
+void check_words(const StringImage& G, const std::vector<int32_t>& img, int L, int nup, int ndn)
+{
+	CHECK(img.size() == G.size() && G.size() == (size_t)((G.ntu + G.ntd) * G.slots + G.nwu + G.nwd + 4));
+	std::vector<uint32_t> wu, wd;
+	if (G.nwu) species_words(L, nup, wu);
+	if (G.nwd) species_words(L, ndn, wd);
+	CHECK((int64_t)wu.size() == G.nwu && (int64_t)wd.size() == G.nwd);
+	for (size_t i = 0; i < wu.size(); i++) CHECK((uint32_t)img[G.words_up() + i] == wu[i]);
+	for (size_t i = 0; i < wd.size(); i++) CHECK((uint32_t)img[G.words_dn() + i] == wd[i]);
+	for (size_t i = G.words_dn() + (size_t)G.nwd; i < img.size(); i++) CHECK(img[i] == 0);
+}
+
+// The upload images of sector (L; nup, ndn): every string alone as apply uploads it (the word lists only with sz entries), and 1, 8 and 5 of the
+// strings that stay in the sector as the bracket kernel's batch of 8 slots; then the refusals.  Returns the number of strings that stay.
+int check_images(const std::vector<std::vector<Op>>& strings, int L, int nup, int ndn)
+{
+	const char* why = nullptr;
+	std::vector<StringPlan> stay;
+	std::vector<int32_t> img;
+	for (const auto& s : strings) {
+		StringPlan P;
+		CHECK(plan(LPP_STRING_MANY_POINT, s, L, nup, ndn, P, &why));
+		if (!P.has) continue;
+		const bool words = P.nsz > 0;
+		const StringImage G { P.n_up_dst, P.n_dn_dst, 1, words ? P.n_up_src : 0, words ? P.n_dn_src : 0 };
+		CHECK(string_image_begin(G, L, nup, ndn, img, &why) && string_image_tables(G, &P, 1, img, &why));
+		check_slot(G, img, 0, P);
+		check_words(G, img, L, nup, ndn);
+		if (P.nup2 == nup && P.ndn2 == ndn) stay.push_back(P);
+	}
+	if (stay.empty()) return 0;
+	const int64_t nu = binom(L, nup), nd = binom(L, ndn);
+	const StringImage G { nu, nd, 8, nu, nd };
+	CHECK(string_image_begin(G, L, nup, ndn, img, &why));
+	for (int ns : { 8, 1, 5 }) { // one image reused as the driver does: a shorter batch leaves the later slots as they were
+		std::vector<StringPlan> batch;
+		for (int s = 0; s < ns; s++) batch.push_back(stay[(size_t)(s + ns) % stay.size()]);
+		CHECK(string_image_tables(G, batch.data(), ns, img, &why));
+		for (int s = 0; s < ns; s++) check_slot(G, img, s, batch[(size_t)s]);
+		for (int s = ns; s < 8; s++) check_slot(G, img, s, stay[(size_t)(s + 8) % stay.size()]);
+		check_words(G, img, L, nup, ndn);
+	}
+	// refusals: nothing is copied
+	const std::vector<int32_t> before = img;
+	std::vector<StringPlan> nine(9, stay[0]);
+	CHECK(!string_image_tables(G, nine.data(), 9, img, &why) && why && img == before);
+	std::vector<int32_t> small(img.begin(), img.end() - 1);
+	CHECK(!string_image_tables(G, nine.data(), 1, small, &why));
+	return (int)stay.size();
+}
+
 } // namespace
 
 int main()
@@ -160,6 +224,35 @@ int main()
 		const char* why = nullptr;
 		CHECK(plan(LPP_STRING_MANY_POINT, strings.back(), 16, 8, 8, P, &why) && P.has);
 		check_invariants(P, 16, 8, 8);
+	}
+
+	// the upload images: on (4; 2, 2), (5; 2, 1) with an odd sector, (6; 3, 3), and where one species has a single state
+	CHECK(check_images(strings, 4, 2, 2) >= 8);
+	CHECK(check_images(strings, 5, 2, 1) >= 8);
+	CHECK(check_images(strings, 6, 3, 3) >= 8);
+	CHECK(check_images(strings, 4, 4, 1) >= 1);
+	// A plan whose table length is not the image's species count is REFUSED by the packer, each species on its own, and nothing is copied:
+	// c up ends in (1, 2), so its up table has C(4, 1) = 4 entries where the image of (2, 2) has slots of C(4, 2) = 6; c down likewise
+	{
+		const StringImage G { 6, 6, 8, 6, 6 };
+		std::vector<int32_t> img;
+		const char* why = nullptr;
+		CHECK(string_image_begin(G, 4, 2, 2, img, &why));
+		const std::vector<int32_t> before = img;
+		StringPlan ok, up, dn;
+		CHECK(plan(LPP_STRING_MANY_POINT, { { N, 0, U, 0 } }, 4, 2, 2, ok, &why) && ok.tu.size() == 6 && ok.td.size() == 6);
+		CHECK(plan(LPP_STRING_MANY_POINT, { { C, 0, U, 0 } }, 4, 2, 2, up, &why) && up.has && up.tu.size() == 4 && up.td.size() == 6);
+		CHECK(plan(LPP_STRING_MANY_POINT, { { C, 0, W, 0 } }, 4, 2, 2, dn, &why) && dn.has && dn.tu.size() == 6 && dn.td.size() == 4);
+		for (const StringPlan& bad : { up, dn }) {
+			const std::vector<StringPlan> batch { ok, bad };
+			why = nullptr;
+			CHECK(!string_image_tables(G, batch.data(), 2, img, &why) && why && img == before); // the good plan before it is not copied either
+		}
+		StringPlan grown = ok; // one entry too many: it would run into the next slot
+		grown.tu.push_back(0);
+		CHECK(!string_image_tables(G, &grown, 1, img, &why) && img == before);
+		// the word lists of another sector are refused as well
+		CHECK(!string_image_begin(G, 4, 1, 2, img, &why) && !string_image_begin(G, 4, 2, 3, img, &why));
 	}
 
 	// measure: hand-worked cases on L = 3, sector (1, 1): up words 1, 2, 4 by rank

@@ -112,7 +112,8 @@ def test_refusals():
 
 def test_planner_under_sanitizers(tmp_path):
     """the host planner in a stand-alone program (its own main) built with the address and undefined-behaviour sanitizers: the strings of this file on the
-    six sectors against a chain of one-operator plans, the refusals, (40;3) and a 16-operator string at 32 sites; the program prints `ok`"""
+    six sectors against a chain of one-operator plans, what a launch of 1, 8 and 5 of them uploads against their plans, the refusals, (40;3) and a
+    16-operator string at 32 sites; the program prints `ok`"""
     src = os.path.join(ROOT, "lanczosplusplus_amd", "host", "test_heis_string_plan.cpp")
     exe = str(tmp_path / "test_heis_string_plan")
     out = subprocess.run([os.environ.get("CXX", "g++"), "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I" + os.path.join(ROOT, "include"),

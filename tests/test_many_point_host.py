@@ -169,7 +169,8 @@ def test_refusals():
 
 def test_planner_under_sanitizers(tmp_path):
     """the host planner in a stand-alone program (its own main) built with the address and undefined-behaviour sanitizers: the strings of this file, the
-    refusals and the largest tables (L = 16, 16 operators); the program checks the tables' invariants itself and prints `ok`"""
+    refusals, the largest tables (L = 16, 16 operators) and the upload images of one string and of batches of 1, 8 and 5 read back against their plans,
+    with a table of the wrong length refused; the program checks the tables' invariants itself and prints `ok`"""
     src = os.path.join(ROOT, "lanczosplusplus_amd", "host", "test_string_plan.cpp")
     exe = str(tmp_path / "test_string_plan")
     out = subprocess.run([os.environ.get("CXX", "g++"), "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I" + os.path.join(ROOT, "include"),
