@@ -672,6 +672,54 @@ lpp_status lpp_engine_bench_string_dot_heis(lpp_engine* e, int32_t convention, i
                                             const int32_t* spins, const int32_t* flags, int32_t nsites, int32_t nup, int32_t ndown, int32_t warmup, int32_t iters,
                                             double* ms_per_launch, double* model_bytes);
 
+/* ---- many-point correlations of the one-orbital t-J basis (entry points added under ABI 7, no struct changes; one GPU; csrc/lpp_obs.hip,
+ *      csrc/lpp_obs_tj_string_plan.h, csrc/lpp_obs_tj_string_kernels.h) ----
+ * The reference's -M for Model=TjMultiOrb with Orbitals=1: Engine::manyPoint chains accModifiedState_ with factor 1 through the sectors of
+ * TjMultiOrb::hasNewParts (no (0,0) sector, none with nup + ndown > sites), served by BasisTjMultiOrbLanczos::getBraIndex (:207-245).  Argument lists as
+ * the Hubbard calls; flags are not read.  LPP_STRING_MANY_POINT only: RahulOperator on this basis is not restated -> LPP_ERR_INVALID.  ops[0] acts first,
+ * with the rules of lpp_engine_apply_operator_tj: c / cdagger flip the species' own bit (cdagger needs the other species absent) with doSignGf -- spin
+ * UP: the parity of the up bits below the site; spin DOWN: the parity of ALL up electrons times the parity of the down bits below the site --, n and a
+ * raw sz are both "the bit of the given spin is set" with value 1, splus makes a down site up and sminus an up site down with value 1 and no sign.
+ * A site is empty, up or down, and every operator fixes the state it meets and the state it leaves, so a whole string composes on the host into
+ *   result[(u, d)] = sign * (-1)^popcount(us & par_up) * (-1)^popcount(ds & par_down) * src[index(us, ds)],  us = u ^ flip_up, ds = d ^ flip_down,
+ *   where (us & touched) == want_up and (ds & touched) == want_down, else 0
+ * (the conditions and the parities are on the SOURCE words; both species are recorded for every touched site, so the source is always a basis word).
+ * A step that meets another state than the steps before left (c twice, n up and n down of one site) makes the string identically zero: "dead".
+ * LPP_ERR_INVALID, as lpp_engine_apply_operator_tj has it: an unknown operator or spin, a site >= nsites, a bad sector (nup + ndown <= nsites <= 30),
+ * splus / sminus with LPP_SPIN_DOWN, 0 or more than 16 operators, and a string that changes the up pattern with more than 24 sites free of down
+ * electrons in its source sector (the pattern rank tables are kept in LDS).  n and sz act in the sector the string has reached (the deviation of the
+ * other two families from Engine.h:397-400).  A partitioned engine -> LPP_ERR_STATE; a hole-major t-J engine is served (its resident states are in the
+ * basis order, lpp_engine_keep_states_tj).  The entry points of the two blocks above keep their behaviour; the Python layer asks for basis="tj", the
+ * C++ shim for the SolverOptions token TjOperatorStrings. */
+
+/* The plan of one string (host only; exposed for the CPU test-suite): *has = 0 where a step leads to no sector; else the final parts, *dead,
+ * words[7] = { flip_up, flip_down, touched, want_up, want_down, par_up, par_down }, *sign, *n_dst, *touched_count = the destinations the string
+ * reaches in closed form (the byte model's count) and, where action is not NULL, action[dst] = +-(src + 1) or 0 for the *n_dst destinations, expanded
+ * through the per-down-word entries and the same lookup function (obs_tj_string_source) the kernels use.  All zero for a dead string.  NULL: not written. */
+lpp_status lpp_obs_string_plan_tj(int32_t convention, int32_t nops, const int32_t* ops, const int32_t* sites, const int32_t* spins, const int32_t* flags, int32_t nsites,
+                                  int32_t nup, int32_t ndown, int32_t* has, int32_t* nup_new, int32_t* ndown_new, int32_t* dead, uint32_t* words, int32_t* sign, int64_t* n_dst,
+                                  int64_t* touched_count, int64_t* action);
+
+/* lpp_engine_apply_string / _host in the t-J basis, contracts as those calls: one launch of k_obs_string_apply_tj, then a stream sync.  *has = 0 where
+ * the string leads to no sector; a dead string launches nothing and gives z = 0 (accumulate: z unchanged). */
+lpp_status lpp_engine_apply_string_tj(lpp_engine* e, int32_t convention, int32_t nops, const int32_t* ops, const int32_t* sites, const int32_t* spins, const int32_t* flags,
+                                      int32_t nsites, int32_t nup, int32_t ndown, double factor_re, double factor_im, const void* d_src, void* d_dst, int32_t accumulate,
+                                      int32_t* has, int32_t* nup_new, int32_t* ndown_new);
+lpp_status lpp_engine_apply_string_tj_host(lpp_engine* e, int32_t convention, int32_t nops, const int32_t* ops, const int32_t* sites, const int32_t* spins,
+                                           const int32_t* flags, int32_t nsites, int32_t nup, int32_t ndown, double factor_re, double factor_im, const void* src, void* dst,
+                                           int32_t accumulate, int32_t* has, int32_t* nup_new, int32_t* ndown_new);
+
+/* lpp_engine_many_point / _host / lpp_engine_bench_string_dot in the t-J basis, contracts as those calls: a dead string, one without a sector and one
+ * that ends in another sector give exactly 0 and launch nothing (Engine.h:364, :382-383); the others go 8 per launch through k_obs_string_dot_tj and a
+ * fixed-order reduction, so a value does not depend on the batch it is computed in, and two calls return the same bits. */
+lpp_status lpp_engine_many_point_tj(lpp_engine* e, int32_t convention, int32_t nstrings, const int64_t* offsets, const int32_t* ops, const int32_t* sites, const int32_t* spins,
+                                    const int32_t* flags, int32_t nsites, int32_t nup, int32_t ndown, int32_t bra_state, int32_t ket_state, double* result);
+lpp_status lpp_engine_many_point_tj_host(lpp_engine* e, int32_t convention, int32_t nstrings, const int64_t* offsets, const int32_t* ops, const int32_t* sites,
+                                         const int32_t* spins, const int32_t* flags, int32_t nsites, int32_t nup, int32_t ndown, const void* bra, const void* ket, double* result);
+lpp_status lpp_engine_bench_string_dot_tj(lpp_engine* e, int32_t convention, int32_t nstrings, const int64_t* offsets, const int32_t* ops, const int32_t* sites,
+                                          const int32_t* spins, const int32_t* flags, int32_t nsites, int32_t nup, int32_t ndown, int32_t warmup, int32_t iters,
+                                          double* ms_per_launch, double* model_bytes);
+
 #ifdef __cplusplus
 }
 #endif

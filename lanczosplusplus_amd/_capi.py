@@ -178,6 +178,15 @@ SYMBOLS = {
     "lpp_engine_many_point_heis": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P] + [C.c_int32] * 5 + [_P]),
     "lpp_engine_many_point_heis_host": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P] + [C.c_int32] * 3 + [_P, _P, _P]),
     "lpp_engine_bench_string_dot_heis": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P] + [C.c_int32] * 5 + [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "lpp_obs_string_plan_tj": (C.c_int32, [C.c_int32, C.c_int32, _P, _P, _P, _P] + [C.c_int32] * 3 + [C.POINTER(C.c_int32)] * 4 + [_P, C.POINTER(C.c_int32)]
+                               + [C.POINTER(C.c_int64)] * 2 + [_P]),
+    "lpp_engine_apply_string_tj": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P] + [C.c_int32] * 3 + [C.c_double, C.c_double, _P, _P, C.c_int32]
+                                   + [C.POINTER(C.c_int32)] * 3),
+    "lpp_engine_apply_string_tj_host": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P] + [C.c_int32] * 3 + [C.c_double, C.c_double, _P, _P, C.c_int32]
+                                        + [C.POINTER(C.c_int32)] * 3),
+    "lpp_engine_many_point_tj": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P] + [C.c_int32] * 5 + [_P]),
+    "lpp_engine_many_point_tj_host": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P] + [C.c_int32] * 3 + [_P, _P, _P]),
+    "lpp_engine_bench_string_dot_tj": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P] + [C.c_int32] * 5 + [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 }
 
 _lib = None

@@ -5,10 +5,11 @@
 //
 // The device side only.  Each family is one ObsBasis: how its plan is built and uploaded (a DevPlan of its own in the engine's cache) and how it is
 // launched; every entry point is one body over an ObsBasis, and the four destination-driven apply kernels go through one launch (OBS_LAUNCH).
-// Operator strings have two families (HubbardStrings, HeisStrings) under one driver and one set of entry-point bodies (STRING_ENTRY).
+// Operator strings have three families (HubbardStrings, HeisStrings, TjStrings) under one driver and one set of entry-point bodies (STRING_ENTRY).
 // The host planners (no GPU, plain C++) are lpp_obs_plan.h (shared sector arithmetic, Hubbard), lpp_obs_tj_plan.h, lpp_obs_heis_plan.h and
-// lpp_obs_string_plan.h, for strings in the Heisenberg basis lpp_obs_heis_string_plan.h; the kernels are lpp_obs_kernels.h, lpp_obs_tj_kernels.h,
-// lpp_obs_heis_kernels.h, lpp_obs_string_kernels.h and lpp_obs_heis_string_kernels.h.
+// lpp_obs_string_plan.h, for strings in the Heisenberg basis lpp_obs_heis_string_plan.h, in the t-J basis lpp_obs_tj_string_plan.h; the kernels are
+// lpp_obs_kernels.h, lpp_obs_tj_kernels.h, lpp_obs_heis_kernels.h, lpp_obs_string_kernels.h, lpp_obs_heis_string_kernels.h and
+// lpp_obs_tj_string_kernels.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -28,6 +29,7 @@
 #include "lpp_obs_tj_kernels.h"
 #include "lpp_obs_heis_kernels.h"
 #include "lpp_obs_heis_string_kernels.h"
+#include "lpp_obs_tj_string_kernels.h"
 
 using namespace lpp;
 using namespace lpp::obs_host;
@@ -570,9 +572,9 @@ lpp_status spectral_body(const ObsBasis& B, const std::string& who, lpp_engine* 
 	return decomposition_device_any(sector, M.p, nsteps, a, b, stats); // (a hole-major sector engine takes the vector through its permutation)
 }
 
-// ---- operator strings on the device: two families, one driver -------------------------------------------------------------------------------------
+// ---- operator strings on the device: three families, one driver -----------------------------------------------------------------------------------
 //
-// A family of strings is a struct (HubbardStrings and HeisStrings below) with
+// A family of strings is a struct (HubbardStrings, HeisStrings and TjStrings below) with
 //   Plan                                  the host plan of one string
 //   kBadSector, kNotResident, kLeaves     its wording of three refusals
 //   refuse(e, who, conv)                  what the engine or the convention rules out
@@ -585,7 +587,7 @@ lpp_status spectral_body(const ObsBasis& B, const std::string& who, lpp_engine* 
 //   scale(P), reached(P, L, nup)          the factor on its bracket; the destinations it reaches, for the byte model
 //   Work                                  the bracket kernel's device workspace for kObsStringBatch strings, a DotOut with
 //                                         prepare(e, L, nup, ndn, nstrings), load(e, plans, ns, L, nup, ndn) and launch(e, bra, ket, d_out)
-// Everything after the two structs is written once over F.  A third family is one more struct and one more name per STRING_ENTRY.
+// Everything after the three structs is written once over F.  A further family is one more struct and one more name per STRING_ENTRY.
 
 // strings as offsets into flat arrays: string s is entries offsets[s] .. offsets[s+1]-1
 struct StringList {
@@ -828,6 +830,113 @@ struct HeisStrings {
 			const size_t lds = obs_heis_string_lds_bytes(A.b.nlo);
 			if (e->is_complex) k_obs_string_dot_heis<true><<<grid, kObsBlock, lds, e->stream>>>(bra, ket, A);
 			else k_obs_string_dot_heis<false><<<grid, kObsBlock, lds, e->stream>>>(bra, ket, A);
+			reduce(e, A.ns, d_out);
+		}
+	};
+};
+
+// the one-orbital t-J basis: a string is a few words, one 32-bit entry per destination down word and a program of pattern steps (plan and upload
+// image: lpp_obs_tj_string_plan.h, kernels: lpp_obs_tj_string_kernels.h).  A hole-major engine is admitted: its resident states are kept in the
+// basis order (lpp_engine_keep_states_tj), the order lpp_engine_two_point_tj reads them in as well.
+struct TjStrings {
+	typedef TjStringPlan Plan;
+	static constexpr const char* kBadSector = ": bad sites / sector (nup + ndown <= sites <= 30)";
+	static constexpr const char* kNotResident = ": (sites, nup, ndown) is not the sector of the resident states";
+	static constexpr const char* kLeaves = ": a string that is identically zero, leads to no sector or leaves the sector launches nothing";
+
+	static lpp_status refuse(const lpp_engine* e, const char* who, int conv)
+	{
+		if (multi(e)) return fail(LPP_ERR_STATE, std::string(who) + ": not on a partitioned (multi-rank) engine");
+		if (conv != LPP_STRING_MANY_POINT)
+			return fail(LPP_ERR_INVALID, std::string(who) + ": the t-J basis has the many-point convention only (RahulOperator on this basis is not restated)");
+		return LPP_OK;
+	}
+	static lpp_status plan(int, int nops, const int32_t* ops, const int32_t* sites, const int32_t* spins, const int32_t*, int L, int nup, int ndn, Plan& P)
+	{
+		const char* why = nullptr;
+		return plan_status(obs_string_plan_tj(nops, ops, sites, spins, L, nup, ndn, P, &why), why);
+	}
+	static int64_t sector_size(int L, int nup, int ndn) { return tj_sector_size(L, nup, ndn); }
+	static bool has_sector(const Plan& P) { return P.has; }
+	static void new_sector(const Plan& P, int32_t* nup, int32_t* ndn) { *nup = P.nup2, *ndn = P.ndn2; }
+	static int64_t n_src(const Plan& P) { return P.n_up_src * P.n_dn_src; }
+	static int64_t n_dst(const Plan& P) { return P.n_up_dst * P.n_dn_dst; }
+	static bool stays(const Plan& P, int nup, int ndn) { return P.has && !P.dead && P.nup2 == nup && P.ndn2 == ndn; } // Engine.h:364, :382-383
+	static double scale(const Plan&) { return 1.0; }
+	static double reached(const Plan& P, int, int) { return (double)tj_string_touched(P); }
+
+	// one launch; none for a dead string: z = 0 or z untouched
+	static lpp_status apply(lpp_engine* e, const Plan& P, int, int, int, double fr, double fi, const void* d_src, void* d_dst, bool acc)
+	{
+		lpp_status st = check_vectors(e, fi, d_src, d_dst);
+		if (st != LPP_OK) return st;
+		if (P.dead) {
+			if (!acc) HIP_TRY(hipMemsetAsync(d_dst, 0, e->esz * (size_t)n_dst(P), e->stream));
+			HIP_TRY(hipStreamSynchronize(e->stream));
+			return LPP_OK;
+		}
+		if (n_dst(P) == 0) return LPP_OK;
+		Work W;
+		if ((st = W.sectors(e, P.L, P.nup, P.ndn, P.nup2, P.ndn2, 1)) != LPP_OK) return st;
+		ObsTjStringApplyArgs A {};
+		if ((st = W.fill(e, &P, 1, A.b, &A.ent, &A.up)) != LPP_OK) return st;
+		A.fr = fr;
+		A.fi = fi;
+		OBS_LAUNCH(k_obs_string_apply_tj, e, acc, n_dst(P), obs_tj_string_lds_bytes(A.b), d_dst, d_src, A);
+		HIP_TRY(hipStreamSynchronize(e->stream));
+		return LPP_OK;
+	}
+
+	// One pair of sectors on the device: the destination's word lists, the source's rank tables and `slots` tables of down entries in one image.  The
+	// fixed part goes up once, the entries of a batch with the batch.  The host copy stays until the struct goes: the uploads are asynchronous.
+	struct Work : DotOut {
+		DevBuf dev;
+		std::vector<int32_t> img;
+		TjStringImage G;
+		ObsTjStringDotArgs A;
+		lpp_status sectors(lpp_engine* e, int L, int nup, int ndn, int nup2, int ndn2, int slots)
+		{
+			const char* why = nullptr;
+			if (!tj_string_image_begin(G, L, nup, ndn, nup2, ndn2, slots, img, &why)) return fail(LPP_ERR_INVALID, why);
+			HIP_TRY_MEM(dev.alloc(4 * img.size()));
+			HIP_TRY(hipMemcpyAsync(dev.p, img.data(), 4 * G.fixed(), hipMemcpyHostToDevice, e->stream));
+			return LPP_OK;
+		}
+		// plans[0 .. ns) (none dead, all of the image's sectors) packed into the slots and uploaded
+		lpp_status fill(lpp_engine* e, const Plan* plans, int ns, ObsTjStringBase& B, const int32_t** d_ent, ObsTjStringUp* d_up)
+		{
+			const char* why = nullptr;
+			if (!tj_string_image_entries(G, plans, ns, img, &why)) return fail(LPP_ERR_INVALID, why);
+			const int32_t* d = (const int32_t*)dev.p;
+			int stage = 0, need_pat = 0;
+			for (int s = 0; s < ns; s++) {
+				d_ent[s] = d + G.entries(s);
+				d_up[s] = plans[s].up;
+				stage |= plans[s].up.changes;
+				need_pat |= plans[s].up.n > 0;
+			}
+			HIP_TRY(hipMemcpyAsync((int32_t*)dev.p + G.entries(0), img.data() + G.entries(0), 4 * (G.entries(ns) - G.entries(0)), hipMemcpyHostToDevice, e->stream));
+			B = ObsTjStringBase { (const uint32_t*)(d + G.down_words()), (const uint32_t*)(d + G.patterns()), d + G.hi_base(), (const uint16_t*)(d + G.lo_rank()), G.lb, G.nhi,
+				                  G.nlo, stage, need_pat, G.n_up, G.n_dn, G.n_up_src };
+			return LPP_OK;
+		}
+		lpp_status prepare(lpp_engine* e, int L, int nup, int ndn, int64_t nstrings)
+		{
+			lpp_status st = sectors(e, L, nup, ndn, nup, ndn, kObsStringBatch);
+			return st != LPP_OK ? st : alloc_out(e, G.n_up * G.n_dn, nstrings);
+		}
+		lpp_status load(lpp_engine* e, const Plan* plans, int ns, int, int, int)
+		{
+			A = ObsTjStringDotArgs {};
+			A.partial = (double*)part.p;
+			A.ns = ns;
+			return fill(e, plans, ns, A.b, A.ent, A.up);
+		}
+		void launch(lpp_engine* e, const double* bra, const double* ket, double* d_out) const
+		{
+			const size_t lds = obs_tj_string_lds_bytes(A.b);
+			if (e->is_complex) k_obs_string_dot_tj<true><<<grid, kObsBlock, lds, e->stream>>>(bra, ket, A);
+			else k_obs_string_dot_tj<false><<<grid, kObsBlock, lds, e->stream>>>(bra, ket, A);
 			reduce(e, A.ns, d_out);
 		}
 	};
@@ -1146,28 +1255,59 @@ lpp_status lpp_obs_string_plan_heis(int32_t convention, int32_t nops, const int3
 	return LPP_OK;
 }
 
-// One entry point per string family over one body<family>(name, arguments...): the Hubbard product basis, the S = 1/2 Heisenberg basis
-#define STRING_ENTRY(body, hubbard, heis, params, ...)                                 \
-	lpp_status hubbard params { return body<HubbardStrings>(#hubbard, __VA_ARGS__); } \
-	lpp_status heis params { return body<HeisStrings>(#heis, __VA_ARGS__); }
+lpp_status lpp_obs_string_plan_tj(int32_t convention, int32_t nops, const int32_t* ops, const int32_t* sites, const int32_t* spins, const int32_t* flags, int32_t nsites,
+                                  int32_t nup, int32_t ndown, int32_t* has, int32_t* nup_new, int32_t* ndown_new, int32_t* dead, uint32_t* words, int32_t* sign, int64_t* n_dst,
+                                  int64_t* touched, int64_t* action)
+{
+	if (!has) return fail(LPP_ERR_INVALID, "lpp_obs_string_plan_tj: null argument");
+	*has = 0;
+	if (convention != LPP_STRING_MANY_POINT) return fail(LPP_ERR_INVALID, "lpp_obs_string_plan_tj: the t-J basis has the many-point convention only");
+	TjStringPlan P;
+	lpp_status st = TjStrings::plan(convention, nops, ops, sites, spins, flags, nsites, nup, ndown, P);
+	if (st != LPP_OK) return st;
+	*has = P.has ? 1 : 0;
+	if (!P.has) return LPP_OK;
+	if (nup_new) *nup_new = P.nup2;
+	if (ndown_new) *ndown_new = P.ndn2;
+	if (dead) *dead = P.dead ? 1 : 0;
+	if (words) {
+		const uint32_t w[7] = { P.flip_up, P.flip_dn, P.touched, P.want_up, P.want_dn, P.par_up, P.par_dn };
+		std::memcpy(words, w, sizeof(w));
+	}
+	if (sign) *sign = P.sign;
+	if (n_dst) *n_dst = P.n_up_dst * P.n_dn_dst;
+	if (touched) *touched = tj_string_touched(P);
+	if (action) {
+		const char* why = nullptr;
+		if (!tj_string_expand(P, action, nullptr, &why)) return fail(LPP_ERR_INVALID, why);
+	}
+	return LPP_OK;
+}
 
-STRING_ENTRY(apply_string_body, lpp_engine_apply_string, lpp_engine_apply_string_heis,
+// One entry point per string family over one body<family>(name, arguments...): the Hubbard product basis, the S = 1/2 Heisenberg basis, the
+// one-orbital t-J basis
+#define STRING_ENTRY(body, hubbard, heis, tj, params, ...)                             \
+	lpp_status hubbard params { return body<HubbardStrings>(#hubbard, __VA_ARGS__); } \
+	lpp_status heis params { return body<HeisStrings>(#heis, __VA_ARGS__); }          \
+	lpp_status tj params { return body<TjStrings>(#tj, __VA_ARGS__); }
+
+STRING_ENTRY(apply_string_body, lpp_engine_apply_string, lpp_engine_apply_string_heis, lpp_engine_apply_string_tj,
              (lpp_engine* e, int32_t convention, int32_t nops, const int32_t* ops, const int32_t* sites, const int32_t* spins, const int32_t* flags, int32_t nsites, int32_t nup,
               int32_t ndown, double factor_re, double factor_im, const void* d_src, void* d_dst, int32_t accumulate, int32_t* has, int32_t* nup_new, int32_t* ndown_new),
              false, e, convention, nops, ops, sites, spins, flags, nsites, nup, ndown, factor_re, factor_im, d_src, d_dst, accumulate, has, nup_new, ndown_new)
-STRING_ENTRY(apply_string_body, lpp_engine_apply_string_host, lpp_engine_apply_string_heis_host,
+STRING_ENTRY(apply_string_body, lpp_engine_apply_string_host, lpp_engine_apply_string_heis_host, lpp_engine_apply_string_tj_host,
              (lpp_engine* e, int32_t convention, int32_t nops, const int32_t* ops, const int32_t* sites, const int32_t* spins, const int32_t* flags, int32_t nsites, int32_t nup,
               int32_t ndown, double factor_re, double factor_im, const void* src, void* dst, int32_t accumulate, int32_t* has, int32_t* nup_new, int32_t* ndown_new),
              true, e, convention, nops, ops, sites, spins, flags, nsites, nup, ndown, factor_re, factor_im, src, dst, accumulate, has, nup_new, ndown_new)
-STRING_ENTRY(many_point_body, lpp_engine_many_point, lpp_engine_many_point_heis,
+STRING_ENTRY(many_point_body, lpp_engine_many_point, lpp_engine_many_point_heis, lpp_engine_many_point_tj,
              (lpp_engine* e, int32_t convention, int32_t nstrings, const int64_t* offsets, const int32_t* ops, const int32_t* sites, const int32_t* spins, const int32_t* flags,
               int32_t nsites, int32_t nup, int32_t ndown, int32_t bra_state, int32_t ket_state, double* result),
              e, convention, nstrings, offsets, ops, sites, spins, flags, nsites, nup, ndown, bra_state, ket_state, result)
-STRING_ENTRY(many_point_host_body, lpp_engine_many_point_host, lpp_engine_many_point_heis_host,
+STRING_ENTRY(many_point_host_body, lpp_engine_many_point_host, lpp_engine_many_point_heis_host, lpp_engine_many_point_tj_host,
              (lpp_engine* e, int32_t convention, int32_t nstrings, const int64_t* offsets, const int32_t* ops, const int32_t* sites, const int32_t* spins, const int32_t* flags,
               int32_t nsites, int32_t nup, int32_t ndown, const void* bra, const void* ket, double* result),
              e, convention, nstrings, offsets, ops, sites, spins, flags, nsites, nup, ndown, bra, ket, result)
-STRING_ENTRY(bench_string_dot_body, lpp_engine_bench_string_dot, lpp_engine_bench_string_dot_heis,
+STRING_ENTRY(bench_string_dot_body, lpp_engine_bench_string_dot, lpp_engine_bench_string_dot_heis, lpp_engine_bench_string_dot_tj,
              (lpp_engine* e, int32_t convention, int32_t nstrings, const int64_t* offsets, const int32_t* ops, const int32_t* sites, const int32_t* spins, const int32_t* flags,
               int32_t nsites, int32_t nup, int32_t ndown, int32_t warmup, int32_t iters, double* ms_per_launch, double* model_bytes),
              e, convention, nstrings, offsets, ops, sites, spins, flags, nsites, nup, ndown, warmup, iters, ms_per_launch, model_bytes)

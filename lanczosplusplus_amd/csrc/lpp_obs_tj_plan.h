@@ -102,6 +102,35 @@ struct ObsTjPlan {
 	std::vector<uint16_t> lo_rank;
 };
 
+// rank(s) among the W-bit words of n set bits, ascending = by the high half, then by the low half: hi_base (2^(W - lb) entries) and lo_rank (2^lb);
+// returns lb = W / 2.  W <= 2 * kObsTjMaxHalf
+inline int tj_rank_tables(int W, int n, std::vector<int32_t>& hi_base, std::vector<uint16_t>& lo_rank)
+{
+	const int lb = W / 2, hb = W - lb;
+	std::vector<int> seen((size_t)lb + 1, 0);
+	lo_rank.resize((size_t)1 << lb);
+	for (uint32_t lo = 0; lo < (1u << lb); lo++) lo_rank[lo] = (uint16_t)seen[(size_t)__builtin_popcount(lo)]++;
+	hi_base.resize((size_t)1 << hb);
+	int64_t acc = 0;
+	for (uint32_t hi = 0; hi < (1u << hb); hi++) {
+		hi_base[hi] = (int32_t)acc;
+		acc += binom(lb, n - __builtin_popcount(hi));
+	}
+	return lb;
+}
+
+// the cnt ascending words of n set bits: the patterns of a sector by rank
+inline void tj_patterns(int n, int64_t cnt, std::vector<uint32_t>& pat)
+{
+	pat.clear();
+	pat.reserve((size_t)cnt);
+	uint64_t w = first_word(n);
+	for (int64_t i = 0; i < cnt; i++) {
+		pat.push_back((uint32_t)w);
+		if (i + 1 < cnt) w = next_word(w);
+	}
+}
+
 // what the operator asks of the destination's down word d' and what the source's down word is
 enum { DN_KEEP_OUT, DN_KEEP_IN, DN_ADD, DN_REMOVE }; // site not in d', source d' | site in d', source d' | not in d', source d' + site | in d', source d' - site
 
@@ -158,25 +187,8 @@ inline bool obs_plan_tj(int op, int site, int spin, int L, int nup, int ndn, boo
 	}
 	if (P.up != TJ_UP_SAME) {
 		if (Ws > 2 * kObsTjMaxHalf) return refuse("t-J observables: more than 24 sites free of down electrons (the pattern rank tables are kept in LDS)");
-		// rank(s) among the Ws-bit words of nup set bits, ascending = by the high half, then by the low half
-		P.lb = Ws / 2;
-		const int hb = Ws - P.lb;
-		std::vector<int> seen((size_t)P.lb + 1, 0);
-		P.lo_rank.resize((size_t)1 << P.lb);
-		for (uint32_t lo = 0; lo < (1u << P.lb); lo++) P.lo_rank[lo] = (uint16_t)seen[(size_t)__builtin_popcount(lo)]++;
-		P.hi_base.resize((size_t)1 << hb);
-		int64_t acc = 0;
-		for (uint32_t hi = 0; hi < (1u << hb); hi++) {
-			P.hi_base[hi] = (int32_t)acc;
-			acc += binom(P.lb, nup - __builtin_popcount(hi));
-		}
-		// the destination's patterns, ascending
-		P.pat.reserve((size_t)P.n_up_dst);
-		uint64_t w = first_word(P.nup2);
-		for (int64_t i = 0; i < P.n_up_dst; i++) {
-			P.pat.push_back((uint32_t)w);
-			if (i + 1 < P.n_up_dst) w = next_word(w);
-		}
+		P.lb = tj_rank_tables(Ws, nup, P.hi_base, P.lo_rank);
+		tj_patterns(P.nup2, P.n_up_dst, P.pat); // the destination's patterns, ascending
 	}
 	const Ranker R(L);
 	P.dn.assign((size_t)P.n_dn_dst, ObsTjDown { 0, 0 });

@@ -409,14 +409,17 @@ class LanczosEngine:
         check(call(self._h, _op_id(op), site, spin, L, nup, ndown, warmup, iters, C.byref(ms), C.byref(by)))
         return ms.value, by.value
 
-    # ---- products of one-site operators: -M many-point correlations and -m measure brackets (Hubbard product basis; basis="spin_half": S = 1/2 words) ----
+    # ---- products of one-site operators: -M many-point correlations and -m measure brackets (Hubbard product basis; basis="spin_half": S = 1/2 words;
+    #      basis="tj": the one-orbital t-J basis) ----
     def _refuse_strings(self, who, basis="hubbard"):
-        """t-J engines: LPP_ERR_INVALID naming the model (its basis is a follow-up).  Heisenberg engines likewise unless the caller opts into the spin
-        basis: there sz is the raw 1 - 2 bit and n reads a spin direction, so a Hubbard string carried over would silently mean something else."""
+        """t-J engines: LPP_ERR_INVALID naming the model unless the caller opts into the t-J basis: there sz is n of the given spin, not up minus down,
+        and splus ignores its spin, so a Hubbard string carried over would silently mean something else.  Heisenberg engines likewise unless the caller
+        opts into the spin basis: there sz is the raw 1 - 2 bit and n reads a spin direction."""
         _string_basis(basis)
-        if self._is_tj():
-            raise _capi.LppError(_capi.LPP_ERR_INVALID, "%s: not for the t-J (TjMultiOrb) model, operator strings are built for the Hubbard product basis" % who)
-        if self._is_heis() and basis != "spin_half":
+        if self._is_tj() and basis != "tj":
+            raise _capi.LppError(_capi.LPP_ERR_INVALID, "%s: not for the t-J (TjMultiOrb) model, operator strings are built for the Hubbard product basis; pass "
+                                 "basis=\"tj\" for strings in the t-J basis (sz is then n of the given spin, the many-point convention only)" % who)
+        if self._is_heis() and basis not in ("spin_half", "tj"):
             raise _capi.LppError(_capi.LPP_ERR_INVALID, "%s: not for the Heisenberg model, operator strings are built for the Hubbard product basis; pass "
                                  "basis=\"spin_half\" for strings of n, sz, splus, sminus in the spin basis (sz is then the raw 1 - 2 bit = -2 S^z)" % who)
 
@@ -424,12 +427,18 @@ class LanczosEngine:
         """z (+)= factor * (the whole string applied to src) in ONE launch (lpp_engine_apply_string_host): returns (z, (nup', ndown')), z starting from `out`
         or from zero, or (None, None) where the string leads to no sector.  ops and convention as operator_string_plan.  basis="spin_half": the S = 1/2
         words of BasisHeisenberg (lpp_engine_apply_string_heis_host; ops as operator_string_plan_heis, nup = szPlusConst, ndown is not read, the
-        many-point convention only); a string that is identically zero returns zeros, and LppError is raised where the reference throws."""
+        many-point convention only); a string that is identically zero returns zeros, and LppError is raised where the reference throws.
+        basis="tj": the one-orbital t-J basis (lpp_engine_apply_string_tj_host; ops as operator_string_plan_tj, the many-point convention only)."""
         self._refuse_strings("apply_operator_string", basis)
         conv, off, o, s, sp, fl = _string_arrays([ops], _string_convention(convention, basis))
         if basis == "spin_half":
             plan = operator_string_plan_heis(ops, L, nup, action=False)
             n, parts = plan["n_dst"], "%d" % plan["szPlusConst"]
+        elif basis == "tj":
+            plan = operator_string_plan_tj(ops, L, nup, ndown, action=False)
+            if plan is None:
+                return None, None
+            n, parts = plan["n_dst"], "%d, %d" % (plan["nup"], plan["ndown"])
         else:
             plan = operator_string_plan(ops, L, nup, ndown, convention)
             if plan is None:
@@ -462,7 +471,12 @@ class LanczosEngine:
         once the string has left it).  8 strings share one read of bra; a value does not depend on the batch it is computed in.
         basis="spin_half", on an engine set up by assemble_heisenberg with twiceS = 1 only: strings of n, sz, splus, sminus in the S = 1/2 basis
         (lpp_engine_many_point_heis; operator_string_plan_heis has the semantics: sz is the raw 1 - 2 bit = -2 S^z, n UP / DOWN is bit / 1 - bit).
-        Without it a Heisenberg engine is refused."""
+        Without it a Heisenberg engine is refused.
+        basis="tj", on an engine set up by assemble_tj only (keep_states_tj before lanczos; ValueError on any other engine): strings of c, cdagger, n,
+        sz, splus, sminus in the one-orbital t-J basis (lpp_engine_many_point_tj; operator_string_plan_tj has the semantics: sz is n of the given
+        spin, splus / sminus take spin 0).  Without it a t-J engine is refused."""
+        if basis == "tj" and not self._is_tj():
+            raise ValueError("many_point: basis=\"tj\" is for engines set up by assemble_tj")
         self._refuse_strings("many_point", "hubbard" if basis is None else basis)
         spin = basis == "spin_half"
         if spin and not self._is_heis("many_point"):
@@ -470,7 +484,7 @@ class LanczosEngine:
         m = self._need_model("many_point")
         conv, off, o, s, sp, fl = _string_arrays(strings, _string_convention(convention, basis))
         res = np.zeros((len(off) - 1, 2))
-        call = self._lib.lpp_engine_many_point_heis if spin else self._lib.lpp_engine_many_point
+        call = self._lib.lpp_engine_many_point_heis if spin else self._lib.lpp_engine_many_point_tj if basis == "tj" else self._lib.lpp_engine_many_point
         check(call(self._h, conv, len(off) - 1, _vp(off), _vp(o), _vp(s), _vp(sp), _vp(fl), m["L"], m["nup"], m["ndown"], int(bra), int(ket), _vp(res)))
         return self._brackets(res)
 
@@ -834,7 +848,7 @@ def _string_arrays(strings, convention):
             np.array(flags + pad, np.int32))
 
 
-STRING_BASES = ("hubbard", "spin_half")
+STRING_BASES = ("hubbard", "spin_half", "tj")
 
 
 def _string_basis(basis):
@@ -843,10 +857,39 @@ def _string_basis(basis):
 
 
 def _string_convention(convention, basis):
-    """the convention as given; the spin basis has the many-point one only (RahulOperator's labels are per fermion species)"""
-    if basis == "spin_half" and convention != "many_point":
-        raise ValueError("basis=\"spin_half\" has convention=\"many_point\" only, not %r" % (convention,))
+    """the convention as given; the spin basis has the many-point one only (RahulOperator's labels are per fermion species), and so has the t-J basis
+    (RahulOperator on it is not restated)"""
+    if basis in ("spin_half", "tj") and convention != "many_point":
+        raise ValueError("basis=\"%s\" has convention=\"many_point\" only, not %r" % (basis, convention))
     return convention
+
+
+def operator_string_plan_tj(ops, L, nup, ndown, action=True):
+    """The plan of a product of c, cdagger, n, sz, splus, sminus in the one-orbital t-J basis (lpp_obs_string_plan_tj, host only), ops = (op, site, spin)
+    or the -M text, the first acting first (Engine::manyPoint with BasisTjMultiOrbLanczos::getBraIndex): c / cdagger flip the species' own bit with
+    doSignGf, n and a raw sz are both "the bit of the given spin is set", splus makes a down site up and sminus an up site down (spin 0; value 1, no
+    sign); the sectors walk by TjMultiOrb::hasNewParts.  None where a step leads to no sector, else a dict with the final sector (nup, ndown), dead (the
+    string is identically zero), the words of
+        result[(u, d)] = sign * (-1)^popcount(us & par_up) * (-1)^popcount(ds & par_down) * src[index(us, ds)],  us = u ^ flip_up, ds = d ^ flip_down,
+        where (us & mask) == want_up and (ds & mask) == want_down,
+    n_dst, touched (the destinations the string reaches, in closed form) and, with action, action[dst] = +-(src + 1) or 0 expanded through the
+    per-down-word entries and the lookup function the kernels use."""
+    lib = _capi.lib()
+    conv, off, o, s, sp, fl = _string_arrays([ops], "many_point")
+    has, n1, n2, dead, sign = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+    n, touched = C.c_int64(), C.c_int64()
+    words = np.zeros(7, np.uint32)
+    args = (conv, int(off[-1]), _vp(o), _vp(s), _vp(sp), _vp(fl), int(L), int(nup), int(ndown), C.byref(has), C.byref(n1), C.byref(n2), C.byref(dead), _vp(words),
+            C.byref(sign), C.byref(n), C.byref(touched))
+    check(lib.lpp_obs_string_plan_tj(*args, None))
+    if not has.value:
+        return None
+    out = dict(nup=n1.value, ndown=n2.value, dead=bool(dead.value), sign=sign.value, n_dst=n.value, touched=touched.value)
+    out.update(zip(("flip_up", "flip_down", "mask", "want_up", "want_down", "par_up", "par_down"), (int(w) for w in words)))
+    if action:
+        out["action"] = np.zeros(n.value, np.int64)
+        check(lib.lpp_obs_string_plan_tj(*args, _vp(out["action"])))
+    return out
 
 
 def operator_string_plan_heis(ops, L, szPlusConst, action=True):

@@ -527,6 +527,8 @@ public:
 	// reference's getNeededBasis hands them the original sector's basis, ill-defined once the string has left it).  Orbital 0 only.
 	// Model=Heisenberg with HeisenbergTwiceS=1: the same through lpp_engine_many_point_heis -- n, sz, splus, sminus as BasisHeisenberg::getBraIndex has them
 	// (sz is the raw 1 - 2 bit); where the reference throws (c / cdagger, S+ met in the all-up sector, S- in the all-down one) LPP_ERR_INVALID is thrown.
+	// Model=TjMultiOrb with Orbitals=1 and the SolverOptions token TjOperatorStrings: the same through lpp_engine_many_point_tj -- the operators as
+	// BasisTjMultiOrbLanczos::getBraIndex has them (sz is n of the given spin); without the token the model is refused by its name.
 	ComplexOrRealType manyPoint(const VectorSizeType& sites, const std::vector<LabeledOperatorType>& what, const VectorSizeType& spins, const VectorSizeType& orbs,
 	                            const PairType& braAndKet) const
 	{
@@ -709,14 +711,26 @@ private:
 		return hamiltonian_->engine();
 	}
 
-	// manyPoint / measure: the Hubbard product basis, and for manyPoint (heisOk) the S = 1/2 Heisenberg basis; otherwise the t-J and Heisenberg models are
-	// refused as LPP_ERR_INVALID by the model's name
-	lpp_engine* stringEngine(const char* who, bool heisOk = false) const
+	// manyPoint / measure: the Hubbard product basis, and for manyPoint (manyPointOk) the S = 1/2 Heisenberg basis and, where the input opts in with the
+	// SolverOptions token TjOperatorStrings, the one-orbital t-J basis (there sz is n of the given spin and splus does not read its spin, so a Hubbard
+	// string carried over would silently mean something else); otherwise the t-J and Heisenberg models are refused as LPP_ERR_INVALID by the model's name
+	lpp_engine* stringEngine(const char* who, bool manyPointOk = false) const
 	{
 		lpp_engine* e = observableEngine(who);
-		if (tjModel() || (heisModel() && !heisOk))
-			throw std::runtime_error(std::string("LPP_ERR_INVALID: ") + who + ": not for the " + (tjModel() ? "TjMultiOrb" : "Heisenberg") + " model, operator strings are built for the Hubbard product basis\n");
+		if (tjModel() && !(manyPointOk && tjStrings()))
+			throw std::runtime_error(std::string("LPP_ERR_INVALID: ") + who + ": not for the TjMultiOrb model, operator strings are built for the Hubbard product basis"
+			                         + (manyPointOk ? "; SolverOptions=...,TjOperatorStrings opts into strings of the t-J basis (sz is then n of the given spin)\n" : "\n"));
+		if (heisModel() && !manyPointOk)
+			throw std::runtime_error(std::string("LPP_ERR_INVALID: ") + who + ": not for the Heisenberg model, operator strings are built for the Hubbard product basis\n");
 		return e;
+	}
+
+	// the input's opt-in for operator strings of the t-J basis (the reference's InputCheck is permissive, so such an input stays valid for it)
+	bool tjStrings() const
+	{
+		LppHost::String options("none");
+		if (io_.has("SolverOptions=")) io_.readline(options, "SolverOptions=");
+		return options.find("TjOperatorStrings") != LppHost::String::npos;
 	}
 
 	ComplexOrRealType bracket(lpp_engine* e, int convention, const std::vector<int32_t>& ops, const std::vector<int32_t>& sites, const std::vector<int32_t>& spins,
@@ -725,7 +739,7 @@ private:
 		const PairType parts = obsParts();
 		const int64_t off[2] = { 0, (int64_t)ops.size() };
 		double out[2] = { 0, 0 };
-		lppCheck((heisModel() ? lpp_engine_many_point_heis : lpp_engine_many_point)(e, convention, 1, off, ops.data(), sites.data(), spins.data(), flags.data(),
+		lppCheck((heisModel() ? lpp_engine_many_point_heis : tjModel() ? lpp_engine_many_point_tj : lpp_engine_many_point)(e, convention, 1, off, ops.data(), sites.data(), spins.data(), flags.data(),
 		                                                                            (int32_t)model_.geometry().numberOfSites(), (int32_t)parts.first, (int32_t)parts.second,
 		                                                                            (int32_t)braAndKet.first, (int32_t)braAndKet.second, out));
 		if constexpr (std::is_same<ComplexOrRealType, double>::value) return out[0];
