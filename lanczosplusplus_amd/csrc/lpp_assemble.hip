@@ -320,7 +320,7 @@ lpp_status assemble_hubbard_pb(lpp_engine* e, AsmParams P, int nup, int ndown, i
                                int64_t blk0 = 0, int64_t nblk_loc = -1, int64_t pitch_dn = 0, int64_t nblk_padded = 0, bool stored = false)
 {
 	*done = false;
-	if (n_up < 512) return LPP_OK;
+	if (n_up < kPbMinRowsForced) return LPP_OK; // (below one slice per row the in-block kernel has nothing to unroll over)
 	const bool cplx = e->is_complex != 0;
 	// complex hoppings (Peierls phases, KaneMele): one-window single-GPU form with the realified in-block matrix (PbState::cplx)
 	if (cplx && (nblk_loc >= 0 || pitch_dn > 0 || (getenv("LPP_PB_COMPLEX") && atoi(getenv("LPP_PB_COMPLEX")) == 0))) return LPP_OK;
@@ -331,6 +331,7 @@ lpp_status assemble_hubbard_pb(lpp_engine* e, AsmParams P, int nup, int ndown, i
 	const LayoutGate gate = layout_gate(e, "LPP_PRODUCT_LAYOUT");
 	if (gate == LayoutGate::Never) return LPP_OK;
 	const bool forced = gate == LayoutGate::Forced;
+	if (!forced && n_up < kPbMinRows) return LPP_OK;
 	if (!forced && (size_t)n_up * (size_t)n_dn * sizeof(double) < ((size_t)32 << 20)) return LPP_OK;
 	// complex hoppings run the any-number-of-groups in-block kernel (4 groups): measured 1659 against 1687 iterations/s (general layout) at
 	// 1.2e7 states (0.19 GB per vector), 327 against 170 at 6.4e7 states (1.0 GB per vector; 0.14 against 8.6 GB resident)

@@ -750,7 +750,7 @@ int pb_combine_axpy(lpp_engine* e, void* x, const void* y, const EpiScale& sc, c
 lpp_status pb_from_csr(lpp_engine* e, const DevCsr& A, int64_t n_up, bool* done)
 {
 	*done = false;
-	if (n_up < 512 || A.nrows <= 0 || A.nrows % n_up != 0 || !A.col || !A.val) return LPP_OK;
+	if (n_up < kPbMinRows || A.nrows <= 0 || A.nrows % n_up != 0 || !A.col || !A.val) return LPP_OK;
 	const bool cplx = e->is_complex != 0; // complex hoppings: realified in-block matrix, complex couplings (PbState::cplx)
 	if (cplx && getenv("LPP_PB_COMPLEX") && atoi(getenv("LPP_PB_COMPLEX")) == 0) return LPP_OK;
 	const size_t vd = cplx ? 2 : 1; // doubles per matrix value

@@ -12,6 +12,10 @@ namespace lpp {
 constexpr int kPbMaxGroups = 8; // distinct off-diagonal values of the in-block matrix
 constexpr int kPbZeroSlots = 32; // zero-valued window elements behind the row (one per LDS bank) that padding entries read
 constexpr int kPbUpThreads = 1024;
+// rows (positions per block) from which the layout is admitted: by itself, and for an uploaded CSR (pb_from_csr) / when
+// LPP_PRODUCT_LAYOUT forces it on a device-assembled Hubbard matrix (one slice of 64 rows: small sectors exist to exercise the
+// kernels' edges -- waves without a slice, a single panel --, not to be fast)
+constexpr int kPbMinRows = 512, kPbMinRowsForced = 64;
 constexpr int kPbPre = 4; // chunks (of 4 slots) of every (slice, group) requested one slice ahead
 #ifndef LPP_PB_PAIRS
 #define LPP_PB_PAIRS 1

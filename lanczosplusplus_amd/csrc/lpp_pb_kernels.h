@@ -62,6 +62,12 @@ struct PbUpArgs {
 // (scripts/experiments/r04_tcp_rate.hip: 70 against 130-140 GB/s per CU), and the number of template loads was what the gather phase of
 // this kernel waited for.
 // Look-ahead depths are then even (kPbPairs, pb_depth: lpp_pb_geom.h).
+// Waits: every s_waitcnt of the block loop is placed by the compiler, and the source is shaped so that it can COUNT (vmcnt(N), N =
+// the loads of the slice after this one) instead of draining: the wave index is a scalar, so the loop's branches are scalar ones;
+// a slice's look-ahead is a fixed number of loads with no branch around any of them; the loop has one exit; every loaded register is
+// named at the end of its slice (compute) so that nothing counts as "possibly in flight" round the loop; the barriers carry no
+// fence over global memory (pb_lds_barrier).  A list longer than the look-ahead streams its remaining chunks with a wait of its
+// own (vmcnt(0): those loads are the newest), on a path that the common one does not share.
 constexpr int kPbPreMax = 6; // deepest look-ahead of one value group (k_pb_up's PRE0)
 constexpr int kPbPreMin = 1; // chunks of a group requested whatever its list length (no branch)
 template <int GT> struct PbWords {
@@ -86,6 +92,15 @@ __device__ __forceinline__ uint32_t pb_hi8(uint32_t w)
 // LDS read at an absolute byte address (k_pb_up owns the whole LDS allocation: its dynamic array starts at address 0)
 typedef __attribute__((address_space(3))) const double pb_lds_cdouble;
 __device__ __forceinline__ double pb_lds_abs(uint32_t byte_addr) { return *(pb_lds_cdouble*)(uintptr_t)byte_addr; }
+
+// Workgroup barrier that orders LDS ONLY: this wave's LDS reads and writes are complete (lgkmcnt(0)), then s_barrier.  Unlike
+// __syncthreads() it carries no fence over global memory, so no vmcnt(0): global loads and stores stay in flight across it.
+// (The asm statement and the barrier builtin both keep the compiler from moving memory accesses across them.)
+__device__ __forceinline__ void pb_lds_barrier()
+{
+	asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+	__builtin_amdgcn_s_barrier();
+}
 
 // (LDS layout and size: pb_up_lds_bytes, lpp_pb_geom.h)
 // GT = number of value groups (1 or 2: unrolled, with look-ahead; 0: any G <= 8, plain loop).
@@ -126,7 +141,9 @@ template <bool DOT, int GT, bool CHAIN = false, int PRE0 = kPbPre> __global__ __
 	}
 	constexpr int NW = kPbUpThreads / 64;
 	constexpr int GG = GT > 0 ? GT : 1;
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	// the wave index in a SCALAR register: every slice counter derived from it is wave-uniform to the compiler, so the bound checks of
+	// the slice loop are scalar branches (no exec-mask regions around the look-ahead loads) and s_waitcnt can count across them
+	const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
 	const int p2 = (int)(a.pitch >> 1), p16 = (int)(a.pitch >> 4); // pitch is a multiple of 16
 	double dot = 0.0;
 	// plain locals for everything the stage functions touch: a reference to the kernel-argument struct inside a lambda made
@@ -148,12 +165,21 @@ template <bool DOT, int GT, bool CHAIN = false, int PRE0 = kPbPre> __global__ __
 		const double2* yb = (const double2*)(a.y + blk * a.pitch);
 		const uint4* db = (const uint4*)(a.dcode + blk * a.pitch);
 		const int64_t rowbase = blk * a.pitch;
-		__syncthreads(); // everyone is done with the previous window (and the metadata is in place)
+		// The two barriers of the block loop order LDS only (pb_lds_barrier): slices done, then the next staging; window and codes
+		// written, then read.  Nothing this kernel stores to global memory is read back from there by this kernel: r_next goes to wbuf
+		// and into the window from the SAME registers (the slices read the window, never wbuf), u is written only, ybuf and y are read
+		// only.  So the write-back of r_next and the last u stores of the block before stay in flight across the barriers instead of
+		// being drained (vmcnt(0)) at each of them.
+		pb_lds_barrier(); // everyone is done with the previous window (and the metadata is in place)
 		// stage the row of y (8 independent 16-byte loads per thread in flight, branch-free: indices beyond the row are clamped,
 		// those threads re-load and re-store the last element) and the block's diagonal codes
 		if (CHAIN) {
 			double2* const wb = (double2*)(a.wbuf + rowbase);
 			const double2* const yo = (const double2*)(a.ybuf + rowbase);
+			// the diagonal codes first: requested in front of the row loads, not behind the last store of r_next (whose completion a
+			// load issued after it would wait for: vector-memory operations retire in order)
+			const int di = min((int)threadIdx.x, p16 - 1);
+			const uint4 dc0 = db[di];
 			constexpr int NS = 4; // pairs per thread and row in flight: 2 -> 1.58 ms, 4 -> 1.57 ms, 8 spills (3.5 ms)
 			for (int i0 = threadIdx.x; i0 < p2; i0 += NS * kPbUpThreads) {
 				// loads unconditional and clamped (all of them in flight together); stores only from the lane that owns the pair -- a
@@ -178,7 +204,8 @@ template <bool DOT, int GT, bool CHAIN = false, int PRE0 = kPbPre> __global__ __
 				for (int q = 0; q < NS; q++)
 					if (i0 + q * kPbUpThreads < p2) ((double2*)win)[idx[q]] = wv[q];
 			}
-			for (int i0 = threadIdx.x; i0 < p16; i0 += kPbUpThreads) ((uint4*)dcode_s)[i0] = db[i0];
+			((uint4*)dcode_s)[di] = dc0;
+			for (int i0 = threadIdx.x + kPbUpThreads; i0 < p16; i0 += kPbUpThreads) ((uint4*)dcode_s)[i0] = db[i0]; // rows beyond 16384 elements
 		} else {
 			constexpr int NS = 8; // loads per thread and pass
 			for (int pass = 0; pass < 8 / NS; pass++) {
@@ -197,7 +224,7 @@ template <bool DOT, int GT, bool CHAIN = false, int PRE0 = kPbPre> __global__ __
 			for (int i0 = threadIdx.x + kPbUpThreads; i0 < p16; i0 += kPbUpThreads) ((uint4*)dcode_s)[i0] = db[i0];
 		}
 		if (threadIdx.x < kPbZeroSlots) win[a.pitch + threadIdx.x] = 0.0;
-		__syncthreads();
+		pb_lds_barrier();
 		const double* const yold = CHAIN ? a.ybuf + rowbase : nullptr;
 		// the row's own element and its diagonal value (code -> dictionary: two dependent LDS reads): asked for in FRONT of a slice's
 		// gathers by the look-ahead path, so that their latency passes under the gathers instead of behind them
@@ -222,18 +249,22 @@ template <bool DOT, int GT, bool CHAIN = false, int PRE0 = kPbPre> __global__ __
 			finish(j, acc, yc, dv, yo);
 		};
 		if (GT > 0) {
+			// The look-ahead of a slice j < spb (the caller checks, with a scalar branch).  Every call issues the SAME number of loads:
+			// all depth(g) / 2 chunk pairs of each group whatever the list's length (a pair beyond the list lies in the next lists or in
+			// the four pairs of slack behind the last one, repack_chunk_pairs, and is an L2 hit nobody uses), then the old row's
+			// element.  With a fixed count and no branch around a load the compiler waits for a slice's words with COUNTED vmcnt,
+			// which leaves the loads of the slice after it in flight.
 			auto load_words = [=](int j, PbWords<GG>& s) __attribute__((always_inline)) {
-				if (j >= spb) return; // wave-uniform
 #pragma unroll
 				for (int g = 0; g < GG; g++) {
 					s.nc[g] = __builtin_amdgcn_readfirstlane((int)len_s[j * GG + g]); // uniform: scalar branches below
 					constexpr int PRE0_ = PRE0;
 					const int depth = pb_depth(GG, g, PRE0_);
 					if (kPbPairs) {
-						const uint4* wp4 = tw4 + (size_t)off_s[j * GG + g] * 64 + lane; // offsets count pairs
+						const uint4* wp4 = tw4 + (size_t)__builtin_amdgcn_readfirstlane(off_s[j * GG + g]) * 64 + lane; // offsets count pairs
 #pragma unroll
 						for (int c = 0; c < kPbPreMax; c += 2)
-							if (c < depth && (c < kPbPreMin || c < s.nc[g])) {
+							if (c < depth) {
 								const uint4 t = wp4[(c >> 1) * 64];
 								s.w[g][c] = uint2 { t.x, t.y };
 								s.w[g][c + 1] = uint2 { t.z, t.w };
@@ -288,21 +319,48 @@ template <bool DOT, int GT, bool CHAIN = false, int PRE0 = kPbPre> __global__ __
 				return s0 + s1;
 			};
 			auto compute = [=](int j, const PbWords<GG>& s) __attribute__((always_inline)) {
-				if (j >= spb) return; // wave-uniform
 				double yc, dv;
 				own(j, yc, dv);
 				double acc = 0.0;
 #pragma unroll
 				for (int g = 0; g < GG; g++) acc = fma(gv[g], group_sum(j, g, s.nc[g], s.w[g], pb_depth(GG, g, PRE0)), acc);
+				// A pair beyond its list was requested and never read.  Name every pair as the input of an empty statement: the compiler
+				// then knows at the end of each slice that the whole register set has arrived (a counted wait for loads issued a slice ago,
+				// which have long returned) instead of carrying "possibly still in flight" round the loop, where it costs a near-drain
+				// in front of the next write to those registers.  No instruction is emitted.
+				if (kPbPairs) {
+#pragma unroll
+					for (int g = 0; g < GG; g++)
+#pragma unroll
+						for (int c = 0; c < kPbPreMax; c += 2)
+							if (c < pb_depth(GG, g, PRE0)) asm volatile("" ::"v"(s.w[g][c].x));
+				}
+				if (CHAIN) asm volatile("" ::"v"(s.yo)); // (its only reader sits behind the bound check of finish)
 				finish(j, acc, yc, dv, CHAIN ? s.yo : 0.0);
 			};
+			// ISSUE slice j + NW, COMPUTE slice j, in two fixed register sets.  The loop takes two slices per trip and runs only while
+			// both have a slice to issue; it has ONE exit, at its end, where the state is the same as at its back edge (the loads of set
+			// a in flight).  An exit from the middle would share a block with the back edge once the compiler has unified the loop's
+			// exits, and the state "set b still in flight" would travel round the loop from there: a wait in front of the next write to
+			// those registers, which drains the look-ahead.  The last one or two slices of a wave run behind the loop, each on a path
+			// of its own for the same reason.  All branches here are scalar.
 			PbWords<GG> wa, wb;
-			load_words(wave, wa);
-			for (int j0 = wave; j0 < spb; j0 += 2 * NW) {
-				load_words(j0 + NW, wb);
-				compute(j0, wa);
-				load_words(j0 + 2 * NW, wa);
-				compute(j0 + NW, wb);
+			int j = wave;
+			if (j < spb) {
+				load_words(j, wa);
+				for (; j + 2 * NW < spb; j += 2 * NW) {
+					load_words(j + NW, wb);
+					compute(j, wa);
+					load_words(j + 2 * NW, wa);
+					compute(j + NW, wb);
+				}
+				if (j + NW < spb) {
+					load_words(j + NW, wb);
+					compute(j, wa);
+					compute(j + NW, wb);
+				} else {
+					compute(j, wa);
+				}
 			}
 		} else {
 			for (int j = wave; j < spb; j += NW) {
@@ -316,14 +374,14 @@ template <bool DOT, int GT, bool CHAIN = false, int PRE0 = kPbPre> __global__ __
 				// four chunks of a list from chunk c0 on: four 8-byte loads, or two 16-byte loads of the pair layout
 				auto load4 = [=](size_t off, int c0, int nc, uint2* w) __attribute__((always_inline)) {
 					if (kPbPairs) {
+						// both pairs whatever the list holds, as in load_words: a fixed number of loads, no branch around one
 						const uint4* wp4 = tw4 + off * 64 + lane;
 #pragma unroll
-						for (int q = 0; q < 4; q += 2)
-							if (c0 + q < nc) {
-								const uint4 t = wp4[((c0 + q) >> 1) * 64];
-								w[q] = uint2 { t.x, t.y };
-								w[q + 1] = uint2 { t.z, t.w };
-							}
+						for (int q = 0; q < 4; q += 2) {
+							const uint4 t = wp4[((c0 + q) >> 1) * 64];
+							w[q] = uint2 { t.x, t.y };
+							w[q + 1] = uint2 { t.z, t.w };
+						}
 					} else {
 						const uint2* wp = tw2 + off * 64 + lane;
 #pragma unroll
@@ -331,7 +389,7 @@ template <bool DOT, int GT, bool CHAIN = false, int PRE0 = kPbPre> __global__ __
 							if (c0 + q < nc) w[q] = wp[(c0 + q) * 64];
 					}
 				};
-				size_t offn = (size_t)off_s[j * G];
+				size_t offn = (size_t)__builtin_amdgcn_readfirstlane(off_s[j * G]);
 				load4(offn, 0, ncn, wn);
 				for (int g = 0; g < G; g++) { // wave-uniform trip counts
 					const int nc = ncn;
@@ -341,7 +399,7 @@ template <bool DOT, int GT, bool CHAIN = false, int PRE0 = kPbPre> __global__ __
 					for (int q = 0; q < 4; q++) w[q] = wn[q];
 					if (g + 1 < G) {
 						ncn = __builtin_amdgcn_readfirstlane((int)len_s[j * G + g + 1]);
-						offn = (size_t)off_s[j * G + g + 1];
+						offn = (size_t)__builtin_amdgcn_readfirstlane(off_s[j * G + g + 1]);
 						load4(offn, 0, ncn, wn);
 					}
 					double s0 = 0.0, s1 = 0.0;
@@ -354,6 +412,7 @@ template <bool DOT, int GT, bool CHAIN = false, int PRE0 = kPbPre> __global__ __
 #pragma unroll
 						for (int q = 0; q < 4; q++)
 							if (c0 + q < nc) gather4(wr[q], s0, s1);
+						if (kPbPairs) asm volatile("" ::"v"(wr[0].x), "v"(wr[2].x)); // a pair requested beyond the list has arrived too (see compute)
 					}
 					acc = fma(a.gval[g], s0 + s1, acc);
 				}
