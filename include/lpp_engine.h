@@ -720,6 +720,68 @@ lpp_status lpp_engine_bench_string_dot_tj(lpp_engine* e, int32_t convention, int
                                           const int32_t* spins, const int32_t* flags, int32_t nsites, int32_t nup, int32_t ndown, int32_t warmup, int32_t iters,
                                           double* ms_per_launch, double* model_bytes);
 
+/* ---- site-weighted operator sums (entry points added under ABI 7, no struct changes; one GPU; csrc/lpp_obs.hip, csrc/lpp_obs_sum_kernels.h) ----
+ *     |phi> = sum_r f_r A_r |src>,   nweights = nsites complex weights f_r = w_re[r] + i w_im[r] (w_im may be NULL: real weights),
+ * the modified state of the momentum-resolved quantities: A(k,w) from c_k = sum_r e^{ikr} c_r, N(q,w), S^zz(q,w), S(q,w).  This is the project's own
+ * definition (the reference's dynamics1.cpp accumulates such a sum but its phase does not depend on the site).  A_r is what Engine::accModifiedState applies
+ * (Engine.h:535-599): c, cdagger, n of the given spin, splus, sminus as lpp_engine_apply_operator; sz = n_up/2 - n_down/2 in the Hubbard and t-J bases; the
+ * Heisenberg basis applies its raw sz (1 - 2 bit), as lpp_engine_spectral_decomposition_heis does.  Hubbard c, cdagger, n, sz go through ONE launch
+ * (k_obs_sum_move_up / _down, k_obs_sum_diag: destination driven, the terms of a destination added in ascending site from 0, so a value does not depend on the
+ * grid and two calls return the same bits), and so does the Heisenberg sz (k_obs_sum_sz_heis); everything else -- the t-J basis, splus / sminus, the Heisenberg n --
+ * and everything under LPP_OBS_SUM_CHAIN=1 (read
+ * when the engine first plans an operator; for tests and the benchmark) chains the one-site launches over the sites with a non-zero weight.  A complex weight
+ * on an f64 engine, nweights != nsites, nsites > 30 -> LPP_ERR_INVALID; engines and operators are refused where the one-site calls refuse them.  Nothing is
+ * launched by a refused call. */
+
+/* The fused plan of sum_r f_r A_r in the Hubbard product basis (host only; exposed for the CPU test-suite): *width terms per destination, W = nsites - n or n
+ * for c / cdagger (n = the moved species' destination count), 1 for n / sz.  With the four tables (n_dst * width entries each, all or none) the plan is
+ * expanded in the kernel's order: term t of destination d reads source src_index[d * width + t] with factor (fac_re, fac_im) = sign * f_site (for n / sz the
+ * source is d itself, site = -1 and the factor is the element's whole coefficient under the given weights).  splus / sminus -> LPP_ERR_INVALID: no fused plan.
+ * *has = 0: hasNewParts refused, nothing else is written. */
+lpp_status lpp_obs_sum_plan(int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, const double* w_re, const double* w_im, int32_t* has, int32_t* nup_new,
+                            int32_t* ndown_new, int64_t* n_dst, int32_t* width, int64_t* src_index, int32_t* site, double* fac_re, double* fac_im);
+
+/* z (+)= sum_r f_r A_r src on device vectors (contracts as lpp_engine_apply_operator: basis order, 16-byte aligned destination, the engine's stream, no sync). */
+lpp_status lpp_engine_apply_operator_sum(lpp_engine* e, int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t nweights, const double* w_re,
+                                         const double* w_im, const void* d_src, void* d_dst, int32_t accumulate, int32_t* has);
+lpp_status lpp_engine_apply_operator_sum_tj(lpp_engine* e, int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t nweights, const double* w_re,
+                                            const double* w_im, const void* d_src, void* d_dst, int32_t accumulate, int32_t* has);
+lpp_status lpp_engine_apply_operator_sum_heis(lpp_engine* e, int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t nweights, const double* w_re,
+                                              const double* w_im, const void* d_src, void* d_dst, int32_t accumulate, int32_t* has);
+/* the same on host vectors; *n_dst (may be NULL) = the destination's length; src == dst == NULL: *has and *n_dst only */
+lpp_status lpp_engine_apply_operator_sum_host(lpp_engine* e, int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t nweights, const double* w_re,
+                                              const double* w_im, const void* src, void* dst, int32_t accumulate, int32_t* has, int64_t* n_dst);
+lpp_status lpp_engine_apply_operator_sum_tj_host(lpp_engine* e, int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t nweights, const double* w_re,
+                                                 const double* w_im, const void* src, void* dst, int32_t accumulate, int32_t* has, int64_t* n_dst);
+lpp_status lpp_engine_apply_operator_sum_heis_host(lpp_engine* e, int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t nweights,
+                                                   const double* w_re, const double* w_im, const void* src, void* dst, int32_t accumulate, int32_t* has, int64_t* n_dst);
+/* Time `iters` sums on zeroed vectors with HIP events; model_bytes = sizeof(value) * (N_dst written, once more when accumulating, + N_src: every source
+ * element touched once) -- the same model for the fused launch and for the chain, which moves about three destination passes per site instead. */
+lpp_status lpp_engine_bench_operator_sum(lpp_engine* e, int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t nweights, const double* w_re,
+                                         const double* w_im, int32_t accumulate, int32_t warmup, int32_t iters, double* ms_per_launch, double* model_bytes);
+lpp_status lpp_engine_bench_operator_sum_tj(lpp_engine* e, int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t nweights, const double* w_re,
+                                            const double* w_im, int32_t accumulate, int32_t warmup, int32_t iters, double* ms_per_launch, double* model_bytes);
+lpp_status lpp_engine_bench_operator_sum_heis(lpp_engine* e, int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t nweights, const double* w_re,
+                                              const double* w_im, int32_t accumulate, int32_t warmup, int32_t iters, double* ms_per_launch, double* model_bytes);
+/* *norm2 = <phi|phi> for resident state `state` of sector (nup, ndown): the static structure factor; no sector engine.  *has = 0: no such sector, *norm2 = 0. */
+lpp_status lpp_engine_sum_norm2(lpp_engine* e, int32_t state, int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t nweights, const double* w_re,
+                                const double* w_im, double* norm2, int32_t* has);
+lpp_status lpp_engine_sum_norm2_tj(lpp_engine* e, int32_t state, int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t nweights, const double* w_re,
+                                   const double* w_im, double* norm2, int32_t* has);
+lpp_status lpp_engine_sum_norm2_heis(lpp_engine* e, int32_t state, int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t nweights, const double* w_re,
+                                     const double* w_im, double* norm2, int32_t* has);
+/* lpp_engine_spectral_decomposition with |phi> as the modified state (built once: no doubling), *weight = <phi|phi>.  An operator that stays in the sector
+ * (n, sz) takes a sector engine of the SAME sector. */
+lpp_status lpp_engine_spectral_decomposition_sum(lpp_engine* e, int32_t state, lpp_engine* sector, int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown,
+                                                 int32_t nweights, const double* w_re, const double* w_im, double* weight, int32_t* nsteps, double* a, double* b,
+                                                 lpp_stats* stats);
+lpp_status lpp_engine_spectral_decomposition_sum_tj(lpp_engine* e, int32_t state, lpp_engine* sector, int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown,
+                                                    int32_t nweights, const double* w_re, const double* w_im, double* weight, int32_t* nsteps, double* a, double* b,
+                                                    lpp_stats* stats);
+lpp_status lpp_engine_spectral_decomposition_sum_heis(lpp_engine* e, int32_t state, lpp_engine* sector, int32_t op, int32_t spin, int32_t nsites, int32_t nup,
+                                                      int32_t ndown, int32_t nweights, const double* w_re, const double* w_im, double* weight, int32_t* nsteps, double* a,
+                                                      double* b, lpp_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

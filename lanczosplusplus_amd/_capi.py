@@ -187,7 +187,17 @@ SYMBOLS = {
     "lpp_engine_many_point_tj": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P] + [C.c_int32] * 5 + [_P]),
     "lpp_engine_many_point_tj_host": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P] + [C.c_int32] * 3 + [_P, _P, _P]),
     "lpp_engine_bench_string_dot_tj": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P] + [C.c_int32] * 5 + [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "lpp_obs_sum_plan": (C.c_int32, [C.c_int32] * 5 + [_P, _P] + [C.POINTER(C.c_int32)] * 3 + [C.POINTER(C.c_int64), C.POINTER(C.c_int32), _P, _P, _P, _P]),
 }
+# site-weighted operator sums: one signature per call, three families
+for _sfx in ("", "_tj", "_heis"):
+    SYMBOLS["lpp_engine_apply_operator_sum" + _sfx] = (C.c_int32, [_P] + [C.c_int32] * 6 + [_P, _P, _P, _P, C.c_int32, C.POINTER(C.c_int32)])
+    SYMBOLS["lpp_engine_apply_operator_sum" + _sfx + "_host"] = (C.c_int32, [_P] + [C.c_int32] * 6 + [_P, _P, _P, _P, C.c_int32, C.POINTER(C.c_int32),
+                                                                                                         C.POINTER(C.c_int64)])
+    SYMBOLS["lpp_engine_bench_operator_sum" + _sfx] = (C.c_int32, [_P] + [C.c_int32] * 6 + [_P, _P] + [C.c_int32] * 3 + [C.POINTER(C.c_double)] * 2)
+    SYMBOLS["lpp_engine_sum_norm2" + _sfx] = (C.c_int32, [_P] + [C.c_int32] * 7 + [_P, _P, C.POINTER(C.c_double), C.POINTER(C.c_int32)])
+    SYMBOLS["lpp_engine_spectral_decomposition_sum" + _sfx] = (C.c_int32, [_P, C.c_int32, _P] + [C.c_int32] * 6 + [_P, _P, C.POINTER(C.c_double), C.POINTER(C.c_int32),
+                                                                                                                     _P, _P, C.POINTER(Stats)])
 
 _lib = None
 

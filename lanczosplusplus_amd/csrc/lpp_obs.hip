@@ -24,6 +24,8 @@
 
 #include "lpp_engine_impl.h"
 #include "lpp_obs_kernels.h"
+#include "lpp_obs_sum_plan.h"
+#include "lpp_obs_sum_kernels.h"
 #include "lpp_obs_string_plan.h"
 #include "lpp_obs_string_kernels.h"
 #include "lpp_obs_tj_kernels.h"
@@ -113,6 +115,10 @@ struct ObsBasis {
 	lpp_status (*build)(int op, int site, int spin, int L, int nup, int ndn, DevPlanPtr& out, hipError_t* err);
 	// z (+)= factor * A src through a plan with has and n_dst > 0
 	lpp_status (*launch)(lpp_engine* e, const DevPlan& D, double fr, double fi, const void* d_src, void* d_dst, bool acc);
+	// optional, the fused form of z (+)= sum_r f_r A_r src (site = -1 names its plan in the cache); null: sum_dev chains `launch` over the sites
+	bool (*sum_fused)(int op);
+	lpp_status (*build_sum)(int op, int site, int spin, int L, int nup, int ndn, DevPlanPtr& out, hipError_t* err);
+	lpp_status (*launch_sum)(lpp_engine* e, const DevPlan& D, const double* w_re, const double* w_im, const void* d_src, void* d_dst, bool acc);
 };
 
 // ---- the Hubbard product basis (plan: lpp_obs_plan.h, kernel: lpp_obs_kernels.h) ---------------------------------------------------------------
@@ -146,6 +152,68 @@ lpp_status launch_hubbard(lpp_engine* e, const DevPlan& D0, double fr, double fi
 	const ObsPlan& P = D.host;
 	ObsArgs A { D.tu, D.td, P.n_up_dst, P.n_dn_dst, P.n_up_src, P.sz ? 1 : 0, fr, fi };
 	OBS_LAUNCH(k_obs_apply, e, acc, D.n_dst, 0, d_dst, d_src, A);
+	return LPP_OK;
+}
+
+// the fused operator sum of this basis (plan: lpp_obs_sum_plan.h, kernels: lpp_obs_sum_kernels.h)
+struct HubbardSumDev : DevPlan {
+	ObsSumPlan host; // tables and word lists dropped after the upload
+	int32_t* tab = nullptr;
+	uint8_t* site = nullptr;
+	uint32_t *wu = nullptr, *wd = nullptr; // diag: the species' words
+	double *cu = nullptr, *cd = nullptr; // diag: the coefficients of the call in flight (rewritten per call, in stream order)
+	~HubbardSumDev() override { free_tables({ tab, site, wu, wd, cu, cd }); }
+};
+
+lpp_status build_hubbard_sum(int op, int, int spin, int L, int nup, int ndn, DevPlanPtr& out, hipError_t* err)
+{
+	std::unique_ptr<HubbardSumDev> D(new HubbardSumDev());
+	ObsSumPlan& P = D->host;
+	const char* why = nullptr;
+	lpp_status st = plan_status(obs_sum_plan(op, spin, L, nup, ndn, &D->has, P, &why), why);
+	if (st != LPP_OK) return st;
+	D->n_src = P.n_up_src * P.n_dn_src;
+	D->n_dst = P.n_up_dst * P.n_dn_dst;
+	D->touched = D->n_src; // every source state holds a particle c may remove / a hole cdagger may fill, or is read by the diagonal stream
+	if (D->has && P.diag) {
+		D->bytes = (4 + 16) * (P.words_up.size() + P.words_dn.size()); // the word lists and the coefficients
+		*err = upload(&D->wu, P.words_up);
+		if (*err == hipSuccess) *err = upload(&D->wd, P.words_dn);
+		if (*err == hipSuccess) *err = hipMalloc((void**)&D->cu, 16 * (size_t)std::max<int64_t>(P.n_up_dst, 1));
+		if (*err == hipSuccess) *err = hipMalloc((void**)&D->cd, 16 * (size_t)std::max<int64_t>(P.n_dn_dst, 1));
+	} else if (D->has) {
+		D->bytes = 5 * P.src.size(); // 1.0 MB per unit of W at 16 sites
+		*err = upload(&D->tab, P.src);
+		if (*err == hipSuccess) *err = upload(&D->site, P.site);
+	}
+	out = std::move(D);
+	return LPP_OK;
+}
+
+lpp_status launch_hubbard_sum(lpp_engine* e, const DevPlan& D0, const double* w_re, const double* w_im, const void* d_src, void* d_dst, bool acc)
+{
+	const HubbardSumDev& D = static_cast<const HubbardSumDev&>(D0);
+	const ObsSumPlan& P = D.host;
+	ObsSumWeights w {};
+	for (int r = 0; r < kObsSumSites; r++) { // (sum_dev pads the weights with zeros past the sites)
+		w.re[r] = w_re[r];
+		w.im[r] = w_im[r];
+	}
+	if (P.diag) {
+		for (int s = 0; s < 2; s++) {
+			const int64_t n = s ? P.n_dn_dst : P.n_up_dst;
+			const int g = (int)std::max<int64_t>(1, std::min<int64_t>((n + kObsBlock - 1) / kObsBlock, 1024));
+			if (e->is_complex) k_obs_sum_coef<true><<<g, kObsBlock, 0, e->stream>>>(s ? D.wd : D.wu, n, s ? D.cd : D.cu, w);
+			else k_obs_sum_coef<false><<<g, kObsBlock, 0, e->stream>>>(s ? D.wd : D.wu, n, s ? D.cd : D.cu, w);
+		}
+		HIP_TRY(hipGetLastError());
+		ObsSumDiagArgs A { D.cu, D.cd, P.n_up_dst, P.n_dn_dst, P.alpha, P.beta };
+		OBS_LAUNCH(k_obs_sum_diag, e, acc, D.n_dst, 0, d_dst, d_src, A);
+		return LPP_OK;
+	}
+	ObsSumMoveArgs A { D.tab, D.site, P.n, P.W, P.n_up_dst, P.n_dn_dst, P.n_up_src, w };
+	if (P.down) OBS_LAUNCH(k_obs_sum_move_down, e, acc, D.n_dst, 0, d_dst, d_src, A);
+	else OBS_LAUNCH(k_obs_sum_move_up, e, acc, D.n_dst, 0, d_dst, d_src, A);
 	return LPP_OK;
 }
 
@@ -231,13 +299,71 @@ lpp_status launch_heis(lpp_engine* e, const DevPlan& D0, double fr, double fi, c
 	return LPP_OK;
 }
 
+// the fused sum_r f_r sz_r of this basis (k_obs_sum_sz_heis): the run table and the low words of the one-site sz plan, and the runs' high parts
+struct HeisSumDev : DevPlan {
+	ObsHeisRun* runs = nullptr;
+	uint16_t* word = nullptr;
+	uint64_t* highs = nullptr;
+	double* hi = nullptr; // the coefficients of the call in flight (rewritten per call, in stream order)
+	int64_t nruns = 0;
+	int nlo = 0, lb = 0;
+	~HeisSumDev() override { free_tables({ runs, word, highs, hi }); }
+};
+
+bool heis_sum_fused_op(int op) { return op == LPP_OP_SZ; }
+
+lpp_status build_heis_sum(int op, int, int spin, int L, int nup, int, DevPlanPtr& out, hipError_t* err)
+{
+	std::unique_ptr<HeisSumDev> D(new HeisSumDev());
+	ObsHeisPlan P;
+	const char* why = nullptr;
+	lpp_status st = plan_status(obs_plan_heis(op, 0, spin, L, nup, P, &why), why); // (site 0 is in the low part: the plan has the low words)
+	if (st != LPP_OK) return st;
+	if (op != LPP_OP_SZ) return fail(LPP_ERR_INVALID, "operator sum: the Heisenberg basis has a fused plan for sz only");
+	std::vector<uint64_t> highs;
+	if (!heis_highs(L - P.lb, P.lb, P.m2, highs) || highs.size() + 1 != P.runs.size())
+		return fail(LPP_ERR_INVALID, "operator sum: the sector has more than 2^22 runs of equal high part (the run table's limit)");
+	D->has = true;
+	D->n_src = P.n_src;
+	D->n_dst = P.n_dst;
+	D->touched = P.n_dst;
+	D->nruns = (int64_t)highs.size();
+	D->nlo = (int)P.word.size();
+	D->lb = P.lb;
+	D->bytes = (sizeof(ObsHeisRun) + 8 + 16) * P.runs.size();
+	*err = upload(&D->runs, P.runs);
+	if (*err == hipSuccess) *err = upload(&D->word, P.word);
+	if (*err == hipSuccess) *err = upload(&D->highs, highs);
+	if (*err == hipSuccess) *err = hipMalloc((void**)&D->hi, 16 * (size_t)std::max<int64_t>(D->nruns, 1));
+	out = std::move(D);
+	return LPP_OK;
+}
+
+lpp_status launch_heis_sum(lpp_engine* e, const DevPlan& D0, const double* w_re, const double* w_im, const void* d_src, void* d_dst, bool acc)
+{
+	const HeisSumDev& D = static_cast<const HeisSumDev&>(D0);
+	ObsSumHeisArgs A { D.runs, D.word, D.hi, D.nlo, D.nruns, D.n_dst, 0.0, 0.0, {} };
+	for (int r = 0; r < kObsSumSites; r++) { // F in ascending site, as every sum of weights here
+		A.w.re[r] = w_re[r];
+		A.w.im[r] = w_im[r];
+		A.F_re += w_re[r];
+		A.F_im += w_im[r];
+	}
+	const int g = (int)std::max<int64_t>(1, std::min<int64_t>((D.nruns + kObsBlock - 1) / kObsBlock, 1024));
+	if (e->is_complex) k_obs_sum_hi_heis<true><<<g, kObsBlock, 0, e->stream>>>(D.highs, D.nruns, D.lb, D.hi, A.w);
+	else k_obs_sum_hi_heis<false><<<g, kObsBlock, 0, e->stream>>>(D.highs, D.nruns, D.lb, D.hi, A.w);
+	HIP_TRY(hipGetLastError());
+	OBS_LAUNCH(k_obs_sum_sz_heis, e, acc, D.n_dst, obs_sum_heis_lds_bytes(A.nlo), d_dst, d_src, A);
+	return LPP_OK;
+}
+
 enum { BASIS_HUBBARD = 0, BASIS_TJ = 1, BASIS_HEIS = 2 };
 const ObsBasis kHubbard { BASIS_HUBBARD, false, true, true, false, true, [](int L, int nup, int ndn) { return L >= 1 && nup >= 0 && ndn >= 0 && nup <= L && ndn <= L; },
-	                      hubbard_sector_size, new_parts, build_hubbard, launch_hubbard };
+	                      hubbard_sector_size, new_parts, build_hubbard, launch_hubbard, obs_sum_fused_op, build_hubbard_sum, launch_hubbard_sum };
 const ObsBasis kTj { BASIS_TJ, true, true, true, false, false, [](int L, int nup, int ndn) { return L >= 1 && nup >= 0 && ndn >= 0 && nup + ndn <= L; },
-	                 tj_sector_size, new_parts_tj, build_tj, launch_tj };
+	                 tj_sector_size, new_parts_tj, build_tj, launch_tj, nullptr, nullptr, nullptr };
 const ObsBasis kHeis { BASIS_HEIS, false, false, false, true, true, [](int L, int nup, int) { return heis_sector_size(L, nup, 0) >= 0; },
-	                   heis_sector_size, new_parts_heis, build_heis, launch_heis };
+	                   heis_sector_size, new_parts_heis, build_heis, launch_heis, heis_sum_fused_op, build_heis_sum, launch_heis_sum };
 
 // The tables of one (operator, site, spin, sites, sector), uploaded once and kept with the engine.  The key is what the caller passes -- the engine
 // needs no model for lpp_engine_apply_operator -- so the cache is bounded: a density of states or a two-point matrix uses at most 2 * sites entries
@@ -250,19 +376,28 @@ typedef std::tuple<int, int, int, int, int, int, int> PlanKey; // basis, operato
 struct ObsCache {
 	std::map<PlanKey, DevPlanPtr> plans;
 	size_t bytes = 0; // DevPlan::bytes summed over the plans
+	ObsSwitches sw = obs_switches_from_env(); // resolved once, when the engine first plans an operator
 };
 
-lpp_status get_plan(lpp_engine* e, const ObsBasis& B, int op, int site, int spin, int L, int nup, int ndn, const DevPlan** out)
+// sum: the fused plan of an operator sum (B.build_sum), kept under site = -1 -- a key no one-site plan has, the planners refuse such a site
+lpp_status get_plan(lpp_engine* e, const ObsBasis& B, int op, int site, int spin, int L, int nup, int ndn, const DevPlan** out, bool sum = false)
 {
 	if (!e->obs) e->obs = new ObsCache();
 	ObsCache* C = (ObsCache*)e->obs;
 	if (!B.reads_ndown) ndn = 0;
+	if (sum) site = -1;
+	else if (site < 0) { // the planner's own refusal, past the cache
+		DevPlanPtr D;
+		hipError_t err = hipSuccess;
+		const lpp_status st = B.build(op, site, spin, L, nup, ndn, D, &err);
+		return st != LPP_OK ? st : fail(LPP_ERR_INVALID, "observables: bad sites / site / sector");
+	}
 	const PlanKey key(B.id, op, site, spin, L, nup, ndn);
 	auto it = C->plans.find(key);
 	if (it == C->plans.end()) {
 		DevPlanPtr D;
 		hipError_t err = hipSuccess;
-		lpp_status st = B.build(op, site, spin, L, nup, ndn, D, &err);
+		lpp_status st = (sum ? B.build_sum : B.build)(op, site, spin, L, nup, ndn, D, &err);
 		if (st != LPP_OK) return st;
 		if (err != hipSuccess) {
 			D.reset(); // the tables uploaded so far
@@ -317,6 +452,63 @@ lpp_status acc_modified_dev(lpp_engine* e, const ObsBasis& B, int op, int site, 
 		return apply_dev(e, B, LPP_OP_N, site, LPP_SPIN_DOWN, L, nup, ndn, -isign * 0.5, 0.0, d_src, d_dst, true, has);
 	}
 	return apply_dev(e, B, op, site, spin, L, nup, ndn, isign, 0.0, d_src, d_dst, acc, has);
+}
+
+// the site weights of an operator sum, checked and padded with zeros to the kernels' fixed count
+struct SumWeights {
+	double re[kObsSumSites] = {}, im[kObsSumSites] = {};
+};
+lpp_status sum_weights(const lpp_engine* e, const char* who, int L, int nweights, const double* w_re, const double* w_im, SumWeights& w)
+{
+	if (!w_re) return fail(LPP_ERR_INVALID, std::string(who) + ": null weights");
+	if (L < 1 || L > kObsSumMaxSites) return fail(LPP_ERR_INVALID, std::string(who) + ": bad sites / sector");
+	if (nweights != L) return fail(LPP_ERR_INVALID, std::string(who) + ": one weight per site");
+	for (int r = 0; r < L; r++) {
+		w.re[r] = w_re[r];
+		w.im[r] = w_im ? w_im[r] : 0.0;
+		if (!e->is_complex && w.im[r] != 0.0) return fail(LPP_ERR_INVALID, std::string(who) + ": complex weight on a real engine");
+	}
+	return LPP_OK;
+}
+
+// z (+)= sum_r f_r A_r src on device vectors in the basis order, A_r as Engine::accModifiedState has them (sz of the two fermion bases is
+// n_up/2 - n_down/2; the Heisenberg basis applies its raw sz, as its spectral functions do).  One fused launch where the basis has one for the
+// operator (B.launch_sum), otherwise -- and under LPP_OBS_SUM_CHAIN=1 -- the chain of B.launch over the sites with a non-zero weight, which is
+// also the yardstick of the fused kernels.  *has == false: no such sector, nothing was launched.  The sizes are reported for the callers that stage.
+lpp_status sum_dev(lpp_engine* e, const ObsBasis& B, int op, int spin, int L, int nup, int ndn, const SumWeights& w, const void* d_src, void* d_dst, bool acc, bool* has,
+                   int64_t* n_src = nullptr, int64_t* n_dst = nullptr)
+{
+	const bool split_sz = (op == LPP_OP_SZ) && B.fermions;
+	const int op1 = split_sz ? LPP_OP_N : op; // the one-site operator whose plan names the sector and carries the basis' refusals
+	const DevPlan* D = nullptr;
+	lpp_status st = get_plan(e, B, op1, 0, spin, L, nup, ndn, &D);
+	if (st != LPP_OK) return st;
+	*has = D->has;
+	if (n_src) *n_src = D->n_src;
+	if (n_dst) *n_dst = D->n_dst;
+	if (!D->has) return LPP_OK;
+	const int64_t nd = D->n_dst;
+	if (!d_src && !d_dst) return LPP_OK; // sizes only
+	if ((st = check_vectors(e, 0.0, d_src, d_dst)) != LPP_OK) return st;
+	if (nd == 0) return LPP_OK;
+	if (B.launch_sum && B.sum_fused(op) && ((ObsCache*)e->obs)->sw.sum_chain.value_or(0) == 0) {
+		if ((st = get_plan(e, B, op, -1, spin, L, nup, ndn, &D, true)) != LPP_OK) return st;
+		return B.launch_sum(e, *D, w.re, w.im, d_src, d_dst, acc);
+	}
+	bool h = false, first = !acc;
+	for (int r = 0; r < L; r++) {
+		if (w.re[r] == 0.0 && w.im[r] == 0.0) continue;
+		if (split_sz) {
+			if ((st = apply_dev(e, B, LPP_OP_N, r, LPP_SPIN_UP, L, nup, ndn, 0.5 * w.re[r], 0.5 * w.im[r], d_src, d_dst, !first, &h)) != LPP_OK) return st;
+			st = apply_dev(e, B, LPP_OP_N, r, LPP_SPIN_DOWN, L, nup, ndn, -0.5 * w.re[r], -0.5 * w.im[r], d_src, d_dst, true, &h);
+		} else {
+			st = apply_dev(e, B, op, r, spin, L, nup, ndn, w.re[r], w.im[r], d_src, d_dst, !first, &h);
+		}
+		if (st != LPP_OK) return st;
+		first = false;
+	}
+	if (first) HIP_TRY(hipMemsetAsync(d_dst, 0, e->esz * (size_t)nd, e->stream)); // no weight: z = 0
+	return LPP_OK;
 }
 
 int blas_blocks(int64_t n2)
@@ -570,6 +762,136 @@ lpp_status spectral_body(const ObsBasis& B, const std::string& who, lpp_engine* 
 	HIP_TRY(hipMemcpyAsync(weight, (double*)part.p + nb, sizeof(double), hipMemcpyDeviceToHost, e->stream));
 	HIP_TRY(hipStreamSynchronize(e->stream)); // the sector engine runs on a stream of its own
 	return decomposition_device_any(sector, M.p, nsteps, a, b, stats); // (a hole-major sector engine takes the vector through its permutation)
+}
+
+// ---- site-weighted operator sums: z (+)= sum_r f_r A_r src, the modified state of the momentum-resolved quantities --------------------------------
+
+lpp_status apply_sum_body(const ObsBasis& B, const char* who, lpp_engine* e, int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t nweights,
+                          const double* w_re, const double* w_im, const void* d_src, void* d_dst, int32_t accumulate, int32_t* has)
+{
+	if (!e || !has || !d_src || !d_dst) return fail(LPP_ERR_INVALID, std::string(who) + ": null argument");
+	lpp_status st = refuse(e, who, B.hole_major_ok);
+	if (st != LPP_OK) return st;
+	SumWeights w;
+	if ((st = sum_weights(e, who, nsites, nweights, w_re, w_im, w)) != LPP_OK) return st;
+	HIP_TRY(hipSetDevice(e->cfg.device));
+	bool h = false;
+	st = sum_dev(e, B, op, spin, nsites, nup, ndown, w, d_src, d_dst, accumulate != 0, &h);
+	*has = h ? 1 : 0;
+	return st;
+}
+
+lpp_status apply_sum_host_body(const ObsBasis& B, const char* who, lpp_engine* e, int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t nweights,
+                               const double* w_re, const double* w_im, const void* src, void* dst, int32_t accumulate, int32_t* has, int64_t* n_dst)
+{
+	if (!e || !has) return fail(LPP_ERR_INVALID, std::string(who) + ": null argument");
+	lpp_status st = refuse(e, who, B.hole_major_ok);
+	if (st != LPP_OK) return st;
+	SumWeights w;
+	if ((st = sum_weights(e, who, nsites, nweights, w_re, w_im, w)) != LPP_OK) return st;
+	HIP_TRY(hipSetDevice(e->cfg.device));
+	bool h = false;
+	int64_t ns = 0, nd = 0;
+	if ((st = sum_dev(e, B, op, spin, nsites, nup, ndown, w, nullptr, nullptr, false, &h, &ns, &nd)) != LPP_OK) return st; // sizes and refusals
+	*has = h ? 1 : 0;
+	if (n_dst) *n_dst = nd;
+	if (!h || (!src && !dst)) return LPP_OK; // both null: the sector's size only
+	if (!src || !dst) return fail(LPP_ERR_INVALID, std::string(who) + ": null vector");
+	return staged(e, e->esz * (size_t)ns, e->esz * (size_t)nd, src, dst, accumulate, [&](const void* d_src, void* d_dst) {
+		return sum_dev(e, B, op, spin, nsites, nup, ndown, w, d_src, d_dst, accumulate != 0, &h);
+	});
+}
+
+lpp_status bench_sum_body(const ObsBasis& B, const char* who, lpp_engine* e, int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t nweights,
+                          const double* w_re, const double* w_im, int32_t accumulate, int32_t warmup, int32_t iters, double* ms_per_launch, double* model_bytes)
+{
+	if (!e || !ms_per_launch || iters < 1 || warmup < 0) return fail(LPP_ERR_INVALID, std::string(who) + ": bad argument");
+	lpp_status st = refuse(e, who, B.hole_major_ok);
+	if (st != LPP_OK) return st;
+	SumWeights w;
+	if ((st = sum_weights(e, who, nsites, nweights, w_re, w_im, w)) != LPP_OK) return st;
+	HIP_TRY(hipSetDevice(e->cfg.device));
+	bool h = false;
+	int64_t ns = 0, nd = 0;
+	if ((st = sum_dev(e, B, op, spin, nsites, nup, ndown, w, nullptr, nullptr, false, &h, &ns, &nd)) != LPP_OK) return st;
+	if (!h) return fail(LPP_ERR_INVALID, std::string(who) + ": the operator leads to no sector");
+	DevBuf ds, dd;
+	HIP_TRY_MEM(hipMalloc(&ds.p, std::max<size_t>(e->esz * (size_t)ns, 16)));
+	HIP_TRY_MEM(hipMalloc(&dd.p, std::max<size_t>(e->esz * (size_t)nd, 16) + 16));
+	HIP_TRY(hipMemsetAsync(ds.p, 0, e->esz * (size_t)ns, e->stream));
+	HIP_TRY(hipMemsetAsync(dd.p, 0, e->esz * (size_t)nd, e->stream));
+	st = timed_steps(e, warmup, iters, ms_per_launch, [&] { return sum_dev(e, B, op, spin, nsites, nup, ndown, w, ds.p, dd.p, accumulate != 0, &h); });
+	if (st != LPP_OK) return st;
+	// the byte model of the sum, whichever way it is launched: destination written (and read when accumulating), source elements touched once
+	if (model_bytes) *model_bytes = (double)e->esz * ((accumulate ? 2.0 : 1.0) * (double)nd + (double)ns);
+	return LPP_OK;
+}
+
+// |phi> = sum_r f_r A_r |resident state> in M (zero padded to a whole 16-byte unit) and <phi|phi>, read back after a stream sync.  sector: the engine
+// that will decompose |phi> (null: none); it must hold the operator's sector, which is checked after the sizes-only pass, before anything is launched
+lpp_status sum_state(const ObsBasis& B, const std::string& who, lpp_engine* e, int32_t state, int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown,
+                     int32_t nweights, const double* w_re, const double* w_im, DevBuf& M, int64_t* ndst, double* norm2, bool* has, const lpp_engine* sector = nullptr)
+{
+	lpp_status st = refuse(e, who.c_str(), B.hole_major_ok);
+	if (st != LPP_OK) return st;
+	SumWeights w;
+	if ((st = sum_weights(e, who.c_str(), nsites, nweights, w_re, w_im, w)) != LPP_OK) return st;
+	double* gs = nullptr;
+	if ((st = state_ptr(e, state, who.c_str(), &gs)) != LPP_OK) return st;
+	if (B.sector_size(nsites, nup, ndown) < 0 || e->resident_len != B.sector_size(nsites, nup, ndown))
+		return fail(LPP_ERR_INVALID, who + ": (sites, nup, ndown) is not the sector of the resident state");
+	HIP_TRY(hipSetDevice(e->cfg.device));
+	int64_t ns = 0;
+	if ((st = sum_dev(e, B, op, spin, nsites, nup, ndown, w, nullptr, nullptr, false, has, &ns, ndst)) != LPP_OK) return st;
+	if (!*has) return sector ? fail(LPP_ERR_INVALID, who + ": the operator leads to no sector (lpp_obs_new_parts)") : LPP_OK;
+	if (sector && *ndst != sector->n_global) return fail(LPP_ERR_INVALID, who + ": the sector engine does not hold the operator's sector");
+	const int wd = e->is_complex ? 2 : 1;
+	const int64_t stride = (*ndst * wd + 1) & ~(int64_t)1;
+	DevBuf part;
+	HIP_TRY_MEM(hipMalloc(&M.p, sizeof(double) * (size_t)stride + 16));
+	const int nb = blas_blocks(stride / 2);
+	HIP_TRY_MEM(hipMalloc(&part.p, sizeof(double) * (size_t)(nb + 1)));
+	HIP_TRY(hipMemsetAsync(M.p, 0, sizeof(double) * (size_t)stride + 16, e->stream)); // the padding element of an odd length stays 0
+	if ((st = sum_dev(e, B, op, spin, nsites, nup, ndown, w, gs, M.p, false, has)) != LPP_OK) return st;
+	k_dot<<<nb, kBlock, 0, e->stream>>>((const double2*)M.p, (const double2*)M.p, stride / 2, (double*)part.p);
+	k_reduce_final<<<1, kBlock, 0, e->stream>>>((const double*)part.p, nb, 1, 1, (double*)part.p + nb);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(norm2, (double*)part.p + nb, sizeof(double), hipMemcpyDeviceToHost, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	return LPP_OK;
+}
+
+lpp_status sum_norm2_body(const ObsBasis& B, const std::string& who, lpp_engine* e, int32_t state, int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown,
+                          int32_t nweights, const double* w_re, const double* w_im, double* norm2, int32_t* has)
+{
+	if (!e || !norm2 || !has) return fail(LPP_ERR_INVALID, who + ": null argument");
+	DevBuf M;
+	int64_t ndst = 0;
+	bool h = false;
+	*norm2 = 0.0;
+	lpp_status st = sum_state(B, who, e, state, op, spin, nsites, nup, ndown, nweights, w_re, w_im, M, &ndst, norm2, &h);
+	*has = h ? 1 : 0;
+	return st;
+}
+
+// spectral_body with the modified state from one sum_dev call; an operator that stays in the sector takes a sector engine of the same sector
+lpp_status spectral_sum_body(const ObsBasis& B, const std::string& who, lpp_engine* e, int32_t state, lpp_engine* sector, int32_t op, int32_t spin, int32_t nsites, int32_t nup,
+                             int32_t ndown, int32_t nweights, const double* w_re, const double* w_im, double* weight, int32_t* nsteps, double* a, double* b, lpp_stats* stats)
+{
+	if (!e || !sector || !weight || !nsteps || !a || !b) return fail(LPP_ERR_INVALID, who + ": null argument");
+	lpp_status st = refuse(sector, (who + " (sector engine)").c_str(), B.hole_major_ok);
+	if (st != LPP_OK) return st;
+	if (e->cfg.device != sector->cfg.device || e->is_complex != sector->is_complex) return fail(LPP_ERR_INVALID, who + ": the sector engine must share device and dtype");
+	if (!sector->has_matrix()) return fail(LPP_ERR_STATE, who + ": the sector engine has no matrix");
+	DevBuf M;
+	int64_t ndst = 0;
+	bool h = false;
+	if ((st = sum_state(B, who, e, state, op, spin, nsites, nup, ndown, nweights, w_re, w_im, M, &ndst, weight, &h, sector)) != LPP_OK) return st;
+	if (*weight == 0.0) { // |phi> = 0 (S^z_q=0 of a singlet, all weights zero): nothing to decompose, the fraction is identically 0
+		*nsteps = 0;
+		return LPP_OK;
+	}
+	return decomposition_device_any(sector, M.p, nsteps, a, b, stats); // (the stream of e is synchronised: the sector engine runs on a stream of its own)
 }
 
 // ---- operator strings on the device: three families, one driver -----------------------------------------------------------------------------------
@@ -1196,6 +1518,28 @@ lpp_status lpp_obs_plan(int32_t op, int32_t site, int32_t spin, int32_t nsites, 
 	return LPP_OK;
 }
 
+lpp_status lpp_obs_sum_plan(int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, const double* w_re, const double* w_im, int32_t* has, int32_t* nup_new,
+                            int32_t* ndown_new, int64_t* n_dst, int32_t* width, int64_t* src_index, int32_t* site, double* fac_re, double* fac_im)
+{
+	if (!has) return fail(LPP_ERR_INVALID, "lpp_obs_sum_plan: null argument");
+	ObsSumPlan P;
+	bool h = false;
+	const char* why = nullptr;
+	lpp_status st = plan_status(obs_sum_plan(op, spin, nsites, nup, ndown, &h, P, &why), why);
+	if (st != LPP_OK) return st;
+	*has = h ? 1 : 0;
+	if (!h) return LPP_OK;
+	if (nup_new) *nup_new = P.nup2;
+	if (ndown_new) *ndown_new = P.ndn2;
+	if (n_dst) *n_dst = P.n_up_dst * P.n_dn_dst;
+	if (width) *width = obs_sum_width(P);
+	if (src_index || site || fac_re || fac_im) {
+		if (!src_index || !site || !fac_re || !fac_im || !w_re) return fail(LPP_ERR_INVALID, "lpp_obs_sum_plan: the expansion takes all four tables and the weights");
+		obs_sum_expand(P, w_re, w_im, src_index, site, fac_re, fac_im);
+	}
+	return LPP_OK;
+}
+
 lpp_status lpp_obs_string_plan(int32_t convention, int32_t nops, const int32_t* ops, const int32_t* sites, const int32_t* spins, const int32_t* flags, int32_t nsites,
                                int32_t nup, int32_t ndown, int32_t* has, int32_t* nup_new, int32_t* ndown_new, double* scale, int64_t* n_up_dst, int64_t* n_down_dst,
                                int32_t* table_up, int32_t* table_down, int32_t* nsz, int32_t* sz)
@@ -1410,5 +1754,26 @@ OBS_ENTRY(spectral_body, lpp_engine_spectral_decomposition, lpp_engine_spectral_
           (lpp_engine* e, int32_t state, lpp_engine* sector, int32_t op, int32_t isite, int32_t jsite, int32_t spin, double isign, int32_t nsites, int32_t nup, int32_t ndown,
            double* weight, int32_t* nsteps, double* a, double* b, lpp_stats* stats),
           e, state, sector, op, isite, jsite, spin, isign, nsites, nup, ndown, weight, nsteps, a, b, stats)
+
+OBS_ENTRY(apply_sum_body, lpp_engine_apply_operator_sum, lpp_engine_apply_operator_sum_tj, lpp_engine_apply_operator_sum_heis,
+          (lpp_engine* e, int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t nweights, const double* w_re, const double* w_im, const void* d_src,
+           void* d_dst, int32_t accumulate, int32_t* has),
+          e, op, spin, nsites, nup, ndown, nweights, w_re, w_im, d_src, d_dst, accumulate, has)
+OBS_ENTRY(apply_sum_host_body, lpp_engine_apply_operator_sum_host, lpp_engine_apply_operator_sum_tj_host, lpp_engine_apply_operator_sum_heis_host,
+          (lpp_engine* e, int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t nweights, const double* w_re, const double* w_im, const void* src,
+           void* dst, int32_t accumulate, int32_t* has, int64_t* n_dst),
+          e, op, spin, nsites, nup, ndown, nweights, w_re, w_im, src, dst, accumulate, has, n_dst)
+OBS_ENTRY(bench_sum_body, lpp_engine_bench_operator_sum, lpp_engine_bench_operator_sum_tj, lpp_engine_bench_operator_sum_heis,
+          (lpp_engine* e, int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t nweights, const double* w_re, const double* w_im, int32_t accumulate,
+           int32_t warmup, int32_t iters, double* ms_per_launch, double* model_bytes),
+          e, op, spin, nsites, nup, ndown, nweights, w_re, w_im, accumulate, warmup, iters, ms_per_launch, model_bytes)
+OBS_ENTRY(sum_norm2_body, lpp_engine_sum_norm2, lpp_engine_sum_norm2_tj, lpp_engine_sum_norm2_heis,
+          (lpp_engine* e, int32_t state, int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t nweights, const double* w_re, const double* w_im,
+           double* norm2, int32_t* has),
+          e, state, op, spin, nsites, nup, ndown, nweights, w_re, w_im, norm2, has)
+OBS_ENTRY(spectral_sum_body, lpp_engine_spectral_decomposition_sum, lpp_engine_spectral_decomposition_sum_tj, lpp_engine_spectral_decomposition_sum_heis,
+          (lpp_engine* e, int32_t state, lpp_engine* sector, int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t nweights, const double* w_re,
+           const double* w_im, double* weight, int32_t* nsteps, double* a, double* b, lpp_stats* stats),
+          e, state, sector, op, spin, nsites, nup, ndown, nweights, w_re, w_im, weight, nsteps, a, b, stats)
 
 } // extern "C"

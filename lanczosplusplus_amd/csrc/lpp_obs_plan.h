@@ -94,6 +94,18 @@ inline uint64_t next_word(uint64_t w)
 	return (((r ^ w) >> 2) / c) | r;
 }
 
+// the ascending words of one species by rank (at most 32 sites)
+inline void species_words(int L, int n, std::vector<uint32_t>& out)
+{
+	const int64_t cnt = binom(L, n);
+	out.resize((size_t)cnt);
+	uint64_t w = first_word(n);
+	for (int64_t i = 0; i < cnt; i++) {
+		out[(size_t)i] = (uint32_t)w;
+		if (i + 1 < cnt) w = next_word(w);
+	}
+}
+
 // ---- one operator in the Hubbard product basis ------------------------------------------------------------------------------------------
 
 enum { SP_C, SP_CDAGGER, SP_N };

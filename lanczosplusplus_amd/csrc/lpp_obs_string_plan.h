@@ -162,18 +162,6 @@ inline bool plan_string(int conv, int nops, const int32_t* ops, const int32_t* s
 	return true;
 }
 
-// the ascending words of one species by rank
-inline void species_words(int L, int n, std::vector<uint32_t>& out)
-{
-	const int64_t cnt = binom(L, n);
-	out.resize((size_t)cnt);
-	uint64_t w = first_word(n);
-	for (int64_t i = 0; i < cnt; i++) {
-		out[(size_t)i] = (uint32_t)w;
-		if (i + 1 < cnt) w = next_word(w);
-	}
-}
-
 // ---- what is uploaded for a launch, packed on the host -----------------------------------------------------------------------------------
 
 // the sz entries of a plan as the kernels read them: entry k is 8 bits of lo (k < 8) or of hi

@@ -409,6 +409,127 @@ class LanczosEngine:
         check(call(self._h, _op_id(op), site, spin, L, nup, ndown, warmup, iters, C.byref(ms), C.byref(by)))
         return ms.value, by.value
 
+    # ---- site-weighted operator sums: |phi> = sum_r f_r A_r |src>, the modified state of A(k,w), N(q,w), S(q,w) ----
+    def apply_operator_sum(self, op, spin, weights, L, nup, ndown, src, out=None, basis="hubbard"):
+        """z (+)= sum_r weights[r] * A_r src on the GPU (lpp_engine_apply_operator_sum): returns (z, (nup', ndown')), z starting from `out` or from zero;
+        (None, None) where the operator leads to no sector.  A_r is what two_point applies: c, cdagger, n of `spin`, splus, sminus as apply_operator;
+        sz = n_up/2 - n_down/2 in the "hubbard" and "tj" bases, the raw 1 - 2 bit in "spin_half".  Hubbard c, cdagger, n, sz and the "spin_half" sz are ONE launch; the "tj"
+        basis, splus / sminus and the "spin_half" n chain the one-site launches over the sites whose weight is not exactly 0 (as everything does under
+        LPP_OBS_SUM_CHAIN=1).  Complex weights need a c128 engine."""
+        oid = _op_id(op)
+        _obs_basis(basis)
+        w = np.asarray(weights, np.complex128).ravel()
+        wr, wi = np.ascontiguousarray(w.real), np.ascontiguousarray(w.imag)
+        src = np.ascontiguousarray(src, self.np_dtype)
+        has, n = C.c_int32(), C.c_int64()
+        call = getattr(self._lib, "lpp_engine_apply_operator_sum" + _OBS_SUFFIX[basis] + "_host")
+        head = (self._h, oid, int(spin), int(L), int(nup), int(ndown), len(w), _vp(wr), _vp(wi))
+        check(call(*head, None, None, 0, C.byref(has), C.byref(n)))
+        if not has.value:
+            return None, None
+        if len(src) != sector_size(L, nup, ndown, basis):
+            raise ValueError("src does not have the length of sector (%d, %d)" % (nup, ndown))
+        if out is None:
+            z = np.zeros(n.value, self.np_dtype)
+        else:
+            z = np.ascontiguousarray(out, self.np_dtype)
+            if len(z) != n.value:
+                raise ValueError("out does not have the length of the operator's sector")
+        check(call(*head, _vp(src), _vp(z), int(out is not None), C.byref(has), C.byref(n)))
+        if basis == "spin_half":
+            return z, (new_parts(op, spin, L, nup, 0, basis) if op in ("splus", "sminus") else (nup, 0))
+        return z, (new_parts(op, spin, L, nup, ndown, basis) if op in ("c", "cdagger", "splus", "sminus") else (nup, ndown))
+
+    def bench_operator_sum(self, op, spin, weights, L, nup, ndown, warmup=2, iters=10, accumulate=False, basis="hubbard"):
+        """(ms per sum, bytes of the byte model: destination written -- and read when accumulating -- plus every source element once) on zeroed vectors"""
+        _obs_basis(basis)
+        w = np.asarray(weights, np.complex128).ravel()
+        wr, wi = np.ascontiguousarray(w.real), np.ascontiguousarray(w.imag)
+        ms, by = C.c_double(), C.c_double()
+        call = getattr(self._lib, "lpp_engine_bench_operator_sum" + _OBS_SUFFIX[basis])
+        check(call(self._h, _op_id(op), int(spin), int(L), int(nup), int(ndown), len(w), _vp(wr), _vp(wi), int(bool(accumulate)), warmup, iters, C.byref(ms), C.byref(by)))
+        return ms.value, by.value
+
+    def weighted_norm2(self, op, weights, spin=0, state=0):
+        """<phi|phi> of |phi> = sum_r weights[r] * A_r |resident state> (lpp_engine_sum_norm2): the static structure factor at the momentum the weights
+        encode; 0.0 where the operator leads to no sector.  No sector engine is needed.  On an f64 engine complex weights are split as in
+        spectral_function_weighted: <phi|phi> = <C|C> + <S|S>."""
+        m = self._need_model("weighted_norm2")
+        self._is_heis("weighted_norm2")
+        call = self._obs_call("lpp_engine_sum_norm2")
+        total = 0.0
+        for _, wr, wi in self._weight_parts(weights, m["L"]):
+            v, has = C.c_double(), C.c_int32()
+            check(call(self._h, int(state), _op_id(op), int(spin), m["L"], m["nup"], m["ndown"], len(wr), _vp(wr), _vp(wi), C.byref(v), C.byref(has)))
+            total += v.value
+        return total
+
+    def _weight_parts(self, weights, L):
+        """[(part, w_re, w_im)]: the weights as the engine takes them.  A c128 engine, or real weights: one entry, part None.  An f64 engine with complex
+        weights: the real and the imaginary weights as two REAL weight vectors, part "re" / "im"; a part whose weights are all zero is skipped."""
+        w = np.asarray(weights, np.complex128).ravel()
+        if len(w) != L:
+            raise ValueError("one weight per site (%d), got %d" % (L, len(w)))
+        wr, wi = np.ascontiguousarray(w.real), np.ascontiguousarray(w.imag)
+        if self.is_complex or not np.any(wi):
+            return [(None, wr, wi)]
+        zero = np.zeros(L)
+        return [(p, x, zero) for p, x in (("re", wr), ("im", wi)) if np.any(x)]
+
+    def spectral_function_weighted(self, op, weights, spin=0, state=0, energy=None, max_steps=200, min_steps=4, eps=1e-12, reortho=False):
+        """The continued fractions of <phi| (z -+ (H - Eg))^-1 |phi> with |phi> = sum_r weights[r] * A_r |gs> built in one pass: the momentum-resolved
+        A(k,w) (op "c" / "cdagger"), N(q,w) ("n"), S^zz(q,w) ("sz") and S(q,w) of the Heisenberg chain.  This is the project's own definition (the
+        reference accumulates such a sum with a phase that does not depend on the site).  Records follow spectral_function's diagonal types: type 0 is
+        the transpose-conjugate operator with CONJUGATED weights, type 1 the operator with the given weights; weight = s2 <phi|phi> with s = +1 (type 0)
+        / -1 (type 1), s2 = s for a bosonic operator and 1 for c / cdagger; sigma = -s.  The state is built once: there is no doubling.  A type whose
+        sector does not exist is skipped.  n and sz stay in the sector (all three bases) and NO elastic line is subtracted: the ground state's own
+        contribution |<gs|phi>|^2 at w = 0 is part of the result.
+        On an f64 engine complex weights are split: |phi> = C + i S with C = sum Re(f_r) A_r gs and S = sum Im(f_r) A_r gs; H is real symmetric and gs
+        real, so <phi|G(z)|phi> = G_CC + G_SS, and a type gives one record per non-zero part, marked part="re" / "im".  The spectral function of a type
+        is the SUM of its records' continued_fraction.  On a c128 engine, or for real weights, a type is one record with part=None.  A state of
+        zero norm (sz at q = 0 in a sector with N_up = N_down) gives a record with weight 0 and no steps; continued_fraction returns 0 for it."""
+        m = self._need_model("spectral_function_weighted")
+        self._is_heis("spectral_function_weighted")
+        L, nup, ndown = m["L"], m["nup"], m["ndown"]
+        _op_id(op)
+        if energy is None:
+            if self._energies is None:
+                raise _capi.LppError(_capi.LPP_ERR_STATE, "spectral_function_weighted: run lanczos() first (after keep_states) or pass energy")
+            energy = float(self._energies[0])
+        if self._is_tj() and op in ("splus", "sminus") and spin != _capi.LPP_SPIN_UP:  # before any sector engine is assembled
+            raise _capi.LppError(_capi.LPP_ERR_INVALID, "spectral_function_weighted: splus / sminus of the t-J basis take spin UP")
+        w = np.asarray(weights, np.complex128).ravel()
+        parts_call = self._obs_call("lpp_obs_new_parts")
+        decomp_call = self._obs_call("lpp_engine_spectral_decomposition_sum")
+        solver = dict(max_steps=max_steps, min_steps=min_steps, eps=eps, reortho=reortho, save_vectors=0)
+        records = []
+        for typ in (0, 1):
+            o = op if typ else _TRANSPOSE_CONJUGATE[op]
+            oid = OPERATORS[o]
+            has, c1, c2 = C.c_int32(1), C.c_int32(nup), C.c_int32(ndown)
+            if o not in ("n", "sz"):  # (those stay in the sector, which gets an engine of its own: self keeps its solver parameters)
+                check(parts_call(oid, spin, L, nup, ndown, C.byref(has), C.byref(c1), C.byref(c2)))
+            if not has.value:
+                continue
+            n1, n2 = c1.value, c2.value
+            s = -1 if typ else 1
+            s2 = 1.0 if o in _FERMIONIC else float(s)
+            for part, wr, wi in self._weight_parts(w if typ else np.conj(w), L):
+                eng = self._sector_engine(n1, n2, solver)
+                a = np.zeros(max_steps + 2)
+                b = np.zeros(max_steps + 2)
+                n, wt, st = C.c_int32(), C.c_double(), Stats()
+                check(decomp_call(self._h, int(state), eng._h, oid, int(spin), L, nup, ndown, L, _vp(wr), _vp(wi), C.byref(wt), C.byref(n), _vp(a), _vp(b), C.byref(st)))
+                records.append(dict(type=typ, part=part, label="%d,%d,0,0" % (spin, typ) + ("," + part if part else ""), a=a[:n.value].copy(), b=b[:n.value].copy(), Eg=energy,
+                                    weight=wt.value * s2, sigma=float(-s), modif_norm2=wt.value, steps=n.value, sector=(n1, n2),
+                                    ms_per_step=1e3 * st.seconds_total / max(st.steps_enqueued, 1), assemblies=self.sector_assemblies))
+        return records
+
+    def spectral_function_k(self, op, q, positions, **kwargs):
+        """spectral_function_weighted with the momentum weights exp(i q.x_r) / sqrt(L) (geometry.momentum_weights): A(k,w), N(q,w), S(q,w)"""
+        from . import geometry
+        return self.spectral_function_weighted(op, geometry.momentum_weights(positions, q), **kwargs)
+
     # ---- products of one-site operators: -M many-point correlations and -m measure brackets (Hubbard product basis; basis="spin_half": S = 1/2 words;
     #      basis="tj": the one-orbital t-J basis) ----
     def _refuse_strings(self, who, basis="hubbard"):
@@ -799,6 +920,28 @@ def operator_plan(op, site, spin, L, nup, ndown):
     return dict(nup=n1.value, ndown=n2.value, table_up=tu, table_down=td)
 
 
+def operator_sum_plan(op, spin, L, nup, ndown, weights=None):
+    """The fused plan of sum_r f_r A_r in the Hubbard product basis (lpp_obs_sum_plan), expanded on the host in the kernel's order: None where the
+    operator leads to no sector, else a dict with the new sector, n_dst, width (sources per destination: L - n or n for c / cdagger, 1 for n / sz) and
+    (n_dst, width) arrays src (source index), site (whose weight applies; -1 for n / sz) and factor (sign * f_site; for n / sz the element's whole
+    coefficient).  weights: default all ones, so that factor is the sign.  Raises for splus / sminus (no fused plan) and where operator_plan raises."""
+    lib = _capi.lib()
+    oid = _op_id(op)
+    w = np.ones(L, np.complex128) if weights is None else np.asarray(weights, np.complex128).ravel()
+    if len(w) != L:
+        raise ValueError("one weight per site (%d), got %d" % (L, len(w)))
+    wr, wi = np.ascontiguousarray(w.real), np.ascontiguousarray(w.imag)
+    has, n1, n2, n, wd = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64(), C.c_int32()
+    head = (oid, int(spin), int(L), int(nup), int(ndown), _vp(wr), _vp(wi), C.byref(has), C.byref(n1), C.byref(n2), C.byref(n), C.byref(wd))
+    check(lib.lpp_obs_sum_plan(*head, None, None, None, None))
+    if not has.value:
+        return None
+    shape = (n.value, wd.value)
+    src, site, fr, fi = np.zeros(shape, np.int64), np.zeros(shape, np.int32), np.zeros(shape), np.zeros(shape)
+    check(lib.lpp_obs_sum_plan(*head, _vp(src), _vp(site), _vp(fr), _vp(fi)))
+    return dict(nup=n1.value, ndown=n2.value, n_dst=n.value, width=wd.value, src=src, site=site, factor=fr + 1j * fi)
+
+
 # RahulOperator::fromString (RahulOperator.h:56-63)
 MEASURE_LABELS = {"c": _capi.LPP_OP_C, "n": _capi.LPP_OP_N, "sz": _capi.LPP_OP_SZ, "identity": _capi.LPP_OP_IDENTITY}
 STRING_CONVENTIONS = {"many_point": _capi.LPP_STRING_MANY_POINT, "measure": _capi.LPP_STRING_MEASURE}
@@ -944,6 +1087,8 @@ def continued_fraction(record, z):
         b = np.concatenate([b, np.zeros(len(a) - len(b))])
     zs = np.atleast_1d(np.asarray(z, np.complex128))
     out = np.zeros(zs.shape, np.complex128)
+    if len(a) == 0 and float(record["weight"]) == 0.0:  # a modified state of zero norm (spectral_function_weighted): no decomposition, G = 0
+        return out if np.ndim(z) else out[0]
     o = np.zeros(2)
     lib = _capi.lib()
     for k, zz in enumerate(zs.ravel()):

@@ -22,6 +22,28 @@ def chain(L, value, periodic=False):
     return m
 
 
+def momentum_weights(positions, q):
+    """exp(i q.x_r) / sqrt(L) for the L site positions x_r: the site weights of c_q = L^-1/2 sum_r e^{iqr} c_r and of n_q, S^z_q
+    (LanczosEngine.spectral_function_weighted, weighted_norm2).  positions: L numbers (a chain) or an (L, d) array; q: a number or d numbers.
+    Phases that are multiples of pi/2 to rounding give exactly real or imaginary weights (q = 0, pi, pi/2 on integer positions)."""
+    x = np.asarray(positions, np.float64)
+    if x.ndim == 1:
+        x = x[:, None]
+    qv = np.atleast_1d(np.asarray(q, np.float64))
+    if x.ndim != 2 or qv.shape != (x.shape[1],):
+        raise ValueError("positions (L, d) and q (d) do not match")
+    phase = x @ qv
+    w = np.exp(1j * phase)
+    # A phase within its own rounding error of a multiple of pi/2 gives the exact 1, i, -1, -i: sin(pi r) is a residue of 1e-16, not a weight, and
+    # would otherwise make the chain launch a site and the f64 split decompose a part for nothing.  (The phase is a sum of d products: its error is
+    # a few ulps of |phase|.)
+    t = phase / (np.pi / 2)
+    k = np.rint(t)
+    axis = np.abs(t - k) <= 4 * np.finfo(float).eps * np.maximum(1.0, np.abs(t)) * x.shape[1]
+    w[axis] = np.array([1, 1j, -1, -1j])[k[axis].astype(np.int64) % 4]
+    return w / np.sqrt(len(x))
+
+
 def ladder(L, leg, value_x, value_y, periodic_x=False, periodic_y=False):
     """leg-leg ladder / 2-D lattice: site = x*leg + y, x along the legs."""
     if L % leg:

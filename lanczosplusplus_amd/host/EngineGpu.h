@@ -656,6 +656,66 @@ public:
 		}
 	}
 
+	// The momentum-resolved spectral function (this project's own definition, lpp_engine_spectral_decomposition_sum): the continued fractions of
+	// |phi> = sum_r weights[r] A_r |gs>, built in one pass on the device.  Records follow spectralFunction's diagonal types: type 0 is the transpose-conjugate
+	// operator with conjugated weights, type 1 the operator with the given weights; weight = s2 <phi|phi>, sigma = -s, s2 = s for a bosonic operator; the
+	// state is built once (no doubling).  n and sz stay in the sector and decompose there, for every model; no elastic line is subtracted.  A real engine
+	// splits complex weights: |phi> = C + i S with real C, S and <phi|G|phi> = G_CC + G_SS, one record per non-zero part, labelled "...,re" / "...,im":
+	// the spectral function of a type is the sum of its records.
+	template <typename ContinuedFractionCollectionType>
+	void spectralFunctionWeighted(ContinuedFractionCollectionType& cfCollection, VectorStringType& vstr, const LabeledOperatorType& lOperator1,
+	                              const std::vector<std::complex<double>>& weights, const std::vector<PairType>& spins) const
+	{
+		typedef typename ContinuedFractionCollectionType::ContinuedFractionType ContinuedFractionType;
+		lpp_engine* e = observableEngine("spectralFunctionWeighted");
+		const int n = (int)model_.geometry().numberOfSites();
+		if ((int)weights.size() != n) throw std::runtime_error("spectralFunctionWeighted: one weight per site\n");
+		const LabeledOperatorType lOperator2 = lOperator1.transposeConjugate();
+		const PairType oldParts = obsParts();
+		const bool isReal = std::is_same<ComplexOrRealType, double>::value;
+		ParametersForSolverType params(io_, "Spectral");
+		for (SizeType si = 0; si < spins.size(); si++) {
+			if (spins[si].first != spins[si].second) throw std::runtime_error("spectralFunctionWeighted: no support yet for off-diagonal spin\n");
+			const int32_t spin = (int32_t)spins[si].first;
+			for (SizeType type = 0; type < 2; ++type) {
+				const LabeledOperatorType& lOperator = (type & 1) ? lOperator1 : lOperator2;
+				int32_t has = 1, nup2 = (int32_t)oldParts.first, ndown2 = (int32_t)oldParts.second;
+				if (lOperator.needsNewBasis())
+					lppCheck((heisModel() ? lpp_obs_new_parts_heis : tjModel() ? lpp_obs_new_parts_tj : lpp_obs_new_parts)(lOperator.id(), spin, n, (int32_t)oldParts.first,
+					                                                                                                      (int32_t)oldParts.second, &has, &nup2, &ndown2));
+				if (!has) continue;
+				std::vector<double> wr((size_t)n), wi((size_t)n);
+				bool anyIm = false;
+				for (int r = 0; r < n; r++) {
+					wr[(size_t)r] = weights[(size_t)r].real();
+					wi[(size_t)r] = (type & 1) ? weights[(size_t)r].imag() : -weights[(size_t)r].imag();
+					anyIm = anyIm || wi[(size_t)r] != 0.0;
+				}
+				const bool split = isReal && anyIm;
+				for (int part = 0; part < (split ? 2 : 1); part++) {
+					std::vector<double> pr = (split && part == 1) ? wi : wr, pi = split ? std::vector<double>((size_t)n, 0.0) : wi;
+					if (split && std::all_of(pr.begin(), pr.end(), [](double v) { return v == 0.0; })) continue;
+					lpp_engine* sector = sectorEngine(nup2, ndown2, params);
+					TridiagonalMatrixType ab;
+					ab.resize(params.steps + 2);
+					double weight = 0;
+					int32_t nsteps = 0;
+					lppCheck((heisModel() ? lpp_engine_spectral_decomposition_sum_heis : tjModel() ? lpp_engine_spectral_decomposition_sum_tj : lpp_engine_spectral_decomposition_sum)(
+					    e, 0, sector, lOperator.id(), spin, n, (int32_t)oldParts.first, (int32_t)oldParts.second, n, pr.data(), pi.data(), &weight, &nsteps, &ab.a(0), &ab.b(0), nullptr));
+					ab.a_.resize(nsteps);
+					ab.b_.resize(nsteps);
+					if (std::sqrt(weight) < 1e-10) std::cerr << "spectralFunctionWeighted: modifVector==0, type=" << type << "\n";
+					const int s = (type & 1) ? -1 : 1;
+					const RealType s2 = lOperator.isFermionic() ? 1 : s;
+					ContinuedFractionType cf;
+					cf.set(ab, energies_[0], weight * s2, -s);
+					vstr.push_back(std::to_string(spin) + "," + std::to_string(type) + ",0,0" + (split ? (part ? ",im" : ",re") : ""));
+					cfCollection.push(cf);
+				}
+			}
+		}
+	}
+
 	// ReducedDensityMatrix (ReducedDensityMatrix.h:40-76) of the resident ground state for the lattice cut at `split` (sites 0 .. split-1 kept), as the
 	// blocks of fixed particle numbers (k_up, k_down) in the kept sites: rho(r, c) = sum over the environment of conj(psi(alpha[r], beta)) psi(alpha[c], beta)
 	// -- the conjugate on the row index (:73).  The Hubbard family, for which the states are resident; other models throw, as the reference's unpack does (:87).

@@ -1,7 +1,7 @@
 // lanczos.cpp -- driver with the reference's command line for this path (src/lanczos.cpp:99-226,
 // src/Engine/LanczosDriver1.h:47-66): reads an InputNg-style file (the reference's TestSuite inputs work
 // unmodified for the in-scope models), builds the model, runs the GPU engine, prints "Energy=".
-//   lanczos -f input.inp [-p precision] [-d device] [-g operator] [-c operator] [-s "s1,s2;..."] [-r siteForSplit] [-M "op?site?spin;...,..."] [-m "<gs|op;op|gs>,..."]
+//   lanczos -f input.inp [-p precision] [-d device] [-g operator [-k momentumIndex | -w weightsFile]] [-c operator] [-s "s1,s2;..."] [-r siteForSplit] [-M "op?site?spin;...,..."] [-m "<gs|op;op|gs>,..."]
 // SolverOptions=useComplex selects complex<double> (lanczos.cpp:194-226).  -c prints the two-point matrix of the ground state, -g writes the
 // continued fractions of the spectral function for the site pairs the input names (TSPSites, TSPCenter=, DoAllPairs=,
 // ComputeDensityOfStates=) into <input basename><counter>.comb (LanczosDriver1.h:81-199; Hubbard family, TjMultiOrb with Orbitals=1 and Heisenberg with HeisenbergTwiceS=1 -- where `-g sz` decomposes the reference's raw 1 - 2 bit = -2 S^z --, one GPU).  -r prints the reduced density
@@ -38,6 +38,9 @@ struct LanczosOptions {
 	int split = -1; // -r siteForSplit (LanczosOptions.h), -1: no reduced density matrix
 	LppHost::String extendedStatic; // -M
 	std::vector<LppHost::String> measure; // -m, one entry per occurrence
+	int momentum = -1; // -k m: the -g operators summed over the sites with f_r = exp(2 pi i m r / L) / sqrt(L), instead of the site pairs
+	LppHost::String weightsFile; // -w file: the same with L lines of `re im`
+	bool weighted() const { return momentum >= 0 || !weightsFile.empty(); }
 };
 
 static std::vector<LppHost::String> splitString(const LppHost::String& s, char sep)
@@ -195,8 +198,55 @@ int mainLoop3(const ModelType& model, LppHost::InputReadable& io, int device, in
 		for (SizeType i = 0; i < n; ++i)
 			for (SizeType j = 0; j < n; ++j) pairOfSites.push_back(PairSizeType(i, j));
 
+	// -g with -k / -w: one .comb file per operator holding the continued fractions of sum_r f_r A_r |gs> (Engine::spectralFunctionWeighted), in place
+	// of the site pairs; the header names the momentum or the weights' file
+	if (lanczosOptions.weighted()) {
+		std::vector<std::complex<double>> weights(n);
+		if (lanczosOptions.momentum >= 0) {
+			const double pi = std::acos(-1.0);
+			// the phase is m r / L of a turn: reduced in integers, and exact on the axes, so that a commensurate momentum (m = 0, L/2; quarter turns)
+			// has weights that ARE real or imaginary -- a rounding residue of sin(pi r) would otherwise pass for a weight and get a record of its own
+			for (SizeType r = 0; r < n; ++r) {
+				const SizeType t = ((SizeType)lanczosOptions.momentum * r) % n; // t / n of a turn
+				const double a = 1.0 / std::sqrt((double)n), ph = 2.0 * pi * (double)t / (double)n;
+				double re = a * std::cos(ph), im = a * std::sin(ph);
+				if ((4 * t) % n == 0) { // a multiple of a quarter turn
+					const SizeType q = 4 * t / n;
+					re = (q == 0) ? a : (q == 2) ? -a : 0.0;
+					im = (q == 1) ? a : (q == 3) ? -a : 0.0;
+				}
+				weights[r] = std::complex<double>(re, im);
+			}
+		} else {
+			std::ifstream fin(lanczosOptions.weightsFile.c_str());
+			if (!fin) throw std::runtime_error("lanczos: cannot read " + lanczosOptions.weightsFile + "\n");
+			for (SizeType r = 0; r < n; ++r) {
+				double re = 0, im = 0;
+				if (!(fin >> re >> im)) throw std::runtime_error("lanczos: " + lanczosOptions.weightsFile + " must hold one line `re im` per site\n");
+				weights[r] = std::complex<double>(re, im);
+			}
+		}
+		for (SizeType gfi = 0; gfi < lanczosOptions.gf.size(); ++gfi) {
+			std::cout << "#gf(weighted)\n";
+			typename EngineType::VectorStringType vstr;
+			ContinuedFractionCollection<ContinuedFraction> cfCollection;
+			engine.spectralFunctionWeighted(cfCollection, vstr, lanczosOptions.gf[gfi], weights, lanczosOptions.spins);
+			const LppHost::String outName = filename + std::to_string(gfi) + ".comb";
+			std::ofstream ioOut(outName.c_str());
+			if (!ioOut) throw std::runtime_error("lanczos: cannot write " + outName + "\n");
+			if (lanczosOptions.momentum >= 0) ioOut << "Momentum=" << lanczosOptions.momentum << "\n";
+			else ioOut << "Weights=" << lanczosOptions.weightsFile << "\n";
+			ioOut << "#INDEXTOCF ";
+			for (SizeType i = 0; i < vstr.size(); ++i) ioOut << vstr[i] << " ";
+			ioOut << "\n";
+			cfCollection.write(ioOut);
+			ioOut.close();
+			if (!ioOut) throw std::runtime_error("lanczos: cannot write " + outName + "\n");
+			std::cerr << "lanczos: Written to " << outName << "\n";
+		}
+	}
 	// -g (LanczosDriver1.h:138-183): one .comb file per site pair, in the working directory
-	for (SizeType gfi = 0; gfi < lanczosOptions.gf.size(); ++gfi) {
+	for (SizeType gfi = 0; gfi < lanczosOptions.gf.size() && !lanczosOptions.weighted(); ++gfi) {
 		SizeType counter = 0;
 		for (SizeType sIndex = 0; sIndex < pairOfSites.size(); ++sIndex) {
 			const SizeType site0 = pairOfSites[sIndex].first, site1 = pairOfSites[sIndex].second;
@@ -456,11 +506,11 @@ int main(int argc, char** argv)
 	LppHost::String file;
 	int device = 0, precision = 8, opt = 0;
 	bool partitioned = false;
-	const char* usage = " -f filename [-p precision] [-d device] [-P] [-g operator] [-c operator] [-s \"s1,s2;...\"] [-r siteForSplit] [-M \"op?site?spin;...\"] [-m \"<gs|op;op|gs>\"]\n";
+	const char* usage = " -f filename [-p precision] [-d device] [-P] [-g operator [-k momentumIndex | -w weightsFile]] [-c operator] [-s \"s1,s2;...\"] [-r siteForSplit] [-M \"op?site?spin;...\"] [-m \"<gs|op;op|gs>\"]\n";
 	LanczosOptions lanczosOptions;
 	LppHost::String spinsArg;
 	std::vector<LppHost::String> gfArgs, cicjArgs;
-	while ((opt = getopt(argc, argv, "f:p:d:Pg:c:s:r:M:m:")) != -1) {
+	while ((opt = getopt(argc, argv, "f:p:d:Pg:c:s:r:M:m:k:w:")) != -1) {
 		switch (opt) {
 		case 'f': file = optarg; break;
 		case 'g': gfArgs.push_back(optarg); break;
@@ -469,6 +519,8 @@ int main(int argc, char** argv)
 		case 'r': lanczosOptions.split = atoi(optarg); break;
 		case 'M': lanczosOptions.extendedStatic = optarg; break;
 		case 'm': lanczosOptions.measure.push_back(optarg); break;
+		case 'k': lanczosOptions.momentum = atoi(optarg); break;
+		case 'w': lanczosOptions.weightsFile = optarg; break;
 		case 'p': precision = atoi(optarg); break;
 		case 'd': device = atoi(optarg); break;
 		case 'P': partitioned = true; break;
@@ -483,6 +535,8 @@ int main(int argc, char** argv)
 		for (const LppHost::String& g : gfArgs) lanczosOptions.gf.push_back(LabeledOperator(g));
 		for (const LppHost::String& c : cicjArgs) lanczosOptions.cicj.push_back(LabeledOperator(c));
 		if (!spinsArg.empty()) fillSpins(lanczosOptions.spins, spinsArg);
+		if (lanczosOptions.weighted() && gfArgs.empty()) throw std::runtime_error("-k / -w give the site weights of -g: not without -g\n");
+		if (lanczosOptions.momentum >= 0 && !lanczosOptions.weightsFile.empty()) throw std::runtime_error("-k and -w both give the site weights: one of them\n");
 		if (partitioned && (!gfArgs.empty() || !cicjArgs.empty() || lanczosOptions.split >= 0 || !lanczosOptions.extendedStatic.empty() || !lanczosOptions.measure.empty()))
 			throw std::runtime_error("-g / -c / -r / -M / -m run on one GPU: not with -P\n");
 		LppHost::InputReadable io(file);
