@@ -102,6 +102,15 @@ __device__ __forceinline__ void pb_lds_barrier()
 	__builtin_amdgcn_s_barrier();
 }
 
+// Every vector-memory operation of this wave has completed (gfx9 encoding of s_waitcnt: vmcnt 0, expcnt 7 and lgkmcnt 15 = not
+// waited for).  The builtin is an instruction the compiler's wait placement reads; the empty statement keeps memory accesses from
+// being moved across it.
+__device__ __forceinline__ void pb_wait_vm0()
+{
+	__builtin_amdgcn_s_waitcnt(0x0F70);
+	asm volatile("" ::: "memory");
+}
+
 // (LDS layout and size: pb_up_lds_bytes, lpp_pb_geom.h)
 // GT = number of value groups (1 or 2: unrolled, with look-ahead; 0: any G <= 8, plain loop).
 // CHAIN: the chained form of the scale-free Lanczos step (pb_launch_chain).  The previous step left w = H r/b - (b/b') r' complete
@@ -113,6 +122,12 @@ __device__ __forceinline__ void pb_lds_barrier()
 // gathers, 1 read, 1 write) in two launches, instead of 9 in three with the separate combine pass (2 + 2 + 5).  (Keeping the old row in
 // registers for the beta term here would save the re-read, but 2 x 13 registers on top of the look-ahead words spill: 476 bytes of
 // scratch per lane at KC = 14.)
+// Staging of the chained form: ONE round trip to memory per block, and most of it under the block before.  The row of w goes into
+// the window by 16-byte global-to-LDS loads behind the barrier that frees the window; the old vector's row (NS pairs per thread) and
+// the diagonal codes, which this kernel only reads, are requested one block ahead from the tail of the slice loop and carried in
+// registers (request_old); every thread corrects in LDS the pairs its own lane has loaded and writes them back.  A timing-only
+// build without the re-read of the old row in the slices is 0.06 ms per step faster at config 2 (2.62 against 2.68 ms): what keeping
+// part of that row in the LDS behind the window could at most win, in proportion to the part that fits (5312 of 12870 positions).
 // PRE0 (two value groups): chunks of group 0 requested one slice ahead; group 1 gets 2 kPbPre - PRE0.  The lists of the two
 // groups are not equally long (config 2: hops with sign + average 11.7 entries per row, 4-5 chunks; sign -: 5.4 entries, 2-3
 // chunks), and a chunk beyond the look-ahead is a load with a full L2 round trip in the middle of a slice.  The host picks
@@ -161,6 +176,34 @@ template <bool DOT, int GT, bool CHAIN = false, int PRE0 = kPbPre> __global__ __
 		s0 += pb_lds_abs(pb_lo8(w.y));
 		s1 += pb_lds_abs(pb_hi8(w.y));
 	};
+	// Chained form: what a block's staging needs and this kernel never writes -- the old vector's row (ybuf) and the diagonal codes -- is
+	// requested one block AHEAD, into registers that the block loop carries: NS pairs per thread (rows of 12870 positions: 6.3) and one
+	// 16-byte word of codes.  The requests are branch-free like the slice look-ahead (a branch around a load merges "nothing newer in
+	// flight" into the waits behind it, which then drain): where there is no next block, or nothing to subtract (gco == 0: the first
+	// step reads no old row), every lane's index is masked to 0 and the loads collapse into one line of a row that is mapped anyway.
+	// (two value groups with the deepest look-ahead, PRE0 = 6, hold ten chunks of words per slice: one pair fewer there, or the tail spills;
+	// a row's remaining pairs take the staging's second trip)
+	constexpr int NS = GT == 2 && PRE0 >= 6 ? 6 : 7;
+	double2 yv[NS] = {};
+	uint4 dc0 = {};
+	const bool sub = gco != 0.0;
+	const double* const ybuf = a.ybuf;
+	const uint8_t* const dcode_g = a.dcode;
+	const int64_t pitch = a.pitch, n_blk = a.n_blk;
+	auto request_old = [=](int64_t nb, double2(&yq)[NS], uint4& dc) __attribute__((always_inline)) {
+		const bool live = nb < n_blk;
+		const int64_t base = (live ? nb : n_blk - 1) * pitch;
+		const int my = live && sub ? -1 : 0, md = live ? -1 : 0;
+		// (the thread index through an empty statement: the indices below are then formed where they are used, two instructions each,
+		// instead of living in eight registers from block to block, which spilled)
+		int t = threadIdx.x;
+		asm volatile("" : "+v"(t));
+		dc = ((const uint4*)(dcode_g + base))[min(t, p16 - 1) & md];
+		const double2* const yo = (const double2*)(ybuf + base);
+#pragma unroll
+		for (int q = 0; q < NS; q++) yq[q] = yo[min(t + q * kPbUpThreads, p2 - 1) & my];
+	};
+	if (CHAIN) request_old(blockIdx.x, yv, dc0);
 	for (int64_t blk = blockIdx.x; blk < a.n_blk; blk += gridDim.x) {
 		const double2* yb = (const double2*)(a.y + blk * a.pitch);
 		const uint4* db = (const uint4*)(a.dcode + blk * a.pitch);
@@ -175,36 +218,52 @@ template <bool DOT, int GT, bool CHAIN = false, int PRE0 = kPbPre> __global__ __
 		// those threads re-load and re-store the last element) and the block's diagonal codes
 		if (CHAIN) {
 			double2* const wb = (double2*)(a.wbuf + rowbase);
-			const double2* const yo = (const double2*)(a.ybuf + rowbase);
-			// the diagonal codes first: requested in front of the row loads, not behind the last store of r_next (whose completion a
-			// load issued after it would wait for: vector-memory operations retire in order)
-			const int di = min((int)threadIdx.x, p16 - 1);
-			const uint4 dc0 = db[di];
-			constexpr int NS = 4; // pairs per thread and row in flight: 2 -> 1.58 ms, 4 -> 1.57 ms, 8 spills (3.5 ms)
-			for (int i0 = threadIdx.x; i0 < p2; i0 += NS * kPbUpThreads) {
-				// loads unconditional and clamped (all of them in flight together); stores only from the lane that owns the pair -- a
-				// clamped lane would subtract g r a second time from a pair its owner has already updated in place
-				double2 wv[NS], yv[NS];
-				int idx[NS];
-#pragma unroll
-				for (int q = 0; q < NS; q++) idx[q] = min(i0 + q * kPbUpThreads, p2 - 1);
-#pragma unroll
-				for (int q = 0; q < NS; q++) wv[q] = wb[idx[q]];
-				if (gco != 0.0) {
-#pragma unroll
-					for (int q = 0; q < NS; q++) yv[q] = yo[idx[q]];
-#pragma unroll
-					for (int q = 0; q < NS; q++) {
-						wv[q].x -= gco * yv[q].x; // padding: 0 - g 0
-						wv[q].y -= gco * yv[q].y;
-						if (i0 + q * kPbUpThreads < p2) wb[idx[q]] = wv[q];
-					}
-				}
+			double2* const win2 = (double2*)win;
+			// ONE round trip to memory per block.  The row of w goes straight into the window with the 16-byte global-to-LDS load (no
+			// registers; lane l of a wave's instruction lands at the instruction's LDS base + 16 l, which is where its pair belongs: the
+			// window starts at LDS address 0), while the old row's pairs and the codes are in flight already, requested a block ago
+			// (request_old).  A thread then corrects, in LDS, exactly the pairs its own lane has loaded -- a global-to-LDS load is ordered
+			// for the wave that issued it by that wave's vmcnt, for nobody else before the barrier -- and writes them back to wbuf.  A
+			// lane beyond the row loads and stores nothing (its old-row index is clamped, its pair unused): r_next is formed once per pair.
+			// The wait is this block's only one on memory in front of the slices; it also covers the u stores of the block before,
+			// which are older.
+			auto stage_row = [=](int i0, int ldsbase, const double2(&yq)[NS]) __attribute__((always_inline)) {
 #pragma unroll
 				for (int q = 0; q < NS; q++)
-					if (i0 + q * kPbUpThreads < p2) ((double2*)win)[idx[q]] = wv[q];
+					if (i0 + q * kPbUpThreads < p2)
+						__builtin_amdgcn_global_load_lds(wb + i0 + q * kPbUpThreads, (__attribute__((address_space(3))) void*)(uintptr_t)(uint32_t)((ldsbase + q * kPbUpThreads) * 16), 16, 0, 0);
+				// vmcnt(0) as the BUILTIN (0x0F70: the other counters left alone), so that the compiler's own count knows the row has
+				// landed: behind a wait in inline assembly it would still hold the global-to-LDS loads for pending writes to LDS and put
+				// a vmcnt(0) of its own in front of the next LDS read -- behind the stores of r_next below, which would be drained
+				pb_wait_vm0();
+				if (sub) {
+#pragma unroll
+					for (int q = 0; q < NS; q++) {
+						const int i = i0 + q * kPbUpThreads;
+						if (i < p2) {
+							double2 wv = win2[i];
+							wv.x -= gco * yq[q].x; // padding: 0 - g 0
+							wv.y -= gco * yq[q].y;
+							win2[i] = wv;
+							wb[i] = wv;
+						}
+					}
+				}
+			};
+			int t0 = threadIdx.x; // (through an empty statement, as in request_old: no per-pair address kept from block to block)
+			asm volatile("" : "+v"(t0));
+			stage_row(t0, wave * 64, yv);
+			((uint4*)dcode_s)[min(t0, p16 - 1)] = dc0;
+			// rows of more than NS x 1024 pairs: further trips, each with its own request of the old row
+			for (int i0 = threadIdx.x + NS * kPbUpThreads; i0 < p2; i0 += NS * kPbUpThreads) {
+				const double2* const yo = (const double2*)(ybuf + rowbase);
+				double2 yt[NS] = {};
+				if (sub) {
+#pragma unroll
+					for (int q = 0; q < NS; q++) yt[q] = yo[min(i0 + q * kPbUpThreads, p2 - 1)];
+				}
+				stage_row(i0, __builtin_amdgcn_readfirstlane(i0 - lane), yt);
 			}
-			((uint4*)dcode_s)[di] = dc0;
 			for (int i0 = threadIdx.x + kPbUpThreads; i0 < p16; i0 += kPbUpThreads) ((uint4*)dcode_s)[i0] = db[i0]; // rows beyond 16384 elements
 		} else {
 			constexpr int NS = 8; // loads per thread and pass
@@ -344,6 +403,11 @@ template <bool DOT, int GT, bool CHAIN = false, int PRE0 = kPbPre> __global__ __
 			// exits, and the state "set b still in flight" would travel round the loop from there: a wait in front of the next write to
 			// those registers, which drains the look-ahead.  The last one or two slices of a wave run behind the loop, each on a path
 			// of its own for the same reason.  All branches here are scalar.
+			// Chained form: the tail is also where a wave asks for the NEXT block's old row and codes (request_old), behind its last
+			// look-ahead and in front of its last one or two slices.  There the register sets of a further look-ahead are dead, and the
+			// counted waits for the tail's own words leave these younger loads in flight: they travel under the tail's gathers and the
+			// skew of the end-of-block barrier instead of behind it.  Nothing waits for them before the staging's own wait: the tail
+			// counts vmcnt(17) down to (8) with the eight of them behind it, and neither barrier waits for memory.
 			PbWords<GG> wa, wb;
 			int j = wave;
 			if (j < spb) {
@@ -354,13 +418,31 @@ template <bool DOT, int GT, bool CHAIN = false, int PRE0 = kPbPre> __global__ __
 					load_words(j + 2 * NW, wa);
 					compute(j + NW, wb);
 				}
-				if (j + NW < spb) {
+				if (CHAIN) {
+					// ONE path for both tails: a wave whose last trip has a single slice asks for that slice's words a second time (L2
+					// hits nobody reads), so that the request stands behind the same loads either way.  As two paths the tails shared
+					// their last store, and the register copy in front of it waited with vmcnt(0) -- for the request.
+					const bool two = j + NW < spb;
+					load_words(two ? j + NW : j, wb);
+					request_old(blk + gridDim.x, yv, dc0);
+					compute(j, wa);
+					if (two) compute(j + NW, wb);
+				} else if (j + NW < spb) {
 					load_words(j + NW, wb);
 					compute(j, wa);
 					compute(j + NW, wb);
 				} else {
 					compute(j, wa);
 				}
+			}
+			// A wave without a slice asks here, on a branch of its own whose condition the compiler cannot fold into the one above (it
+			// passes through an empty statement, in a scalar register: still a scalar branch).  As the else of that condition the request
+			// lay on a static path INTO the slices, and every wave then waited at its first slice for loads into these registers that
+			// it had never issued -- a vmcnt(0) behind the stores of r_next.
+			if (CHAIN) {
+				int idle = __builtin_amdgcn_readfirstlane((int)(wave >= spb));
+				asm volatile("" : "+s"(idle));
+				if (idle) request_old(blk + gridDim.x, yv, dc0);
 			}
 		} else {
 			for (int j = wave; j < spb; j += NW) {
@@ -418,6 +500,8 @@ template <bool DOT, int GT, bool CHAIN = false, int PRE0 = kPbPre> __global__ __
 				}
 				epilogue(j, acc, yo_g);
 			}
+			// (this loop has no peeled tail: the next block's old row and codes are requested behind it, under the barrier's skew)
+			if (CHAIN) request_old(blk + gridDim.x, yv, dc0);
 		}
 	}
 	if (DOT) {
