@@ -17,7 +17,7 @@ PbSwitches pb_switches_from_env()
 	sw.wide = rd("LPP_PB_WIDE"), sw.bank_ways = rd("LPP_PB_BANK_WAYS"), sw.perm = rd("LPP_PB_PERM"), sw.seg = rd("LPP_PB_SEG"), sw.pre0 = rd("LPP_PB_PRE0");
 	sw.down_rounds = rd("LPP_PB_DOWN_ROUNDS"), sw.order_window = rd("LPP_PB_ORDER_WINDOW"), sw.down_image = rd("LPP_PB_DOWN_IMAGE"), sw.pace = rd("LPP_PB_PACE");
 	sw.chain = rd("LPP_PB_CHAIN"), sw.down_tasks = rd("LPP_PB_DOWN_TASKS"), sw.down_pf = rd("LPP_PB_DOWN_PF"), sw.chain_pace = rd("LPP_PB_CHAIN_PACE");
-	sw.lazy_tx = rd("LPP_PB_LAZY_TX");
+	sw.lazy_tx = rd("LPP_PB_LAZY_TX"), sw.down_grid = rd("LPP_PB_DOWN_GRID");
 	sw.verbose = rd("LPP_VERBOSE").set;
 	return sw;
 }
@@ -506,6 +506,9 @@ lpp_status plan_down_geometry(const PbSwitches& sw, const Choice& c, int num_cus
 {
 	PbForm& B = P.form;
 	int grid = num_cus & ~7;
+	// LPP_PB_DOWN_GRID=n (diagnostic): n workgroups instead of one per CU, a multiple of 8 from 8 up to that -- the ranges of hundreds of blocks
+	// per workgroup that only the largest sectors have (the 64-block unit of plan_rounds, more than 64 tasks per step) on a matrix of test size
+	if (sw.down_grid.set && grid >= 8) grid = std::max(8, std::min(sw.down_grid.v, grid)) & ~7;
 	if (grid < 8) grid = num_cus; // fewer than 8 CUs: one group
 	P.slots = grid >= 8 ? grid / 8 : grid;
 	B.rowcap = (int)std::max<int64_t>(4, (longest_list + 3) & ~(int64_t)3);
@@ -574,6 +577,7 @@ void pb_plan_print(const PbPlan& P)
 		for (int g = 0; g < T.G; g++) fprintf(stderr, "lpp: template group %d: slices with 0..8+ chunks: %d %d %d %d %d %d %d %d %d\n", g, hist[g][0], hist[g][1], hist[g][2], hist[g][3], hist[g][4], hist[g][5], hist[g][6], hist[g][7], hist[g][8]);
 		if (!T.flen.empty()) fprintf(stderr, "lpp: template far slots / 4 per slice 0..8+: %d %d %d %d %d %d %d %d %d; %lld entries in pieces, %lld far\n", fh[0], fh[1], fh[2], fh[3], fh[4], fh[5], fh[6], fh[7], fh[8], (long long)T.entries, (long long)T.far_entries);
 	}
+	fprintf(stderr, "lpp: coupling kernel grid %d (%d workgroups per group, %d blocks each in %d rounds of %d)\n", B.down_grid, P.slots, B.ids_per_wg, B.down_rounds, B.ids_per_round);
 	fprintf(stderr, "lpp: product-basis launch forms: chain %d, down tasks %d, chained counter form %d, pacing dropped %d, lazy exchange %d\n", B.chain_ok ? 1 : 0,
 	        B.down_tasks ? 1 : 0, B.down_pf ? 1 : 0, B.chain_drop_pace ? 1 : 0, B.lazy_tx ? 1 : 0);
 }

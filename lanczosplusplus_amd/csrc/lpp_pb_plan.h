@@ -37,7 +37,7 @@ struct PbBuildInput {
 
 struct PbSwitches { // LPP_PB_<NAME> (EnvSwitch, lpp_switch.h), in the order pb_plan consults them
 	EnvSwitch big2, big2_four, piece_rows, parts, wide, bank_ways, perm, seg, pre0, down_rounds, order_window, down_image, pace, chain, down_tasks, down_pf,
-	    chain_pace, lazy_tx;
+	    chain_pace, lazy_tx, down_grid;
 	bool verbose = false; // LPP_VERBOSE
 };
 PbSwitches pb_switches_from_env(); // the only getenv of the product-basis build (lpp_pb_plan.cpp)

@@ -3,7 +3,8 @@
 // Inputs are made here: the hopping matrix of one species on a ring or open chain, enumerated from bit words, as T, and that of another species
 // as the block couplings C.  Over small species, block counts, CU counts, the exchange on and off and the forced forms it checks what every plan
 // must satisfy (permutations, P T P^T, the chunk-pair repack, coupling codes, block bases, block order, rounds, part starts, LDS bounds), the
-// launch forms at the sizes of the suite's 2x6 ladder, and the text of every refusal these sizes reach.
+// launch forms at the sizes of the suite's 2x6 ladder, the coupling kernel's geometry at 256 CUs for the cases of tests/test_gpu_pb_down_edges.py
+// (the forced grid and forced rounds included), and the text of every refusal these sizes reach.
 // Prints `ok` and returns 0, or says what failed and returns 1.
 #include <algorithm>
 #include <cmath>
@@ -225,7 +226,9 @@ void check_plan(const PbBuildInput& in, const PbSwitches& sw, int num_cus, const
 	CHECK(B.nnz_loc == P.base[(size_t)(B.blk0 + B.nblk_loc)] - P.base[(size_t)B.blk0]);
 	CHECK(in.cx ? P.cdict.size() == 512 : P.cdict.empty());
 	// the coupling kernel's geometry
-	CHECK(B.down_grid == (num_cus >= 8 ? (num_cus & ~7) : num_cus) && P.slots == (num_cus >= 8 ? B.down_grid / 8 : num_cus));
+	int want_grid = num_cus >= 8 ? (num_cus & ~7) : num_cus;
+	if (sw.down_grid.set && num_cus >= 8) want_grid = std::max(8, std::min(sw.down_grid.v, want_grid)) & ~7; // LPP_PB_DOWN_GRID: a multiple of 8 from 8 to the CUs'
+	CHECK(B.down_grid == want_grid && B.down_grid <= std::max(num_cus, 1) && P.slots == (num_cus >= 8 ? B.down_grid / 8 : num_cus));
 	CHECK((int64_t)B.ids_per_wg * P.slots >= n_blk && (int64_t)(B.ids_per_wg - 1) * P.slots < n_blk);
 	CHECK(B.rowcap % 4 == 0 && B.rowcap >= 4);
 	for (int64_t b = 0; b < n_blk; b++) CHECK(P.cp[(size_t)b + 1] - P.cp[(size_t)b] <= B.rowcap);
@@ -311,6 +314,13 @@ std::vector<Forced> forced_forms()
 		f.back().sw.pace = on(0);
 		f.back().sw.order_window = on(0);
 	}
+	for (const int g : { 8, 20, 4096, -3 }) { // the forced grid: as given, rounded down to a multiple of 8, clamped from above and from below
+		f.push_back({ "grid", PbSwitches() });
+		f.back().sw.down_grid = on(g);
+	}
+	f.push_back({ "grid 8, rounds", PbSwitches() });
+	f.back().sw.down_grid = on(8);
+	f.back().sw.down_rounds = on(2);
 	f.push_back({ "basis order, wide", PbSwitches() });
 	f.back().sw.perm = on(0);
 	f.back().sw.wide = on(1);
@@ -478,6 +488,137 @@ void check_launch_forms()
 	}
 }
 
+// hopping matrix of n particles on L sites for any symmetric real hop[L * L] (zero: no bond), same basis and sign rule as species()
+Csr species_of(int L, int n, const std::vector<double>& hop)
+{
+	std::vector<uint32_t> words;
+	for (uint32_t w = 0; w < (1u << L); w++)
+		if (__builtin_popcount(w) == n) words.push_back(w);
+	Csr A;
+	A.n = (int64_t)words.size();
+	A.rp.assign(1, 0);
+	std::vector<std::pair<int32_t, double>> row;
+	for (const uint32_t w : words) {
+		row.clear();
+		for (int from = 0; from < L; from++)
+			for (int to = 0; to < L; to++) {
+				const double t = hop[(size_t)from * L + to];
+				if (from == to || t == 0.0 || !((w >> from) & 1) || ((w >> to) & 1)) continue;
+				const int lo = std::min(from, to), hi = std::max(from, to);
+				const uint32_t between = w & ((1u << hi) - 1) & ~((1u << (lo + 1)) - 1);
+				row.push_back({ (int32_t)(std::lower_bound(words.begin(), words.end(), w ^ (1u << from) ^ (1u << to)) - words.begin()), (__builtin_popcount(between) & 1) ? -t : t });
+			}
+		std::sort(row.begin(), row.end());
+		for (const auto& en : row) {
+			A.ci.push_back(en.first);
+			A.va.push_back(en.second);
+		}
+		A.rp.push_back((int64_t)A.ci.size());
+	}
+	return A;
+}
+std::vector<double> hop_all_to_all(int L) // every pair of sites, +-1 (the signs do not enter the geometry: the suite's matrices draw them from a seed)
+{
+	std::vector<double> h((size_t)L * L, 0.0);
+	for (int i = 0; i < L; i++)
+		for (int j = 0; j < L; j++)
+			if (i != j) h[(size_t)i * L + j] = ((i + j) & 1) ? -1.0 : 1.0;
+	return h;
+}
+std::vector<double> hop_ring(int L, double t1, double t2) // nearest neighbours t1 on the ring, second neighbours t2 on the open chain
+{
+	std::vector<double> h((size_t)L * L, 0.0);
+	for (int i = 0; i < L; i++) {
+		h[(size_t)i * L + (i + 1) % L] = h[(size_t)((i + 1) % L) * L + i] = t1;
+		if (i + 2 < L) h[(size_t)i * L + i + 2] = h[(size_t)(i + 2) * L + i] = t2;
+	}
+	return h;
+}
+
+// tests/test_gpu_pb_down_edges.py: the coupling kernel's geometry at 256 CUs for every case of that file, under the forced grid and the forced rounds
+void check_down_edge_cases()
+{
+	struct Want {
+		int slots, ids_per_wg, rounds, ids_per_round, rowcap;
+	};
+	auto pin = [&](const char* name, const PbBuildInput& in, const PbSwitches& sw, const Want& w) {
+		PbPlan P;
+		if (pb_plan(in, sw, 256, P) != LPP_OK) {
+			if (failures++ < 20) std::printf("FAILED down edges %s: refused \"%s\"\n", name, lpp_last_error());
+			return PbPlan();
+		}
+		const PbForm& B = P.form;
+		if (P.slots != w.slots || B.down_grid != 8 * w.slots || B.ids_per_wg != w.ids_per_wg || B.down_rounds != w.rounds || B.ids_per_round != w.ids_per_round || B.rowcap != w.rowcap) {
+			if (failures++ < 20)
+				std::printf("FAILED down edges %s: slots %d, grid %d, ids_per_wg %d, rounds %d, ids_per_round %d, rowcap %d\n", name, P.slots, B.down_grid, B.ids_per_wg, B.down_rounds, B.ids_per_round, B.rowcap);
+		}
+		check_plan(in, sw, 256, P);
+		return P;
+	};
+	PbSwitches none, rounds2, grid8, grid8_rounds2, rounds2_rebuilt;
+	rounds2.down_rounds = on(2);
+	rounds2_rebuilt.down_rounds = on(2);
+	rounds2_rebuilt.down_image = on(0);
+	grid8.down_grid = on(8);
+	grid8_rounds2.down_grid = on(8);
+	grid8_rounds2.down_rounds = on(2);
+	const std::vector<double> a8 = hop_all_to_all(8), a10 = hop_all_to_all(10), a12 = hop_all_to_all(12);
+	Problem p;
+	make_problem(p, species_of(8, 4, a8), species_of(8, 1, a8), false); // 8 blocks: 24 of the 32 workgroups of a group own nothing; lists of 7
+	CHECK(p.in.n_up == 70 && p.in.n_blk == 8);
+	pin("(8,4,1)", p.in, none, { 32, 1, 1, 1, 8 });
+	make_problem(p, species_of(8, 4, a8), species_of(8, 3, a8), false); // lists of 15
+	CHECK(p.in.n_blk == 56);
+	pin("(8,4,3)", p.in, none, { 32, 2, 1, 2, 16 });
+	make_problem(p, species_of(10, 3, a10), species_of(10, 5, a10), false); // lists of 25: 28 places, a stride of 28
+	CHECK(p.in.n_blk == 252 && pb_down_stride(28) == 28);
+	pin("(10,3,5)", p.in, none, { 32, 8, 1, 8, 28 });
+	make_problem(p, species_of(12, 2, a12), species_of(12, 6, a12), false); // lists of 36
+	CHECK(p.in.n_blk == 924 && p.in.n_up == 66);
+	pin("(12,2,6)", p.in, none, { 32, 29, 1, 29, 36 });
+	pin("(12,2,6) rounds 2", p.in, rounds2, { 32, 29, 2, 16, 36 }); // units of 8: 16 + 13
+	{ // one workgroup per group owns all 924 blocks: 116 tasks, image and task sums inside 150 KB, so the counter forms and the chained step stay
+		const PbPlan P = pin("(12,2,6) grid 8", p.in, grid8, { 1, 924, 1, 924, 36 });
+		CHECK(P.form.down_lds == 140464 && P.form.down_lds_pf == 140464 + 116 * 32 && P.form.down_lds_pf <= kPbDownLdsMax);
+		CHECK(P.form.chain_ok && P.form.down_pf && P.form.down_tasks && P.form.chain_drop_pace && P.image_bytes == 0);
+		const PbPlan Q = pin("(12,2,6) grid 8 rounds 2", p.in, grid8_rounds2, { 1, 924, 2, 512, 36 }); // 512 blocks and more per workgroup: units of 64, 512 + 412
+		CHECK(!Q.form.chain_ok && Q.image_bytes == 2 * pb_down_lds_bytes(512, 36));
+	}
+	{
+		const std::vector<double> h = hop_ring(11, -1.0, 0.5);
+		make_problem(p, species_of(11, 5, h), species_of(11, 4, h), false); // lists of 4 to 14, four coupling values, 29 panels
+		CHECK(p.in.n_blk == 330 && p.in.ndict == 5 && pb_pitch_for(p.in.n_up) / 16 == 29);
+		const PbPlan P = pin("t-t' (11,5,4)", p.in, none, { 32, 11, 1, 11, 16 });
+		int64_t lo = 1 << 30;
+		for (int64_t b = 0; b < 330; b++) lo = std::min(lo, P.cp[(size_t)b + 1] - P.cp[(size_t)b]);
+		CHECK(lo == 4 && P.pace_counters == 8 * 29);
+	}
+	make_problem(p, species(14, 2, true, -1.0), species(14, 4, true, -1.0), false);
+	CHECK(p.in.n_blk == 1001);
+	pin("(14,2,4)", p.in, none, { 32, 32, 1, 32, 8 });
+	pin("(14,2,4) rounds 2", p.in, rounds2, { 32, 32, 2, 16, 8 }); // the last workgroup owns 1001 - 31 * 32 = 9 blocks: its second round is empty
+	pin("(14,2,4) rounds 2, rebuilt", p.in, rounds2_rebuilt, { 32, 32, 2, 16, 8 });
+	{ // a last round that would be empty for EVERY workgroup is trimmed: 3 rounds of 16 blocks asked for 32 per workgroup
+		PbSwitches rounds3;
+		rounds3.down_rounds = on(3);
+		pin("(14,2,4) rounds 3", p.in, rounds3, { 32, 32, 2, 16, 8 });
+	}
+	make_problem(p, species(15, 2, true, -1.0), species(15, 6, true, -1.0), false); // 20 tasks per workgroup against 16 waves
+	CHECK(p.in.n_blk == 5005);
+	pin("(15,2,6)", p.in, none, { 32, 157, 1, 157, 12 });
+	{
+		Problem q;
+		make_complex_problem(q, species(11, 5, true, -1.0, 0.37), species(11, 4, true, -1.0, 0.37));
+		CHECK(q.in.n_blk == 330 && q.in.n_up == 924);
+		const PbPlan P = pin("Peierls (11,5,4)", q.in, none, { 32, 11, 1, 11, 8 });
+		CHECK(P.form.cplx && P.form.chain_ok && P.pace_counters == 8 * 58);
+		PbSwitches pf0;
+		pf0.down_pf = on(0);
+		const PbPlan Q = pin("Peierls (11,5,4), fixed shares", q.in, pf0, { 32, 11, 1, 11, 8 });
+		CHECK(Q.form.cplx && Q.form.chain_ok && !Q.form.down_pf && !Q.form.chain_drop_pace); // k_pb_down<1024, true, false, true, false>
+	}
+}
+
 } // namespace
 
 int main()
@@ -514,6 +655,7 @@ int main()
 	CHECK(seen_perm > 0 && seen_seg > 0 && seen_big2 > 0 && seen_rounds3 > 0 && seen_parts3 > 0 && seen_two_groups > 0);
 	check_refusals();
 	check_launch_forms();
+	check_down_edge_cases();
 	if (failures) {
 		std::printf("%d checks failed (%d plans, %d refusals)\n", failures, plans, refused);
 		return 1;

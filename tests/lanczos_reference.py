@@ -6,7 +6,8 @@ Gram-Schmidt).  The twin shares nothing with the engine: it measures what the al
 the bound the device is held to.  Nothing here reads the engine's output.
 
 The cases of tests/test_gpu_lanczos_steps.py are listed here (CASES_A, CASES_B, CASES_C, CASE_D, pb_case) so that tests/test_lanczos_reference_host.py can assert
-their input conditions without a GPU.
+their input conditions without a GPU.  So are the cases of tests/test_gpu_pb_down_edges.py (PB_DOWN_CASES), with the elementwise bound of a product
+(product_bound) and the coupling kernel's launch geometry restated (down_geometry).
 """
 from collections import namedtuple
 
@@ -303,6 +304,48 @@ K_E = 16
 SEED_E = 4321
 
 
+def all_to_all(L, magnitudes, seed):
+    """_all_to_all of tests/test_gpu_pb_up_waits.py, restated (that module needs a GPU to import; tests/test_gpu_pb_down_edges.py asserts they agree)"""
+    rng = np.random.default_rng(seed)
+    m = np.zeros((L, L))
+    for i in range(L):
+        for j in range(i + 1, L):
+            m[i, j] = m[j, i] = rng.choice(magnitudes) * rng.choice([-1.0, 1.0])
+    return m
+
+
+def peierls_ring(L, phase=0.37):
+    """_phases of tests/test_gpu_pb_up_staging.py, restated: a ring with a Peierls phase on every bond"""
+    from helpers import chain
+    up = np.triu(np.ones((L, L)), 1) > 0
+    return chain(L, -1.0, True).astype(complex) * np.where(up, np.exp(1j * phase), np.exp(-1j * phase))
+
+
+# group F (tests/test_gpu_pb_down_edges.py): the coupling kernel's own structure.  name -> (L, n_up, n_down, hopping); U = 4 on every site, no
+# potentials.  C(L, n_up) positions per block, C(L, n_down) blocks; a block's coupling list is the down species' hops out of its configuration.
+def _ring2(L):
+    from helpers import chain
+    return chain(L, -1.0, True) + 0.5 * (np.diag(np.ones(L - 2), 2) + np.diag(np.ones(L - 2), -2))
+
+
+def _ring(L):
+    from helpers import chain
+    return chain(L, -1.0, True)
+
+
+PB_DOWN_CASES = {
+    "a2a_8_4_1": (8, 4, 1, lambda: all_to_all(8, [1.0], 3)),
+    "a2a_8_4_3": (8, 4, 3, lambda: all_to_all(8, [1.0], 3)),
+    "a2a_10_3_5": (10, 3, 5, lambda: all_to_all(10, [1.0], 3)),
+    "a2a_12_2_6": (12, 2, 6, lambda: all_to_all(12, [1.0], 11)),
+    "ttp_ring_11_5_4": (11, 5, 4, lambda: _ring2(11)),
+    "ring_14_2_4": (14, 2, 4, lambda: _ring(14)),
+    "ring_15_2_6": (15, 2, 6, lambda: _ring(15)),
+    "peierls_11_5_4": (11, 5, 4, lambda: peierls_ring(11)),
+}
+K_F_LARGE_ROWS = 200000  # cases above it run 8 steps, the others 16
+
+
 def pb_case(name):
     """(L, nup, ndown, hop, U, V)"""
     from helpers import chain
@@ -310,13 +353,96 @@ def pb_case(name):
         return 12, 6, 6, chain(12, -1.0, False), np.full(12, 4.0), np.zeros(24)
     if name == "disorder":
         return 12, 6, 5, chain(12, -1.0, True), np.random.default_rng(5).uniform(1, 5, 12), np.random.default_rng(6).uniform(-0.5, 0.5, 24)
+    if name in PB_DOWN_CASES:
+        L, nup, ndown, hop = PB_DOWN_CASES[name]
+        return L, nup, ndown, hop(), np.full(L, 4.0), np.zeros(2 * L)
     raise KeyError(name)
+
+
+def pb_rows(name):
+    from math import comb
+    L, nup, ndown = (PB_DOWN_CASES[name] if name in PB_DOWN_CASES else pb_case(name))[:3]
+    return comb(L, nup) * comb(L, ndown)
+
+
+def pb_is_complex(name):
+    return name == "peierls_11_5_4"
+
+
+def pb_steps(name):
+    return 8 if pb_rows(name) > K_F_LARGE_ROWS else K_E
 
 
 def pb_matrix(name):
     import oracle
     A = oracle.hubbard_csr(*pb_case(name))
     return Csr(A.rowptr, A.colind, A.values, A.nrows)
+
+
+def pb_start(name):
+    return start_vector(pb_rows(name), pb_is_complex(name), SEED_E)
+
+
+# ---- the elementwise bound of a product ---------------------------------------------------------------------------------------------------
+def product_bound(H, x0, y):
+    """bound[i] on |fl(x0 + H y)_i - (x0 + H y)_i| for ANY double-precision evaluation: (nnz_i + 4) 2^-53 (|x0_i| + sum_j |H_ij| |y_j|), the
+    first-order forward bound of a sum of nnz_i products accumulated in any order, with or without FMA, plus four more roundings (the scale, the
+    diagonal and the two adds of a combine pass).  Complex rows: (2 nnz_i + 6) 2^-53 with moduli (a complex product is two real products and an add
+    per component).  Derived, not measured; evaluated in long double."""
+    cplx = np.iscomplexobj(H.values) or np.iscomplexobj(y)
+    per_row = np.diff(H.rowptr).astype(LD)
+    mass = np.abs(np.asarray(x0)).astype(LD) + product(H, np.abs(H.values).astype(LD), np.abs(np.asarray(y)).astype(LD))
+    return ((2 * per_row + 6) if cplx else (per_row + 4)) * LD(2.0) ** -53 * mass
+
+
+def product_reference(H, x0, y):
+    """x0 + H y in long double"""
+    t = CLD if (np.iscomplexobj(H.values) or np.iscomplexobj(y)) else LD
+    return np.asarray(x0).astype(t) + product(H, H.values.astype(t), np.asarray(y).astype(t))
+
+
+# ---- the coupling kernel's launch geometry, restated -------------------------------------------------------------------------------------------
+def coupling_list_lengths(L, ndown, hop):
+    """entries of every block's coupling list: hops of the block species (n_down particles) out of each configuration, ascending-word order"""
+    from itertools import combinations
+    nz = np.asarray(hop) != 0
+    np.fill_diagonal(nz, False)
+    words = sorted(sum(1 << s for s in occ) for occ in combinations(range(L), ndown))
+    out = []
+    for w in words:
+        occ = [s for s in range(L) if (w >> s) & 1]
+        emp = [s for s in range(L) if not (w >> s) & 1]
+        out.append(int(sum(nz[i, j] for i in occ for j in emp)))
+    return np.array(out)
+
+
+def _down_lds_bytes(ids, rowcap):
+    stride = rowcap if (rowcap >> 2) & 1 else rowcap + 4
+    return ((ids * 8 + 15) & ~15) + ids * stride * 4 + 16
+
+
+def down_geometry(n_blk, longest, num_cus, grid=None, rounds=None):
+    """plan_down_geometry / plan_rounds of lpp_pb_plan.cpp for the whole-panel form and vectors below 16 GB: dict(grid, slots, ids_per_wg, rowcap, rounds,
+    ids_per_round, lds, lds_pf); 8 CUs at least.  grid: LPP_PB_DOWN_GRID; rounds: LPP_PB_DOWN_ROUNDS"""
+    assert num_cus >= 8
+    g = num_cus & ~7
+    if grid is not None:
+        g = max(8, min(grid, g)) & ~7
+    slots = g // 8
+    rowcap = max(4, (longest + 3) & ~3)
+    ids = -(-n_blk // slots)
+    unit = 64 if ids >= 512 else 8
+
+    def per_round(r):
+        return ids if r == 1 else -(-(-(-ids // r)) // unit) * unit
+
+    r = 1 if rounds is None else max(1, min(rounds, 64))
+    while r < 64 and _down_lds_bytes(per_round(r), rowcap) > 150 * 1024:
+        r += 1
+    while r > 1 and per_round(r) * (r - 1) >= ids:
+        r -= 1
+    lds = _down_lds_bytes(per_round(r), rowcap)
+    return dict(grid=g, slots=slots, ids_per_wg=ids, rowcap=rowcap, rounds=r, ids_per_round=per_round(r), lds=lds, lds_pf=lds + (per_round(r) + 7) // 8 * 32)
 
 
 _CACHE = {}

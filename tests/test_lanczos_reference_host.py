@@ -123,3 +123,96 @@ def test_input_conditions_product_basis(name):
     H = R.pb_matrix(name)
     init = R.start_vector(H.n, False, R.SEED_E)
     _conditions(H, init, R.K_E, R.APPLICABLE["derived_norm" if name == "open_chain_L12" else "scalefree"], vectors=name == "open_chain_L12")
+
+
+# ---- group F: the cases of tests/test_gpu_pb_down_edges.py ---------------------------------------------------------------------------------
+_F = {}
+
+
+def _f_matrix(name):
+    if name not in _F:
+        _F[name] = R.pb_matrix(name)
+    return _F[name]
+
+
+@pytest.mark.parametrize("name", list(R.PB_DOWN_CASES))
+def test_input_conditions_coupling_kernel_cases(name):
+    """every case at its own K, for all three twins (the chained step is held to the derived-norm set, the three-kernel step to a subset of it)"""
+    H = _f_matrix(name)
+    assert H.n == R.pb_rows(name) and np.iscomplexobj(H.values) == R.pb_is_complex(name)
+    K = R.pb_steps(name)
+    assert K == (8 if name == "ring_15_2_6" else 16)
+    worst = _conditions(H, R.pb_start(name), K, R.APPLICABLE["derived_norm"])
+    print("[lanczos-steps] group F %s: largest |twin - reference| / (eps |H|_inf) = %s" % (name, {f: round(v, 3) for f, v in worst.items()}))
+
+
+# (rows, blocks, blocks per workgroup, shortest and longest coupling list, rowcap) at 256 CUs: 32 coupling workgroups per group
+GEOMETRY_256 = {
+    "a2a_8_4_1": (560, 8, 1, 7, 7, 8),
+    "a2a_8_4_3": (3920, 56, 2, 15, 15, 16),
+    "a2a_10_3_5": (30240, 252, 8, 25, 25, 28),
+    "a2a_12_2_6": (60984, 924, 29, 36, 36, 36),
+    "ttp_ring_11_5_4": (152460, 330, 11, 4, 14, 16),
+    "ring_14_2_4": (91091, 1001, 32, 2, 8, 8),
+    "ring_15_2_6": (525525, 5005, 157, 2, 12, 12),
+    "peierls_11_5_4": (152460, 330, 11, 2, 8, 8),
+}
+
+
+@pytest.mark.parametrize("name", list(R.PB_DOWN_CASES))
+def test_geometry_of_the_coupling_kernel_cases(name):
+    """what each case is there for, at the 256 CUs of the GPU the suite runs on (tests/test_gpu_pb_down_edges.py asserts the same from the device's count)"""
+    from math import comb
+    L, nup, ndown, hop = R.pb_case(name)[:4]
+    rows, n_blk, ids, lo, hi, rowcap = GEOMETRY_256[name]
+    lens = R.coupling_list_lengths(L, ndown, hop)
+    assert (R.pb_rows(name), comb(L, ndown), int(lens.min()), int(lens.max())) == (rows, n_blk, lo, hi)
+    H = _f_matrix(name)
+    assert H.rowptr[-1] == comb(L, nup) * int(lens.sum()) + comb(L, ndown) * int(R.coupling_list_lengths(L, nup, hop).sum()) + rows  # both species' hops and the diagonal
+    g = R.down_geometry(n_blk, hi, 256)
+    assert (g["grid"], g["slots"], g["ids_per_wg"], g["rowcap"], g["rounds"], g["ids_per_round"]) == (256, 32, ids, rowcap, 1, ids)
+    n4 = (hi + 3) // 4  # trip count of the longest list's task: prologue of two chunks, loop unrolled by three
+    assert n4 == {"a2a_8_4_1": 2, "a2a_8_4_3": 4, "a2a_10_3_5": 7, "a2a_12_2_6": 9, "ttp_ring_11_5_4": 4, "ring_14_2_4": 2, "ring_15_2_6": 3, "peierls_11_5_4": 2}[name]
+    if name == "a2a_8_4_1":
+        assert 32 - n_blk == 24 and comb(L, nup) == 70 and (70 + 15) // 16 == 5  # 24 workgroups own nothing; 5 panels for 8 groups
+    if name == "a2a_10_3_5":
+        assert n_blk == 31 * 8 + 4 and g["rowcap"] == 28 and (28 >> 2) & 1  # full tasks and half a task; the stride is the row capacity itself
+    if name == "a2a_12_2_6":
+        assert ids == 3 * 8 + 5
+        f = R.down_geometry(n_blk, hi, 256, grid=8)  # one workgroup per group owns every block
+        assert (f["grid"], f["slots"], f["ids_per_wg"], f["rounds"]) == (8, 1, 924, 1) and (924 + 7) // 8 == 116 and f["lds"] == 140464 and f["lds_pf"] <= 150 * 1024
+        f = R.down_geometry(n_blk, hi, 256, grid=8, rounds=2)  # rounds in units of 64
+        assert (f["rounds"], f["ids_per_round"]) == (2, 512) and 924 - 512 == 412
+        f = R.down_geometry(n_blk, hi, 256, rounds=2)
+        assert (f["rounds"], f["ids_per_round"]) == (2, 16)
+    if name == "ttp_ring_11_5_4":
+        assert (comb(L, nup) + 15) // 16 == 29 and len(np.unique(hop[hop != 0])) == 2  # 29 panels: groups of 4 and of 3; (+-1, +-0.5 with the fermion sign: four values)
+    if name == "ring_14_2_4":
+        f = R.down_geometry(n_blk, hi, 256, rounds=2)
+        assert (f["rounds"], f["ids_per_round"]) == (2, 16) and n_blk - 31 * 32 == 9  # the last workgroup's second round is empty
+    if name == "ring_15_2_6":
+        assert (ids + 7) // 8 == 20  # tasks against 16 waves
+    if name == "peierls_11_5_4":
+        assert 2 * comb(L, nup) // 16 >= 8 * 2 + 8  # panels of doubles: enough to wait on
+
+
+@pytest.mark.parametrize("name", list(R.PB_DOWN_CASES))
+def test_elementwise_product_bound_holds_for_the_oracle_and_sees_a_dropped_term(name):
+    """the reference alone meets the bound: the C oracle's float64 x0 + H y stays inside product_bound of the long-double product; one term of one
+    row left out does not"""
+    H = _f_matrix(name)
+    cplx = R.pb_is_complex(name)
+    x0, y = oracle.fill_random(H.n, 5, cplx), oracle.fill_random(H.n, 6, cplx)
+    xr, bound = R.product_reference(H, x0, y), R.product_bound(H, x0, y)
+    assert xr.dtype == (np.clongdouble if cplx else np.longdouble) and bound.dtype == np.longdouble and float(bound.min()) > 0.0
+    xo = oracle.spmv_acc(oracle.Csr(H.rowptr, H.colind, H.values), x0.copy(), y)
+    dev = np.abs(xo.astype(xr.dtype) - xr)
+    print("[lanczos-steps] group F %s: oracle product, largest deviation / bound = %.3f" % (name, float((dev / bound).max())))
+    assert np.all(dev <= bound)
+    i = H.n // 2 + 3
+    k = int(H.rowptr[i + 1]) - 1  # the last term of row i
+    assert H.values[k] != 0 and y[H.colind[k]] != 0
+    xd = xo.copy()
+    xd[i] -= H.values[k] * y[H.colind[k]]
+    devd = np.abs(xd.astype(xr.dtype) - xr)
+    assert devd[i] > bound[i] and np.all(np.delete(devd, i) <= np.delete(bound, i))
