@@ -14,6 +14,7 @@
 #include "lpp_assemble_kernels.h"
 #include "lpp_engine_impl.h"
 #include "lpp_kron_kernels.h"
+#include "lpp_launch.h"
 
 using namespace lpp;
 
@@ -1278,6 +1279,57 @@ void free_kron(lpp_engine* e)
 	K = KronState();
 }
 
+// ---- kernel arguments: everything that comes from the state; whatever is not named here is zero (as in lpp_pb.hip) ------------------------
+// k_spmv_kron_packed / _chunked; the caller sets id0, nid, ywin, ydown, x, partial, xcd_map, sc, part
+template <typename T> static KronPackedArgs<T> kron_packed_args(const KronState& K)
+{
+	KronPackedArgs<T> pa = {};
+	pa.words = K.pk_words;
+	pa.slice_off = K.pk_off;
+	pa.slice_len = K.pk_len;
+	pa.dict = K.pk_dict;
+	pa.spb = K.pk_spb;
+	pa.n_up = K.n_up;
+	pa.dn_rowptr = K.dn.rowptr;
+	pa.dn_col = K.dn.col;
+	pa.dn_val = (const T*)K.dn.val;
+	pa.up_words = K.up_words;
+	pa.dn_words = K.dn_words;
+	pa.U = K.U;
+	pa.cdiag_up = K.cdiag_up;
+	pa.cdiag_dn = K.cdiag_dn;
+	pa.cross = K.cross;
+	pa.L = K.L;
+	pa.n_dn = K.n_dn;
+	return pa;
+}
+
+// k_spmv_kron: of H_up's sliced form only what describes the matrix; the caller sets id0, nid, ywin, ydown, x, partial, xcd_map, sc
+template <typename T> static KronArgs<T> kron_args(const KronState& K)
+{
+	KronArgs<T> a = {};
+	a.up.g = K.up.geom;
+	a.up.slice_ptr = K.up.slice_ptr;
+	a.up.row_len = K.up.row_len;
+	a.up.col = K.up.scol;
+	a.up.val = (const T*)K.up.sval;
+	a.up.codes = K.up.codes;
+	a.up.code_ptr = K.up.code_ptr;
+	a.up.dict = K.up.dict;
+	a.n_up = K.n_up;
+	a.dn_rowptr = K.dn.rowptr;
+	a.dn_col = K.dn.col;
+	a.dn_val = (const T*)K.dn.val;
+	a.up_words = K.up_words;
+	a.dn_words = K.dn_words;
+	a.U = K.U;
+	a.cdiag_up = K.cdiag_up;
+	a.cdiag_dn = K.cdiag_dn;
+	a.cross = K.cross;
+	a.L = K.L;
+	return a;
+}
+
 template <typename T> static int kron_launch_t(lpp_engine* e, const void* ywin, const void* ydown, void* x, double* partial, const EpiScale& sc, int part, int64_t b0, int64_t cnt)
 {
 	KronState& K = e->kron;
@@ -1297,25 +1349,9 @@ template <typename T> static int kron_launch_t(lpp_engine* e, const void* ywin, 
 	if (cnt == 0 && part != 2) return 0;
 	if (part != 0 && !K.packed) return -1;
 	if (K.packed) {
-		KronPackedArgs<T> pa;
-		pa.words = K.pk_words;
-		pa.slice_off = K.pk_off;
-		pa.slice_len = K.pk_len;
-		pa.dict = K.pk_dict;
-		pa.spb = K.pk_spb;
-		pa.n_up = K.n_up;
+		KronPackedArgs<T> pa = kron_packed_args<T>(K);
 		pa.id0 = K.id0 + b0; // a sub-range of blocks: the slice pointers move with it
 		pa.nid = cnt;
-		pa.dn_rowptr = K.dn.rowptr;
-		pa.dn_col = K.dn.col;
-		pa.dn_val = (const T*)K.dn.val;
-		pa.up_words = K.up_words;
-		pa.dn_words = K.dn_words;
-		pa.U = K.U;
-		pa.cdiag_up = K.cdiag_up;
-		pa.cdiag_dn = K.cdiag_dn;
-		pa.cross = K.cross;
-		pa.L = K.L;
 		pa.ywin = ywin ? (const T*)ywin + b0 * K.n_up : nullptr;
 		pa.ydown = (const T*)ydown;
 		pa.x = (T*)x + (part == 2 ? 0 : b0 * K.n_up);
@@ -1323,7 +1359,6 @@ template <typename T> static int kron_launch_t(lpp_engine* e, const void* ywin, 
 		pa.xcd_map = (e->k2_variant >> 1) & 1;
 		pa.sc = sc;
 		pa.part = part;
-		pa.n_dn = K.n_dn;
 		bool use_window = K.window;
 		if (part == 2) { // down-hops on the transposed slice: rows per down index = peru, all (padded) down indices
 			pa.n_up = e->tx_peru;
@@ -1334,74 +1369,24 @@ template <typename T> static int kron_launch_t(lpp_engine* e, const void* ywin, 
 		}
 		const size_t ldsb = use_window ? sizeof(T) * (size_t)std::max<int64_t>(K.n_up, 64) : 64;
 		const int pcu = std::max(1, std::min(2, (int)((160 * 1024 - 8192) / (ldsb + 1))));
-		int nbp = (int)std::max<int64_t>(1, std::min<int64_t>(pa.nid, (int64_t)e->num_cus * pcu));
-		if (nbp >= 8) nbp &= ~7;
+		const int nbp = launch_grid(pa.nid, e->num_cus, pcu);
 		const bool dotp = partial != nullptr;
 		if (K.pk_nchunk > 1 && part != 2) { // N_up exceeds LDS: the source row is staged in pieces (part 2 has no up-hops)
-			KronChunkArgs<T> ca;
+			KronChunkArgs<T> ca = {};
 			ca.k = pa;
 			ca.nchunk = K.pk_nchunk;
 			ca.cw = K.pk_cw;
 			const size_t ldsc = sizeof(T) * (size_t)K.pk_cw;
 			const int nbc = (int)std::max<int64_t>(1, std::min<int64_t>(pa.nid, (int64_t)e->num_cus));
-			if (dotp) {
-				(void)hipFuncSetAttribute((const void*)k_spmv_kron_chunked<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsc);
-				k_spmv_kron_chunked<T, true><<<nbc, kWinThreads, ldsc, e->stream>>>(ca);
-			} else {
-				(void)hipFuncSetAttribute((const void*)k_spmv_kron_chunked<T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsc);
-				k_spmv_kron_chunked<T, false><<<nbc, kWinThreads, ldsc, e->stream>>>(ca);
-			}
+			with_flags([&](auto dot) { launch_lds(k_spmv_kron_chunked<T, decltype(dot)::value>, nbc, kWinThreads, ldsc, e->stream, ca); }, dotp);
 			return dotp ? nbc : 0;
 		}
-#define LPP_KP(DOT_, WIN_)                                                                                            \
-	do {                                                                                                              \
-		(void)hipFuncSetAttribute((const void*)k_spmv_kron_packed<T, DOT_, WIN_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb); \
-		k_spmv_kron_packed<T, DOT_, WIN_><<<nbp, kWinThreads, ldsb, e->stream>>>(pa);                                   \
-	} while (0)
-		if (dotp && use_window) LPP_KP(true, true);
-		else if (dotp) LPP_KP(true, false);
-		else if (use_window) LPP_KP(false, true);
-		else LPP_KP(false, false);
-#undef LPP_KP
+		with_flags([&](auto dot, auto win) { launch_lds(k_spmv_kron_packed<T, decltype(dot)::value, decltype(win)::value>, nbp, kWinThreads, ldsb, e->stream, pa); }, dotp, use_window);
 		return dotp ? nbp : 0;
 	}
-	KronArgs<T> a;
-	a.up.g = K.up.geom;
-	a.up.slice_ptr = K.up.slice_ptr;
-	a.up.row_len = K.up.row_len;
-	a.up.col = K.up.scol;
-	a.up.val = (const T*)K.up.sval;
-	a.up.codes = K.up.codes;
-	a.up.code_ptr = K.up.code_ptr;
-	a.up.dict = K.up.dict;
-	a.up.src = nullptr;
-	a.up.x = nullptr;
-	a.up.ydot = nullptr;
-	a.up.partial = nullptr;
-	a.up.xcd_map = 0;
-	a.up.sc = EpiScale { nullptr, nullptr, 0 };
-	a.up.dia_stride = 0;
-	a.up.dia_off = nullptr;
-	a.up.dia_val = nullptr;
-	a.up.tmpl = 0;
-	a.up.dcode = nullptr;
-	a.up.tw = nullptr;
-	a.up.tw_off = nullptr;
-	a.up.tw_len = nullptr;
-	a.up.rowmap = nullptr;
-	a.n_up = K.n_up;
+	KronArgs<T> a = kron_args<T>(K);
 	a.id0 = K.id0 + b0;
 	a.nid = cnt;
-	a.dn_rowptr = K.dn.rowptr;
-	a.dn_col = K.dn.col;
-	a.dn_val = (const T*)K.dn.val;
-	a.up_words = K.up_words;
-	a.dn_words = K.dn_words;
-	a.U = K.U;
-	a.cdiag_up = K.cdiag_up;
-	a.cdiag_dn = K.cdiag_dn;
-	a.cross = K.cross;
-	a.L = K.L;
 	a.ywin = (const T*)ywin + b0 * K.n_up;
 	a.ydown = (const T*)ydown;
 	a.x = (T*)x + b0 * K.n_up;
@@ -1410,27 +1395,13 @@ template <typename T> static int kron_launch_t(lpp_engine* e, const void* ywin, 
 	a.sc = sc;
 	const size_t lds_bytes = K.window ? sizeof(T) * (size_t)std::max<int64_t>(K.n_up, 64) : 64;
 	const int per_cu = std::max(1, std::min(2, (int)((160 * 1024 - 8192) / (lds_bytes + 1))));
-	int nb = (int)std::max<int64_t>(1, std::min<int64_t>(cnt, (int64_t)e->num_cus * per_cu));
-	if (nb >= 8) nb &= ~7;
+	const int nb = launch_grid(cnt, e->num_cus, per_cu);
 	const bool dot = partial != nullptr;
-	const int sel = (dot ? 4 : 0) | (K.window ? 2 : 0) | (K.up.coded ? 1 : 0);
-	hipStream_t st = e->stream;
-#define LPP_KRON(DOT_, WIN_, CODED_)                                                                                   \
-	do {                                                                                                              \
-		(void)hipFuncSetAttribute((const void*)k_spmv_kron<T, DOT_, WIN_, CODED_, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); \
-		k_spmv_kron<T, DOT_, WIN_, CODED_, 8><<<nb, kWinThreads, lds_bytes, st>>>(a);                                   \
-	} while (0)
-	switch (sel) {
-	case 0: LPP_KRON(false, false, false); break;
-	case 1: LPP_KRON(false, false, true); break;
-	case 2: LPP_KRON(false, true, false); break;
-	case 3: LPP_KRON(false, true, true); break;
-	case 4: LPP_KRON(true, false, false); break;
-	case 5: LPP_KRON(true, false, true); break;
-	case 6: LPP_KRON(true, true, false); break;
-	default: LPP_KRON(true, true, true); break;
-	}
-#undef LPP_KRON
+	with_flags(
+	    [&](auto with_dot, auto win, auto coded) {
+		    launch_lds(k_spmv_kron<T, decltype(with_dot)::value, decltype(win)::value, decltype(coded)::value, 8>, nb, kWinThreads, lds_bytes, e->stream, a);
+	    },
+	    dot, K.window, K.up.coded);
 	return dot ? nb : 0;
 }
 

@@ -18,6 +18,7 @@
 
 #include "lpp_assemble_kernels.h"
 #include "lpp_engine_impl.h"
+#include "lpp_launch.h"
 
 using namespace lpp;
 
@@ -71,31 +72,6 @@ static SlicedArgs<T> sliced_args(const DevCsr& A, const void* src, void* x, cons
 	return a;
 }
 
-// the (DOT, CODED, U) instantiation of a sliced kernel: launch(dot, coded, u) gets them as integral constants
-template <typename F> static void with_sliced_variant(bool dot, bool coded, bool u8, F&& launch)
-{
-	using No = std::false_type;
-	using Yes = std::true_type;
-	using U4 = std::integral_constant<int, 4>;
-	using U8 = std::integral_constant<int, 8>;
-	switch ((dot ? 4 : 0) | (coded ? 2 : 0) | (u8 ? 1 : 0)) {
-	case 0: launch(No {}, No {}, U4 {}); break;
-	case 1: launch(No {}, No {}, U8 {}); break;
-	case 2: launch(No {}, Yes {}, U4 {}); break;
-	case 3: launch(No {}, Yes {}, U8 {}); break;
-	case 4: launch(Yes {}, No {}, U4 {}); break;
-	case 5: launch(Yes {}, No {}, U8 {}); break;
-	case 6: launch(Yes {}, Yes {}, U4 {}); break;
-	default: launch(Yes {}, Yes {}, U8 {}); break;
-	}
-}
-
-template <typename T, bool DOT, bool CODED, int U, bool L16> static void launch_window(const SlicedArgs<T>& a, int nb, size_t lds_bytes, hipStream_t st)
-{
-	(void)hipFuncSetAttribute((const void*)k_spmv_window<T, DOT, CODED, U, L16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-	k_spmv_window<T, DOT, CODED, U, L16><<<nb, kWinThreads, lds_bytes, st>>>(a);
-}
-
 // x += A * src ; if partial != nullptr also partial[b] = block sums of Re<ydot|x>.
 // Returns the number of partials written (0 when partial == nullptr).
 template <typename T> static int spmv_launch_t(lpp_engine* e, const DevCsr& A, const void* src, void* x, const void* ydot, double* partial, const EpiScale& sc)
@@ -109,21 +85,18 @@ template <typename T> static int spmv_launch_t(lpp_engine* e, const DevCsr& A, c
 		if (A.window) {
 			const size_t lds_bytes = sizeof(T) * (size_t)std::max<int64_t>(A.geom.B, 64);
 			const int per_cu = std::max(1, std::min(2, (int)((160 * 1024 - 4096) / (lds_bytes + 1))));
-			nb = (int)std::max<int64_t>(1, std::min<int64_t>(A.geom.nblocks, (int64_t)e->num_cus * per_cu));
-			if (nb >= 8) nb &= ~7;
-			with_sliced_variant(partial != nullptr, A.coded, u8, [&](auto dot, auto coded, auto u) {
-				if (A.local16)
-					launch_window<T, decltype(dot)::value, decltype(coded)::value, decltype(u)::value, true>(a, nb, lds_bytes, st);
-				else
-					launch_window<T, decltype(dot)::value, decltype(coded)::value, decltype(u)::value, false>(a, nb, lds_bytes, st);
-			});
+			nb = launch_grid(A.geom.nblocks, e->num_cus, per_cu);
+			with_flags(
+			    [&](auto dot, auto coded, auto u8, auto l16) {
+				    launch_lds(k_spmv_window<T, decltype(dot)::value, decltype(coded)::value, decltype(u8)::value ? 8 : 4, decltype(l16)::value>, nb, kWinThreads, lds_bytes, st, a);
+			    },
+			    partial != nullptr, A.coded, u8, A.local16);
 		} else {
 			const int64_t need = (A.geom.nslices + (kBlock / 64) - 1) / (kBlock / 64);
 			nb = (int)std::max<int64_t>(1, std::min<int64_t>(need, e->spmv_max_blocks));
 			if (nb >= 8) nb &= ~7; // multiple of 8 so the XCD-contiguous mapping applies
-			with_sliced_variant(partial != nullptr, A.coded, u8, [&](auto dot, auto coded, auto u) {
-				k_spmv_sliced<T, decltype(dot)::value, decltype(coded)::value, decltype(u)::value><<<nb, kBlock, 0, st>>>(a);
-			});
+			with_flags([&](auto dot, auto coded, auto u8) { k_spmv_sliced<T, decltype(dot)::value, decltype(coded)::value, decltype(u8)::value ? 8 : 4><<<nb, kBlock, 0, st>>>(a); },
+			           partial != nullptr, A.coded, u8);
 		}
 		return partial ? nb : 0;
 	}
@@ -149,9 +122,7 @@ template <typename T> static int spmv_launch_out_t(lpp_engine* e, const DevCsr& 
 	int nb = (int)std::max<int64_t>(1, std::min<int64_t>(need, std::min<int64_t>(e->spmv_max_blocks, 2 * (int64_t)e->num_cus)));
 	if (nb >= 8) nb &= ~7;
 	hipStream_t st = e->stream;
-	with_sliced_variant(partial != nullptr, A.coded, true, [&](auto dot, auto coded, auto u) {
-		k_spmv_sliced<T, decltype(dot)::value, decltype(coded)::value, decltype(u)::value><<<nb, kBlock, 0, st>>>(a);
-	});
+	with_flags([&](auto dot, auto coded) { k_spmv_sliced<T, decltype(dot)::value, decltype(coded)::value, 8><<<nb, kBlock, 0, st>>>(a); }, partial != nullptr, A.coded);
 	return partial ? nb : 0;
 }
 

@@ -135,6 +135,21 @@ struct KronState {
 	void* terms_bufs[8] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
 };
 
+// The template instances of the product-basis kernels that this layout's launches run (the lists: lpp_pb_instances.h), found once at the
+// end of pb_build from the planned form.  Only the form's own are set; the planner has checked that each exists.
+struct PbSegArgs;
+struct PbKernels {
+	// in-block part without / with the partial sums of Re<y|u>: the form has one of the three
+	void (*up[2])(PbUpArgs) = { nullptr, nullptr }; // one window (k_pb_up)
+	void (*up_big[2])(PbUpBigArgs) = { nullptr, nullptr }; // by pieces (k_pb_up_big / k_pb_up_big2)
+	void (*up_seg[2])(PbSegArgs) = { nullptr, nullptr }; // segmented (k_pb_up_seg)
+	void (*up_chain)(PbUpArgs) = nullptr; // chained step (chain_ok)
+	// block couplings: whole panels (k_pb_down) plain and chained, or over parts of the source range (k_pb_down_parts)
+	void (*down)(PbDownArgs) = nullptr;
+	void (*down_chain)(PbDownArgs) = nullptr;
+	void (*down_parts)(PbDownPartsArgs) = nullptr;
+};
+
 // product-basis stored matrix  H = 1 (x) T + C (x) 1 + D  (lpp_pb_kernels.h): everything the 5.8e9-entry CSR of BASELINE
 // config 2 needs is T, C, a 256-entry dictionary and one code per row
 struct PbState : PbForm { // (PbForm, lpp_pb_plan.h: the scalars the planner fills; here: what lives on the device or comes after the build)
@@ -190,6 +205,7 @@ struct PbState : PbForm { // (PbForm, lpp_pb_plan.h: the scalars the planner fil
 	uint8_t* dcode = nullptr; // n_blk * pitch codes
 	double* dval = nullptr; // the diagonal as a plain f64 stream (n_blk * pitch doubles) when it has more than 256 distinct values; the codes are then all 0
 	int64_t* blockbase = nullptr; // first CSR entry of every block (n_blk + 1), for get_csr
+	PbKernels k; // the template instances the launches run
 };
 
 // one-orbital t-J Hamiltonian without a stored matrix, hole-major order (lpp_tj_kernels.h)

@@ -8,10 +8,13 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <utility>
 #include <vector>
 
 #include "lpp_assemble_kernels.h"
 #include "lpp_engine_impl.h"
+#include "lpp_launch.h"
+#include "lpp_pb_instances.h"
 #include "lpp_pbig_kernels.h"
 #include "lpp_pbseg_kernels.h"
 
@@ -214,6 +217,145 @@ static PbCombineArgs combine_args(const PbState& B, void* x, const void* y, cons
 	return c;
 }
 
+// k_pb_up_big and k_pb_up_big2; the caller sets dcode, n_blk, y, u, partial, sc
+static PbUpBigArgs up_big_args(const PbState& B)
+{
+	PbUpBigArgs a = {};
+	a.tw = B.tw;
+	a.tw_off = B.tw_off;
+	a.tw_len = B.tw_len;
+	a.fw = B.fw;
+	a.f_off = B.f_off;
+	a.f_len = B.f_len;
+	a.G = B.G;
+	for (int g = 0; g < B.G; g++) a.gval[g] = B.gval[g];
+	a.dict = B.dict;
+	a.n_up = B.n_up;
+	a.pitch = B.pitch;
+	a.W = B.W;
+	a.npieces = B.npieces;
+	return a;
+}
+
+// k_pb_up_seg; the caller sets dcode, n_blk, y, u, partial, sc
+static PbSegArgs seg_args(const PbState& B)
+{
+	PbSegArgs g = {};
+	g.items = (const SegItem*)B.seg_items;
+	g.nitems = B.seg_nitems;
+	g.cross = (const SegCross*)B.seg_cross;
+	g.hh = (const SegHh*)B.seg_hh;
+	g.slices = (const SegSlice*)B.seg_slices;
+	g.tw = B.seg_tw;
+	g.xw = B.seg_xw;
+	g.G = B.G;
+	for (int v = 0; v < std::min(B.G, 2); v++) g.gval[v] = B.gval[v];
+	g.dict = B.dict;
+	g.n_up = B.n_up;
+	g.pitch = B.pitch;
+	g.ws = B.seg_ws;
+	g.wmax = B.seg_wmax;
+	g.flat = B.seg_one ? 1 : 0;
+	return g;
+}
+
+// k_pb_down_parts on rows of `pitch` positions; the caller sets y, z, partial, sc
+static PbDownPartsArgs down_parts_args(const PbState& B, int64_t pitch)
+{
+	PbDownPartsArgs d = {};
+	d.pitch = pitch;
+	d.n_blk = B.n_blk;
+	d.npanels = (int)(pitch / 16);
+	d.ids_per_wg = B.ids_per_wg;
+	d.nparts = B.nparts;
+	d.ent_cap = B.ent_cap;
+	d.c_ptr = B.c_ptr;
+	d.c_col = B.c_col;
+	d.c_code = B.c_code;
+	d.c_pstart = B.c_pstart;
+	d.order = B.order;
+	d.dict = B.dict;
+	d.pace = B.pace;
+	d.pace_stride = B.pace_stride;
+	return d;
+}
+
+// ---- kernel instances: a list of lpp_pb_instances.h is instantiated entry by entry, and nothing else is --------------------------------
+static_assert(kPbBigPre == kBigPre, "the lists name k_pb_up_big's default depth");
+template <typename Args> using Kernel = void (*)(Args);
+template <typename Args, typename At, size_t... I> static Kernel<Args> kernel_table_at(int i, At at, std::index_sequence<I...>)
+{
+	const Kernel<Args> t[] = { at(std::integral_constant<size_t, I> {})... };
+	return i < 0 ? nullptr : t[i];
+}
+// the kernel of `key`, null when the list does not hold it; at(i) names the template instance of the list's entry i
+template <typename Args, typename K, size_t N, typename At> static Kernel<Args> kernel_of(const std::array<K, N>& list, const K& key, At at)
+{
+	return kernel_table_at<Args>(inst_index(list, key), at, std::make_index_sequence<N> {});
+}
+static Kernel<PbUpArgs> up_kernel(const PbUpInst& key)
+{
+	return kernel_of<PbUpArgs>(kPbUpInsts, key, [](auto i) -> Kernel<PbUpArgs> {
+		constexpr PbUpInst k = kPbUpInsts[decltype(i)::value];
+		return k_pb_up<k.dot, k.gt, k.chain, k.pre0>;
+	});
+}
+static Kernel<PbUpBigArgs> big_kernel(const PbBigInst& key)
+{
+	return kernel_of<PbUpBigArgs>(kPbBigInsts, key, [](auto i) -> Kernel<PbUpBigArgs> {
+		constexpr PbBigInst k = kPbBigInsts[decltype(i)::value];
+		return k_pb_up_big<k.dot, k.gt, k.pre>;
+	});
+}
+static Kernel<PbUpBigArgs> big2_kernel(const PbBigInst& key)
+{
+	return kernel_of<PbUpBigArgs>(kPbBig2Insts, key, [](auto i) -> Kernel<PbUpBigArgs> {
+		constexpr PbBigInst k = kPbBig2Insts[decltype(i)::value];
+		return k_pb_up_big2<k.dot, k.gt, k.pre>;
+	});
+}
+static Kernel<PbSegArgs> seg_kernel(const PbSegInst& key)
+{
+	return kernel_of<PbSegArgs>(kPbSegInsts, key, [](auto i) -> Kernel<PbSegArgs> {
+		constexpr PbSegInst k = kPbSegInsts[decltype(i)::value];
+		return k_pb_up_seg<k.dot, k.gt, k.p0, 4, k.shape.nc, k.shape.nh, k.shape.rows>;
+	});
+}
+static Kernel<PbDownArgs> down_kernel(const PbDownInst& key)
+{
+	return kernel_of<PbDownArgs>(kPbDownInsts, key, [](auto i) -> Kernel<PbDownArgs> {
+		constexpr PbDownInst k = kPbDownInsts[decltype(i)::value];
+		return k_pb_down<1024, k.rmw, k.wide, k.cplx, k.pf>;
+	});
+}
+static Kernel<PbDownPartsArgs> parts_kernel(const PbPartsInst& key)
+{
+	return kernel_of<PbDownPartsArgs>(kPbPartsInsts, key, [](auto i) -> Kernel<PbDownPartsArgs> {
+		constexpr PbPartsInst k = kPbPartsInsts[decltype(i)::value];
+		return k_pb_down_parts<kPbPartsThreads, k.r>;
+	});
+}
+
+// the kernels of the planned form.  pb_plan has checked every key against the same lists: a miss here is an internal error
+static lpp_status resolve_kernels(PbState& B)
+{
+	PbKernels& k = B.k;
+	bool ok = true;
+	for (int dot = 0; dot < 2; dot++) {
+		if (B.seg) ok = (k.up_seg[dot] = seg_kernel(pb_seg_inst(B, dot != 0))) && ok;
+		else if (B.big2) ok = (k.up_big[dot] = big2_kernel(pb_big2_inst(B, dot != 0))) && ok;
+		else if (B.big) ok = (k.up_big[dot] = big_kernel(pb_big_inst(B, dot != 0))) && ok;
+		else ok = (k.up[dot] = up_kernel(pb_up_inst(B, dot != 0, false))) && ok;
+	}
+	if (B.parts) ok = (k.down_parts = parts_kernel(pb_parts_inst(B))) && ok;
+	else ok = (k.down = down_kernel(pb_down_inst(B, false))) && ok;
+	if (B.chain_ok) {
+		ok = (k.up_chain = up_kernel(pb_up_inst(B, false, true))) && ok;
+		ok = (k.down_chain = down_kernel(pb_down_inst(B, true))) && ok;
+	}
+	return ok ? LPP_OK : fail(LPP_ERR_STATE, "pb_build: the planned form names a kernel instance that does not exist");
+}
+
 // Straight-line: the switches, the plan (lpp_pb_plan.cpp: every decision, refusal and host vector), then uploads and allocations in a fixed
 // order.  Nothing here decides anything beyond "was this vector planned".
 lpp_status pb_build(lpp_engine* e, const PbBuildInput& in)
@@ -287,6 +429,7 @@ lpp_status pb_build(lpp_engine* e, const PbBuildInput& in)
 	e->pitch = B.cplx ? B.pitch / 2 : B.pitch; // in vector elements
 	e->pitch_rows = B.cplx ? B.n_c : B.n_up;
 	e->pitch_blocks = B.nblk_loc;
+	if ((rc = resolve_kernels(B)) != LPP_OK) return rc;
 	B.active = true;
 	return LPP_OK;
 }
@@ -295,7 +438,8 @@ lpp_status pb_build(lpp_engine* e, const PbBuildInput& in)
 // Nothing from here to the handed-over-CSR section reads the environment.  Which form of a kernel a launch takes was decided at the
 // end of pb_build and is kept in PbState (chain_ok, down_tasks, down_pf, chain_drop_pace, lazy_tx): LPP_PB_CHAIN, LPP_PB_DOWN_TASKS,
 // LPP_PB_DOWN_PF, LPP_PB_CHAIN_PACE and LPP_PB_LAZY_TX take effect when the layout is BUILT, not at the first or at every launch.
-// Kernel arguments come from down_args / up_args / combine_args (above pb_build); a launch site sets only what is its own.
+// Kernel arguments come from the builders above pb_build (down_args, up_args, ...), the template instance from PbState::k (resolve_kernels,
+// at the end of pb_build); a launch site sets only what is its own.
 //
 // x = beta x + alpha H y (EpiScale semantics of the other product kernels) as two independent kernels that only read y,
 //   k_pb_down  z = alpha C y            (+ partials of Re<y|z>)
@@ -303,174 +447,42 @@ lpp_status pb_build(lpp_engine* e, const PbBuildInput& in)
 // and a streaming pass x = beta x + u + z (k_pb_combine).  defer_combine: the caller runs that pass itself, folded into its own
 // pass over x (pb_combine_axpy of the scale-free recurrence).  Returns the number of partials written; their sum is
 // Re<y | u + z>, to which the caller adds beta Re<y | x_old> (pb.xy, left by the previous combine pass).
-constexpr int kPreLo = kPbPairs ? 2 : 3, kPreHi = kPbPairs ? 6 : 5; // the unequal look-ahead splits k_pb_up is instantiated for
-template <bool DOT> static void launch_up(const PbState& B, const PbUpArgs& u, int nb, size_t lds, hipStream_t st)
-{
-	const int gt = B.G <= 2 ? B.G : 0;
-#define LPP_PB_UP(GT_)                                                                                                \
-	do {                                                                                                              \
-		(void)hipFuncSetAttribute((const void*)k_pb_up<DOT, GT_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-		k_pb_up<DOT, GT_><<<nb, kPbUpThreads, lds, st>>>(u);                                                            \
-	} while (0)
-#define LPP_PB_UP2(PRE_)                                                                                              \
-	do {                                                                                                              \
-		(void)hipFuncSetAttribute((const void*)k_pb_up<DOT, 2, false, PRE_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-		k_pb_up<DOT, 2, false, PRE_><<<nb, kPbUpThreads, lds, st>>>(u);                                                 \
-	} while (0)
-	if (gt == 1) LPP_PB_UP(1);
-	else if (gt == 2 && B.pre0 == kPreLo) LPP_PB_UP2(kPreLo); // look-ahead split of the two value groups (pb_build)
-	else if (gt == 2 && B.pre0 == kPreHi) LPP_PB_UP2(kPreHi);
-	else if (gt == 2) LPP_PB_UP(2);
-	else LPP_PB_UP(0);
-#undef LPP_PB_UP2
-#undef LPP_PB_UP
-}
-
-
 // ---- rows beyond one LDS window / vectors beyond 4 GiB (lpp_pbig_kernels.h) -------------------------------------------
 static int big_grid(const lpp_engine* e, int64_t cnt)
 {
 	const PbState& B = e->pb;
-	if (B.big2 || B.seg) { // one workgroup per CU, items = (pair of blocks of one XCD, piece)
-		int nb = (int)std::max<int64_t>(1, std::min<int64_t>((B.seg_one ? cnt : (cnt + 1) / 2) * B.npieces, (int64_t)e->num_cus));
-		if (nb >= 8) nb &= ~7;
-		return nb;
-	}
+	// one workgroup per CU, items = (pair of blocks of one XCD, piece)
+	if (B.big2 || B.seg) return launch_grid((B.seg_one ? cnt : (cnt + 1) / 2) * B.npieces, e->num_cus);
 	const size_t lds = pb_big_lds_bytes(B.W);
-	const int per_cu = std::max(1, std::min(2, (int)(((size_t)160 * 1024) / (lds + 512))));
-	int nb = (int)std::max<int64_t>(1, std::min<int64_t>(cnt * B.npieces, (int64_t)e->num_cus * per_cu));
-	if (nb >= 8) nb &= ~7;
-	return nb;
+	return launch_grid(cnt * B.npieces, e->num_cus, std::max(1, std::min(2, (int)(((size_t)160 * 1024) / (lds + 512)))));
 }
 
 // in-block part by pieces: `cnt` blocks from `y` (pitched), result to `u`; returns the number of partials written
 static int launch_up_big(lpp_engine* e, const double* y, double* u, const uint8_t* dcode, int64_t cnt, double* partial, const EpiScale& sc, hipStream_t st)
 {
 	const PbState& B = e->pb;
-	PbUpBigArgs a;
-	a.tw = B.tw;
-	a.tw_off = B.tw_off;
-	a.tw_len = B.tw_len;
-	a.fw = B.fw;
-	a.f_off = B.f_off;
-	a.f_len = B.f_len;
-	a.G = B.G;
-	for (int g = 0; g <= kPbMaxGroups; g++) a.gval[g] = g < B.G ? B.gval[g] : 0.0;
-	a.dict = B.dict;
-	a.dcode = dcode;
-	a.n_up = B.n_up;
-	a.pitch = B.pitch;
-	a.n_blk = cnt;
-	a.W = B.W;
-	a.npieces = B.npieces;
-	a.y = y;
-	a.u = u;
-	a.partial = partial;
-	a.sc = sc;
-	const int nb = big_grid(e, cnt);
-	if (B.seg) {
-		PbSegArgs g;
-		g.items = (const SegItem*)B.seg_items;
-		g.nitems = B.seg_nitems;
-		g.cross = (const SegCross*)B.seg_cross;
-		g.hh = (const SegHh*)B.seg_hh;
-		g.slices = (const SegSlice*)B.seg_slices;
-		g.tw = B.seg_tw;
-		g.xw = B.seg_xw;
-		g.G = B.G;
-		g.gval[0] = B.gval[0];
-		g.gval[1] = B.G > 1 ? B.gval[1] : 0.0;
-		g.dict = B.dict;
+	const int nb = big_grid(e, cnt), dot = partial ? 1 : 0;
+	if (B.seg) { // cross / high-high hops per segment: the instance the plan padded its lists for; chunks of value group 0 requested ahead: its choice
+		PbSegArgs g = seg_args(B);
 		g.dcode = dcode;
-		g.n_up = B.n_up;
-		g.pitch = B.pitch;
 		g.n_blk = cnt;
-		g.ws = B.seg_ws;
-		g.wmax = B.seg_wmax;
 		g.y = y;
 		g.u = u;
 		g.partial = partial;
 		g.sc = sc;
-		g.flat = B.seg_one ? 1 : 0;
-		const size_t lds = pb_seg_lds_bytes(B.seg_ws, B.seg_wmax, B.seg_one ? 1 : 2);
-#define LPP_PB_SEG(DOT_, GT_, P0_, NC_, NH_)                                                                            \
-	do {                                                                                                              \
-		(void)hipFuncSetAttribute((const void*)k_pb_up_seg<DOT_, GT_, P0_, 4, NC_, NH_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-		k_pb_up_seg<DOT_, GT_, P0_, 4, NC_, NH_><<<nb, kSegThreads, lds, st>>>(g);                                      \
-	} while (0)
-#define LPP_PB_SEG1(DOT_, GT_, P0_, NC_, NH_)                                                                           \
-	do {                                                                                                              \
-		(void)hipFuncSetAttribute((const void*)k_pb_up_seg<DOT_, GT_, P0_, 4, NC_, NH_, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-		k_pb_up_seg<DOT_, GT_, P0_, 4, NC_, NH_, 1><<<nb, kSegThreads, lds, st>>>(g);                                   \
-	} while (0)
-#define LPP_PB_SEG_N(DOT_, GT_, P0_)                                                                                   \
-	do {                                                                                                              \
-		if (B.seg_one && B.seg_nh == 12 && B.seg_nc == 1) LPP_PB_SEG1(DOT_, GT_, P0_, 1, 12);                           \
-		else if (B.seg_one && B.seg_nh == 12) LPP_PB_SEG1(DOT_, GT_, P0_, 2, 12);                                       \
-		else if (B.seg_one && B.seg_nh == 16 && B.seg_nc == 1) LPP_PB_SEG1(DOT_, GT_, P0_, 1, 16);                      \
-		else if (B.seg_one && B.seg_nh == 16) LPP_PB_SEG1(DOT_, GT_, P0_, 2, 16);                                       \
-		else if (B.seg_one) LPP_PB_SEG1(DOT_, GT_, P0_, 2, 2);                                                          \
-		else if (B.seg_nc == 2) LPP_PB_SEG(DOT_, GT_, P0_, 2, 2);                                                            \
-		else if (B.seg_nc == 5) LPP_PB_SEG(DOT_, GT_, P0_, 5, 4);                                                       \
-		else LPP_PB_SEG(DOT_, GT_, P0_, 6, 8);                                                                          \
-	} while (0)
-		// cross / high-high hops per segment: the instance the plan padded its lists for; chunks of value group 0 requested ahead: its choice
-		if (partial) {
-			if (B.G == 1) LPP_PB_SEG_N(true, 1, 4);
-			else if (B.seg_pre0 == 2) LPP_PB_SEG_N(true, 2, 2);
-			else LPP_PB_SEG_N(true, 2, 4);
-		} else {
-			if (B.G == 1) LPP_PB_SEG_N(false, 1, 4);
-			else if (B.seg_pre0 == 2) LPP_PB_SEG_N(false, 2, 2);
-			else LPP_PB_SEG_N(false, 2, 4);
-		}
-#undef LPP_PB_SEG_N
-#undef LPP_PB_SEG1
-#undef LPP_PB_SEG
+		launch_lds(B.k.up_seg[dot], nb, kSegThreads, pb_seg_lds_bytes(B.seg_ws, B.seg_wmax, B.seg_one ? 1 : 2), st, g);
 		return partial ? nb : 0;
 	}
-	if (B.big2) {
-		const size_t lds2 = pb_big2_lds_bytes(B.W);
-#define LPP_PB_BIG2(DOT_, GT_, PRE_)                                                                                   \
-	do {                                                                                                              \
-		(void)hipFuncSetAttribute((const void*)k_pb_up_big2<DOT_, GT_, PRE_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2); \
-		k_pb_up_big2<DOT_, GT_, PRE_><<<nb, kPbBig2Threads, lds2, st>>>(a);                                             \
-	} while (0)
-		if (partial) {
-			if (B.G == 1) LPP_PB_BIG2(true, 1, 4);
-			else if (B.G == 4) LPP_PB_BIG2(true, 4, 2); // two chunks of each of the four groups ahead (three spill: 5.00 against 4.74 ms at 1.47e8 complex states)
-			else if (B.pre0 == 3) LPP_PB_BIG2(true, 2, 3);
-			else if (B.pre0 == 5) LPP_PB_BIG2(true, 2, 5);
-			else LPP_PB_BIG2(true, 2, 4);
-		} else {
-			if (B.G == 1) LPP_PB_BIG2(false, 1, 4);
-			else if (B.G == 4) LPP_PB_BIG2(false, 4, 2);
-			else if (B.pre0 == 3) LPP_PB_BIG2(false, 2, 3);
-			else if (B.pre0 == 5) LPP_PB_BIG2(false, 2, 5);
-			else LPP_PB_BIG2(false, 2, 4);
-		}
-#undef LPP_PB_BIG2
-		return partial ? nb : 0;
-	}
-	const size_t lds = pb_big_lds_bytes(B.W);
-	const int gt = B.G <= 2 || B.G == 4 ? B.G : 0;
-#define LPP_PB_BIG(DOT_, GT_, PRE_)                                                                                    \
-	do {                                                                                                              \
-		(void)hipFuncSetAttribute((const void*)k_pb_up_big<DOT_, GT_, PRE_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-		k_pb_up_big<DOT_, GT_, PRE_><<<nb, kPbBigThreads, lds, st>>>(a);                                                \
-	} while (0)
-	if (partial) {
-		if (gt == 1) LPP_PB_BIG(true, 1, kBigPre);
-		else if (gt == 2) LPP_PB_BIG(true, 2, kBigPre);
-		else if (gt == 4) LPP_PB_BIG(true, 4, 3);
-		else LPP_PB_BIG(true, 0, kBigPre);
-	} else {
-		if (gt == 1) LPP_PB_BIG(false, 1, kBigPre);
-		else if (gt == 2) LPP_PB_BIG(false, 2, kBigPre);
-		else if (gt == 4) LPP_PB_BIG(false, 4, 3);
-		else LPP_PB_BIG(false, 0, kBigPre);
-	}
-#undef LPP_PB_BIG
+	PbUpBigArgs a = up_big_args(B);
+	a.dcode = dcode;
+	a.n_blk = cnt;
+	a.y = y;
+	a.u = u;
+	a.partial = partial;
+	a.sc = sc;
+	// (two blocks per workgroup, four value groups: two chunks of each ahead -- three spill: 5.00 against 4.74 ms at 1.47e8 complex states)
+	if (B.big2) launch_lds(B.k.up_big[dot], nb, kPbBig2Threads, pb_big2_lds_bytes(B.W), st, a);
+	else launch_lds(B.k.up_big[dot], nb, kPbBigThreads, pb_big_lds_bytes(B.W), st, a);
 	return partial ? nb : 0;
 }
 
@@ -484,64 +496,20 @@ static void pb_launch_down_plain(const PbState& B, PbDownArgs& d, hipStream_t st
 	const bool tasks = B.down_tasks;
 	if (tasks) d.pace = nullptr;
 	if (d.pace) (void)hipMemsetAsync(d.pace, 0, sizeof(int) * 8 * (size_t)d.npanels, st);
-#define LPP_PB_DOWN_PLAIN(WIDE_, CPLX_, PF_)                                                                           \
-	do {                                                                                                              \
-		const size_t lds_ = PF_ ? B.down_lds_pf : B.down_lds;                                                            \
-		(void)hipFuncSetAttribute((const void*)k_pb_down<1024, false, WIDE_, CPLX_, PF_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_); \
-		k_pb_down<1024, false, WIDE_, CPLX_, PF_><<<B.down_grid, 1024, lds_, st>>>(d);                                  \
-	} while (0)
-	if (B.cplx && B.wide) {
-		if (tasks) LPP_PB_DOWN_PLAIN(true, true, true);
-		else LPP_PB_DOWN_PLAIN(true, true, false);
-	} else if (B.cplx) {
-		if (tasks) LPP_PB_DOWN_PLAIN(false, true, true);
-		else LPP_PB_DOWN_PLAIN(false, true, false);
-	} else if (B.wide) {
-		if (tasks) LPP_PB_DOWN_PLAIN(true, false, true);
-		else LPP_PB_DOWN_PLAIN(true, false, false);
-	} else {
-		if (tasks) LPP_PB_DOWN_PLAIN(false, false, true);
-		else LPP_PB_DOWN_PLAIN(false, false, false);
-	}
-#undef LPP_PB_DOWN_PLAIN
+	launch_lds(B.k.down, B.down_grid, 1024, tasks ? B.down_lds_pf : B.down_lds, st, d);
 }
 
 // block couplings over parts of the source range: z = alpha C y on rows of `pitch` positions; returns the number of partials written
 static int launch_down_parts(lpp_engine* e, const double* y, double* z, int64_t pitch, double* partial, const EpiScale& sc, hipStream_t st)
 {
 	const PbState& B = e->pb;
-	PbDownPartsArgs d;
-	d.pitch = pitch;
-	d.n_blk = B.n_blk;
-	d.npanels = (int)(pitch / 16);
-	d.ids_per_wg = B.ids_per_wg;
-	d.nparts = B.nparts;
-	d.ent_cap = B.ent_cap;
-	d.c_ptr = B.c_ptr;
-	d.c_col = B.c_col;
-	d.c_code = B.c_code;
-	d.c_pstart = B.c_pstart;
-	d.order = B.order;
-	d.dict = B.dict;
+	PbDownPartsArgs d = down_parts_args(B, pitch);
 	d.y = y;
 	d.z = z;
 	d.partial = partial;
 	d.sc = sc;
-	d.pace = B.pace;
-	d.pace_stride = B.pace_stride;
 	if (d.pace) (void)hipMemsetAsync(d.pace, 0, sizeof(int) * 8 * (size_t)B.pace_stride, st);
-#define LPP_PB_PARTS(R_)                                                                                               \
-	do {                                                                                                              \
-		(void)hipFuncSetAttribute((const void*)k_pb_down_parts<kPbPartsThreads, R_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)B.down_lds); \
-		k_pb_down_parts<kPbPartsThreads, R_><<<B.down_grid, kPbPartsThreads, B.down_lds, st>>>(d);                      \
-	} while (0)
-	if (B.maxr <= 4) LPP_PB_PARTS(4);
-	else if (B.maxr <= 8) LPP_PB_PARTS(8);
-	else if (B.maxr <= 12) LPP_PB_PARTS(12);
-	else if (B.maxr <= 16) LPP_PB_PARTS(16);
-	else if (B.maxr <= 20) LPP_PB_PARTS(20);
-	else LPP_PB_PARTS(24);
-#undef LPP_PB_PARTS
+	launch_lds(B.k.down_parts, B.down_grid, kPbPartsThreads, B.down_lds, st, d);
 	return partial ? B.down_grid : 0;
 }
 
@@ -582,9 +550,7 @@ int pb_launch(lpp_engine* e, const void* y, void* x, double* partial, const EpiS
 		u.u = B.u;
 		u.partial = partial;
 		u.sc = sc;
-		const size_t lds = pb_up_lds_bytes(B.pitch, B.spb, B.G);
-		if (partial) launch_up<true>(B, u, nb, lds, st);
-		else launch_up<false>(B, u, nb, lds, st);
+		launch_lds(B.k.up[partial ? 1 : 0], nb, kPbUpThreads, pb_up_lds_bytes(B.pitch, B.spb, B.G), st, u);
 	}
 	if (!defer_combine) {
 		PbCombineArgs c = combine_args(B, x, y, sc);
@@ -617,7 +583,7 @@ void pb_tx_up(lpp_engine* e, const void* y, const EpiScale& sc, int64_t b0, int6
 	u.u = B.u + b0 * B.pitch;
 	u.sc = sc;
 	const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(cnt, (int64_t)e->num_cus));
-	launch_up<false>(B, u, nb, pb_up_lds_bytes(B.pitch, B.spb, B.G), e->stream);
+	launch_lds(B.k.up[0], nb, kPbUpThreads, pb_up_lds_bytes(B.pitch, B.spb, B.G), e->stream, u);
 }
 
 void pb_tx_down(lpp_engine* e, const void* gath, void* send2, const EpiScale& sc)
@@ -648,12 +614,6 @@ int pb_tx_unpack_combine(lpp_engine* e, void* x, const void* y, const void* recv
 // (a plain-stream diagonal is attached by pb_build's caller, after the build: the streaming pass of the three-kernel form adds it)
 bool pb_chain_ok(const lpp_engine* e) { return e->pb.chain_ok && !e->pb.dval; }
 
-template <int GT, int PRE0 = kPbPre> static void launch_up_chain(const PbUpArgs& u, int nb, size_t lds, hipStream_t st)
-{
-	(void)hipFuncSetAttribute((const void*)k_pb_up<false, GT, true, PRE0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-	k_pb_up<false, GT, true, PRE0><<<nb, kPbUpThreads, lds, st>>>(u);
-}
-
 // One scale-free Lanczos step in two launches.  In: w (= w_{j-1}, or r_j itself when g_a is null) and y (= r_{j-1}).
 // Out: w holds r_j, y holds w_j = alpha H r_j + beta r_{j-1} (the in-block part passes through pb.u); partial holds pairs (Re<r_j|w_j>, |w_j|^2), their number is returned
 // (negative: the state is not one the chained kernels serve, nothing was launched).
@@ -662,7 +622,7 @@ int pb_launch_chain(lpp_engine* e, void* w, void* y, double* partial, const EpiS
 	PbState& B = e->pb;
 	hipStream_t st = e->stream;
 	// k_pb_down<RMW> adds u_in and touches the u lines ahead once per panel: one LDS image per workgroup, whatever let the caller in here
-	if (B.down_rounds != 1) return -1;
+	if (B.down_rounds != 1 || !B.k.up_chain || !B.k.down_chain) return -1;
 	const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(B.n_blk, (int64_t)e->num_cus));
 	PbUpArgs u = up_args(B);
 	u.dcode = B.dcode;
@@ -673,15 +633,8 @@ int pb_launch_chain(lpp_engine* e, void* w, void* y, double* partial, const EpiS
 	u.ybuf = (double*)y;
 	u.g_a = g_a;
 	u.g_b2 = g_b2;
-	{
-		// beta r_{j-1} rides in u (k_pb_up<CHAIN>), so the coupling kernel reads one stream less
-		const size_t lds = pb_up_lds_bytes(B.pitch, B.spb, B.G);
-		if (B.G == 1) launch_up_chain<1>(u, nb, lds, st);
-		else if (B.G > 2) launch_up_chain<0>(u, nb, lds, st);
-		else if (B.pre0 == kPreLo) launch_up_chain<2, kPreLo>(u, nb, lds, st);
-		else if (B.pre0 == kPreHi) launch_up_chain<2, kPreHi>(u, nb, lds, st);
-		else launch_up_chain<2>(u, nb, lds, st);
-	}
+	// beta r_{j-1} rides in u (k_pb_up<CHAIN>), so the coupling kernel reads one stream less
+	launch_lds(B.k.up_chain, nb, kPbUpThreads, pb_up_lds_bytes(B.pitch, B.spb, B.G), st, u);
 	PbDownArgs d = down_args(B, B.pitch);
 	d.y = (const double*)w;
 	d.z = (double*)y;
@@ -700,17 +653,7 @@ int pb_launch_chain(lpp_engine* e, void* w, void* y, double* partial, const EpiS
 	// a panel beyond an XCD's L2 keeps it too (PbState::chain_drop_pace)
 	if (B.chain_drop_pace) d.pace = nullptr;
 	if (d.pace) (void)hipMemsetAsync(d.pace, 0, sizeof(int) * 8 * (size_t)d.npanels, st);
-#define LPP_PB_DOWN_RMW(CPLX_, PF_)                                                                                    \
-	do {                                                                                                              \
-		const size_t lds_ = PF_ ? B.down_lds_pf : B.down_lds;                                                            \
-		(void)hipFuncSetAttribute((const void*)k_pb_down<1024, true, false, CPLX_, PF_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_); \
-		k_pb_down<1024, true, false, CPLX_, PF_><<<B.down_grid, 1024, lds_, st>>>(d);                                   \
-	} while (0)
-	if (B.cplx && pf) LPP_PB_DOWN_RMW(true, true);
-	else if (B.cplx) LPP_PB_DOWN_RMW(true, false);
-	else if (pf) LPP_PB_DOWN_RMW(false, true);
-	else LPP_PB_DOWN_RMW(false, false);
-#undef LPP_PB_DOWN_RMW
+	launch_lds(B.k.down_chain, B.down_grid, 1024, pf ? B.down_lds_pf : B.down_lds, st, d);
 	return B.down_grid;
 }
 
@@ -901,7 +844,7 @@ lpp_status pb_chain(lpp_engine* e, const AsmParams& P, int L, int n, const std::
 	if (getenv("LPP_VERBOSE"))
 		fprintf(stderr, "lpp: chain as one block of the segmented form %s (L = %d, n = %d, %d high sites, %zu segments, %zu items of <= %d positions, <= %d + %d hops per segment)\n",
 		        ok ? "planned" : "does not apply", SP.L, SP.n, SP.s, SP.segs.size(), SP.items.size(), SP.wmax, SP.max_cross, SP.max_hh);
-	if (!ok || SP.n_up != n_up || SP.nc_pad > 2) return LPP_OK; // (one block per workgroup: the instances with <= 2 pairs of cross hops)
+	if (!ok || SP.n_up != n_up || inst_index(kPbSegShapes, PbSegShape { SP.nc_pad, SP.nh_pad, 1 }) < 0) return LPP_OK; // (an instance with one block per workgroup)
 	hipStream_t st = e->stream;
 	DevBuf d_dval, d_len, d_sum, d_y, d_x, d_ys, d_xs;
 	// D: the diagonal of every row straight from the state (the assembler's diag_of: Heisenberg.h:251-275 in the reference's loop order),

@@ -1,6 +1,8 @@
 // lpp_pb_plan.cpp -- the product-basis build's decisions and host data (lpp_pb_plan.h); pb_build (lpp_pb.hip) uploads the result.
 #include "lpp_pb_plan.h"
 
+#include "lpp_pb_instances.h"
+
 #include <algorithm>
 #include <climits>
 #include <cstdio>
@@ -303,9 +305,10 @@ lpp_status plan_template(const PbBuildInput& in, const PbSwitches& sw, const Cho
 	B.pre0 = kPbPre;
 	const bool pairs = kPbPairs && !B.big; // one-window form: chunk pairs, even look-ahead depths (2,6), (4,4) or (6,4)
 	if (T.G == 2 && !B.seg) {
-		// look-ahead split of the in-block kernels: the depth pair (3,5), (4,4) or (5,3) that leaves the fewest chunks beyond it
+		// look-ahead split of the in-block kernels: the depth pair (3,5), (4,4) or (5,3) that leaves the fewest chunks beyond it, among the
+		// depths the kernel is instantiated for (lpp_pb_instances.h)
 		int64_t best = -1;
-		for (int p0 = pairs ? 2 : 3; p0 <= (pairs ? 6 : 5); p0 += pairs ? 2 : 1) {
+		pb_for_each_pre0(B.big, [&](int p0) {
 			int64_t beyond = 0;
 			const int p1 = pairs ? pb_depth(2, 1, p0) : 2 * kPbPre - p0;
 			for (int j = 0; j < T.spb; j++) beyond += std::max(0, (int)T.len[(size_t)j * 2] - p0) + std::max(0, (int)T.len[(size_t)j * 2 + 1] - p1);
@@ -313,8 +316,8 @@ lpp_status plan_template(const PbBuildInput& in, const PbSwitches& sw, const Cho
 				best = beyond;
 				B.pre0 = p0;
 			}
-		}
-		if (sw.pre0.set) B.pre0 = pairs ? std::max(2, std::min(sw.pre0.v, 6)) & ~1 : std::max(3, std::min(sw.pre0.v, 5));
+		});
+		if (sw.pre0.set) B.pre0 = pb_listed_pre0(B.big, sw.pre0.v);
 	}
 	if (pairs && !B.seg) repack_chunk_pairs(T);
 	B.tw_words = (int64_t)T.words.size();
@@ -556,6 +559,28 @@ lpp_status pb_plan(const PbBuildInput& in, const PbSwitches& sw, int num_cus, Pb
 	if ((rc = plan_couplings(in, P, &longest)) != LPP_OK) return rc;
 	if ((rc = plan_down_geometry(sw, c, num_cus, longest, P)) != LPP_OK) return rc;
 	plan_launch_forms(sw, P.form);
+	return pb_check_instances(P.form);
+}
+
+lpp_status pb_check_instances(const PbForm& B)
+{
+	const char* missing = nullptr;
+	auto need = [&](int index, const char* kernel) {
+		if (index < 0 && !missing) missing = kernel;
+	};
+	for (const bool dot : { false, true }) {
+		if (B.seg) need(inst_index(kPbSegInsts, pb_seg_inst(B, dot)), "k_pb_up_seg");
+		else if (B.big2) need(inst_index(kPbBig2Insts, pb_big2_inst(B, dot)), "k_pb_up_big2");
+		else if (B.big) need(inst_index(kPbBigInsts, pb_big_inst(B, dot)), "k_pb_up_big");
+		else need(inst_index(kPbUpInsts, pb_up_inst(B, dot, false)), "k_pb_up");
+	}
+	if (B.parts) need(inst_index(kPbPartsInsts, pb_parts_inst(B)), "k_pb_down_parts");
+	else need(inst_index(kPbDownInsts, pb_down_inst(B, false)), "k_pb_down");
+	if (B.chain_ok) {
+		need(inst_index(kPbUpInsts, pb_up_inst(B, false, true)), "k_pb_up (chained)");
+		need(inst_index(kPbDownInsts, pb_down_inst(B, true)), "k_pb_down (chained)");
+	}
+	if (missing) return fail(LPP_ERR_INVALID, std::string("pb_build: no kernel instance for ") + missing + " of this form");
 	return LPP_OK;
 }
 

@@ -123,6 +123,9 @@ void pb_list_length_order(const PbBuildInput& in, std::vector<int32_t>& perm, st
                           std::vector<double>& p_va);
 // LPP_ERR_INVALID with a "pb_build: ..." message: the layout does not hold this matrix, the caller keeps the general one
 lpp_status pb_plan(const PbBuildInput& in, const PbSwitches& sw, int num_cus, PbPlan& out);
+// pb_plan's last step: every kernel instance the launches of this form ask for is in its list (lpp_pb_instances.h); otherwise
+// LPP_ERR_INVALID, "pb_build: no kernel instance for ..."
+lpp_status pb_check_instances(const PbForm& B);
 // the LPP_VERBOSE lines of a plan, to stderr
 void pb_plan_print(const PbPlan& P);
 

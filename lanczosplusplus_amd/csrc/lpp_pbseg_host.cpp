@@ -8,6 +8,7 @@
 #include <map>
 
 #include "lpp_host.h"
+#include "lpp_pb_instances.h"
 #include "lpp_pbseg.h"
 
 namespace lpp {
@@ -464,18 +465,16 @@ lpp_status pb_seg_plan_model(int L, int n, const std::vector<double>& hv, const 
 	// every segment's lists padded to the kernel instance's width with entries of value 0.0 that read valid addresses: the slice
 	// loop then carries no condition at all (padded cross entries: a table of the segment's own class -- or table 0, the longest --
 	// and the row's first elements; padded high-high entries: the segment itself)
-	// kernel instances (NC, NH): (2, 2), (5, 4), (6, 8) and -- one block per workgroup only: chains -- (1, 12), (2, 12)
 	if (one_block) { // k_pb_up_seg<..., ROWS = 1> reads the first hop of a pair only: a chain's high sites have one low neighbour each
 		for (const SegCross& c : P.cross)
 			if (c.val[1] != 0.0) return LPP_OK;
 	}
-	if (P.max_cross <= 2 && P.max_hh <= 2) P.nc_pad = 2, P.nh_pad = 2;
-	else if (one_block && P.max_cross <= 1) P.nc_pad = 1, P.nh_pad = P.max_hh <= 12 ? 12 : 16; // an open chain: the one bond between the low and the high sites
-	else if (one_block && P.max_cross <= 2) P.nc_pad = 2, P.nh_pad = P.max_hh <= 12 ? 12 : 16; // ... and the bond between the two ends
-	else if (one_block) return LPP_OK;
-	else if (P.max_cross <= 5 && P.max_hh <= 4) P.nc_pad = 5, P.nh_pad = 4;
-	else if (P.max_cross <= 6 && P.max_hh <= 8) P.nc_pad = 6, P.nh_pad = 8;
-	else return LPP_OK;
+	// the first (NC, NH) the kernel is instantiated for that holds them (kPbSegShapes, lpp_pb_instances.h); one block per workgroup: an open
+	// chain has the one bond between the low and the high sites (NC = 1), a ring the bond between the two ends too (NC = 2)
+	const PbSegShape* const shape = pb_seg_shape_for(P.max_cross, P.max_hh, one_block ? 1 : 2);
+	if (!shape) return LPP_OK;
+	P.nc_pad = shape->nc;
+	P.nh_pad = shape->nh;
 	{
 		std::vector<SegCross> cp(P.segs.size() * (size_t)P.nc_pad);
 		std::vector<SegHh> hp(P.segs.size() * (size_t)P.nh_pad);

@@ -10,6 +10,7 @@
 
 #include "lpp_assemble_kernels.h"
 #include "lpp_engine_impl.h"
+#include "lpp_launch.h"
 #include "lpp_tj_kernels.h"
 
 using namespace lpp;
@@ -151,22 +152,13 @@ int tj_launch(lpp_engine* e, const void* src, void* x, const void* ydot, double*
 	const bool dot = ydot != nullptr && partial != nullptr;
 	hipStream_t st = e->stream;
 	const size_t lds = tj_lds_bytes(e->esz, S.nhi, S.nlo);
-	if (!e->is_complex) {
-		if (dot)
-			k_tj_apply<double, false, true><<<S.grid, kTjThreads, lds, st>>>(a);
-		else
-			k_tj_apply<double, false, false><<<S.grid, kTjThreads, lds, st>>>(a);
-	} else if (S.cplx_hops) {
-		if (dot)
-			k_tj_apply<cplx, true, true><<<S.grid, kTjThreads, lds, st>>>(a);
-		else
-			k_tj_apply<cplx, true, false><<<S.grid, kTjThreads, lds, st>>>(a);
-	} else {
-		if (dot)
-			k_tj_apply<cplx, false, true><<<S.grid, kTjThreads, lds, st>>>(a);
-		else
-			k_tj_apply<cplx, false, false><<<S.grid, kTjThreads, lds, st>>>(a);
-	}
+	// (complex hoppings are a form of the complex engine only: a real engine runs the real kernel whatever the state says)
+	with_flags(
+	    [&](auto cx, auto hops, auto with_dot) {
+		    using T = std::conditional_t<decltype(cx)::value, cplx, double>;
+		    if constexpr (decltype(cx)::value || !decltype(hops)::value) k_tj_apply<T, decltype(hops)::value, decltype(with_dot)::value><<<S.grid, kTjThreads, lds, st>>>(a);
+	    },
+	    e->is_complex != 0, e->is_complex && S.cplx_hops, dot);
 	return dot ? S.grid : 0;
 }
 

@@ -4,15 +4,18 @@
 // as the block couplings C.  Over small species, block counts, CU counts, the exchange on and off and the forced forms it checks what every plan
 // must satisfy (permutations, P T P^T, the chunk-pair repack, coupling codes, block bases, block order, rounds, part starts, LDS bounds), the
 // launch forms at the sizes of the suite's 2x6 ladder, the coupling kernel's geometry at 256 CUs for the cases of tests/test_gpu_pb_down_edges.py
-// (the forced grid and forced rounds included), and the text of every refusal these sizes reach.
+// (the forced grid and forced rounds included), the text of every refusal these sizes reach, and the kernel instance lists (csrc/lpp_pb_instances.h):
+// their sizes, that every plan made here finds its kernels in them, and that a form without an instance is refused.
 // Prints `ok` and returns 0, or says what failed and returns 1.
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
 
+#include "lpp_pb_instances.h"
 #include "lpp_pb_plan.h"
 
 using namespace lpp;
@@ -328,6 +331,9 @@ std::vector<Forced> forced_forms()
 	return f;
 }
 
+void check_keys(const PbForm& B); // (kernel instances: below)
+void note_shape(const PbForm& B);
+
 int plans = 0, refused = 0, seen_perm = 0, seen_seg = 0, seen_big2 = 0, seen_rounds3 = 0, seen_parts3 = 0, seen_two_groups = 0;
 void run(const Problem& p, const PbSwitches& sw, int num_cus)
 {
@@ -340,6 +346,8 @@ void run(const Problem& p, const PbSwitches& sw, int num_cus)
 	}
 	plans++;
 	check_plan(p.in, sw, num_cus, P);
+	check_keys(P.form);
+	note_shape(P.form);
 	seen_perm += !P.form.seg && !P.perm.empty();
 	seen_seg += P.form.seg;
 	seen_big2 += P.form.big2 && !P.form.seg;
@@ -619,6 +627,141 @@ void check_down_edge_cases()
 	}
 }
 
+// ---- kernel instances (csrc/lpp_pb_instances.h) -------------------------------------------------------------------------------------------
+template <typename K, size_t N> bool no_duplicates(const std::array<K, N>& list)
+{
+	for (size_t i = 0; i < N; i++)
+		for (size_t j = i + 1; j < N; j++)
+			if (list[i] == list[j]) return false;
+	return true;
+}
+
+// every kernel the launches of a planned form ask for, looked up key by key (what pb_plan's last step checks in one go)
+void check_keys(const PbForm& B)
+{
+	CHECK(pb_check_instances(B) == LPP_OK);
+	for (const bool dot : { false, true }) {
+		if (B.seg) CHECK(inst_index(kPbSegInsts, pb_seg_inst(B, dot)) >= 0);
+		else if (B.big2) CHECK(inst_index(kPbBig2Insts, pb_big2_inst(B, dot)) >= 0);
+		else if (B.big) CHECK(inst_index(kPbBigInsts, pb_big_inst(B, dot)) >= 0);
+		else CHECK(inst_index(kPbUpInsts, pb_up_inst(B, dot, false)) >= 0);
+	}
+	if (B.parts) CHECK(inst_index(kPbPartsInsts, pb_parts_inst(B)) >= 0 && pb_parts_inst(B).r == B.maxr);
+	else CHECK(inst_index(kPbDownInsts, pb_down_inst(B, false)) >= 0);
+	if (B.chain_ok) CHECK(inst_index(kPbUpInsts, pb_up_inst(B, false, true)) >= 0 && inst_index(kPbDownInsts, pb_down_inst(B, true)) >= 0);
+}
+
+// the up spins of a Heisenberg chain as ONE block of the segmented form, planned from the model and handed to pb_plan ready-made (pb_chain)
+bool plan_chain(int L, int n, bool ring, PbPlan& P)
+{
+	std::vector<double> hv((size_t)L * L, 0.0);
+	std::vector<int64_t> cnt((size_t)L * L, 0);
+	for (int i = 0; i < (ring ? L : L - 1); i++) {
+		const int j = (i + 1) % L;
+		hv[(size_t)i * L + j] = hv[(size_t)j * L + i] = 0.5;
+		cnt[(size_t)i * L + j] = cnt[(size_t)j * L + i] = 1;
+	}
+	SegPlan SP;
+	bool ok = false;
+	if (pb_seg_plan_model(L, n, hv, cnt, 64, SP, &ok, true) != LPP_OK || !ok) return false;
+	const int64_t c_rp[2] = { 0, 0 };
+	const std::vector<double> dict(256, 0.0);
+	PbBuildInput in;
+	in.n_up = SP.n_up;
+	in.n_blk = 1;
+	in.c_rp = c_rp;
+	in.dict256 = dict.data();
+	in.ndict = 1;
+	in.pre = &SP;
+	in.pre_nnz = 1;
+	PbSwitches sw;
+	sw.piece_rows = on(64);
+	return pb_plan(in, sw, 256, P) == LPP_OK;
+}
+
+int seen_shape[kPbSegShapes.size()] = { 0 };
+void note_shape(const PbForm& B)
+{
+	if (!B.seg) return;
+	const int at = inst_index(kPbSegShapes, PbSegShape { B.seg_nc, B.seg_nh, B.seg_one ? 1 : 2 });
+	CHECK(at >= 0);
+	if (at >= 0) seen_shape[at]++;
+}
+
+void check_instances()
+{
+	CHECK(kPbUpInsts.size() == 15 && kPbBigInsts.size() == 8 && kPbBig2Insts.size() == 10 && kPbSegInsts.size() == 48 && kPbDownInsts.size() == 12 && kPbPartsInsts.size() == 6);
+	CHECK(no_duplicates(kPbUpInsts) && no_duplicates(kPbBigInsts) && no_duplicates(kPbBig2Insts) && no_duplicates(kPbSegInsts) && no_duplicates(kPbDownInsts) && no_duplicates(kPbPartsInsts));
+	CHECK(no_duplicates(kPbSegShapes) && no_duplicates(kPbSegDepths) && no_duplicates(kPbUpDepths) && no_duplicates(kPbBigDepths) && no_duplicates(kPbBig2Depths));
+	CHECK(inst_index(kPbPartsInsts, PbPartsInst { 28 }) == -1 && inst_index(kPbPartsInsts, PbPartsInst { 24 }) == 5 && inst_index(kPbUpInsts, kPbUpInsts[7]) == 7);
+	// LPP_PB_PRE0 = 0 .. 8 lands on a listed depth in the one-window form (216 blocks of 924 positions) and by pieces (k_pb_up_big2)
+	const Csr S = species(12, 6, true, -1.0);
+	Problem p;
+	make_problem(p, S, species(9, 4, true, -1.0), false);
+	for (int v = 0; v <= 8; v++)
+		for (const bool pieces : { false, true }) {
+			PbSwitches sw;
+			sw.pre0 = on(v);
+			if (pieces) sw.piece_rows = on(128);
+			PbPlan P;
+			CHECK(pb_plan(p.in, sw, 256, P) == LPP_OK && P.form.G == 2 && P.form.big2 == pieces && !P.form.seg);
+			check_keys(P.form);
+			const int want = pieces ? std::max(3, std::min(v, 5)) : kPbPairs ? std::max(2, std::min(v, 6)) & ~1 : std::max(3, std::min(v, 5));
+			CHECK(P.form.pre0 == want);
+		}
+	// the shapes of the segmented kernel: two blocks per workgroup on rings and lattices, one block on chains
+	struct Lattice {
+		int L, n;
+		std::vector<double> hop;
+	};
+	std::vector<Lattice> lattices;
+	lattices.push_back({ 10, 4, hop_ring(10, -1.0, 0.0) });
+	lattices.push_back({ 12, 6, hop_ring(12, -1.0, 0.0) });
+	{ // a 4 x 3 lattice, periodic in both directions
+		std::vector<double> h(144, 0.0);
+		for (int x = 0; x < 4; x++)
+			for (int y = 0; y < 3; y++) {
+				const int i = x + 4 * y, r = (x + 1) % 4 + 4 * y, u = x + 4 * ((y + 1) % 3);
+				h[(size_t)i * 12 + r] = h[(size_t)r * 12 + i] = -1.0;
+				h[(size_t)i * 12 + u] = h[(size_t)u * 12 + i] = -1.0;
+			}
+		lattices.push_back({ 12, 6, h });
+	}
+	for (const Lattice& l : lattices) {
+		make_problem(p, species_of(l.L, l.n, l.hop), species(6, 2, false, -1.0), false);
+		PbSwitches sw;
+		sw.piece_rows = on(64);
+		sw.seg = on(1);
+		PbPlan P;
+		CHECK(pb_plan(p.in, sw, 256, P) == LPP_OK);
+		CHECK(P.form.seg && !P.form.seg_one);
+		check_keys(P.form);
+		note_shape(P.form);
+	}
+	// (open: one bond between the low and the high sites; 10 sites: 2 high-high hops per segment, 16: 8, 21: 13)
+	for (const int L : { 10, 16, 21 })
+		for (const bool ring : { false, true }) {
+			PbPlan P;
+			CHECK(plan_chain(L, L / 2, ring, P) && P.form.seg && P.form.seg_one);
+			check_keys(P.form);
+			note_shape(P.form);
+		}
+	for (size_t k = 0; k < kPbSegShapes.size(); k++) // every (NC, NH, blocks per workgroup) of the list was planned by some fixture above or in main
+		if (seen_shape[k] == 0 && failures++ < 20) std::printf("FAILED no plan reached the shape (%d, %d, %d)\n", kPbSegShapes[k].nc, kPbSegShapes[k].nh, kPbSegShapes[k].rows);
+	{ // a form whose lists were padded to a width no instance has is refused by the planner's last step, in the build's words
+		PbPlan P;
+		CHECK(plan_chain(10, 5, false, P));
+		PbForm B = P.form;
+		B.seg_nc = 3;
+		CHECK(pb_check_instances(B) == LPP_ERR_INVALID && std::strncmp(lpp_last_error(), "pb_build: no kernel instance for k_pb_up_seg", 44) == 0);
+		B = P.form;
+		B.seg = false; // (pieces of one block: k_pb_up_big2 with three value groups has no instance either)
+		B.big2 = true;
+		B.G = 3;
+		CHECK(pb_check_instances(B) == LPP_ERR_INVALID && std::strncmp(lpp_last_error(), "pb_build: no kernel instance for k_pb_up_big2", 45) == 0);
+	}
+}
+
 } // namespace
 
 int main()
@@ -656,6 +799,7 @@ int main()
 	check_refusals();
 	check_launch_forms();
 	check_down_edge_cases();
+	check_instances();
 	if (failures) {
 		std::printf("%d checks failed (%d plans, %d refusals)\n", failures, plans, refused);
 		return 1;
