@@ -782,6 +782,55 @@ lpp_status lpp_engine_spectral_decomposition_sum_heis(lpp_engine* e, int32_t sta
                                                       int32_t ndown, int32_t nweights, const double* w_re, const double* w_im, double* weight, int32_t* nsteps, double* a,
                                                       double* b, lpp_stats* stats);
 
+/* ---- observables of the spin-S Heisenberg digit basis (opt-in, added under ABI 7 with no struct change) ----
+ * BasisHeisenberg (reference BasisHeisenberg.h:24-47) for any twiceS lpp_engine_assemble_heisenberg_spin admits: L digits of `bits` bits, site p at bit
+ * offset p * bits, digit d = m + S in [0, twiceS], the words of digit sum szPlusConst ascending.  The reference THROWS for spins above 1/2
+ * (BasisHeisenberg.h:130,263, Heisenberg.h:223), so the operators are the project's own definition, with m = d - S of the SOURCE state:
+ *   - splus: digit d -> d + 1, value sqrt(S(S+1) - m(m+1)), nothing leaves d = twiceS; sminus: digit d -> d - 1, value sqrt(S(S+1) - m(m-1)), nothing
+ *     leaves d = 0; sz: index kept, value m -- the TRUE S^z in every call of this family (there is no raw -2 S^z form), a value of 0 leaves the
+ *     destination untouched;
+ *   - n, c, cdagger: LPP_ERR_INVALID; the spin arguments are checked to be 0 or 1 and otherwise not read;
+ *   - S+ on the top sector (szPlusConst = nsites * twiceS) and S- on szPlusConst = 0 are LPP_ERR_INVALID, not "no sector"; a new sector is reported as
+ *     (szPlusConst +- 1, 0); whatever the assembler refuses (odd twiceS with twiceS + 1 no power of two, bits * nsites > 62) is LPP_ERR_INVALID here,
+ *     and so is twiceS > 4095.
+ * Every call takes (nsites, twiceS, szPlusConst) where the families above take (nsites, nup, ndown); twiceS = 1 is accepted (splus / sminus then
+ * equal the _heis calls bit for bit, sz is -1/2 times their raw one).  Otherwise the contracts are those of the _heis calls of the same name:
+ * two_point gives result[i][j] = <A_j bra | A_i ket> (<S^z_j S^z_i>, <S^-_j S^+_i>) and the trace; spectral_decomposition builds
+ * A_i |state> + isign A_j |state> (a diagonal pair is accumulated twice), sz decomposes in the state's own sector on a sector engine of that sector.
+ * Resident states whose length is not the sector's size are refused.  The operator sums always chain the one-site launches (no fused kernel).
+ * Operator strings, the reduced density matrix and partitioned engines stay refused for these spins.
+ * lpp_obs_plan_heis_spin (host only): *n_dst, *low_digits = the cut lb (a site below it gathers inside the runs of equal high part, a site at or
+ * above it maps run onto run), and where not NULL action[dst] = src + 1 or 0 and coef[dst] = the value (0 where untouched), expanded through the
+ * run table and the lookup function the kernel uses. */
+lpp_status lpp_obs_new_parts_heis_spin(int32_t op, int32_t spin, int32_t nsites, int32_t twiceS, int32_t szPlusConst, int32_t* has, int32_t* szPlusConst_new,
+                                       int32_t* zero);
+lpp_status lpp_obs_plan_heis_spin(int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t twiceS, int32_t szPlusConst, int32_t* has, int32_t* szPlusConst_new,
+                                  int64_t* n_dst, int32_t* low_digits, int64_t* action, double* coef);
+lpp_status lpp_engine_apply_operator_heis_spin(lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t twiceS, int32_t szPlusConst,
+                                               double factor_re, double factor_im, const void* d_src, void* d_dst, int32_t accumulate, int32_t* has);
+lpp_status lpp_engine_apply_operator_heis_spin_host(lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t twiceS, int32_t szPlusConst,
+                                                    double factor_re, double factor_im, const void* src, void* dst, int32_t accumulate, int32_t* has);
+lpp_status lpp_engine_bench_operator_heis_spin(lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t twiceS, int32_t szPlusConst,
+                                               int32_t warmup, int32_t iters, double* ms_per_launch, double* model_bytes);
+lpp_status lpp_engine_two_point_heis_spin(lpp_engine* e, int32_t op, int32_t spin1, int32_t spin2, int32_t nsites, int32_t twiceS, int32_t szPlusConst,
+                                          int32_t bra_state, int32_t ket_state, void* result, void* trace);
+lpp_status lpp_engine_spectral_decomposition_heis_spin(lpp_engine* e, int32_t state, lpp_engine* sector, int32_t op, int32_t isite, int32_t jsite, int32_t spin,
+                                                       double isign, int32_t nsites, int32_t twiceS, int32_t szPlusConst, double* weight, int32_t* nsteps, double* a,
+                                                       double* b, lpp_stats* stats);
+lpp_status lpp_engine_apply_operator_sum_heis_spin(lpp_engine* e, int32_t op, int32_t spin, int32_t nsites, int32_t twiceS, int32_t szPlusConst, int32_t nweights,
+                                                   const double* w_re, const double* w_im, const void* d_src, void* d_dst, int32_t accumulate, int32_t* has);
+lpp_status lpp_engine_apply_operator_sum_heis_spin_host(lpp_engine* e, int32_t op, int32_t spin, int32_t nsites, int32_t twiceS, int32_t szPlusConst, int32_t nweights,
+                                                        const double* w_re, const double* w_im, const void* src, void* dst, int32_t accumulate, int32_t* has,
+                                                        int64_t* n_dst);
+lpp_status lpp_engine_bench_operator_sum_heis_spin(lpp_engine* e, int32_t op, int32_t spin, int32_t nsites, int32_t twiceS, int32_t szPlusConst, int32_t nweights,
+                                                   const double* w_re, const double* w_im, int32_t accumulate, int32_t warmup, int32_t iters, double* ms_per_launch,
+                                                   double* model_bytes);
+lpp_status lpp_engine_sum_norm2_heis_spin(lpp_engine* e, int32_t state, int32_t op, int32_t spin, int32_t nsites, int32_t twiceS, int32_t szPlusConst, int32_t nweights,
+                                          const double* w_re, const double* w_im, double* norm2, int32_t* has);
+lpp_status lpp_engine_spectral_decomposition_sum_heis_spin(lpp_engine* e, int32_t state, lpp_engine* sector, int32_t op, int32_t spin, int32_t nsites, int32_t twiceS,
+                                                           int32_t szPlusConst, int32_t nweights, const double* w_re, const double* w_im, double* weight,
+                                                           int32_t* nsteps, double* a, double* b, lpp_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

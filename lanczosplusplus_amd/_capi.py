@@ -154,6 +154,14 @@ SYMBOLS = {
     "lpp_engine_two_point_heis": (C.c_int32, [_P] + [C.c_int32] * 8 + [_P, _P]),
     "lpp_engine_spectral_decomposition_heis": (C.c_int32, [_P, C.c_int32, _P] + [C.c_int32] * 4 + [C.c_double] + [C.c_int32] * 3
                                                + [C.POINTER(C.c_double), C.POINTER(C.c_int32), _P, _P, C.POINTER(Stats)]),
+    "lpp_obs_new_parts_heis_spin": (C.c_int32, [C.c_int32] * 5 + [C.POINTER(C.c_int32)] * 3),
+    "lpp_obs_plan_heis_spin": (C.c_int32, [C.c_int32] * 6 + [C.POINTER(C.c_int32)] * 2 + [C.POINTER(C.c_int64), C.POINTER(C.c_int32), _P, _P]),
+    "lpp_engine_apply_operator_heis_spin": (C.c_int32, [_P] + [C.c_int32] * 6 + [C.c_double, C.c_double, _P, _P, C.c_int32, C.POINTER(C.c_int32)]),
+    "lpp_engine_apply_operator_heis_spin_host": (C.c_int32, [_P] + [C.c_int32] * 6 + [C.c_double, C.c_double, _P, _P, C.c_int32, C.POINTER(C.c_int32)]),
+    "lpp_engine_bench_operator_heis_spin": (C.c_int32, [_P] + [C.c_int32] * 8 + [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "lpp_engine_two_point_heis_spin": (C.c_int32, [_P] + [C.c_int32] * 8 + [_P, _P]),
+    "lpp_engine_spectral_decomposition_heis_spin": (C.c_int32, [_P, C.c_int32, _P] + [C.c_int32] * 4 + [C.c_double] + [C.c_int32] * 3
+                                                    + [C.POINTER(C.c_double), C.POINTER(C.c_int32), _P, _P, C.POINTER(Stats)]),
     "lpp_continued_fraction": (C.c_int32, [C.c_int32, _P, _P] + [C.c_double] * 5 + [_P]),
     "lpp_rdm_plan": (C.c_int32, [C.c_int32] * 5 + [C.POINTER(C.c_int32)] + [C.POINTER(C.c_int64)] * 4 + [_P, _P, _P, _P]),
     "lpp_engine_reduced_density_matrix": (C.c_int32, [_P] + [C.c_int32] * 5 + [_P, _P]),
@@ -189,8 +197,8 @@ SYMBOLS = {
     "lpp_engine_bench_string_dot_tj": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P] + [C.c_int32] * 5 + [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "lpp_obs_sum_plan": (C.c_int32, [C.c_int32] * 5 + [_P, _P] + [C.POINTER(C.c_int32)] * 3 + [C.POINTER(C.c_int64), C.POINTER(C.c_int32), _P, _P, _P, _P]),
 }
-# site-weighted operator sums: one signature per call, three families
-for _sfx in ("", "_tj", "_heis"):
+# site-weighted operator sums: one signature per call, four families
+for _sfx in ("", "_tj", "_heis", "_heis_spin"):
     SYMBOLS["lpp_engine_apply_operator_sum" + _sfx] = (C.c_int32, [_P] + [C.c_int32] * 6 + [_P, _P, _P, _P, C.c_int32, C.POINTER(C.c_int32)])
     SYMBOLS["lpp_engine_apply_operator_sum" + _sfx + "_host"] = (C.c_int32, [_P] + [C.c_int32] * 6 + [_P, _P, _P, _P, C.c_int32, C.POINTER(C.c_int32),
                                                                                                          C.POINTER(C.c_int64)])

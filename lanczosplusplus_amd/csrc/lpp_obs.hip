@@ -1,10 +1,12 @@
-// lpp_obs.hip -- ground-state observables of the Hubbard product basis, of the one-orbital t-J basis and of the S = 1/2 Heisenberg basis on one GPU:
+// lpp_obs.hip -- ground-state observables of the Hubbard product basis, of the one-orbital t-J basis, of the S = 1/2 Heisenberg basis and of the spin-S
+// Heisenberg digit basis on one GPU:
 // one-site operators applied to device vectors (Engine::accModifiedState_, reference src/Engine/Engine.h:416-458), the two-point matrix
 // (Engine::twoPoint :266-338), the modified state + decomposition of one spectral-function type (Engine::spectralFunction :134-206, getModifiedState
 // :494-533, calcSpectral :460-490), operator strings (Engine::manyPoint :341-389) and the continued-fraction evaluator.
 //
 // The device side only.  Each family is one ObsBasis: how its plan is built and uploaded (a DevPlan of its own in the engine's cache) and how it is
-// launched; every entry point is one body over an ObsBasis, and the four destination-driven apply kernels go through one launch (OBS_LAUNCH).
+// launched; every entry point is one body over an ObsBasis, and the four destination-driven apply kernels go through one launch (OBS_LAUNCH); the
+// spin-S kernel (lpp_obs_heis_spin_plan.h, lpp_obs_heis_spin_kernels.h) names its instance through lpp_launch.h's with_flags.
 // Operator strings have three families (HubbardStrings, HeisStrings, TjStrings) under one driver and one set of entry-point bodies (STRING_ENTRY).
 // The host planners (no GPU, plain C++) are lpp_obs_plan.h (shared sector arithmetic, Hubbard), lpp_obs_tj_plan.h, lpp_obs_heis_plan.h and
 // lpp_obs_string_plan.h, for strings in the Heisenberg basis lpp_obs_heis_string_plan.h, in the t-J basis lpp_obs_tj_string_plan.h; the kernels are
@@ -30,6 +32,8 @@
 #include "lpp_obs_string_kernels.h"
 #include "lpp_obs_tj_kernels.h"
 #include "lpp_obs_heis_kernels.h"
+#include "lpp_obs_heis_spin_kernels.h"
+#include "lpp_launch.h"
 #include "lpp_obs_heis_string_kernels.h"
 #include "lpp_obs_tj_string_kernels.h"
 
@@ -119,6 +123,9 @@ struct ObsBasis {
 	bool (*sum_fused)(int op);
 	lpp_status (*build_sum)(int op, int site, int spin, int L, int nup, int ndn, DevPlanPtr& out, hipError_t* err);
 	lpp_status (*launch_sum)(lpp_engine* e, const DevPlan& D, const double* w_re, const double* w_im, const void* d_src, void* d_dst, bool acc);
+	// the spin-S digit basis: the two counts are (twiceS, szPlusConst), sz is ONE operator of the basis (no n to split it into), and lpp_obs_new_parts*
+	// reports the new sector as (szPlusConst', 0)
+	bool spin_args = false;
 };
 
 // ---- the Hubbard product basis (plan: lpp_obs_plan.h, kernel: lpp_obs_kernels.h) ---------------------------------------------------------------
@@ -357,13 +364,66 @@ lpp_status launch_heis_sum(lpp_engine* e, const DevPlan& D0, const double* w_re,
 	return LPP_OK;
 }
 
-enum { BASIS_HUBBARD = 0, BASIS_TJ = 1, BASIS_HEIS = 2 };
+// ---- the spin-S Heisenberg digit basis (plan: lpp_obs_heis_spin_plan.h, kernel: lpp_obs_heis_spin_kernels.h); nup = twiceS, ndn = szPlusConst --------
+struct HeisSpinDev : DevPlan {
+	ObsHeisSpinPlan host; // the tables dropped after the upload
+	ObsHeisSpinRun* runs = nullptr;
+	uint16_t *word = nullptr, *rank = nullptr;
+	double* val = nullptr;
+	int64_t nruns = 0;
+	int nword = 0, nrank = 0;
+	~HeisSpinDev() override { free_tables({ runs, word, rank, val }); }
+};
+
+lpp_status build_heis_spin(int op, int site, int spin, int L, int twiceS, int m, DevPlanPtr& out, hipError_t* err)
+{
+	std::unique_ptr<HeisSpinDev> D(new HeisSpinDev());
+	ObsHeisSpinPlan& P = D->host;
+	const char* why = nullptr;
+	lpp_status st = plan_status(obs_plan_heis_spin(op, site, spin, L, twiceS, m, P, &why), why);
+	if (st != LPP_OK) return st;
+	D->has = true; // (this basis has no "no sector": the plan refuses S+ on the top sector and S- on szPlusConst = 0)
+	D->n_src = P.n_src;
+	D->n_dst = P.n_dst;
+	D->touched = heis_spin_touched(op, L, twiceS, P.m2);
+	D->nruns = (int64_t)P.runs.size() - 1;
+	D->nword = (int)P.word.size();
+	D->nrank = (int)P.rank.size();
+	D->bytes = sizeof(ObsHeisSpinRun) * P.runs.size();
+	*err = upload(&D->runs, P.runs);
+	if (*err == hipSuccess) *err = upload(&D->word, P.word);
+	if (*err == hipSuccess) *err = upload(&D->rank, P.rank);
+	if (*err == hipSuccess) *err = upload(&D->val, P.val);
+	out = std::move(D);
+	return LPP_OK;
+}
+
+lpp_status launch_heis_spin(lpp_engine* e, const DevPlan& D0, double fr, double fi, const void* d_src, void* d_dst, bool acc)
+{
+	const HeisSpinDev& D = static_cast<const HeisSpinDev&>(D0);
+	const ObsHeisSpinPlan& P = D.host;
+	const ObsHeisSpinArgs A { D.runs, D.word, D.rank, D.val, P.mode, D.nword, D.nrank, P.shift, P.mask, P.twiceS, D.nruns, D.n_dst, fr, fi };
+	const int grid = obs_grid(e, e->is_complex ? D.n_dst : (D.n_dst + 1) / 2);
+	const size_t lds = obs_heis_spin_lds_bytes(A.mode, A.nword, A.nrank);
+	with_flags(
+	    [&](auto cplx, auto accumulate) {
+		    k_obs_apply_heis_spin<decltype(cplx)::value, decltype(accumulate)::value><<<grid, kObsBlock, lds, e->stream>>>((double*)d_dst, (const double*)d_src, A);
+	    },
+	    e->is_complex, acc);
+	HIP_TRY(hipGetLastError());
+	return LPP_OK;
+}
+
+enum { BASIS_HUBBARD = 0, BASIS_TJ = 1, BASIS_HEIS = 2, BASIS_HEIS_SPIN = 3 };
 const ObsBasis kHubbard { BASIS_HUBBARD, false, true, true, false, true, [](int L, int nup, int ndn) { return L >= 1 && nup >= 0 && ndn >= 0 && nup <= L && ndn <= L; },
 	                      hubbard_sector_size, new_parts, build_hubbard, launch_hubbard, obs_sum_fused_op, build_hubbard_sum, launch_hubbard_sum };
 const ObsBasis kTj { BASIS_TJ, true, true, true, false, false, [](int L, int nup, int ndn) { return L >= 1 && nup >= 0 && ndn >= 0 && nup + ndn <= L; },
 	                 tj_sector_size, new_parts_tj, build_tj, launch_tj, nullptr, nullptr, nullptr };
 const ObsBasis kHeis { BASIS_HEIS, false, false, false, true, true, [](int L, int nup, int) { return heis_sector_size(L, nup, 0) >= 0; },
 	                   heis_sector_size, new_parts_heis, build_heis, launch_heis, heis_sum_fused_op, build_heis_sum, launch_heis_sum };
+// (reads_ndown: the cache key holds both counts, so it tells twiceS apart; the operator sums chain the one-site launches)
+const ObsBasis kHeisSpin { BASIS_HEIS_SPIN, false, true, false, true, true, [](int L, int twiceS, int m) { return heis_spin_sector_size(L, twiceS, m) >= 0; },
+	                       heis_spin_sector_size, new_parts_heis_spin, build_heis_spin, launch_heis_spin, nullptr, nullptr, nullptr, true };
 
 // The tables of one (operator, site, spin, sites, sector), uploaded once and kept with the engine.  The key is what the caller passes -- the engine
 // needs no model for lpp_engine_apply_operator -- so the cache is bounded: a density of states or a two-point matrix uses at most 2 * sites entries
@@ -443,10 +503,11 @@ lpp_status apply_dev(lpp_engine* e, const ObsBasis& B, int op, int site, int spi
 	return B.launch(e, *D, fr, fi, d_src, d_dst, acc);
 }
 
-// the operator Engine::accModifiedState applies (Engine.h:535-599): n directly, sz as n_up/2 - n_down/2, the others as given
+// the operator Engine::accModifiedState applies (Engine.h:535-599): n directly, sz as n_up/2 - n_down/2 (the spin-S digit basis: its own sz), the
+// others as given
 lpp_status acc_modified_dev(lpp_engine* e, const ObsBasis& B, int op, int site, int spin, int L, int nup, int ndn, double isign, const void* d_src, void* d_dst, bool acc, bool* has)
 {
-	if (op == LPP_OP_SZ) {
+	if (op == LPP_OP_SZ && !B.spin_args) {
 		lpp_status st = apply_dev(e, B, LPP_OP_N, site, LPP_SPIN_UP, L, nup, ndn, isign * 0.5, 0.0, d_src, d_dst, acc, has);
 		if (st != LPP_OK) return st;
 		return apply_dev(e, B, LPP_OP_N, site, LPP_SPIN_DOWN, L, nup, ndn, -isign * 0.5, 0.0, d_src, d_dst, true, has);
@@ -1451,6 +1512,7 @@ lpp_status new_parts_body(const ObsBasis& B, const std::string& who, int32_t op,
 	if (!B.new_parts(op, spin, nsites, nup, B.reads_ndown ? ndown : 0, &n1, &n2))
 		return B.no_sector_throws ? fail(LPP_ERR_INVALID, "hasNewParts: S+ to all ups or S- to all downs") : LPP_OK; // the reference throws (Heisenberg.h:239)
 	*has = 1;
+	if (B.spin_args) n1 = n2, n2 = 0; // (twiceS, szPlusConst') is reported as (szPlusConst', 0)
 	if (nup_new) *nup_new = n1;
 	if (ndown_new) *ndown_new = n2;
 	return LPP_OK;
@@ -1488,10 +1550,12 @@ void free_obs(lpp_engine* e)
 extern "C" {
 
 // One entry point per family over one body(basis, name, arguments...): the Hubbard product basis, the one-orbital t-J basis, the S = 1/2 Heisenberg basis
-#define OBS_ENTRY(body, hubbard, tj, heis, params, ...)                           \
+// and the spin-S Heisenberg digit basis, whose (nup, ndown) are (twiceS, szPlusConst)
+#define OBS_ENTRY(body, hubbard, tj, heis, heis_spin, params, ...)                \
 	lpp_status hubbard params { return body(kHubbard, #hubbard, __VA_ARGS__); } \
 	lpp_status tj params { return body(kTj, #tj, __VA_ARGS__); }                \
-	lpp_status heis params { return body(kHeis, #heis, __VA_ARGS__); }
+	lpp_status heis params { return body(kHeis, #heis, __VA_ARGS__); }          \
+	lpp_status heis_spin params { return body(kHeisSpin, #heis_spin, __VA_ARGS__); }
 
 lpp_status lpp_obs_plan(int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t* has, int32_t* nup_new, int32_t* ndown_new,
                         int64_t* n_up_dst, int64_t* n_down_dst, int32_t* table_up, int32_t* table_down)
@@ -1693,6 +1757,23 @@ lpp_status lpp_obs_plan_heis(int32_t op, int32_t site, int32_t spin, int32_t nsi
 	return LPP_OK;
 }
 
+lpp_status lpp_obs_plan_heis_spin(int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t twiceS, int32_t szPlusConst, int32_t* has, int32_t* szPlusConst_new,
+                                  int64_t* n_dst, int32_t* low_digits, int64_t* action, double* coef)
+{
+	if (!has) return fail(LPP_ERR_INVALID, "lpp_obs_plan_heis_spin: null argument");
+	*has = 0;
+	ObsHeisSpinPlan P;
+	const char* why = nullptr;
+	lpp_status st = plan_status(obs_plan_heis_spin(op, site, spin, nsites, twiceS, szPlusConst, P, &why), why);
+	if (st != LPP_OK) return st;
+	*has = 1;
+	if (szPlusConst_new) *szPlusConst_new = P.m2;
+	if (n_dst) *n_dst = P.n_dst;
+	if (low_digits) *low_digits = P.lb;
+	if (action || coef) heis_spin_expand(P, action, coef, nullptr);
+	return LPP_OK;
+}
+
 lpp_status lpp_continued_fraction(int32_t n, const double* a, const double* b, double eg, double weight, double sigma, double z_re, double z_im, double* out)
 {
 	if (n < 1 || !a || !b || !out) return fail(LPP_ERR_INVALID, "lpp_continued_fraction: bad argument");
@@ -1705,19 +1786,20 @@ lpp_status lpp_continued_fraction(int32_t n, const double* a, const double* b, d
 	return LPP_OK;
 }
 
-OBS_ENTRY(apply_operator_body, lpp_engine_apply_operator, lpp_engine_apply_operator_tj, lpp_engine_apply_operator_heis,
+OBS_ENTRY(apply_operator_body, lpp_engine_apply_operator, lpp_engine_apply_operator_tj, lpp_engine_apply_operator_heis, lpp_engine_apply_operator_heis_spin,
           (lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, double factor_re, double factor_im, const void* d_src, void* d_dst,
            int32_t accumulate, int32_t* has),
           e, op, site, spin, nsites, nup, ndown, factor_re, factor_im, d_src, d_dst, accumulate, has)
 OBS_ENTRY(apply_operator_host_body, lpp_engine_apply_operator_host, lpp_engine_apply_operator_tj_host, lpp_engine_apply_operator_heis_host,
+          lpp_engine_apply_operator_heis_spin_host,
           (lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, double factor_re, double factor_im, const void* src, void* dst,
            int32_t accumulate, int32_t* has),
           e, op, site, spin, nsites, nup, ndown, factor_re, factor_im, src, dst, accumulate, has)
-OBS_ENTRY(bench_operator_body, lpp_engine_bench_operator, lpp_engine_bench_operator_tj, lpp_engine_bench_operator_heis,
+OBS_ENTRY(bench_operator_body, lpp_engine_bench_operator, lpp_engine_bench_operator_tj, lpp_engine_bench_operator_heis, lpp_engine_bench_operator_heis_spin,
           (lpp_engine* e, int32_t op, int32_t site, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t warmup, int32_t iters, double* ms_per_launch,
            double* model_bytes),
           e, op, site, spin, nsites, nup, ndown, warmup, iters, ms_per_launch, model_bytes)
-OBS_ENTRY(new_parts_body, lpp_obs_new_parts, lpp_obs_new_parts_tj, lpp_obs_new_parts_heis,
+OBS_ENTRY(new_parts_body, lpp_obs_new_parts, lpp_obs_new_parts_tj, lpp_obs_new_parts_heis, lpp_obs_new_parts_heis_spin,
           (int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t* has, int32_t* nup_new, int32_t* ndown_new), op, spin, nsites, nup, ndown, has, nup_new,
           ndown_new)
 
@@ -1747,31 +1829,36 @@ lpp_status lpp_engine_state_to_host(lpp_engine* e, int32_t k, void* host)
 	return LPP_OK;
 }
 
-OBS_ENTRY(two_point_body, lpp_engine_two_point, lpp_engine_two_point_tj, lpp_engine_two_point_heis,
+OBS_ENTRY(two_point_body, lpp_engine_two_point, lpp_engine_two_point_tj, lpp_engine_two_point_heis, lpp_engine_two_point_heis_spin,
           (lpp_engine* e, int32_t op, int32_t spin1, int32_t spin2, int32_t nsites, int32_t nup, int32_t ndown, int32_t bra_state, int32_t ket_state, void* result, void* trace),
           e, op, spin1, spin2, nsites, nup, ndown, bra_state, ket_state, result, trace)
 OBS_ENTRY(spectral_body, lpp_engine_spectral_decomposition, lpp_engine_spectral_decomposition_tj, lpp_engine_spectral_decomposition_heis,
+          lpp_engine_spectral_decomposition_heis_spin,
           (lpp_engine* e, int32_t state, lpp_engine* sector, int32_t op, int32_t isite, int32_t jsite, int32_t spin, double isign, int32_t nsites, int32_t nup, int32_t ndown,
            double* weight, int32_t* nsteps, double* a, double* b, lpp_stats* stats),
           e, state, sector, op, isite, jsite, spin, isign, nsites, nup, ndown, weight, nsteps, a, b, stats)
 
 OBS_ENTRY(apply_sum_body, lpp_engine_apply_operator_sum, lpp_engine_apply_operator_sum_tj, lpp_engine_apply_operator_sum_heis,
+          lpp_engine_apply_operator_sum_heis_spin,
           (lpp_engine* e, int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t nweights, const double* w_re, const double* w_im, const void* d_src,
            void* d_dst, int32_t accumulate, int32_t* has),
           e, op, spin, nsites, nup, ndown, nweights, w_re, w_im, d_src, d_dst, accumulate, has)
 OBS_ENTRY(apply_sum_host_body, lpp_engine_apply_operator_sum_host, lpp_engine_apply_operator_sum_tj_host, lpp_engine_apply_operator_sum_heis_host,
+          lpp_engine_apply_operator_sum_heis_spin_host,
           (lpp_engine* e, int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t nweights, const double* w_re, const double* w_im, const void* src,
            void* dst, int32_t accumulate, int32_t* has, int64_t* n_dst),
           e, op, spin, nsites, nup, ndown, nweights, w_re, w_im, src, dst, accumulate, has, n_dst)
 OBS_ENTRY(bench_sum_body, lpp_engine_bench_operator_sum, lpp_engine_bench_operator_sum_tj, lpp_engine_bench_operator_sum_heis,
+          lpp_engine_bench_operator_sum_heis_spin,
           (lpp_engine* e, int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t nweights, const double* w_re, const double* w_im, int32_t accumulate,
            int32_t warmup, int32_t iters, double* ms_per_launch, double* model_bytes),
           e, op, spin, nsites, nup, ndown, nweights, w_re, w_im, accumulate, warmup, iters, ms_per_launch, model_bytes)
-OBS_ENTRY(sum_norm2_body, lpp_engine_sum_norm2, lpp_engine_sum_norm2_tj, lpp_engine_sum_norm2_heis,
+OBS_ENTRY(sum_norm2_body, lpp_engine_sum_norm2, lpp_engine_sum_norm2_tj, lpp_engine_sum_norm2_heis, lpp_engine_sum_norm2_heis_spin,
           (lpp_engine* e, int32_t state, int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t nweights, const double* w_re, const double* w_im,
            double* norm2, int32_t* has),
           e, state, op, spin, nsites, nup, ndown, nweights, w_re, w_im, norm2, has)
 OBS_ENTRY(spectral_sum_body, lpp_engine_spectral_decomposition_sum, lpp_engine_spectral_decomposition_sum_tj, lpp_engine_spectral_decomposition_sum_heis,
+          lpp_engine_spectral_decomposition_sum_heis_spin,
           (lpp_engine* e, int32_t state, lpp_engine* sector, int32_t op, int32_t spin, int32_t nsites, int32_t nup, int32_t ndown, int32_t nweights, const double* w_re,
            const double* w_im, double* weight, int32_t* nsteps, double* a, double* b, lpp_stats* stats),
           e, state, sector, op, spin, nsites, nup, ndown, nweights, w_re, w_im, weight, nsteps, a, b, stats)

@@ -343,9 +343,24 @@ class LanczosEngine:
             raise _capi.LppError(_capi.LPP_ERR_INVALID, "%s: the observables of a Heisenberg model need twiceS = 1 (the reference throws for higher spins)" % who)
         return True
 
-    def _obs_call(self, stem):
-        """the entry point of the engine's model: stem, stem_tj or stem_heis"""
-        return getattr(self._lib, stem + ("_tj" if self._is_tj() else "_heis" if self._is_heis() else ""))
+    def _obs_call(self, stem, spin=False):
+        """the entry point of the engine's model: stem, stem_tj or stem_heis; spin: stem_heis_spin (the opt-in digit basis)"""
+        return getattr(self._lib, stem + ("_heis_spin" if spin else "_tj" if self._is_tj() else "_heis" if self._is_heis() else ""))
+
+    def _spin_basis(self, who, basis):
+        """basis=None: the engine's own family, False.  basis="spin": the opt-in digit basis of a Heisenberg engine of any admitted twiceS, True
+        (LPP_ERR_INVALID on any other engine).  Anything else is a ValueError."""
+        if basis is None:
+            return False
+        if basis != "spin":
+            raise ValueError("%s: unsupported basis %r (None for the engine's own, or \"spin\")" % (who, basis))
+        if not self._is_heis():
+            raise _capi.LppError(_capi.LPP_ERR_INVALID, "%s: basis=\"spin\" is for engines set up by assemble_heisenberg" % who)
+        return True
+
+    def _obs_sector(self, m, spin):
+        """(count, count) as the entry points take them: (nup, ndown), in the digit basis (twiceS, szPlusConst)"""
+        return (m["twiceS"], m["nup"]) if spin else (m["nup"], m["ndown"])
 
     def keep_states_tj(self, k=1):
         """keep_states that also accepts a hole-major t-J engine (lpp_engine_keep_states_tj): state(k) is then the host Ritz vector bit for bit"""
@@ -368,18 +383,23 @@ class LanczosEngine:
         check(self._lib.lpp_engine_state_to_host(self._h, int(k), _vp(out)))
         return out
 
-    def apply_operator(self, op, site, spin, L, nup, ndown, src, factor=1.0, out=None, basis="hubbard"):
+    def apply_operator(self, op, site, spin, L, nup, ndown, src, factor=1.0, out=None, basis="hubbard", twiceS=None):
         """Engine::accModifiedState_ (Engine.h:416-458) on the GPU: returns (z, (nup', ndown')) with z[bra] += factor*sign*value*src[ket],
         z starting from `out` (new sector's length) or from zero; (None, None) where the operator leads to no sector.  src: host vector of the
         (nup, ndown) sector in the basis order.  basis: "hubbard" (BasisHubbardLanczos), "tj" (BasisTjMultiOrbLanczos, one orbital) or "spin_half"
         (BasisHeisenberg with twiceS = 1: nup = szPlusConst, ndown is not read; sz is the reference's raw 1 - 2 bit = -2 S^z, and where the reference
-        throws -- c, cdagger, S+ on all ups, S- on all downs -- LppError is raised)."""
+        throws -- c, cdagger, S+ on all ups, S- on all downs -- LppError is raised) or "spin" with twiceS=...: the digit basis of any spin
+        assemble_heisenberg admits (operator_plan_heis_spin has the definition: nup = szPlusConst, ndown is not read, sz is the true S^z, n / c /
+        cdagger and S+ on the top sector / S- on szPlusConst = 0 raise LppError)."""
         oid = _op_id(op)
         tj = _obs_basis(basis)
         src = np.ascontiguousarray(src, self.np_dtype)
         has, n1, n2 = C.c_int32(), C.c_int32(), C.c_int32()
         nu, nd = C.c_int64(1), C.c_int64()
-        if basis == "spin_half":
+        c1, c2 = _obs_counts(basis, nup, ndown, twiceS)
+        if basis == "spin":
+            check(self._lib.lpp_obs_plan_heis_spin(oid, site, spin, L, c1, c2, C.byref(has), C.byref(n1), C.byref(nd), None, None, None))
+        elif basis == "spin_half":
             check(self._lib.lpp_obs_plan_heis(oid, site, spin, L, nup, ndown, C.byref(has), C.byref(n1), C.byref(n2), C.byref(nd), None, None))
         elif tj:
             check(self._lib.lpp_obs_plan_tj(oid, site, spin, L, nup, ndown, C.byref(has), C.byref(n1), C.byref(n2), C.byref(nd), None))
@@ -387,7 +407,7 @@ class LanczosEngine:
             check(self._lib.lpp_obs_plan(oid, site, spin, L, nup, ndown, C.byref(has), C.byref(n1), C.byref(n2), C.byref(nu), C.byref(nd), None, None))
         if not has.value:
             return None, None
-        if len(src) != sector_size(L, nup, ndown, basis):
+        if len(src) != sector_size(L, nup, ndown, basis, twiceS):
             raise ValueError("src does not have the length of sector (%d, %d)" % (nup, ndown))
         n = nu.value * nd.value
         if out is None:
@@ -398,36 +418,38 @@ class LanczosEngine:
                 raise ValueError("out does not have the length of sector (%d, %d)" % (n1.value, n2.value))
         f = complex(factor)
         call = getattr(self._lib, "lpp_engine_apply_operator" + _OBS_SUFFIX[basis] + "_host")
-        check(call(self._h, oid, site, spin, L, nup, ndown, f.real, f.imag, _vp(src), _vp(z), int(out is not None), C.byref(has)))
+        check(call(self._h, oid, site, spin, L, c1, c2, f.real, f.imag, _vp(src), _vp(z), int(out is not None), C.byref(has)))
         return z, (n1.value, n2.value)
 
-    def bench_operator(self, op, site, spin, L, nup, ndown, warmup=2, iters=10, basis="hubbard"):
+    def bench_operator(self, op, site, spin, L, nup, ndown, warmup=2, iters=10, basis="hubbard", twiceS=None):
         """(ms per launch, bytes of the byte model) of the operator kernel on resident vectors"""
         ms, by = C.c_double(), C.c_double()
         _obs_basis(basis)
+        c1, c2 = _obs_counts(basis, nup, ndown, twiceS)
         call = getattr(self._lib, "lpp_engine_bench_operator" + _OBS_SUFFIX[basis])
-        check(call(self._h, _op_id(op), site, spin, L, nup, ndown, warmup, iters, C.byref(ms), C.byref(by)))
+        check(call(self._h, _op_id(op), site, spin, L, c1, c2, warmup, iters, C.byref(ms), C.byref(by)))
         return ms.value, by.value
 
     # ---- site-weighted operator sums: |phi> = sum_r f_r A_r |src>, the modified state of A(k,w), N(q,w), S(q,w) ----
-    def apply_operator_sum(self, op, spin, weights, L, nup, ndown, src, out=None, basis="hubbard"):
+    def apply_operator_sum(self, op, spin, weights, L, nup, ndown, src, out=None, basis="hubbard", twiceS=None):
         """z (+)= sum_r weights[r] * A_r src on the GPU (lpp_engine_apply_operator_sum): returns (z, (nup', ndown')), z starting from `out` or from zero;
         (None, None) where the operator leads to no sector.  A_r is what two_point applies: c, cdagger, n of `spin`, splus, sminus as apply_operator;
         sz = n_up/2 - n_down/2 in the "hubbard" and "tj" bases, the raw 1 - 2 bit in "spin_half".  Hubbard c, cdagger, n, sz and the "spin_half" sz are ONE launch; the "tj"
         basis, splus / sminus and the "spin_half" n chain the one-site launches over the sites whose weight is not exactly 0 (as everything does under
-        LPP_OBS_SUM_CHAIN=1).  Complex weights need a c128 engine."""
+        LPP_OBS_SUM_CHAIN=1), and so does everything in the "spin" basis (twiceS=...: sz is the true S^z).  Complex weights need a c128 engine."""
         oid = _op_id(op)
         _obs_basis(basis)
+        c1, c2 = _obs_counts(basis, nup, ndown, twiceS)
         w = np.asarray(weights, np.complex128).ravel()
         wr, wi = np.ascontiguousarray(w.real), np.ascontiguousarray(w.imag)
         src = np.ascontiguousarray(src, self.np_dtype)
         has, n = C.c_int32(), C.c_int64()
         call = getattr(self._lib, "lpp_engine_apply_operator_sum" + _OBS_SUFFIX[basis] + "_host")
-        head = (self._h, oid, int(spin), int(L), int(nup), int(ndown), len(w), _vp(wr), _vp(wi))
+        head = (self._h, oid, int(spin), int(L), c1, c2, len(w), _vp(wr), _vp(wi))
         check(call(*head, None, None, 0, C.byref(has), C.byref(n)))
         if not has.value:
             return None, None
-        if len(src) != sector_size(L, nup, ndown, basis):
+        if len(src) != sector_size(L, nup, ndown, basis, twiceS):
             raise ValueError("src does not have the length of sector (%d, %d)" % (nup, ndown))
         if out is None:
             z = np.zeros(n.value, self.np_dtype)
@@ -436,31 +458,35 @@ class LanczosEngine:
             if len(z) != n.value:
                 raise ValueError("out does not have the length of the operator's sector")
         check(call(*head, _vp(src), _vp(z), int(out is not None), C.byref(has), C.byref(n)))
-        if basis == "spin_half":
-            return z, (new_parts(op, spin, L, nup, 0, basis) if op in ("splus", "sminus") else (nup, 0))
+        if basis in ("spin_half", "spin"):
+            return z, (new_parts(op, spin, L, nup, 0, basis, twiceS) if op in ("splus", "sminus") else (nup, 0))
         return z, (new_parts(op, spin, L, nup, ndown, basis) if op in ("c", "cdagger", "splus", "sminus") else (nup, ndown))
 
-    def bench_operator_sum(self, op, spin, weights, L, nup, ndown, warmup=2, iters=10, accumulate=False, basis="hubbard"):
+    def bench_operator_sum(self, op, spin, weights, L, nup, ndown, warmup=2, iters=10, accumulate=False, basis="hubbard", twiceS=None):
         """(ms per sum, bytes of the byte model: destination written -- and read when accumulating -- plus every source element once) on zeroed vectors"""
         _obs_basis(basis)
         w = np.asarray(weights, np.complex128).ravel()
         wr, wi = np.ascontiguousarray(w.real), np.ascontiguousarray(w.imag)
         ms, by = C.c_double(), C.c_double()
+        c1, c2 = _obs_counts(basis, nup, ndown, twiceS)
         call = getattr(self._lib, "lpp_engine_bench_operator_sum" + _OBS_SUFFIX[basis])
-        check(call(self._h, _op_id(op), int(spin), int(L), int(nup), int(ndown), len(w), _vp(wr), _vp(wi), int(bool(accumulate)), warmup, iters, C.byref(ms), C.byref(by)))
+        check(call(self._h, _op_id(op), int(spin), int(L), c1, c2, len(w), _vp(wr), _vp(wi), int(bool(accumulate)), warmup, iters, C.byref(ms), C.byref(by)))
         return ms.value, by.value
 
-    def weighted_norm2(self, op, weights, spin=0, state=0):
+    def weighted_norm2(self, op, weights, spin=0, state=0, basis=None):
         """<phi|phi> of |phi> = sum_r weights[r] * A_r |resident state> (lpp_engine_sum_norm2): the static structure factor at the momentum the weights
         encode; 0.0 where the operator leads to no sector.  No sector engine is needed.  On an f64 engine complex weights are split as in
-        spectral_function_weighted: <phi|phi> = <C|C> + <S|S>."""
+        spectral_function_weighted: <phi|phi> = <C|C> + <S|S>.  basis="spin": as two_point."""
         m = self._need_model("weighted_norm2")
-        self._is_heis("weighted_norm2")
-        call = self._obs_call("lpp_engine_sum_norm2")
+        sb = self._spin_basis("weighted_norm2", basis)
+        if not sb:
+            self._is_heis("weighted_norm2")
+        call = self._obs_call("lpp_engine_sum_norm2", sb)
+        c1, c2 = self._obs_sector(m, sb)
         total = 0.0
         for _, wr, wi in self._weight_parts(weights, m["L"]):
             v, has = C.c_double(), C.c_int32()
-            check(call(self._h, int(state), _op_id(op), int(spin), m["L"], m["nup"], m["ndown"], len(wr), _vp(wr), _vp(wi), C.byref(v), C.byref(has)))
+            check(call(self._h, int(state), _op_id(op), int(spin), m["L"], c1, c2, len(wr), _vp(wr), _vp(wi), C.byref(v), C.byref(has)))
             total += v.value
         return total
 
@@ -476,7 +502,7 @@ class LanczosEngine:
         zero = np.zeros(L)
         return [(p, x, zero) for p, x in (("re", wr), ("im", wi)) if np.any(x)]
 
-    def spectral_function_weighted(self, op, weights, spin=0, state=0, energy=None, max_steps=200, min_steps=4, eps=1e-12, reortho=False):
+    def spectral_function_weighted(self, op, weights, spin=0, state=0, energy=None, max_steps=200, min_steps=4, eps=1e-12, reortho=False, basis=None):
         """The continued fractions of <phi| (z -+ (H - Eg))^-1 |phi> with |phi> = sum_r weights[r] * A_r |gs> built in one pass: the momentum-resolved
         A(k,w) (op "c" / "cdagger"), N(q,w) ("n"), S^zz(q,w) ("sz") and S(q,w) of the Heisenberg chain.  This is the project's own definition (the
         reference accumulates such a sum with a phase that does not depend on the site).  Records follow spectral_function's diagonal types: type 0 is
@@ -487,10 +513,14 @@ class LanczosEngine:
         On an f64 engine complex weights are split: |phi> = C + i S with C = sum Re(f_r) A_r gs and S = sum Im(f_r) A_r gs; H is real symmetric and gs
         real, so <phi|G(z)|phi> = G_CC + G_SS, and a type gives one record per non-zero part, marked part="re" / "im".  The spectral function of a type
         is the SUM of its records' continued_fraction.  On a c128 engine, or for real weights, a type is one record with part=None.  A state of
-        zero norm (sz at q = 0 in a sector with N_up = N_down) gives a record with weight 0 and no steps; continued_fraction returns 0 for it."""
+        zero norm (sz at q = 0 in a sector with N_up = N_down) gives a record with weight 0 and no steps; continued_fraction returns 0 for it.
+        basis="spin": as two_point; sz is then the true S^z, so S^zz(q,w) comes without the factor 1/4 of the S = 1/2 family's raw sz."""
         m = self._need_model("spectral_function_weighted")
-        self._is_heis("spectral_function_weighted")
+        sb = self._spin_basis("spectral_function_weighted", basis)
+        if not sb:
+            self._is_heis("spectral_function_weighted")
         L, nup, ndown = m["L"], m["nup"], m["ndown"]
+        k1, k2 = self._obs_sector(m, sb)
         _op_id(op)
         if energy is None:
             if self._energies is None:
@@ -499,8 +529,8 @@ class LanczosEngine:
         if self._is_tj() and op in ("splus", "sminus") and spin != _capi.LPP_SPIN_UP:  # before any sector engine is assembled
             raise _capi.LppError(_capi.LPP_ERR_INVALID, "spectral_function_weighted: splus / sminus of the t-J basis take spin UP")
         w = np.asarray(weights, np.complex128).ravel()
-        parts_call = self._obs_call("lpp_obs_new_parts")
-        decomp_call = self._obs_call("lpp_engine_spectral_decomposition_sum")
+        parts_call = self._obs_call("lpp_obs_new_parts", sb)
+        decomp_call = self._obs_call("lpp_engine_spectral_decomposition_sum", sb)
         solver = dict(max_steps=max_steps, min_steps=min_steps, eps=eps, reortho=reortho, save_vectors=0)
         records = []
         for typ in (0, 1):
@@ -508,7 +538,7 @@ class LanczosEngine:
             oid = OPERATORS[o]
             has, c1, c2 = C.c_int32(1), C.c_int32(nup), C.c_int32(ndown)
             if o not in ("n", "sz"):  # (those stay in the sector, which gets an engine of its own: self keeps its solver parameters)
-                check(parts_call(oid, spin, L, nup, ndown, C.byref(has), C.byref(c1), C.byref(c2)))
+                check(parts_call(oid, spin, L, k1, k2, C.byref(has), C.byref(c1), C.byref(c2)))
             if not has.value:
                 continue
             n1, n2 = c1.value, c2.value
@@ -519,7 +549,7 @@ class LanczosEngine:
                 a = np.zeros(max_steps + 2)
                 b = np.zeros(max_steps + 2)
                 n, wt, st = C.c_int32(), C.c_double(), Stats()
-                check(decomp_call(self._h, int(state), eng._h, oid, int(spin), L, nup, ndown, L, _vp(wr), _vp(wi), C.byref(wt), C.byref(n), _vp(a), _vp(b), C.byref(st)))
+                check(decomp_call(self._h, int(state), eng._h, oid, int(spin), L, k1, k2, L, _vp(wr), _vp(wi), C.byref(wt), C.byref(n), _vp(a), _vp(b), C.byref(st)))
                 records.append(dict(type=typ, part=part, label="%d,%d,0,0" % (spin, typ) + ("," + part if part else ""), a=a[:n.value].copy(), b=b[:n.value].copy(), Eg=energy,
                                     weight=wt.value * s2, sigma=float(-s), modif_norm2=wt.value, steps=n.value, sector=(n1, n2),
                                     ms_per_step=1e3 * st.seconds_total / max(st.steps_enqueued, 1), assemblies=self.sector_assemblies))
@@ -701,16 +731,21 @@ class LanczosEngine:
             raise _capi.LppError(_capi.LPP_ERR_STATE, "%s needs a single-GPU engine set up by assemble_hubbard / setup_hubbard_onthefly / assemble_tj / assemble_heisenberg" % who)
         return self._model
 
-    def two_point(self, op, spins=(0, 0), bra=0, ket=0):
+    def two_point(self, op, spins=(0, 0), bra=0, ket=0, basis=None):
         """Engine::twoPoint (Engine.h:266-338): (L x L matrix, trace) with result[i, j] = (A_j^{spins[1]} bra) . (A_i^{spins[0]} ket) for resident
-        states bra / ket (keep_states before lanczos); -100 everywhere where the operator leads to no sector."""
+        states bra / ket (keep_states before lanczos); -100 everywhere where the operator leads to no sector.
+        basis="spin", on an engine set up by assemble_heisenberg with any admitted twiceS: the opt-in digit basis (operator_plan_heis_spin has the
+        definition, the project's own: the reference throws for spins above 1/2), <S^z_j S^z_i> for "sz" and <S^-_j S^+_i> for "splus"."""
         m = self._need_model("two_point")
-        self._is_heis("two_point")
+        sb = self._spin_basis("two_point", basis)
+        if not sb:
+            self._is_heis("two_point")
         L = m["L"]
         res = np.zeros((L, L), self.np_dtype)
         tr = np.zeros(1, self.np_dtype)
-        call = self._obs_call("lpp_engine_two_point")
-        check(call(self._h, _op_id(op), int(spins[0]), int(spins[1]), L, m["nup"], m["ndown"], int(bra), int(ket), _vp(res), _vp(tr)))
+        call = self._obs_call("lpp_engine_two_point", sb)
+        c1, c2 = self._obs_sector(m, sb)
+        check(call(self._h, _op_id(op), int(spins[0]), int(spins[1]), L, c1, c2, int(bra), int(ket), _vp(res), _vp(tr)))
         return res, tr[0]
 
     def _sector_engine(self, nup, ndown, solver):
@@ -721,7 +756,7 @@ class LanczosEngine:
             if self._is_tj():
                 eng.assemble_tj(m["L"], nup, ndown, m["hop"], m["jpm"], m["jzz"], m["w"], m["potentialV"])
             elif self._is_heis():
-                eng.assemble_heisenberg(m["L"], nup, m["jpm"], m["jzz"], field=m["field"], twiceS=1, anisotropy=m["anisotropy"])
+                eng.assemble_heisenberg(m["L"], nup, m["jpm"], m["jzz"], field=m["field"], twiceS=m["twiceS"], anisotropy=m["anisotropy"])
             else:
                 getattr(eng, m["how"])(m["L"], nup, ndown, m["hop"], m["U"], m["V"], ninj=m["ninj"], jcoup=m["jcoup"])
             self._sectors[(nup, ndown)] = eng
@@ -729,15 +764,19 @@ class LanczosEngine:
         eng.set_solver(**solver)
         return eng
 
-    def spectral_function(self, op, isite, jsite, spin=0, state=0, energy=None, max_steps=200, min_steps=4, eps=1e-12, reortho=False):
+    def spectral_function(self, op, isite, jsite, spin=0, state=0, energy=None, max_steps=200, min_steps=4, eps=1e-12, reortho=False, basis=None):
         """Engine::spectralFunction (Engine.h:134-206) for one (operator, site pair, spin): a list of records, one per type 0..3 (odd types: the
         operator, even types: its transpose-conjugate; a diagonal pair skips types 2 and 3; a type whose sector does not exist is skipped).
         A record is the argument list of cf.set (:489): a, b, Eg, weight (= <modif|modif> * s2), sigma (= -s), plus type, label, steps,
         ms_per_step and `assemblies` = sector Hamiltonians assembled by this engine so far (the N+-1 engines are kept, keyed by (nup, ndown)).
-        max_steps .. reortho: ParametersForSolver(io, "Spectral").  energy: Eg, default the lowest eigenvalue of the last lanczos()."""
+        max_steps .. reortho: ParametersForSolver(io, "Spectral").  energy: Eg, default the lowest eigenvalue of the last lanczos().
+        basis="spin": as two_point; the sector engines are assembled with the model's twiceS and anisotropy on szPlusConst +- 1 (sz: the state's own
+        sector, on a sector engine of its own)."""
         m = self._need_model("spectral_function")
-        heis = self._is_heis("spectral_function")
+        sb = self._spin_basis("spectral_function", basis)
+        heis = sb or self._is_heis("spectral_function")
         L, nup, ndown = m["L"], m["nup"], m["ndown"]
+        k1, k2 = self._obs_sector(m, sb)
         _op_id(op)
         if op in ("n", "sz") and not heis:  # before any sector engine is assembled (Heisenberg: needsNewBasis() is false, the new basis is the model's own)
             raise _capi.LppError(_capi.LPP_ERR_INVALID, "spectral_function: operators that stay in the sector (n, sz) are not supported")
@@ -748,8 +787,8 @@ class LanczosEngine:
         op2 = _TRANSPOSE_CONJUGATE[op]
         diagonal = isite == jsite
         tj = self._is_tj()
-        parts_call = self._obs_call("lpp_obs_new_parts")
-        decomp_call = self._obs_call("lpp_engine_spectral_decomposition")
+        parts_call = self._obs_call("lpp_obs_new_parts", sb)
+        decomp_call = self._obs_call("lpp_engine_spectral_decomposition", sb)
         if tj and op in ("splus", "sminus") and spin != _capi.LPP_SPIN_UP:  # before any sector engine is assembled
             raise _capi.LppError(_capi.LPP_ERR_INVALID, "spectral_function: splus / sminus of the t-J basis take spin UP (the reference ranks words outside the basis otherwise)")
         solver = dict(max_steps=max_steps, min_steps=min_steps, eps=eps, reortho=reortho, save_vectors=0)
@@ -761,7 +800,7 @@ class LanczosEngine:
             oid = OPERATORS[o]
             has, c1, c2 = C.c_int32(1), C.c_int32(nup), C.c_int32(ndown)
             if not (heis and o in ("n", "sz")):  # (those stay in the sector, which gets an engine of its own: self keeps its solver parameters)
-                check(parts_call(oid, spin, L, nup, ndown, C.byref(has), C.byref(c1), C.byref(c2)))
+                check(parts_call(oid, spin, L, k1, k2, C.byref(has), C.byref(c1), C.byref(c2)))
             if not has.value:
                 continue
             n1, n2 = c1.value, c2.value
@@ -770,7 +809,7 @@ class LanczosEngine:
             b = np.zeros(max_steps + 2)
             n, w, st = C.c_int32(), C.c_double(), Stats()
             isign = -1.0 if typ > 1 else 1.0
-            check(decomp_call(self._h, int(state), eng._h, oid, isite, jsite, spin, isign, L, nup, ndown, C.byref(w), C.byref(n), _vp(a), _vp(b), C.byref(st)))
+            check(decomp_call(self._h, int(state), eng._h, oid, isite, jsite, spin, isign, L, k1, k2, C.byref(w), C.byref(n), _vp(a), _vp(b), C.byref(st)))
             s = -1 if (typ & 1) else 1  # calcSpectral, Engine.h:481-489
             s2 = -1.0 if typ > 1 else 1.0
             if o not in _FERMIONIC:
@@ -847,8 +886,8 @@ def _rdm_dense(blocks, plan, dtype):
     return out
 
 
-OBS_BASES = ("hubbard", "tj", "spin_half")
-_OBS_SUFFIX = {"hubbard": "", "tj": "_tj", "spin_half": "_heis"}  # of the C entry points
+OBS_BASES = ("hubbard", "tj", "spin_half", "spin")
+_OBS_SUFFIX = {"hubbard": "", "tj": "_tj", "spin_half": "_heis", "spin": "_heis_spin"}  # of the C entry points
 
 
 def _obs_basis(basis):
@@ -858,23 +897,41 @@ def _obs_basis(basis):
     return basis == "tj"
 
 
-def sector_size(L, nup, ndown, basis="hubbard"):
+def _obs_counts(basis, nup, ndown, twiceS):
+    """the two counts as the entry points of the basis take them: (nup, ndown); basis="spin": (twiceS, szPlusConst = nup), and twiceS is required"""
+    if basis != "spin":
+        return int(nup), int(ndown)
+    if twiceS is None:
+        raise ValueError("basis=\"spin\" needs twiceS")
+    return int(twiceS), int(nup)
+
+
+def sector_size(L, nup, ndown, basis="hubbard", twiceS=None):
+    """states of the sector; basis="spin" (twiceS=...): the words of L digits 0 .. twiceS whose digits add up to nup = szPlusConst"""
     from math import comb
     if _obs_basis(basis):
         return comb(L, ndown) * comb(L - ndown, nup) if nup + ndown <= L else 0
+    if basis == "spin":
+        t, m = _obs_counts(basis, nup, ndown, twiceS)
+        count = [1] + [0] * (L * t)  # strings of no digit
+        for _ in range(L):
+            count = [sum(count[max(0, s - t):s + 1]) for s in range(L * t + 1)]
+        return count[m] if 0 <= m <= L * t else 0
     if basis == "spin_half":
         return comb(L, nup)
     return comb(L, nup) * comb(L, ndown)
 
 
-def new_parts(op, spin, L, nup, ndown, basis="hubbard"):
+def new_parts(op, spin, L, nup, ndown, basis="hubbard", twiceS=None):
     """HubbardOneOrbital::hasNewParts (basis="tj": TjMultiOrb::hasNewParts, basis="spin_half": Heisenberg::hasNewParts with nup = szPlusConst, the new
     sector as (szPlusConst', 0)): the new (nup, ndown), or None where the reference returns false (LPP_ERR_INVALID where it throws: n, for the t-J model
-    sz, for the Heisenberg model c, cdagger, S+ on all ups and S- on all downs)."""
+    sz, for the Heisenberg model c, cdagger, S+ on all ups and S- on all downs).  basis="spin" with twiceS=...: the digit basis of any admitted spin,
+    nup = szPlusConst, the new sector as (szPlusConst', 0); LPP_ERR_INVALID for n, c, cdagger, S+ on the top sector and S- on szPlusConst = 0."""
     has, n1, n2 = C.c_int32(), C.c_int32(), C.c_int32()
     _obs_basis(basis)
+    c1, c2 = _obs_counts(basis, nup, ndown, twiceS)
     call = getattr(_capi.lib(), "lpp_obs_new_parts" + _OBS_SUFFIX[basis])
-    check(call(_op_id(op), spin, L, nup, ndown, C.byref(has), C.byref(n1), C.byref(n2)))
+    check(call(_op_id(op), spin, L, c1, c2, C.byref(has), C.byref(n1), C.byref(n2)))
     return (n1.value, n2.value) if has.value else None
 
 
@@ -903,6 +960,24 @@ def operator_plan_heis(op, site, spin, L, szPlusConst):
     action = np.zeros(n.value, np.int64)
     check(lib.lpp_obs_plan_heis(oid, site, spin, L, szPlusConst, 0, C.byref(has), C.byref(n1), C.byref(n2), C.byref(n), C.byref(lb), _vp(action)))
     return dict(nup=n1.value, ndown=n2.value, action=action, lb=lb.value)
+
+
+def operator_plan_heis_spin(op, site, L, twiceS, szPlusConst):
+    """The expanded plan of one operator application in the digit basis of a spin-S Heisenberg model (lpp_obs_plan_heis_spin; the project's own
+    definition, the reference throws for spins above 1/2).  Words of L digits of `bits` bits, site p at bit offset p * bits, digit d = m + S in
+    [0, twiceS], digit sum szPlusConst, ascending.  With m = d - S of the source: splus d -> d + 1 with value sqrt(S(S+1) - m(m+1)), sminus d -> d - 1
+    with sqrt(S(S+1) - m(m-1)), sz keeps the index with value m (a value of 0 leaves the destination untouched).  Returns a dict with the new sector
+    (nup = szPlusConst', ndown = 0), action[dst] = src + 1 or 0, coef[dst] = the value, both expanded on the host through the run table and the lookup
+    function the kernel uses, and lb: the cut of the word in digits.  Raises for n, c, cdagger, S+ on the top sector, S- on szPlusConst = 0 and for
+    spins the assembler refuses."""
+    lib = _capi.lib()
+    oid = _op_id(op)
+    has, m2, n, lb = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int32()
+    head = (oid, int(site), 0, int(L), int(twiceS), int(szPlusConst), C.byref(has), C.byref(m2), C.byref(n), C.byref(lb))
+    check(lib.lpp_obs_plan_heis_spin(*head, None, None))
+    action, coef = np.zeros(n.value, np.int64), np.zeros(n.value)
+    check(lib.lpp_obs_plan_heis_spin(*head, _vp(action), _vp(coef)))
+    return dict(nup=m2.value, ndown=0, action=action, coef=coef, lb=lb.value)
 
 
 def operator_plan(op, site, spin, L, nup, ndown):

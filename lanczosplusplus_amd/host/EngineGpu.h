@@ -512,7 +512,7 @@ public:
 		std::vector<ComplexOrRealType> flat(total * total);
 		ComplexOrRealType sum = 0;
 		std::cout << "orbs=" << orbs.first << " " << orbs.second << "\n";
-		lppCheck((heisModel() ? lpp_engine_two_point_heis : tjModel() ? lpp_engine_two_point_tj : lpp_engine_two_point)(e, lOperator.id(), (int32_t)spins.first, (int32_t)spins.second, (int32_t)total, (int32_t)parts.first, (int32_t)parts.second,
+		lppCheck((heisSpinModel() ? lpp_engine_two_point_heis_spin : heisModel() ? lpp_engine_two_point_heis : tjModel() ? lpp_engine_two_point_tj : lpp_engine_two_point)(e, lOperator.id(), (int32_t)spins.first, (int32_t)spins.second, (int32_t)total, (int32_t)parts.first, (int32_t)parts.second,
 		                                                                      (int32_t)braAndKet.first, (int32_t)braAndKet.second, flat.data(), &sum));
 		for (SizeType i = 0; i < total; i++)
 			for (SizeType j = 0; j < total; j++) result(i, j) = flat[i * total + j];
@@ -620,7 +620,7 @@ public:
 		lpp_engine* e = observableEngine("spectralFunction");
 		const LabeledOperatorType lOperator2 = lOperator1.transposeConjugate();
 		// refused before any sector engine is assembled; the Heisenberg model decomposes them in its own sector (needsNewBasis() is false, Engine.h:172-174)
-		if (!lOperator1.needsNewBasis() && !heisModel()) throw std::runtime_error("spectralFunction: operators that stay in the sector (n, sz) are not supported\n");
+		if (!lOperator1.needsNewBasis() && !heisModel() && !heisSpinModel()) throw std::runtime_error("spectralFunction: operators that stay in the sector (n, sz) are not supported\n");
 		const int n = (int)model_.geometry().numberOfSites();
 		if (isite < 0 || jsite < 0 || isite >= n || jsite >= n) throw std::runtime_error("spectralFunction: site out of range\n");
 		const bool isDiagonal = (isite == jsite);
@@ -629,9 +629,9 @@ public:
 		for (SizeType type = 0; type < lOperator1.numberOfTypes(); ++type) {
 			if (isDiagonal && type > 1) continue;
 			const LabeledOperatorType& lOperator = (type & 1) ? lOperator1 : lOperator2;
-			int32_t has = 1, nup2 = (int32_t)oldParts.first, ndown2 = (int32_t)oldParts.second;
+			int32_t has = 1, nup2 = (int32_t)ownSector().first, ndown2 = (int32_t)ownSector().second;
 			if (lOperator.needsNewBasis())
-				lppCheck((heisModel() ? lpp_obs_new_parts_heis : tjModel() ? lpp_obs_new_parts_tj : lpp_obs_new_parts)(lOperator.id(), (int32_t)spins.first, n, (int32_t)oldParts.first,
+				lppCheck((heisSpinModel() ? lpp_obs_new_parts_heis_spin : heisModel() ? lpp_obs_new_parts_heis : tjModel() ? lpp_obs_new_parts_tj : lpp_obs_new_parts)(lOperator.id(), (int32_t)spins.first, n, (int32_t)oldParts.first,
 				                                                                                                      (int32_t)oldParts.second, &has, &nup2, &ndown2));
 			if (!has) continue;
 			lpp_engine* sector = sectorEngine(nup2, ndown2, params);
@@ -639,7 +639,7 @@ public:
 			ab.resize(params.steps + 2);
 			double weight = 0;
 			int32_t nsteps = 0;
-			lppCheck((heisModel() ? lpp_engine_spectral_decomposition_heis : tjModel() ? lpp_engine_spectral_decomposition_tj : lpp_engine_spectral_decomposition)(e, 0, sector, lOperator.id(), isite, jsite, (int32_t)spins.first,
+			lppCheck((heisSpinModel() ? lpp_engine_spectral_decomposition_heis_spin : heisModel() ? lpp_engine_spectral_decomposition_heis : tjModel() ? lpp_engine_spectral_decomposition_tj : lpp_engine_spectral_decomposition)(e, 0, sector, lOperator.id(), isite, jsite, (int32_t)spins.first,
 			                                                                                                type > 1 ? -1.0 : 1.0, n, (int32_t)oldParts.first, (int32_t)oldParts.second,
 			                                                                                                &weight, &nsteps, &ab.a(0), &ab.b(0), nullptr));
 			ab.a_.resize(nsteps);
@@ -679,9 +679,9 @@ public:
 			const int32_t spin = (int32_t)spins[si].first;
 			for (SizeType type = 0; type < 2; ++type) {
 				const LabeledOperatorType& lOperator = (type & 1) ? lOperator1 : lOperator2;
-				int32_t has = 1, nup2 = (int32_t)oldParts.first, ndown2 = (int32_t)oldParts.second;
+				int32_t has = 1, nup2 = (int32_t)ownSector().first, ndown2 = (int32_t)ownSector().second;
 				if (lOperator.needsNewBasis())
-					lppCheck((heisModel() ? lpp_obs_new_parts_heis : tjModel() ? lpp_obs_new_parts_tj : lpp_obs_new_parts)(lOperator.id(), spin, n, (int32_t)oldParts.first,
+					lppCheck((heisSpinModel() ? lpp_obs_new_parts_heis_spin : heisModel() ? lpp_obs_new_parts_heis : tjModel() ? lpp_obs_new_parts_tj : lpp_obs_new_parts)(lOperator.id(), spin, n, (int32_t)oldParts.first,
 					                                                                                                      (int32_t)oldParts.second, &has, &nup2, &ndown2));
 				if (!has) continue;
 				std::vector<double> wr((size_t)n), wi((size_t)n);
@@ -700,7 +700,7 @@ public:
 					ab.resize(params.steps + 2);
 					double weight = 0;
 					int32_t nsteps = 0;
-					lppCheck((heisModel() ? lpp_engine_spectral_decomposition_sum_heis : tjModel() ? lpp_engine_spectral_decomposition_sum_tj : lpp_engine_spectral_decomposition_sum)(
+					lppCheck((heisSpinModel() ? lpp_engine_spectral_decomposition_sum_heis_spin : heisModel() ? lpp_engine_spectral_decomposition_sum_heis : tjModel() ? lpp_engine_spectral_decomposition_sum_tj : lpp_engine_spectral_decomposition_sum)(
 					    e, 0, sector, lOperator.id(), spin, n, (int32_t)oldParts.first, (int32_t)oldParts.second, n, pr.data(), pi.data(), &weight, &nsteps, &ab.a(0), &ab.b(0), nullptr));
 					ab.a_.resize(nsteps);
 					ab.b_.resize(nsteps);
@@ -766,8 +766,8 @@ private:
 	{
 		if (hubbardOnly && !hubbard())
 			throw std::runtime_error(std::string(who) + ": needs a Model of the HubbardOneOrbital family solved by the GPU Lanczos (no symmetry sectors, no dense fallback)\n");
-		if (!(hubbard() || tjModel() || heisModel()) || !hamiltonian_ || !statesResident_)
-			throw std::runtime_error(std::string(who) + ": needs a Model of the HubbardOneOrbital family, TjMultiOrb with Orbitals=1 or Heisenberg with HeisenbergTwiceS=1 and no AnisotropyD solved by the GPU Lanczos (no symmetry sectors, no dense fallback)\n");
+		if (!(hubbard() || tjModel() || heisModel() || heisSpinModel()) || !hamiltonian_ || !statesResident_)
+			throw std::runtime_error(std::string(who) + ": needs a Model of the HubbardOneOrbital family, TjMultiOrb with Orbitals=1 or Heisenberg with HeisenbergTwiceS=1 and no AnisotropyD (any spin and AnisotropyD with SolverOptions=...,HeisenbergSpinObservables) solved by the GPU Lanczos (no symmetry sectors, no dense fallback)\n");
 		return hamiltonian_->engine();
 	}
 
@@ -780,17 +780,20 @@ private:
 		if (tjModel() && !(manyPointOk && tjStrings()))
 			throw std::runtime_error(std::string("LPP_ERR_INVALID: ") + who + ": not for the TjMultiOrb model, operator strings are built for the Hubbard product basis"
 			                         + (manyPointOk ? "; SolverOptions=...,TjOperatorStrings opts into strings of the t-J basis (sz is then n of the given spin)\n" : "\n"));
+		if (heisSpinModel())
+			throw std::runtime_error(std::string("LPP_ERR_INVALID: ") + who + ": operator strings are not built for the spin-S digit basis (HeisenbergSpinObservables)\n");
 		if (heisModel() && !manyPointOk)
 			throw std::runtime_error(std::string("LPP_ERR_INVALID: ") + who + ": not for the Heisenberg model, operator strings are built for the Hubbard product basis\n");
 		return e;
 	}
 
 	// the input's opt-in for operator strings of the t-J basis (the reference's InputCheck is permissive, so such an input stays valid for it)
-	bool tjStrings() const
+	bool tjStrings() const { return solverOption("TjOperatorStrings"); }
+	bool solverOption(const char* token) const
 	{
 		LppHost::String options("none");
 		if (io_.has("SolverOptions=")) io_.readline(options, "SolverOptions=");
-		return options.find("TjOperatorStrings") != LppHost::String::npos;
+		return options.find(token) != LppHost::String::npos;
 	}
 
 	ComplexOrRealType bracket(lpp_engine* e, int convention, const std::vector<int32_t>& ops, const std::vector<int32_t>& sites, const std::vector<int32_t>& spins,
@@ -822,14 +825,26 @@ private:
 	const Heisenberg<ComplexOrRealType>* heisModel() const
 	{
 		const Heisenberg<ComplexOrRealType>* hs = dynamic_cast<const Heisenberg<ComplexOrRealType>*>(&model_);
-		return (hs && hs->twiceTheSpin() == 1 && hs->anisotropy.empty()) ? hs : nullptr;
+		return (hs && hs->twiceTheSpin() == 1 && hs->anisotropy.empty() && !heisSpinModel()) ? hs : nullptr;
 	}
-	// the sector as the observable entry points take it: (nup, ndown), for the Heisenberg model (szPlusConst, 0) -- its parts() are (twiceS, szPlusConst)
+	// The input's opt-in for the observables of the spin-S digit basis, the SolverOptions token HeisenbergSpinObservables: a Model=Heisenberg input of
+	// any spin the assembler admits, AnisotropyD included, goes through the _heis_spin entry points (the project's own definition -- the reference throws
+	// for spins above 1/2 --, sz is the true S^z; the reference's InputCheck is permissive, so such an input stays valid for it).  Without the token
+	// every input behaves as before.
+	const Heisenberg<ComplexOrRealType>* heisSpinModel() const
+	{
+		const Heisenberg<ComplexOrRealType>* hs = dynamic_cast<const Heisenberg<ComplexOrRealType>*>(&model_);
+		return (hs && solverOption("HeisenbergSpinObservables")) ? hs : nullptr;
+	}
+	// the sector as the observable entry points take it: (nup, ndown), for the Heisenberg model (szPlusConst, 0) -- its parts() are (twiceS, szPlusConst),
+	// which is what the _heis_spin entry points take
 	PairType obsParts() const
 	{
 		const typename ModelType::BasisBaseType::PairIntType parts = model_.basis().parts();
 		return heisModel() ? PairType(parts.second, 0) : PairType(parts.first, parts.second);
 	}
+	// the key of the resident states' own sector among the sector engines: obsParts(), in the spin-S digit basis (szPlusConst, 0) as its new sectors
+	PairType ownSector() const { return heisSpinModel() ? PairType(model_.basis().parts().second, 0) : obsParts(); }
 
 	lpp_engine* sectorEngine(int nup, int ndown, const ParametersForSolverType& params) const
 	{
@@ -837,7 +852,8 @@ private:
 		if (!slot) {
 			const HubbardOneOrbital<ComplexOrRealType>* hub = hubbard();
 			const TjMultiOrb<ComplexOrRealType>* tj = tjModel();
-			const Heisenberg<ComplexOrRealType>* hs = heisModel();
+			const Heisenberg<ComplexOrRealType>* spinModel = heisSpinModel();
+			const Heisenberg<ComplexOrRealType>* hs = spinModel ? spinModel : heisModel();
 			const SizeType n = model_.geometry().numberOfSites();
 			std::vector<double> hr(n * n), hi(n * n);
 			for (SizeType k = 0; k < n * n && !hs; k++) {
@@ -849,7 +865,11 @@ private:
 			cfg.device = device_;
 			cfg.dtype = LppDtype<ComplexOrRealType>::value;
 			std::unique_ptr<EngineHandle> fresh(new EngineHandle(cfg));
-			if (hs) {
+			if (spinModel) { // the recorded model's twiceS and anisotropy on szPlusConst +- 1 (or the state's own sector for sz)
+				lppCheck(lpp_engine_assemble_heisenberg_spin(fresh->get(), (int32_t)n, (int32_t)hs->twiceTheSpin(), nup, hs->jpm().data(), hs->jzz().data(),
+				                                             hs->magneticField.empty() ? nullptr : hs->magneticField.data(), (int32_t)hs->magneticField.size(),
+				                                             hs->anisotropy.empty() ? nullptr : hs->anisotropy.data(), (int32_t)hs->anisotropy.size()));
+			} else if (hs) {
 				const double* field = hs->magneticField.empty() ? nullptr : hs->magneticField.data();
 				lppCheck(lpp_engine_assemble_heisenberg(fresh->get(), (int32_t)n, nup, hs->jpm().data(), hs->jzz().data(), field, (int32_t)hs->magneticField.size()));
 			} else if (hub) {
@@ -917,7 +937,7 @@ private:
 		SpecialSymmetryType& rs = *rs_;
 		InternalProductType& hamiltonian = *hamiltonian_;
 		LanczosSolverType lanczosSolver(hamiltonian, params); // pushes params into the engine
-		const bool keep = (hubbard() || tjModel() || heisModel()) && rs.sectors() == 1;
+		const bool keep = (hubbard() || tjModel() || heisModel() || heisSpinModel()) && rs.sectors() == 1;
 		// (a t-J matrix may be held in the hole-major form, which only the _tj call lets keep its states)
 		if (keep) lppCheck((tjModel() ? lpp_engine_keep_states_tj : lpp_engine_keep_states)(hamiltonian.engine(), (int32_t)nstates));
 		energies_.assign(nstates, 0);

@@ -19,9 +19,15 @@ profiles/observables_heis_L28.json / _L32.json), the operator kernel being k_obs
   hubbard_yardstick k_obs_apply's c up on config 2 (16 sites, 8 up 8 down) in the same process, and `bar`: every launch's share of the stream rate
                     against half of the share that yardstick gets
   unless --operators-only: two_point(sz), two_point(splus), the -g sz set of one centre site (L pairs) and the step times as above
+--model heisenberg --twice-s T --sites L --m M (T > 1): the spin-S chain in the opt-in digit basis (f64; committed for S = 1, (18;18), as
+profiles/observables_heis_spin1_L18.json), the operator kernel being k_obs_apply_heis_spin:
+  operator          splus and sz at site 0 and at site L-1, accumulating launches, and each one's ratio to the SAME-SITE launch of
+  spin_half_yardstick   k_obs_apply_heis at (28;14) in the same process (4.0e7 states), next to hubbard_yardstick and `bar` as above
+  unless --operators-only: the ring (J = 1, periodic): two_point("sz", basis="spin") and one S^zz(q = pi, w) decomposition (spectral_function_k)
 Usage: hipcc --offload-arch=gfx950 -O3 -o scripts/calib_stream scripts/calib_stream.hip
        python scripts/bench_observables.py [--model hubbard|tj] [--lx 4 --ly 4 --nup 8 --ndown 8] [--calib-stream scripts/calib_stream] [--spectral-steps 40]
-       python scripts/bench_observables.py --model heisenberg --sites 28 --m 14 [--operators-only] [--calib-stream scripts/calib_stream]"""
+       python scripts/bench_observables.py --model heisenberg --sites 28 --m 14 [--operators-only] [--calib-stream scripts/calib_stream]
+       python scripts/bench_observables.py --model heisenberg --twice-s 2 --sites 18 --m 18 --operators-only"""
 import argparse
 import json
 import os
@@ -127,6 +133,62 @@ def heisenberg(a, rate):
     print(json.dumps(out))
 
 
+SPIN_HALF_YARD = (28, 14)  # the S = 1/2 sector of --twice-s's yardstick: 4.0e7 states
+
+
+def heisenberg_spin(a, rate):
+    """--model heisenberg --twice-s T: one JSON line"""
+    L, m, t = a.sites, a.m, a.twice_s
+    out = dict(config="Heisenberg twiceS=%d chain L=%d szPlusConst=%d J=1 f64, digit basis" % (t, L, m),
+               stream_rate=dict(tool="scripts/calib_stream.hip", line=CALIB_LINE, kind="read, 16 bytes per lane, 4 GiB", gbs=rate) if rate else None)
+    with LanczosEngine(max_steps=a.gs_steps, save_vectors=0) as e:
+
+        def bench(op, site, sites, nup, ndown, basis, twiceS=None):
+            ms, by = e.bench_operator(op, site, 0, sites, nup, ndown, warmup=2, iters=10, basis=basis, twiceS=twiceS)
+            gbs = by / ms * 1e-6
+            return dict(ms=round(ms, 4), model_bytes=by, gbs=round(gbs, 1), ratio_to_stream=round(gbs / rate, 3) if rate else None)
+
+        ops, half = {}, {}
+        Lh, mh = SPIN_HALF_YARD
+        for name, op, last in (("splus_site0", "splus", False), ("splus_last_site", "splus", True), ("sz_site0", "sz", False), ("sz_last_site", "sz", True)):
+            ops[name] = bench(op, L - 1 if last else 0, L, m, 0, "spin", t)
+            half[name] = bench(op, Lh - 1 if last else 0, Lh, mh, 0, "spin_half")
+            ops[name]["ms_over_spin_half_same_site"] = round(ops[name]["ms"] / half[name]["ms"], 3)
+            ops[name]["gbs_over_spin_half_same_site"] = round(ops[name]["gbs"] / half[name]["gbs"], 3)
+        out["operator"] = ops
+        half["sector"] = list(SPIN_HALF_YARD)
+        out["spin_half_yardstick"] = half
+        yard = bench("c", 8, 16, 8, 8, "hubbard")
+        yard["sector"] = [16, 8, 8]
+        out["hubbard_yardstick_c_up"] = yard
+        worst = min(ops, key=lambda k: ops[k]["gbs"])
+        out["bar"] = dict(rule="every launch >= half of the Hubbard c up launch's share of the stream rate (same run)", worst=worst,
+                          worst_over_yardstick=round(ops[worst]["gbs"] / yard["gbs"], 3), met=bool(ops[worst]["gbs"] >= 0.5 * yard["gbs"]))
+        if a.operators_only:
+            print(json.dumps(out))
+            return
+        j = chain(L, 1.0)
+        j[0, L - 1] = j[L - 1, 0] = 1.0
+        t0 = time.time()
+        e.assemble_heisenberg(L, m, j, j, twiceS=t)
+        out["assemble_s"] = round(time.time() - t0, 3)
+        out["layout_kernel"] = e.layout()["kernel"]
+        out["states"] = e.rows()
+        e.keep_states(1)
+        t0 = time.time()
+        eg, _, st = e.lanczos(1, want_vectors=False)
+        out["ground_state"] = dict(E0=eg[0], steps=st["steps"], seconds=round(time.time() - t0, 3))
+        t0 = time.time()
+        res, tr = e.two_point("sz", basis="spin")
+        out["two_point_sz"] = dict(seconds=round(time.time() - t0, 3), trace=float(tr), nearest_neighbour=float(res[0, 1]))
+        t0 = time.time()
+        recs = e.spectral_function_k("sz", np.pi, np.arange(L), max_steps=a.spectral_steps, eps=0.0, basis="spin")
+        out["szz_q_pi"] = dict(seconds_both_types=round(time.time() - t0, 3), records=len(recs), steps=[r["steps"] for r in recs], assemblies=e.sector_assemblies,
+                               ms_per_step=[round(r["ms_per_step"], 4) for r in recs], static_structure_factor=float(recs[0]["modif_norm2"]),
+                               note="the first record includes the assembly of the sector engine")
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lx", type=int, default=4)
@@ -139,6 +201,7 @@ def main():
     ap.add_argument("--model", choices=("hubbard", "tj", "heisenberg"), default="hubbard")
     ap.add_argument("--sites", type=int, default=28, help="--model heisenberg: chain length")
     ap.add_argument("--m", type=int, default=14, help="--model heisenberg: szPlusConst")
+    ap.add_argument("--twice-s", type=int, default=1, help="--model heisenberg: twiceS; above 1 the opt-in digit basis (k_obs_apply_heis_spin) is measured")
     ap.add_argument("--operators-only", action="store_true", help="--model heisenberg: the operator launches and the yardstick only (no matrix)")
     a = ap.parse_args()
     L = a.lx * a.ly
@@ -146,7 +209,7 @@ def main():
     hop, U = square(a.lx, a.ly, -1.0), np.full(L, 4.0)
     rate = stream_rate(a.calib_stream) if a.calib_stream else 0.0
     if a.model == "heisenberg":
-        return heisenberg(a, rate)
+        return heisenberg_spin(a, rate) if a.twice_s > 1 else heisenberg(a, rate)
     out = dict(config=("t-J %dx%d %dup %ddown t=-1 J=0.4 W=-0.1 c128" if tj else "%dx%d %dup %ddown U=4") % (a.lx, a.ly, a.nup, a.ndown),
                stream_rate=dict(tool="scripts/calib_stream.hip", line=CALIB_LINE, kind="read, 16 bytes per lane, 4 GiB", gbs=rate) if rate else None)
     basis = "tj" if tj else "hubbard"
