@@ -123,45 +123,17 @@ SYMBOLS = {
                                          C.POINTER(C.c_int64), _P, _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32]),
     "lpp_pb_seg_plan_stats": (C.c_int32, [C.c_int64, _P, _P, _P, C.c_int32, _P, _P]),
     "lpp_tj_plan_stats": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_int32, _P]),
-    "lpp_obs_new_parts": (C.c_int32, [C.c_int32] * 5 + [C.POINTER(C.c_int32)] * 3),
     "lpp_obs_plan": (C.c_int32, [C.c_int32] * 6 + [C.POINTER(C.c_int32)] * 3 + [C.POINTER(C.c_int64)] * 2 + [_P, _P]),
-    "lpp_engine_apply_operator": (C.c_int32, [_P] + [C.c_int32] * 6 + [C.c_double, C.c_double, _P, _P, C.c_int32, C.POINTER(C.c_int32)]),
-    "lpp_engine_apply_operator_host": (C.c_int32, [_P] + [C.c_int32] * 6 + [C.c_double, C.c_double, _P, _P, C.c_int32, C.POINTER(C.c_int32)]),
-    "lpp_engine_bench_operator": (C.c_int32, [_P] + [C.c_int32] * 8 + [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "lpp_engine_keep_states": (C.c_int32, [_P, C.c_int32]),
     "lpp_engine_state_device": (C.c_int32, [_P, C.c_int32, C.POINTER(_P), C.POINTER(C.c_int64)]),
     "lpp_engine_state_to_host": (C.c_int32, [_P, C.c_int32, _P]),
     "lpp_engine_lanczos_device": (C.c_int32, [_P, _P, C.c_int32, _P, _P, C.POINTER(Stats)]),
     "lpp_engine_lanczos_begin_device": (C.c_int32, [_P, _P]),
     "lpp_engine_decomposition_device": (C.c_int32, [_P, _P, C.POINTER(C.c_int32), _P, _P, C.POINTER(Stats)]),
-    "lpp_engine_two_point": (C.c_int32, [_P] + [C.c_int32] * 8 + [_P, _P]),
-    "lpp_engine_spectral_decomposition": (C.c_int32, [_P, C.c_int32, _P] + [C.c_int32] * 4 + [C.c_double] + [C.c_int32] * 3
-                                          + [C.POINTER(C.c_double), C.POINTER(C.c_int32), _P, _P, C.POINTER(Stats)]),
-    "lpp_obs_new_parts_tj": (C.c_int32, [C.c_int32] * 5 + [C.POINTER(C.c_int32)] * 3),
     "lpp_obs_plan_tj": (C.c_int32, [C.c_int32] * 6 + [C.POINTER(C.c_int32)] * 3 + [C.POINTER(C.c_int64), _P]),
-    "lpp_engine_apply_operator_tj": (C.c_int32, [_P] + [C.c_int32] * 6 + [C.c_double, C.c_double, _P, _P, C.c_int32, C.POINTER(C.c_int32)]),
-    "lpp_engine_apply_operator_tj_host": (C.c_int32, [_P] + [C.c_int32] * 6 + [C.c_double, C.c_double, _P, _P, C.c_int32, C.POINTER(C.c_int32)]),
-    "lpp_engine_bench_operator_tj": (C.c_int32, [_P] + [C.c_int32] * 8 + [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "lpp_engine_keep_states_tj": (C.c_int32, [_P, C.c_int32]),
-    "lpp_engine_two_point_tj": (C.c_int32, [_P] + [C.c_int32] * 8 + [_P, _P]),
-    "lpp_engine_spectral_decomposition_tj": (C.c_int32, [_P, C.c_int32, _P] + [C.c_int32] * 4 + [C.c_double] + [C.c_int32] * 3
-                                             + [C.POINTER(C.c_double), C.POINTER(C.c_int32), _P, _P, C.POINTER(Stats)]),
-    "lpp_obs_new_parts_heis": (C.c_int32, [C.c_int32] * 5 + [C.POINTER(C.c_int32)] * 3),
     "lpp_obs_plan_heis": (C.c_int32, [C.c_int32] * 6 + [C.POINTER(C.c_int32)] * 3 + [C.POINTER(C.c_int64), C.POINTER(C.c_int32), _P]),
-    "lpp_engine_apply_operator_heis": (C.c_int32, [_P] + [C.c_int32] * 6 + [C.c_double, C.c_double, _P, _P, C.c_int32, C.POINTER(C.c_int32)]),
-    "lpp_engine_apply_operator_heis_host": (C.c_int32, [_P] + [C.c_int32] * 6 + [C.c_double, C.c_double, _P, _P, C.c_int32, C.POINTER(C.c_int32)]),
-    "lpp_engine_bench_operator_heis": (C.c_int32, [_P] + [C.c_int32] * 8 + [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
-    "lpp_engine_two_point_heis": (C.c_int32, [_P] + [C.c_int32] * 8 + [_P, _P]),
-    "lpp_engine_spectral_decomposition_heis": (C.c_int32, [_P, C.c_int32, _P] + [C.c_int32] * 4 + [C.c_double] + [C.c_int32] * 3
-                                               + [C.POINTER(C.c_double), C.POINTER(C.c_int32), _P, _P, C.POINTER(Stats)]),
-    "lpp_obs_new_parts_heis_spin": (C.c_int32, [C.c_int32] * 5 + [C.POINTER(C.c_int32)] * 3),
     "lpp_obs_plan_heis_spin": (C.c_int32, [C.c_int32] * 6 + [C.POINTER(C.c_int32)] * 2 + [C.POINTER(C.c_int64), C.POINTER(C.c_int32), _P, _P]),
-    "lpp_engine_apply_operator_heis_spin": (C.c_int32, [_P] + [C.c_int32] * 6 + [C.c_double, C.c_double, _P, _P, C.c_int32, C.POINTER(C.c_int32)]),
-    "lpp_engine_apply_operator_heis_spin_host": (C.c_int32, [_P] + [C.c_int32] * 6 + [C.c_double, C.c_double, _P, _P, C.c_int32, C.POINTER(C.c_int32)]),
-    "lpp_engine_bench_operator_heis_spin": (C.c_int32, [_P] + [C.c_int32] * 8 + [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
-    "lpp_engine_two_point_heis_spin": (C.c_int32, [_P] + [C.c_int32] * 8 + [_P, _P]),
-    "lpp_engine_spectral_decomposition_heis_spin": (C.c_int32, [_P, C.c_int32, _P] + [C.c_int32] * 4 + [C.c_double] + [C.c_int32] * 3
-                                                    + [C.POINTER(C.c_double), C.POINTER(C.c_int32), _P, _P, C.POINTER(Stats)]),
     "lpp_continued_fraction": (C.c_int32, [C.c_int32, _P, _P] + [C.c_double] * 5 + [_P]),
     "lpp_rdm_plan": (C.c_int32, [C.c_int32] * 5 + [C.POINTER(C.c_int32)] + [C.POINTER(C.c_int64)] * 4 + [_P, _P, _P, _P]),
     "lpp_engine_reduced_density_matrix": (C.c_int32, [_P] + [C.c_int32] * 5 + [_P, _P]),
@@ -170,42 +142,46 @@ SYMBOLS = {
     "lpp_engine_bench_rdm": (C.c_int32, [_P] + [C.c_int32] * 7 + [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "lpp_obs_string_plan": (C.c_int32, [C.c_int32, C.c_int32, _P, _P, _P, _P] + [C.c_int32] * 3 + [C.POINTER(C.c_int32)] * 3 + [C.POINTER(C.c_double)]
                             + [C.POINTER(C.c_int64)] * 2 + [_P, _P, C.POINTER(C.c_int32), _P]),
-    "lpp_engine_apply_string": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P] + [C.c_int32] * 3 + [C.c_double, C.c_double, _P, _P, C.c_int32]
-                                + [C.POINTER(C.c_int32)] * 3),
-    "lpp_engine_apply_string_host": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P] + [C.c_int32] * 3 + [C.c_double, C.c_double, _P, _P, C.c_int32]
-                                     + [C.POINTER(C.c_int32)] * 3),
-    "lpp_engine_many_point": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P] + [C.c_int32] * 5 + [_P]),
-    "lpp_engine_many_point_host": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P] + [C.c_int32] * 3 + [_P, _P, _P]),
-    "lpp_engine_bench_string_dot": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P] + [C.c_int32] * 5 + [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "lpp_obs_string_plan_heis": (C.c_int32, [C.c_int32, C.c_int32, _P, _P, _P, _P] + [C.c_int32] * 3 + [C.POINTER(C.c_int32)] * 2 + [C.POINTER(C.c_uint64)] * 4
                                  + [C.POINTER(C.c_int32)] * 2 + [C.POINTER(C.c_int64), _P]),
-    "lpp_engine_apply_string_heis": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P] + [C.c_int32] * 3 + [C.c_double, C.c_double, _P, _P, C.c_int32]
-                                     + [C.POINTER(C.c_int32)] * 3),
-    "lpp_engine_apply_string_heis_host": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P] + [C.c_int32] * 3 + [C.c_double, C.c_double, _P, _P, C.c_int32]
-                                          + [C.POINTER(C.c_int32)] * 3),
-    "lpp_engine_many_point_heis": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P] + [C.c_int32] * 5 + [_P]),
-    "lpp_engine_many_point_heis_host": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P] + [C.c_int32] * 3 + [_P, _P, _P]),
-    "lpp_engine_bench_string_dot_heis": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P] + [C.c_int32] * 5 + [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "lpp_obs_string_plan_tj": (C.c_int32, [C.c_int32, C.c_int32, _P, _P, _P, _P] + [C.c_int32] * 3 + [C.POINTER(C.c_int32)] * 4 + [_P, C.POINTER(C.c_int32)]
                                + [C.POINTER(C.c_int64)] * 2 + [_P]),
-    "lpp_engine_apply_string_tj": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P] + [C.c_int32] * 3 + [C.c_double, C.c_double, _P, _P, C.c_int32]
-                                   + [C.POINTER(C.c_int32)] * 3),
-    "lpp_engine_apply_string_tj_host": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P] + [C.c_int32] * 3 + [C.c_double, C.c_double, _P, _P, C.c_int32]
-                                        + [C.POINTER(C.c_int32)] * 3),
-    "lpp_engine_many_point_tj": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P] + [C.c_int32] * 5 + [_P]),
-    "lpp_engine_many_point_tj_host": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P] + [C.c_int32] * 3 + [_P, _P, _P]),
-    "lpp_engine_bench_string_dot_tj": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P] + [C.c_int32] * 5 + [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "lpp_obs_sum_plan": (C.c_int32, [C.c_int32] * 5 + [_P, _P] + [C.POINTER(C.c_int32)] * 3 + [C.POINTER(C.c_int64), C.POINTER(C.c_int32), _P, _P, _P, _P]),
 }
-# site-weighted operator sums: one signature per call, four families
-for _sfx in ("", "_tj", "_heis", "_heis_spin"):
-    SYMBOLS["lpp_engine_apply_operator_sum" + _sfx] = (C.c_int32, [_P] + [C.c_int32] * 6 + [_P, _P, _P, _P, C.c_int32, C.POINTER(C.c_int32)])
-    SYMBOLS["lpp_engine_apply_operator_sum" + _sfx + "_host"] = (C.c_int32, [_P] + [C.c_int32] * 6 + [_P, _P, _P, _P, C.c_int32, C.POINTER(C.c_int32),
-                                                                                                         C.POINTER(C.c_int64)])
-    SYMBOLS["lpp_engine_bench_operator_sum" + _sfx] = (C.c_int32, [_P] + [C.c_int32] * 6 + [_P, _P] + [C.c_int32] * 3 + [C.POINTER(C.c_double)] * 2)
-    SYMBOLS["lpp_engine_sum_norm2" + _sfx] = (C.c_int32, [_P] + [C.c_int32] * 7 + [_P, _P, C.POINTER(C.c_double), C.POINTER(C.c_int32)])
-    SYMBOLS["lpp_engine_spectral_decomposition_sum" + _sfx] = (C.c_int32, [_P, C.c_int32, _P] + [C.c_int32] * 6 + [_P, _P, C.POINTER(C.c_double), C.POINTER(C.c_int32),
-                                                                                                                     _P, _P, C.POINTER(Stats)])
+# The entry points every observable family has under its own suffix: one signature per stem; "{}" is where the suffix goes (before _host).
+# The lpp_obs_plan* and lpp_obs_string_plan* calls above differ per family and stay spelled out.
+_APPLY = [_P] + [C.c_int32] * 6 + [C.c_double, C.c_double, _P, _P, C.c_int32, C.POINTER(C.c_int32)]
+_APPLY_SUM = [_P] + [C.c_int32] * 6 + [_P, _P, _P, _P, C.c_int32, C.POINTER(C.c_int32)]
+_STRING = [_P, C.c_int32, C.c_int32, _P, _P, _P, _P]  # engine, convention, count, then the flat arrays of the strings
+_APPLY_STRING = _STRING + [C.c_int32] * 3 + [C.c_double, C.c_double, _P, _P, C.c_int32] + [C.POINTER(C.c_int32)] * 3
+_PER_FAMILY = {
+    ("", "_tj", "_heis", "_heis_spin"): {
+        "lpp_obs_new_parts{}": [C.c_int32] * 5 + [C.POINTER(C.c_int32)] * 3,
+        "lpp_engine_apply_operator{}": _APPLY,
+        "lpp_engine_apply_operator{}_host": _APPLY,
+        "lpp_engine_bench_operator{}": [_P] + [C.c_int32] * 8 + [C.POINTER(C.c_double), C.POINTER(C.c_double)],
+        "lpp_engine_two_point{}": [_P] + [C.c_int32] * 8 + [_P, _P],
+        "lpp_engine_spectral_decomposition{}": [_P, C.c_int32, _P] + [C.c_int32] * 4 + [C.c_double] + [C.c_int32] * 3
+                                               + [C.POINTER(C.c_double), C.POINTER(C.c_int32), _P, _P, C.POINTER(Stats)],
+        # site-weighted operator sums
+        "lpp_engine_apply_operator_sum{}": _APPLY_SUM,
+        "lpp_engine_apply_operator_sum{}_host": _APPLY_SUM + [C.POINTER(C.c_int64)],
+        "lpp_engine_bench_operator_sum{}": [_P] + [C.c_int32] * 6 + [_P, _P] + [C.c_int32] * 3 + [C.POINTER(C.c_double)] * 2,
+        "lpp_engine_sum_norm2{}": [_P] + [C.c_int32] * 7 + [_P, _P, C.POINTER(C.c_double), C.POINTER(C.c_int32)],
+        "lpp_engine_spectral_decomposition_sum{}": [_P, C.c_int32, _P] + [C.c_int32] * 6 + [_P, _P, C.POINTER(C.c_double), C.POINTER(C.c_int32), _P, _P, C.POINTER(Stats)],
+    },
+    ("", "_heis", "_tj"): {  # operator strings
+        "lpp_engine_apply_string{}": _APPLY_STRING,
+        "lpp_engine_apply_string{}_host": _APPLY_STRING,
+        "lpp_engine_many_point{}": _STRING + [_P] + [C.c_int32] * 5 + [_P],
+        "lpp_engine_many_point{}_host": _STRING + [_P] + [C.c_int32] * 3 + [_P, _P, _P],
+        "lpp_engine_bench_string_dot{}": _STRING + [_P] + [C.c_int32] * 5 + [C.POINTER(C.c_double), C.POINTER(C.c_double)],
+    },
+}
+for _families, _stems in _PER_FAMILY.items():
+    for _sfx in _families:
+        for _stem, _args in _stems.items():
+            SYMBOLS[_stem.format(_sfx)] = (C.c_int32, list(_args))
 
 _lib = None
 

@@ -5,8 +5,8 @@
 // :494-533, calcSpectral :460-490), operator strings (Engine::manyPoint :341-389) and the continued-fraction evaluator.
 //
 // The device side only.  Each family is one ObsBasis: how its plan is built and uploaded (a DevPlan of its own in the engine's cache) and how it is
-// launched; every entry point is one body over an ObsBasis, and the four destination-driven apply kernels go through one launch (OBS_LAUNCH); the
-// spin-S kernel (lpp_obs_heis_spin_plan.h, lpp_obs_heis_spin_kernels.h) names its instance through lpp_launch.h's with_flags.
+// launched; every entry point is one body over an ObsBasis, and every destination-driven kernel (one-site, fused sum, string apply) goes through one
+// launch (obs_launch), which like the other kernels here names its instance through lpp_launch.h's with_flags.
 // Operator strings have three families (HubbardStrings, HeisStrings, TjStrings) under one driver and one set of entry-point bodies (STRING_ENTRY).
 // The host planners (no GPU, plain C++) are lpp_obs_plan.h (shared sector arithmetic, Hubbard), lpp_obs_tj_plan.h, lpp_obs_heis_plan.h and
 // lpp_obs_string_plan.h, for strings in the Heisenberg basis lpp_obs_heis_string_plan.h, in the t-J basis lpp_obs_tj_string_plan.h; the kernels are
@@ -89,20 +89,14 @@ int obs_grid(const lpp_engine* e, int64_t units)
 }
 
 // The one launch of a destination-driven kernel template <CPLX, ACC>(dst, src, args) over n destination elements: 16-byte units in tiles of kObsTile,
-// at most 32 blocks per CU, on the engine's stream.  Returns from the calling function on a launch error.
-#define OBS_LAUNCH(kernel, e, acc, n, lds, d_dst, d_src, args)                                                                     \
-	do {                                                                                                                           \
-		const int64_t n_ = (n);                                                                                                    \
-		const int g_ = obs_grid((e), (e)->is_complex ? n_ : (n_ + 1) / 2);                                                         \
-		if ((e)->is_complex) {                                                                                                     \
-			if (acc) kernel<true, true><<<g_, kObsBlock, (lds), (e)->stream>>>((double*)(d_dst), (const double*)(d_src), (args));  \
-			else kernel<true, false><<<g_, kObsBlock, (lds), (e)->stream>>>((double*)(d_dst), (const double*)(d_src), (args));     \
-		} else {                                                                                                                   \
-			if (acc) kernel<false, true><<<g_, kObsBlock, (lds), (e)->stream>>>((double*)(d_dst), (const double*)(d_src), (args)); \
-			else kernel<false, false><<<g_, kObsBlock, (lds), (e)->stream>>>((double*)(d_dst), (const double*)(d_src), (args));    \
-		}                                                                                                                          \
-		HIP_TRY(hipGetLastError());                                                                                                \
-	} while (0)
+// at most 32 blocks per CU.  launch(grid, lds, cplx, acc) names the instance with the two std::bool_constants and enqueues it on the engine's stream.
+template <typename Launch> lpp_status obs_launch(const lpp_engine* e, bool acc, int64_t n, size_t lds, Launch&& launch)
+{
+	const int grid = obs_grid(e, e->is_complex ? n : (n + 1) / 2);
+	with_flags([&](auto cplx, auto accumulate) { launch(grid, lds, cplx, accumulate); }, e->is_complex, acc);
+	HIP_TRY(hipGetLastError());
+	return LPP_OK;
+}
 
 // Everything the entry points below need to know about a basis: they are written once and run for every family.
 struct ObsBasis {
@@ -125,7 +119,7 @@ struct ObsBasis {
 	lpp_status (*launch_sum)(lpp_engine* e, const DevPlan& D, const double* w_re, const double* w_im, const void* d_src, void* d_dst, bool acc);
 	// the spin-S digit basis: the two counts are (twiceS, szPlusConst), sz is ONE operator of the basis (no n to split it into), and lpp_obs_new_parts*
 	// reports the new sector as (szPlusConst', 0)
-	bool spin_args = false;
+	bool spin_args;
 };
 
 // ---- the Hubbard product basis (plan: lpp_obs_plan.h, kernel: lpp_obs_kernels.h) ---------------------------------------------------------------
@@ -158,8 +152,7 @@ lpp_status launch_hubbard(lpp_engine* e, const DevPlan& D0, double fr, double fi
 	const HubbardDev& D = static_cast<const HubbardDev&>(D0);
 	const ObsPlan& P = D.host;
 	ObsArgs A { D.tu, D.td, P.n_up_dst, P.n_dn_dst, P.n_up_src, P.sz ? 1 : 0, fr, fi };
-	OBS_LAUNCH(k_obs_apply, e, acc, D.n_dst, 0, d_dst, d_src, A);
-	return LPP_OK;
+	return obs_launch(e, acc, D.n_dst, 0, [&](int g, size_t lds, auto c, auto a) { k_obs_apply<c, a><<<g, kObsBlock, lds, e->stream>>>((double*)d_dst, (const double*)d_src, A); });
 }
 
 // the fused operator sum of this basis (plan: lpp_obs_sum_plan.h, kernels: lpp_obs_sum_kernels.h)
@@ -210,18 +203,15 @@ lpp_status launch_hubbard_sum(lpp_engine* e, const DevPlan& D0, const double* w_
 		for (int s = 0; s < 2; s++) {
 			const int64_t n = s ? P.n_dn_dst : P.n_up_dst;
 			const int g = (int)std::max<int64_t>(1, std::min<int64_t>((n + kObsBlock - 1) / kObsBlock, 1024));
-			if (e->is_complex) k_obs_sum_coef<true><<<g, kObsBlock, 0, e->stream>>>(s ? D.wd : D.wu, n, s ? D.cd : D.cu, w);
-			else k_obs_sum_coef<false><<<g, kObsBlock, 0, e->stream>>>(s ? D.wd : D.wu, n, s ? D.cd : D.cu, w);
+			with_flags([&](auto c) { k_obs_sum_coef<c><<<g, kObsBlock, 0, e->stream>>>(s ? D.wd : D.wu, n, s ? D.cd : D.cu, w); }, e->is_complex);
 		}
 		HIP_TRY(hipGetLastError());
 		ObsSumDiagArgs A { D.cu, D.cd, P.n_up_dst, P.n_dn_dst, P.alpha, P.beta };
-		OBS_LAUNCH(k_obs_sum_diag, e, acc, D.n_dst, 0, d_dst, d_src, A);
-		return LPP_OK;
+		return obs_launch(e, acc, D.n_dst, 0, [&](int g, size_t lds, auto c, auto a) { k_obs_sum_diag<c, a><<<g, kObsBlock, lds, e->stream>>>((double*)d_dst, (const double*)d_src, A); });
 	}
 	ObsSumMoveArgs A { D.tab, D.site, P.n, P.W, P.n_up_dst, P.n_dn_dst, P.n_up_src, w };
-	if (P.down) OBS_LAUNCH(k_obs_sum_move_down, e, acc, D.n_dst, 0, d_dst, d_src, A);
-	else OBS_LAUNCH(k_obs_sum_move_up, e, acc, D.n_dst, 0, d_dst, d_src, A);
-	return LPP_OK;
+	if (P.down) return obs_launch(e, acc, D.n_dst, 0, [&](int g, size_t lds, auto c, auto a) { k_obs_sum_move_down<c, a><<<g, kObsBlock, lds, e->stream>>>((double*)d_dst, (const double*)d_src, A); });
+	return obs_launch(e, acc, D.n_dst, 0, [&](int g, size_t lds, auto c, auto a) { k_obs_sum_move_up<c, a><<<g, kObsBlock, lds, e->stream>>>((double*)d_dst, (const double*)d_src, A); });
 }
 
 // ---- the one-orbital t-J basis (plan: lpp_obs_tj_plan.h, kernel: lpp_obs_tj_kernels.h) -------------------------------------------------------
@@ -262,8 +252,8 @@ lpp_status launch_tj(lpp_engine* e, const DevPlan& D0, double fr, double fi, con
 	const TjDev& D = static_cast<const TjDev&>(D0);
 	const ObsTjPlan& P = D.host;
 	ObsTjArgs A { D.dn, D.pat, D.hi, D.lo, P.up, P.lb, D.nhi, D.nlo, P.n_up_dst, P.n_dn_dst, P.n_up_src, fr, fi };
-	OBS_LAUNCH(k_obs_apply_tj, e, acc, D.n_dst, obs_tj_lds_bytes(A.nhi, A.nlo), d_dst, d_src, A);
-	return LPP_OK;
+	return obs_launch(e, acc, D.n_dst, obs_tj_lds_bytes(A.nhi, A.nlo),
+	                  [&](int g, size_t lds, auto c, auto a) { k_obs_apply_tj<c, a><<<g, kObsBlock, lds, e->stream>>>((double*)d_dst, (const double*)d_src, A); });
 }
 
 // ---- the S = 1/2 Heisenberg basis (plan: lpp_obs_heis_plan.h, kernel: lpp_obs_heis_kernels.h); nup = szPlusConst -----------------------------
@@ -302,8 +292,8 @@ lpp_status launch_heis(lpp_engine* e, const DevPlan& D0, double fr, double fi, c
 	const HeisDev& D = static_cast<const HeisDev&>(D0);
 	const ObsHeisPlan& P = D.host;
 	ObsHeisArgs A { D.runs, D.word, D.rank, P.mode, D.nlo, P.bit, D.nruns, D.n_dst, fr, fi };
-	OBS_LAUNCH(k_obs_apply_heis, e, acc, D.n_dst, obs_heis_lds_bytes(A.mode, A.nlo), d_dst, d_src, A);
-	return LPP_OK;
+	return obs_launch(e, acc, D.n_dst, obs_heis_lds_bytes(A.mode, A.nlo),
+	                  [&](int g, size_t lds, auto c, auto a) { k_obs_apply_heis<c, a><<<g, kObsBlock, lds, e->stream>>>((double*)d_dst, (const double*)d_src, A); });
 }
 
 // the fused sum_r f_r sz_r of this basis (k_obs_sum_sz_heis): the run table and the low words of the one-site sz plan, and the runs' high parts
@@ -357,11 +347,10 @@ lpp_status launch_heis_sum(lpp_engine* e, const DevPlan& D0, const double* w_re,
 		A.F_im += w_im[r];
 	}
 	const int g = (int)std::max<int64_t>(1, std::min<int64_t>((D.nruns + kObsBlock - 1) / kObsBlock, 1024));
-	if (e->is_complex) k_obs_sum_hi_heis<true><<<g, kObsBlock, 0, e->stream>>>(D.highs, D.nruns, D.lb, D.hi, A.w);
-	else k_obs_sum_hi_heis<false><<<g, kObsBlock, 0, e->stream>>>(D.highs, D.nruns, D.lb, D.hi, A.w);
+	with_flags([&](auto c) { k_obs_sum_hi_heis<c><<<g, kObsBlock, 0, e->stream>>>(D.highs, D.nruns, D.lb, D.hi, A.w); }, e->is_complex);
 	HIP_TRY(hipGetLastError());
-	OBS_LAUNCH(k_obs_sum_sz_heis, e, acc, D.n_dst, obs_sum_heis_lds_bytes(A.nlo), d_dst, d_src, A);
-	return LPP_OK;
+	return obs_launch(e, acc, D.n_dst, obs_sum_heis_lds_bytes(A.nlo),
+	                  [&](int g, size_t lds, auto c, auto a) { k_obs_sum_sz_heis<c, a><<<g, kObsBlock, lds, e->stream>>>((double*)d_dst, (const double*)d_src, A); });
 }
 
 // ---- the spin-S Heisenberg digit basis (plan: lpp_obs_heis_spin_plan.h, kernel: lpp_obs_heis_spin_kernels.h); nup = twiceS, ndn = szPlusConst --------
@@ -403,27 +392,32 @@ lpp_status launch_heis_spin(lpp_engine* e, const DevPlan& D0, double fr, double 
 	const HeisSpinDev& D = static_cast<const HeisSpinDev&>(D0);
 	const ObsHeisSpinPlan& P = D.host;
 	const ObsHeisSpinArgs A { D.runs, D.word, D.rank, D.val, P.mode, D.nword, D.nrank, P.shift, P.mask, P.twiceS, D.nruns, D.n_dst, fr, fi };
-	const int grid = obs_grid(e, e->is_complex ? D.n_dst : (D.n_dst + 1) / 2);
-	const size_t lds = obs_heis_spin_lds_bytes(A.mode, A.nword, A.nrank);
-	with_flags(
-	    [&](auto cplx, auto accumulate) {
-		    k_obs_apply_heis_spin<decltype(cplx)::value, decltype(accumulate)::value><<<grid, kObsBlock, lds, e->stream>>>((double*)d_dst, (const double*)d_src, A);
-	    },
-	    e->is_complex, acc);
-	HIP_TRY(hipGetLastError());
-	return LPP_OK;
+	return obs_launch(e, acc, D.n_dst, obs_heis_spin_lds_bytes(A.mode, A.nword, A.nrank),
+	                  [&](int g, size_t lds, auto c, auto a) { k_obs_apply_heis_spin<c, a><<<g, kObsBlock, lds, e->stream>>>((double*)d_dst, (const double*)d_src, A); });
 }
 
 enum { BASIS_HUBBARD = 0, BASIS_TJ = 1, BASIS_HEIS = 2, BASIS_HEIS_SPIN = 3 };
-const ObsBasis kHubbard { BASIS_HUBBARD, false, true, true, false, true, [](int L, int nup, int ndn) { return L >= 1 && nup >= 0 && ndn >= 0 && nup <= L && ndn <= L; },
-	                      hubbard_sector_size, new_parts, build_hubbard, launch_hubbard, obs_sum_fused_op, build_hubbard_sum, launch_hubbard_sum };
-const ObsBasis kTj { BASIS_TJ, true, true, true, false, false, [](int L, int nup, int ndn) { return L >= 1 && nup >= 0 && ndn >= 0 && nup + ndn <= L; },
-	                 tj_sector_size, new_parts_tj, build_tj, launch_tj, nullptr, nullptr, nullptr };
-const ObsBasis kHeis { BASIS_HEIS, false, false, false, true, true, [](int L, int nup, int) { return heis_sector_size(L, nup, 0) >= 0; },
-	                   heis_sector_size, new_parts_heis, build_heis, launch_heis, heis_sum_fused_op, build_heis_sum, launch_heis_sum };
+const ObsBasis kHubbard {
+	.id = BASIS_HUBBARD, .hole_major_ok = false, .reads_ndown = true, .fermions = true, .no_sector_throws = false, .sz_has_no_parts = true,
+	.counts_ok = [](int L, int nup, int ndn) { return L >= 1 && nup >= 0 && ndn >= 0 && nup <= L && ndn <= L; },
+	.sector_size = hubbard_sector_size, .new_parts = new_parts, .build = build_hubbard, .launch = launch_hubbard,
+	.sum_fused = obs_sum_fused_op, .build_sum = build_hubbard_sum, .launch_sum = launch_hubbard_sum, .spin_args = false };
+const ObsBasis kTj {
+	.id = BASIS_TJ, .hole_major_ok = true, .reads_ndown = true, .fermions = true, .no_sector_throws = false, .sz_has_no_parts = false,
+	.counts_ok = [](int L, int nup, int ndn) { return L >= 1 && nup >= 0 && ndn >= 0 && nup + ndn <= L; },
+	.sector_size = tj_sector_size, .new_parts = new_parts_tj, .build = build_tj, .launch = launch_tj,
+	.sum_fused = nullptr, .build_sum = nullptr, .launch_sum = nullptr, .spin_args = false };
+const ObsBasis kHeis {
+	.id = BASIS_HEIS, .hole_major_ok = false, .reads_ndown = false, .fermions = false, .no_sector_throws = true, .sz_has_no_parts = true,
+	.counts_ok = [](int L, int nup, int) { return heis_sector_size(L, nup, 0) >= 0; },
+	.sector_size = heis_sector_size, .new_parts = new_parts_heis, .build = build_heis, .launch = launch_heis,
+	.sum_fused = heis_sum_fused_op, .build_sum = build_heis_sum, .launch_sum = launch_heis_sum, .spin_args = false };
 // (reads_ndown: the cache key holds both counts, so it tells twiceS apart; the operator sums chain the one-site launches)
-const ObsBasis kHeisSpin { BASIS_HEIS_SPIN, false, true, false, true, true, [](int L, int twiceS, int m) { return heis_spin_sector_size(L, twiceS, m) >= 0; },
-	                       heis_spin_sector_size, new_parts_heis_spin, build_heis_spin, launch_heis_spin, nullptr, nullptr, nullptr, true };
+const ObsBasis kHeisSpin {
+	.id = BASIS_HEIS_SPIN, .hole_major_ok = false, .reads_ndown = true, .fermions = false, .no_sector_throws = true, .sz_has_no_parts = true,
+	.counts_ok = [](int L, int twiceS, int m) { return heis_spin_sector_size(L, twiceS, m) >= 0; },
+	.sector_size = heis_spin_sector_size, .new_parts = new_parts_heis_spin, .build = build_heis_spin, .launch = launch_heis_spin,
+	.sum_fused = nullptr, .build_sum = nullptr, .launch_sum = nullptr, .spin_args = true };
 
 // The tables of one (operator, site, spin, sites, sector), uploaded once and kept with the engine.  The key is what the caller passes -- the engine
 // needs no model for lpp_engine_apply_operator -- so the cache is bounded: a density of states or a two-point matrix uses at most 2 * sites entries
@@ -757,8 +751,7 @@ lpp_status two_point_body(const ObsBasis& Bs, const std::string& who, lpp_engine
 				const int np = std::min(kPanel, nj - p0);
 				const double2* v0 = (const double2*)((double*)B.p + (int64_t)p0 * stride);
 				// coef_p = sum conj(v_p) x: the bra side (the left factor of modifVector2 * modifVector1) is conjugated
-				if (e->is_complex) k_multi_dot<true><<<nb, kBlock, 0, e->stream>>>((const double2*)xi, v0, ld2, np, n2, (double*)part.p);
-				else k_multi_dot<false><<<nb, kBlock, 0, e->stream>>>((const double2*)xi, v0, ld2, np, n2, (double*)part.p);
+				with_flags([&](auto c) { k_multi_dot<c><<<nb, kBlock, 0, e->stream>>>((const double2*)xi, v0, ld2, np, n2, (double*)part.p); }, e->is_complex);
 				k_reduce_final<<<1, kBlock, 0, e->stream>>>((const double*)part.p, nb, 2 * kPanel, 2 * np, (double*)out.p + 2 * ((int64_t)i * L + j0 + p0));
 			}
 		}
@@ -1061,7 +1054,8 @@ struct HubbardStrings {
 		const int32_t* d = (const int32_t*)T.p;
 		ObsStringApplyArgs A { dev_string(P, G, d, 0), (const uint32_t*)(d + G.words_up()), (const uint32_t*)(d + G.words_dn()), P.n_up_dst, P.n_dn_dst, P.n_up_src,
 			                   fr * P.scale, fi * P.scale };
-		OBS_LAUNCH(k_obs_string_apply, e, acc, n_dst(P), 0, d_dst, d_src, A);
+		st = obs_launch(e, acc, n_dst(P), 0, [&](int g, size_t lds, auto c, auto a) { k_obs_string_apply<c, a><<<g, kObsBlock, lds, e->stream>>>((double*)d_dst, (const double*)d_src, A); });
+		if (st != LPP_OK) return st;
 		HIP_TRY(hipStreamSynchronize(e->stream));
 		return LPP_OK;
 	}
@@ -1099,8 +1093,7 @@ struct HubbardStrings {
 		}
 		void launch(lpp_engine* e, const double* bra, const double* ket, double* d_out) const
 		{
-			if (e->is_complex) k_obs_string_dot<true><<<grid, kObsBlock, 0, e->stream>>>(bra, ket, A);
-			else k_obs_string_dot<false><<<grid, kObsBlock, 0, e->stream>>>(bra, ket, A);
+			with_flags([&](auto c) { k_obs_string_dot<c><<<grid, kObsBlock, 0, e->stream>>>(bra, ket, A); }, e->is_complex);
 			reduce(e, A.ns, d_out);
 		}
 	};
@@ -1152,7 +1145,9 @@ struct HeisStrings {
 		if ((st = W.fill(e, &P, 1, L, m, A.b, &A.src, &A.low)) != LPP_OK) return st;
 		A.fr = fr;
 		A.fi = fi;
-		OBS_LAUNCH(k_obs_string_apply_heis, e, acc, P.n_dst, obs_heis_string_lds_bytes(A.b.nlo), d_dst, d_src, A);
+		st = obs_launch(e, acc, P.n_dst, obs_heis_string_lds_bytes(A.b.nlo),
+		                [&](int g, size_t lds, auto c, auto a) { k_obs_string_apply_heis<c, a><<<g, kObsBlock, lds, e->stream>>>((double*)d_dst, (const double*)d_src, A); });
+		if (st != LPP_OK) return st;
 		HIP_TRY(hipStreamSynchronize(e->stream));
 		return LPP_OK;
 	}
@@ -1211,8 +1206,7 @@ struct HeisStrings {
 		void launch(lpp_engine* e, const double* bra, const double* ket, double* d_out) const
 		{
 			const size_t lds = obs_heis_string_lds_bytes(A.b.nlo);
-			if (e->is_complex) k_obs_string_dot_heis<true><<<grid, kObsBlock, lds, e->stream>>>(bra, ket, A);
-			else k_obs_string_dot_heis<false><<<grid, kObsBlock, lds, e->stream>>>(bra, ket, A);
+			with_flags([&](auto c) { k_obs_string_dot_heis<c><<<grid, kObsBlock, lds, e->stream>>>(bra, ket, A); }, e->is_complex);
 			reduce(e, A.ns, d_out);
 		}
 	};
@@ -1265,7 +1259,9 @@ struct TjStrings {
 		if ((st = W.fill(e, &P, 1, A.b, &A.ent, &A.up)) != LPP_OK) return st;
 		A.fr = fr;
 		A.fi = fi;
-		OBS_LAUNCH(k_obs_string_apply_tj, e, acc, n_dst(P), obs_tj_string_lds_bytes(A.b), d_dst, d_src, A);
+		st = obs_launch(e, acc, n_dst(P), obs_tj_string_lds_bytes(A.b),
+		                [&](int g, size_t lds, auto c, auto a) { k_obs_string_apply_tj<c, a><<<g, kObsBlock, lds, e->stream>>>((double*)d_dst, (const double*)d_src, A); });
+		if (st != LPP_OK) return st;
 		HIP_TRY(hipStreamSynchronize(e->stream));
 		return LPP_OK;
 	}
@@ -1318,8 +1314,7 @@ struct TjStrings {
 		void launch(lpp_engine* e, const double* bra, const double* ket, double* d_out) const
 		{
 			const size_t lds = obs_tj_string_lds_bytes(A.b);
-			if (e->is_complex) k_obs_string_dot_tj<true><<<grid, kObsBlock, lds, e->stream>>>(bra, ket, A);
-			else k_obs_string_dot_tj<false><<<grid, kObsBlock, lds, e->stream>>>(bra, ket, A);
+			with_flags([&](auto c) { k_obs_string_dot_tj<c><<<grid, kObsBlock, lds, e->stream>>>(bra, ket, A); }, e->is_complex);
 			reduce(e, A.ns, d_out);
 		}
 	};

@@ -7,6 +7,8 @@ src/Engine/Engine.h:626,478).  It is a thin ctypes layer over the C ABI (include
 all arithmetic runs in liblpp_engine.so on the GPU.  numpy arrays are the host buffers.
 """
 import ctypes as C
+from collections import namedtuple
+from math import comb
 
 import numpy as np
 
@@ -159,7 +161,7 @@ class LanczosEngine:
         V = np.zeros(L) if V is None else np.ascontiguousarray(np.asarray(V, np.float64)[:L])
         nj = None if ninj is None else _mat(ninj, L)
         self._comm_keepalive = comm
-        self._set_model("assemble_hubbard", L, nup, ndown, hop, U, V, ninj, jcoup, comm)
+        self._set_model(None if comm is not None else "assemble_hubbard", L=L, nup=nup, ndown=ndown, hop=hop, U=U, V=V, ninj=ninj, jcoup=jcoup)
         self._basis = ("hubbard", L, nup, ndown) if comm is None else None
         cs = C.byref(comm.struct) if comm is not None else None
         jc = None if jcoup is None else _mat(jcoup, L)
@@ -176,7 +178,7 @@ class LanczosEngine:
         V = np.zeros(L) if V is None else np.ascontiguousarray(np.asarray(V, np.float64)[:L])
         nj = None if ninj is None else _mat(ninj, L)
         self._comm_keepalive = comm
-        self._set_model("setup_hubbard_onthefly", L, nup, ndown, hop, U, V, ninj, jcoup, comm)
+        self._set_model(None if comm is not None else "setup_hubbard_onthefly", L=L, nup=nup, ndown=ndown, hop=hop, U=U, V=V, ninj=ninj, jcoup=jcoup)
         self._basis = ("hubbard", L, nup, ndown) if comm is None else None
         cs = C.byref(comm.struct) if comm is not None else None
         jc = None if jcoup is None else _mat(jcoup, L)
@@ -187,7 +189,7 @@ class LanczosEngine:
         f = None if field is None else np.ascontiguousarray(field, np.float64)
         # ReducedDensityMatrix::unpackHeisenberg reads one bit per site: S = 1/2 only
         self._basis = ("spin_half", L, szPlusConst, 0) if twiceS == 1 else "the reduced density matrix of a Heisenberg model needs twiceS = 1 (one bit per site)"
-        self._set_model_heisenberg(L, szPlusConst, jpm, jzz, field, twiceS, anisotropy)
+        self._set_model("assemble_heisenberg", L=L, szPlusConst=szPlusConst, jpm=jpm, jzz=jzz, field=field, twiceS=twiceS, anisotropy=anisotropy)
         if twiceS == 1 and anisotropy is None:
             check(self._lib.lpp_engine_assemble_heisenberg(self._h, L, szPlusConst, _vp(_mat(jpm, L)), _vp(_mat(jzz, L)),
                                                            _vp(f), 0 if f is None else len(f)))
@@ -202,7 +204,7 @@ class LanczosEngine:
         hi = _mat(hop.imag, L) if np.iscomplexobj(hop) else None
         pv = None if potentialV is None else np.ascontiguousarray(potentialV, np.float64)
         self._basis = None  # the reference's ReducedDensityMatrix does not know this basis
-        self._set_model_tj(L, nup, ndown, hop, jpm, jzz, w, potentialV)
+        self._set_model("assemble_tj", L=L, nup=nup, ndown=ndown, hop=hop, jpm=jpm, jzz=jzz, w=w, potentialV=potentialV)
         check(self._lib.lpp_engine_assemble_tj(self._h, L, nup, ndown, _vp(hr), _vp(hi), _vp(_mat(jpm, L)),
                                                _vp(_mat(jzz, L)), _vp(_mat(w, L)), _vp(pv),
                                                0 if pv is None else len(pv)))
@@ -307,60 +309,56 @@ class LanczosEngine:
         return ms.value
 
 
-    # ---- observables of the Hubbard product basis (one GPU) -----------------------------------------
-    def _set_model(self, how, L, nup, ndown, hop, U, V, ninj, jcoup, comm):
-        self._model = None if comm is not None else dict(how=how, L=L, nup=nup, ndown=ndown, hop=np.array(hop, copy=True), U=np.array(U, copy=True),
-                                                         V=None if V is None else np.array(V, copy=True), ninj=None if ninj is None else np.array(ninj, copy=True),
-                                                         jcoup=None if jcoup is None else np.array(jcoup, copy=True))
+    # ---- observables of the four basis families of _FAMILIES (below) on one GPU -----------------------------------------
+    def _set_model(self, how, **fields):
+        """Record the keyword arguments of the assemble_* / setup_* method `how`, arrays copied: _sector_engine replays them on another sector.
+        how=None (a partitioned engine): no model.  The sector engines of the model before are dropped."""
+        self._model = None if how is None else dict(how=how, **{k: v if v is None or np.ndim(v) == 0 else np.array(v, copy=True) for k, v in fields.items()})
         for eng in self._sectors.values():
             eng.close()
         self._sectors = {}
 
-    def _set_model_tj(self, L, nup, ndown, hop, jpm, jzz, w, potentialV):
-        self._model = dict(how="assemble_tj", L=L, nup=nup, ndown=ndown, hop=np.array(hop, copy=True), jpm=np.array(jpm, copy=True), jzz=np.array(jzz, copy=True),
-                           w=np.array(w, copy=True), potentialV=None if potentialV is None else np.array(potentialV, copy=True))
-        for eng in self._sectors.values():
-            eng.close()
-        self._sectors = {}
-
-    def _set_model_heisenberg(self, L, szPlusConst, jpm, jzz, field, twiceS, anisotropy):
-        """nup = szPlusConst, ndown = 0: the sector as the _heis calls and LPP_BASIS_SPIN_HALF take it"""
-        self._model = dict(how="assemble_heisenberg", L=L, nup=szPlusConst, ndown=0, jpm=np.array(jpm, copy=True), jzz=np.array(jzz, copy=True),
-                           field=None if field is None else np.array(field, copy=True), twiceS=twiceS,
-                           anisotropy=None if anisotropy is None else np.array(anisotropy, copy=True))
-        for eng in self._sectors.values():
-            eng.close()
-        self._sectors = {}
+    def _own_basis(self):
+        """the name in OBS_BASES of the family the engine was set up in (assemble_heisenberg with any spin: "spin_half"); None without a model"""
+        return None if self._model is None else next(b for b, f in _FAMILIES.items() if self._model["how"] in f.assemble)
 
     def _is_tj(self):
-        return self._model is not None and self._model["how"] == "assemble_tj"
+        return self._own_basis() == "tj"
 
-    def _is_heis(self, who=None):
-        """True on an engine set up by assemble_heisenberg; with `who`, spins above 1/2 raise as the reference throws (BasisHeisenberg.h:130, Heisenberg.h:223)"""
-        if self._model is None or self._model["how"] != "assemble_heisenberg":
-            return False
-        if who is not None and self._model["twiceS"] != 1:
+    def _is_heis(self):
+        return self._own_basis() == "spin_half"
+
+    def _own_family(self, who, basis=None):
+        """(row of _FAMILIES, sites, own sector, the two counts of the entry points) for the observables of the resident states.  basis=None: the engine's
+        own family, where spins above 1/2 raise as the reference throws (BasisHeisenberg.h:130, Heisenberg.h:223).  basis="spin": the opt-in digit basis
+        of a Heisenberg engine of any admitted twiceS (LPP_ERR_INVALID on any other engine).  Anything else is a ValueError."""
+        m = self._need_model(who)
+        own = self._own_basis()
+        if basis is not None:
+            if basis != "spin":
+                raise ValueError("%s: unsupported basis %r (None for the engine's own, or \"spin\")" % (who, basis))
+            if own != "spin_half":
+                raise _capi.LppError(_capi.LPP_ERR_INVALID, "%s: basis=\"spin\" is for engines set up by assemble_heisenberg" % who)
+            own = "spin"
+        elif own == "spin_half":
+            self._refuse_higher_spin(who)
+        fam = _FAMILIES[own]
+        sector = fam.sector(m)
+        return fam, m["L"], sector, fam.counts(*sector, m.get("twiceS"))
+
+    def _refuse_higher_spin(self, who):
+        if self._model["twiceS"] != 1:
             raise _capi.LppError(_capi.LPP_ERR_INVALID, "%s: the observables of a Heisenberg model need twiceS = 1 (the reference throws for higher spins)" % who)
-        return True
 
-    def _obs_call(self, stem, spin=False):
-        """the entry point of the engine's model: stem, stem_tj or stem_heis; spin: stem_heis_spin (the opt-in digit basis)"""
-        return getattr(self._lib, stem + ("_heis_spin" if spin else "_tj" if self._is_tj() else "_heis" if self._is_heis() else ""))
+    def _destination(self, out, n, what):
+        """zeros, or the caller's `out` as a contiguous vector of the engine's dtype; it must have the n elements of `what`"""
+        if out is None:
+            return np.zeros(n, self.np_dtype)
+        z = np.ascontiguousarray(out, self.np_dtype)
+        if len(z) != n:
+            raise ValueError("out does not have the length of " + what)
+        return z
 
-    def _spin_basis(self, who, basis):
-        """basis=None: the engine's own family, False.  basis="spin": the opt-in digit basis of a Heisenberg engine of any admitted twiceS, True
-        (LPP_ERR_INVALID on any other engine).  Anything else is a ValueError."""
-        if basis is None:
-            return False
-        if basis != "spin":
-            raise ValueError("%s: unsupported basis %r (None for the engine's own, or \"spin\")" % (who, basis))
-        if not self._is_heis():
-            raise _capi.LppError(_capi.LPP_ERR_INVALID, "%s: basis=\"spin\" is for engines set up by assemble_heisenberg" % who)
-        return True
-
-    def _obs_sector(self, m, spin):
-        """(count, count) as the entry points take them: (nup, ndown), in the digit basis (twiceS, szPlusConst)"""
-        return (m["twiceS"], m["nup"]) if spin else (m["nup"], m["ndown"])
 
     def keep_states_tj(self, k=1):
         """keep_states that also accepts a hole-major t-J engine (lpp_engine_keep_states_tj): state(k) is then the host Ritz vector bit for bit"""
@@ -392,42 +390,26 @@ class LanczosEngine:
         assemble_heisenberg admits (operator_plan_heis_spin has the definition: nup = szPlusConst, ndown is not read, sz is the true S^z, n / c /
         cdagger and S+ on the top sector / S- on szPlusConst = 0 raise LppError)."""
         oid = _op_id(op)
-        tj = _obs_basis(basis)
+        fam = _obs_family(basis)
         src = np.ascontiguousarray(src, self.np_dtype)
-        has, n1, n2 = C.c_int32(), C.c_int32(), C.c_int32()
-        nu, nd = C.c_int64(1), C.c_int64()
-        c1, c2 = _obs_counts(basis, nup, ndown, twiceS)
-        if basis == "spin":
-            check(self._lib.lpp_obs_plan_heis_spin(oid, site, spin, L, c1, c2, C.byref(has), C.byref(n1), C.byref(nd), None, None, None))
-        elif basis == "spin_half":
-            check(self._lib.lpp_obs_plan_heis(oid, site, spin, L, nup, ndown, C.byref(has), C.byref(n1), C.byref(n2), C.byref(nd), None, None))
-        elif tj:
-            check(self._lib.lpp_obs_plan_tj(oid, site, spin, L, nup, ndown, C.byref(has), C.byref(n1), C.byref(n2), C.byref(nd), None))
-        else:
-            check(self._lib.lpp_obs_plan(oid, site, spin, L, nup, ndown, C.byref(has), C.byref(n1), C.byref(n2), C.byref(nu), C.byref(nd), None, None))
-        if not has.value:
+        c1, c2 = fam.counts(nup, ndown, twiceS)
+        has, new, n = fam.one_site_plan(oid, site, spin, L, c1, c2)
+        if not has:
             return None, None
-        if len(src) != sector_size(L, nup, ndown, basis, twiceS):
+        if len(src) != fam.size(L, c1, c2):
             raise ValueError("src does not have the length of sector (%d, %d)" % (nup, ndown))
-        n = nu.value * nd.value
-        if out is None:
-            z = np.zeros(n, self.np_dtype)
-        else:
-            z = np.ascontiguousarray(out, self.np_dtype)
-            if len(z) != n:
-                raise ValueError("out does not have the length of sector (%d, %d)" % (n1.value, n2.value))
+        z = self._destination(out, n, "sector (%d, %d)" % new)
         f = complex(factor)
-        call = getattr(self._lib, "lpp_engine_apply_operator" + _OBS_SUFFIX[basis] + "_host")
-        check(call(self._h, oid, site, spin, L, c1, c2, f.real, f.imag, _vp(src), _vp(z), int(out is not None), C.byref(has)))
-        return z, (n1.value, n2.value)
+        call = fam.entry("lpp_engine_apply_operator", host=True)
+        check(call(self._h, oid, site, spin, L, c1, c2, f.real, f.imag, _vp(src), _vp(z), int(out is not None), C.byref(C.c_int32())))
+        return z, new
 
     def bench_operator(self, op, site, spin, L, nup, ndown, warmup=2, iters=10, basis="hubbard", twiceS=None):
         """(ms per launch, bytes of the byte model) of the operator kernel on resident vectors"""
         ms, by = C.c_double(), C.c_double()
-        _obs_basis(basis)
-        c1, c2 = _obs_counts(basis, nup, ndown, twiceS)
-        call = getattr(self._lib, "lpp_engine_bench_operator" + _OBS_SUFFIX[basis])
-        check(call(self._h, _op_id(op), site, spin, L, c1, c2, warmup, iters, C.byref(ms), C.byref(by)))
+        fam = _obs_family(basis)
+        c1, c2 = fam.counts(nup, ndown, twiceS)
+        check(fam.entry("lpp_engine_bench_operator")(self._h, _op_id(op), site, spin, L, c1, c2, warmup, iters, C.byref(ms), C.byref(by)))
         return ms.value, by.value
 
     # ---- site-weighted operator sums: |phi> = sum_r f_r A_r |src>, the modified state of A(k,w), N(q,w), S(q,w) ----
@@ -438,55 +420,45 @@ class LanczosEngine:
         basis, splus / sminus and the "spin_half" n chain the one-site launches over the sites whose weight is not exactly 0 (as everything does under
         LPP_OBS_SUM_CHAIN=1), and so does everything in the "spin" basis (twiceS=...: sz is the true S^z).  Complex weights need a c128 engine."""
         oid = _op_id(op)
-        _obs_basis(basis)
-        c1, c2 = _obs_counts(basis, nup, ndown, twiceS)
+        fam = _obs_family(basis)
+        c1, c2 = fam.counts(nup, ndown, twiceS)
         w = np.asarray(weights, np.complex128).ravel()
         wr, wi = np.ascontiguousarray(w.real), np.ascontiguousarray(w.imag)
         src = np.ascontiguousarray(src, self.np_dtype)
         has, n = C.c_int32(), C.c_int64()
-        call = getattr(self._lib, "lpp_engine_apply_operator_sum" + _OBS_SUFFIX[basis] + "_host")
+        call = fam.entry("lpp_engine_apply_operator_sum", host=True)
         head = (self._h, oid, int(spin), int(L), c1, c2, len(w), _vp(wr), _vp(wi))
         check(call(*head, None, None, 0, C.byref(has), C.byref(n)))
         if not has.value:
             return None, None
-        if len(src) != sector_size(L, nup, ndown, basis, twiceS):
+        if len(src) != fam.size(L, c1, c2):
             raise ValueError("src does not have the length of sector (%d, %d)" % (nup, ndown))
-        if out is None:
-            z = np.zeros(n.value, self.np_dtype)
-        else:
-            z = np.ascontiguousarray(out, self.np_dtype)
-            if len(z) != n.value:
-                raise ValueError("out does not have the length of the operator's sector")
+        z = self._destination(out, n.value, "the operator's sector")
         check(call(*head, _vp(src), _vp(z), int(out is not None), C.byref(has), C.byref(n)))
-        if basis in ("spin_half", "spin"):
-            return z, (new_parts(op, spin, L, nup, 0, basis, twiceS) if op in ("splus", "sminus") else (nup, 0))
-        return z, (new_parts(op, spin, L, nup, ndown, basis) if op in ("c", "cdagger", "splus", "sminus") else (nup, ndown))
+        own = fam.reported(nup, ndown)
+        return z, (new_parts(op, spin, L, *own, basis, twiceS) if op in ("c", "cdagger", "splus", "sminus") else own)
 
     def bench_operator_sum(self, op, spin, weights, L, nup, ndown, warmup=2, iters=10, accumulate=False, basis="hubbard", twiceS=None):
         """(ms per sum, bytes of the byte model: destination written -- and read when accumulating -- plus every source element once) on zeroed vectors"""
-        _obs_basis(basis)
+        fam = _obs_family(basis)
         w = np.asarray(weights, np.complex128).ravel()
         wr, wi = np.ascontiguousarray(w.real), np.ascontiguousarray(w.imag)
         ms, by = C.c_double(), C.c_double()
-        c1, c2 = _obs_counts(basis, nup, ndown, twiceS)
-        call = getattr(self._lib, "lpp_engine_bench_operator_sum" + _OBS_SUFFIX[basis])
-        check(call(self._h, _op_id(op), int(spin), int(L), c1, c2, len(w), _vp(wr), _vp(wi), int(bool(accumulate)), warmup, iters, C.byref(ms), C.byref(by)))
+        c1, c2 = fam.counts(nup, ndown, twiceS)
+        check(fam.entry("lpp_engine_bench_operator_sum")(self._h, _op_id(op), int(spin), int(L), c1, c2, len(w), _vp(wr), _vp(wi), int(bool(accumulate)), warmup, iters,
+                                                         C.byref(ms), C.byref(by)))
         return ms.value, by.value
 
     def weighted_norm2(self, op, weights, spin=0, state=0, basis=None):
         """<phi|phi> of |phi> = sum_r weights[r] * A_r |resident state> (lpp_engine_sum_norm2): the static structure factor at the momentum the weights
         encode; 0.0 where the operator leads to no sector.  No sector engine is needed.  On an f64 engine complex weights are split as in
         spectral_function_weighted: <phi|phi> = <C|C> + <S|S>.  basis="spin": as two_point."""
-        m = self._need_model("weighted_norm2")
-        sb = self._spin_basis("weighted_norm2", basis)
-        if not sb:
-            self._is_heis("weighted_norm2")
-        call = self._obs_call("lpp_engine_sum_norm2", sb)
-        c1, c2 = self._obs_sector(m, sb)
+        fam, L, _, (c1, c2) = self._own_family("weighted_norm2", basis)
+        call = fam.entry("lpp_engine_sum_norm2")
         total = 0.0
-        for _, wr, wi in self._weight_parts(weights, m["L"]):
+        for _, wr, wi in self._weight_parts(weights, L):
             v, has = C.c_double(), C.c_int32()
-            check(call(self._h, int(state), _op_id(op), int(spin), m["L"], c1, c2, len(wr), _vp(wr), _vp(wi), C.byref(v), C.byref(has)))
+            check(call(self._h, int(state), _op_id(op), int(spin), L, c1, c2, len(wr), _vp(wr), _vp(wi), C.byref(v), C.byref(has)))
             total += v.value
         return total
 
@@ -515,44 +487,54 @@ class LanczosEngine:
         is the SUM of its records' continued_fraction.  On a c128 engine, or for real weights, a type is one record with part=None.  A state of
         zero norm (sz at q = 0 in a sector with N_up = N_down) gives a record with weight 0 and no steps; continued_fraction returns 0 for it.
         basis="spin": as two_point; sz is then the true S^z, so S^zz(q,w) comes without the factor 1/4 of the S = 1/2 family's raw sz."""
-        m = self._need_model("spectral_function_weighted")
-        sb = self._spin_basis("spectral_function_weighted", basis)
-        if not sb:
-            self._is_heis("spectral_function_weighted")
-        L, nup, ndown = m["L"], m["nup"], m["ndown"]
-        k1, k2 = self._obs_sector(m, sb)
+        F = _, L, _, counts = self._own_family("spectral_function_weighted", basis)
         _op_id(op)
-        if energy is None:
-            if self._energies is None:
-                raise _capi.LppError(_capi.LPP_ERR_STATE, "spectral_function_weighted: run lanczos() first (after keep_states) or pass energy")
-            energy = float(self._energies[0])
+        energy = self._ground_energy("spectral_function_weighted", energy)
         if self._is_tj() and op in ("splus", "sminus") and spin != _capi.LPP_SPIN_UP:  # before any sector engine is assembled
             raise _capi.LppError(_capi.LPP_ERR_INVALID, "spectral_function_weighted: splus / sminus of the t-J basis take spin UP")
         w = np.asarray(weights, np.complex128).ravel()
-        parts_call = self._obs_call("lpp_obs_new_parts", sb)
-        decomp_call = self._obs_call("lpp_engine_spectral_decomposition_sum", sb)
         solver = dict(max_steps=max_steps, min_steps=min_steps, eps=eps, reortho=reortho, save_vectors=0)
         records = []
         for typ in (0, 1):
             o = op if typ else _TRANSPOSE_CONJUGATE[op]
-            oid = OPERATORS[o]
-            has, c1, c2 = C.c_int32(1), C.c_int32(nup), C.c_int32(ndown)
-            if o not in ("n", "sz"):  # (those stay in the sector, which gets an engine of its own: self keeps its solver parameters)
-                check(parts_call(oid, spin, L, k1, k2, C.byref(has), C.byref(c1), C.byref(c2)))
-            if not has.value:
-                continue
-            n1, n2 = c1.value, c2.value
             s = -1 if typ else 1
-            s2 = 1.0 if o in _FERMIONIC else float(s)
-            for part, wr, wi in self._weight_parts(w if typ else np.conj(w), L):
-                eng = self._sector_engine(n1, n2, solver)
-                a = np.zeros(max_steps + 2)
-                b = np.zeros(max_steps + 2)
-                n, wt, st = C.c_int32(), C.c_double(), Stats()
-                check(decomp_call(self._h, int(state), eng._h, oid, int(spin), L, k1, k2, L, _vp(wr), _vp(wi), C.byref(wt), C.byref(n), _vp(a), _vp(b), C.byref(st)))
-                records.append(dict(type=typ, part=part, label="%d,%d,0,0" % (spin, typ) + ("," + part if part else ""), a=a[:n.value].copy(), b=b[:n.value].copy(), Eg=energy,
-                                    weight=wt.value * s2, sigma=float(-s), modif_norm2=wt.value, steps=n.value, sector=(n1, n2),
-                                    ms_per_step=1e3 * st.seconds_total / max(st.steps_enqueued, 1), assemblies=self.sector_assemblies))
+
+            def runs():
+                return [(dict(type=typ, part=part, label="%d,%d,0,0" % (spin, typ) + ("," + part if part else "")), (int(spin), L, *counts, L, wr, wi))
+                        for part, wr, wi in self._weight_parts(w if typ else np.conj(w), L)]
+            records += self._spectral_type(F, "lpp_engine_spectral_decomposition_sum", o, spin, o in ("n", "sz"), state, energy, solver, s,
+                                           1.0 if o in _FERMIONIC else float(s), runs)
+        return records
+
+    def _ground_energy(self, who, energy):
+        if energy is None:
+            if self._energies is None:
+                raise _capi.LppError(_capi.LPP_ERR_STATE, "%s: run lanczos() first (after keep_states) or pass energy" % who)
+            energy = float(self._energies[0])
+        return energy
+
+    def _spectral_type(self, F, stem, o, spin, stays, state, energy, solver, s, s2, runs):
+        """The records of one type of spectral_function / spectral_function_weighted: operator o on resident state `state`, F from _own_family.  The
+        sector is the operator's new one (none: no records) or, where it `stays`, the state's own, which gets an engine of its own (self keeps its solver
+        parameters).  runs() -> [(the record's first keys, the arguments of the decomposition call `stem` between the operator and its outputs)]: one
+        decomposition on the sector's engine each.  weight = s2 <modif|modif>, sigma = -s (calcSpectral, Engine.h:481-489)."""
+        fam, L, own, (k1, k2) = F
+        oid = OPERATORS[o]
+        has, c1, c2 = C.c_int32(1), C.c_int32(own[0]), C.c_int32(own[1])
+        if not stays:
+            check(fam.entry("lpp_obs_new_parts")(oid, spin, L, k1, k2, C.byref(has), C.byref(c1), C.byref(c2)))
+        if not has.value:
+            return []
+        sector, records = (c1.value, c2.value), []
+        for head, args in runs():
+            eng = self._sector_engine(*sector, solver)
+            a = np.zeros(solver["max_steps"] + 2)
+            b = np.zeros(solver["max_steps"] + 2)
+            n, w, st = C.c_int32(), C.c_double(), Stats()
+            check(fam.entry(stem)(self._h, int(state), eng._h, oid, *(_vp(x) if isinstance(x, np.ndarray) else x for x in args), C.byref(w), C.byref(n), _vp(a), _vp(b),
+                                  C.byref(st)))
+            records.append(dict(head, a=a[:n.value].copy(), b=b[:n.value].copy(), Eg=energy, weight=w.value * s2, sigma=float(-s), modif_norm2=w.value, steps=n.value,
+                                sector=sector, ms_per_step=1e3 * st.seconds_total / max(st.steps_enqueued, 1), assemblies=self.sector_assemblies))
         return records
 
     def spectral_function_k(self, op, q, positions, **kwargs):
@@ -566,13 +548,14 @@ class LanczosEngine:
         """t-J engines: LPP_ERR_INVALID naming the model unless the caller opts into the t-J basis: there sz is n of the given spin, not up minus down,
         and splus ignores its spin, so a Hubbard string carried over would silently mean something else.  Heisenberg engines likewise unless the caller
         opts into the spin basis: there sz is the raw 1 - 2 bit and n reads a spin direction."""
-        _string_basis(basis)
+        fam = _string_family(basis)
         if self._is_tj() and basis != "tj":
             raise _capi.LppError(_capi.LPP_ERR_INVALID, "%s: not for the t-J (TjMultiOrb) model, operator strings are built for the Hubbard product basis; pass "
                                  "basis=\"tj\" for strings in the t-J basis (sz is then n of the given spin, the many-point convention only)" % who)
         if self._is_heis() and basis not in ("spin_half", "tj"):
             raise _capi.LppError(_capi.LPP_ERR_INVALID, "%s: not for the Heisenberg model, operator strings are built for the Hubbard product basis; pass "
                                  "basis=\"spin_half\" for strings of n, sz, splus, sminus in the spin basis (sz is then the raw 1 - 2 bit = -2 S^z)" % who)
+        return fam
 
     def apply_operator_string(self, ops, L, nup, ndown, src, factor=1.0, out=None, convention="many_point", basis="hubbard"):
         """z (+)= factor * (the whole string applied to src) in ONE launch (lpp_engine_apply_string_host): returns (z, (nup', ndown')), z starting from `out`
@@ -580,8 +563,8 @@ class LanczosEngine:
         words of BasisHeisenberg (lpp_engine_apply_string_heis_host; ops as operator_string_plan_heis, nup = szPlusConst, ndown is not read, the
         many-point convention only); a string that is identically zero returns zeros, and LppError is raised where the reference throws.
         basis="tj": the one-orbital t-J basis (lpp_engine_apply_string_tj_host; ops as operator_string_plan_tj, the many-point convention only)."""
-        self._refuse_strings("apply_operator_string", basis)
-        conv, off, o, s, sp, fl = _string_arrays([ops], _string_convention(convention, basis))
+        fam = self._refuse_strings("apply_operator_string", basis)
+        conv, off, o, s, sp, fl = _string_arrays([ops], fam.convention(convention))
         if basis == "spin_half":
             plan = operator_string_plan_heis(ops, L, nup, action=False)
             n, parts = plan["n_dst"], "%d" % plan["szPlusConst"]
@@ -596,17 +579,12 @@ class LanczosEngine:
                 return None, None
             n, parts = len(plan["table_up"]) * len(plan["table_down"]), "%d, %d" % (plan["nup"], plan["ndown"])
         src = np.ascontiguousarray(src, self.np_dtype)
-        if len(src) != sector_size(L, nup, ndown, basis):
+        if len(src) != fam.size(L, nup, ndown):
             raise ValueError("src does not have the length of sector (%d, %d)" % (nup, ndown))
-        if out is None:
-            z = np.zeros(n, self.np_dtype)
-        else:
-            z = np.ascontiguousarray(out, self.np_dtype)
-            if len(z) != n:
-                raise ValueError("out does not have the length of sector (%s)" % parts)
+        z = self._destination(out, n, "sector (%s)" % parts)
         f = complex(factor)
         has, n1, n2 = C.c_int32(), C.c_int32(), C.c_int32()
-        call = getattr(self._lib, "lpp_engine_apply_string" + _OBS_SUFFIX[basis] + "_host")
+        call = fam.entry("lpp_engine_apply_string", host=True)
         check(call(self._h, conv, int(off[-1]), _vp(o), _vp(s), _vp(sp), _vp(fl), L, nup, ndown, f.real, f.imag, _vp(src), _vp(z), int(out is not None), C.byref(has),
                    C.byref(n1), C.byref(n2)))
         return z, (n1.value, n2.value)
@@ -628,28 +606,27 @@ class LanczosEngine:
         spin, splus / sminus take spin 0).  Without it a t-J engine is refused."""
         if basis == "tj" and not self._is_tj():
             raise ValueError("many_point: basis=\"tj\" is for engines set up by assemble_tj")
-        self._refuse_strings("many_point", "hubbard" if basis is None else basis)
-        spin = basis == "spin_half"
-        if spin and not self._is_heis("many_point"):
-            raise _capi.LppError(_capi.LPP_ERR_INVALID, "many_point: basis=\"spin_half\" is for engines set up by assemble_heisenberg (twiceS = 1)")
+        fam = self._refuse_strings("many_point", "hubbard" if basis is None else basis)
+        if basis == "spin_half":
+            if not self._is_heis():
+                raise _capi.LppError(_capi.LPP_ERR_INVALID, "many_point: basis=\"spin_half\" is for engines set up by assemble_heisenberg (twiceS = 1)")
+            self._refuse_higher_spin("many_point")
         m = self._need_model("many_point")
-        conv, off, o, s, sp, fl = _string_arrays(strings, _string_convention(convention, basis))
+        conv, off, o, s, sp, fl = _string_arrays(strings, fam.convention(convention))
         res = np.zeros((len(off) - 1, 2))
-        call = self._lib.lpp_engine_many_point_heis if spin else self._lib.lpp_engine_many_point_tj if basis == "tj" else self._lib.lpp_engine_many_point
-        check(call(self._h, conv, len(off) - 1, _vp(off), _vp(o), _vp(s), _vp(sp), _vp(fl), m["L"], m["nup"], m["ndown"], int(bra), int(ket), _vp(res)))
+        check(fam.entry("lpp_engine_many_point")(self._h, conv, len(off) - 1, _vp(off), _vp(o), _vp(s), _vp(sp), _vp(fl), m["L"], *fam.sector(m), int(bra), int(ket), _vp(res)))
         return self._brackets(res)
 
     def many_point_of(self, strings, L, nup, ndown, bra, ket, convention="many_point", basis="hubbard"):
         """the same for host vectors bra / ket of sector (nup, ndown) in the basis order; the engine needs no matrix.  basis="spin_half": nup = szPlusConst"""
-        self._refuse_strings("many_point_of", basis)
-        conv, off, o, s, sp, fl = _string_arrays(strings, _string_convention(convention, basis))
+        fam = self._refuse_strings("many_point_of", basis)
+        conv, off, o, s, sp, fl = _string_arrays(strings, fam.convention(convention))
         bra = np.ascontiguousarray(bra, self.np_dtype)
         ket = np.ascontiguousarray(ket, self.np_dtype)
-        if len(bra) != sector_size(L, nup, ndown, basis) or len(ket) != len(bra):
+        if len(bra) != fam.size(L, nup, ndown) or len(ket) != len(bra):
             raise ValueError("bra / ket do not have the length of sector (%d, %d)" % (nup, ndown))
         res = np.zeros((len(off) - 1, 2))
-        call = getattr(self._lib, "lpp_engine_many_point" + _OBS_SUFFIX[basis] + "_host")
-        check(call(self._h, conv, len(off) - 1, _vp(off), _vp(o), _vp(s), _vp(sp), _vp(fl), L, nup, ndown, _vp(bra), _vp(ket), _vp(res)))
+        check(fam.entry("lpp_engine_many_point", host=True)(self._h, conv, len(off) - 1, _vp(off), _vp(o), _vp(s), _vp(sp), _vp(fl), L, nup, ndown, _vp(bra), _vp(ket), _vp(res)))
         return self._brackets(res)
 
     def measure(self, ops, bra=0, ket=0):
@@ -661,11 +638,10 @@ class LanczosEngine:
 
     def bench_string_dot(self, strings, L, nup, ndown, warmup=2, iters=10, convention="many_point", basis="hubbard"):
         """(ms per launch, bytes of the byte model) of the bracket kernel + reduction on one batch of 1 .. 8 strings, zeroed vectors"""
-        _string_basis(basis)
-        conv, off, o, s, sp, fl = _string_arrays(strings, _string_convention(convention, basis))
+        fam = _string_family(basis)
+        conv, off, o, s, sp, fl = _string_arrays(strings, fam.convention(convention))
         ms, by = C.c_double(), C.c_double()
-        call = getattr(self._lib, "lpp_engine_bench_string_dot" + _OBS_SUFFIX[basis])
-        check(call(self._h, conv, len(off) - 1, _vp(off), _vp(o), _vp(s), _vp(sp), _vp(fl), L, nup, ndown, warmup, iters, C.byref(ms), C.byref(by)))
+        check(fam.entry("lpp_engine_bench_string_dot")(self._h, conv, len(off) - 1, _vp(off), _vp(o), _vp(s), _vp(sp), _vp(fl), L, nup, ndown, warmup, iters, C.byref(ms), C.byref(by)))
         return ms.value, by.value
 
     # ---- reduced density matrix of the low `split` sites (lpp_rdm.hip) ---------------------------------------
@@ -736,29 +712,19 @@ class LanczosEngine:
         states bra / ket (keep_states before lanczos); -100 everywhere where the operator leads to no sector.
         basis="spin", on an engine set up by assemble_heisenberg with any admitted twiceS: the opt-in digit basis (operator_plan_heis_spin has the
         definition, the project's own: the reference throws for spins above 1/2), <S^z_j S^z_i> for "sz" and <S^-_j S^+_i> for "splus"."""
-        m = self._need_model("two_point")
-        sb = self._spin_basis("two_point", basis)
-        if not sb:
-            self._is_heis("two_point")
-        L = m["L"]
+        fam, L, _, (c1, c2) = self._own_family("two_point", basis)
         res = np.zeros((L, L), self.np_dtype)
         tr = np.zeros(1, self.np_dtype)
-        call = self._obs_call("lpp_engine_two_point", sb)
-        c1, c2 = self._obs_sector(m, sb)
-        check(call(self._h, _op_id(op), int(spins[0]), int(spins[1]), L, c1, c2, int(bra), int(ket), _vp(res), _vp(tr)))
+        check(fam.entry("lpp_engine_two_point")(self._h, _op_id(op), int(spins[0]), int(spins[1]), L, c1, c2, int(bra), int(ket), _vp(res), _vp(tr)))
         return res, tr[0]
 
     def _sector_engine(self, nup, ndown, solver):
         eng = self._sectors.get((nup, ndown))
         if eng is None:
-            m = self._model
             eng = LanczosEngine(**self._ctor)
-            if self._is_tj():
-                eng.assemble_tj(m["L"], nup, ndown, m["hop"], m["jpm"], m["jzz"], m["w"], m["potentialV"])
-            elif self._is_heis():
-                eng.assemble_heisenberg(m["L"], nup, m["jpm"], m["jzz"], field=m["field"], twiceS=m["twiceS"], anisotropy=m["anisotropy"])
-            else:
-                getattr(eng, m["how"])(m["L"], nup, ndown, m["hop"], m["U"], m["V"], ninj=m["ninj"], jcoup=m["jcoup"])
+            replay = {k: v for k, v in self._model.items() if k != "how"}  # what the model's assemble_* / setup_* was given, on the new counts
+            replay.update(zip(_FAMILIES[self._own_basis()].sector_names, (nup, ndown)))
+            getattr(eng, self._model["how"])(**replay)
             self._sectors[(nup, ndown)] = eng
             self.sector_assemblies += 1
         eng.set_solver(**solver)
@@ -772,52 +738,26 @@ class LanczosEngine:
         max_steps .. reortho: ParametersForSolver(io, "Spectral").  energy: Eg, default the lowest eigenvalue of the last lanczos().
         basis="spin": as two_point; the sector engines are assembled with the model's twiceS and anisotropy on szPlusConst +- 1 (sz: the state's own
         sector, on a sector engine of its own)."""
-        m = self._need_model("spectral_function")
-        sb = self._spin_basis("spectral_function", basis)
-        heis = sb or self._is_heis("spectral_function")
-        L, nup, ndown = m["L"], m["nup"], m["ndown"]
-        k1, k2 = self._obs_sector(m, sb)
+        F = fam, L, _, counts = self._own_family("spectral_function", basis)
+        heis = len(fam.sector_names) == 1  # (needsNewBasis() is false for n and sz, the new basis is the model's own)
         _op_id(op)
-        if op in ("n", "sz") and not heis:  # before any sector engine is assembled (Heisenberg: needsNewBasis() is false, the new basis is the model's own)
+        if op in ("n", "sz") and not heis:  # before any sector engine is assembled
             raise _capi.LppError(_capi.LPP_ERR_INVALID, "spectral_function: operators that stay in the sector (n, sz) are not supported")
-        if energy is None:
-            if self._energies is None:
-                raise _capi.LppError(_capi.LPP_ERR_STATE, "spectral_function: run lanczos() first (after keep_states) or pass energy")
-            energy = float(self._energies[0])
-        op2 = _TRANSPOSE_CONJUGATE[op]
+        energy = self._ground_energy("spectral_function", energy)
         diagonal = isite == jsite
-        tj = self._is_tj()
-        parts_call = self._obs_call("lpp_obs_new_parts", sb)
-        decomp_call = self._obs_call("lpp_engine_spectral_decomposition", sb)
-        if tj and op in ("splus", "sminus") and spin != _capi.LPP_SPIN_UP:  # before any sector engine is assembled
+        if self._is_tj() and op in ("splus", "sminus") and spin != _capi.LPP_SPIN_UP:  # before any sector engine is assembled
             raise _capi.LppError(_capi.LPP_ERR_INVALID, "spectral_function: splus / sminus of the t-J basis take spin UP (the reference ranks words outside the basis otherwise)")
         solver = dict(max_steps=max_steps, min_steps=min_steps, eps=eps, reortho=reortho, save_vectors=0)
         records = []
-        for typ in range(4):  # LabeledOperator::numberOfTypes
-            if diagonal and typ > 1:
-                continue
-            o = op if (typ & 1) else op2
-            oid = OPERATORS[o]
-            has, c1, c2 = C.c_int32(1), C.c_int32(nup), C.c_int32(ndown)
-            if not (heis and o in ("n", "sz")):  # (those stay in the sector, which gets an engine of its own: self keeps its solver parameters)
-                check(parts_call(oid, spin, L, k1, k2, C.byref(has), C.byref(c1), C.byref(c2)))
-            if not has.value:
-                continue
-            n1, n2 = c1.value, c2.value
-            eng = self._sector_engine(n1, n2, solver)
-            a = np.zeros(max_steps + 2)
-            b = np.zeros(max_steps + 2)
-            n, w, st = C.c_int32(), C.c_double(), Stats()
-            isign = -1.0 if typ > 1 else 1.0
-            check(decomp_call(self._h, int(state), eng._h, oid, isite, jsite, spin, isign, L, k1, k2, C.byref(w), C.byref(n), _vp(a), _vp(b), C.byref(st)))
-            s = -1 if (typ & 1) else 1  # calcSpectral, Engine.h:481-489
+        for typ in range(2 if diagonal else 4):  # LabeledOperator::numberOfTypes; a diagonal pair has the first two
+            o = op if (typ & 1) else _TRANSPOSE_CONJUGATE[op]
+            s = -1 if (typ & 1) else 1
             s2 = -1.0 if typ > 1 else 1.0
             if o not in _FERMIONIC:
                 s2 *= s
             s2 *= 1.0 if diagonal else 0.5
-            records.append(dict(type=typ, label="%d,%d,0,0" % (spin, typ), a=a[:n.value].copy(), b=b[:n.value].copy(), Eg=energy, weight=w.value * s2,
-                                sigma=float(-s), modif_norm2=w.value, steps=n.value, sector=(n1, n2),
-                                ms_per_step=1e3 * st.seconds_total / max(st.steps_enqueued, 1), assemblies=self.sector_assemblies))
+            records += self._spectral_type(F, "lpp_engine_spectral_decomposition", o, spin, heis and o in ("n", "sz"), state, energy, solver, s, s2,
+                                           lambda: [(dict(type=typ, label="%d,%d,0,0" % (spin, typ)), (isite, jsite, spin, -1.0 if typ > 1 else 1.0, L, *counts))])
         return records
 
 
@@ -842,7 +782,6 @@ def rdm_plan(L, nup, ndown, split, basis="hubbard"):
     k_up, k_down, dim_up, dim_down, dim, env_up, env_down, terms = env_up * env_down, offset, alpha = the alpha word of every row), `total`
     (packed elements), `states` (the sector's size) and `starts_up` / `starts_down`: {k: run-start ranks of the environment words, ascending}.
     basis "spin_half": nup = number of set bits, ndown is ignored."""
-    from math import comb
     lib = _capi.lib()
     bid = _basis_id(basis)
     nb, tot, rows, nsu, nsd = C.c_int32(), C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
@@ -886,41 +825,92 @@ def _rdm_dense(blocks, plan, dtype):
     return out
 
 
-OBS_BASES = ("hubbard", "tj", "spin_half", "spin")
-_OBS_SUFFIX = {"hubbard": "", "tj": "_tj", "spin_half": "_heis", "spin": "_heis_spin"}  # of the C entry points
+# ---- the observable families: everything above and below that depends on the basis asks one row of this table ----
+class _Family(namedtuple("_Family", "name suffix counts size plan conventions sector_names assemble")):
+    """name: the `basis` argument.  suffix: of the family's C entry points.  counts(nup, ndown, twiceS): the two counts those take.  size(L, *counts):
+    states of the sector.  plan(lib, head, has, n1, n2, nu, nd, lb): the family's lpp_obs_plan* call without tables, head = (op, site, spin, L, *counts).
+    conventions: of its operator strings, () where it has none.  sector_names: the arguments of its assemble_* that name the sector; with one name a
+    sector is reported as (count, 0).  assemble: the LanczosEngine methods that make an engine of the family."""
+    __slots__ = ()
+
+    def entry(self, stem, host=False):
+        """the family's C entry point of that stem, e.g. lpp_engine_apply_operator_tj_host"""
+        return getattr(_capi.lib(), stem + self.suffix + ("_host" if host else ""))
+
+    def reported(self, nup, ndown):
+        return (nup, ndown) if len(self.sector_names) == 2 else (nup, 0)
+
+    def sector(self, model):
+        """the sector of a recorded model (LanczosEngine._set_model), as reported"""
+        return self.reported(*(tuple(model[k] for k in self.sector_names) + (0,))[:2])
+
+    def one_site_plan(self, op, site, spin, L, c1, c2):
+        """(has, the new sector as reported, n_dst) of one operator application"""
+        has, n1, n2, lb, nu, nd = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64(1), C.c_int64()
+        check(self.plan(_capi.lib(), (op, site, spin, L, c1, c2), *(C.byref(x) for x in (has, n1, n2, nu, nd, lb))))
+        return bool(has.value), (n1.value, n2.value), nu.value * nd.value
+
+    def convention(self, convention):
+        """the convention as given; the spin and t-J bases have the many-point one only (RahulOperator's labels are per fermion species, and on the t-J
+        basis it is not restated)"""
+        if self.conventions == ("many_point",) and convention != "many_point":
+            raise ValueError("basis=\"%s\" has convention=\"many_point\" only, not %r" % (self.name, convention))
+        return convention
 
 
-def _obs_basis(basis):
-    """True for the t-J basis"""
-    if basis not in OBS_BASES:
-        raise ValueError("unsupported basis %r (one of %s)" % (basis, ", ".join(OBS_BASES)))
-    return basis == "tj"
+def _two_counts(nup, ndown, twiceS):
+    return int(nup), int(ndown)
 
 
-def _obs_counts(basis, nup, ndown, twiceS):
-    """the two counts as the entry points of the basis take them: (nup, ndown); basis="spin": (twiceS, szPlusConst = nup), and twiceS is required"""
-    if basis != "spin":
-        return int(nup), int(ndown)
+def _spin_counts(nup, ndown, twiceS):
+    """(twiceS, szPlusConst = nup), and twiceS is required"""
     if twiceS is None:
         raise ValueError("basis=\"spin\" needs twiceS")
     return int(twiceS), int(nup)
 
 
+def _digit_words(L, t, m):
+    """the words of L digits 0 .. t whose digits add up to m"""
+    count = [1] + [0] * (L * t)  # strings of no digit
+    for _ in range(L):
+        count = [sum(count[max(0, s - t):s + 1]) for s in range(L * t + 1)]
+    return count[m] if 0 <= m <= L * t else 0
+
+
+_FAMILIES = {f.name: f for f in (
+    _Family(name="hubbard", suffix="", counts=_two_counts, size=lambda L, nup, ndown: comb(L, nup) * comb(L, ndown),
+            plan=lambda lib, head, has, n1, n2, nu, nd, lb: lib.lpp_obs_plan(*head, has, n1, n2, nu, nd, None, None),
+            conventions=("many_point", "measure"), sector_names=("nup", "ndown"), assemble=("assemble_hubbard", "setup_hubbard_onthefly")),
+    _Family(name="tj", suffix="_tj", counts=_two_counts, size=lambda L, nup, ndown: comb(L, ndown) * comb(L - ndown, nup) if nup + ndown <= L else 0,
+            plan=lambda lib, head, has, n1, n2, nu, nd, lb: lib.lpp_obs_plan_tj(*head, has, n1, n2, nd, None),
+            conventions=("many_point",), sector_names=("nup", "ndown"), assemble=("assemble_tj",)),
+    _Family(name="spin_half", suffix="_heis", counts=_two_counts, size=lambda L, nup, ndown: comb(L, nup),
+            plan=lambda lib, head, has, n1, n2, nu, nd, lb: lib.lpp_obs_plan_heis(*head, has, n1, n2, nd, lb, None),
+            conventions=("many_point",), sector_names=("szPlusConst",), assemble=("assemble_heisenberg",)),
+    # the opt-in digit basis of a Heisenberg engine of any admitted spin (an engine's own family is the FIRST row that names its assemble method)
+    _Family(name="spin", suffix="_heis_spin", counts=_spin_counts, size=_digit_words,
+            plan=lambda lib, head, has, n1, n2, nu, nd, lb: lib.lpp_obs_plan_heis_spin(*head, has, n1, nd, lb, None, None),
+            conventions=(), sector_names=("szPlusConst",), assemble=("assemble_heisenberg",)))}
+OBS_BASES = tuple(_FAMILIES)
+STRING_BASES = tuple(sorted(b for b, f in _FAMILIES.items() if f.conventions))
+
+
+def _obs_family(basis):
+    if basis not in OBS_BASES:
+        raise ValueError("unsupported basis %r (one of %s)" % (basis, ", ".join(OBS_BASES)))
+    return _FAMILIES[basis]
+
+
+def _string_family(basis):
+    if basis not in STRING_BASES:
+        raise ValueError("unsupported basis %r for operator strings (one of %s)" % (basis, ", ".join(STRING_BASES)))
+    return _FAMILIES[basis]
+
+
 def sector_size(L, nup, ndown, basis="hubbard", twiceS=None):
     """states of the sector; basis="spin" (twiceS=...): the words of L digits 0 .. twiceS whose digits add up to nup = szPlusConst"""
-    from math import comb
-    if _obs_basis(basis):
-        return comb(L, ndown) * comb(L - ndown, nup) if nup + ndown <= L else 0
-    if basis == "spin":
-        t, m = _obs_counts(basis, nup, ndown, twiceS)
-        count = [1] + [0] * (L * t)  # strings of no digit
-        for _ in range(L):
-            count = [sum(count[max(0, s - t):s + 1]) for s in range(L * t + 1)]
-        return count[m] if 0 <= m <= L * t else 0
-    if basis == "spin_half":
-        return comb(L, nup)
-    return comb(L, nup) * comb(L, ndown)
-
+    fam = _obs_family(basis)
+    return fam.size(L, *fam.counts(nup, ndown, twiceS))
 
 def new_parts(op, spin, L, nup, ndown, basis="hubbard", twiceS=None):
     """HubbardOneOrbital::hasNewParts (basis="tj": TjMultiOrb::hasNewParts, basis="spin_half": Heisenberg::hasNewParts with nup = szPlusConst, the new
@@ -928,10 +918,9 @@ def new_parts(op, spin, L, nup, ndown, basis="hubbard", twiceS=None):
     sz, for the Heisenberg model c, cdagger, S+ on all ups and S- on all downs).  basis="spin" with twiceS=...: the digit basis of any admitted spin,
     nup = szPlusConst, the new sector as (szPlusConst', 0); LPP_ERR_INVALID for n, c, cdagger, S+ on the top sector and S- on szPlusConst = 0."""
     has, n1, n2 = C.c_int32(), C.c_int32(), C.c_int32()
-    _obs_basis(basis)
-    c1, c2 = _obs_counts(basis, nup, ndown, twiceS)
-    call = getattr(_capi.lib(), "lpp_obs_new_parts" + _OBS_SUFFIX[basis])
-    check(call(_op_id(op), spin, L, c1, c2, C.byref(has), C.byref(n1), C.byref(n2)))
+    fam = _obs_family(basis)
+    c1, c2 = fam.counts(nup, ndown, twiceS)
+    check(fam.entry("lpp_obs_new_parts")(_op_id(op), spin, L, c1, c2, C.byref(has), C.byref(n1), C.byref(n2)))
     return (n1.value, n2.value) if has.value else None
 
 
@@ -1064,22 +1053,6 @@ def _string_arrays(strings, convention):
     pad = [0] if not ops else []  # (a valid pointer for an empty list)
     return (conv, np.array(off, np.int64), np.array(ops + pad, np.int32), np.array(sites + pad, np.int32), np.array(spins + pad, np.int32),
             np.array(flags + pad, np.int32))
-
-
-STRING_BASES = ("hubbard", "spin_half", "tj")
-
-
-def _string_basis(basis):
-    if basis not in STRING_BASES:
-        raise ValueError("unsupported basis %r for operator strings (one of %s)" % (basis, ", ".join(STRING_BASES)))
-
-
-def _string_convention(convention, basis):
-    """the convention as given; the spin basis has the many-point one only (RahulOperator's labels are per fermion species), and so has the t-J basis
-    (RahulOperator on it is not restated)"""
-    if basis in ("spin_half", "tj") and convention != "many_point":
-        raise ValueError("basis=\"%s\" has convention=\"many_point\" only, not %r" % (basis, convention))
-    return convention
 
 
 def operator_string_plan_tj(ops, L, nup, ndown, action=True):

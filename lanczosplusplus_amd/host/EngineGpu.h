@@ -470,7 +470,7 @@ public:
 	typedef LanczosSolver<ParametersForSolverType, InternalProductType, VectorType> LanczosSolverType;
 	typedef typename LanczosSolverType::TridiagonalMatrixType TridiagonalMatrixType;
 
-	Engine(const ModelType& model, LppHost::InputReadable& io, int device = 0) : model_(model), io_(io), device_(device)
+	Engine(const ModelType& model, LppHost::InputReadable& io, int device = 0) : model_(model), io_(io), device_(device), fam_(resolveFamily())
 	{
 		SizeType excited = 0;
 		if (io_.has("Excited=")) io_.readline(excited, "Excited=");
@@ -508,12 +508,11 @@ public:
 		checkBraOrKet("ket", braAndKet.second);
 		const SizeType total = model_.geometry().numberOfSites();
 		if (result.n_row() != total || result.n_col() != total) result.resize(total, total);
-		const PairType parts = obsParts();
 		std::vector<ComplexOrRealType> flat(total * total);
 		ComplexOrRealType sum = 0;
 		std::cout << "orbs=" << orbs.first << " " << orbs.second << "\n";
-		lppCheck((heisSpinModel() ? lpp_engine_two_point_heis_spin : heisModel() ? lpp_engine_two_point_heis : tjModel() ? lpp_engine_two_point_tj : lpp_engine_two_point)(e, lOperator.id(), (int32_t)spins.first, (int32_t)spins.second, (int32_t)total, (int32_t)parts.first, (int32_t)parts.second,
-		                                                                      (int32_t)braAndKet.first, (int32_t)braAndKet.second, flat.data(), &sum));
+		lppCheck(fam_.two_point(e, lOperator.id(), (int32_t)spins.first, (int32_t)spins.second, (int32_t)total, (int32_t)fam_.parts.first, (int32_t)fam_.parts.second,
+		                        (int32_t)braAndKet.first, (int32_t)braAndKet.second, flat.data(), &sum));
 		for (SizeType i = 0; i < total; i++)
 			for (SizeType j = 0; j < total; j++) result(i, j) = flat[i * total + j];
 		std::cout << "MatrixDiagonal = " << sum << "\n";
@@ -525,9 +524,9 @@ public:
 	// accModifiedState_ through the sectors of hasNewParts; 0 where a step leads to no sector or the string ends in another sector.  The whole string
 	// is ONE pass of the bracket kernel (lpp_engine_many_point), no intermediate vector.  n and sz act in the sector the string has reached (the
 	// reference's getNeededBasis hands them the original sector's basis, ill-defined once the string has left it).  Orbital 0 only.
-	// Model=Heisenberg with HeisenbergTwiceS=1: the same through lpp_engine_many_point_heis -- n, sz, splus, sminus as BasisHeisenberg::getBraIndex has them
+	// Model=Heisenberg with HeisenbergTwiceS=1: the same through the S = 1/2 family's many-point call -- n, sz, splus, sminus as BasisHeisenberg::getBraIndex has them
 	// (sz is the raw 1 - 2 bit); where the reference throws (c / cdagger, S+ met in the all-up sector, S- in the all-down one) LPP_ERR_INVALID is thrown.
-	// Model=TjMultiOrb with Orbitals=1 and the SolverOptions token TjOperatorStrings: the same through lpp_engine_many_point_tj -- the operators as
+	// Model=TjMultiOrb with Orbitals=1 and the SolverOptions token TjOperatorStrings: the same through the t-J family's many-point call -- the operators as
 	// BasisTjMultiOrbLanczos::getBraIndex has them (sz is n of the given spin); without the token the model is refused by its name.
 	ComplexOrRealType manyPoint(const VectorSizeType& sites, const std::vector<LabeledOperatorType>& what, const VectorSizeType& spins, const VectorSizeType& orbs,
 	                            const PairType& braAndKet) const
@@ -614,45 +613,27 @@ public:
 	void spectralFunction(ContinuedFractionCollectionType& cfCollection, VectorStringType& vstr, const LabeledOperatorType& lOperator1, int isite, int jsite,
 	                      const PairType& spins, const PairType& orbs) const
 	{
-		typedef typename ContinuedFractionCollectionType::ContinuedFractionType ContinuedFractionType;
 		if (spins.first != spins.second) throw std::runtime_error("spectralFunction: no support yet for off-diagonal spin\n");
 		if (orbs.first != 0 || orbs.second != 0) throw std::runtime_error("spectralFunction: one orbital only\n");
 		lpp_engine* e = observableEngine("spectralFunction");
 		const LabeledOperatorType lOperator2 = lOperator1.transposeConjugate();
 		// refused before any sector engine is assembled; the Heisenberg model decomposes them in its own sector (needsNewBasis() is false, Engine.h:172-174)
-		if (!lOperator1.needsNewBasis() && !heisModel() && !heisSpinModel()) throw std::runtime_error("spectralFunction: operators that stay in the sector (n, sz) are not supported\n");
+		if (!lOperator1.needsNewBasis() && !fam_.heis) throw std::runtime_error("spectralFunction: operators that stay in the sector (n, sz) are not supported\n");
 		const int n = (int)model_.geometry().numberOfSites();
 		if (isite < 0 || jsite < 0 || isite >= n || jsite >= n) throw std::runtime_error("spectralFunction: site out of range\n");
 		const bool isDiagonal = (isite == jsite);
-		const PairType oldParts = obsParts();
+		const int32_t spin = (int32_t)spins.first, nup = (int32_t)fam_.parts.first, ndown = (int32_t)fam_.parts.second;
 		ParametersForSolverType params(io_, "Spectral");
 		for (SizeType type = 0; type < lOperator1.numberOfTypes(); ++type) {
 			if (isDiagonal && type > 1) continue;
 			const LabeledOperatorType& lOperator = (type & 1) ? lOperator1 : lOperator2;
-			int32_t has = 1, nup2 = (int32_t)ownSector().first, ndown2 = (int32_t)ownSector().second;
-			if (lOperator.needsNewBasis())
-				lppCheck((heisSpinModel() ? lpp_obs_new_parts_heis_spin : heisModel() ? lpp_obs_new_parts_heis : tjModel() ? lpp_obs_new_parts_tj : lpp_obs_new_parts)(lOperator.id(), (int32_t)spins.first, n, (int32_t)oldParts.first,
-				                                                                                                      (int32_t)oldParts.second, &has, &nup2, &ndown2));
-			if (!has) continue;
-			lpp_engine* sector = sectorEngine(nup2, ndown2, params);
-			TridiagonalMatrixType ab;
-			ab.resize(params.steps + 2);
-			double weight = 0;
-			int32_t nsteps = 0;
-			lppCheck((heisSpinModel() ? lpp_engine_spectral_decomposition_heis_spin : heisModel() ? lpp_engine_spectral_decomposition_heis : tjModel() ? lpp_engine_spectral_decomposition_tj : lpp_engine_spectral_decomposition)(e, 0, sector, lOperator.id(), isite, jsite, (int32_t)spins.first,
-			                                                                                                type > 1 ? -1.0 : 1.0, n, (int32_t)oldParts.first, (int32_t)oldParts.second,
-			                                                                                                &weight, &nsteps, &ab.a(0), &ab.b(0), nullptr));
-			ab.a_.resize(nsteps);
-			ab.b_.resize(nsteps);
-			if (std::sqrt(weight) < 1e-10) std::cerr << "spectralFunction: modifVector==0, type=" << type << "\n";
-			const int s = (type & 1) ? -1 : 1; // calcSpectral, Engine.h:481-489
-			RealType s2 = (type > 1) ? -1 : 1;
-			if (!lOperator.isFermionic()) s2 *= s;
-			s2 *= isDiagonal ? 1 : 0.5;
-			ContinuedFractionType cf;
-			cf.set(ab, energies_[0], weight * s2, -s);
-			vstr.push_back(std::to_string(spins.first) + "," + std::to_string(type) + "," + std::to_string(orbs.first) + "," + std::to_string(orbs.second));
-			cfCollection.push(cf);
+			int32_t nup2 = 0, ndown2 = 0;
+			if (!newSector(lOperator, spin, n, nup2, ndown2)) continue;
+			decomposeAndPush(cfCollection, vstr, "spectralFunction", lOperator, type, ((type > 1) ? -1 : 1) * (isDiagonal ? 1 : 0.5),
+			                 std::to_string(spins.first) + "," + std::to_string(type) + "," + std::to_string(orbs.first) + "," + std::to_string(orbs.second), nup2, ndown2, params,
+			                 [&](lpp_engine* sector, double* weight, int32_t* nsteps, double* a, double* b) {
+				                 return fam_.spectral_decomposition(e, 0, sector, lOperator.id(), isite, jsite, spin, type > 1 ? -1.0 : 1.0, n, nup, ndown, weight, nsteps, a, b, nullptr);
+			                 });
 		}
 	}
 
@@ -666,12 +647,11 @@ public:
 	void spectralFunctionWeighted(ContinuedFractionCollectionType& cfCollection, VectorStringType& vstr, const LabeledOperatorType& lOperator1,
 	                              const std::vector<std::complex<double>>& weights, const std::vector<PairType>& spins) const
 	{
-		typedef typename ContinuedFractionCollectionType::ContinuedFractionType ContinuedFractionType;
 		lpp_engine* e = observableEngine("spectralFunctionWeighted");
 		const int n = (int)model_.geometry().numberOfSites();
 		if ((int)weights.size() != n) throw std::runtime_error("spectralFunctionWeighted: one weight per site\n");
 		const LabeledOperatorType lOperator2 = lOperator1.transposeConjugate();
-		const PairType oldParts = obsParts();
+		const int32_t nup = (int32_t)fam_.parts.first, ndown = (int32_t)fam_.parts.second;
 		const bool isReal = std::is_same<ComplexOrRealType, double>::value;
 		ParametersForSolverType params(io_, "Spectral");
 		for (SizeType si = 0; si < spins.size(); si++) {
@@ -679,11 +659,8 @@ public:
 			const int32_t spin = (int32_t)spins[si].first;
 			for (SizeType type = 0; type < 2; ++type) {
 				const LabeledOperatorType& lOperator = (type & 1) ? lOperator1 : lOperator2;
-				int32_t has = 1, nup2 = (int32_t)ownSector().first, ndown2 = (int32_t)ownSector().second;
-				if (lOperator.needsNewBasis())
-					lppCheck((heisSpinModel() ? lpp_obs_new_parts_heis_spin : heisModel() ? lpp_obs_new_parts_heis : tjModel() ? lpp_obs_new_parts_tj : lpp_obs_new_parts)(lOperator.id(), spin, n, (int32_t)oldParts.first,
-					                                                                                                      (int32_t)oldParts.second, &has, &nup2, &ndown2));
-				if (!has) continue;
+				int32_t nup2 = 0, ndown2 = 0;
+				if (!newSector(lOperator, spin, n, nup2, ndown2)) continue;
 				std::vector<double> wr((size_t)n), wi((size_t)n);
 				bool anyIm = false;
 				for (int r = 0; r < n; r++) {
@@ -695,22 +672,11 @@ public:
 				for (int part = 0; part < (split ? 2 : 1); part++) {
 					std::vector<double> pr = (split && part == 1) ? wi : wr, pi = split ? std::vector<double>((size_t)n, 0.0) : wi;
 					if (split && std::all_of(pr.begin(), pr.end(), [](double v) { return v == 0.0; })) continue;
-					lpp_engine* sector = sectorEngine(nup2, ndown2, params);
-					TridiagonalMatrixType ab;
-					ab.resize(params.steps + 2);
-					double weight = 0;
-					int32_t nsteps = 0;
-					lppCheck((heisSpinModel() ? lpp_engine_spectral_decomposition_sum_heis_spin : heisModel() ? lpp_engine_spectral_decomposition_sum_heis : tjModel() ? lpp_engine_spectral_decomposition_sum_tj : lpp_engine_spectral_decomposition_sum)(
-					    e, 0, sector, lOperator.id(), spin, n, (int32_t)oldParts.first, (int32_t)oldParts.second, n, pr.data(), pi.data(), &weight, &nsteps, &ab.a(0), &ab.b(0), nullptr));
-					ab.a_.resize(nsteps);
-					ab.b_.resize(nsteps);
-					if (std::sqrt(weight) < 1e-10) std::cerr << "spectralFunctionWeighted: modifVector==0, type=" << type << "\n";
-					const int s = (type & 1) ? -1 : 1;
-					const RealType s2 = lOperator.isFermionic() ? 1 : s;
-					ContinuedFractionType cf;
-					cf.set(ab, energies_[0], weight * s2, -s);
-					vstr.push_back(std::to_string(spin) + "," + std::to_string(type) + ",0,0" + (split ? (part ? ",im" : ",re") : ""));
-					cfCollection.push(cf);
+					decomposeAndPush(cfCollection, vstr, "spectralFunctionWeighted", lOperator, type, 1,
+					                 std::to_string(spin) + "," + std::to_string(type) + ",0,0" + (split ? (part ? ",im" : ",re") : ""), nup2, ndown2, params,
+					                 [&](lpp_engine* sector, double* weight, int32_t* nsteps, double* a, double* b) {
+						                 return fam_.spectral_decomposition_sum(e, 0, sector, lOperator.id(), spin, n, nup, ndown, n, pr.data(), pi.data(), weight, nsteps, a, b, nullptr);
+					                 });
 				}
 			}
 		}
@@ -760,13 +726,86 @@ private:
 		if (ind >= vectors_.size()) throw std::runtime_error(std::string("Engine: ") + what + " index exceeds the states computed (Excited=)\n");
 	}
 
-	// the GPU engine that holds the resident states: the Hubbard family or (unless hubbardOnly) the one-orbital t-J model or the S = 1/2 Heisenberg model
+	// The observable family of the model: which C entry points its resident states go through, with which counts, and the model as sectorEngine reads it.
+	// resolveFamily() fills it once, in the constructor: the model and the input are held by reference for the engine's lifetime and nothing in this class
+	// changes either.  A further family is one more branch there.
+	struct Family {
+		decltype(&lpp_engine_two_point) two_point = nullptr; // null: the model has no observables here
+		decltype(&lpp_obs_new_parts) new_parts = nullptr;
+		decltype(&lpp_engine_spectral_decomposition) spectral_decomposition = nullptr;
+		decltype(&lpp_engine_spectral_decomposition_sum) spectral_decomposition_sum = nullptr;
+		decltype(&lpp_engine_many_point) many_point = nullptr; // null: the family has no operator strings
+		decltype(&lpp_engine_keep_states) keep_states = lpp_engine_keep_states;
+		PairType parts; // the sector as the entry points take it: (nup, ndown); Heisenberg (szPlusConst, 0); the spin-S digit basis (twiceS, szPlusConst)
+		PairType ownSector; // the key of the resident states' own sector among the sector engines: parts; the spin-S digit basis (szPlusConst, 0), as its new sectors
+		// the model (one of the three is set)
+		const HubbardOneOrbital<ComplexOrRealType>* hubbard = nullptr;
+		const TjMultiOrb<ComplexOrRealType>* tj = nullptr; // (Orbitals=1: the only one the shim builds)
+		const Heisenberg<ComplexOrRealType>* heis = nullptr;
+		bool spinS = false; // heis in the spin-S digit basis: sector engines come from the any-spin assembler
+		bool tjStrings = false; // the input's opt-in for operator strings of the t-J basis (the reference's InputCheck is permissive, so such an input stays valid for it)
+	};
+
+	Family resolveFamily() const
+	{
+		Family f;
+		const Heisenberg<ComplexOrRealType>* hs = dynamic_cast<const Heisenberg<ComplexOrRealType>*>(&model_);
+		if (hs && solverOption("HeisenbergSpinObservables")) {
+			// The input's opt-in for the observables of the spin-S digit basis: a Model=Heisenberg input of any spin the assembler admits, AnisotropyD included
+			// (the project's own definition -- the reference throws for spins above 1/2 --, sz is the true S^z; the reference's InputCheck is permissive,
+			// so such an input stays valid for it).  Without the token every input behaves as before.
+			f.heis = hs;
+			f.spinS = true;
+			f.two_point = lpp_engine_two_point_heis_spin;
+			f.new_parts = lpp_obs_new_parts_heis_spin;
+			f.spectral_decomposition = lpp_engine_spectral_decomposition_heis_spin;
+			f.spectral_decomposition_sum = lpp_engine_spectral_decomposition_sum_heis_spin;
+		} else if (hs && hs->twiceTheSpin() == 1 && hs->anisotropy.empty()) {
+			// S = 1/2 only: the reference throws for higher spins (BasisHeisenberg.h:130, Heisenberg.h:223).  An input with AnisotropyD is not admitted here yet:
+			// its sector engines would come from the any-spin assembler, and no driver test covers that (the Python layer does both, and is tested)
+			f.heis = hs;
+			f.two_point = lpp_engine_two_point_heis;
+			f.new_parts = lpp_obs_new_parts_heis;
+			f.spectral_decomposition = lpp_engine_spectral_decomposition_heis;
+			f.spectral_decomposition_sum = lpp_engine_spectral_decomposition_sum_heis;
+			f.many_point = lpp_engine_many_point_heis;
+		} else if ((f.tj = dynamic_cast<const TjMultiOrb<ComplexOrRealType>*>(&model_))) {
+			f.tjStrings = solverOption("TjOperatorStrings");
+			f.two_point = lpp_engine_two_point_tj;
+			f.new_parts = lpp_obs_new_parts_tj;
+			f.spectral_decomposition = lpp_engine_spectral_decomposition_tj;
+			f.spectral_decomposition_sum = lpp_engine_spectral_decomposition_sum_tj;
+			f.many_point = lpp_engine_many_point_tj;
+			f.keep_states = lpp_engine_keep_states_tj; // (a t-J matrix may be held in the hole-major form, which only this call lets keep its states)
+		} else if ((f.hubbard = dynamic_cast<const HubbardOneOrbital<ComplexOrRealType>*>(&model_))) {
+			f.two_point = lpp_engine_two_point;
+			f.new_parts = lpp_obs_new_parts;
+			f.spectral_decomposition = lpp_engine_spectral_decomposition;
+			f.spectral_decomposition_sum = lpp_engine_spectral_decomposition_sum;
+			f.many_point = lpp_engine_many_point;
+		}
+		if (f.two_point) {
+			const typename ModelType::BasisBaseType::PairIntType parts = model_.basis().parts(); // (the Heisenberg model's are (twiceS, szPlusConst))
+			f.parts = (f.heis && !f.spinS) ? PairType(parts.second, 0) : PairType(parts.first, parts.second);
+			f.ownSector = f.heis ? PairType(parts.second, 0) : f.parts;
+		}
+		return f;
+	}
+
+	bool solverOption(const char* token) const
+	{
+		LppHost::String options("none");
+		if (io_.has("SolverOptions=")) io_.readline(options, "SolverOptions=");
+		return options.find(token) != LppHost::String::npos;
+	}
+
+	// the GPU engine that holds the resident states: the Hubbard family or (unless hubbardOnly) the one-orbital t-J model or the Heisenberg model
 	// on one GPU, a one-sector symmetry, states from the device solver
 	lpp_engine* observableEngine(const char* who, bool hubbardOnly = false) const
 	{
-		if (hubbardOnly && !hubbard())
+		if (hubbardOnly && !fam_.hubbard)
 			throw std::runtime_error(std::string(who) + ": needs a Model of the HubbardOneOrbital family solved by the GPU Lanczos (no symmetry sectors, no dense fallback)\n");
-		if (!(hubbard() || tjModel() || heisModel() || heisSpinModel()) || !hamiltonian_ || !statesResident_)
+		if (!fam_.two_point || !hamiltonian_ || !statesResident_)
 			throw std::runtime_error(std::string(who) + ": needs a Model of the HubbardOneOrbital family, TjMultiOrb with Orbitals=1 or Heisenberg with HeisenbergTwiceS=1 and no AnisotropyD (any spin and AnisotropyD with SolverOptions=...,HeisenbergSpinObservables) solved by the GPU Lanczos (no symmetry sectors, no dense fallback)\n");
 		return hamiltonian_->engine();
 	}
@@ -777,34 +816,23 @@ private:
 	lpp_engine* stringEngine(const char* who, bool manyPointOk = false) const
 	{
 		lpp_engine* e = observableEngine(who);
-		if (tjModel() && !(manyPointOk && tjStrings()))
+		if (fam_.tj && !(manyPointOk && fam_.tjStrings))
 			throw std::runtime_error(std::string("LPP_ERR_INVALID: ") + who + ": not for the TjMultiOrb model, operator strings are built for the Hubbard product basis"
 			                         + (manyPointOk ? "; SolverOptions=...,TjOperatorStrings opts into strings of the t-J basis (sz is then n of the given spin)\n" : "\n"));
-		if (heisSpinModel())
+		if (fam_.spinS)
 			throw std::runtime_error(std::string("LPP_ERR_INVALID: ") + who + ": operator strings are not built for the spin-S digit basis (HeisenbergSpinObservables)\n");
-		if (heisModel() && !manyPointOk)
+		if (fam_.heis && !manyPointOk)
 			throw std::runtime_error(std::string("LPP_ERR_INVALID: ") + who + ": not for the Heisenberg model, operator strings are built for the Hubbard product basis\n");
 		return e;
-	}
-
-	// the input's opt-in for operator strings of the t-J basis (the reference's InputCheck is permissive, so such an input stays valid for it)
-	bool tjStrings() const { return solverOption("TjOperatorStrings"); }
-	bool solverOption(const char* token) const
-	{
-		LppHost::String options("none");
-		if (io_.has("SolverOptions=")) io_.readline(options, "SolverOptions=");
-		return options.find(token) != LppHost::String::npos;
 	}
 
 	ComplexOrRealType bracket(lpp_engine* e, int convention, const std::vector<int32_t>& ops, const std::vector<int32_t>& sites, const std::vector<int32_t>& spins,
 	                          const std::vector<int32_t>& flags, const PairType& braAndKet) const
 	{
-		const PairType parts = obsParts();
 		const int64_t off[2] = { 0, (int64_t)ops.size() };
 		double out[2] = { 0, 0 };
-		lppCheck((heisModel() ? lpp_engine_many_point_heis : tjModel() ? lpp_engine_many_point_tj : lpp_engine_many_point)(e, convention, 1, off, ops.data(), sites.data(), spins.data(), flags.data(),
-		                                                                            (int32_t)model_.geometry().numberOfSites(), (int32_t)parts.first, (int32_t)parts.second,
-		                                                                            (int32_t)braAndKet.first, (int32_t)braAndKet.second, out));
+		lppCheck(fam_.many_point(e, convention, 1, off, ops.data(), sites.data(), spins.data(), flags.data(), (int32_t)model_.geometry().numberOfSites(),
+		                         (int32_t)fam_.parts.first, (int32_t)fam_.parts.second, (int32_t)braAndKet.first, (int32_t)braAndKet.second, out));
 		if constexpr (std::is_same<ComplexOrRealType, double>::value) return out[0];
 		else return ComplexOrRealType(out[0], out[1]);
 	}
@@ -818,42 +846,47 @@ private:
 		return 0;
 	}
 
-	const HubbardOneOrbital<ComplexOrRealType>* hubbard() const { return dynamic_cast<const HubbardOneOrbital<ComplexOrRealType>*>(&model_); }
-	const TjMultiOrb<ComplexOrRealType>* tjModel() const { return dynamic_cast<const TjMultiOrb<ComplexOrRealType>*>(&model_); } // (Orbitals=1: the only one the shim builds)
-	// S = 1/2 only: the reference throws for higher spins (BasisHeisenberg.h:130, Heisenberg.h:223).  An input with AnisotropyD is not admitted here yet:
-	// its sector engines would come from the any-spin assembler, and no driver test covers that (the Python layer does both, and is tested)
-	const Heisenberg<ComplexOrRealType>* heisModel() const
+	// the sector an operator of a spectral function decomposes in: the family's new parts or, for one that stays, the resident states' own; false: none
+	bool newSector(const LabeledOperatorType& lOperator, int32_t spin, int n, int32_t& nup2, int32_t& ndown2) const
 	{
-		const Heisenberg<ComplexOrRealType>* hs = dynamic_cast<const Heisenberg<ComplexOrRealType>*>(&model_);
-		return (hs && hs->twiceTheSpin() == 1 && hs->anisotropy.empty() && !heisSpinModel()) ? hs : nullptr;
+		int32_t has = 1;
+		nup2 = (int32_t)fam_.ownSector.first;
+		ndown2 = (int32_t)fam_.ownSector.second;
+		if (lOperator.needsNewBasis()) lppCheck(fam_.new_parts(lOperator.id(), spin, n, (int32_t)fam_.parts.first, (int32_t)fam_.parts.second, &has, &nup2, &ndown2));
+		return has != 0;
 	}
-	// The input's opt-in for the observables of the spin-S digit basis, the SolverOptions token HeisenbergSpinObservables: a Model=Heisenberg input of
-	// any spin the assembler admits, AnisotropyD included, goes through the _heis_spin entry points (the project's own definition -- the reference throws
-	// for spins above 1/2 --, sz is the true S^z; the reference's InputCheck is permissive, so such an input stays valid for it).  Without the token
-	// every input behaves as before.
-	const Heisenberg<ComplexOrRealType>* heisSpinModel() const
+
+	// One record of spectralFunction / spectralFunctionWeighted: decompose(sector engine, &weight, &steps, a, b) builds the modified state and decomposes it
+	// on the engine of sector (nup2, ndown2); the record is the argument list of cf.set with s = -1 for the odd types (calcSpectral, Engine.h:481-489)
+	// and s2 = scale, times s for a bosonic operator.
+	template <typename ContinuedFractionCollectionType, typename DecomposeType>
+	void decomposeAndPush(ContinuedFractionCollectionType& cfCollection, VectorStringType& vstr, const char* who, const LabeledOperatorType& lOperator, SizeType type,
+	                      RealType scale, const LppHost::String& label, int nup2, int ndown2, const ParametersForSolverType& params, DecomposeType&& decompose) const
 	{
-		const Heisenberg<ComplexOrRealType>* hs = dynamic_cast<const Heisenberg<ComplexOrRealType>*>(&model_);
-		return (hs && solverOption("HeisenbergSpinObservables")) ? hs : nullptr;
+		lpp_engine* sector = sectorEngine(nup2, ndown2, params);
+		TridiagonalMatrixType ab;
+		ab.resize(params.steps + 2);
+		double weight = 0;
+		int32_t nsteps = 0;
+		lppCheck(decompose(sector, &weight, &nsteps, &ab.a(0), &ab.b(0)));
+		ab.a_.resize(nsteps);
+		ab.b_.resize(nsteps);
+		if (std::sqrt(weight) < 1e-10) std::cerr << who << ": modifVector==0, type=" << type << "\n";
+		const int s = (type & 1) ? -1 : 1;
+		const RealType s2 = scale * (lOperator.isFermionic() ? 1 : s);
+		typename ContinuedFractionCollectionType::ContinuedFractionType cf;
+		cf.set(ab, energies_[0], weight * s2, -s);
+		vstr.push_back(label);
+		cfCollection.push(cf);
 	}
-	// the sector as the observable entry points take it: (nup, ndown), for the Heisenberg model (szPlusConst, 0) -- its parts() are (twiceS, szPlusConst),
-	// which is what the _heis_spin entry points take
-	PairType obsParts() const
-	{
-		const typename ModelType::BasisBaseType::PairIntType parts = model_.basis().parts();
-		return heisModel() ? PairType(parts.second, 0) : PairType(parts.first, parts.second);
-	}
-	// the key of the resident states' own sector among the sector engines: obsParts(), in the spin-S digit basis (szPlusConst, 0) as its new sectors
-	PairType ownSector() const { return heisSpinModel() ? PairType(model_.basis().parts().second, 0) : obsParts(); }
 
 	lpp_engine* sectorEngine(int nup, int ndown, const ParametersForSolverType& params) const
 	{
 		std::unique_ptr<EngineHandle>& slot = sectorEngines_[PairType(nup, ndown)];
 		if (!slot) {
-			const HubbardOneOrbital<ComplexOrRealType>* hub = hubbard();
-			const TjMultiOrb<ComplexOrRealType>* tj = tjModel();
-			const Heisenberg<ComplexOrRealType>* spinModel = heisSpinModel();
-			const Heisenberg<ComplexOrRealType>* hs = spinModel ? spinModel : heisModel();
+			const HubbardOneOrbital<ComplexOrRealType>* hub = fam_.hubbard;
+			const TjMultiOrb<ComplexOrRealType>* tj = fam_.tj;
+			const Heisenberg<ComplexOrRealType>* hs = fam_.heis;
 			const SizeType n = model_.geometry().numberOfSites();
 			std::vector<double> hr(n * n), hi(n * n);
 			for (SizeType k = 0; k < n * n && !hs; k++) {
@@ -865,7 +898,7 @@ private:
 			cfg.device = device_;
 			cfg.dtype = LppDtype<ComplexOrRealType>::value;
 			std::unique_ptr<EngineHandle> fresh(new EngineHandle(cfg));
-			if (spinModel) { // the recorded model's twiceS and anisotropy on szPlusConst +- 1 (or the state's own sector for sz)
+			if (fam_.spinS) { // the recorded model's twiceS and anisotropy on szPlusConst +- 1 (or the state's own sector for sz)
 				lppCheck(lpp_engine_assemble_heisenberg_spin(fresh->get(), (int32_t)n, (int32_t)hs->twiceTheSpin(), nup, hs->jpm().data(), hs->jzz().data(),
 				                                             hs->magneticField.empty() ? nullptr : hs->magneticField.data(), (int32_t)hs->magneticField.size(),
 				                                             hs->anisotropy.empty() ? nullptr : hs->anisotropy.data(), (int32_t)hs->anisotropy.size()));
@@ -937,9 +970,8 @@ private:
 		SpecialSymmetryType& rs = *rs_;
 		InternalProductType& hamiltonian = *hamiltonian_;
 		LanczosSolverType lanczosSolver(hamiltonian, params); // pushes params into the engine
-		const bool keep = (hubbard() || tjModel() || heisModel() || heisSpinModel()) && rs.sectors() == 1;
-		// (a t-J matrix may be held in the hole-major form, which only the _tj call lets keep its states)
-		if (keep) lppCheck((tjModel() ? lpp_engine_keep_states_tj : lpp_engine_keep_states)(hamiltonian.engine(), (int32_t)nstates));
+		const bool keep = fam_.two_point && rs.sectors() == 1;
+		if (keep) lppCheck(fam_.keep_states(hamiltonian.engine(), (int32_t)nstates));
 		energies_.assign(nstates, 0);
 		vectors_.assign(nstates, VectorType());
 		bool have = false;
@@ -969,6 +1001,7 @@ private:
 	const ModelType& model_;
 	LppHost::InputReadable& io_;
 	int device_;
+	const Family fam_;
 	VectorRealType energies_;
 	VectorVectorType vectors_;
 	SizeType steps_ = 0, sector_ = 0;

@@ -352,6 +352,16 @@ def test_driver_without_the_token_still_refuses():
     assert res.returncode == 2 and "twoPoint" in res.stderr and "MatrixDiagonal" not in res.stdout
 
 
+@pytest.mark.parametrize("args, sentence", [
+    (["-M", "sz?0?0;sz?1?0"], "LPP_ERR_INVALID: manyPoint: operator strings are not built for the spin-S digit basis (HeisenbergSpinObservables)"),
+    (["-r", "4"], "reducedDensityMatrix: needs a Model of the HubbardOneOrbital family solved by the GPU Lanczos (no symmetry sectors, no dense fallback)")])
+def test_driver_with_the_token_refuses_strings_and_the_density_matrix(args, sentence):
+    """the two refusals of the shim that name no other model's input: operator strings and -r on the input that opts into the digit basis"""
+    assert os.path.exists(DRIVER), "run __graft_entry__.build()"
+    res = subprocess.run([DRIVER, "-f", os.path.join(GOLD, NAME)] + args, capture_output=True, text=True, timeout=120)
+    assert res.returncode == 2 and sentence in res.stderr, res.stderr
+
+
 def _parse_comb(text):
     """the record layout of INTEGRATION.md"""
     head = dict(re.findall(r"^(Site0|Site1|TSPCenter)=(\d+)$", text, re.M))
